@@ -12,7 +12,13 @@ the line with their own `value`, the fastest verified one repeated as `throughpu
 region's (one frame per pass), so that `ms_per_step` >= the dominant kernel's time per step (`roofline.kernel_ms`).  Rendering several frames per pass (flx_render_batch, a throughput mode with a latency of
 F frames) is reported beside it as `batched`, with a different camera for every frame of a batch.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dragon|dragon_100k|dragon_4k|cornell_obj|cornell|theater]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dragon|dragon_100k|dragon_4k|cornell_obj|cornell|theater] [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps rank 0 writes the frame the last of them computed — the [H, W, 4] float32 frame a caller of the
+timed path receives — as DIR/frame.npy with every value finite, and the frame's NaN / +inf / -inf (which are part of what it computes) as
+DIR/frame_nonfinite.npy: their flat indices and kinds.  A frame of more than 64 MB (4K) is written as a fixed, seeded sample of its pixels
+(DIR/frame_sample.npy, frame_sample_nonfinite.npy, frame_sample_pixels.npy).  The inputs (scene, camera, seed) are fixed by the arguments,
+so two builds can be compared output for output.
 
 N > 1: one rank per GPU.  Under torch.distributed.run the ranks are there already (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from
 the environment); started plainly — `python bench.py --gpus 8` — this process launches the N ranks itself as child processes
@@ -75,6 +81,9 @@ WORKLOADS = {
     "theater": ("theater", "configs[4]: examples/theater.js 1080p, 16 spp, 6 bounces"),
     "dragon_4k": ("dragon", "configs[3]: dragon.obj (dragon_lp.obj) 3840x2160, 8 spp, 4 bounces", 3840, 2160),
 }
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SAMPLE_PIXELS = 1 << 21  # pixels of the seeded sample written in place of a larger frame (16 + 8 bytes each: 48 MB)
 
 PMC_WARMUP_FRAMES = 2       # frames tools/pmc_pass.py renders before the ones that count (its --warmup)
 KT_FRAMES = 12              # frames of the kernel-trace pass
@@ -234,6 +243,64 @@ def collect_pmc(args, tile=None):
     if class_error:
         acc["_meta"]["class_passes"] = class_error
     return acc
+
+
+DUMP_NAMES = ("frame", "frame_nonfinite", "frame_sample", "frame_sample_nonfinite", "frame_sample_pixels")
+NONFINITE_KINDS = {1.0: float("nan"), 2.0: float("inf"), 3.0: float("-inf")}       # kind code -> value (column 1 of frame_*nonfinite.npy)
+
+
+def split_nonfinite(a):
+    """float32 array -> (a copy with 0 where `a` is NaN / +inf / -inf, [k, 2] float64: flat index into `a`, kind 1 NaN / 2 +inf / 3 -inf).
+    The frame's NaNs are part of what it computes (the reference's NaN semantics: SURVEY.md R2; the CPU oracle has the same ones)."""
+    import numpy as np
+    flat = a.reshape(-1)
+    bad = np.flatnonzero(~np.isfinite(flat))
+    v = flat[bad]
+    kind = np.where(np.isnan(v), 1.0, np.where(v > 0, 2.0, 3.0))
+    values = a.copy()
+    values.reshape(-1)[bad] = 0
+    return values, np.stack([bad.astype(np.float64), kind], axis=1).reshape(-1, 2)
+
+
+def join_nonfinite(values, nonfinite):
+    """split_nonfinite's inverse: the array with its NaN / +inf / -inf back in place"""
+    a = values.copy()
+    for kind, v in NONFINITE_KINDS.items():
+        a.reshape(-1)[nonfinite[nonfinite[:, 1] == kind, 0].astype(int)] = v
+    return a
+
+
+def dump_outputs(out_dir, frame, limit=DUMP_LIMIT_BYTES, sample_pixels=DUMP_SAMPLE_PIXELS):
+    """--dump-outputs: `frame` ([H, W, 4] float32, the timed path's last frame) -> out_dir/frame.npy, every value finite (0 where the frame
+    holds NaN / +inf / -inf), and out_dir/frame_nonfinite.npy ([k, 2] float64: flat index, kind 1 NaN / 2 +inf / 3 -inf; k may be 0) —
+    join_nonfinite() of the two is the frame.  A frame that does not fit `limit` bytes so is written as the seeded sample
+    out_dir/frame_sample.npy ([n, 4] float32) + frame_sample_nonfinite.npy (indices into it) + frame_sample_pixels.npy ([n] float64, the
+    pixels' flat indices row * W + column, ascending): the same pixels for every frame of the size (fewer, halved, only if the sample's
+    non-finite values would not fit).  Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    budget = limit - 3 * 128                                                # (the .npy headers)
+    values, nonfinite = split_nonfinite(frame)
+    if values.nbytes + nonfinite.nbytes <= budget:
+        arrays = {"frame": values, "frame_nonfinite": nonfinite}
+    else:
+        h, w = frame.shape[:2]
+        n = min(sample_pixels, h * w, budget // 24)
+        while True:
+            idx = np.sort(np.random.default_rng(0).choice(h * w, n, replace=False))
+            values, nonfinite = split_nonfinite(frame.reshape(h * w, -1)[idx])
+            if 24 * n + nonfinite.nbytes <= budget or n == 1:
+                break
+            n //= 2
+        arrays = {"frame_sample": values, "frame_sample_nonfinite": nonfinite, "frame_sample_pixels": idx.astype(np.float64)}
+    for name in DUMP_NAMES:                                                 # no file of an earlier run's other form stays beside these
+        path = os.path.join(out_dir, name + ".npy")
+        if name not in arrays and os.path.exists(path):
+            os.unlink(path)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def launch_ranks(args):
@@ -587,10 +654,15 @@ def main():
     ap.add_argument("--rank-timeout", type=int, default=900, help="N > 1 launched by bench.py itself: seconds after which ranks still running are stopped and the run fails")
     ap.add_argument("--headline", default="one_frame_per_pass", choices=["auto", "one_frame_per_pass"],
                     help="kept for old command lines: `value` / `ms_per_step` are the timed region (one frame per pass) either way; the frame loops are `pipelined` / `shared` / `throughput_best`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last one computed as DIR/frame.npy (float32 [H, W, 4], finite; its NaN / inf in "
+                         "DIR/frame_nonfinite.npy; above 64 MB a seeded sample of its pixels)")
     ap.add_argument("--secondary-timeout", type=int, default=300, help="seconds the measurements after the timed region (`pipelined`, `shared`, `batched`) may take in all before the run ends with the line as it stands; 0 = no limit")
     ap.add_argument("--no-shared", action="store_true", help="N > 1: skip the frame loop without a collective (flx_share_*: the `shared` entry of the line)")
     ap.add_argument("--gather", choices=["root", "all"], default="root", help="N > 1: root = only rank 0, which presents the frame, receives the strips (ncclSend / ncclRecv; the reference presents from its one context); all = ncclAllGather, every rank ends up with the frame")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args)                   # never returns
@@ -712,6 +784,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frames_out[0].cpu().numpy())      # outside the timed region; frames_out[0] is the last timed step's frame
 
     verified = None
     if verify and multi and rank == 0:

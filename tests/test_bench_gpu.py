@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +43,26 @@ def test_bench_line_single_gpu():
     # K = 6 < 8: the loops time 20 frames, not K — no candidate for the headline
     assert d["headline"]["mode"] == "one_frame_per_pass" and d["one_frame_per_pass"]["ms_per_step"] == d["ms_per_step"] and d["pipelined"]["frames"] == 20
     assert d["counters"]["primary_hits"] > 0
+
+
+def test_bench_dumps_the_frame_of_its_last_timed_step(scenes, tmp_path):
+    """--dump-outputs: the frame the timed steps computed (the last of exactly --steps), as one context renders it from the same arguments, bit for bit"""
+    d = _last_json(subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "0", "--no-pmc", "--dump-outputs", str(tmp_path)] + SMALL,
+                                           timeout=900, stderr=subprocess.DEVNULL))
+    assert d["steps"] == 6 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(str(tmp_path))) == ["frame.npy", "frame_nonfinite.npy"]
+    got, nonfinite = np.load(str(tmp_path / "frame.npy")), np.load(str(tmp_path / "frame_nonfinite.npy"))
+    assert got.dtype == np.float32 and got.shape == (270, 480, 4) and np.isfinite(got).all() and np.isfinite(nonfinite).all()
+    from flexlight_hip import capi
+    sc = scenes("dragon")
+    with capi.Context(0) as ctx:                 # a context of its own: no setting an earlier test left on the shared one
+        ctx.update_scene(sc)
+        want, _, _ = ctx.render(sc.frame_params(width=480, height=270))
+    fin = np.isfinite(want)
+    assert np.array_equal(got.view(np.int32)[fin], want.view(np.int32)[fin])             # bit for bit where the frame is finite
+    sys.path.insert(0, ROOT)
+    import bench
+    assert np.array_equal(bench.join_nonfinite(got, nonfinite), want, equal_nan=True)      # and its NaN / inf, listed, in the same places
 
 
 def test_bench_value_is_one_frame_per_pass_and_the_loops_stand_beside_it():

@@ -1,25 +1,49 @@
 """The JavaScript host layer (web-ray-tracer_amd/js): the arrays it flattens for the GPU must equal what
 the reference's own modules/scene.js emits (tests/golden/ref_<scene>.json holds their sha256, produced
 by tools/ref_goldens.js from the reference itself), and the N-API addon must load and export the
-renderer's entry points.  CPU only; scenes that need OBJ / JPEG assets are skipped where the reference
-checkout (which holds the assets) is not mounted."""
+renderer's entry points.  CPU only.  The OBJ / MTL assets the scenes import are the reference's own files, stored gzipped
+under tests/golden/assets and unpacked into a temporary asset root for the module; the theater's texture is stored as the
+pixels of it that its atlas reads (tests/analysis/make_texture_fixture.py)."""
+import gzip
+import hashlib
 import json
 import os
 import shutil
 import subprocess
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = os.environ.get("FLX_REFERENCE", "/root/reference")
+ASSETS = os.path.join(ROOT, "tests", "golden", "assets")
+# fixture -> the asset it stands in for: lossless, full size, black where the 512 x 512 atlas cell reads nothing
+# (tools/host_arrays.js decodes images with PIL, which goes by the file's content, not its name)
+STANDS_IN = {"holz_sampled.png": "holz.jpg"}
 NODE = shutil.which("node")
+sys.path.insert(0, os.path.join(ROOT, "web-ray-tracer_amd"))
+from flexlight_hip.scene_io import Scene  # noqa: E402
 
 pytestmark = pytest.mark.skipif(NODE is None, reason="node is not installed")
-needs_assets = pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "objects")), reason="OBJ/JPEG assets not mounted")
 
 
-def host_arrays(scene, native=False):
-    cmd = [NODE, os.path.join(ROOT, "tools", "host_arrays.js"), scene, "--assets", REFERENCE] + (["--native"] if native else [])
+@pytest.fixture(scope="module")
+def assets(tmp_path_factory):
+    """tests/golden/assets unpacked: <root>/objects/*.obj|*.mtl, <root>/textures/holz.jpg, as the scenes name them"""
+    root = tmp_path_factory.mktemp("assets")
+    for sub in sorted(os.listdir(ASSETS)):
+        os.makedirs(str(root / sub))
+        for name in sorted(os.listdir(os.path.join(ASSETS, sub))):
+            src = os.path.join(ASSETS, sub, name)
+            if name.endswith(".gz"):
+                with gzip.open(src, "rb") as fin, open(str(root / sub / name[:-3]), "wb") as fout:
+                    shutil.copyfileobj(fin, fout)
+            else:
+                shutil.copyfile(src, str(root / sub / STANDS_IN.get(name, name)))
+    return str(root)
+
+
+def host_arrays(scene, native=False, assets=None):
+    cmd = [NODE, os.path.join(ROOT, "tools", "host_arrays.js"), scene] + (["--assets", assets] if assets else []) + (["--native"] if native else [])
     out = subprocess.check_output(cmd, timeout=300)
     return json.loads(out.decode().strip().splitlines()[-1])
 
@@ -29,43 +53,42 @@ def golden(scene):
         return json.load(fh)
 
 
-def check(scene, native=False):
-    got, want = host_arrays(scene, native), golden(scene)
+def check(scene, native=False, assets=None):
+    got, want = host_arrays(scene, native, assets), golden(scene)
     for key in ("textureLength", "bufferLength", "entriesPadded", "transforms"):
         assert got[key] == want[key], key
     for key, digest in want["sha256"].items():
         assert got["sha256"][key] == digest, "%s: array '%s' differs from the reference's" % (scene, key)
+    stored = Scene.golden(scene)              # the texture atlases, against the scene file the reference's scene.js emitted
+    for key in ("atlasAlbedo", "atlasPbr", "atlasTpo"):
+        assert got["sha256"][key] == hashlib.sha256(stored.arrays[key].tobytes()).hexdigest(), "%s: atlas '%s' differs from the reference's" % (scene, key)
 
 
 def test_cornell_arrays_equal_reference():
     check("cornell")                       # built purely through the API: no asset files needed
 
 
-@needs_assets
 @pytest.mark.parametrize("scene", ["cornell_obj", "dragon", "theater"])
-def test_imported_scene_arrays_equal_reference(scene):
-    check(scene)                           # OBJ/MTL import + BVH builder + transforms
+def test_imported_scene_arrays_equal_reference(scene, assets):
+    check(scene, assets=assets)            # OBJ/MTL import + BVH builder + transforms
 
 
-@needs_assets
 @pytest.mark.parametrize("scene", ["cornell_obj", "dragon"])
-def test_native_import_arrays_equal_reference(scene):
+def test_native_import_arrays_equal_reference(scene, assets):
     """OBJ / MTL parsing, BVH build and flattening in native code (flx_mesh_* through the N-API addon),
     spliced into the JavaScript scene, and N3: the transform arrays from flx_transforms_pack — the whole scene still hashes to
     what the reference's own scene.js emits."""
-    check(scene, native=True)
+    check(scene, native=True, assets=assets)
 
 
-@needs_assets
 @pytest.mark.parametrize("native", [False, True], ids=["js_host", "native_import"])
-def test_synthetic_100k_dragon_arrays_equal_reference(native):
+def test_synthetic_100k_dragon_arrays_equal_reference(native, assets):
     """The >= 100k-triangle stand-in for the absent objects/dragon.obj (tools/make_dragon_100k.py: dragon_lp.obj split 1 -> 4,
     174 276 triangles): the scene built from it by the JavaScript host layer, and by the native importer, hashes to the arrays
     the reference's own scene.js emits for the same OBJ (tests/golden/ref_dragon_100k.json) — 289 189 entries."""
-    obj = os.path.join(ROOT, "build", "assets", "objects", "dragon_100k.obj")
-    if not os.path.exists(obj):
-        subprocess.check_call(["python3", os.path.join(ROOT, "tools", "make_dragon_100k.py"), REFERENCE])
-    check("dragon_100k", native)
+    if not os.path.exists(os.path.join(assets, "objects", "dragon_100k.obj")):
+        subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_dragon_100k.py"), assets, assets])
+    check("dragon_100k", native, assets)
     assert golden("dragon_100k")["triangles"] >= 100000
 
 
