@@ -182,8 +182,8 @@ flx_status flx_set_frame_lanes(flx_context *ctx, int lanes);
  * (modules/pathtracerWGL2.js:254-303); a frame's own launches, though, end in a drain — the last paths of the frame keep a few waves busy while the
  * other CUs idle — and for a short frame (a rank's eighth of a 1080p frame: 0.8 ms of work, 1.65 ms from launch to end) the drain is half of the time.
  *   0  every frame has its own launches, on the lanes of flx_set_frame_lanes;
- *   1  (only in `make EXPERIMENTS=1`'s library; refused by the shipped one) a chain of launches (csrc/flx_chain.hip): the frame kernel of frame k works ahead on
- *      frame k + 1 and hands what it holds of it to the next launch.  Measured: the relaunch per frame costs what the overlap gains;
+ *   1  refused (FLX_ERR_INVALID): the chain of launches it once selected — the frame kernel of frame k working ahead on frame k + 1 — was removed, the
+ *      relaunch per frame cost what the overlap gained;
  *   2  (default) the frame server (csrc/flx_server.hip) for frames of fewer than 64 8 x 8 screen tiles per CU — a rank's share of a frame — and mode 0 for the
  *      others: ONE persistent launch renders the loop's frames as flx_frame_begin posts them (the view goes through pinned memory; nothing is launched per
  *      frame), every workgroup works on the oldest frame first and fills its idle lanes with the next ones, resolves the screen tiles it made and the last

@@ -19,7 +19,7 @@ extern "C" {
 flx_status flx_set_counters_enabled(flx_context *ctx, int enabled);
 flx_status flx_get_counters(flx_context *ctx, flx_counters *out);
 
-/* The last frame begun in the loop: 0 its own launches, 1 it began a chain of launches, 2 it continued one, 3 it went to the frame server. */
+/* The last frame begun in the loop: 0 its own launches, 3 it went to the frame server. */
 flx_status flx_last_chained(flx_context *ctx, int *chained);
 
 /* A scene that MOVES in the frame server.  The reference refills its transform UBO and its light texture before every frame (modules/pathtracerWGL2.js:258-262,
@@ -48,10 +48,6 @@ flx_status flx_debug_set_angle_table(flx_context *ctx, int on);
  * sample, the cross-sample globals of the shader (fragment:83-89) replayed in the shader's order afterwards — for frames of 2, 4 or 8 samples and at most 4 bounces; 0: the
  * sample-sequential k_trace_pixels always.  Frames, G-buffers and work counters are identical; for A/B runs (profiles/r05_sample_parallel.txt). */
 flx_status flx_debug_set_sample_parallel(flx_context *ctx, int on);
-/* Walk jobs per lane of the frame kernel's walk waves: 1 = k_wf_frame (1 024-thread workgroups, a path's walks per lane), 2 = k_wf_frame2 (512-thread workgroups, two
- * independent jobs per lane, a box phase and a triangle phase per trip; only where the front of the frame is inside the launch), 0 = the library's default.  Frames and
- * work counters are identical; for A/B runs (profiles/r05_two_walks.txt). */
-flx_status flx_debug_set_walk_jobs(flx_context *ctx, int jobs);
 /* the order in which the frame kernel draws a frame's 8 x 8 screen tiles: order[q] = the tile of the q-th draw (a permutation of the frame's n tiles; n = 0: tile q); frames do not depend on it */
 flx_status flx_debug_set_tile_order(flx_context *ctx, const uint32_t *order, uint32_t n);
 /* the adaptive tile order — the draw order made from what every tile cost in the last frame of the same shape (the lightest tiles last) — on (1, the default) or off (0: screen order) */
@@ -68,18 +64,6 @@ flx_status flx_debug_set_server_groups(flx_context *ctx, uint32_t groups);
 flx_status flx_get_server_stats(flx_context *ctx, uint64_t *out /* [16] */);
 /* the control words of up to four workgroups of the frame server that gave up (72 words each: workgroup, wave, its 64 LDS control words, the relayed posts, the slots' tile cursors) */
 flx_status flx_get_server_dump(flx_context *ctx, uint64_t *out /* [4 * 72] */);
-/* ---- only in `make EXPERIMENTS=1`'s libflexlight_hip_experiments.so (flx_has_experiments): the chained launches of flx_set_frame_chain(ctx, 1), csrc/flx_chain.hip ---- */
-#ifdef FLX_EXPERIMENTS
-/* Diagnostics of the chained launches of mode 1 (tools/chain_stats.py): 64 launches (by sequence number mod 64) x 64 words — when the launch started and ended,
- * when the next frame's view was seen, when its own frame was complete, tiles made for either frame, paths handed to the next kernel, walks abandoned. */
-flx_status flx_set_chain_stats(flx_context *ctx, int on);
-flx_status flx_get_chain_stats(flx_context *ctx, uint64_t *out /* [64 * 64] */);
-/* Experiments with the order in which a chained frame's 8 x 8 screen tiles are drawn (tools/chain_order.py): an explicit permutation of the frame's tiles
- * (n = 0: the row-major default), and per-tile counts of the shadings its paths took after bounce 0 (n tiles per slot; 2 x n words out). */
-flx_status flx_set_chain_order(flx_context *ctx, const uint32_t *order, uint32_t n);
-flx_status flx_set_chain_cost(flx_context *ctx, uint32_t n);
-flx_status flx_get_chain_cost(flx_context *ctx, uint32_t *out);
-#endif /* FLX_EXPERIMENTS */
 
 /* ranks of the context's communicator as RCCL reports them (ncclCommCount); 0: the context belongs to none */
 int flx_comm_count(const flx_context *ctx);
@@ -112,21 +96,6 @@ flx_status flx_set_frame_front(flx_context *ctx, int mode);
 /* What the wavefront pipeline ran for the last frame: 1 rounds, 2 the frame kernel, 3 the frame kernel with the front of the frame inside it;
  * 0 when another pipeline rendered it (flx_last_pipeline). */
 flx_status flx_last_organisation(flx_context *ctx, int *organisation);
-/* Wavefront pipeline: how the bounce walks are scheduled.  Every mode walks every ray through the same entries with the
- * same arithmetic (frames and work counters are identical); they differ in speed and exist for A/B measurements
- * (profiles/r01_ab_tail_schedulers.txt).
- *   scheduler      FLX_WALK_LANES (default): one walk per lane, lanes refilled as walks end (k_wf_walk_pre)
- *                  FLX_WALK_QUEUES: walk states in LDS, waves take 64 walks that need the same test (flx_walkq.hip)
- *                  FLX_WALK_LANES_FINISHER: as FLX_WALK_LANES, suspended walks are finished a wave per walk (flx_walkcoop.hip)
- *   suspend_walks  FLX_WALK_LANES*: a walk workgroup that has found the queue dry and is down to this many walks hands
- *                  them over (to the next round's walk kernel, or to the finisher) instead of finishing them; 0 = never */
-#define FLX_WALK_LANES 0
-#define FLX_WALK_QUEUES 1
-#define FLX_WALK_LANES_FINISHER 2
-flx_status flx_set_walk_scheduler(flx_context *ctx, int scheduler, uint32_t suspend_walks);
-/* 1 when the library carries the experimental schedulers above (`make EXPERIMENTS=1`: libflexlight_hip_experiments.so); the
- * shipped library returns 0 and its flx_set_walk_scheduler accepts (FLX_WALK_LANES, 0) only. */
-int flx_has_experiments(void);
 
 /* ---- diagnostics --------------------------------------------------------------------------------- */
 /* Evaluate one of include/flx_math.h's routines on the GPU for n inputs (b may be NULL for unary

@@ -7,26 +7,23 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def declared_functions(headers=("flexlight_hip.h", "flexlight_hip_debug.h"), experiments=False):
-    """every function the boundary (flexlight_hip.h) and the instrumentation header (flexlight_hip_debug.h) declare; what the latter keeps under
-    #ifdef FLX_EXPERIMENTS exists in `make EXPERIMENTS=1`'s library only"""
+def declared_functions(headers=("flexlight_hip.h", "flexlight_hip_debug.h")):
+    """every function the boundary (flexlight_hip.h) and the instrumentation header (flexlight_hip_debug.h) declare"""
     names = set()
     for h in headers:
         text = open(os.path.join(ROOT, "include", h)).read()
         text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        if not experiments:
-            text = re.sub(r"#ifdef FLX_EXPERIMENTS.*?#endif", "", text, flags=re.S)
         names.update(re.findall(r"\b(flx_[a-z0-9_]+)\s*\(", text))
     return sorted(names)
 
 
-def test_header_symbols_are_exported():
+def test_every_declared_function_is_exported():
     from flexlight_hip import capi
-    names = declared_functions(experiments=capi.has_experiments())
+    names = declared_functions()
     assert len(names) >= 20
     for name in names:
         assert hasattr(capi.LIB, name), "libflexlight_hip.so does not export %s" % name
-    every = declared_functions(experiments=True)
+    every = declared_functions()
     assert sorted(capi.EXPORTS) == [n for n in every if n in capi.EXPORTS]
     missing = [n for n in every if n not in capi.EXPORTS]
     assert not missing, "capi.EXPORTS lacks %s" % missing
@@ -106,13 +103,10 @@ def test_batch_limit_matches_the_header():
     assert int(re.search(r"#define FLX_MAX_BATCH (\d+)", dev).group(1)) == capi.MAX_BATCH_FRAMES
 
 
-def test_the_drivers_build_check_accepts_the_shipped_library():
-    """__graft_entry__.build() ends with this check: every function the bindings list is exported, except the chain of launches' five, which are in the experiments library only
-    (a check that asked for those too would fail every round's build step)"""
+def test_the_drivers_build_check_accepts_every_binding():
+    """__graft_entry__.build() ends with this check: every function the bindings list is exported"""
     import sys
     sys.path.insert(0, ROOT)
     import __graft_entry__ as entry
     from flexlight_hip import capi
     entry.check_exports()
-    if not capi.has_experiments():
-        assert all(not hasattr(capi.LIB, n) for n in capi.EXPERIMENTS_ONLY)

@@ -3,6 +3,8 @@ nothing throws or aborts, and the context stays usable afterwards."""
 import numpy as np
 import pytest
 
+from parity_util import bit_mismatches
+
 pytestmark = pytest.mark.gpu
 
 
@@ -212,3 +214,30 @@ def test_a_scene_change_between_frames_in_flight(hip, oracle, scenes):
         assert np.array_equal(got, want[prev], equal_nan=True), "frame before change %d" % k
     assert np.array_equal(hip.frame_end()[0], want[order[-1]], equal_nan=True)
     assert hip.frames_in_flight() == 0
+
+
+def test_a_tripped_watchdog_reaches_the_status_code(hip, scenes):
+    """fault injection: the frame kernel's shade waves drop every batch and its waves give up after a few hundred polls — the frame is incomplete and
+    flx_render says so (FLX_ERR_DEVICE with the bits), the word is cleared, and the context renders on"""
+    from flexlight_hip import capi
+    sc = scenes("dragon")
+    hip.update_scene(sc)
+    p = sc.frame_params(width=480, height=272, samples=2, max_reflections=4, use_filter=0)
+    want = hip.render(p)[0]
+    assert hip.last_organisation() in (2, 3)                  # the frame kernel ran
+    hip.inject_fault(400, 1)
+    try:
+        with pytest.raises(capi.FlexLightHipError) as e:
+            hip.render(p)
+        assert "device error" in str(e.value) and "watchdog" in str(e.value), str(e.value)
+        # through the frame loop too: flx_frame_end reports it
+        hip.set_frame_chain(0)
+        hip.frame_begin(p)
+        with pytest.raises(capi.FlexLightHipError) as e:
+            hip.frame_end()
+        assert "device error" in str(e.value)
+    finally:
+        hip.inject_fault(0, 0)
+        hip.set_frame_chain(2)
+    got = hip.render(p)[0]                                     # the word was cleared, the rings re-initialised
+    assert bit_mismatches(got, want) == 0

@@ -463,76 +463,6 @@ def test_frame_kernel_hands_paths_over_the_same_way_every_time(hip, oracle, scen
         hip.set_frame_front(1)
 
 
-@pytest.mark.experiments
-@pytest.mark.parametrize("scheduler,suspend", [(0, 128), (0, 16), (1, 0), (2, 16), (2, 128), (0, 0)])
-@pytest.mark.parametrize("name,w,h,spp,bounces", [("dragon", 480, 270, 2, 4), ("cornell_obj", 128, 96, 2, 5), ("theater", 96, 64, 1, 1)])
-def test_walk_schedulers_do_not_change_the_frame(hip, oracle, scenes, name, w, h, spp, bounces, scheduler, suspend):
-    """Queue scheduler, suspension to the next round, cooperative finisher: other orders of the same work — same bits, same
-    work counters (every ray visits the same entries)."""
-    sc = scenes(name)
-    hip.update_scene(sc)
-    p = sc.frame_params(width=w, height=h, samples=spp, max_reflections=bounces, use_filter=0)
-    key = (name, w, h, spp, bounces)
-    if key not in _ORACLE_CACHE:
-        _ORACLE_CACHE[key] = oracle.render(sc, p)[:2]
-    want, want_cnt = _ORACLE_CACHE[key]
-    try:
-        hip.set_walk_scheduler(scheduler, suspend)
-        for _ in range(2):
-            got, cnt, _ = hip.render(p, counters=True)
-            assert np.array_equal(got, want, equal_nan=True)
-            assert cnt == want_cnt
-        got, _, _ = hip.render(p)
-        assert np.array_equal(got, want, equal_nan=True)
-    finally:
-        hip.set_walk_scheduler(0, 0)
-
-
-@pytest.mark.experiments
-@pytest.mark.parametrize("w,h,spp,bounces", [(480, 270, 2, 4), (640, 368, 8, 4), (200, 120, 3, 6)])
-def test_two_walk_jobs_per_lane_do_not_change_the_frame(hip, oracle, scenes, w, h, spp, bounces):
-    """k_wf_frame2 (round 5, measured slower, `make EXPERIMENTS=1` only): the walk waves of the frame kernel hold two independent jobs per lane and step them in a box phase
-    and a triangle phase — another order of the same work: same bits, same work counters as the oracle"""
-    sc = scenes("dragon")
-    hip.update_scene(sc)
-    p = sc.frame_params(width=w, height=h, samples=spp, max_reflections=bounces, use_filter=0)
-    key = ("dragon", w, h, spp, bounces)
-    if key not in _ORACLE_CACHE:
-        _ORACLE_CACHE[key] = oracle.render(sc, p)[:2]
-    want, want_cnt = _ORACLE_CACHE[key]
-    try:
-        hip.set_pipeline(3)
-        hip.set_wavefront_organisation(2)
-        hip.set_frame_front(2)                                  # the front of the frame inside the launch whatever the frame's size: the kernel the two-job variant replaces
-        hip.set_walk_jobs(2)
-        for _ in range(2):
-            got, cnt, _ = hip.render(p, counters=True)
-            assert hip.last_organisation() == 3
-            assert np.array_equal(got, want, equal_nan=True)
-            assert cnt == want_cnt
-        got, _, _ = hip.render(p)
-        assert np.array_equal(got, want, equal_nan=True)
-    finally:
-        hip.set_walk_jobs(1)
-        hip.set_pipeline(0)
-        hip.set_wavefront_organisation(0)
-        hip.set_frame_front(1)
-
-
-def test_walk_scheduler_arguments(hip):
-    from flexlight_hip import capi
-    for args in ((3, 0), (-1, 0), (0, 513), (1, 8)):
-        with pytest.raises(capi.FlexLightHipError):
-            hip.set_walk_scheduler(*args)
-    hip.set_walk_scheduler(0, 0)
-    if not capi.has_experiments():                                # the shipped library carries the default scheduler only
-        for args in ((1, 0), (2, 16), (0, 16)):
-            with pytest.raises(capi.FlexLightHipError, match="EXPERIMENTS"):
-                hip.set_walk_scheduler(*args)
-        with pytest.raises(capi.FlexLightHipError, match="EXPERIMENTS"):
-            hip.set_walk_jobs(2)
-
-
 def test_errors_are_reported_not_thrown(hip, scenes):
     from flexlight_hip import capi
     sc = scenes("cornell")
@@ -541,6 +471,10 @@ def test_errors_are_reported_not_thrown(hip, scenes):
     p.width = 0
     with pytest.raises(capi.FlexLightHipError, match="width"):
         hip.render(p)
+    with pytest.raises(capi.FlexLightHipError, match="removed"):      # mode 1, the chain of launches, is gone; the numbers of the others stay
+        hip.set_frame_chain(1)
+    with pytest.raises(capi.FlexLightHipError, match="flx_set_frame_chain"):
+        hip.set_frame_chain(4)
     fresh = capi.Context(0)
     try:
         with pytest.raises(capi.FlexLightHipError, match="before"):

@@ -25,8 +25,6 @@ def main():
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--batch", type=int, default=1, help="frames per launch (flx_render_batch) instead of one")
-    ap.add_argument("--scheduler", type=int, default=0, help="flx_set_walk_scheduler: 0 lanes, 1 queues, 2 lanes + cooperative finisher")
-    ap.add_argument("--suspend", type=int, default=0, help="walks a walk workgroup may hand over (flx_set_walk_scheduler)")
     ap.add_argument("--tile-rows", type=int, default=0, help="with --tile-count N: render rank --tile-index's strips of the frame (what one of N ranks traces)")
     ap.add_argument("--tile-index", type=int, default=0)
     ap.add_argument("--tile-count", type=int, default=0)
@@ -41,7 +39,6 @@ def main():
     p = scene.frame_params(width=args.width, height=args.height, tile=tile)
     with capi.Context(0) as ctx:
         ctx.update_scene(scene)
-        ctx.set_walk_scheduler(args.scheduler, args.suspend)
         ctx.set_frame_lanes(1)                 # one frame after the other, as bench.py's timed steps
         for _ in range(args.warmup + args.frames):
             if args.batch > 1:

@@ -8,9 +8,6 @@ from flexlight_hip.scene_io import Scene
 sc = Scene.golden("dragon")
 ctx = capi.Context(0)
 ctx.update_scene(sc)
-if os.environ.get("FLX_SCHED"):                     # "scheduler,suspend_walks"
-    a, b = os.environ["FLX_SCHED"].split(",")
-    ctx.set_walk_scheduler(int(a), int(b))
 if os.environ.get("FLX_GROUPS"):
     ctx.set_wavefront_groups(int(os.environ["FLX_GROUPS"]))
 if os.environ.get("FLX_PIPELINE"):

@@ -23,9 +23,6 @@
 
 using namespace flx;
 
-#ifndef FLX_EXPERIMENTS
-#define FLX_EXPERIMENTS 0                   /* Makefile: EXPERIMENTS=1 */
-#endif
 #ifndef FLX_FRONT_FUSED_MAX_ITEMS
 #define FLX_FRONT_FUSED_MAX_ITEMS (128u << 20)
 #endif
@@ -69,9 +66,6 @@ extern "C" flx_status flx_context_create(int device, flx_context **out) {
   if (device < 0 || device >= n) { g_create_error = "flx_context_create: device index out of range"; return FLX_ERR_INVALID; }
   flx_context *ctx = new flx_context();
   ctx->device = device;
-#if FLX_EXPERIMENTS
-  if (const char *wj = getenv("FLX_WALK_JOBS")) { if (wj[0] == '1' || wj[0] == '2') ctx->walk_jobs = (uint32_t)(wj[0] - '0'); }      /* A/B runs of whole test suites and bench.py (flx_debug_set_walk_jobs) */
-#endif
   auto bail = [&](const char *what, hipError_t err) {
     g_create_error = std::string(what) + ": " + hipGetErrorString(err);
     delete ctx;
@@ -91,7 +85,7 @@ extern "C" flx_status flx_context_create(int device, flx_context **out) {
   if ((e = hipMalloc(&ctx->d_counters, FLX_COUNTER_SLOTS * sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
   if ((e = hipMemset(ctx->d_counters, 0, FLX_COUNTER_SLOTS * sizeof(unsigned long long))) != hipSuccess) return bail("hipMemset", e);
   if ((e = hipMalloc(&ctx->d_queue, sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
-  if ((e = hipMalloc(&ctx->d_wfcounts, WF_MAX_GROUPS * 4 * (WF_MAX_ROUNDS + 2) * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
+  if ((e = hipMalloc(&ctx->d_wfcounts, WF_MAX_GROUPS * 2 * (WF_MAX_BOUNCES + 2) * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
   for (int i = 0; i < 3; i++) {
     if ((e = hipStreamCreateWithFlags(&ctx->aux_stream[i], hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
     if ((e = hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
@@ -116,7 +110,7 @@ extern "C" void flx_context_destroy(flx_context *ctx) {
   void *bufs[] = { ctx->d_geometry, ctx->d_attributes, ctx->d_rotation, ctx->d_shift, ctx->d_ids, ctx->d_lights,
                    ctx->d_atlas[0], ctx->d_atlas[1], ctx->d_atlas[2], ctx->d_out, ctx->d_gb[0], ctx->d_gb[1], ctx->d_gb[2],
                    ctx->d_gb[3], ctx->d_gb[4], ctx->d_gb[5], ctx->d_counters, ctx->d_hits, ctx->d_samples, ctx->d_last, ctx->d_queue,
-                   ctx->d_send, ctx->d_send8, ctx->d_recv, ctx->d_frames, ctx->d_gplanes, ctx->d_angle_tan, ctx->d_rec, ctx->d_rec0, ctx->d_pix0, ctx->d_tail_pool, ctx->d_strag, ctx->d_live[0], ctx->d_live[1], ctx->d_wfcounts, ctx->d_walk, ctx->d_fwd, ctx->d_frame_rings, ctx->d_qbatch, ctx->d_tile_order, ctx->d_tile_cost, ctx->d_tile_time, ctx->d_auto_order,
+                   ctx->d_send, ctx->d_send8, ctx->d_recv, ctx->d_frames, ctx->d_gplanes, ctx->d_angle_tan, ctx->d_rec, ctx->d_rec0, ctx->d_pix0, ctx->d_tail_pool, ctx->d_live[0], ctx->d_live[1], ctx->d_wfcounts, ctx->d_walk, ctx->d_fwd, ctx->d_frame_rings, ctx->d_qbatch, ctx->d_tile_order, ctx->d_tile_cost, ctx->d_tile_time, ctx->d_auto_order,
                    ctx->d_planes[0], ctx->d_planes[1], ctx->d_planes[2], ctx->d_planes[3], ctx->d_planes[4], ctx->d_planes[5], ctx->d_planes[6],
                    ctx->d_planes[7], ctx->d_planes[8], ctx->d_planes[9], ctx->d_planes[10], ctx->d_planes[11], ctx->d_planes[12] };
   for (void *b : bufs) if (b) (void)hipFree(b);
@@ -136,11 +130,9 @@ extern "C" void flx_context_destroy(flx_context *ctx) {
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   for (hipEvent_t ev : ctx->stage_done) if (ev) (void)hipEventDestroy(ev);
   if (ctx->stage) (void)hipHostFree(ctx->stage);
-  if (ctx->h_chain_mail) (void)hipHostFree(ctx->h_chain_mail);
   if (ctx->h_sv_mail) (void)hipHostFree(ctx->h_sv_mail);
   for (void *b : { (void *)ctx->d_sv_slots, (void *)ctx->d_sv_relay, (void *)ctx->d_sv_rings, (void *)ctx->d_sv_stats, (void *)ctx->d_sv_out, (void *)ctx->d_sv_tiles, (void *)ctx->d_sv_versions }) if (b) (void)hipFree(b);
   if (ctx->sv_stream) (void)hipStreamDestroy(ctx->sv_stream);
-  for (void *b : { (void *)ctx->d_chain_slots, (void *)ctx->d_chain_relay, (void *)ctx->d_chain_lists, (void *)ctx->d_chain_rings, (void *)ctx->d_chain_stats, (void *)ctx->d_chain_susp, (void *)ctx->d_chain_order, (void *)ctx->d_chain_cost }) if (b) (void)hipFree(b);
   if (ctx->h_dev_error) (void)hipHostFree(ctx->h_dev_error);
 
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -175,7 +167,7 @@ template <typename T>
 static flx_status upload(flx_context *ctx, T **dst, const void *src, size_t bytes) {
   { flx_status ss = flx_server_stop(ctx); if (ss) return ss; }      /* (a running frame server reads the scene) */
   ctx->structure_version++;              /* (the uploads a launch for a scene that moves goes on over do not come through here: flx_transforms_upload) */
-  ctx->scene_version++;                  /* (a chain of frames does not go on over a changed scene: flx_chain.hip) */
+  ctx->scene_version++;                  /* (the frame server's launch does not go on over a changed scene) */
   size_t &cap = ctx->upload_capacity[(void **)dst];
   if (bytes == 0) {                      /* "none": the kernels test the pointer */
     if (*dst && ctx->twin) FLX_HIP(ctx, hipStreamSynchronize(ctx->twin->stream));
@@ -578,11 +570,7 @@ flx_status flx_check_device_error(flx_context *ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   if (ctx->twin) { (void)hipStreamSynchronize(ctx->twin->stream); ctx->twin->h_dev_error[0] = 0u; }
   ctx->h_dev_error[0] = 0u;
-  ctx->chain_seq = 0;
   /* the kernels' rings may hold ids nobody popped: back to "empty" for the next launch */
-#if FLX_EXPERIMENTS
-  if (ctx->d_chain_rings) (void)hipMemsetAsync(ctx->d_chain_rings, 0xff, (size_t)ctx->prop.multiProcessorCount * chain_rings_per_group() * sizeof(uint32_t), ctx->stream);
-#endif
   if (ctx->d_sv_rings) (void)hipMemsetAsync(ctx->d_sv_rings, 0xff, (size_t)ctx->prop.multiProcessorCount * server_rings_per_group() * sizeof(uint32_t), ctx->stream);
   for (flx_context *c : { ctx, ctx->twin })
     if (c && c->d_frame_rings) (void)hipMemsetAsync(c->d_frame_rings, 0xff, (size_t)c->frame_rings_chains * c->prop.multiProcessorCount * WF_FRAME_RINGS * WF_FRAME_RING * sizeof(uint32_t), c->stream);
@@ -668,14 +656,6 @@ static flx_status ensure_workspace(flx_context *ctx, const DeviceFrame &fr, int 
       }
       ctx->live_capacity = need;
     }
-    /* suspended walks (flx_set_walk_scheduler): room for every possible walk workgroup of every chain, only while suspension is on */
-    const size_t needStrag = ctx->walk_suspend ? (size_t)wf_chains * 2 * cus * 8u * ctx->walk_suspend * WF_STRAG_F4 : 0;
-    if (ctx->strag_capacity < needStrag) {
-      ctx->strag_capacity = 0;
-      if (ctx->d_strag) { FLX_HIP(ctx, hipFree(ctx->d_strag)); ctx->d_strag = nullptr; }
-      FLX_HIP(ctx, hipMalloc(&ctx->d_strag, needStrag * sizeof(float4)));
-      ctx->strag_capacity = needStrag;
-    }
   }
   return FLX_OK;
 }
@@ -699,7 +679,6 @@ static flx_status angle_table(flx_context *ctx, DeviceScene &scT) {
 
 flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFrame &fr, float4 *d_out, const GBufferPtrs &gb) {
   { flx_status ss = flx_server_stop(ctx); if (ss) return ss; }      /* (the frame server renders into the same workspace) */
-  ctx->chain_seq = 0;                    /* this frame's kernels use the workspace a chain of frames keeps its state in: the chain ends here */
   unsigned long long *cnt = ctx->counters_enabled ? ctx->d_counters : nullptr;
   /* The G-buffer accumulators of the filter path carry state from sample to sample (fragment:83-89),
    * so filter frames use the sample-sequential kernel; everything else runs the wavefront pipeline. */
@@ -758,8 +737,8 @@ flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFr
     launch_resolve(fr, ctx->d_hits, ctx->d_samples, ctx->d_last, d_out, ctx->stream);
     FLX_HIP(ctx, hipGetLastError());
   } else {
-    FLX_HIP(ctx, hipMemsetAsync(ctx->d_wfcounts, 0, WF_MAX_GROUPS * 4 * (WF_MAX_ROUNDS + 2) * sizeof(uint32_t), ctx->stream));
-    /* scratch of the walk kernel's tail consolidation and suspension: one slice per chain and possible walk workgroup */
+    FLX_HIP(ctx, hipMemsetAsync(ctx->d_wfcounts, 0, WF_MAX_GROUPS * 2 * (WF_MAX_BOUNCES + 2) * sizeof(uint32_t), ctx->stream));
+    /* scratch of the walk kernel's tail consolidation: one slice per chain and possible walk workgroup */
     if (!ctx->d_tail_pool) FLX_HIP(ctx, hipMalloc(&ctx->d_tail_pool, (size_t)WF_MAX_GROUPS * cus * 8u * WF_TAIL_POOL_F4 * sizeof(float4)));
     /* the frame kernel's rings: one slice per chain that can run (48 MB each at 256 CUs), WF_INVALID everywhere — a launch leaves them so */
     if (ctx->frame_rings_chains < wf_chains) {
@@ -778,7 +757,7 @@ flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFr
     const int frontMode = wf_chains == 1 ? ctx->frame_front : 0;
     const bool front = (frontMode == 1 || frontMode == 2) && ctx->d_rec0 != nullptr &&
                        (frontMode == 2 || frameTiles >= (uint32_t)FLX_FRONT_MIN_TILES_PER_CU * cus) &&
-                       wavefront_front_in_kernel(sc, fr, path_item_count(fr), ctx->walk_scheduler, ctx->walk_suspend, organisationNow);
+                       wavefront_front_in_kernel(sc, fr, path_item_count(fr), organisationNow);
     const bool fusedFront = !front && (frontMode == 2 || frontMode == 3 || (frontMode == 1 && path_item_count(fr) <= (uint32_t)FLX_FRONT_FUSED_MAX_ITEMS));
     if (!front && !fusedFront) launch_primary(sc, fr, ctx->d_hits, cnt, ctx->stream);
     FLX_HIP(ctx, hipGetLastError());
@@ -818,16 +797,14 @@ flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFr
       wb.tailPool = ctx->d_tail_pool + (size_t)g * cus * 8u * WF_TAIL_POOL_F4;
       wb.frameRings = ctx->d_frame_rings + (size_t)g * cus * WF_FRAME_RINGS * WF_FRAME_RING;
       wb.front = front ? 1u : (fusedFront ? 2u : 0u);
-      wb.error = ctx->d_dev_error; wb.watchdog = ctx->inject_watchdog; wb.inject = ctx->inject_flags; wb.walkJobs = ctx->walk_jobs | ((adaptive && front) ? WF_STAMP_COSTS : 0u);
+      wb.error = ctx->d_dev_error; wb.watchdog = ctx->inject_watchdog; wb.inject = ctx->inject_flags; wb.stampCosts = (adaptive && front) ? 1u : 0u;
       wb.tileOrder = (groups == 1 && ctx->d_tile_order && ctx->tile_order_n == tiles) ? ctx->d_tile_order : nullptr;
       if (!wb.tileOrder && adaptive && ctx->auto_order_tiles == tiles && ctx->auto_order_width == fr.width && ctx->auto_order_rows == fr.rows && ctx->auto_order_mode == orderMode)
         wb.tileOrder = ctx->d_auto_order;                     /* made by the last frame of this shape */
       wb.tileCost = (cnt && ctx->d_tile_cost && ctx->tile_cost_n >= tiles) ? ctx->d_tile_cost : nullptr;
       wb.tileCostPrimary = (wb.tileCost && ctx->tile_cost_n >= 2u * tiles) ? 1u : 0u;
       wb.live[0] = ctx->d_live[0] + listSlice * g; wb.live[1] = ctx->d_live[1] + listSlice * g;
-      wb.counts = ctx->d_wfcounts + (size_t)g * 4 * (WF_MAX_ROUNDS + 2); wb.walkQueue = wb.counts + (WF_MAX_ROUNDS + 2); wb.stragCount = wb.walkQueue + (WF_MAX_ROUNDS + 2);
-      wb.coopQueue = wb.stragCount + (WF_MAX_ROUNDS + 2);
-      for (int k = 0; k < 2; k++) wb.strag[k] = ctx->d_strag ? ctx->d_strag + ((size_t)g * 2 + k) * cus * 8u * ctx->walk_suspend * WF_STRAG_F4 : nullptr;
+      wb.counts = ctx->d_wfcounts + (size_t)g * 2 * (WF_MAX_BOUNCES + 2); wb.walkQueue = wb.counts + (WF_MAX_BOUNCES + 2);
       wb.item_base = t0 * perTile; wb.item_count = (t1 - t0) * perTile;
       wb.hits = ctx->d_hits; wb.sampleRadiance = ctx->d_samples; wb.lastOriginal = ctx->d_last; wb.counters = cnt;
       hipStream_t st = g == 0 ? ctx->stream : ctx->aux_stream[g - 1];
@@ -835,8 +812,7 @@ flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFr
        * CU until they end, and the other lane's RCCL kernel — a handful of workgroups that carry the finished frame's strips — would wait
        * behind them for a whole frame.  Such a context leaves a few CUs to the exchange. */
       const uint32_t cusWalk = (ctx->comm && (ctx->twin || ctx->is_twin) && cus > 4u * FLX_COMM_RESERVED_CUS) ? cus - FLX_COMM_RESERVED_CUS : cus;
-      const int ran = launch_wavefront(sc, fr, wb, cusWalk, cnt != nullptr, ctx->walk_scheduler, ctx->walk_suspend, organisationNow,
-                                       g == 0 ? ctx->ev_k0 : nullptr, g == 0 ? ctx->ev_k1 : nullptr, st);
+      const int ran = launch_wavefront(sc, fr, wb, cusWalk, cnt != nullptr, organisationNow, g == 0 ? ctx->ev_k0 : nullptr, g == 0 ? ctx->ev_k1 : nullptr, st);
       FLX_HIP(ctx, hipGetLastError());
       if (ran == -2) return fail(ctx, FLX_ERR_DEVICE, "the walk kernels need 156 KB of dynamic LDS and hipFuncSetAttribute refused it on this device");
       if (ran < 0) return fail(ctx, FLX_ERR_DEVICE, "internal: the frame kernel was to trace the primary rays but does not take this frame");
@@ -1060,22 +1036,6 @@ extern "C" flx_status flx_present(flx_context *ctx, uint32_t width, uint32_t hei
   FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return FLX_OK;
 }
-
-extern "C" flx_status flx_set_walk_scheduler(flx_context *ctx, int scheduler, uint32_t suspend_walks) {
-  if (!ctx) return FLX_ERR_INVALID;
-  if (scheduler < FLX_WALK_LANES || scheduler > FLX_WALK_LANES_FINISHER) return fail(ctx, FLX_ERR_INVALID, "flx_set_walk_scheduler: scheduler 0 lanes, 1 queues, 2 lanes + finisher");
-  if (suspend_walks > WF_STRAG_MAX) return fail(ctx, FLX_ERR_INVALID, "flx_set_walk_scheduler: suspend_walks 0..512");
-  if (scheduler == FLX_WALK_QUEUES && suspend_walks != 0u) return fail(ctx, FLX_ERR_INVALID, "flx_set_walk_scheduler: the queue scheduler does not suspend walks");
-#if !FLX_EXPERIMENTS
-  if (scheduler != FLX_WALK_LANES || suspend_walks != 0u)
-    return fail(ctx, FLX_ERR_INVALID, "flx_set_walk_scheduler: this library was built without the experimental walk schedulers (make EXPERIMENTS=1 builds libflexlight_hip_experiments.so)");
-#endif
-  ctx->walk_scheduler = scheduler;
-  ctx->walk_suspend = suspend_walks;
-  return FLX_OK;
-}
-
-extern "C" int flx_has_experiments(void) { return FLX_EXPERIMENTS; }
 
 extern "C" flx_status flx_last_organisation(flx_context *ctx, int *organisation) {
   if (!ctx || !organisation) return FLX_ERR_INVALID;
@@ -1389,15 +1349,15 @@ static void mirror_scene(flx_context *ctx) {
 }
 
 
-/* ---- the chained frame loop (flx_chain.hip) -------------------------------------------------------------------------------
- * Two frames in flight share ONE stacked workspace (the layout of a batch of two) and one stream: the kernel of frame k completes the slot of frame k and
- * works ahead on the slot of frame k + 1 — whose view flx_frame_begin of that frame posts while the kernel runs — and hands what it holds of it to the
- * kernel of frame k + 1 when frame k is complete.  The drain of a launch, a third of a rank's share of a 1080p frame, disappears under the next frame's bulk. */
+/* ---- which frames of the loop run chained (flx_set_frame_chain: the frame server) --------------------------------------------------------------------- */
 #ifndef FLX_SERVER_MAX_TILES_PER_CU
 #define FLX_SERVER_MAX_TILES_PER_CU 64
 #endif
 #ifndef FLX_CHAIN_MIN_LANES
 #define FLX_CHAIN_MIN_LANES 2
+#endif
+#ifndef FLX_CHAIN_RESERVE
+#define FLX_CHAIN_RESERVE 2048            /* places of a workgroup's rings kept back from a frame's fresh paths (two of them under WF_FRAME_RING) */
 #endif
 static bool chain_same_shape(const flx_frame_params &a, const flx_frame_params &b) {
   return a.width == b.width && a.height == b.height && a.samples == b.samples && a.max_reflections == b.max_reflections && a.min_importancy == b.min_importancy &&
@@ -1411,121 +1371,14 @@ static bool chain_wanted(flx_context *ctx, const flx_frame_params *p, const Devi
   if (!(ctx->pipeline == 3 || (ctx->pipeline == 0 && ctx->walk_entries > 128u))) return false;
   if (fr.max_reflections < 1 || fr.max_reflections > WF_MAX_BOUNCES) return false;
   const int organisation = FLX_WF_ORGANISATION_DEFAULT ? FLX_WF_ORGANISATION_DEFAULT : ctx->wf_organisation;
-  if (organisation == 1 || ctx->walk_scheduler != 0 || ctx->walk_suspend != 0u || ctx->wf_groups > 1 || !(ctx->frame_front == 1 || ctx->frame_front == 2)) return false;
+  if (organisation == 1 || ctx->wf_groups > 1 || !(ctx->frame_front == 1 || ctx->frame_front == 2)) return false;
   if (fr.frame_rows == 0u || (fr.frame_rows & 7u) != 0u) return false;
   if (path_item_count64(fr) * (uint64_t)(ctx->frame_lanes == 3 ? 3 : 2) >= (1ull << 31)) return false;
   if ((uint32_t)fr.samples * 64u * 2u + 2u * (uint32_t)FLX_CHAIN_RESERVE > (uint32_t)WF_FRAME_RING - 256u) return false;
   uint32_t a = 0, b = 0;
-#if FLX_EXPERIMENTS
-  if (ctx->frame_chain == 1) return chain_kernel_fits(sc, a, b);
-#endif
   return server_kernel_fits(sc, a, b, SV_MAX_DEPTH);          /* (with room for a moving scene's transforms per slot) */
 }
 
-#if FLX_EXPERIMENTS      /* the chain of launches (mode 1) was measured and lost to the frame server: only `make EXPERIMENTS=1` carries it (Makefile) */
-static flx_status chain_resources(flx_context *ctx, size_t itemsPerSlot) {
-  const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
-  if (!ctx->d_chain_slots) {
-    FLX_HIP(ctx, hipMalloc(&ctx->d_chain_slots, CH_MAX_DEPTH * sizeof(ChainSlot)));
-    FLX_HIP(ctx, hipMemsetAsync(ctx->d_chain_slots, 0, CH_MAX_DEPTH * sizeof(ChainSlot), ctx->stream));
-    /* the mailbox: pinned host memory the host writes with plain stores while the kernel runs and the kernel reads with system-scope loads
-     * (tools/micro/mailbox.hip).  Not a copy on a stream: a small hipMemcpyAsync is a kernel of its own, and the persistent launch leaves it no CU. */
-    FLX_HIP(ctx, hipHostMalloc((void **)&ctx->h_chain_mail, sizeof(ChainMail), hipHostMallocMapped | hipHostMallocCoherent));
-    memset(ctx->h_chain_mail, 0, sizeof(ChainMail));
-    FLX_HIP(ctx, hipHostGetDevicePointer((void **)&ctx->d_chain_mail, ctx->h_chain_mail, 0));
-    FLX_HIP(ctx, hipMalloc(&ctx->d_chain_relay, sizeof(ChainMail)));
-    FLX_HIP(ctx, hipMemsetAsync(ctx->d_chain_relay, 0, sizeof(ChainMail), ctx->stream));
-    const size_t ringWords = (size_t)cus * chain_rings_per_group();
-    FLX_HIP(ctx, hipMalloc(&ctx->d_chain_rings, ringWords * sizeof(uint32_t)));
-    FLX_HIP(ctx, hipMemsetAsync(ctx->d_chain_rings, 0xff, ringWords * sizeof(uint32_t), ctx->stream));      /* WF_INVALID everywhere; a kernel leaves them so */
-    ctx->chain_susp_cap = (size_t)cus * 1024u;                                  /* every lane of every workgroup may hold a walk when the launch stops */
-    FLX_HIP(ctx, hipMalloc(&ctx->d_chain_susp, (size_t)CH_MAX_DEPTH * 2 * ctx->chain_susp_cap * CH_SUSP_F4 * sizeof(float4)));
-  }
-  /* a resume list holds what the workgroups had in their rings and lanes when a launch stopped: never more than the slot's paths, nor than the rings take */
-  size_t cap = (size_t)cus * WF_FRAME_RING;
-  if (cap > itemsPerSlot) cap = itemsPerSlot;
-  if (ctx->chain_list_cap < cap) {
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->chain_list_cap = 0; ctx->chain_seq = 0;
-    if (ctx->d_chain_lists) { FLX_HIP(ctx, hipFree(ctx->d_chain_lists)); ctx->d_chain_lists = nullptr; }
-    FLX_HIP(ctx, hipMalloc(&ctx->d_chain_lists, (size_t)CH_MAX_DEPTH * 2 * 3 * cap * sizeof(uint32_t)));
-    ctx->chain_list_cap = cap;
-  }
-  return FLX_OK;
-}
-
-/* One frame of the loop, chained: its view posted to the kernels before it (when it continues a chain), the slot it will leave behind reset for the frame
- * `depth` later, its own kernel and the resolve of its slot — everything on the context's stream but the post. */
-static flx_status chain_run_frame(flx_context *ctx, const flx_frame_params *params, const DeviceScene &sc, const DeviceFrame &frOne, float4 *d_out) {
-  { flx_status ss = flx_server_stop(ctx); if (ss) return ss; }
-  const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
-  const uint32_t depth = ctx->frame_lanes == 3 ? 3u : 2u;
-  DeviceFrame fr = frOne;                                   /* the slots stacked like a batch of frames */
-  fr.frames = depth; fr.rows = depth * frOne.frame_rows;
-  const size_t itemsPerSlot = (size_t)path_item_count64(frOne);
-  flx_status s;
-  if ((s = chain_resources(ctx, itemsPerSlot))) return s;
-  int chains = 1;
-  if ((s = ensure_workspace(ctx, fr, 3, false, chains))) return s;
-  const bool continuing = ctx->chain_seq != 0 && ctx->chain_depth == depth && chain_same_shape(ctx->chain_params, *params) && ctx->chain_scene_version == ctx->scene_version;
-  /* sequence numbers: consecutive within a chain (the kernel of frame q expects the posts q + 1, q + 2), never reused, never 0 */
-  if (!continuing) ctx->chain_counter += 8u;
-  uint32_t seq = ++ctx->chain_counter;
-  if (seq < 16u) { ctx->chain_counter = 16u; seq = 16u; }
-  const uint32_t slotP = continuing ? (ctx->chain_slot + 1u) % depth : 0u;
-  for (uint32_t i = 0; i < depth; i++) memset(&fr.view[i], 0, sizeof(FrameView));
-  fr.view[slotP] = frOne.view[0];
-  if (continuing) {
-    /* post: the view, then the number that says whose view it is (a kernel takes the view of exactly the frame it was told to expect, so nothing has to be
-     * reset).  The kernels before this one — the one running and, at depth 3, the one queued behind it — may work ahead on this frame from now on. */
-    memcpy((void *)&ctx->h_chain_mail->view[slotP], &frOne.view[0], sizeof(FrameView));
-    __atomic_store_n(&ctx->h_chain_mail->posted[slotP], seq, __ATOMIC_RELEASE);
-  }
-  /* The slot of the frame before this one is free for the frame `depth - 1` after this one once that frame's kernel and resolve — earlier in this stream
-   * — are through: its cursors back to zero; and of every slot the list set this kernel writes (a frame that begins a chain resets everything). */
-  const uint32_t recycled = (slotP + depth - 1u) % depth;
-  launch_chain_reset(ctx->d_chain_slots, depth, continuing ? 1u << recycled : 7u, seq & 1u, ctx->stream);
-  FLX_HIP(ctx, hipGetLastError());
-  WavefrontBuffers wb = {};
-  wb.rec = ctx->d_rec; wb.rec0 = ctx->d_rec0; wb.pix0 = ctx->d_pix0;
-  wb.frameRings = ctx->d_chain_rings; wb.front = 1u;
-  wb.error = ctx->d_dev_error; wb.watchdog = 0u; wb.inject = 0u;
-  wb.item_base = 0u; wb.item_count = (uint32_t)(depth * itemsPerSlot);
-  wb.hits = ctx->d_hits; wb.sampleRadiance = ctx->d_samples; wb.lastOriginal = ctx->d_last; wb.counters = nullptr;
-  ChainArgs ca = {};
-  ca.slots = ctx->d_chain_slots; ca.mail = ctx->d_chain_mail; ca.relay = ctx->d_chain_relay;
-  ca.lists = ctx->d_chain_lists; ca.listCap = (uint32_t)ctx->chain_list_cap;
-  ca.susp = ctx->d_chain_susp; ca.suspCap = (uint32_t)ctx->chain_susp_cap;
-  ca.depth = depth; ca.ahead = depth - 1u;
-  ca.slotP = slotP;
-  ca.seqP = seq;
-  ca.tilesPerSlot = (uint32_t)(itemsPerSlot / ((size_t)fr.samples * 64u));
-  ca.itemsPerSlot = (uint32_t)itemsPerSlot;
-  for (uint32_t i = 0; i < depth; i++) {
-    ca.order[i] = (ctx->d_chain_order && ctx->chain_order_n == ca.tilesPerSlot) ? ctx->d_chain_order : nullptr;
-    ca.cost[i] = (ctx->d_chain_cost && ctx->chain_cost_n == ca.tilesPerSlot) ? ctx->d_chain_cost + (size_t)i * ctx->chain_cost_n : nullptr;
-  }
-  ca.error = ctx->d_dev_error;
-  ca.stats = nullptr;
-  if (ctx->d_chain_stats) {
-    ca.stats = ctx->d_chain_stats + (size_t)(seq % CH_STAT_LAUNCHES) * CH_STAT_WORDS;
-    unsigned long long init[CH_STAT_WORDS] = {};
-    init[CS_START_MIN] = init[CS_SAVAIL_MIN] = init[CS_STOP_MIN] = init[CS_PDONE_MIN] = init[CS_END_MIN] = init[CS_SDRY_MIN] = init[CS_SAVAIL2_MIN] = ~0ull; init[CS_SEQ] = seq;
-    FLX_HIP(ctx, hipMemcpyAsync(ca.stats, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));      /* (pageable: the copy is staged before the call returns) */
-  }
-  const uint32_t cusWalk = (ctx->comm && cus > 4u * FLX_COMM_RESERVED_CUS) ? cus - FLX_COMM_RESERVED_CUS : cus;      /* (a gathering rank leaves a few CUs to the exchange of the frame before) */
-  if (launch_chain(sc, fr, wb, ca, cusWalk, ctx->stream) != 0) return fail(ctx, FLX_ERR_DEVICE, "internal: the chained frame kernel does not take this scene");
-  FLX_HIP(ctx, hipGetLastError());
-  const size_t P1 = (size_t)frOne.rows * frOne.width;
-  launch_resolve(frOne, ctx->d_hits + (size_t)slotP * P1, ctx->d_samples + (size_t)slotP * P1, ctx->d_last + (size_t)slotP * P1, d_out, ctx->stream, (size_t)depth * P1);
-  FLX_HIP(ctx, hipGetLastError());
-  ctx->timed = false;                                        /* (flx_last_frame_ms: the chained loop's frames are timed by flx_frame_end) */
-  ctx->last_pipeline = 3; ctx->last_organisation = 4;
-  ctx->last_chained = continuing ? 2 : 1;
-  ctx->chain_seq = seq; ctx->chain_slot = slotP; ctx->chain_depth = depth; ctx->chain_params = *params; ctx->chain_scene_version = ctx->scene_version;
-  return FLX_OK;
-}
-#endif /* FLX_EXPERIMENTS */
 
 
 /* ---- the frame server (flx_server.hip) -------------------------------------------------------------------------------------
@@ -1694,7 +1547,6 @@ static flx_status server_post(flx_context *ctx, const flx_frame_params *params, 
     if ((s = server_allocate(ctx, frOne, depth))) return s;
     const size_t P1 = (size_t)frOne.rows * frOne.width;
     ctx->sv_out_pixels = P1;
-    ctx->chain_seq = 0;                                      /* (the workspace a chain of launches keeps its state in is the server's now) */
     FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));         /* whatever used the workspace before, and the allocations above */
     ctx->sv_counter += 16u;                                  /* sequence numbers: consecutive within a launch, never reused across launches, never 0 */
     if (ctx->sv_counter < 16u) ctx->sv_counter = 16u;
@@ -1810,12 +1662,12 @@ static flx_status server_take(flx_context *ctx, int k) {
 }
 
 constexpr int NOT_GATHERED = -2;      /* frame_begin_on's `gather`: this context's own frame; -1: gathered on every rank; >= 0: on that rank */
-static flx_status frame_begin_on(flx_context *ctx, const flx_frame_params *params, int format, int gather, int *slot, int chained = 0 /* 1: a chain of launches, 2: the frame server */) {
+static flx_status frame_begin_on(flx_context *ctx, const flx_frame_params *params, int format, int gather, int *slot, int chained = 0 /* 2: the frame server */) {
   FLX_HIP(ctx, hipSetDevice(ctx->device));
   DeviceScene sc; DeviceFrame fr;
   flx_status s = flx_make_frame(ctx, params, sc, fr);
   if (s) return s;
-  if (!chained) { ctx->chain_seq = 0; ctx->last_chained = 0; }      /* (a frame of another kind ends the chain: its kernels share the workspace) */
+  if (!chained) ctx->last_chained = 0;
   const bool gathered = gather != NOT_GATHERED;
   const bool receiver = !gathered || gather < 0 || gather == ctx->comm_rank;
   if (gathered) { fr.rows = receiver ? params->height : 0u; }      /* the slot holds the WHOLE frame on a rank that receives it, nothing elsewhere */
@@ -1869,10 +1721,6 @@ static flx_status frame_begin_on(flx_context *ctx, const flx_frame_params *param
   } else if (pixels) {
     if (params->use_filter || params->is_temporal) {
       s = run_post_frame(ctx, sc, fr, params, ctx->d_slot[k]);
-#if FLX_EXPERIMENTS
-    } else if (chained == 1) {
-      s = chain_run_frame(ctx, params, sc, fr, ctx->d_slot[k]);
-#endif
     } else {
       GBufferPtrs gb = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
       s = flx_run_frame(ctx, sc, fr, ctx->d_slot[k], gb);
@@ -1907,68 +1755,12 @@ extern "C" flx_status flx_debug_inject_fault(flx_context *ctx, uint32_t watchdog
 }
 extern "C" flx_status flx_set_frame_chain(flx_context *ctx, int mode) {
   if (!ctx) return FLX_ERR_INVALID;
-  if (mode < 0 || mode > 3) return fail(ctx, FLX_ERR_INVALID, "flx_set_frame_chain: 0 (every frame its own launches), 1 (a chain of launches that work ahead on each other's frames), 2 (the frame server — one persistent launch takes the loop's frames as they are posted — for frames of fewer than 64 screen tiles per CU) or 3 (the frame server for every frame it can take)");
-#if !FLX_EXPERIMENTS
-  if (mode == 1) return fail(ctx, FLX_ERR_INVALID, "flx_set_frame_chain: the chain of launches (mode 1) is not in the shipped library (make EXPERIMENTS=1; it lost to the frame server, modes 2 / 3)");
-#endif
+  if (mode < 0 || mode > 3) return fail(ctx, FLX_ERR_INVALID, "flx_set_frame_chain: 0 (every frame its own launches), 2 (the frame server — one persistent launch takes the loop's frames as they are posted — for frames of fewer than 64 screen tiles per CU) or 3 (the frame server for every frame it can take)");
+  if (mode == 1) return fail(ctx, FLX_ERR_INVALID, "flx_set_frame_chain: the chain of launches (mode 1) was removed: it lost to the frame server, modes 2 / 3");
   if (ctx->fifo_n) return fail(ctx, FLX_ERR_INVALID, "flx_set_frame_chain: frames are in flight");
-  ctx->frame_chain = mode; ctx->chain_seq = 0;
+  ctx->frame_chain = mode;
   return FLX_OK;
 }
-#if FLX_EXPERIMENTS
-extern "C" flx_status flx_set_chain_stats(flx_context *ctx, int on) {
-  if (!ctx) return FLX_ERR_INVALID;
-  FLX_HIP(ctx, hipSetDevice(ctx->device));
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (on && !ctx->d_chain_stats) {
-    FLX_HIP(ctx, hipMalloc(&ctx->d_chain_stats, (size_t)CH_STAT_LAUNCHES * CH_STAT_WORDS * sizeof(unsigned long long)));
-    FLX_HIP(ctx, hipMemset(ctx->d_chain_stats, 0, (size_t)CH_STAT_LAUNCHES * CH_STAT_WORDS * sizeof(unsigned long long)));
-  } else if (!on && ctx->d_chain_stats) { FLX_HIP(ctx, hipFree(ctx->d_chain_stats)); ctx->d_chain_stats = nullptr; }
-  return FLX_OK;
-}
-extern "C" flx_status flx_get_chain_stats(flx_context *ctx, uint64_t *out) {
-  if (!ctx || !out) return FLX_ERR_INVALID;
-  if (!ctx->d_chain_stats) return fail(ctx, FLX_ERR_INVALID, "flx_get_chain_stats: flx_set_chain_stats(ctx, 1) first");
-  FLX_HIP(ctx, hipSetDevice(ctx->device));
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  FLX_HIP(ctx, hipMemcpy(out, ctx->d_chain_stats, (size_t)CH_STAT_LAUNCHES * CH_STAT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  return FLX_OK;
-}
-/* diagnostics / experiments: an explicit order of the screen tiles of a chained frame (n = tiles of the frame, or 0: none), and per-tile shading counts */
-extern "C" flx_status flx_set_chain_order(flx_context *ctx, const uint32_t *order, uint32_t n) {
-  if (!ctx) return FLX_ERR_INVALID;
-  FLX_HIP(ctx, hipSetDevice(ctx->device));
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->chain_seq = 0;
-  if (ctx->d_chain_order) { FLX_HIP(ctx, hipFree(ctx->d_chain_order)); ctx->d_chain_order = nullptr; ctx->chain_order_n = 0; }
-  if (!order || n == 0u) return FLX_OK;
-  std::vector<uint8_t> seen(n, 0);
-  for (uint32_t i = 0; i < n; i++) { if (order[i] >= n || seen[order[i]]) return fail(ctx, FLX_ERR_INVALID, "flx_set_chain_order: not a permutation"); seen[order[i]] = 1; }
-  FLX_HIP(ctx, hipMalloc(&ctx->d_chain_order, (size_t)n * sizeof(uint32_t)));
-  FLX_HIP(ctx, hipMemcpy(ctx->d_chain_order, order, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-  ctx->chain_order_n = n;
-  return FLX_OK;
-}
-extern "C" flx_status flx_set_chain_cost(flx_context *ctx, uint32_t n) {
-  if (!ctx) return FLX_ERR_INVALID;
-  FLX_HIP(ctx, hipSetDevice(ctx->device));
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->chain_seq = 0;
-  if (ctx->d_chain_cost) { FLX_HIP(ctx, hipFree(ctx->d_chain_cost)); ctx->d_chain_cost = nullptr; ctx->chain_cost_n = 0; }
-  if (n == 0u) return FLX_OK;
-  FLX_HIP(ctx, hipMalloc(&ctx->d_chain_cost, 2 * (size_t)n * sizeof(uint32_t)));
-  FLX_HIP(ctx, hipMemset(ctx->d_chain_cost, 0, 2 * (size_t)n * sizeof(uint32_t)));
-  ctx->chain_cost_n = n;
-  return FLX_OK;
-}
-extern "C" flx_status flx_get_chain_cost(flx_context *ctx, uint32_t *out /* [2 * n] */) {
-  if (!ctx || !out || !ctx->d_chain_cost) return FLX_ERR_INVALID;
-  FLX_HIP(ctx, hipSetDevice(ctx->device));
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  FLX_HIP(ctx, hipMemcpy(out, ctx->d_chain_cost, 2 * ctx->chain_cost_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return FLX_OK;
-}
-#endif /* FLX_EXPERIMENTS */
 extern "C" flx_status flx_get_server_dump(flx_context *ctx, uint64_t *out /* [4 * 72] */) {
   if (!ctx || !out || !ctx->d_sv_stats) return FLX_ERR_INVALID;
   FLX_HIP(ctx, hipSetDevice(ctx->device));
@@ -2031,17 +1823,6 @@ extern "C" flx_status flx_debug_set_sample_parallel(flx_context *ctx, int on) {
   if (!ctx) return FLX_ERR_INVALID;
   if (ctx->fifo_n) return fail(ctx, FLX_ERR_INVALID, "flx_debug_set_sample_parallel: frames are in flight");
   ctx->sample_parallel = on ? 1 : 0;
-  return FLX_OK;
-}
-/* walk jobs per lane of the frame kernel's walk waves (1: k_wf_frame, 2: k_wf_frame2 where the front of the frame is inside the launch); for A/B runs */
-extern "C" flx_status flx_debug_set_walk_jobs(flx_context *ctx, int jobs) {
-  if (!ctx) return FLX_ERR_INVALID;
-  if (jobs < 0 || jobs > 2) return fail(ctx, FLX_ERR_INVALID, "flx_debug_set_walk_jobs: 0 (the default), 1 or 2");
-#if !FLX_EXPERIMENTS
-  if (jobs == 2) return fail(ctx, FLX_ERR_INVALID, "flx_debug_set_walk_jobs: two jobs per lane (k_wf_frame2) measured slower and is not in the shipped library (make EXPERIMENTS=1)");
-#endif
-  if (ctx->fifo_n) return fail(ctx, FLX_ERR_INVALID, "flx_debug_set_walk_jobs: frames are in flight");
-  ctx->walk_jobs = jobs ? (uint32_t)jobs : (uint32_t)FLX_WALK_JOBS_DEFAULT;
   return FLX_OK;
 }
 /* The order in which the frame kernel's workgroups draw the frame's 8 x 8 screen tiles (k_wf_frame with its front inside): order[q] = the tile the q-th draw makes, a permutation of
@@ -2196,7 +1977,7 @@ static flx_status frame_begin(flx_context *ctx, const flx_frame_params *params, 
     flx_context *t = ctx->twin;
     t->comm = ctx->comm_twin; t->comm_rank = ctx->comm_rank; t->comm_size = ctx->comm_size; t->comm_owned = false;      /* (the primary owns and destroys both) */
     mirror_scene(ctx);
-    t->pipeline = ctx->pipeline; t->wf_groups = ctx->wf_groups; t->wf_organisation = ctx->wf_organisation; t->frame_front = ctx->frame_front; t->walk_scheduler = ctx->walk_scheduler; t->walk_suspend = ctx->walk_suspend;
+    t->pipeline = ctx->pipeline; t->wf_groups = ctx->wf_groups; t->wf_organisation = ctx->wf_organisation; t->frame_front = ctx->frame_front;
     if (ctx->twin_dyn_version != ctx->dyn_version) {          /* lights / transforms changed since the twin's last frame: its own copies, on its stream */
       flx_status s;
       if (ctx->have_transforms && (s = flx_transforms_upload(t, ctx->h_rotation.data(), ctx->h_shift.data(), ctx->n_transforms))) return fail(ctx, s, flx_last_error(t));
@@ -2206,7 +1987,6 @@ static flx_status frame_begin(flx_context *ctx, const flx_frame_params *params, 
     lane = t;
   }
   int slot = 0;
-  if (!chained && lane != ctx && ctx->chain_seq) { ctx->chain_seq = 0; ctx->last_chained = 0; }
   flx_status s = frame_begin_on(lane, params, format, gather, &slot, chained);
   if (s) { if (lane != ctx) ctx->err = lane->err; return s; }
   ctx->fifo[ctx->fifo_n].lane = lane; ctx->fifo[ctx->fifo_n].slot = slot; ctx->fifo_n++;

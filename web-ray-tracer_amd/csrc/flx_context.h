@@ -14,7 +14,6 @@
 #include "flexlight_hip.h"
 #include "flexlight_hip_debug.h"
 #include "flx_kernels.h"
-#include "flx_chain.h"
 #include "flx_server.h"
 
 struct flx_share;                                 /* flx_share.hip: this context's part in the ranks' shared frames */
@@ -24,17 +23,13 @@ typedef struct ncclComm *flx_nccl_comm;          /* = ncclComm_t (rccl.h), kept 
 #define FLX_WF_GROUPS 1      /* measured on MI355X: 2-4 concurrent chains are slower than one (profiles/r01_ab_stream_groups.txt) */
 #endif
 constexpr int WF_MAX_GROUPS = 4;
-#ifndef FLX_FRAME_CHAIN_DEFAULT
 #ifndef FLX_SAMPLE_PARALLEL_DEFAULT
 #define FLX_SAMPLE_PARALLEL_DEFAULT 1
 #endif
-#ifndef FLX_WALK_JOBS_DEFAULT
-#define FLX_WALK_JOBS_DEFAULT 1
-#endif
+#ifndef FLX_FRAME_CHAIN_DEFAULT
 #define FLX_FRAME_CHAIN_DEFAULT 2      /* flx_set_frame_chain's default: the frame server where a frame is a rank's thin share */
 #endif
 constexpr int FLX_COUNTER_SLOTS = 80;          /* 8 work counters + 32 scheduler diagnostics (flx_get_diag) + 40 tail profile (flx_get_tail_diag) */
-constexpr uint32_t WF_STRAG_MAX = 512;         /* most walks a walk workgroup can suspend */
 
 extern thread_local std::string g_create_error;
 
@@ -57,7 +52,6 @@ struct flx_context {
   bool lock_ok = false;                          /* the scene is small and in one object space: its bounce walks may go in lockstep */
   bool lock_use = true;                          /* flx_set_lockstep */
   bool gb_float_wanted = false;                  /* flx_render was given `gbuffers`: the filter frame keeps its float G-buffers */
-  int walk_scheduler = 0;
   int sample_parallel = FLX_SAMPLE_PARALLEL_DEFAULT;      /* flx_debug_set_sample_parallel: k_trace_samples instead of k_trace_pixels where the frame allows it */
   /* Adaptive tile order (flx_debug_set_adaptive_order; on by default): k_resolve sums what every screen tile's paths cost (time in walk lanes), k_tile_order makes the
    * next frame's draw order of it — the lightest tiles last, so that the launch does not end in the chains of a heavy tile's paths.  Frames do not depend on the order. */
@@ -66,7 +60,6 @@ struct flx_context {
   uint32_t auto_order_tiles = 0, auto_order_width = 0, auto_order_rows = 0; int auto_order_mode = -1;      /* the frame shape d_auto_order is for (0 tiles: none yet) */
   uint32_t *d_tile_order = nullptr; uint32_t tile_order_n = 0;      /* flx_debug_set_tile_order: the frame kernel's draw order over the frame's screen tiles */
   unsigned long long *d_tile_cost = nullptr; uint32_t tile_cost_n = 0;      /* flx_debug_tile_cost: counted frames' visits per screen tile */
-  uint32_t walk_jobs = FLX_WALK_JOBS_DEFAULT;    /* flx_debug_set_walk_jobs: walk jobs per lane of the frame kernel's walk waves */
   int32_t *d_ids = nullptr;
   float *d_lights = nullptr;
   uchar4 *d_atlas[3] = { nullptr, nullptr, nullptr };
@@ -110,13 +103,10 @@ struct flx_context {
   size_t aa_io_capacity = 0;
   float4 *d_rec0 = nullptr, *d_pix0 = nullptr;   /* compact bounce-0 records: 3 float4 per path, 3 float4 per pixel */
   size_t rec0_capacity = 0, pix0_capacity = 0;
-  float4 *d_strag = nullptr;                     /* per chain 2 x (walk workgroups x strag_walks) suspended walks; allocated only while suspension is on */
-  size_t strag_capacity = 0;                     /* float4 units */
-  uint32_t walk_suspend = 0;                     /* walks a walk workgroup may leave to the next round (0 = off) */
   size_t rec_capacity = 0;                       /* float4 units */
   uint32_t *d_live[2] = { nullptr, nullptr };
   size_t live_capacity = 0;
-  uint32_t *d_wfcounts = nullptr;                /* per chain: counts, walkQueue, stragCount, [WF_MAX_ROUNDS + 2] each */
+  uint32_t *d_wfcounts = nullptr;                /* per chain: counts, walkQueue, [WF_MAX_BOUNCES + 2] each */
   int pipeline = 0;                              /* 0 auto, 1 per-pixel megakernel, 2 persistent paths, 3 wavefront */
   int last_pipeline = 0;                         /* what the last frame ran */
   int wf_groups = FLX_WF_GROUPS;                 /* wavefront pipeline: independent item groups on separate streams (tails of one overlap the other) */
@@ -166,32 +156,10 @@ struct flx_context {
   int fifo_n = 0;
   std::vector<float> h_lights, h_rotation, h_shift;      /* host copies of what changes per frame, for the twin's own buffers */
   uint64_t dyn_version = 0, twin_dyn_version = 0;
-  /* the chained frame loop (flx_chain.hip): consecutive frames of flx_frame_begin / _end overlap inside the persistent launch */
-  int frame_chain = FLX_FRAME_CHAIN_DEFAULT;                           /* flx_set_frame_chain: 0 never, 1 where the frame loop's second lane would be used and the frame kernel takes the frame */
-  flx::ChainSlot *d_chain_slots = nullptr;       /* [2] */
-  flx::ChainMail *h_chain_mail = nullptr;        /* pinned host memory: the next frame's view is posted (plain stores) while the kernel runs */
-  flx::ChainMail *d_chain_mail = nullptr;        /* its device address */
-  flx::ChainMail *d_chain_relay = nullptr;       /* device memory: the post as the kernel's relaying waves pass it on to the other workgroups */
-  uint32_t *d_chain_lists = nullptr;             /* resume lists: [slot: 3][set: 2][walk, shade, ready] x chain_list_cap entries */
-  size_t chain_list_cap = 0;
-  uint32_t *d_chain_order = nullptr;             /* flx_set_chain_order: the order of a slot's screen tiles, or nullptr */
-  size_t chain_order_n = 0;
-  uint32_t *d_chain_cost = nullptr;              /* flx_set_chain_cost: 2 x chain_cost_n per-tile counts */
-  size_t chain_cost_n = 0;
-  float4 *d_chain_susp = nullptr;                /* walks suspended in flight: [slot: 3][set: 2] x chain_susp_cap x CH_SUSP_F4 float4 */
-  size_t chain_susp_cap = 0;
-  uint32_t *d_chain_rings = nullptr;             /* per workgroup CH_RINGS rings; all slots WF_INVALID between launches */
-
-  unsigned long long *d_chain_stats = nullptr;   /* flx_set_chain_stats: CH_STAT_LAUNCHES x CH_STAT_WORDS diagnostics, by sequence number */
-  uint64_t chain_seq = 0;                        /* sequence number of the last chained frame begun (0: no chain stands) */
-  uint32_t chain_counter = 0;                    /* sequence numbers handed out (never 0) */
-  uint32_t chain_slot = 0;                       /* the slot of that frame */
-  uint32_t chain_depth = 0;                      /* slots of the chain that stands (2 or 3) */
-  flx_frame_params chain_params = {};            /* its shape: a frame continues the chain only with the same one */
-  uint64_t chain_scene_version = 0;              /* ... and the same scene */
+  int frame_chain = FLX_FRAME_CHAIN_DEFAULT;     /* flx_set_frame_chain: 0 never, 2 the frame server for a rank's thin share, 3 for every frame it can take */
   uint64_t scene_version = 0;                    /* bumped by every upload */
   uint64_t begin_scene_version = 0;              /* ... as the last flx_frame_begin found it (0: no frame begun yet) */
-  int last_chained = 0;                          /* flx_last_chained: 0 the last frame of the loop was not chained, 1 it began a chain, 2 it continued one */
+  int last_chained = 0;                          /* flx_last_chained: 0 the last frame of the loop was not chained, 3 the frame server took it */
   /* the frame server (flx_server.hip): one persistent launch renders the loop's frames as they are posted (flx_set_frame_chain mode 2) */
   flx::ServerSlot *d_sv_slots = nullptr;
   flx::ServerMail *h_sv_mail = nullptr, *d_sv_mail = nullptr, *d_sv_relay = nullptr;      /* pinned host memory (and its device address); device memory */

@@ -111,8 +111,8 @@ struct DeviceScene {
 constexpr uint32_t WALK_END = 0x30000000u;      /* kind 3, index 0: as an index it names the threaded copy's shared terminator (entry 0), so a kernel that does not count visits needs
                                                  * no test for it — it fetches the terminator and ends there (walkFetchG); larger than every real index, for the copies whose links are plain indices */
 /* A successor link = threaded index | kind of the entry it names << 28 | (that entry's transform differs from this
- * entry's) << 30.  Kinds: 0 terminator, 1 box, 2 triangle, 3 = WALK_END.  The queue scheduler (flx_walkq.hip) routes a
- * walk to its next test from the link alone, without fetching the entry. */
+ * entry's) << 30.  Kinds: 0 terminator, 1 box, 2 triangle, 3 = WALK_END: a walk knows its next
+ * test from the link alone, without fetching the entry. */
 constexpr uint32_t LINK_INDEX = 0x0fffffffu, LINK_XFORM = 0x40000000u;
 constexpr int LINK_KIND_SHIFT = 28;
 FLX_DEV uint32_t linkIndex(uint32_t link) { return link & LINK_INDEX; }
@@ -159,8 +159,8 @@ FLX_DEV f3 view_camera(const FrameView &v) { return F3(v.camera[0], v.camera[1],
 FLX_DEV f3 view_ambient(const FrameView &v) { return F3(v.ambient[0], v.ambient[1], v.ambient[2]); }
 FLX_DEV f3 frame_camera(const DeviceFrame &fr, uint32_t f) { return view_camera(fr.view[f]); }
 FLX_DEV f3 frame_ambient(const DeviceFrame &fr, uint32_t f) { return view_ambient(fr.view[f]); }
-/* The views of a frame's batch: the kernel's arguments (LV = false) or a copy the kernel keeps in LDS (LV = true: the chained frame kernel, whose second
- * frame's view arrives while it runs). */
+/* The views of a frame's batch: the kernel's arguments (LV = false) or a copy the kernel keeps in LDS (LV = true: the frame server, whose later frames'
+ * views arrive while it runs). */
 template <bool LV>
 FLX_DEV const FrameView &view_at(const DeviceFrame &fr, const FrameView *lv, uint32_t f) { if (LV) return lv[f]; else return fr.view[f]; }
 /* image row (0 = top, within its frame) of packed row k under the tile policy */
@@ -967,21 +967,6 @@ FLX_DEV bool walkTriT(WalkState &w, const WalkEntry &cur) {
   w.i = __float_as_int(cur.e2.y);
   return ended;
 }
-/* walkTriT's second half on its own: what a triangle test's answer does to the walk (fragment:217-222 / :270-273) and the link it leaves by — for callers that run the
- * test on operands they picked themselves (the two-job walk waves, flx_wavefront.hip: k_wf_frame2) */
-FLX_DEV bool walkTriApply(WalkState &w, const WalkEntry &cur, bool hit, f3 suv) {
-  bool ended = false;
-  if (hit) {
-    if (w.mode == 0) { w.shadowed = true; ended = true; }
-    else if (suv.x != 0.0f) {                        /* fragment:217 */
-      w.suv = suv; w.hitTI = (__float_as_int(cur.e2.z) >> 2) << 1; w.tri = __float_as_int(cur.e2.w);
-      w.minLen = suv.x;
-    }
-  }
-  w.i = __float_as_int(cur.e2.y);
-  return ended;
-}
-FLX_DEV f3 sel3(bool c, f3 a, f3 b) { return F3(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z); }
 FLX_DEV void walkStartT(const DeviceScene &sc, WalkState &w, int mode, const Ray &ray, float len) {
   w.mode = mode; w.src = ray; w.tR = ray; w.cachedTI = 0; w.minLen = len; w.i = (int)sc.walk_root;
   walkPrepareRay(sc, w);

@@ -1,4 +1,4 @@
-/* flx_frame_common.h — what the shade kernels, the frame kernel (flx_wavefront.hip) and the chained frame kernel (flx_chain.hip) share: the
+/* flx_frame_common.h — what the shade kernels, the frame kernel (flx_wavefront.hip) and the frame server (flx_server.hip) share: the
  * kernel arguments read from the kernarg segment, the front of a frame for one screen tile, one path's shading, the rings of a workgroup. */
 #pragma once
 #include "flx_kernels.h"
@@ -230,7 +230,7 @@ FLX_DEV void shade_path(FrameArgsP ab, uint32_t pathId, WorkCounters &cnt, const
 }
 
 /* ---- a walk lane of the persistent frame kernels ------------------------------------------------------------------------------------------------------
- * What a lane of a walk wave holds and does is the same in every persistent kernel (k_wf_frame, the frame server's k_wf_server, the experiments' k_wf_frame2): a path —
+ * What a lane of a walk wave holds and does is the same in every persistent kernel (k_wf_frame, the frame server's k_wf_server): a path —
  * its shadow walk, then its closest-hit walk — whose record it loads, walks and folds.  The kernels differ in where path ids come from and go to (one set of rings, rings
  * per frame slot, a mailbox); that stays with them.  One body here, so that a change to the walk is a change to all of them. */
 struct WalkLane {

@@ -37,16 +37,13 @@ constexpr int WF_MAX_BOUNCES = 250;
 struct WavefrontBuffers {
   float4 *rec;                  /* 8 x float4 (128 B) per path item */
   uint32_t *live[2];            /* live path lists, alternating per bounce */
-  uint32_t *counts;             /* [WF_MAX_ROUNDS + 2] slots used in the live list of round r */
-  uint32_t *walkQueue;          /* [WF_MAX_ROUNDS + 2] per-round refill cursor of the walk kernel */
+  uint32_t *counts;             /* [WF_MAX_BOUNCES + 2] slots used in the live list of round r */
+  uint32_t *walkQueue;          /* [WF_MAX_BOUNCES + 2] per-round refill cursor of the walk kernel */
   uint32_t item_base, item_count; /* the path items [item_base, item_base + item_count) this group of launches owns */
   const float4 *hits;
   float4 *sampleRadiance, *lastOriginal;
   unsigned long long *counters; /* or nullptr */
   float4 *tailPool;             /* WF_TAIL_POOL_F4 float4 per walk workgroup: scratch of the tail consolidation */
-  float4 *strag[2];             /* walks suspended by the walk kernel of round r (slot r & 1), WF_STRAG_F4 float4 each */
-  uint32_t *stragCount;         /* [WF_MAX_ROUNDS + 2] walks suspended in round r */
-  uint32_t *coopQueue;          /* [WF_MAX_ROUNDS + 2] cursor of the cooperative finisher over round r's suspended walks */
   /* Compact records of bounce 0 (or nullptr: full records).  The samples of a pixel share the primary hit, so what their
    * first shading yields splits into a part per pixel — next origin, shadow origin, albedo, base luminance: pix0, 3 float4,
    * indexed [screen tile][lane] —
@@ -60,7 +57,7 @@ struct WavefrontBuffers {
   uint32_t *error;              /* the context's device error word (pinned host memory, WF_ERR_* bits), or nullptr: a watchdog that trips says so here (flx_status FLX_ERR_DEVICE at the next point the host waits) */
   uint32_t watchdog;            /* frame kernels: polls after which a wave that waits gives up (0: FQ_WATCHDOG, seconds); fault injection sets it low */
   uint32_t inject;              /* fault injection (flx_debug_inject_fault): WF_INJECT_* */
-  uint32_t walkJobs;            /* frame kernel with its front inside: low byte 2 = two walk jobs per lane (k_wf_frame2), else one (k_wf_frame); | WF_STAMP_COSTS: the variant whose walk lanes stamp what a path cost (adaptive tile order) */
+  uint32_t stampCosts;          /* frame kernel with its front inside: 1 = the variant whose walk lanes stamp what a path cost (k_wf_frame_stamped: adaptive tile order) */
   uint32_t tileCostPrimary;     /* tileCost (below) has a second half for the primary rays' visits per tile */
   const uint32_t *tileOrder;    /* frame kernel with its front inside: the screen tile the q-th draw from the frame's tile queue makes (a permutation of the frame's tiles), or nullptr: tile q */
   unsigned long long *tileCost; /* counted frames: entries visited by the paths of every screen tile (flx_debug_tile_cost), or nullptr */
@@ -68,26 +65,20 @@ struct WavefrontBuffers {
 /* the arguments of the shade kernels and the frame kernels, read from the kernarg segment where they are used (flx_frame_common.h) */
 struct FrameArgs { DeviceScene sc; DeviceFrame fr; WavefrontBuffers wb; };
 constexpr uint32_t WF_FRAME_RING = 16384;
-constexpr uint32_t WF_STAMP_COSTS = 0x100u;   /* WavefrontBuffers::walkJobs */
 /* device error word: who gave up */
 constexpr uint32_t WF_ERR_SHADE_WATCHDOG = 1u, WF_ERR_WALK_WATCHDOG = 2u, WF_ERR_LIST = 4u, WF_ERR_LEFTOVER = 8u, WF_ERR_RING_SLOT = 16u, WF_ERR_SERVER_IDLE = 32u, WF_ERR_SERVER_TIMEOUT = 64u;
 constexpr uint32_t WF_INJECT_NO_SHADING = 1u;      /* the shade waves of a frame kernel drop what they pop: the paths never come back and the walk waves' watchdog must trip */
 constexpr uint32_t WF_FRAME_RINGS = 3;       /* to shade, to walk, fresh (tile, sample) units */
 constexpr size_t WF_TAIL_POOL_F4 = 1024 * 8;
-constexpr uint32_t WF_STRAG_F4 = 5;
-constexpr int WF_MAX_ROUNDS = 2 * WF_MAX_BOUNCES;    /* regular rounds + the rounds that drain suspended walks */
 size_t wavefront_live_capacity(const DeviceFrame &fr, uint32_t compute_units);
-/* walk_scheduler: bit 0: 0 = one walk per lane (k_wf_walk_pre / k_wf_walk), 1 = workgroup-wide test queues (flx_walkq.hip);
- * bit 1: suspended walks are finished by k_wf_walk_coop (a wave per walk) instead of being carried to the next round */
-/* suspend_max: walks a walk workgroup may hand over to the next round instead of finishing them (0 = never) */
 /* organisation: 0 automatic — the whole bounce loop in ONE persistent launch (k_wf_frame: walk waves and shade waves of a workgroup
  * hand paths to each other through LDS rings, no barrier between bounces) where the scene's transforms leave room in LDS, else
  * rounds; 1 = rounds (one k_wf_shade + k_wf_walk_pre pair per bounce); 2 = the frame kernel (rounds if it does not fit). */
-bool wavefront_front_in_kernel(const DeviceScene &sc, const DeviceFrame &fr, uint32_t item_count, int walk_scheduler, uint32_t suspend_max, int organisation);
+bool wavefront_front_in_kernel(const DeviceScene &sc, const DeviceFrame &fr, uint32_t item_count, int organisation);
 /* -> what ran: 1 rounds, 2 the frame kernel, 3 the frame kernel with the front of the frame inside it; -1: wb.front set but the frame kernel cannot run; -2: the walk
  * kernels' dynamic LDS limit could not be raised on this device */
 int launch_wavefront(const DeviceScene &sc, const DeviceFrame &fr, const WavefrontBuffers &wb, uint32_t compute_units, bool count,
-                     int walk_scheduler, uint32_t suspend_max, int organisation, hipEvent_t walk0_begin, hipEvent_t walk0_end, hipStream_t stream);
+                     int organisation, hipEvent_t walk0_begin, hipEvent_t walk0_end, hipStream_t stream);
 /* denoise chain (flx_filter.hip): 13 RGBA8 planes = the reference's RenderTexture[0..3], IpRenderTexture[0..3],
  * OriginalRenderTexture[0..1], IdRenderTexture[0..1], OriginalIdRenderTexture (pathtracerWGL2.js:224-252). */
 struct FilterPlanes { uint32_t *R[4], *Ip[4], *O[2], *Id[2], *OId; };

@@ -4,7 +4,7 @@
  * Why.  A frame kernel launch (flx_wavefront.hip: k_wf_frame) ends in a drain: once its tile queue is dry a workgroup finishes the paths it holds at the pace
  * of their chains walk -> shade -> walk.  For a rank's eighth of the 1080p dragon frame that is half of the launch (1.65 ms where the work is 0.8: 3.9x at 8
  * GPUs).  Two launches cannot share a CU, so a second lane only fills the CUs the first one has left (1.29 ms per frame); and a chain of launches that work
- * ahead on each other's frames (flx_chain.hip) pays per launch — stop, hand-over lists, relaunch, ramp-up — what the overlap gains (1.36 - 1.47 ms).  The
+ * ahead on each other's frames (measured, then removed) pays per launch — stop, hand-over lists, relaunch, ramp-up — what the overlap gains (1.36 - 1.47 ms).  The
  * chains themselves are long (1.3 - 2 ms from a frame's first tile under load): the machine needs two to three frames in flight AT ALL TIMES, with nothing in
  * between.  The reference's loop renders frame after frame from one context without waiting for the GPU (modules/pathtracerWGL2.js:254-303); the shader's
  * loop is per pixel (shaders/pathtracer_fragment.glsl:475-596): nothing in the algorithm ties a launch to a frame.

@@ -18,22 +18,21 @@ EXPORTS = [
     "flx_context_create", "flx_context_destroy", "flx_last_error", "flx_scene_upload", "flx_transforms_upload",
     "flx_lights_upload", "flx_atlas_upload", "flx_scene_upload_view", "flx_tile_row_count", "flx_tile_row_at",
     "flx_render", "flx_render_device", "flx_sync", "flx_set_stream", "flx_set_counters_enabled", "flx_get_counters",
-    "flx_last_frame_ms", "flx_debug_math", "flx_debug_intersect", "flx_debug_walk", "flx_device_info", "flx_version", "flx_set_pipeline", "flx_set_lockstep", "flx_last_pipeline", "flx_get_diag", "flx_set_wavefront_groups", "flx_temporal_reset", "flx_set_walk_scheduler", "flx_render_batch", "flx_render_batch_device", "flx_render_planes_device", "flx_filter_planes_device",
+    "flx_last_frame_ms", "flx_debug_math", "flx_debug_intersect", "flx_debug_walk", "flx_device_info", "flx_version", "flx_set_pipeline", "flx_set_lockstep", "flx_last_pipeline", "flx_get_diag", "flx_set_wavefront_groups", "flx_temporal_reset", "flx_render_batch", "flx_render_batch_device", "flx_render_planes_device", "flx_filter_planes_device",
     "flx_mesh_import_obj", "flx_mesh_destroy", "flx_mesh_entry_count", "flx_mesh_triangle_count", "flx_mesh_set_transform", "flx_mesh_move",
     "flx_mesh_scale", "flx_mesh_set_material", "flx_mesh_bounding", "flx_mesh_flatten", "flx_transforms_pack", "flx_fxaa_device", "flx_taa_device", "flx_fxaa", "flx_taa", "flx_taa_reset", "flx_present", "flx_present_device",
     "flx_comm_unique_id", "flx_comm_init_rank", "flx_comm_destroy", "flx_render_gathered_device",
     "flx_group_create", "flx_group_destroy", "flx_group_last_error", "flx_group_size", "flx_group_uses_rccl", "flx_group_context",
-    "flx_frame_begin", "flx_frame_end", "flx_frames_in_flight", "flx_set_frame_lanes", "flx_set_server_moving_scenes", "flx_server_moving", "flx_get_tail_diag", "flx_set_frame_chain", "flx_last_chained", "flx_debug_inject_fault", "flx_set_chain_stats", "flx_get_chain_stats", "flx_get_server_stats", "flx_get_server_dump", "flx_set_chain_order", "flx_set_chain_cost", "flx_get_chain_cost",
-    "flx_render_gathered_root_device", "flx_comm_count", "flx_frame_begin_gathered", "flx_group_set_gather", "flx_frame_host_slots", "flx_has_experiments", "flx_set_wavefront_organisation", "flx_set_frame_front", "flx_last_organisation",
+    "flx_frame_begin", "flx_frame_end", "flx_frames_in_flight", "flx_set_frame_lanes", "flx_set_server_moving_scenes", "flx_server_moving", "flx_get_tail_diag", "flx_set_frame_chain", "flx_last_chained", "flx_debug_inject_fault", "flx_get_server_stats", "flx_get_server_dump",
+    "flx_render_gathered_root_device", "flx_comm_count", "flx_frame_begin_gathered", "flx_group_set_gather", "flx_frame_host_slots", "flx_set_wavefront_organisation", "flx_set_frame_front", "flx_last_organisation",
     "flx_group_scene_upload", "flx_group_transforms_upload", "flx_group_lights_upload", "flx_group_atlas_upload", "flx_group_scene_upload_view", "flx_group_render",
     "flx_group_frame_begin", "flx_group_frame_end", "flx_group_frames_in_flight", "flx_group_set_frame_lanes",
     "flx_frame_server_takes", "flx_frame_target_set", "flx_frame_target_index", "flx_debug_set_server_groups",
     "flx_share_create", "flx_share_join", "flx_share_leave", "flx_frame_begin_shared", "flx_frame_end_shared",
-    "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_walk_jobs", "flx_debug_set_sample_parallel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
+    "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_sample_parallel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
 ]
 
 
-EXPERIMENTS_ONLY = ("flx_set_chain_stats", "flx_get_chain_stats", "flx_set_chain_order", "flx_set_chain_cost", "flx_get_chain_cost")      # include/flexlight_hip_debug.h, #ifdef FLX_EXPERIMENTS
 
 SHARE_HANDLE_BYTES = 128      # FLX_SHARE_HANDLE_BYTES
 MAX_BATCH_FRAMES = 32          # FLX_MAX_BATCH_FRAMES of include/flexlight_hip.h
@@ -79,7 +78,6 @@ def _load():
         "flx_debug_intersect": (C.c_int, [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32]),
         "flx_debug_walk": (C.c_int, [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32]),
         "flx_temporal_reset": (C.c_int, [vp]),
-        "flx_set_walk_scheduler": (C.c_int, [vp, C.c_int, C.c_uint32]),
         "flx_render_batch": (C.c_int, [vp, C.POINTER(FrameParams), u32, fp, C.POINTER(Counters)]),
         "flx_render_batch_device": (C.c_int, [vp, C.POINTER(FrameParams), u32, vp]),
         "flx_render_planes_device": (C.c_int, [vp, C.c_void_p, C.c_void_p]),
@@ -112,13 +110,8 @@ def _load():
         "flx_server_moving": (C.c_int, [vp]),
         "flx_last_chained": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "flx_debug_inject_fault": (C.c_int, [vp, u32, u32]),
-        "flx_set_chain_stats": (C.c_int, [vp, C.c_int]),
         "flx_get_server_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "flx_get_server_dump": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
-        "flx_get_chain_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
-        "flx_set_chain_order": (C.c_int, [vp, C.POINTER(C.c_uint32), u32]),
-        "flx_set_chain_cost": (C.c_int, [vp, u32]),
-        "flx_get_chain_cost": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
         "flx_comm_unique_id": (C.c_int, [C.c_char_p]),
         "flx_comm_init_rank": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
         "flx_comm_destroy": (C.c_int, [vp]),
@@ -128,7 +121,6 @@ def _load():
         "flx_frame_begin_gathered": (C.c_int, [vp, C.POINTER(FrameParams), C.c_int, C.c_int]),
         "flx_group_set_gather": (C.c_int, [vp, C.c_int]),
         "flx_frame_host_slots": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_int)]),
-        "flx_has_experiments": (C.c_int, []),
         "flx_set_wavefront_organisation": (C.c_int, [vp, C.c_int]),
         "flx_set_frame_front": (C.c_int, [vp, C.c_int]),
         "flx_last_organisation": (C.c_int, [vp, C.POINTER(C.c_int)]),
@@ -159,7 +151,6 @@ def _load():
         "flx_share_create": (C.c_int, [vp, u32, u32, u32, C.c_int, C.c_int, C.c_char_p]),
         "flx_share_join": (C.c_int, [vp, C.c_char_p, C.c_int]),
         "flx_share_leave": (C.c_int, [vp]),
-        "flx_debug_set_walk_jobs": (C.c_int, [vp, C.c_int]),
         "flx_debug_set_sample_parallel": (C.c_int, [vp, C.c_int]),
         "flx_debug_set_adaptive_order": (C.c_int, [vp, C.c_int]),
         "flx_debug_tile_order_of": (C.c_int, [vp, C.POINTER(C.c_float), u32, C.c_int, C.POINTER(u32)]),
@@ -172,8 +163,6 @@ def _load():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            if name in EXPERIMENTS_ONLY:       # the chain of launches: `make EXPERIMENTS=1` only
-                continue
             if os.environ.get("FLX_LIB"):      # an A/B variant (an earlier round's library): what it lacks fails when it is called
                 continue
             raise
@@ -182,11 +171,6 @@ def _load():
 
 
 LIB = _load()
-
-
-def has_experiments():
-    """the loaded library carries the experimental walk schedulers (`make EXPERIMENTS=1`)"""
-    return bool(LIB.flx_has_experiments())
 
 
 def _fp(a):
@@ -203,6 +187,7 @@ class Context:
         if rc != 0:
             raise FlexLightHipError("flx_context_create(%d) failed (%d): %s" % (device, rc, LIB.flx_last_error(None).decode()))
         self._h = h
+        self._pending = []                     # the frame loop's frames in flight, oldest first (frame_begin / frame_end)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -314,7 +299,6 @@ class Context:
 
     def frame_begin_gathered(self, params, root=-1):
         """flx_frame_begin over the communicator: the gathered whole frame stays in device memory (frame_end -> its pointer)"""
-        self._pending = getattr(self, "_pending", [])
         self._check(LIB.flx_frame_begin_gathered(self._h, C.byref(params), 2, int(root)), "flx_frame_begin_gathered")
         self._pending.append((params.height, params.width, False, True))
 
@@ -324,7 +308,7 @@ class Context:
         self._check(LIB.flx_set_frame_lanes(self._h, int(lanes)), "flx_set_frame_lanes")
 
     def set_frame_chain(self, mode):
-        """0 every frame its own launches; 1 a chain of launches (flx_chain.hip); 2 (default) the frame server (flx_server.hip) for thin frames; 3 the server for every frame it takes"""
+        """0 every frame its own launches; 1 refused (the chain of launches was removed); 2 (default) the frame server (flx_server.hip) for thin frames; 3 the server for every frame it takes"""
         self._check(LIB.flx_set_frame_chain(self._h, int(mode)), "flx_set_frame_chain")
 
     def set_server_moving_scenes(self, on):
@@ -422,44 +406,13 @@ class Context:
         self._tile_cost_n = int(n)
         return out
 
-    def set_walk_jobs(self, jobs):
-        """walk jobs per lane of the frame kernel's walk waves (flx_debug_set_walk_jobs): 1, 2, or 0 = the library's default"""
-        self._check(LIB.flx_debug_set_walk_jobs(self._h, int(jobs)), "flx_debug_set_walk_jobs")
-
-    def set_chain_stats(self, on):
-        self._check(LIB.flx_set_chain_stats(self._h, int(bool(on))), "flx_set_chain_stats")
-
-    def chain_stats(self):
-        """-> uint64 [64 launches, 64 words] (flx_chain.h: CS_*)"""
-        out = np.zeros((64, 64), np.uint64)
-        self._check(LIB.flx_get_chain_stats(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))), "flx_get_chain_stats")
-        return out
-
-    def set_chain_order(self, order):
-        """explicit order of a chained frame's screen tiles (a permutation; None: the default)"""
-        if order is None:
-            self._check(LIB.flx_set_chain_order(self._h, None, 0), "flx_set_chain_order")
-            return
-        o = np.ascontiguousarray(order, np.uint32)
-        self._check(LIB.flx_set_chain_order(self._h, o.ctypes.data_as(C.POINTER(C.c_uint32)), o.size), "flx_set_chain_order")
-
-    def set_chain_cost(self, n):
-        self._check(LIB.flx_set_chain_cost(self._h, int(n)), "flx_set_chain_cost")
-        self._chain_cost_n = int(n)
-
-    def chain_cost(self):
-        out = np.zeros((2, self._chain_cost_n), np.uint32)
-        self._check(LIB.flx_get_chain_cost(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))), "flx_get_chain_cost")
-        return out
-
     def last_chained(self):
-        """0 the last frame begun in the loop was not chained, 1 it began a chain, 2 it continued one"""
+        """0 the last frame begun in the loop was not chained, 3 the frame server took it"""
         v = C.c_int()
         self._check(LIB.flx_last_chained(self._h, C.byref(v)), "flx_last_chained")
         return v.value
 
     def frame_begin(self, params, rgba8=False, device=False):
-        self._pending = getattr(self, "_pending", [])
         self._check(LIB.flx_frame_begin(self._h, C.byref(params), 2 if device else (1 if rgba8 else 0)), "flx_frame_begin")
         self._pending.append((self.tile_row_count(params), params.width, rgba8, device))
 
@@ -581,10 +534,6 @@ class Context:
     def set_frame_front(self, mode):
         """primary rays and bounce-0 shading: 0 k_primary + k_wf_shade0 in front, 3 one kernel in front, 2 inside the frame kernel wherever it runs, 1 (default) automatic"""
         self._check(LIB.flx_set_frame_front(self._h, int(mode)), "flx_set_frame_front")
-
-    def set_walk_scheduler(self, scheduler, suspend_walks=0):
-        """0 one walk per lane (default), 1 LDS test queues, 2 lanes + cooperative finisher; identical results"""
-        self._check(LIB.flx_set_walk_scheduler(self._h, int(scheduler), int(suspend_walks)), "flx_set_walk_scheduler")
 
     def get_diag(self):
         out = (C.c_uint64 * 32)()
