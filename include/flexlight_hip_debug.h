@@ -48,6 +48,10 @@ flx_status flx_debug_set_angle_table(flx_context *ctx, int on);
  * sample, the cross-sample globals of the shader (fragment:83-89) replayed in the shader's order afterwards — for frames of 2, 4 or 8 samples and at most 4 bounces; 0: the
  * sample-sequential k_trace_pixels always.  Frames, G-buffers and work counters are identical; for A/B runs (profiles/r05_sample_parallel.txt). */
 flx_status flx_debug_set_sample_parallel(flx_context *ctx, int on);
+/* Which per-pixel kernel the last frame ran, where it ran pipeline 1 (flx_last_pipeline): samples_side_by_side 0 for the sample-sequential k_trace_pixels,
+ * S for k_trace_samples<S>; lockstep 1 for the variant with the wave's lockstep walk; counted 1 for the build with the work counters.  All three are -1
+ * when the last frame ran another pipeline.  For tests: they prove which instantiation rendered a frame. */
+flx_status flx_debug_last_trace_kernel(flx_context *ctx, int *samples_side_by_side, int *lockstep, int *counted);
 /* the order in which the frame kernel draws a frame's 8 x 8 screen tiles: order[q] = the tile of the q-th draw (a permutation of the frame's n tiles; n = 0: tile q); frames do not depend on it */
 flx_status flx_debug_set_tile_order(flx_context *ctx, const uint32_t *order, uint32_t n);
 /* the adaptive tile order — the draw order made from what every tile cost in the last frame of the same shape (the lightest tiles last) — on (1, the default) or off (0: screen order) */

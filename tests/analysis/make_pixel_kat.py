@@ -204,7 +204,10 @@ def oracle_primary(sc, params, px, py_gl):
     return [f32(x) for x in suv], ti.value, tri.value, [f32(x) for x in d]
 
 
-CASES = [("cornell_obj", 48, 27, 2, 3, 0.0), ("dragon", 24, 14, 2, 4, 1.0), ("dragon", 12, 8, 3, 6, 2.0), ("theater", 32, 18, 2, 3, 3.0), ("cornell", 20, 20, 2, 2, 1.0)]
+CASES = [("cornell_obj", 48, 27, 2, 3, 0.0), ("dragon", 24, 14, 2, 4, 1.0), ("dragon", 12, 8, 3, 6, 2.0), ("theater", 32, 18, 2, 3, 3.0), ("cornell", 20, 20, 2, 2, 1.0),
+         # the samples and bounces of the per-pixel kernels that run side by side: configs[1]'s 4 x 3 (cornell.obj: a frame that still covers 90 pixels),
+         # 8 x 3 on the dragon (glass paths: the filter's glassFilter / dontFilter bits) and on a scene of the lockstep walk
+         ("cornell_obj", 36, 20, 4, 3, 0.0), ("dragon", 24, 14, 8, 3, 4.0), ("cornell", 16, 12, 8, 3, 5.0)]
 
 
 def rows():

@@ -62,6 +62,16 @@ def test_radiance_matches_oracle(hip, oracle, scenes, name, w, h, spp, bounces, 
     assert (got[..., 3] == 1).sum() == want_cnt["primary_hits"]
     if (name, w, h, spp, bounces) == ("cornell", 256, 256, 1, 1):
         _assert_fullsize_hash("configs[0] cornell 256x256 1spp 1b", got, got_cnt)
+        # ... and the build without counters, the one bench.py times (per pixel: k_trace_pixels<false, true>)
+        hip.set_pipeline(pipeline)
+        try:
+            plain, _, _ = hip.render(p)
+            kernel = hip.last_trace_kernel()
+        finally:
+            hip.set_pipeline(0)
+        assert np.array_equal(plain, want, equal_nan=True)
+        _assert_fullsize_hash("configs[0] cornell 256x256 1spp 1b", plain, got_cnt)
+        assert kernel == ((0, 1, 0) if pipeline == 1 else (-1, -1, -1))
 
 
 @pytest.mark.parametrize("pipeline", [2, 1], ids=["persistent", "per_pixel"])
@@ -160,7 +170,14 @@ def test_multi_gpu_configs_at_full_size(hip, oracle, scenes, name, w, h, spp, bo
     want, want_cnt = oracle.render(sc, p, threads=0)[:2]
     assert np.array_equal(got, want, equal_nan=True)
     assert got_cnt == want_cnt
-    _assert_fullsize_hash({"dragon": "configs[3] dragon 4K 8spp 4b", "theater": "configs[4] theater 1080p 16spp 6b"}[name], got, got_cnt)
+    key = {"dragon": "configs[3] dragon 4K 8spp 4b", "theater": "configs[4] theater 1080p 16spp 6b"}[name]
+    _assert_fullsize_hash(key, got, got_cnt)
+    # the build without counters, the one bench.py times (configs[3]: the wavefront pipeline; configs[4]: the persistent path kernel, k_paths<false>)
+    plain, _, _ = hip.render(p)
+    assert hip.last_pipeline() == {"dragon": 3, "theater": 2}[name]
+    assert hip.last_trace_kernel() == (-1, -1, -1)
+    assert np.array_equal(plain, want, equal_nan=True)
+    _assert_fullsize_hash(key, plain, got_cnt)
 
 
 def _moved(sc, p, i):
@@ -526,7 +543,16 @@ def test_filter_frame_at_full_size(hip, oracle, scenes):
     assert np.array_equal(got, want, equal_nan=True)
     assert got_cnt == want_cnt
     assert hip.last_pipeline() == 1
+    assert hip.last_trace_kernel() == (4, 1, 1)
     _assert_fullsize_hash("configs[1] cornell_obj 1080p 4spp 3b filter", got, got_cnt, got_gb)
+    # the build without counters, the one bench.py times: k_trace_samples<false, true, 4>
+    plain, _, plain_gb = hip.render(p, gbuffers=True)
+    assert hip.last_pipeline() == 1
+    assert hip.last_trace_kernel() == (4, 1, 0)
+    for key in want_gb:
+        assert np.array_equal(plain_gb[key], want_gb[key], equal_nan=True), key
+    assert np.array_equal(plain, want, equal_nan=True)
+    _assert_fullsize_hash("configs[1] cornell_obj 1080p 4spp 3b filter", plain, got_cnt, plain_gb)
 
 
 def test_filter_refuses_tiles(hip, scenes):

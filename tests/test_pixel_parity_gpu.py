@@ -9,22 +9,32 @@ from test_oracle_kat import _pixel_kat_cases, assert_pixel_kat, pixel_kat_expect
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("k", range(5))
+@pytest.mark.parametrize("k", range(len(_pixel_kat_cases())))
 def test_whole_pixels_literal(hip, scenes, k):
     case = _pixel_kat_cases()[k]
     sc, p, rows, want_color, want_gb = pixel_kat_expectations(case, scenes)
     hip.update_scene(sc)
-    p.use_filter = 1
-    _, _, gbs = hip.render(p, gbuffers=True)                       # the per-pixel kernel with the filter's outputs
-    p.use_filter = 0
     try:
-        for pipeline, organisation, front in ((1, 0, 1), (2, 0, 1), (3, 1, 0), (3, 2, 0), (3, 2, 2), (3, 1, 3), (0, 0, 1)):
+        # the per-pixel kernel twice — a pixel's samples side by side (k_trace_samples, where the frame allows it) and one after the other (k_trace_pixels) —,
+        # with the filter's outputs and without
+        for pipeline, organisation, front, sample_parallel in ((1, 0, 1, 1), (1, 0, 1, 0), (2, 0, 1, 1), (3, 1, 0, 1), (3, 2, 0, 1), (3, 2, 2, 1), (3, 1, 3, 1), (0, 0, 1, 1)):
             hip.set_pipeline(pipeline)
             hip.set_wavefront_organisation(organisation)
             hip.set_frame_front(front)
+            hip.set_sample_parallel(sample_parallel)
+            gbs = {}
+            if pipeline == 1:
+                p.use_filter = 1
+                _, _, gbs = hip.render(p, gbuffers=True)
+                p.use_filter = 0
             frame, _, _ = hip.render(p)
-            assert_pixel_kat(case, rows, want_color, want_gb if pipeline == 1 else {}, frame, gbs, "GPU pipeline %d organisation %d front %d, case %d" % (pipeline, organisation, front, k))
+            what = "GPU pipeline %d organisation %d front %d sample_parallel %d, case %d" % (pipeline, organisation, front, sample_parallel, k)
+            if pipeline == 1:
+                ts = hip.last_trace_kernel()[0]
+                assert ts == (case["samples"] if sample_parallel and case["samples"] in (2, 4, 8) and case["bounces"] <= 4 and (case["samples"], case["bounces"]) != (8, 4) else 0), (what, ts)
+            assert_pixel_kat(case, rows, want_color, want_gb if pipeline == 1 else {}, frame, gbs, what)
     finally:
         hip.set_pipeline(0)
         hip.set_wavefront_organisation(0)
         hip.set_frame_front(1)
+        hip.set_sample_parallel(1)

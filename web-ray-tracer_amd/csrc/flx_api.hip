@@ -703,6 +703,7 @@ flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFr
   if (pipeline == 3 && fr.max_reflections > WF_MAX_BOUNCES) pipeline = 2;
   ctx->last_pipeline = pipeline;
   ctx->last_organisation = 0;
+  ctx->last_trace = TraceKernel{ -1, -1, -1 };
   if (pipeline != 1 && (fr.use_filter || fr.is_temporal)) return fail(ctx, FLX_ERR_INVALID, "pipelines 2 and 3 do not produce the G-buffers of filter / temporal frames");
   const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
   int wf_chains = 1;
@@ -715,7 +716,7 @@ flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFr
     DeviceScene scT = sc;
     { flx_status es = angle_table(ctx, scT); if (es) return es; }
     FLX_HIP(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
-    launch_trace_pixels(scT, fr, d_out, gb, cnt, ctx->stream, ctx->sample_parallel);
+    ctx->last_trace = launch_trace_pixels(scT, fr, d_out, gb, cnt, ctx->stream, ctx->sample_parallel);
     FLX_HIP(ctx, hipGetLastError());
     FLX_HIP(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
   } else if (pipeline == 2) {
@@ -1046,6 +1047,14 @@ extern "C" flx_status flx_last_organisation(flx_context *ctx, int *organisation)
 extern "C" flx_status flx_last_pipeline(flx_context *ctx, int *pipeline) {
   if (!ctx || !pipeline) return FLX_ERR_INVALID;
   *pipeline = ctx->last_pipeline;
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_debug_last_trace_kernel(flx_context *ctx, int *samples_side_by_side, int *lockstep, int *counted) {
+  if (!ctx || !samples_side_by_side || !lockstep || !counted) return FLX_ERR_INVALID;
+  *samples_side_by_side = ctx->last_trace.samples;
+  *lockstep = ctx->last_trace.lockstep;
+  *counted = ctx->last_trace.counted;
   return FLX_OK;
 }
 
@@ -1614,7 +1623,7 @@ static flx_status server_post(flx_context *ctx, const flx_frame_params *params, 
   }
   __atomic_store_n(&ctx->h_sv_mail->posted[slot], seq, __ATOMIC_RELEASE);
   *seqOut = seq; *slotOut = slot;
-  ctx->last_pipeline = 3; ctx->last_organisation = 5; ctx->last_chained = 3;
+  ctx->last_pipeline = 3; ctx->last_organisation = 5; ctx->last_chained = 3; ctx->last_trace = TraceKernel{ -1, -1, -1 };
   return FLX_OK;
 }
 

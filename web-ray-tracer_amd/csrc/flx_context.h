@@ -109,6 +109,7 @@ struct flx_context {
   uint32_t *d_wfcounts = nullptr;                /* per chain: counts, walkQueue, [WF_MAX_BOUNCES + 2] each */
   int pipeline = 0;                              /* 0 auto, 1 per-pixel megakernel, 2 persistent paths, 3 wavefront */
   int last_pipeline = 0;                         /* what the last frame ran */
+  flx::TraceKernel last_trace = { -1, -1, -1 };     /* ... and which per-pixel kernel, where that was pipeline 1 (all -1 otherwise) */
   int wf_groups = FLX_WF_GROUPS;                 /* wavefront pipeline: independent item groups on separate streams (tails of one overlap the other) */
   hipStream_t aux_stream[3] = { nullptr, nullptr, nullptr };
   hipEvent_t ev_fork = nullptr, ev_join[3] = { nullptr, nullptr, nullptr };

@@ -16,9 +16,11 @@ struct GBufferPtrs {
   uint32_t *q_color = nullptr, *q_color_ip = nullptr, *q_original_color = nullptr, *q_id = nullptr, *q_original_id = nullptr;
 };
 
+/* which per-pixel kernel a launch ran (flx_debug_last_trace_kernel): samples = 0 k_trace_pixels, S k_trace_samples<S>; lockstep, counted: its LOCK and COUNT */
+struct TraceKernel { int samples, lockstep, counted; };
 /* counters: 8 x u64 in flx_counters order, or nullptr (no counting code is compiled in). */
-void launch_trace_pixels(const DeviceScene &sc, const DeviceFrame &fr, float4 *out, const GBufferPtrs &gb,
-                         unsigned long long *counters, hipStream_t stream, int sample_parallel = 0);
+TraceKernel launch_trace_pixels(const DeviceScene &sc, const DeviceFrame &fr, float4 *out, const GBufferPtrs &gb,
+                                unsigned long long *counters, hipStream_t stream, int sample_parallel = 0);
 /* v2 pipeline: primary hits (float4 s,u,v,triangleId-as-bits per pixel) -> persistent path kernel -> resolve. */
 uint32_t path_item_count(const DeviceFrame &fr);
 uint64_t path_item_count64(const DeviceFrame &fr);

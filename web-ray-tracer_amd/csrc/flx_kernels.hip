@@ -353,11 +353,11 @@ static bool launch_trace_samples(const DeviceScene &sc, const DeviceFrame &fr, f
   return true;
 }
 
-void launch_trace_pixels(const DeviceScene &sc, const DeviceFrame &fr, float4 *out, const GBufferPtrs &gb,
-                         unsigned long long *counters, hipStream_t stream, int sample_parallel) {
+TraceKernel launch_trace_pixels(const DeviceScene &sc, const DeviceFrame &fr, float4 *out, const GBufferPtrs &gb,
+                                unsigned long long *counters, hipStream_t stream, int sample_parallel) {
   const uint32_t tiles = ((fr.width + 15u) >> 4) * ((fr.rows + 15u) >> 4);
   const bool lock = FLX_LOCKSTEP && sc.lock_entries != 0u;      /* small scene in one object space: the variant with the wave-wide walk */
-  if (sample_parallel && launch_trace_samples(sc, fr, out, gb, counters, stream, lock)) return;
+  if (sample_parallel && launch_trace_samples(sc, fr, out, gb, counters, stream, lock)) return TraceKernel{ fr.samples, lock ? 1 : 0, counters ? 1 : 0 };
   if (lock) {
     if (counters) hipLaunchKernelGGL((k_trace_pixels<true, true>), dim3(tiles * (256u / FLX_TRACE_BLOCK)), dim3(FLX_TRACE_BLOCK), 0, stream, sc, fr, out, gb, counters);
     else hipLaunchKernelGGL((k_trace_pixels<false, true>), dim3(tiles * (256u / FLX_TRACE_BLOCK)), dim3(FLX_TRACE_BLOCK), 0, stream, sc, fr, out, gb, counters);
@@ -365,6 +365,7 @@ void launch_trace_pixels(const DeviceScene &sc, const DeviceFrame &fr, float4 *o
     if (counters) hipLaunchKernelGGL((k_trace_pixels<true, false>), dim3(tiles * (256u / FLX_TRACE_BLOCK)), dim3(FLX_TRACE_BLOCK), 0, stream, sc, fr, out, gb, counters);
     else hipLaunchKernelGGL((k_trace_pixels<false, false>), dim3(tiles * (256u / FLX_TRACE_BLOCK)), dim3(FLX_TRACE_BLOCK), 0, stream, sc, fr, out, gb, counters);
   }
+  return TraceKernel{ 0, lock ? 1 : 0, counters ? 1 : 0 };
 }
 
 /* ---- v2: primary kernel + persistent path kernel with lane refill + resolve ---------------------- */

@@ -29,7 +29,7 @@ EXPORTS = [
     "flx_group_frame_begin", "flx_group_frame_end", "flx_group_frames_in_flight", "flx_group_set_frame_lanes",
     "flx_frame_server_takes", "flx_frame_target_set", "flx_frame_target_index", "flx_debug_set_server_groups",
     "flx_share_create", "flx_share_join", "flx_share_leave", "flx_frame_begin_shared", "flx_frame_end_shared",
-    "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_sample_parallel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
+    "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_sample_parallel", "flx_debug_last_trace_kernel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
 ]
 
 
@@ -152,6 +152,7 @@ def _load():
         "flx_share_join": (C.c_int, [vp, C.c_char_p, C.c_int]),
         "flx_share_leave": (C.c_int, [vp]),
         "flx_debug_set_sample_parallel": (C.c_int, [vp, C.c_int]),
+        "flx_debug_last_trace_kernel": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "flx_debug_set_adaptive_order": (C.c_int, [vp, C.c_int]),
         "flx_debug_tile_order_of": (C.c_int, [vp, C.POINTER(C.c_float), u32, C.c_int, C.POINTER(u32)]),
         "flx_debug_set_tile_order": (C.c_int, [vp, C.POINTER(u32), u32]),
@@ -381,6 +382,13 @@ class Context:
     def set_sample_parallel(self, on):
         """k_trace_samples (a pixel's samples side by side) instead of k_trace_pixels where the frame allows it (flx_debug_set_sample_parallel)"""
         self._check(LIB.flx_debug_set_sample_parallel(self._h, int(bool(on))), "flx_debug_set_sample_parallel")
+
+    def last_trace_kernel(self):
+        """-> (samples side by side: 0 k_trace_pixels, S k_trace_samples<S>; lockstep 0 / 1; counted 0 / 1) of the last frame's per-pixel kernel,
+        (-1, -1, -1) when it ran another pipeline (flx_debug_last_trace_kernel)"""
+        s, lock, count = C.c_int(), C.c_int(), C.c_int()
+        self._check(LIB.flx_debug_last_trace_kernel(self._h, C.byref(s), C.byref(lock), C.byref(count)), "flx_debug_last_trace_kernel")
+        return s.value, lock.value, count.value
 
     def set_adaptive_order(self, on):
         """the frame kernel's draw order made from the last frame's per-tile cost (flx_debug_set_adaptive_order): on by default"""
