@@ -146,6 +146,14 @@ flx_status flx_render_batch(flx_context *ctx, const flx_frame_params *params, ui
 flx_status flx_render_batch_device(flx_context *ctx, const flx_frame_params *params, uint32_t n_frames, void *d_out_rgba);
 #define FLX_MAX_BATCH_FRAMES 32
 flx_status flx_sync(flx_context *ctx);
+/* The rasterizer renderer: replaces rasterizerWGL2.js's rasterizingPass (rasterizerWGL2.js:253-312, the draw state of :395-401)
+ * with shaders/rasterizer_vertex.glsl and rasterizer_fragment.glsl:202-291 — every triangle drawn two-sided under the depth test
+ * LESS and blended (ONE, ONE_MINUS_SRC_ALPHA / ONE, ONE) into the RGBA8 drawing buffer cleared to (0,0,0,0); the pins are
+ * DESIGN.md §2 "Rasterizer".  Uses width, height, camera, view_matrix, hdr, ambient, texture_width and the tile policy; ignores
+ * the path-tracing fields.  Output rows as flx_render; every value is the buffer's byte k as k / 255 (flx_present gives the bytes
+ * back).  Exactly one of out_rgba (host) / d_out_rgba (device memory, enqueued on the context's stream) is non-NULL; counters
+ * may be NULL (given, the call waits for the frame). */
+flx_status flx_raster_render(flx_context *ctx, const flx_frame_params *params, float *out_rgba, void *d_out_rgba, flx_counters *counters);
 /* Use an existing hipStream_t (e.g. torch's current stream) instead of the context's own. NULL restores it. */
 flx_status flx_set_stream(flx_context *ctx, void *hip_stream);
 /* GPU time of the last frame between HIP events on the context's stream, and of its dominant

@@ -2,8 +2,9 @@
 /*
  * Render one BASELINE scene through the whole JavaScript path — FlexLight facade, scene graph, host
  * flattening, N-API addon, libflexlight_hip.so — and write the float32 radiance to a file.
- *   node tools/render_scene.js <scene> --out frame.f32 [--width W --height H --spp S --bounces B --filter 0|1 --aa fxaa|taa --frames N --batch N --present FILE --assets DIR --devices N | a,b,...]
+ *   node tools/render_scene.js <scene> --out frame.f32 [--width W --height H --spp S --bounces B --filter 0|1 --aa fxaa|taa --frames N --batch N --present FILE --assets DIR --devices N | a,b,... --renderer pathtracer|rasterizer]
  *   --devices: the frame split over several GPUs in this process (flx_group_*): N = GPUs 0 .. N - 1, or a list (a number may repeat)
+ *   --renderer: 'pathtracer' (default) or 'rasterizer' (one GPU; --spp, --bounces, --filter and --batch do not apply to it)
  */
 const fs = require('fs');
 const os = require('os');
@@ -42,9 +43,10 @@ function loadImage (rel) {
   engine.config.maxReflections = Number(opt('--bounces', frame.maxReflections));
   engine.config.filter = Number(opt('--filter', frame.filter ? 1 : 0)) === 1;
   engine.config.antialiasing = opt('--aa', undefined);               // 'fxaa' | 'taa'
-  engine.renderer = 'pathtracer';
+  engine.renderer = opt('--renderer', 'pathtracer');
   await engine.renderer.updateScene();
   const batch = Number(opt('--batch', 0));                            // N frames of a camera move through renderBatch: all N are written
+  if (batch > 0 && engine.renderer.type !== 'pathtracer') throw new Error('--batch renders through the path tracer\'s renderBatch; the ' + engine.renderer.type + ' has none');
   if (batch > 0) {
     const cam = engine.camera;
     const cameras = Array.from({ length: batch }, (_, i) => ({ x: cam.x + 0.3 * i, y: cam.y + 0.1 * i, fx: cam.fx + 0.05 * i, fy: cam.fy - 0.02 * i }));

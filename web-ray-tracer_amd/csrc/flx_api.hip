@@ -1339,6 +1339,47 @@ extern "C" flx_status flx_render(flx_context *ctx, const flx_frame_params *param
   return flx_check_device_error(ctx);
 }
 
+/* The rasterizer renderer: one k_raster launch (flx_raster.hip), timed like a frame (flx_last_frame_ms). */
+extern "C" flx_status flx_raster_render(flx_context *ctx, const flx_frame_params *params, float *out_rgba, void *d_out_rgba, flx_counters *counters) {
+  if (!ctx) return FLX_ERR_INVALID;
+  if ((out_rgba == nullptr) == (d_out_rgba == nullptr)) return fail(ctx, FLX_ERR_INVALID, "flx_raster_render: exactly one of out_rgba and d_out_rgba must be given");
+  if (!params) return fail(ctx, FLX_ERR_INVALID, "frame params are NULL");
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  flx_frame_params p = *params;
+  p.samples = 1; p.max_reflections = 0; p.use_filter = 0; p.is_temporal = 0;      /* the path-tracing fields are not the rasterizer's */
+  DeviceScene sc; DeviceFrame fr;
+  flx_status s = flx_make_frame(ctx, &p, sc, fr);
+  if (s) return s;
+  if ((s = flx_server_stop(ctx))) return s;                 /* (the frame server renders into the same workspace) */
+  const size_t pixels = (size_t)fr.rows * fr.width;
+  float4 *dst = (float4 *)d_out_rgba;
+  if (!dst && pixels) {
+    if ((s = flx_ensure_pixels(ctx, &ctx->d_out, &ctx->out_capacity, pixels))) return s;
+    dst = ctx->d_out;
+  }
+  unsigned long long *cnt = counters ? ctx->d_counters : nullptr;
+  FLX_HIP(ctx, hipEventRecord(ctx->ev_frame0, ctx->stream));
+  if (cnt) FLX_HIP(ctx, hipMemsetAsync(cnt, 0, FLX_COUNTER_SLOTS * sizeof(unsigned long long), ctx->stream));
+  FLX_HIP(ctx, hipEventRecord(ctx->ev_k0, ctx->stream));
+  if (pixels) {
+    launch_raster(sc, fr, params->hdr, dst, cnt, ctx->stream);
+    FLX_HIP(ctx, hipGetLastError());
+  }
+  FLX_HIP(ctx, hipEventRecord(ctx->ev_k1, ctx->stream));
+  FLX_HIP(ctx, hipEventRecord(ctx->ev_frame1, ctx->stream));
+  ctx->timed = true;
+  if (out_rgba && pixels) FLX_HIP(ctx, hipMemcpyAsync(out_rgba, dst, pixels * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  unsigned long long host_cnt[8];
+  if (counters) FLX_HIP(ctx, hipMemcpyAsync(host_cnt, ctx->d_counters, sizeof host_cnt, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_rgba || counters) FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (counters) {
+    memcpy(counters, host_cnt, sizeof host_cnt);
+    ctx->last_counters = *counters;
+  }
+  /* after a wait, as flx_render: a frame kernel's watchdog that tripped on this stream earlier is reported here; enqueued only, as flx_render_device */
+  return (out_rgba || counters) ? flx_check_device_error(ctx) : FLX_OK;
+}
+
 /* ---- the frame loop: begin / end with two frames in flight (include/flexlight_hip.h) -------------------------------------
  * Two frames in flight overlap on the GPU when they run on two streams with a workspace each: the kernels of a frame are a
  * dependent chain and every one of them ends in a tail that leaves most CUs idle; frame k + 1's kernels fill those

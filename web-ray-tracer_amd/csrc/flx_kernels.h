@@ -97,6 +97,8 @@ void launch_filter_chain(const FilterPlanes &pl, float4 *out, int W, int H, int 
 struct TemporalRings { const uint32_t *c[16], *ip[16], *id[16], *oid[16]; int n; };
 void launch_temporal(const TemporalRings &rings, int W, int H, int hdr, int use_filter, uint32_t *dColor, uint32_t *dIp, float4 *out,
                      hipStream_t stream);
+/* the rasterizer renderer (flx_raster.hip): one frame of k_raster into float4 out[rows][width] (the RGBA8 drawing buffer's values as float32) */
+void launch_raster(const DeviceScene &sc, const DeviceFrame &fr, int hdr, float4 *out, unsigned long long *counters, hipStream_t stream);
 void launch_debug_math(int fn, const float *a, const float *b, float *out, uint32_t n, hipStream_t stream);
 void launch_debug_intersect(int fn, const float *in, float *out, uint32_t n, hipStream_t stream);
 bool launch_debug_walk(int variant, const DeviceScene &sc, const float *in, float *out, uint32_t n, hipStream_t stream);      /* false: the scene does not allow that variant */

@@ -30,6 +30,7 @@ EXPORTS = [
     "flx_frame_server_takes", "flx_frame_target_set", "flx_frame_target_index", "flx_debug_set_server_groups",
     "flx_share_create", "flx_share_join", "flx_share_leave", "flx_frame_begin_shared", "flx_frame_end_shared",
     "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_sample_parallel", "flx_debug_last_trace_kernel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
+    "flx_raster_render",
 ]
 
 
@@ -62,6 +63,7 @@ def _load():
         "flx_tile_row_at": (u32, [C.POINTER(FrameParams), u32]),
         "flx_render": (C.c_int, [vp, C.POINTER(FrameParams), fp, C.POINTER(GBuffers), C.POINTER(Counters)]),
         "flx_render_device": (C.c_int, [vp, C.POINTER(FrameParams), vp]),
+        "flx_raster_render": (C.c_int, [vp, C.POINTER(FrameParams), fp, vp, C.POINTER(Counters)]),
         "flx_sync": (C.c_int, [vp]),
         "flx_set_stream": (C.c_int, [vp, vp]),
         "flx_set_counters_enabled": (C.c_int, [vp, C.c_int]),
@@ -252,6 +254,19 @@ class Context:
         rc = LIB.flx_render(self._h, C.byref(params), _fp(out), C.byref(gb) if gb else None, C.byref(cnt) if cnt else None)
         self._check(rc, "flx_render")
         return out, (cnt.as_dict() if cnt else None), gbs
+
+    def raster_render(self, params, counters=False):
+        """One frame of the rasterizer renderer -> (rgba [rows, W, 4] float32, counters dict or None).  Every value is k / 255,
+        the RGBA8 drawing buffer's byte k."""
+        rows = self.tile_row_count(params)
+        out = np.zeros((rows, params.width, 4), np.float32)
+        cnt = Counters() if counters else None
+        self._check(LIB.flx_raster_render(self._h, C.byref(params), _fp(out), None, C.byref(cnt) if cnt else None), "flx_raster_render")
+        return out, (cnt.as_dict() if cnt else None)
+
+    def raster_render_device(self, params, device_ptr):
+        """the rasterizer's frame into device memory (float4[rows][W]), enqueued on the context's stream"""
+        self._check(LIB.flx_raster_render(self._h, C.byref(params), None, C.c_void_p(device_ptr), None), "flx_raster_render")
 
     def render_batch(self, params_list, counters=False):
         """1 .. 32 frames in one pass -> (rgba [n, rows, W, 4] float32, counters dict (summed over the batch) or None)."""

@@ -3,14 +3,16 @@
  * FlexLight — engine facade for the HIP back-end, same surface as the reference's flexlight.js:13-144:
  *   const engine = new FlexLight(canvas);  engine.scene.queue.push(...);
  *   engine.renderer = 'pathtracer';        engine.renderer.render();
- * `canvas` is any {width, height} object (headless); api is 'hip'.  Only the path tracer exists here:
- * asking for the rasterizer is reported like an unknown renderer in the reference (console.error, the
- * current renderer stays).  io / ui are browser input handling and are accepted but ignored.
+ * `canvas` is any {width, height} object (headless); api is 'hip'.  Both renderers of the reference exist:
+ * 'pathtracer' (PathTracerHIP, the default here) and 'rasterizer' (RasterizerHIP, one GPU: options.devices is
+ * refused).  An unknown name is reported as in the reference (console.error, the current renderer stays).
+ * io / ui are browser input handling and are accepted but ignored.
  */
 const { Camera } = require('./camera.js');
 const { Config } = require('./config.js');
 const { Scene, Transform, Primitive, Triangle, Plane, Object3D, Cuboid, Bounding } = require('./scene.js');
 const { PathTracerHIP } = require('./pathtracerHIP.js');
+const { RasterizerHIP } = require('./rasterizerHIP.js');
 
 class FlexLight {
   constructor (canvas, options) {
@@ -49,19 +51,23 @@ class FlexLight {
   set camera (camera) { this._camera = camera; this._renderer.camera = camera; }
   set scene (scene) { this._scene = scene; this._renderer.scene = scene; }
 
-  set renderer (name) {
-    if (name !== 'pathtracer') {
+  set renderer (name) {                                   // flexlight.js:106-129
+    if (name !== 'pathtracer' && name !== 'rasterizer') {
       console.error('Renderer option', name, 'on api', this._api, 'doesn\'t exist.');
       return;
+    }
+    if (name === 'rasterizer' && this._options.devices !== undefined && this._options.devices !== null) {
+      throw new Error('The rasterizer renderer runs on one GPU: options.devices is only for the path tracer');
     }
     this._idRenderer = name;
     const wasRunning = this._renderer && !this._renderer._halt;
     if (this._renderer) this._renderer.halt();
-    this._renderer = new PathTracerHIP(this._canvas, this._scene, this._camera, this._config, this._options);
+    const Renderer = name === 'rasterizer' ? RasterizerHIP : PathTracerHIP;
+    this._renderer = new Renderer(this._canvas, this._scene, this._camera, this._config, this._options);
     if (wasRunning) this._renderer.render();
   }
 
   set io (name) { this._io = name; }
 }
 
-module.exports = { FlexLight, PathTracerHIP, Camera, Config, Scene, Transform, Primitive, Triangle, Plane, Object3D, Cuboid, Bounding };
+module.exports = { FlexLight, PathTracerHIP, RasterizerHIP, Camera, Config, Scene, Transform, Primitive, Triangle, Plane, Object3D, Cuboid, Bounding };

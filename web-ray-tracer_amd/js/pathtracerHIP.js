@@ -366,4 +366,4 @@ function taaVectors (n, random) {
   return vecs;
 }
 
-module.exports = { PathTracerHIP, taaVectors };
+module.exports = { PathTracerHIP, taaVectors, native };

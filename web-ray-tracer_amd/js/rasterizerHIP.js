@@ -1,0 +1,185 @@
+'use strict';
+/*
+ * RasterizerHIP — FlexLight's rasterizer renderer (reference modules/rasterizerWGL2.js) with its frames drawn by
+ * libflexlight_hip.so (flx_raster_render, k_raster) instead of by WebGL2.  Same surface as the reference's object:
+ * type = 'rasterizer', public config / camera / scene, fps, fpsLimit, canvas getter, async render(), halt(),
+ * async updateScene(), async updatePrimaryLightSources() — plus renderFrame(), a synchronous single frame for headless use,
+ * and presentFrame() as PathTracerHIP has them.  One GPU context (no groups of GPUs, no frame loop in the library).
+ * A raster frame is short, so the loop calls the synchronous binding once per tick: no native work is ever pending between
+ * ticks, and updateScene() / updatePrimaryLightSources() may run at any time.
+ * The "canvas" is any object with width and height; if it has onFrame(frame) the loop calls it.
+ */
+const { Transform } = require('./scene.js');
+const sceneFile = require('./sceneFile.js');
+const { native, taaVectors } = require('./pathtracerHIP.js');
+
+class RasterizerHIP {
+  constructor (canvas, scene, camera, config, options) {
+    this.type = 'rasterizer';
+    this.config = config;
+    this.camera = camera;
+    this.scene = scene;
+    this.fps = 0;
+    this.fpsLimit = Infinity;
+    this._canvas = canvas;
+    this._device = (options && options.device) || 0;
+    this._tile = (options && options.tile) || null;      // {rows, index, count}: this context's strips of the frame
+    this._ctx = null;
+    this._halt = true;
+    this._atlasLists = [null, null, null];
+    this._haveScene = false;
+    this.lastFrame = null;
+  }
+
+  get canvas () { return this._canvas; }
+
+  _context () {
+    if (!this._ctx) this._ctx = native().createContext(this._device);
+    return this._ctx;
+  }
+
+  halt () {                                               // rasterizerWGL2.js:50-57
+    this._halt = true;
+    if (this._ctx) {
+      try { native().destroyContext(this._ctx); } catch (e) { console.warn('Unable to release the GPU context', e.message); }
+      this._ctx = null;
+    }
+    this._haveScene = false;
+    this._atlasLists = [null, null, null];
+  }
+
+  async updateScene () {                                  // rasterizerWGL2.js:150-190
+    const built = await this.scene.generateArraysFromGraph();
+    native().uploadScene(this._context(), built.geometryBuffer, built.sceneBuffer, built.idBuffer);
+    this._haveScene = true;
+  }
+
+  async updatePrimaryLightSources () {                    // rasterizerWGL2.js:125-148
+    native().uploadLights(this._context(), sceneFile.buildLightArray(this.scene));
+  }
+
+  _updateAtlases () {                                     // rasterizerWGL2.js:65-123: rebuilt only when the list object or its members changed
+    const n = native(), c = this._context();
+    if (this.scene.prebuiltAtlases) {
+      if (this._atlasLists[0] !== this.scene.prebuiltAtlases) {
+        this.scene.prebuiltAtlases.forEach((a, which) => n.uploadAtlas(c, which, a.data, a.width, a.height));
+        this._atlasLists = [this.scene.prebuiltAtlases, null, null];
+      }
+      return;
+    }
+    const lists = [this.scene.textures, this.scene.pbrTextures, this.scene.translucencyTextures];
+    lists.forEach((list, which) => {
+      const old = this._atlasLists[which];
+      if (old && old.length === list.length && list.every((e, i) => e === old[i])) return;
+      this._atlasLists[which] = list.slice();
+      if (list.length === 0) { n.uploadAtlas(c, which, null, 0, 0); return; }
+      const atlas = sceneFile.buildAtlas(list, this.scene.standardTextureSizes);
+      n.uploadAtlas(c, which, atlas.data, atlas.width, atlas.height);
+    });
+  }
+
+  /* the uniforms of rasterizingPass (rasterizerWGL2.js:253-284); the path-tracing fields the binding requires are fixed */
+  frameParams (jitter) {
+    const q = this.config.renderQuality > 0 ? this.config.renderQuality : 1;
+    const w = Math.max(1, Math.round(this._canvas.width * q)), h = Math.max(1, Math.round(this._canvas.height * q));
+    const cam = jitter ? Object.assign(Object.create(this.camera), { fx: this.camera.fx + jitter.x, fy: this.camera.fy + jitter.y }) : this.camera;
+    const p = {
+      width: w, height: h,
+      camera: [this.camera.x, this.camera.y, this.camera.z],
+      viewMatrix: Array.from(sceneFile.buildViewMatrix(cam, w, h)),                 // rasterizerWGL2.js:254-265: jittered direction, same matrix as the path tracer's
+      samples: 1, maxReflections: 0, minImportancy: 0,
+      hdr: this.config.hdr ? 1 : 0,
+      ambient: [this.scene.ambientLight[0], this.scene.ambientLight[1], this.scene.ambientLight[2]],
+      textureWidth: Math.floor(2048 / this.scene.standardTextureSizes[0])
+    };
+    if (this._tile) { p.tileRows = this._tile.rows; p.tileIndex = this._tile.index; p.tileCount = this._tile.count; }
+    return p;
+  }
+
+  /* config.antialiasing: 'fxaa' | 'taa' | anything else = none (rasterizerWGL2.js:216-232); TAA as in PathTracerHIP */
+  _antialiasing () {
+    const v = typeof this.config.antialiasing === 'string' ? this.config.antialiasing.toLowerCase() : undefined;
+    const mode = (v === 'fxaa' || v === 'taa') ? v : undefined;
+    if (mode !== this._aaMode) {
+      this._aaMode = mode;
+      this._taaNum = 0;
+      if (mode === 'taa') { this._taaVecs = taaVectors(9, this.random || Math.random); if (this._ctx) native().taaReset(this._ctx); }
+    }
+    return mode;
+  }
+
+  _jitter () {                                            // taa.js:120-127
+    this._taaNum = (this._taaNum + 1) % 9;
+    const scale = 0.3 / Math.min(this._canvas.width, this._canvas.height);
+    return { x: this._taaVecs[this._taaNum][0] * scale, y: this._taaVecs[this._taaNum][1] * scale };
+  }
+
+  /* One frame, synchronously: scene once, then lights, transforms and atlases as the reference re-derives them every frame
+   * (rasterizerWGL2.js:232, 303-305).  Returns {width, height, rows, radiance: Float32Array(rows*width*4), frameMs, counters?};
+   * radiance holds the RGBA8 drawing buffer's bytes as k / 255 (after an anti-aliasing pass: that pass's output). */
+  renderFrame (options) {
+    const n = native(), c = this._context();
+    if (!this._haveScene) {
+      const built = this.scene.generateArraysFromGraph();
+      n.uploadScene(c, built.geometryBuffer, built.sceneBuffer, built.idBuffer);
+      this._haveScene = true;
+    }
+    this._updateAtlases();
+    n.uploadLights(c, sceneFile.buildLightArray(this.scene));
+    const tr = Transform.buildWGL2Arrays();
+    n.uploadTransforms(c, tr[0], tr[1]);
+    const aa = this._antialiasing();
+    const p = this.frameParams(aa === 'taa' ? this._jitter() : null);
+    const rows = n.tileRowCount(p);
+    let radiance = new Float32Array(rows * p.width * 4);
+    const info = n.rasterRender(c, p, radiance, !!(options && options.counters));
+    if (aa && rows === p.height) {                        // the pass reads neighbouring texels: whole frames only
+      const out = new Float32Array(radiance.length);
+      if (aa === 'fxaa') n.fxaa(c, p.width, p.height, radiance, out);
+      else n.taa(c, p.width, p.height, radiance, out);
+      radiance = out;
+    }
+    this.lastFrame = Object.assign({ width: p.width, height: p.height, rows, radiance }, info);
+    return this.lastFrame;
+  }
+
+  /* the RGBA8 the reference's canvas would hold for a whole frame of renderFrame(): { width, height, data: Uint8ClampedArray } */
+  presentFrame (frame) {
+    const f = frame || this.lastFrame;
+    if (!f || f.rows !== f.height) throw new Error('presentFrame: a whole frame of renderFrame() is needed');
+    const data = new Uint8ClampedArray(f.width * f.height * 4);
+    native().present(this._context(), f.width, f.height, f.radiance, data);
+    return { width: f.width, height: f.height, data };
+  }
+
+  /* The frame loop (rasterizerWGL2.js:201-251): one synchronous frame per tick, `fps` as in :240-245. */
+  async render () {
+    if (!this._halt) return;
+    this._halt = false;
+    await this.updateScene();
+    let frames = 0, windowStart = Date.now();
+    const cycle = () => {
+      if (this._halt) return;
+      try {
+        const frame = this.renderFrame();
+        if (typeof this._canvas.onFrame === 'function') this._canvas.onFrame(frame);
+      } catch (e) {
+        console.error(e);
+        this._halt = true;
+        return;
+      }
+      frames++;
+      const now = Date.now();
+      if (now - windowStart >= 500) {
+        this.fps = (1000 * frames / (now - windowStart)).toFixed(0);
+        frames = 0; windowStart = now;
+      }
+      if (this._halt) return;
+      if (this.fpsLimit === Infinity) setImmediate(cycle);
+      else setTimeout(cycle, 1000 / this.fpsLimit);
+    };
+    setImmediate(cycle);
+  }
+}
+
+module.exports = { RasterizerHIP };

@@ -280,6 +280,39 @@ static napi_value Render(napi_env env, napi_callback_info info) {
   return res;
 }
 
+/* rasterRender(handle, params, out Float32Array(rows*width*4), wantCounters) -> { frameMs, counters? }: the rasterizer renderer
+ * (flx_raster_render), synchronous */
+static napi_value RasterRender(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  flx_frame_params p;
+  if (!read_params(env, argv[1], &p)) return nullptr;
+  void *out; size_t n;
+  if (!typed(env, argv[2], napi_float32_array, &out, &n)) return nullptr;
+  if (!out || n != (size_t)flx_tile_row_count(&p) * p.width * 4) { napi_throw_range_error(env, nullptr, "out needs rows*width*4 floats"); return nullptr; }
+  bool want = false;
+  napi_get_value_bool(env, argv[3], &want);
+  flx_counters c;
+  flx_status rc = flx_raster_render(ctx, &p, (float *)out, nullptr, want ? &c : nullptr);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_raster_render", rc);
+  float frame_ms = 0.f;
+  flx_last_frame_ms(ctx, &frame_ms, nullptr);
+  napi_value res, v;
+  NAPI_OK(env, napi_create_object(env, &res));
+  napi_create_double(env, frame_ms, &v); napi_set_named_property(env, res, "frameMs", v);
+  if (want) {
+    napi_value co;
+    napi_create_object(env, &co);
+    const char *names[8] = { "primaryVisits", "closestVisits", "shadowVisits", "closestWalks", "shadowWalks", "shades", "primaryHits", "atlasTexels" };
+    const uint64_t vals[8] = { c.primary_visits, c.closest_visits, c.shadow_visits, c.closest_walks, c.shadow_walks, c.shades, c.primary_hits, c.atlas_texels };
+    for (int i = 0; i < 8; i++) { napi_create_double(env, (double)vals[i], &v); napi_set_named_property(env, co, names[i], v); }
+    napi_set_named_property(env, res, "counters", co);
+  }
+  return res;
+}
+
 /* renderBatch(handle, [params, ...], out Float32Array, wantCounters) -> { frameMs, counters? }: flx_render_batch, the frames
  * one after the other in `out` */
 static napi_value RenderBatch(napi_env env, napi_callback_info info) {
@@ -947,7 +980,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
     { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas },
-    { "tileRowCount", TileRowCount }, { "render", Render }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
+    { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
     { "meshScale", MeshScale }, { "meshSetMaterial", MeshSetMaterial }, { "meshFlatten", MeshFlatten }, { "meshBounding", MeshBounding }, { "packTransforms", PackTransforms },
     { "present", Present }, { "fxaa", Fxaa }, { "taa", Taa }, { "taaReset", TaaReset },
