@@ -167,10 +167,24 @@ flx_status flx_last_frame_ms(flx_context *ctx, float *frame_ms, float *trace_ker
  * the result into a pinned host buffer the context owns (on a copy stream: the next frame's kernels start meanwhile), and
  * returns.  flx_frame_end waits for the OLDEST frame begun and hands out its pixels and its GPU time.  At most two frames (three with
  * flx_set_frame_lanes(ctx, 3)) are in flight (a set of buffers each): the host prepares and begins frame N + 1 while frame N is traced and copied.  The pixels
- * stay valid until the second flx_frame_begin after the one that made them (or the context's end); rows as flx_render. */
+ * stay valid until the second flx_frame_begin after the one that made them (or the context's end); rows as flx_render.
+ * `format & 0x0f` is one of FLX_FRAME_FLOAT / _RGBA8 / _DEVICE; the flags below may be OR'ed into it (flx_frame_begin only, not
+ * flx_frame_begin_gathered or flx_group_frame_begin):
+ *   FLX_FRAME_FXAA / FLX_FRAME_TAA: the anti-aliasing pass runs over the frame inside the loop — the frame equals flx_render (or
+ *     flx_raster_render) followed by flx_fxaa / flx_taa, and with FLX_FRAME_RGBA8 the pass stores the canvas' bytes itself.  Whole
+ *     frames only (the passes read neighbouring texels), one of the two.  FXAA frames use either lane, each lane its own plane; TAA
+ *     frames rotate the context's ring of flx_taa (advanced when the frame is begun: flx_taa_reset applies to the frames begun after
+ *     it, a change of size resets it) and run on the first lane.
+ *   FLX_FRAME_RASTERIZER: the frame is flx_raster_render's (the path-tracing fields are ignored, tiles as flx_render), uncounted, on
+ *     both lanes.
+ * The frame server (flx_set_frame_chain) takes none of these frames: a running launch is ended first.  Frames of every kind may be
+ * interleaved and complete in the order they were begun. */
 #define FLX_FRAME_FLOAT 0      /* float32 RGBA, what flx_render returns */
 #define FLX_FRAME_RGBA8 1      /* bytes R G B A as the canvas' drawing buffer holds them (flx_present): a quarter of the bytes over PCIe */
 #define FLX_FRAME_DEVICE 2     /* float32 RGBA left in device memory: flx_frame_end hands out a device pointer (no copy to the host) */
+#define FLX_FRAME_FXAA        0x10   /* the FXAA pass (flx_fxaa_device) over the frame, inside the loop */
+#define FLX_FRAME_TAA         0x20   /* the TAA pass (flx_taa_device) over the frame, inside the loop: the context's nine-frame ring */
+#define FLX_FRAME_RASTERIZER  0x100  /* the frame is the rasterizer's (what flx_raster_render draws), not the path tracer's */
 flx_status flx_frame_begin(flx_context *ctx, const flx_frame_params *params, int format);
 flx_status flx_frame_end(flx_context *ctx, const void **pixels, size_t *bytes, float *gpu_ms);
 /* The pinned host buffers behind flx_frame_end's `pixels` (FLX_FRAME_FLOAT / FLX_FRAME_RGBA8): slots[0..1] the first lane's,

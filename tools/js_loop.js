@@ -7,6 +7,8 @@
  *                         [--devices 0,1,..  (a group of GPUs in this process; a number may repeat: rehearsal on one GPU)  --lanes 2|3]
  *                         [--dump PREFIX --dump-frames K]    (the first K frames as PREFIX<k>.f32 + the camera / transforms used, for the parity test)
  *                         [--blocking 1]   (flx_frame_end on the main thread, as before round 5, instead of frameEndAsync on a worker thread)
+ *                         [--renderer rasterizer]   (RasterizerHIP.render(): raster frames in the library's loop; the default is the path tracer)
+ *                         [--aa fxaa|taa]   (config.antialiasing: the pass inside the library's loop)   [--filter 0|1]   (the fixture's setting by default)
  * Prints one JSON line: frames, seconds, fps (wall clock over the loop), the renderer's own fps counter, median GPU ms per frame, and how late a 1 ms
  * timer of the application fires while the loop runs (eventLoopLagMs: the main thread is in the event loop while a worker waits for the GPU).
  */
@@ -33,7 +35,9 @@ engine.scene = replay;
 Object.assign(engine.camera, meta.camera);
 engine.config.samplesPerRay = Number(opt('--spp', meta.frame.samplesPerRay));
 engine.config.maxReflections = Number(opt('--bounces', meta.frame.maxReflections));
-engine.config.filter = !!meta.frame.filter;
+engine.config.filter = opt('--filter', null) === null ? !!meta.frame.filter : Number(opt('--filter', 0)) === 1;
+engine.config.antialiasing = opt('--aa', undefined);
+const rendererName = opt('--renderer', 'pathtracer');
 let faceCamera = () => {};
 if (meta.name === 'dragon') {                              // the two transforms of examples/dragon.js:27-29, 52-54
   const dragonTransform = new Transform(); dragonTransform.move(15, 0, 15); dragonTransform.scale(0.5);
@@ -50,7 +54,7 @@ if (meta.name === 'dragon') {                              // the two transforms
 } else {
   for (let t = 1; t < meta.transforms; t++) new Transform();   // (identity stand-ins: replayed scenes other than the dragon have one transform)
 }
-engine.renderer = 'pathtracer';
+engine.renderer = rendererName;
 engine.renderer.scene = replay;
 engine.renderer.present8 = Number(opt('--present8', 0)) === 1;
 if (devices) engine.renderer.groupLanes = Number(opt('--lanes', 3));
@@ -97,7 +101,7 @@ canvas.onFrame = f => {
     const lagStats = lag.length ? { samples: lag.length, mean: lag.reduce((a, b) => a + b, 0) / lag.length, median: lag[lag.length >> 1], p99: lag[Math.floor(lag.length * 0.99)], max: lag[lag.length - 1] } : null;
     gpuMs.sort((a, b) => a - b);
     if (dumpPrefix) fs.writeFileSync(dumpPrefix + 'log.json', JSON.stringify(log));
-    console.log(JSON.stringify({ scene: meta.name, width: canvas.width, height: canvas.height, spp: engine.config.samplesPerRay, bounces: engine.config.maxReflections,
+    console.log(JSON.stringify({ scene: meta.name, renderer: rendererName, antialiasing: engine.config.antialiasing || null, filter: engine.config.filter, width: canvas.width, height: canvas.height, spp: engine.config.samplesPerRay, bounces: engine.config.maxReflections,
       frames, seconds, fps: frames / seconds, rendererFps: Number(rendererFps), gpuMsMedian: gpuMs[gpuMs.length >> 1], present8: engine.renderer.present8, moving: move, devices: devices ? devices.split(',').map(Number) : null, lanes: devices ? engine.renderer.groupLanes : 2,
       frameEnd: engine.renderer.blockingFrameEnd ? 'blocking' : 'async (worker thread)', eventLoopLagMs: lagStats }));
   }

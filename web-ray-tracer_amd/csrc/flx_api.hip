@@ -1339,14 +1339,20 @@ extern "C" flx_status flx_render(flx_context *ctx, const flx_frame_params *param
   return flx_check_device_error(ctx);
 }
 
+/* flx_raster_render's view of the frame params: the path-tracing fields are not the rasterizer's */
+static flx_frame_params raster_params(const flx_frame_params &p) {
+  flx_frame_params r = p;
+  r.samples = 1; r.max_reflections = 0; r.use_filter = 0; r.is_temporal = 0;
+  return r;
+}
+
 /* The rasterizer renderer: one k_raster launch (flx_raster.hip), timed like a frame (flx_last_frame_ms). */
 extern "C" flx_status flx_raster_render(flx_context *ctx, const flx_frame_params *params, float *out_rgba, void *d_out_rgba, flx_counters *counters) {
   if (!ctx) return FLX_ERR_INVALID;
   if ((out_rgba == nullptr) == (d_out_rgba == nullptr)) return fail(ctx, FLX_ERR_INVALID, "flx_raster_render: exactly one of out_rgba and d_out_rgba must be given");
   if (!params) return fail(ctx, FLX_ERR_INVALID, "frame params are NULL");
   FLX_HIP(ctx, hipSetDevice(ctx->device));
-  flx_frame_params p = *params;
-  p.samples = 1; p.max_reflections = 0; p.use_filter = 0; p.is_temporal = 0;      /* the path-tracing fields are not the rasterizer's */
+  const flx_frame_params p = raster_params(*params);
   DeviceScene sc; DeviceFrame fr;
   flx_status s = flx_make_frame(ctx, &p, sc, fr);
   if (s) return s;
@@ -1712,7 +1718,10 @@ static flx_status server_take(flx_context *ctx, int k) {
 }
 
 constexpr int NOT_GATHERED = -2;      /* frame_begin_on's `gather`: this context's own frame; -1: gathered on every rank; >= 0: on that rank */
-static flx_status frame_begin_on(flx_context *ctx, const flx_frame_params *params, int format, int gather, int *slot, int chained = 0 /* 2: the frame server */) {
+/* what flx_frame_begin's flags ask of a frame (frame_begin parses and checks them) */
+struct FrameKind { bool raster = false; int aa = 0; /* 0 none, FLX_FRAME_FXAA, FLX_FRAME_TAA */ };
+static flx_status frame_begin_on(flx_context *ctx, const flx_frame_params *params, int format, int gather, int *slot, int chained = 0 /* 2: the frame server */,
+                                 FrameKind kind = FrameKind()) {
   FLX_HIP(ctx, hipSetDevice(ctx->device));
   DeviceScene sc; DeviceFrame fr;
   flx_status s = flx_make_frame(ctx, params, sc, fr);
@@ -1762,12 +1771,33 @@ static flx_status frame_begin_on(flx_context *ctx, const flx_frame_params *param
     *slot = k;
     return FLX_OK;
   }
+  /* the anti-aliasing pass's RGBA8 input: this lane's FXAA plane, or the head of the TAA ring (TAA frames run on the first lane, whose ring flx_taa
+   * rotates), advanced here as flx_taa_device does.  (aa_prepare may re-allocate: the frame server has been stopped, frame_begin.) */
+  uint32_t *aa_plane = nullptr;
+  const uint32_t *taa_planes[9] = {};
+  if (kind.aa && pixels) {
+    if ((s = aa_prepare(ctx, fr.width, fr.rows))) return s;
+    if (kind.aa == FLX_FRAME_TAA) {
+      ctx->taa_head = (ctx->taa_head + 8) % 9;
+      if (ctx->taa_filled < 9) ctx->taa_filled++;
+      aa_plane = ctx->d_aa[ctx->taa_head];
+      for (int j = 0; j < 9; j++) taa_planes[j] = j < ctx->taa_filled ? ctx->d_aa[(ctx->taa_head + j) % 9] : nullptr;
+    } else {
+      aa_plane = ctx->d_aa[9];
+    }
+  }
   ctx->slot_dev_ptr[k] = nullptr; ctx->slot_latency_ms[k] = -1.f;
   FLX_HIP(ctx, hipEventRecord(ctx->ev_slot_start[k], ctx->stream));
   if (gathered) {
     /* this rank's strips, the exchange over the lane's communicator and the reassembly, all on the lane's stream */
     if ((s = flx_gather_enqueue(ctx, params, 1, gather, receiver ? ctx->d_slot[k] : nullptr))) return s;
     if (pixels && format == FLX_FRAME_RGBA8) { launch_quantize(ctx->d_slot[k], ctx->d_slot8[k], pixels, ctx->stream); FLX_HIP(ctx, hipGetLastError()); }
+  } else if (pixels && kind.raster) {
+    /* k_raster stores the RGBA8 words itself where bytes are wanted: the pass's texture, or the canvas' bytes of a frame without a pass */
+    if (aa_plane) launch_raster(sc, fr, params->hdr, aa_plane, ctx->stream);
+    else if (format == FLX_FRAME_RGBA8) launch_raster(sc, fr, params->hdr, ctx->d_slot8[k], ctx->stream);
+    else launch_raster(sc, fr, params->hdr, ctx->d_slot[k], nullptr, ctx->stream);
+    FLX_HIP(ctx, hipGetLastError());
   } else if (pixels) {
     if (params->use_filter || params->is_temporal) {
       s = run_post_frame(ctx, sc, fr, params, ctx->d_slot[k]);
@@ -1776,7 +1806,20 @@ static flx_status frame_begin_on(flx_context *ctx, const flx_frame_params *param
       s = flx_run_frame(ctx, sc, fr, ctx->d_slot[k], gb);
     }
     if (s) return s;
-    if (format == FLX_FRAME_RGBA8) { launch_quantize(ctx->d_slot[k], ctx->d_slot8[k], pixels, ctx->stream); FLX_HIP(ctx, hipGetLastError()); }
+    if (aa_plane) { launch_quantize(ctx->d_slot[k], aa_plane, pixels, ctx->stream); FLX_HIP(ctx, hipGetLastError()); }
+    else if (format == FLX_FRAME_RGBA8) { launch_quantize(ctx->d_slot[k], ctx->d_slot8[k], pixels, ctx->stream); FLX_HIP(ctx, hipGetLastError()); }
+  }
+  if (aa_plane) {
+    /* the pass over the texture: the float frame into the slot (its input has been read into the plane), or the canvas' bytes */
+    const int W = (int)fr.width, H = (int)fr.rows;
+    if (kind.aa == FLX_FRAME_FXAA) {
+      if (format == FLX_FRAME_RGBA8) launch_fxaa(aa_plane, ctx->d_slot8[k], W, H, ctx->stream);
+      else launch_fxaa(aa_plane, ctx->d_slot[k], W, H, ctx->stream);
+    } else {
+      if (format == FLX_FRAME_RGBA8) launch_taa(taa_planes, ctx->d_slot8[k], W, H, ctx->stream);
+      else launch_taa(taa_planes, ctx->d_slot[k], W, H, ctx->stream);
+    }
+    FLX_HIP(ctx, hipGetLastError());
   }
   FLX_HIP(ctx, hipEventRecord(ctx->ev_slot_traced[k], ctx->stream));
   if (format == FLX_FRAME_DEVICE) {
@@ -1980,10 +2023,21 @@ extern "C" flx_status flx_set_frame_lanes(flx_context *ctx, int lanes) {
   return FLX_OK;
 }
 
-static flx_status frame_begin(flx_context *ctx, const flx_frame_params *params, int format, int gather) {
+static flx_status frame_begin(flx_context *ctx, const flx_frame_params *params, int format_and_flags, int gather) {
+  const int format = format_and_flags & 0x0f, flags = format_and_flags & ~0x0f;      /* (the format in the low four bits, the flags above them) */
   if (format != FLX_FRAME_FLOAT && format != FLX_FRAME_RGBA8 && format != FLX_FRAME_DEVICE) return fail(ctx, FLX_ERR_INVALID, "flx_frame_begin: format is FLX_FRAME_FLOAT, FLX_FRAME_RGBA8 or FLX_FRAME_DEVICE");
+  if (flags & ~(FLX_FRAME_FXAA | FLX_FRAME_TAA | FLX_FRAME_RASTERIZER)) return fail(ctx, FLX_ERR_INVALID, "flx_frame_begin: unknown flags in format (FLX_FRAME_FXAA, FLX_FRAME_TAA, FLX_FRAME_RASTERIZER)");
+  if ((flags & FLX_FRAME_FXAA) && (flags & FLX_FRAME_TAA)) return fail(ctx, FLX_ERR_INVALID, "flx_frame_begin: FLX_FRAME_FXAA and FLX_FRAME_TAA together (one anti-aliasing pass per frame)");
+  if (flags && gather != NOT_GATHERED) return fail(ctx, FLX_ERR_INVALID, "flx_frame_begin_gathered: takes no flags (anti-aliasing and the rasterizer run on one context: flx_frame_begin)");
   if (ctx->fifo_n >= (ctx->frame_lanes == 3 ? 3 : 2)) return fail(ctx, FLX_ERR_INVALID, ctx->frame_lanes == 3 ? "flx_frame_begin: three frames are in flight already (flx_set_frame_lanes), take one with flx_frame_end first" : "flx_frame_begin: two frames are in flight already, take one with flx_frame_end first");
   if (!params) return fail(ctx, FLX_ERR_INVALID, "frame params are NULL");
+  FrameKind kind;
+  kind.raster = (flags & FLX_FRAME_RASTERIZER) != 0;
+  kind.aa = flags & (FLX_FRAME_FXAA | FLX_FRAME_TAA);
+  if (kind.aa && flx_tile_row_count(params) != params->height)
+    return fail(ctx, FLX_ERR_INVALID, "flx_frame_begin: an anti-aliasing pass reads neighbouring texels: whole frames only (the frame's tile policy gives some of its rows)");
+  flx_frame_params rp;
+  if (kind.raster) { rp = raster_params(*params); params = &rp; }
   if (gather != NOT_GATHERED) {
     if (!ctx->comm) return fail(ctx, FLX_ERR_INVALID, "flx_frame_begin_gathered: the context belongs to no communicator (flx_comm_init_rank)");
     if (params->is_temporal) return fail(ctx, FLX_ERR_INVALID, "flx_frame_begin_gathered: temporal frames keep their history in one context and are not sharded");
@@ -1991,7 +2045,7 @@ static flx_status frame_begin(flx_context *ctx, const flx_frame_params *params, 
   }
   flx_context *lane = ctx;
   int chained = 0;
-  if (gather == NOT_GATHERED) {
+  if (gather == NOT_GATHERED && !kind.raster && !kind.aa) {      /* (the frame server takes neither: a running launch ends below) */
     DeviceScene scT; DeviceFrame frT;
     if (flx_make_frame(ctx, params, scT, frT) == FLX_OK && frT.rows != 0u && chain_wanted(ctx, params, scT, frT)) {
       chained = ctx->frame_chain;
@@ -2012,11 +2066,12 @@ static flx_status frame_begin(flx_context *ctx, const flx_frame_params *params, 
   if (ctx->sv_target_slots && (chained != 2 || format != FLX_FRAME_DEVICE || ctx->sv_target_slots != (ctx->frame_lanes == 3 ? 3u : 2u)))
     return fail(ctx, FLX_ERR_INVALID, "flx_frame_begin: a frame target is set (flx_frame_target_set) — the frame must be one the frame server takes (flx_frame_server_takes), FLX_FRAME_DEVICE, and the target must have as many images as the loop has frames in flight");
   if (chained == 0) ctx->last_chained = 0;
+  const bool first_lane = params->is_temporal || kind.aa == FLX_FRAME_TAA;      /* (the history of temporal frames and the TAA ring live in the first lane) */
   if (chained != 2) { flx_status ss = flx_server_stop(ctx); if (ss) return ss; }      /* (a frame of another kind: the server's launch ends, its frames are resolved) */
   if (chained) {
     /* both frames in flight live in the primary context: make sure nothing of the second lane is (a frame of another kind just before) */
     if (ctx->twin && ctx->fifo_n && ctx->fifo[ctx->fifo_n - 1].lane != ctx) FLX_HIP(ctx, hipStreamSynchronize(ctx->twin->stream));
-  } else if (ctx->frame_lanes >= 2 && !params->is_temporal && (ctx->lane_next & 1u)) {
+  } else if (ctx->frame_lanes >= 2 && !first_lane && (ctx->lane_next & 1u)) {
     FLX_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->twin) {
       flx_status s = flx_context_create(ctx->device, &ctx->twin);
@@ -2037,10 +2092,10 @@ static flx_status frame_begin(flx_context *ctx, const flx_frame_params *params, 
     lane = t;
   }
   int slot = 0;
-  flx_status s = frame_begin_on(lane, params, format, gather, &slot, chained);
+  flx_status s = frame_begin_on(lane, params, format, gather, &slot, chained, kind);
   if (s) { if (lane != ctx) ctx->err = lane->err; return s; }
   ctx->fifo[ctx->fifo_n].lane = lane; ctx->fifo[ctx->fifo_n].slot = slot; ctx->fifo_n++;
-  if (!params->is_temporal) ctx->lane_next++;
+  if (!first_lane) ctx->lane_next++;
   return FLX_OK;
 }
 

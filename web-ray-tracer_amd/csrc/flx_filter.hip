@@ -487,12 +487,17 @@ __global__ __launch_bounds__(256) void k_filter_final(Tex tColor, Tex tIp, Tex t
 __device__ __forceinline__ float fxaa_luma(f4 c) { return (c.y * (0.587f / 0.299f) + c.x) * c.w; }
 __device__ __forceinline__ f4 mix4(f4 a, f4 b, float t) { return F4(flx_mix(a.x, b.x, t), flx_mix(a.y, b.y, t), flx_mix(a.z, b.z, t), flx_mix(a.w, b.w, t)); }
 
-__global__ __launch_bounds__(256) void k_fxaa(Tex t, int W, int H, float4 *__restrict__ out) {
+/* the pass's output texel: the float the shader outputs, or (the frame loop's FLX_FRAME_RGBA8) the canvas' byte store of it */
+__device__ __forceinline__ void aa_store(float4 *dst, float4 v) { *dst = v; }
+__device__ __forceinline__ void aa_store(uint32_t *dst, float4 v) { *dst = pack_rgba8(v.x, v.y, v.z, v.w); }
+
+template <typename OUT>
+__global__ __launch_bounds__(256) void k_fxaa(Tex t, int W, int H, OUT *__restrict__ out) {
   int px, py;
   if (!texel_of_thread(W, H, px, py)) return;
 #define FETCH(dx, dy) fetch(t, W, H, px + (dx), py + (dy))
 #define LUMA(dx, dy) fxaa_luma(FETCH(dx, dy))
-  float4 *dst = out + (size_t)(H - 1 - py) * W + px;
+  OUT *dst = out + (size_t)(H - 1 - py) * W + px;
   const f4 original = FETCH(0, 0);
   float luma[3][3];
 #pragma unroll
@@ -511,7 +516,7 @@ __global__ __launch_bounds__(256) void k_fxaa(Tex t, int W, int H, float4 *__res
     const float c = luma[1][1], n = luma[0][1], w = luma[1][0], s = luma[2][1], e = luma[1][2];
     const float lo = flx_min(c, flx_min(flx_min(n, w), flx_min(s, e))), hi = flx_max(c, flx_max(flx_max(n, w), flx_max(s, e)));
     const float range = hi - lo;
-    if (range < flx_max(1.0f / 32.0f, hi * 1.0f / 2.0f)) { *dst = make_float4(original.x, original.y, original.z, original.w); return; }
+    if (range < flx_max(1.0f / 32.0f, hi * 1.0f / 2.0f)) { aa_store(dst, make_float4(original.x, original.y, original.z, original.w)); return; }
   }
   int nx = -sx, ny = -sy, qx = sx, qy = sy;
   f4 color = original;
@@ -543,13 +548,14 @@ __global__ __launch_bounds__(256) void k_fxaa(Tex t, int W, int H, float4 *__res
     if (!done_n) { done_n = done; nx -= sx; ny -= sy; }
     else { done_p = done; qx += sx; qy += sy; }
   }
-  *dst = make_float4(color.x / pixel_count, color.y / pixel_count, color.z / pixel_count, color.w / pixel_count);
+  aa_store(dst, make_float4(color.x / pixel_count, color.y / pixel_count, color.z / pixel_count, color.w / pixel_count));
 #undef FETCH
 #undef LUMA
 }
 
 struct TaaRing { const uint32_t *p[9]; };          /* newest first; null = not rendered yet (zero texture) */
-__global__ __launch_bounds__(256) void k_taa(TaaRing r, int W, int H, float4 *__restrict__ out) {
+template <typename OUT>
+__global__ __launch_bounds__(256) void k_taa(TaaRing r, int W, int H, OUT *__restrict__ out) {
   int x, y;
   if (!texel_of_thread(W, H, x, y)) return;
   const Tex t0 = { r.p[0] };
@@ -569,21 +575,27 @@ __global__ __launch_bounds__(256) void k_taa(TaaRing r, int W, int H, float4 *__
     const f4 c = fetch(tk, W, H, x, y);
     o = add4(o, F4(flx_min(flx_max(c.x, lo.x), hi.x), flx_min(flx_max(c.y, lo.y), hi.y), flx_min(flx_max(c.z, lo.z), hi.z), flx_min(flx_max(c.w, lo.w), hi.w)));
   }
-  out[(size_t)(H - 1 - y) * W + x] = make_float4(o.x / 9.0f, o.y / 9.0f, o.z / 9.0f, o.w / 9.0f);
+  aa_store(out + (size_t)(H - 1 - y) * W + x, make_float4(o.x / 9.0f, o.y / 9.0f, o.z / 9.0f, o.w / 9.0f));
 }
 
-void launch_fxaa(const uint32_t *plane, float4 *out, int W, int H, hipStream_t stream) {
+template <typename OUT>
+static void fxaa_on(const uint32_t *plane, OUT *out, int W, int H, hipStream_t stream) {
   const dim3 grid(((W + 15) >> 4) * ((H + 15) >> 4)), block(256);
   Tex t = { plane };
-  hipLaunchKernelGGL(k_fxaa, grid, block, 0, stream, t, W, H, out);
+  hipLaunchKernelGGL(k_fxaa<OUT>, grid, block, 0, stream, t, W, H, out);
 }
+void launch_fxaa(const uint32_t *plane, float4 *out, int W, int H, hipStream_t stream) { fxaa_on(plane, out, W, H, stream); }
+void launch_fxaa(const uint32_t *plane, uint32_t *out8, int W, int H, hipStream_t stream) { fxaa_on(plane, out8, W, H, stream); }
 
-void launch_taa(const uint32_t *const planes[9], float4 *out, int W, int H, hipStream_t stream) {
+template <typename OUT>
+static void taa_on(const uint32_t *const planes[9], OUT *out, int W, int H, hipStream_t stream) {
   const dim3 grid(((W + 15) >> 4) * ((H + 15) >> 4)), block(256);
   TaaRing r;
   for (int i = 0; i < 9; i++) r.p[i] = planes[i];
-  hipLaunchKernelGGL(k_taa, grid, block, 0, stream, r, W, H, out);
+  hipLaunchKernelGGL(k_taa<OUT>, grid, block, 0, stream, r, W, H, out);
 }
+void launch_taa(const uint32_t *const planes[9], float4 *out, int W, int H, hipStream_t stream) { taa_on(planes, out, W, H, stream); }
+void launch_taa(const uint32_t *const planes[9], uint32_t *out8, int W, int H, hipStream_t stream) { taa_on(planes, out8, W, H, stream); }
 
 void launch_quantize(const float4 *src, uint32_t *dst, size_t n, hipStream_t stream) {
   hipLaunchKernelGGL(k_quantize, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, src, dst, n);

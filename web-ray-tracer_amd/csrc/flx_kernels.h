@@ -87,6 +87,9 @@ struct FilterPlanes { uint32_t *R[4], *Ip[4], *O[2], *Id[2], *OId; };
 /* anti-aliasing post passes over RGBA8 planes (modules/fxaa.js, modules/taa.js); taa planes newest first, null = zero texture */
 void launch_fxaa(const uint32_t *plane, float4 *out, int W, int H, hipStream_t stream);
 void launch_taa(const uint32_t *const planes[9], float4 *out, int W, int H, hipStream_t stream);
+/* ... storing the canvas' RGBA8 of what they compute (pack_rgba8: flx_present of the float output) */
+void launch_fxaa(const uint32_t *plane, uint32_t *out8, int W, int H, hipStream_t stream);
+void launch_taa(const uint32_t *const planes[9], uint32_t *out8, int W, int H, hipStream_t stream);
 /* float4 plane -> RGBA8 plane (a render-target store) */
 void launch_quantize(const float4 *src, uint32_t *dst, size_t n, hipStream_t stream);
 void launch_angle_tan(const DeviceScene &sc, float4 *out, hipStream_t stream);      /* DeviceScene::angle_tan for the scene as it stands */
@@ -99,6 +102,8 @@ void launch_temporal(const TemporalRings &rings, int W, int H, int hdr, int use_
                      hipStream_t stream);
 /* the rasterizer renderer (flx_raster.hip): one frame of k_raster into float4 out[rows][width] (the RGBA8 drawing buffer's values as float32) */
 void launch_raster(const DeviceScene &sc, const DeviceFrame &fr, int hdr, float4 *out, unsigned long long *counters, hipStream_t stream);
+/* ... into the RGBA8 words k_quantize would store for that frame (uncounted) */
+void launch_raster(const DeviceScene &sc, const DeviceFrame &fr, int hdr, uint32_t *out8, hipStream_t stream);
 void launch_debug_math(int fn, const float *a, const float *b, float *out, uint32_t n, hipStream_t stream);
 void launch_debug_intersect(int fn, const float *in, float *out, uint32_t n, hipStream_t stream);
 bool launch_debug_walk(int variant, const DeviceScene &sc, const float *in, float *out, uint32_t n, hipStream_t stream);      /* false: the scene does not allow that variant */

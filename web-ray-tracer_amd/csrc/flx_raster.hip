@@ -165,8 +165,13 @@ FLX_DEV float4 rasterShade(const DeviceScene &sc, const DeviceFrame &fr, int hdr
  * entries, their order, the arithmetic and the visit count are those of the reference-order walk (tests/raster_ref). */
 /* (256, 4): the register allocation must allow four waves per SIMD — 128 VGPRs, no spill without counters, one VGPR with them; bounded at three
  * waves the compiler takes 131 / 139 VGPRs and the frames measured 1 - 14 % slower (profiles/raster_1080p.txt) */
-template <bool COUNT>
-__global__ __launch_bounds__(256, 4) void k_raster(DeviceScene sc, DeviceFrame fr, int hdr, float4 *__restrict__ out, unsigned long long *__restrict__ counters) {
+/* The pixel's store: OUT = float4, the drawing buffer's values k / 255 as float32 (flx_raster_render); OUT = uint32_t, the RGBA8 word
+ * k_quantize would store for that float4 (the frame loop's canvas bytes and the texture an anti-aliasing pass reads).  Q(k / 255) = k for
+ * every k in 0 .. 255 (tests/test_frame_flags_cpu.py), so the word holds the blend's k themselves. */
+FLX_DEV void rasterStore(float4 *out, size_t i, float4 c) { out[i] = c; }
+FLX_DEV void rasterStore(uint32_t *out, size_t i, float4 c) { out[i] = pack_rgba8(c.x, c.y, c.z, c.w); }
+template <bool COUNT, typename OUT>
+__global__ __launch_bounds__(256, 4) void k_raster(DeviceScene sc, DeviceFrame fr, int hdr, OUT *__restrict__ out, unsigned long long *__restrict__ counters) {
   const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6);
   uint32_t px, k;
   tile8_pixel(fr, tile, threadIdx.x & 63u, px, k);
@@ -263,7 +268,7 @@ __global__ __launch_bounds__(256, 4) void k_raster(DeviceScene sc, DeviceFrame f
   if (COUNT) { cnt.shades += seg.shades; cnt.shadow_walks += seg.shadow_walks; cnt.shadow_visits += seg.shadow_visits; cnt.atlas_texels += seg.atlas_texels; }
   if (inImage) {
     if (COUNT && covered) cnt.primary_hits++;
-    out[(size_t)k * fr.width + px] = color;
+    rasterStore(out, (size_t)k * fr.width + px, color);
   }
   flush_counters<COUNT>(cnt, counters);
 }
@@ -271,8 +276,14 @@ __global__ __launch_bounds__(256, 4) void k_raster(DeviceScene sc, DeviceFrame f
 void launch_raster(const DeviceScene &sc, const DeviceFrame &fr, int hdr, float4 *out, unsigned long long *counters, hipStream_t stream) {
   const uint32_t tiles = ((fr.width + 7u) >> 3) * ((fr.rows + 7u) >> 3);
   const uint32_t blocks = (tiles + 3u) / 4u;
-  if (counters) hipLaunchKernelGGL(k_raster<true>, dim3(blocks), dim3(256), 0, stream, sc, fr, hdr, out, counters);
-  else hipLaunchKernelGGL(k_raster<false>, dim3(blocks), dim3(256), 0, stream, sc, fr, hdr, out, counters);
+  if (counters) hipLaunchKernelGGL((k_raster<true, float4>), dim3(blocks), dim3(256), 0, stream, sc, fr, hdr, out, counters);
+  else hipLaunchKernelGGL((k_raster<false, float4>), dim3(blocks), dim3(256), 0, stream, sc, fr, hdr, out, counters);
+}
+
+void launch_raster(const DeviceScene &sc, const DeviceFrame &fr, int hdr, uint32_t *out8, hipStream_t stream) {
+  const uint32_t tiles = ((fr.width + 7u) >> 3) * ((fr.rows + 7u) >> 3);
+  const uint32_t blocks = (tiles + 3u) / 4u;
+  hipLaunchKernelGGL((k_raster<false, uint32_t>), dim3(blocks), dim3(256), 0, stream, sc, fr, hdr, out8, (unsigned long long *)nullptr);
 }
 
 }  // namespace flx

@@ -36,6 +36,9 @@ EXPORTS = [
 
 
 SHARE_HANDLE_BYTES = 128      # FLX_SHARE_HANDLE_BYTES
+FRAME_FXAA = 0x10              # FLX_FRAME_FXAA: flags of flx_frame_begin's format
+FRAME_TAA = 0x20               # FLX_FRAME_TAA
+FRAME_RASTERIZER = 0x100       # FLX_FRAME_RASTERIZER
 MAX_BATCH_FRAMES = 32          # FLX_MAX_BATCH_FRAMES of include/flexlight_hip.h
 
 
@@ -435,8 +438,13 @@ class Context:
         self._check(LIB.flx_last_chained(self._h, C.byref(v)), "flx_last_chained")
         return v.value
 
-    def frame_begin(self, params, rgba8=False, device=False):
-        self._check(LIB.flx_frame_begin(self._h, C.byref(params), 2 if device else (1 if rgba8 else 0)), "flx_frame_begin")
+    def frame_begin(self, params, rgba8=False, device=False, rasterizer=False, antialiasing=None):
+        """rasterizer: flx_raster_render's frame instead of the path tracer's; antialiasing: None, 'fxaa' or 'taa' (the pass inside the loop)"""
+        if antialiasing not in (None, "fxaa", "taa"):
+            raise ValueError("antialiasing is None, 'fxaa' or 'taa'")
+        fmt = 2 if device else (1 if rgba8 else 0)
+        fmt |= (FRAME_RASTERIZER if rasterizer else 0) | {None: 0, "fxaa": FRAME_FXAA, "taa": FRAME_TAA}[antialiasing]
+        self._check(LIB.flx_frame_begin(self._h, C.byref(params), fmt), "flx_frame_begin")
         self._pending.append((self.tile_row_count(params), params.width, rgba8, device))
 
     def frame_end(self):

@@ -262,7 +262,8 @@ class PathTracerHIP {
    * taken (flx_frame_end) and handed to canvas.onFrame — `pixels` is a view of that pinned memory (Float32Array, or the canvas'
    * RGBA8 as a Uint8ClampedArray with this.present8), valid until the frame after the next is begun.  A group of GPUs (`devices`) runs the
    * same loop through flx_group_frame_begin / _end with up to this.groupLanes (3) frames in flight, `pixels` valid until the next frame is begun.
-   * Anti-aliasing passes and tiles take the synchronous renderFrame() per cycle instead.  `fps` as in pathtracerWGL2.js:293-298;
+   * One context runs the anti-aliasing pass inside the library's loop too (frameBegin's { antialiasing }: FLX_FRAME_FXAA / FLX_FRAME_TAA, the TAA
+   * jitter drawn per frame as renderFrame() draws it); tiles, and a group with a pass, take the synchronous renderFrame() per cycle instead.  `fps` as in pathtracerWGL2.js:293-298;
    * `gpuMs` = GPU time of the last frame taken. */
   async render () {
     if (!this._halt) return;                              // already running (the WebGPU renderer guards the same way)
@@ -307,7 +308,7 @@ class PathTracerHIP {
         /* a group of GPUs (flx_group_frame_begin / _end): every GPU's frame server resolves its strips straight into one image in pinned host memory, up to
          * three frames in flight, nothing waits for a GPU inside a frame; `pixels` is a view of that image, the frame's until the next frame is begun */
         const grouped = !!this._devices && !this._tile && !aa;      // (present8: the servers quantise their tiles as they resolve them — the canvas' bytes, a quarter of what every GPU writes)
-        const pipelined = !this._devices && !this._tile && !aa;
+        const pipelined = !this._devices && !this._tile;
         if (grouped) {
           this._uploadFrameState();
           const p = this.frameParams();
@@ -325,8 +326,9 @@ class PathTracerHIP {
           this._temporalFrame = (this._temporalFrame + 1) % Math.max(1, this.config.temporalSamples);
         } else if (pipelined) {
           this._uploadFrameState();
-          const p = this.frameParams();
-          native().frameBegin(this._context(), p, this.present8);
+          const p = aa ? this.frameParams(aa === 'taa' ? this._jitter() : { x: 0, y: 0 }) : this.frameParams();      // (the camera renderFrame() gives the pass)
+          if (aa) native().frameBegin(this._context(), p, this.present8, { antialiasing: aa });
+          else native().frameBegin(this._context(), p, this.present8);
           this._inFlight++;
           pending.push({ width: p.width, height: p.height, rows: p.height, rgba8: this.present8 });
           this._temporalFrame = (this._temporalFrame + 1) % Math.max(1, this.config.temporalSamples);

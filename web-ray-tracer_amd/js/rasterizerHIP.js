@@ -4,9 +4,9 @@
  * libflexlight_hip.so (flx_raster_render, k_raster) instead of by WebGL2.  Same surface as the reference's object:
  * type = 'rasterizer', public config / camera / scene, fps, fpsLimit, canvas getter, async render(), halt(),
  * async updateScene(), async updatePrimaryLightSources() — plus renderFrame(), a synchronous single frame for headless use,
- * and presentFrame() as PathTracerHIP has them.  One GPU context (no groups of GPUs, no frame loop in the library).
- * A raster frame is short, so the loop calls the synchronous binding once per tick: no native work is ever pending between
- * ticks, and updateScene() / updatePrimaryLightSources() may run at any time.
+ * and presentFrame() as PathTracerHIP has them.  One GPU context (no groups of GPUs).  render() runs the library's frame loop
+ * (flx_frame_begin with FLX_FRAME_RASTERIZER) and takes every frame with the blocking frameEnd: no native work is ever pending
+ * between ticks, and updateScene() / updatePrimaryLightSources() may run at any time.
  * The "canvas" is any object with width and height; if it has onFrame(frame) the loop calls it.
  */
 const { Transform } = require('./scene.js');
@@ -24,7 +24,9 @@ class RasterizerHIP {
     this._canvas = canvas;
     this._device = (options && options.device) || 0;
     this._tile = (options && options.tile) || null;      // {rows, index, count}: this context's strips of the frame
+    this.present8 = !!(options && options.present8);     // the frame loop hands out the canvas' RGBA8 instead of the float frame
     this._ctx = null;
+    this._pending = [];                                  // the frame loop's frames begun and not yet taken
     this._halt = true;
     this._atlasLists = [null, null, null];
     this._haveScene = false;
@@ -46,6 +48,7 @@ class RasterizerHIP {
     }
     this._haveScene = false;
     this._atlasLists = [null, null, null];
+    this._pending = [];                                  // (frames in flight: the library waits for them as the context goes)
   }
 
   async updateScene () {                                  // rasterizerWGL2.js:150-190
@@ -117,7 +120,7 @@ class RasterizerHIP {
   /* One frame, synchronously: scene once, then lights, transforms and atlases as the reference re-derives them every frame
    * (rasterizerWGL2.js:232, 303-305).  Returns {width, height, rows, radiance: Float32Array(rows*width*4), frameMs, counters?};
    * radiance holds the RGBA8 drawing buffer's bytes as k / 255 (after an anti-aliasing pass: that pass's output). */
-  renderFrame (options) {
+  _uploadFrameState () {
     const n = native(), c = this._context();
     if (!this._haveScene) {
       const built = this.scene.generateArraysFromGraph();
@@ -128,6 +131,11 @@ class RasterizerHIP {
     n.uploadLights(c, sceneFile.buildLightArray(this.scene));
     const tr = Transform.buildWGL2Arrays();
     n.uploadTransforms(c, tr[0], tr[1]);
+  }
+
+  renderFrame (options) {
+    const n = native(), c = this._context();
+    this._uploadFrameState();
     const aa = this._antialiasing();
     const p = this.frameParams(aa === 'taa' ? this._jitter() : null);
     const rows = n.tileRowCount(p);
@@ -152,27 +160,47 @@ class RasterizerHIP {
     return { width: f.width, height: f.height, data };
   }
 
-  /* The frame loop (rasterizerWGL2.js:201-251): one synchronous frame per tick, `fps` as in :240-245. */
+  /* The frame loop (rasterizerWGL2.js:201-251) in the library's loop (flx_frame_begin with FLX_FRAME_RASTERIZER, and FLX_FRAME_FXAA /
+   * FLX_FRAME_TAA for config.antialiasing on whole frames): every tick enqueues a frame (frameBegin) and, with two in flight, takes the older one
+   * with the blocking frameEnd and hands it to canvas.onFrame as { width, height, rows, radiance | rgba8, pixels, frameMs }.  `pixels` is a view
+   * of pinned memory (a Float32Array of the drawing buffer's k / 255, or the canvas' RGBA8 as a Uint8ClampedArray with this.present8), valid
+   * until the frame after the next one is begun.  `fps` as in :240-245. */
   async render () {
     if (!this._halt) return;
     this._halt = false;
     await this.updateScene();
     let frames = 0, windowStart = Date.now();
-    const cycle = () => {
-      if (this._halt) return;
-      try {
-        const frame = this.renderFrame();
-        if (typeof this._canvas.onFrame === 'function') this._canvas.onFrame(frame);
-      } catch (e) {
-        console.error(e);
-        this._halt = true;
-        return;
-      }
+    this._pending = [];
+    const take = () => {
+      const q = this._pending.shift();
+      const r = native().frameEnd(this._ctx, q.rgba8);
+      const frame = { width: q.width, height: q.height, rows: q.rows, radiance: q.rgba8 ? undefined : r.pixels, rgba8: q.rgba8 ? r.pixels : undefined,
+        pixels: r.pixels, frameMs: r.gpuMs };
+      this.lastFrame = frame;
+      if (typeof this._canvas.onFrame === 'function') this._canvas.onFrame(frame);
       frames++;
       const now = Date.now();
       if (now - windowStart >= 500) {
         this.fps = (1000 * frames / (now - windowStart)).toFixed(0);
         frames = 0; windowStart = now;
+      }
+    };
+    const cycle = () => {
+      if (this._halt) return;
+      try {
+        this._uploadFrameState();
+        const aa = this._antialiasing();
+        const p = this.frameParams(aa === 'taa' ? this._jitter() : null);
+        const rows = native().tileRowCount(p);
+        const opts = { renderer: 'rasterizer' };
+        if (aa && rows === p.height) opts.antialiasing = aa;      // the pass reads neighbouring texels: whole frames only
+        native().frameBegin(this._ctx, p, this.present8, opts);
+        this._pending.push({ width: p.width, height: p.height, rows, rgba8: this.present8 });
+        if (this._pending.length === 2) take();
+      } catch (e) {
+        console.error(e);
+        this._halt = true;
+        return;
       }
       if (this._halt) return;
       if (this.fpsLimit === Infinity) setImmediate(cycle);

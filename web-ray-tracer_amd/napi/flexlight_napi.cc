@@ -568,14 +568,37 @@ static napi_value PackTransforms(napi_env env, napi_callback_info info) {
 }
 
 
-/* ---- the frame loop: frameBegin(handle, params, rgba8) / frameEnd(handle) -> { pixels, gpuMs } ---------------------------
+/* ---- the frame loop: frameBegin(handle, params, rgba8[, { renderer, antialiasing }]) / frameEnd(handle) -> { pixels, gpuMs } ---------------------------
+ * The optional fourth argument: renderer 'rasterizer' (flx_raster_render's frame; anything else: the path tracer's), antialiasing 'fxaa' | 'taa' (the pass
+ * inside the loop: FLX_FRAME_FXAA / FLX_FRAME_TAA; anything else: none).
  * `pixels` is a typed array over the context's pinned host buffer (no copy).  It belongs to that frame until the library re-uses
  * or frees the buffer — the frameBegin that will copy a newer frame into it (with two lanes: the fourth after the one that made
  * it; with one lane the second), a frameBegin that re-allocates it for a larger frame, or halt() — at which point the addon
  * DETACHES it: `pixels.length` becomes 0 instead of the array showing another frame or freed memory. */
+static int frame_flags(napi_env env, napi_value opts, bool &ok) {
+  ok = true;
+  napi_valuetype t;
+  napi_typeof(env, opts, &t);
+  if (t == napi_undefined || t == napi_null) return 0;
+  if (t != napi_object) { napi_throw_type_error(env, nullptr, "frameBegin: the fourth argument is { renderer, antialiasing }"); ok = false; return 0; }
+  int flags = 0;
+  napi_value v;
+  std::string text;
+  bool present = false;
+  if (napi_get_named_property(env, opts, "renderer", &v) != napi_ok || !get_text(env, v, text, present)) { ok = false; return 0; }
+  if (present && text == "rasterizer") flags |= FLX_FRAME_RASTERIZER;
+  if (napi_get_named_property(env, opts, "antialiasing", &v) != napi_ok || !get_text(env, v, text, present)) { ok = false; return 0; }
+  if (present && text == "fxaa") flags |= FLX_FRAME_FXAA;
+  else if (present && text == "taa") flags |= FLX_FRAME_TAA;
+  return flags;
+}
 static napi_value FrameBegin(napi_env env, napi_callback_info info) {
-  napi_value argv[3];
-  if (!get_args(env, info, 3, argv)) return nullptr;
+  napi_value argv[4];
+  size_t argc = 4;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 3) {
+    napi_throw_type_error(env, nullptr, "wrong number of arguments");
+    return nullptr;
+  }
   CtxBox *box = get_box(env, argv[0]);
   if (!box) return nullptr;
   flx_context *ctx = box->ctx;
@@ -583,7 +606,10 @@ static napi_value FrameBegin(napi_env env, napi_callback_info info) {
   if (!read_params(env, argv[1], &p)) return nullptr;
   bool rgba8 = false;
   napi_get_value_bool(env, argv[2], &rgba8);
-  flx_status rc = flx_frame_begin(ctx, &p, rgba8 ? FLX_FRAME_RGBA8 : FLX_FRAME_FLOAT);
+  bool ok = true;
+  const int flags = argc > 3 ? frame_flags(env, argv[3], ok) : 0;
+  if (!ok) return nullptr;
+  flx_status rc = flx_frame_begin(ctx, &p, (rgba8 ? FLX_FRAME_RGBA8 : FLX_FRAME_FLOAT) | flags);
   /* a larger frame (canvas or renderQuality changed) made the library re-allocate a pinned slot: the views over the old one go
    * (no JavaScript has run since the free — this is one native call) */
   const void *slots[4] = { nullptr, nullptr, nullptr, nullptr };
