@@ -120,6 +120,14 @@ flx_status flx_debug_intersect(flx_context *ctx, int fn, const float *in, float 
  * out: 8 floats each: s, u, v, 2 x transform number and entry index of the closest hit (zeros and -1 for none), entries that walk fetched, shadowTest's
  * answer (0 / 1), entries the shadow walk fetched. */
 flx_status flx_debug_walk(flx_context *ctx, int variant, const float *rays, float *out, uint32_t n);
+/* Variant 0 of flx_debug_walk with the threaded entries [0, min(lds_count, walk_hot)) staged in LDS as the wavefront walk kernels stage the tree's top, every other
+ * entry fetched from global memory (walkFetchP, walkSetupRays).  out: 10 floats per ray: flx_debug_walk's 8, then the entries both walks fetched from LDS and
+ * the entries they fetched from global memory.  FLX_ERR_INVALID when the staged entries, the transforms and the rays need more than the kernel's 160 KB of LDS. */
+flx_status flx_debug_walk_staged(flx_context *ctx, uint32_t lds_count, const float *rays, float *out, uint32_t n);
+/* out[0 .. 3]: the last wavefront frame or frame server launch since the scene upload (zeros if none): the ldsCount (entries of the tree's top staged in LDS) it
+ * launched with, whether its rays were pre-transformed (0 / 1), which launch (1 rounds, 2 the frame kernel, 3 the frame kernel with the front inside, 4 the frame
+ * server), n_transforms; out[4 .. 6]: the uploaded scene's walk_hot, walk_entries and fwd_entries (the size the lockstep copy is judged by). */
+flx_status flx_debug_last_walk_lds(flx_context *ctx, uint32_t out[7]);
 /* Scheduler statistics of the last counted frame (wavefront pipeline): for bounce b = 0..3 (3 = all
  * later ones) out[2b] = wave-iterations of the walk kernel, out[2b+1] = fold/refill batches. */
 flx_status flx_get_diag(flx_context *ctx, uint64_t out[32]);   /* out[8..12]: bounce-0 walk kernel stamps: fold, refill, step cycles, wave lifetime, waves; out[16+3b..]: per bounce sum / count / max of wave lifetimes */

@@ -114,6 +114,11 @@ def make(seed=0, n_objects=3, tris_per_object=40, n_transforms=3, n_lights=2, te
             g = geo[1].copy(); g[[1, 4, 7]] -= 0.01 * (len(geo) % 7 + 1)
             geo.append(g); att.append(att[1].copy())
         geo[0][6] = len(geo) - 1
+    return _package(rng, seed, geo, att, rotation, shift, n_transforms, n_lights, n_tex, width, height, samples, bounces, axis_aligned_view)
+
+
+def _package(rng, seed, geo, att, rotation, shift, n_transforms, n_lights, n_tex, width, height, samples, bounces, axis_aligned_view):
+    """flattened entries, transforms -> Scene: padding to a multiple of 256, lights, atlases, camera"""
     entries = len(geo)
     padded = ((entries + 255) // 256) * 256
     geometry = np.zeros((padded, 12), np.float32)
@@ -150,3 +155,92 @@ def make(seed=0, n_objects=3, tris_per_object=40, n_transforms=3, n_lights=2, te
         "atlasAlbedo": aa, "atlasPbr": ap, "atlasTpo": at,
     }
     return Scene(meta, arrays)
+
+
+def _count_entries(n, leaf=4):
+    """entries (_flatten) of _bvh over n triangles: one box per group, one entry per triangle"""
+    return 1 + n if n <= leaf else 1 + _count_entries(n // 2, leaf) + _count_entries(n - n // 2, leaf)
+
+
+def _leaves(node):
+    kids = node[2]
+    if all(k[0] == "tri" for k in kids):
+        return [node]
+    return [leaf for k in kids if k[0] == "group" for leaf in _leaves(k)]
+
+
+def _small_transform(rng):
+    """a turn of at most 0.3 rad about a random axis, a scale near 1, a short shift: an object space whose triangles still land in view"""
+    axis = rng.normal(size=3)
+    axis /= np.linalg.norm(axis)
+    a = rng.uniform(-0.3, 0.3)
+    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    m = (np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * K @ K) * rng.choice([0.8, 1.0, 1.25])
+    return m, rng.uniform(-1, 1, 3)
+
+
+def make_sized(entries, n_transforms, seed=0, n_lights=2, width=64, height=48, samples=2, bounces=3):
+    """A scene of exactly `entries` non-terminator entries (a root box, two floor triangles, one BVH per object), so that the threaded copy's walk_hot
+    is min(entries, 4096) + 1 and its walk_entries and fwd_entries are entries + 1.  Small triangles fill the view at every depth from z = 0 to z = 20 (world
+    space; each object's vertices are taken into its own object space), so that camera rays cross several of them and walk deep into the tree.  Object o
+    stands in transform o % n_transforms; every transform has at least one object."""
+    rng = np.random.default_rng(seed)
+    n_objects = max(n_transforms, 2)
+    fixed = 3                                                       # root box, two floor triangles
+    if entries < fixed + 2 * n_objects:
+        raise ValueError("make_sized: at least %d entries for %d objects" % (fixed + 2 * n_objects, n_objects))
+    rotation = np.zeros((n_transforms, 24), np.float32)
+    shift = np.zeros((n_transforms, 8), np.float32)
+    spaces = []
+    for t in range(n_transforms):
+        m, pos = (np.eye(3), np.zeros(3)) if t == 0 else _small_transform(rng)      # transform 0 is the identity (scene.js:590-593)
+        inv = np.linalg.inv(m)
+        for r in range(3):
+            rotation[t, 4 * r:4 * r + 3] = m[r]
+            rotation[t, 12 + 4 * r:12 + 4 * r + 3] = inv[r]
+        shift[t, 0:3] = pos
+        shift[t, 4:7] = -pos
+        spaces.append((inv, pos))
+    rest = entries - fixed
+    budgets = [rest // n_objects + (1 if o < rest % n_objects else 0) for o in range(n_objects)]
+    n_tris = sum(budgets) - n_objects                               # a generous bound of the triangles all objects take
+    size = float(np.sqrt(1000.0 / max(n_tris, 1)))                 # ~2 triangles across a camera ray's way through the volume
+
+    def triangle(transform):
+        centre = np.array([rng.uniform(-9, 9), rng.uniform(-7, 7), rng.uniform(0, 20)])
+        v = centre + rng.normal(scale=0.5 * size, size=(3, 3))
+        inv, pos = spaces[transform]
+        local = (v - pos) @ inv.T                                   # world = m @ local + pos
+        n = np.cross(v[0] - v[2], v[0] - v[1])
+        n = n / (np.linalg.norm(n) + 1e-30)
+        attrs = np.zeros(28, np.float32)
+        attrs[0:9] = np.tile(n, 3)
+        attrs[15:18] = -1
+        attrs[18:21] = rng.uniform(0.2, 1.0, 3)
+        attrs[21:24] = [rng.uniform(0, 1), rng.uniform(0, 1), 0]
+        attrs[24:27] = [rng.choice([0, 0, 1.0]), 0, rng.uniform(1.0, 1.8)]
+        return ("tri", transform, local.reshape(-1), attrs)
+
+    objects = []
+    for o, budget in enumerate(budgets):
+        transform = o % n_transforms
+        n = 1
+        while _count_entries(n + 1) <= budget:
+            n += 1
+        node = _bvh([triangle(transform) for _ in range(n)], transform, rng)
+        leaves = _leaves(node)
+        for k in range(budget - _count_entries(n)):                 # one entry each, into the leaves in turn
+            leaves[k % len(leaves)][2].append(triangle(transform))
+        objects.append(node)
+    floor = []
+    for quad in ([[-30, -8, -5], [30, -8, -5], [30, -8, 40]], [[30, -8, 40], [-30, -8, 40], [-30, -8, -5]]):
+        attrs = np.zeros(28, np.float32)
+        attrs[0:9] = np.tile([0, 1, 0], 3)
+        attrs[15:18] = -1
+        attrs[18:24] = [0.8, 0.8, 0.8, 1, 0, 0]
+        attrs[24:27] = [0, 0, 1]
+        floor.append(("tri", 0, np.array(quad, np.float64).reshape(-1), attrs))
+    geo, att = [], []
+    _flatten(("group", 0, floor + objects), geo, att, None)
+    assert len(geo) == entries, (len(geo), entries)
+    return _package(rng, seed, geo, att, rotation, shift, n_transforms, n_lights, 0, width, height, samples, bounces, False)

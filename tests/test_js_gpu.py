@@ -207,23 +207,29 @@ def test_group_presents_rgba8_through_node(hip, oracle, scenes, tmp_path):
         assert np.array_equal(got, want), "frame %d" % k
 
 
-def test_the_frame_loop_leaves_the_main_thread_in_the_event_loop(tmp_path):
+def test_the_frame_loop_leaves_the_main_thread_in_the_event_loop_alternating(tmp_path):
     """SURVEY 8b ("a napi_async_work worker for the non-blocking variant") / pathtracerWGL2.js:300-302 (the reference's loop returns to the event loop every frame):
     PathTracerHIP.render() waits for a frame on a worker thread (frameEndAsync), so an application timer of 1 ms fires on time while whole 1080p frames (6.4 ms each) are
-    traced; with the blocking flx_frame_end of round 4 the same timer is late by most of a frame.  Frames are the same bytes either way."""
+    traced; with the blocking flx_frame_end of round 4 the same timer is late by most of a frame.  Frames are the same bytes either way.
+    The two loops run three times each, one after the other in turn: the GPU time of a 1080p frame moves by a fifth from run to run where other work shares the device,
+    so the frame rates are compared best against best; every run's timer must hold."""
     node = shutil.which("node")
     assert node
-    out = {}
-    for mode in ("0", "1"):
-        prefix = str(tmp_path / ("lag%s_" % mode))
-        cmd = [node, os.path.join(ROOT, "tools", "js_loop.js"), os.path.join(ROOT, "tests", "golden", "ref_dragon.flxs.gz"), "--frames", "40", "--move", "1",
-               "--blocking", mode, "--dump", prefix, "--dump-frames", "3"]
-        out[mode] = json.loads(subprocess.check_output(cmd, timeout=600).decode().splitlines()[-1])
-    a, b = out["0"], out["1"]
-    assert a["frameEnd"].startswith("async") and b["frameEnd"] == "blocking"
-    assert a["eventLoopLagMs"]["samples"] > 40 and a["eventLoopLagMs"]["median"] < 1.0, a["eventLoopLagMs"]
-    assert b["eventLoopLagMs"]["median"] > 2.0 * max(a["eventLoopLagMs"]["median"], 0.25), (a["eventLoopLagMs"], b["eventLoopLagMs"])      # the blocking loop holds the thread for the frame
-    assert a["fps"] > 0.9 * b["fps"], (a["fps"], b["fps"])                                         # ... and the worker thread costs the loop next to nothing
+    runs = {"0": [], "1": []}
+    for rep in range(3):
+        for mode in ("0", "1"):
+            prefix = str(tmp_path / ("lag%s_" % mode))
+            cmd = [node, os.path.join(ROOT, "tools", "js_loop.js"), os.path.join(ROOT, "tests", "golden", "ref_dragon.flxs.gz"), "--frames", "40", "--move", "1",
+                   "--blocking", mode] + (["--dump", prefix, "--dump-frames", "3"] if rep == 0 else [])
+            runs[mode].append(json.loads(subprocess.check_output(cmd, timeout=600).decode().splitlines()[-1]))
+    assert all(a["frameEnd"].startswith("async") for a in runs["0"]) and all(b["frameEnd"] == "blocking" for b in runs["1"])
+    for a in runs["0"]:
+        assert a["eventLoopLagMs"]["samples"] > 40 and a["eventLoopLagMs"]["median"] < 1.0, a["eventLoopLagMs"]
+    worst_async_lag = max(a["eventLoopLagMs"]["median"] for a in runs["0"])
+    for b in runs["1"]:
+        assert b["eventLoopLagMs"]["median"] > 2.0 * max(worst_async_lag, 0.25), (worst_async_lag, b["eventLoopLagMs"])   # the blocking loop holds the thread for the frame
+    fa, fb = max(a["fps"] for a in runs["0"]), max(b["fps"] for b in runs["1"])
+    assert fa > 0.9 * fb, ([a["fps"] for a in runs["0"]], [b["fps"] for b in runs["1"]])              # ... and the worker thread costs the loop next to nothing
     for k in range(3):
         fa = np.fromfile(str(tmp_path / ("lag0_%d.f32" % k)), np.float32)
         fb = np.fromfile(str(tmp_path / ("lag1_%d.f32" % k)), np.float32)

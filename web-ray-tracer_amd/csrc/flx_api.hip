@@ -350,6 +350,7 @@ extern "C" flx_status flx_scene_upload(flx_context *ctx, const float *geometry, 
   flx_status s;
   if ((s = shared_upload_begin(ctx))) return s;
   ctx->have_scene = false;
+  ctx->last_walk_lds = WalkLdsLaunch();
   ctx->geometry_version++;
   if ((s = upload(ctx, &ctx->d_geometry, geometry, (size_t)n_entries_padded * 48))) return s;
   if ((s = upload(ctx, &ctx->d_attributes, attributes, (size_t)n_entries_padded * 112))) return s;
@@ -813,11 +814,13 @@ flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFr
        * CU until they end, and the other lane's RCCL kernel — a handful of workgroups that carry the finished frame's strips — would wait
        * behind them for a whole frame.  Such a context leaves a few CUs to the exchange. */
       const uint32_t cusWalk = (ctx->comm && (ctx->twin || ctx->is_twin) && cus > 4u * FLX_COMM_RESERVED_CUS) ? cus - FLX_COMM_RESERVED_CUS : cus;
-      const int ran = launch_wavefront(sc, fr, wb, cusWalk, cnt != nullptr, organisationNow, g == 0 ? ctx->ev_k0 : nullptr, g == 0 ? ctx->ev_k1 : nullptr, st);
+      WalkLdsLaunch lds;
+      const int ran = launch_wavefront(sc, fr, wb, cusWalk, cnt != nullptr, organisationNow, g == 0 ? ctx->ev_k0 : nullptr, g == 0 ? ctx->ev_k1 : nullptr, st, &lds);
       FLX_HIP(ctx, hipGetLastError());
       if (ran == -2) return fail(ctx, FLX_ERR_DEVICE, "the walk kernels need 156 KB of dynamic LDS and hipFuncSetAttribute refused it on this device");
       if (ran < 0) return fail(ctx, FLX_ERR_DEVICE, "internal: the frame kernel was to trace the primary rays but does not take this frame");
       ctx->last_organisation = ran;
+      ctx->last_walk_lds = lds;
       if (g > 0) {
         FLX_HIP(ctx, hipEventRecord(ctx->ev_join[g - 1], st));
         FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join[g - 1], 0));
@@ -1055,6 +1058,14 @@ extern "C" flx_status flx_debug_last_trace_kernel(flx_context *ctx, int *samples
   *samples_side_by_side = ctx->last_trace.samples;
   *lockstep = ctx->last_trace.lockstep;
   *counted = ctx->last_trace.counted;
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_debug_last_walk_lds(flx_context *ctx, uint32_t out[7]) {
+  if (!ctx || !out) return FLX_ERR_INVALID;
+  const WalkLdsLaunch &l = ctx->last_walk_lds;
+  out[0] = l.ldsCount; out[1] = l.pre; out[2] = l.kind; out[3] = l.nTransforms;
+  out[4] = ctx->walk_hot; out[5] = ctx->walk_entries; out[6] = ctx->fwd_entries;
   return FLX_OK;
 }
 
@@ -1651,7 +1662,7 @@ static flx_status server_post(flx_context *ctx, const flx_frame_params *params, 
       scL.shift = (const float4 *)(ctx->d_sv_versions + versions * ctx->n_transforms * 24u);
       scL.lights = (const float *)(ctx->d_sv_versions + versions * ctx->n_transforms * 32u);
     }
-    if (launch_server(scL, fr, wb, sa, cusWalk, ctx->sv_stream) != 0) return fail(ctx, FLX_ERR_DEVICE, "internal: the frame server does not take this scene");
+    if (launch_server(scL, fr, wb, sa, cusWalk, ctx->sv_stream, &ctx->last_walk_lds) != 0) return fail(ctx, FLX_ERR_DEVICE, "internal: the frame server does not take this scene");
     FLX_HIP(ctx, hipGetLastError());
     ctx->sv_running = true; ctx->sv_depth = depth; ctx->sv_next_seq = seq0; ctx->sv_next_slot = slot0;
     ctx->sv_params = *params; ctx->sv_scene_version = ctx->scene_version; ctx->sv_out8 = out8;
@@ -2291,6 +2302,29 @@ extern "C" flx_status flx_debug_walk(flx_context *ctx, int variant, const float 
     FLX_HIP(ctx, hipMemcpy(out, d_out.p, (size_t)n * 8 * 4, hipMemcpyDeviceToHost));
   }
   return ok ? FLX_OK : fail(ctx, FLX_ERR_INVALID, "flx_debug_walk: this scene does not have that walk (variant 2 needs the lockstep copy: at most 128 entries in one object space)");
+}
+
+extern "C" flx_status flx_debug_walk_staged(flx_context *ctx, uint32_t lds_count, const float *rays, float *out, uint32_t n) {
+  if (!ctx || !rays || !out) return FLX_ERR_INVALID;
+  if (n == 0) return FLX_OK;
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  flx_frame_params p;
+  memset(&p, 0, sizeof p);
+  p.width = p.height = 8; p.samples = 1; p.max_reflections = 1; p.texture_width = 1;
+  DeviceScene sc; DeviceFrame fr;
+  flx_status st = flx_make_frame(ctx, &p, sc, fr);
+  if (st != FLX_OK) return st;
+  const uint32_t staged = lds_count < sc.walk_hot ? lds_count : sc.walk_hot;
+  DeviceScratch d_in, d_out;                               /* freed on every way out */
+  FLX_HIP(ctx, hipMalloc(&d_in.p, (size_t)n * 7 * 4));
+  FLX_HIP(ctx, hipMalloc(&d_out.p, (size_t)n * 10 * 4));
+  FLX_HIP(ctx, hipMemcpy(d_in.p, rays, (size_t)n * 7 * 4, hipMemcpyHostToDevice));
+  if (!launch_debug_walk_staged(sc, staged, (const float *)d_in.p, (float *)d_out.p, n, ctx->stream))
+    return fail(ctx, FLX_ERR_INVALID, "flx_debug_walk_staged: the staged entries, the transforms and the rays need more LDS than the kernel may have (160 KB)");
+  FLX_HIP(ctx, hipGetLastError());
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  FLX_HIP(ctx, hipMemcpy(out, d_out.p, (size_t)n * 10 * 4, hipMemcpyDeviceToHost));
+  return FLX_OK;
 }
 
 extern "C" flx_status flx_device_info(flx_context *ctx, char *name, uint32_t name_len, uint32_t *compute_units) {

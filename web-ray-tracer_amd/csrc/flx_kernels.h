@@ -79,8 +79,11 @@ size_t wavefront_live_capacity(const DeviceFrame &fr, uint32_t compute_units);
 bool wavefront_front_in_kernel(const DeviceScene &sc, const DeviceFrame &fr, uint32_t item_count, int organisation);
 /* -> what ran: 1 rounds, 2 the frame kernel, 3 the frame kernel with the front of the frame inside it; -1: wb.front set but the frame kernel cannot run; -2: the walk
  * kernels' dynamic LDS limit could not be raised on this device */
+/* What a walk launch staged of the tree's top (flx_debug_last_walk_lds): the ldsCount it was given, whether its rays are pre-transformed, and which launch it was
+ * (1 rounds, 2 the frame kernel, 3 the frame kernel with the front inside, 4 the frame server) */
+struct WalkLdsLaunch { uint32_t ldsCount = 0, pre = 0, kind = 0, nTransforms = 0; };
 int launch_wavefront(const DeviceScene &sc, const DeviceFrame &fr, const WavefrontBuffers &wb, uint32_t compute_units, bool count,
-                     int organisation, hipEvent_t walk0_begin, hipEvent_t walk0_end, hipStream_t stream);
+                     int organisation, hipEvent_t walk0_begin, hipEvent_t walk0_end, hipStream_t stream, WalkLdsLaunch *ran = nullptr);
 /* denoise chain (flx_filter.hip): 13 RGBA8 planes = the reference's RenderTexture[0..3], IpRenderTexture[0..3],
  * OriginalRenderTexture[0..1], IdRenderTexture[0..1], OriginalIdRenderTexture (pathtracerWGL2.js:224-252). */
 struct FilterPlanes { uint32_t *R[4], *Ip[4], *O[2], *Id[2], *OId; };
@@ -107,6 +110,9 @@ void launch_raster(const DeviceScene &sc, const DeviceFrame &fr, int hdr, uint32
 void launch_debug_math(int fn, const float *a, const float *b, float *out, uint32_t n, hipStream_t stream);
 void launch_debug_intersect(int fn, const float *in, float *out, uint32_t n, hipStream_t stream);
 bool launch_debug_walk(int variant, const DeviceScene &sc, const float *in, float *out, uint32_t n, hipStream_t stream);      /* false: the scene does not allow that variant */
+/* variant 0 of launch_debug_walk with the threaded entries [0, ldsCount) staged in LDS (ldsCount <= walk_hot); out: 10 floats per ray.  false: the LDS it needs is more than
+ * the kernel may have */
+bool launch_debug_walk_staged(const DeviceScene &sc, uint32_t ldsCount, const float *in, float *out, uint32_t n, hipStream_t stream);
 
 }  // namespace flx
 #endif

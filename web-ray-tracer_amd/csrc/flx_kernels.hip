@@ -14,6 +14,8 @@
 #include "flx_kernels.h"
 #include "flx_kernel_util.h"
 
+#include <mutex>
+
 #ifndef FLX_PRIMARY_FWD
 #define FLX_PRIMARY_FWD 1                  /* primary rays: the wave steps through the forward-ordered copy together (primaryWalkF; k_primary 0.424 -> 0.391 ms) */
 #endif
@@ -795,6 +797,73 @@ __global__ __launch_bounds__(64) void k_debug_walk(DeviceScene sc, const float *
   o[0] = hit.triangleId != -1 ? hit.suv.x : 0.0f; o[1] = hit.triangleId != -1 ? hit.suv.y : 0.0f; o[2] = hit.triangleId != -1 ? hit.suv.z : 0.0f;
   o[3] = (float)(hit.triangleId != -1 ? hit.transformId : 0); o[4] = (float)hit.triangleId;
   o[5] = (float)cnt.closest_visits; o[6] = shadowed ? 1.0f : 0.0f; o[7] = (float)cnt.shadow_visits;
+}
+
+/* ---- diagnostics: variant 0 with the tree's top in LDS (flx_debug_walk_staged) ---------------------------------------------------------------------
+ * LDS: [entries 0 .. ldsCount - 1 of the threaded copy, 3 float4 each][T x 4 float4 of staged transforms][64 lanes x T x 40 B of pre-transformed rays], the
+ * layout of the rounds walk kernel.  out: 10 floats per ray, k_debug_walk's 8, then the entries both walks fetched from LDS and those they fetched from the
+ * global copy — told apart here, from the link, before every walkFetchP. */
+__global__ __launch_bounds__(64) void k_debug_walk_staged(DeviceScene sc, uint32_t ldsCount, const float *__restrict__ in, float *__restrict__ out, uint32_t n) {
+  extern __shared__ float4 ldsDebug[];
+  const uint32_t lane = threadIdx.x, i = blockIdx.x * 64u + lane;
+  const bool have = i < n;
+  const float *r = in + (size_t)(have ? i : 0u) * 7u;
+  Ray ray; ray.origin = F3(r[0], r[1], r[2]); ray.dir = F3(r[3], r[4], r[5]);
+  const float l = r[6];
+  const uint32_t T = sc.n_transforms;
+  float4 *ldsEntries = ldsDebug;
+  float4 *ldsXf = ldsDebug + (size_t)ldsCount * 3u;
+  float2 *myRays = (float2 *)(ldsXf + (size_t)T * 4u) + (size_t)lane * T * 5u;
+  for (uint32_t t = lane; t < ldsCount * 3u; t += 64u) ldsEntries[t] = sc.walk[t];
+  for (uint32_t t = lane; t < T * 4u; t += 64u) {
+    const uint32_t tr = t >> 2, k = t & 3u, iI = 2u * tr + 1u;
+    ldsXf[t] = k < 3u ? sc.rotation[3u * iI + k] : sc.shift[iI];
+  }
+  __syncthreads();
+  WorkCounters cnt = {};
+  uint32_t fromLds = 0u, fromGlobal = 0u;
+  Hit hit; hit.suv = F3(0.0f, 0.0f, 0.0f); hit.transformId = 0; hit.triangleId = -1;
+  bool shadowed = false;
+  for (int mode = 0; mode < 2; mode++) {                     /* the shadow walk, then the closest-hit walk, as k_debug_walk<0> */
+    const bool shadowMode = mode == 0;
+    WalkState w;
+    walkClearResults(w);
+    w.src = ray; w.mode = mode;
+    WalkEntry cur; cur.e0 = cur.e1 = cur.e2 = make_float4(0.f, 0.f, 0.f, 0.f);
+    walkSetupRays(sc, T, ldsXf, myRays, ray, shadowMode);
+    w.tR = ray; w.cachedTI = 0; w.minLen = shadowMode ? l : POW32; w.i = (int)sc.walk_root;
+    reciprocalOfDir(sc, ray.dir, ray.origin, w.inv, w.fastDiv);
+    bool ended = !have;
+    while (true) {
+      if (!ended && linkKind((uint32_t)w.i) != 3u) { if (linkIndex((uint32_t)w.i) < ldsCount) fromLds++; else fromGlobal++; }      /* (the loop bound: no fetch) */
+      if (!ended) ended = walkFetchP<true>(sc, ldsEntries, ldsCount, myRays, w, cur, cnt);
+      if (ended) break;
+      if (walkIsBoxT(cur)) walkBoxP(w, cur); else ended = walkTriT(w, cur);
+      if (ended) break;
+    }
+    if (shadowMode) shadowed = w.shadowed != 0;
+    else { hit.suv = w.suv; hit.transformId = w.hitTI; hit.triangleId = w.tri; }
+  }
+  if (!have) return;
+  float *o = out + (size_t)i * 10u;
+  o[0] = hit.triangleId != -1 ? hit.suv.x : 0.0f; o[1] = hit.triangleId != -1 ? hit.suv.y : 0.0f; o[2] = hit.triangleId != -1 ? hit.suv.z : 0.0f;
+  o[3] = (float)(hit.triangleId != -1 ? hit.transformId : 0); o[4] = (float)hit.triangleId;
+  o[5] = (float)cnt.closest_visits; o[6] = shadowed ? 1.0f : 0.0f; o[7] = (float)cnt.shadow_visits;
+  o[8] = (float)fromLds; o[9] = (float)fromGlobal;
+}
+
+bool launch_debug_walk_staged(const DeviceScene &sc, uint32_t ldsCount, const float *in, float *out, uint32_t n, hipStream_t stream) {
+  const size_t lds = (size_t)ldsCount * 48u + (size_t)sc.n_transforms * 4u * sizeof(float4) + 64u * (size_t)sc.n_transforms * 40u;
+  const size_t limit = 160u * 1024u;                          /* what set_lds_limit (flx_wavefront.hip) allows the walk kernels */
+  if (ldsCount > sc.walk_hot || lds > limit) return false;
+  static std::once_flag once[64];
+  static bool ok[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+  std::call_once(once[dev], [&]() { ok[dev] = hipFuncSetAttribute((const void *)k_debug_walk_staged, hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit) == hipSuccess; });
+  if (!ok[dev]) return false;
+  hipLaunchKernelGGL(k_debug_walk_staged, dim3((n + 63u) / 64u), dim3(64), lds, stream, sc, ldsCount, in, out, n);
+  return true;
 }
 
 bool launch_debug_walk(int variant, const DeviceScene &sc, const float *in, float *out, uint32_t n, hipStream_t stream) {

@@ -60,7 +60,8 @@ struct ServerKernelArgs { FrameArgs fa; ServerArgs sa; };
 bool server_kernel_fits(const DeviceScene &sc, uint32_t &ldsCount, uint32_t &ldsBytes, uint32_t xfSlots = 1u /* depth for a scene that moves */, uint32_t shadeWaves = 0u /* 0: the default of three slots */);
 size_t server_rings_per_group();
 /* fr: the slots stacked (frames = depth); its views are NOT used (they come through the mailbox).  0, or -1 if the kernel does not fit */
-int launch_server(const DeviceScene &sc, const DeviceFrame &fr, const WavefrontBuffers &wb, const ServerArgs &sa, uint32_t compute_units, hipStream_t stream);
+int launch_server(const DeviceScene &sc, const DeviceFrame &fr, const WavefrontBuffers &wb, const ServerArgs &sa, uint32_t compute_units, hipStream_t stream,
+                  WalkLdsLaunch *ran = nullptr);
 
 }  // namespace flx
 #endif

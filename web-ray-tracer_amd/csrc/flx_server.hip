@@ -528,7 +528,8 @@ bool server_kernel_fits(const DeviceScene &sc, uint32_t &ldsCount, uint32_t &lds
 
 size_t server_rings_per_group() { return (size_t)SV_RINGS * FQ_SIZE; }
 
-int launch_server(const DeviceScene &sc, const DeviceFrame &fr, const WavefrontBuffers &wb, const ServerArgs &sa, uint32_t compute_units, hipStream_t stream) {
+int launch_server(const DeviceScene &sc, const DeviceFrame &fr, const WavefrontBuffers &wb, const ServerArgs &sa, uint32_t compute_units, hipStream_t stream,
+                  WalkLdsLaunch *ran) {
   uint32_t ldsCount = 0, ldsBytes = 0;
   const bool ver = sa.blobWords != 0u;                         /* the scene moves: its lights and transforms come with every frame */
   if (sa.depth < 2u || sa.depth > SV_MAX_DEPTH) return -1;
@@ -550,6 +551,7 @@ int launch_server(const DeviceScene &sc, const DeviceFrame &fr, const WavefrontB
   readyUnits = readyUnits < (uint32_t)FLX_FRAME_READY_UNITS / 4u ? (uint32_t)FLX_FRAME_READY_UNITS / 4u : (readyUnits > (uint32_t)FLX_FRAME_READY_UNITS ? (uint32_t)FLX_FRAME_READY_UNITS : readyUnits);
   if (ver) hipLaunchKernelGGL(k_wf_server<true>, dim3(compute_units), dim3(FLX_WF_WALK_THREADS), ldsBytes, stream, ka, ldsCount, sc.n_transforms, shadeWaves, readyUnits);
   else hipLaunchKernelGGL(k_wf_server<false>, dim3(compute_units), dim3(FLX_WF_WALK_THREADS), ldsBytes, stream, ka, ldsCount, sc.n_transforms, shadeWaves, readyUnits);
+  if (ran) { ran->ldsCount = ldsCount; ran->pre = 1u; ran->kind = 4u; ran->nTransforms = sc.n_transforms; }
   return 0;
 }
 

@@ -1226,7 +1226,7 @@ bool wavefront_front_in_kernel(const DeviceScene &sc, const DeviceFrame &fr, uin
 }
 
 int launch_wavefront(const DeviceScene &sc, const DeviceFrame &fr, const WavefrontBuffers &wbIn, uint32_t compute_units, bool count,
-                     int organisation, hipEvent_t walk0_begin, hipEvent_t walk0_end, hipStream_t stream) {
+                     int organisation, hipEvent_t walk0_begin, hipEvent_t walk0_end, hipStream_t stream, WalkLdsLaunch *ran) {
   WavefrontBuffers wb = wbIn;
   const bool fused = wb.front == 2u;                        /* no hits yet: primary rays and bounce-0 shading in one launch (k_wf_front) in front of whatever walks */
   if (fused) wb.front = 0u;
@@ -1271,6 +1271,7 @@ int launch_wavefront(const DeviceScene &sc, const DeviceFrame &fr, const Wavefro
         else hipLaunchKernelGGL((k_wf_frame<false, false>), grid, block, ldsBytesF, stream, fa, total, ldsCountF, sc.n_transforms, shadeWaves, readyUnits);
       }
       if (walk0_end) (void)hipEventRecord(walk0_end, stream);
+      if (ran) { ran->ldsCount = ldsCountF; ran->pre = 1u; ran->kind = wb.front ? 3u : 2u; ran->nTransforms = sc.n_transforms; }
       return wb.front ? 3 : 2;
     }
   }
@@ -1326,6 +1327,7 @@ int launch_wavefront(const DeviceScene &sc, const DeviceFrame &fr, const Wavefro
     }
     if (r == 0 && walk0_end) (void)hipEventRecord(walk0_end, stream);
   }
+  if (ran) { ran->ldsCount = ldsCount; ran->pre = pre ? 1u : 0u; ran->kind = 1u; ran->nTransforms = T; }
   return 1;
 }
 

@@ -30,7 +30,7 @@ EXPORTS = [
     "flx_frame_server_takes", "flx_frame_target_set", "flx_frame_target_index", "flx_debug_set_server_groups",
     "flx_share_create", "flx_share_join", "flx_share_leave", "flx_frame_begin_shared", "flx_frame_end_shared",
     "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_sample_parallel", "flx_debug_last_trace_kernel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
-    "flx_raster_render",
+    "flx_raster_render", "flx_debug_walk_staged", "flx_debug_last_walk_lds",
 ]
 
 
@@ -158,6 +158,8 @@ def _load():
         "flx_share_leave": (C.c_int, [vp]),
         "flx_debug_set_sample_parallel": (C.c_int, [vp, C.c_int]),
         "flx_debug_last_trace_kernel": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "flx_debug_walk_staged": (C.c_int, [vp, u32, C.POINTER(C.c_float), C.POINTER(C.c_float), u32]),
+        "flx_debug_last_walk_lds": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_debug_set_adaptive_order": (C.c_int, [vp, C.c_int]),
         "flx_debug_tile_order_of": (C.c_int, [vp, C.POINTER(C.c_float), u32, C.c_int, C.POINTER(u32)]),
         "flx_debug_set_tile_order": (C.c_int, [vp, C.POINTER(u32), u32]),
@@ -507,6 +509,21 @@ class Context:
         out = np.zeros((rays.shape[0], 8), np.float32)
         self._check(LIB.flx_debug_walk(self._h, int(variant), _fp(rays), _fp(out), rays.shape[0]), "flx_debug_walk")
         return out
+
+    def debug_walk_staged(self, lds_count, rays):
+        """flx_debug_walk_staged: flx_debug_walk's variant 0 with the threaded entries [0, min(lds_count, walk_hot)) in LDS; rays [n, 7] float32 -> [n, 10]
+        float32: debug_walk's 8 columns, then the entries both walks fetched from LDS and from global memory"""
+        rays = np.ascontiguousarray(rays, np.float32)
+        out = np.zeros((rays.shape[0], 10), np.float32)
+        self._check(LIB.flx_debug_walk_staged(self._h, int(lds_count), _fp(rays), _fp(out), rays.shape[0]), "flx_debug_walk_staged")
+        return out
+
+    def last_walk_lds(self):
+        """flx_debug_last_walk_lds -> dict: what the last wavefront frame or frame server launch staged (lds_count, pre, kind: 1 rounds, 2 frame kernel, 3 frame
+        kernel with the front inside, 4 server; n_transforms; zeros when none ran since the scene upload) and the scene's walk_hot, walk_entries, fwd_entries"""
+        out = (C.c_uint32 * 7)()
+        self._check(LIB.flx_debug_last_walk_lds(self._h, out), "flx_debug_last_walk_lds")
+        return dict(zip(("lds_count", "pre", "kind", "n_transforms", "walk_hot", "walk_entries", "fwd_entries"), list(out)))
 
     def last_pipeline(self):
         v = C.c_int()
