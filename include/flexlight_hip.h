@@ -129,7 +129,10 @@ flx_status flx_render(flx_context *ctx, const flx_frame_params *params, float *o
 /* Temporal frames (is_temporal = 1) keep config.temporalSamples frames of history in the context, like the
  * reference's TempTexture rings (pathtracerWGL2.js:389-402,419-460): every call rotates the ring, traces with
  * params->random_seed (the caller passes frame % temporalSamples, pathtracerWGL2.js:291,347) and averages the
- * history where the packed ids match.  flx_temporal_reset forgets the history (a resize does the same). */
+ * history where the packed ids match.  flx_temporal_reset forgets the history (a resize does the same).  A temporal frame
+ * without the filter may be tiled (params->tile_*): the pass is per pixel, and the context keeps the history of exactly the
+ * rows it traces — a change of temporalSamples, size or tile policy starts a fresh history, and a context given no rows does
+ * nothing.  Filter frames are whole frames (the denoise chain reads neighbouring pixels; tiled ones are refused). */
 flx_status flx_temporal_reset(flx_context *ctx);
 /* Same, output left in DEVICE memory (d_out_rgba is a device pointer on the context's GPU, e.g. a
  * torch tensor's data_ptr) and enqueued on the context's stream without a host sync: for the
@@ -167,7 +170,9 @@ flx_status flx_last_frame_ms(flx_context *ctx, float *frame_ms, float *trace_ker
  * the result into a pinned host buffer the context owns (on a copy stream: the next frame's kernels start meanwhile), and
  * returns.  flx_frame_end waits for the OLDEST frame begun and hands out its pixels and its GPU time.  At most two frames (three with
  * flx_set_frame_lanes(ctx, 3)) are in flight (a set of buffers each): the host prepares and begins frame N + 1 while frame N is traced and copied.  The pixels
- * stay valid until the second flx_frame_begin after the one that made them (or the context's end); rows as flx_render.
+ * stay valid until the second flx_frame_begin after the one that made them (or the context's end); rows and tiles as flx_render: a temporal frame
+ * may be tiled without the filter (the history of the context's own rows), a filter frame is whole.  Temporal frames run on the first lane, where the
+ * history lives.
  * `format & 0x0f` is one of FLX_FRAME_FLOAT / _RGBA8 / _DEVICE; the flags below may be OR'ed into it (flx_frame_begin only, not
  * flx_frame_begin_gathered or flx_group_frame_begin):
  *   FLX_FRAME_FXAA / FLX_FRAME_TAA: the anti-aliasing pass runs over the frame inside the loop — the frame equals flx_render (or
@@ -228,7 +233,6 @@ flx_status flx_frame_target_set(flx_context *ctx, void *const *d_images, uint32_
 /* ... images of the canvas' RGBA8 — uint8[height][width][4], the bytes flx_present stores: the launch quantises its tiles as it resolves them (a quarter of the bytes
  * every GPU of a group writes).  Without a target the server does the same for frames begun as FLX_FRAME_RGBA8. */
 flx_status flx_frame_target_set8(flx_context *ctx, void *const *d_images, uint32_t n_images);
-int flx_frame_target_index(const flx_context *ctx);      /* which of the images the frame begun last goes to (-1: none) */
 /* Device faults reach the status code.  The frame kernels' wait loops have watchdogs (seconds); a wave that gives up — or finds a ring slot that never
  * fills — sets a bit in the context's device error word (pinned host memory), and the next call in which the host waits for frames (flx_render,
  * flx_render_batch, flx_frame_end, flx_sync) returns FLX_ERR_DEVICE with the bits in flx_last_error and clears the word: the frame is incomplete.  A healthy
@@ -251,8 +255,9 @@ flx_status flx_filter_planes_device(flx_context *ctx, const flx_frame_params *pa
  * replicated on every GPU, and ONE exchange step per frame (or batch of frames) brings the strips together: ncclAllGather
  * (RCCL over xGMI) of the packed strips on the contexts' streams, then a kernel of the library puts the gathered rows in
  * image order.  With use_filter the five RGBA8 render targets are gathered instead (5 x 8.3 MB at 1080p) and the denoise
- * chain, which reads up to ~194 rows around a pixel, runs on the whole frame.  Temporal frames keep their history in one
- * context and are not sharded.  The reference has one WebGL2 context per renderer (pathtracerWGL2.js:60-68); this is what
+ * chain, which reads up to ~194 rows around a pixel, runs on the whole frame.  Temporal frames go through a group's frame loop
+ * only (flx_group_frame_begin), where every context keeps the history of its own strips; the stateless and batch entry points
+ * below refuse them.  The reference has one WebGL2 context per renderer (pathtracerWGL2.js:60-68); this is what
  * `new FlexLight(canvas, { devices: N })` of the JavaScript host layer sits on. */
 
 /* One process per GPU (bench.py under torch.distributed.run).  Rank 0 makes an id (ncclGetUniqueId) and hands it to the other
@@ -336,13 +341,18 @@ flx_status flx_group_render_rgba8(flx_group *group, const flx_frame_params *para
  * (FLX_FRAME_DEVICE) — so a frame needs no exchange, no reassembly and no copy.
  * flx_group_frame_end waits for the oldest frame's completion words (no stream is synchronised) and hands the image out: float4[height][width], valid until
  * `lanes` more frames have been begun; ms: the slowest context's time from the post to its word, on the host's clock.  Up to `lanes` frames (2 or 3,
- * default 3) are in flight; frames complete in order and equal flx_render's bit for bit.  Frames the server does not take (filter and temporal frames,
- * scenes of <= 128 entries, strips that are no multiple of 8 rows) are rendered by flx_group_render inside flx_group_frame_begin and handed out by the
- * matching flx_group_frame_end. */
+ * default 3) are in flight; frames complete in order and equal flx_render's bit for bit.  Float frames the server does not take (temporal frames, scenes
+ * of <= 128 entries, strips that are no multiple of 8 rows) are begun on every context's two lanes and their strips copied into the image by the matching
+ * flx_group_frame_end; filter frames, and the canvas' bytes of frames the server does not take, are rendered as flx_group_render does inside
+ * flx_group_frame_begin.  Temporal frames (not FLX_FRAME_DEVICE): every context keeps the history of its own strips (flx_temporal_reset), so a sequence equals
+ * the same sequence on one context frame by frame, and with the filter the five render targets after the temporal pass are exchanged and the chain runs on
+ * context 0.  The history starts again where it does on one context, and also where tile_rows changes.  flx_group_temporal_reset: flx_temporal_reset on
+ * every context. */
 flx_status flx_group_frame_begin(flx_group *group, const flx_frame_params *params, uint32_t tile_rows, int format);
 flx_status flx_group_frame_end(flx_group *group, const void **pixels, size_t *bytes, float *ms);
 int flx_group_frames_in_flight(const flx_group *group);
 flx_status flx_group_set_frame_lanes(flx_group *group, int lanes);
+flx_status flx_group_temporal_reset(flx_group *group);
 
 /* Anti-aliasing post passes: config.antialiasing = 'fxaa' | 'taa' of the reference (modules/fxaa.js:7-137,
  * modules/taa.js:11-59).  Both read the RGBA8 texture the renderer drew into — the frame is stored as the reference stores it,

@@ -33,6 +33,8 @@ int flx_server_moving(const flx_context *ctx);
 
 /* Would flx_frame_begin hand this frame to the frame server (under flx_set_frame_chain(ctx, 3): whatever its size)?  1 / 0. */
 int flx_frame_server_takes(flx_context *ctx, const flx_frame_params *params);
+/* Which of the images of flx_frame_target_set the frame begun last goes to (-1: none). */
+int flx_frame_target_index(const flx_context *ctx);
 
 /* Device faults reach the status code.  The frame kernels' wait loops have watchdogs (seconds); a wave that gives up — or finds a ring slot that never
  * fills — sets a bit in the context's device error word (pinned host memory), and the next call in which the host waits for frames (flx_render,

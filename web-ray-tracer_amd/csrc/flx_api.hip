@@ -840,38 +840,34 @@ flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFr
   return FLX_OK;
 }
 
+static flx_status ensure_post_buffers(flx_context *ctx, size_t pixels, bool gbuffers, bool planes);
+
 /* Frames with a post pass (temporal accumulation and / or the denoise chain): trace with the per-pixel kernel
- * into float G-buffers, store them to RGBA8 planes like the reference's render targets, run the passes. */
-static flx_status run_post_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFrame &fr, const flx_frame_params *p, float4 *d_out) {
-  if (fr.rows != fr.height)
-    return fail(ctx, FLX_ERR_INVALID, "temporal / filter frames cannot be tiled: they read neighbouring pixels and history (render the whole frame on one context)");
-  const size_t pixels = (size_t)fr.rows * fr.width;
+ * into float G-buffers, store them to RGBA8 planes like the reference's render targets, run the passes.
+ * Temporal frames may be tiled: the pass reads its own pixel of every history slot only, and the context keeps the history of
+ * the rows it traces (the ring is keyed by the frame's tile policy).  The denoise chain reads neighbouring pixels: a filter frame
+ * is whole, except where planes_out takes the five render targets of a temporal filter frame's strips after the temporal pass
+ * (uint32[5][rows][width], flx_temporal_planes_enqueue) — the chain then runs on the gathered whole frame. */
+static flx_status run_post_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFrame &fr, const flx_frame_params *p, float4 *d_out, uint32_t *planes_out = nullptr) {
   const bool temporal = fr.is_temporal == 1, filter = fr.use_filter == 1;
+  if (fr.rows != fr.height && (!temporal || (filter && !planes_out)))
+    return fail(ctx, FLX_ERR_INVALID, "filter frames cannot be tiled: the denoise chain reads neighbouring pixels (render the whole frame on one context)");
+  const size_t pixels = (size_t)fr.rows * fr.width;
   flx_status s;
-  if (ctx->gb_capacity < pixels) {
-    ctx->gb_capacity = 0;                 /* a failed allocation below must not leave the old size standing */
-    for (int i = 0; i < 6; i++) {
-      size_t cap = 0;
-      if (ctx->d_gb[i]) { FLX_HIP(ctx, hipFree(ctx->d_gb[i])); ctx->d_gb[i] = nullptr; }
-      if ((s = flx_ensure_pixels(ctx, &ctx->d_gb[i], &cap, pixels))) return s;
-    }
-    ctx->gb_capacity = pixels;
+  if ((s = ensure_post_buffers(ctx, pixels, true, filter && !planes_out))) return s;
+  FilterPlanes pl = {};
+  if (planes_out) {
+    pl.R[0] = planes_out; pl.Ip[0] = planes_out + pixels; pl.O[0] = planes_out + 2 * pixels; pl.Id[0] = planes_out + 3 * pixels; pl.OId = planes_out + 4 * pixels;
+  } else if (filter) {
+    for (int i = 0; i < 4; i++) { pl.R[i] = ctx->d_planes[i]; pl.Ip[i] = ctx->d_planes[4 + i]; }
+    pl.O[0] = ctx->d_planes[8]; pl.O[1] = ctx->d_planes[9]; pl.Id[0] = ctx->d_planes[10]; pl.Id[1] = ctx->d_planes[11]; pl.OId = ctx->d_planes[12];
   }
-  if (ctx->planes_capacity < pixels) {
-    ctx->planes_capacity = 0;                 /* a failed allocation below must not leave the old size standing */
-    for (int i = 0; i < 13; i++) {
-      if (ctx->d_planes[i]) { FLX_HIP(ctx, hipFree(ctx->d_planes[i])); ctx->d_planes[i] = nullptr; }
-      FLX_HIP(ctx, hipMalloc(&ctx->d_planes[i], pixels * sizeof(uint32_t)));
-    }
-    ctx->planes_capacity = pixels;
-  }
-  FilterPlanes pl;
-  for (int i = 0; i < 4; i++) { pl.R[i] = ctx->d_planes[i]; pl.Ip[i] = ctx->d_planes[4 + i]; }
-  pl.O[0] = ctx->d_planes[8]; pl.O[1] = ctx->d_planes[9]; pl.Id[0] = ctx->d_planes[10]; pl.Id[1] = ctx->d_planes[11]; pl.OId = ctx->d_planes[12];
   int N = 1;
   if (temporal) {
     N = p->temporal_samples <= 0 ? 4 : (p->temporal_samples > 16 ? 16 : p->temporal_samples);
-    if (ctx->ring_n != N || ctx->ring_w != fr.width || ctx->ring_h != fr.height) {      /* new size: fresh (zero) history, like a resize */
+    /* another depth, size or tile policy: fresh (zero) history, like a resize */
+    if (ctx->ring_n != N || ctx->ring_w != fr.width || ctx->ring_h != fr.height ||
+        ctx->ring_tile_rows != fr.tile_rows || ctx->ring_tile_index != fr.tile_index || ctx->ring_tile_count != fr.tile_count) {
       ctx->ring_n = 0;                     /* (re)allocation in progress: a failure below leaves no size to match */
       for (auto &ring : ctx->d_ring) for (uint32_t *&plane : ring) if (plane) { FLX_HIP(ctx, hipFree(plane)); plane = nullptr; }
       for (int r = 0; r < 4; r++) for (int i = 0; i < N; i++) {
@@ -879,6 +875,7 @@ static flx_status run_post_frame(flx_context *ctx, const DeviceScene &sc, const 
         FLX_HIP(ctx, hipMemsetAsync(ctx->d_ring[r][i], 0, pixels * sizeof(uint32_t), ctx->stream));
       }
       ctx->ring_n = N; ctx->ring_head = 0; ctx->ring_w = fr.width; ctx->ring_h = fr.height;
+      ctx->ring_tile_rows = fr.tile_rows; ctx->ring_tile_index = fr.tile_index; ctx->ring_tile_count = fr.tile_count;
     }
   }
   GBufferPtrs gb = { ctx->d_gb[0], ctx->d_gb[1], ctx->d_gb[2], ctx->d_gb[3], ctx->d_gb[4], ctx->d_gb[5] };
@@ -895,30 +892,28 @@ static flx_status run_post_frame(flx_context *ctx, const DeviceScene &sc, const 
     return FLX_OK;
   }
   if ((s = flx_run_frame(ctx, sc, fr, nullptr, gb))) return s;
-  launch_quantize(gb.color, pl.R[0], pixels, ctx->stream);
-  launch_quantize(gb.color_ip, pl.Ip[0], pixels, ctx->stream);
   if (temporal) {
+    /* one pass: the ring head's planes, the average over the history, the frame (or, with the filter, the render targets the chain reads) */
     ctx->ring_head = (ctx->ring_head + N - 1) % N;                  /* TempTexture.unshift(TempTexture.pop()) */
-    TemporalRings rings;
-    rings.n = N;
+    TemporalPass t = {};
+    t.color = gb.color; t.color_ip = gb.color_ip; t.location_id = gb.location_id; t.original_id = gb.original_id; t.original_color = gb.original_color; t.id = gb.id;
     for (int k = 0; k < 16; k++) {
       const int slot = (ctx->ring_head + k) % N;
-      rings.c[k] = k < N ? ctx->d_ring[0][slot] : nullptr; rings.ip[k] = k < N ? ctx->d_ring[1][slot] : nullptr;
-      rings.id[k] = k < N ? ctx->d_ring[2][slot] : nullptr; rings.oid[k] = k < N ? ctx->d_ring[3][slot] : nullptr;
+      t.ring_c[k] = k < N ? ctx->d_ring[0][slot] : nullptr; t.ring_ip[k] = k < N ? ctx->d_ring[1][slot] : nullptr;
+      t.ring_id[k] = k < N ? ctx->d_ring[2][slot] : nullptr; t.ring_oid[k] = k < N ? ctx->d_ring[3][slot] : nullptr;
     }
-    const int h0 = ctx->ring_head;
-    FLX_HIP(ctx, hipMemcpyAsync(ctx->d_ring[0][h0], pl.R[0], pixels * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    FLX_HIP(ctx, hipMemcpyAsync(ctx->d_ring[1][h0], pl.Ip[0], pixels * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    launch_quantize(gb.location_id, ctx->d_ring[2][h0], pixels, ctx->stream);
-    launch_quantize(gb.original_id, ctx->d_ring[3][h0], pixels, ctx->stream);
-    launch_temporal(rings, (int)fr.width, (int)fr.height, p->hdr, filter ? 1 : 0, pl.R[0], pl.Ip[0], d_out, ctx->stream);
-  }
-  if (filter) {
+    t.n = N; t.hdr = p->hdr; t.pixels = pixels;
+    if (filter) { t.dColor = pl.R[0]; t.dIp = pl.Ip[0]; t.dOColor = pl.O[0]; t.dId = pl.Id[0]; t.dOId = pl.OId; }
+    else t.out = d_out;
+    launch_temporal(t, ctx->stream);
+  } else {
+    launch_quantize(gb.color, pl.R[0], pixels, ctx->stream);
+    launch_quantize(gb.color_ip, pl.Ip[0], pixels, ctx->stream);
     launch_quantize(gb.original_color, pl.O[0], pixels, ctx->stream);
     launch_quantize(gb.id, pl.Id[0], pixels, ctx->stream);
     launch_quantize(gb.original_id, pl.OId, pixels, ctx->stream);
-    launch_filter_chain(pl, d_out, (int)fr.width, (int)fr.height, p->hdr, ctx->stream);
   }
+  if (filter && !planes_out) launch_filter_chain(pl, d_out, (int)fr.width, (int)fr.height, p->hdr, ctx->stream);
   FLX_HIP(ctx, hipGetLastError());
   FLX_HIP(ctx, hipEventRecord(ctx->ev_frame1, ctx->stream));
   return FLX_OK;
@@ -930,6 +925,7 @@ extern "C" flx_status flx_temporal_reset(flx_context *ctx) {
   FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (auto &ring : ctx->d_ring) for (uint32_t *&plane : ring) if (plane) { FLX_HIP(ctx, hipFree(plane)); plane = nullptr; }
   ctx->ring_n = 0; ctx->ring_head = 0; ctx->ring_w = ctx->ring_h = 0;
+  ctx->ring_tile_rows = ctx->ring_tile_index = ctx->ring_tile_count = 0;
   return FLX_OK;
 }
 
@@ -1149,8 +1145,6 @@ flx_status flx_make_batch(flx_context *ctx, const flx_frame_params *params, uint
   return FLX_OK;
 }
 
-static flx_status ensure_post_buffers(flx_context *ctx, size_t pixels, bool gbuffers, bool planes);
-
 /* A batch of filter frames: ONE trace pass over the stacked frames into the RGBA8 render targets (the per-pixel kernel: the G-buffer
  * accumulators carry state from sample to sample), then per frame the denoise chain — which starts from the reference's frame-0
  * texture state every time (launch_filter_chain), so the frames of a batch do not depend on each other.  Each frame equals its
@@ -1281,6 +1275,16 @@ extern "C" flx_status flx_render_planes_device(flx_context *ctx, const flx_frame
   FLX_HIP(ctx, hipGetLastError());
   FLX_HIP(ctx, hipEventRecord(ctx->ev_frame1, ctx->stream));
   return FLX_OK;
+}
+
+flx_status flx_temporal_planes_enqueue(flx_context *ctx, const flx_frame_params *params, void *d_planes) {
+  if (!params || params->use_filter != 1 || params->is_temporal != 1) return fail(ctx, FLX_ERR_INVALID, "internal: flx_temporal_planes_enqueue takes temporal filter frames");
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  DeviceScene sc; DeviceFrame fr;
+  flx_status s = flx_make_frame(ctx, params, sc, fr);
+  if (s) return s;
+  if ((size_t)fr.rows * fr.width == 0) return empty_share(ctx);
+  return run_post_frame(ctx, sc, fr, params, nullptr, (uint32_t *)d_planes);
 }
 
 extern "C" flx_status flx_filter_planes_device(flx_context *ctx, const flx_frame_params *params, const void *d_planes, void *d_out_rgba) {

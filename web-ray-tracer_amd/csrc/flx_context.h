@@ -85,10 +85,12 @@ struct flx_context {
   uint32_t *d_qbatch = nullptr;                  /* batches of filter frames: the five render targets of every frame, 5 x pixels */
   size_t qbatch_capacity = 0;                    /* pixels */
   size_t planes_capacity = 0;
-  /* temporal history: rings of RGBA8 planes (colour, colour ip, location id, original id), newest at ring_head */
+  /* temporal history: rings of RGBA8 planes (colour, colour ip, location id, original id), newest at ring_head, of the rows this
+   * context traces (packed strips of a tiled frame): for frames of ring_n slots, ring_w x ring_h and the (normalised) tile policy ring_tile_* */
   uint32_t *d_ring[4][16] = {};
   int ring_n = 0, ring_head = 0;
   uint32_t ring_w = 0, ring_h = 0;
+  uint32_t ring_tile_rows = 0, ring_tile_index = 0, ring_tile_count = 0;
   /* v2 pipeline workspace: primary hits, per-(sample,pixel) radiance, last sample's originalColor, item queue */
   float4 *d_hits = nullptr, *d_samples = nullptr, *d_last = nullptr;
   size_t hits_capacity = 0, samples_capacity = 0, last_capacity = 0;
@@ -229,6 +231,9 @@ int flx_server_continues(flx_context *ctx, const flx_frame_params *params);     
 flx_status flx_server_prepare(flx_context *ctx, const flx_frame_params *params); /* the launch ends; everything a launch for frames like this needs is allocated */
 flx_status flx_server_stop(flx_context *ctx);      /* the frame server's launch ends (after the frames posted to it), the frames in flight are resolved into their output slots */
 flx_status flx_check_device_error(flx_context *ctx);      /* FLX_ERR_DEVICE (and the word cleared) if a frame kernel's watchdog has tripped since the last check */
+/* a temporal filter frame's strips (params->tile_*; use_filter = 1, is_temporal = 1): traced, the temporal pass over this context's history,
+ * the five render targets the chain reads stored to d_planes = uint32[5][rows][width] (flx_render_planes_device's layout); enqueued on its stream */
+flx_status flx_temporal_planes_enqueue(flx_context *ctx, const flx_frame_params *params, void *d_planes);
 /* flx_filter_planes_device; stamp_start = false leaves the frame's start event alone (the trace of the same frame recorded it) */
 flx_status flx_filter_planes_enqueue(flx_context *ctx, const flx_frame_params *params, const void *d_planes, void *d_out_rgba, bool stamp_start);
 

@@ -138,51 +138,55 @@ __global__ __launch_bounds__(256) void k_quantize(const float4 *__restrict__ src
   dst[i] = pack(F4(v.x, v.y, v.z, v.w));
 }
 
-/* Temporal accumulation, the shader modules/pathtracerWGL2.js:571-662 generates: average the history slots whose
- * location id equals the newest frame's; slots are visited in groups of four with vec4(0) standing in for slots >= n
- * (an all-zero id — an uncovered pixel — "matches" those stand-ins too, as in the shader). */
-__global__ __launch_bounds__(256) void k_temporal(TemporalRings r, int W, int H, int hdr, int use_filter, uint32_t *dColor, uint32_t *dIp, float4 *out) {
-  int x, y;
-  if (!texel_of_thread(W, H, x, y)) return;
-  Tex c0 = { r.c[0] }, ip0 = { r.ip[0] }, id0 = { r.id[0] }, oid0 = { r.oid[0] };
-  const f4 id = fetch(id0, W, H, x, y), originalId = fetch(oid0, W, H, x, y);
+/* Temporal accumulation, the shader modules/pathtracerWGL2.js:571-662 generates, in one pass over the frame's pixels in storage order (whole frames and a
+ * context's packed strips alike: the pass reads and writes the texel of its own pixel only).  A thread quantises its pixel's float G-buffers into the
+ * ring-head planes — the bytes k_quantize stores —, averages the history slots whose location id equals the newest frame's (slots visited in groups of four,
+ * vec4(0) standing in for slots >= n: an all-zero id, an uncovered pixel, "matches" those stand-ins too, as in the shader) and writes the canvas float4, or,
+ * with the filter, RenderTexture[0] / IpRenderTexture[0] and the OriginalColor / Id / OriginalId targets the chain reads.  The texels are compared as bytes:
+ * two are equal as vec4s exactly when their bytes are (k / 255 is injective). */
+__global__ __launch_bounds__(256) void k_temporal_frame(TemporalPass t) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= t.pixels) return;
+  const float4 gc = t.color[i], gip = t.color_ip[i], gloc = t.location_id[i], goid = t.original_id[i];
+  const uint32_t qc = pack(F4(gc.x, gc.y, gc.z, gc.w)), qip = pack(F4(gip.x, gip.y, gip.z, gip.w));
+  const uint32_t qid = pack(F4(gloc.x, gloc.y, gloc.z, gloc.w)), qoid = pack(F4(goid.x, goid.y, goid.z, goid.w));
+  t.ring_c[0][i] = qc; t.ring_ip[0][i] = qip; t.ring_id[0][i] = qid; t.ring_oid[0][i] = qoid;
   float counter = 1.0f, glassCounter = 1.0f;
-  const f4 cc = fetch(c0, W, H, x, y), ci = fetch(ip0, W, H, x, y);
+  const f4 cc = unpack(qc), ci = unpack(qip);
   const float centerW = cc.w;
   float color[3] = { cc.x + ci.x * 256.0f, cc.y + ci.y * 256.0f, cc.z + ci.z * 256.0f };
   float glassFilter = ci.w;
-  for (int i = 1; i < r.n; i += 4) {
-    f4 cs[4], ips[4], ids[4], oids[4];
+  for (int k = 1; k < t.n; k += 4) {
+    uint32_t cs[4], ips[4], ids[4], oids[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      const int k = i + j;
-      if (k < r.n) {
-        Tex tc = { r.c[k] }, tip = { r.ip[k] }, tid = { r.id[k] }, toid = { r.oid[k] };
-        cs[j] = fetch(tc, W, H, x, y); ips[j] = fetch(tip, W, H, x, y); ids[j] = fetch(tid, W, H, x, y); oids[j] = fetch(toid, W, H, x, y);
-      } else {
-        cs[j] = ips[j] = ids[j] = oids[j] = F4(0.0f, 0.0f, 0.0f, 0.0f);
-      }
+      if (k + j < t.n) { cs[j] = t.ring_c[k + j][i]; ips[j] = t.ring_ip[k + j][i]; ids[j] = t.ring_id[k + j][i]; oids[j] = t.ring_oid[k + j][i]; }
+      else cs[j] = ips[j] = ids[j] = oids[j] = 0u;
     }
 #pragma unroll
-    for (int j = 0; j < 4; j++) if (eq4(ids[j], id)) {
-      color[0] += cs[j].x + ips[j].x * 256.0f; color[1] += cs[j].y + ips[j].y * 256.0f; color[2] += cs[j].z + ips[j].z * 256.0f;
+    for (int j = 0; j < 4; j++) if (ids[j] == qid) {
+      const f4 c = unpack(cs[j]), p = unpack(ips[j]);
+      color[0] += c.x + p.x * 256.0f; color[1] += c.y + p.y * 256.0f; color[2] += c.z + p.z * 256.0f;
       counter += 1.0f;
     }
 #pragma unroll
-    for (int j = 0; j < 4; j++) if (eq4(oids[j], originalId)) {
-      glassFilter += ips[j].w;
+    for (int j = 0; j < 4; j++) if (oids[j] == qoid) {
+      glassFilter += unorm8(rawW(ips[j]));
       glassCounter += 1.0f;
     }
   }
 #pragma unroll
   for (int k = 0; k < 3; k++) color[k] /= counter;
   glassFilter /= glassCounter;
-  const size_t o = (size_t)(H - 1 - y) * W + x;
-  if (use_filter) {
-    dColor[o] = pack(F4(flx_mod(color[0], 1.0f), flx_mod(color[1], 1.0f), flx_mod(color[2], 1.0f), centerW));
-    dIp[o] = pack(F4(flx_floor(color[0]) / 256.0f, flx_floor(color[1]) / 256.0f, flx_floor(color[2]) / 256.0f, glassFilter));
+  if (t.dColor) {
+    const float4 go = t.original_color[i], gid = t.id[i];
+    t.dColor[i] = pack(F4(flx_mod(color[0], 1.0f), flx_mod(color[1], 1.0f), flx_mod(color[2], 1.0f), centerW));
+    t.dIp[i] = pack(F4(flx_floor(color[0]) / 256.0f, flx_floor(color[1]) / 256.0f, flx_floor(color[2]) / 256.0f, glassFilter));
+    t.dOColor[i] = pack(F4(go.x, go.y, go.z, go.w));
+    t.dId[i] = pack(F4(gid.x, gid.y, gid.z, gid.w));
+    t.dOId[i] = qoid;
   } else {
-    if (hdr == 1) {
+    if (t.hdr == 1) {
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         color[k] = color[k] / (color[k] + 1.0f);
@@ -190,7 +194,7 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalRings r, int W, int H,
         color[k] = flx_pow(4.0f * color[k], 1.0f / gamma) / 4.0f * 1.3f;
       }
     }
-    out[o] = make_float4(color[0], color[1], color[2], centerW);
+    t.out[i] = make_float4(color[0], color[1], color[2], centerW);
   }
 }
 
@@ -601,10 +605,8 @@ void launch_quantize(const float4 *src, uint32_t *dst, size_t n, hipStream_t str
   hipLaunchKernelGGL(k_quantize, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, src, dst, n);
 }
 
-void launch_temporal(const TemporalRings &rings, int W, int H, int hdr, int use_filter, uint32_t *dColor, uint32_t *dIp, float4 *out,
-                     hipStream_t stream) {
-  const dim3 grid(((W + 15) >> 4) * ((H + 15) >> 4)), block(256);
-  hipLaunchKernelGGL(k_temporal, grid, block, 0, stream, rings, W, H, hdr, use_filter, dColor, dIp, out);
+void launch_temporal(const TemporalPass &pass, hipStream_t stream) {
+  hipLaunchKernelGGL(k_temporal_frame, dim3((uint32_t)((pass.pixels + 255) / 256)), dim3(256), 0, stream, pass);
 }
 
 void launch_filter_chain(const FilterPlanes &pl, float4 *out, int W, int H, int hdr, hipStream_t stream) {

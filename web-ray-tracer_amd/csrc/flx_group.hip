@@ -99,9 +99,12 @@ struct Share {                   /* what one context contributes to a gathered f
   bool rgba8 = false;            /* the presenter wants the canvas' RGBA8: the strips are quantised where they were traced and travel as uint32 texels (slot of them per rank) */
 };
 
-flx_status check_params(flx_context *ctx, const flx_frame_params *params, uint32_t n_frames, int rank, int size, Share &sh) {
+/* temporal: the group's frame loop (flx_group_frame_begin), where every context keeps the history of its own strips, may render a temporal frame; the
+ * public entry points are stateless or render batches and refuse it */
+flx_status check_params(flx_context *ctx, const flx_frame_params *params, uint32_t n_frames, int rank, int size, Share &sh, bool temporal = false) {
   if (!params || n_frames < 1u || n_frames > FLX_MAX_BATCH_FRAMES) return flx_fail(ctx, FLX_ERR_INVALID, "gathered render: 1 .. 32 frames");
-  if (params->is_temporal) return flx_fail(ctx, FLX_ERR_INVALID, "gathered render: temporal frames keep their history in one context and are not sharded");
+  if (params->is_temporal && !temporal) return flx_fail(ctx, FLX_ERR_INVALID, "gathered render: temporal frames keep their history in one context and are not sharded");
+  if (params->is_temporal && n_frames != 1u) return flx_fail(ctx, FLX_ERR_INVALID, "gathered render: temporal frames are rendered one by one");
   if (params->use_filter && n_frames != 1u) return flx_fail(ctx, FLX_ERR_INVALID, "gathered render: filter frames are rendered one by one");
   if (params->tile_rows == 0u) return flx_fail(ctx, FLX_ERR_INVALID, "gathered render: tile_rows must be positive");
   for (uint32_t i = 0; i < n_frames; i++)
@@ -122,8 +125,12 @@ flx_status trace_share(flx_context *ctx, const flx_frame_params *params, const S
   flx_status s;
   if ((s = ensure_f4(ctx, &ctx->d_send, &ctx->send_capacity, sh.slot))) return s;
   if ((s = ensure_f4(ctx, &ctx->d_recv, &ctx->recv_capacity, sh.slot * sh.n))) return s;
-  if (sh.planes) return flx_render_planes_device(ctx, params, ctx->d_send);
-  if ((s = flx_render_batch_device(ctx, params, sh.frames, ctx->d_send))) return s;
+  if (params->is_temporal) {
+    /* (one frame: check_params) the temporal pass over this context's history of its strips — the five render targets of a filter frame after it, or the frame's strips */
+    if (sh.planes) return flx_temporal_planes_enqueue(ctx, params, ctx->d_send);
+    if ((s = flx_render_device(ctx, params, ctx->d_send))) return s;
+  } else if (sh.planes) return flx_render_planes_device(ctx, params, ctx->d_send);
+  else if ((s = flx_render_batch_device(ctx, params, sh.frames, ctx->d_send))) return s;
   if (sh.rgba8) {
     /* floor(clamp(x) * 255 + 0.5) per channel — flx_present's store, texel by texel: the same bytes whether a strip is quantised here or the frame after
      * the exchange.  (The padding rows of a rank with a strip less hold whatever was there: nobody reads them.) */
@@ -415,7 +422,9 @@ extern "C" flx_status flx_group_atlas_upload(flx_group *g, int which, const uint
 extern "C" flx_status flx_group_scene_upload_view(flx_group *g, const flx_scene_view *scene) { FLX_GROUP_EACH(g, flx_scene_upload_view(c, scene)); }
 
 /* n_frames frames (a batch; 1 = one frame) of a camera path on all contexts of the group; the frames arrive on the host. */
-static flx_status group_render(flx_group *g, const flx_frame_params *params, uint32_t n_frames, uint32_t tile_rows, void *out_rgba, flx_counters *counters, bool rgba8) {
+/* temporal: the frame loop's frames (flx_group_frame_begin) — a temporal frame is rendered, every context over the history of its strips */
+static flx_status group_render(flx_group *g, const flx_frame_params *params, uint32_t n_frames, uint32_t tile_rows, void *out_rgba, flx_counters *counters, bool rgba8,
+                               bool temporal = false) {
   if (!g) return FLX_ERR_INVALID;
   auto gfail = [&](flx_context *c, flx_status s) { g->err = c ? flx_last_error(c) : "flx_group_render: bad arguments"; return s; };
   if (!params || !out_rgba || n_frames < 1u || n_frames > FLX_MAX_BATCH_FRAMES || tile_rows == 0u) return gfail(nullptr, FLX_ERR_INVALID);
@@ -425,7 +434,7 @@ static flx_status group_render(flx_group *g, const flx_frame_params *params, uin
   flx_status s;
   for (int r = 0; r < n; r++) {
     for (auto &q : p[r]) { q.tile_rows = tile_rows; q.tile_index = (uint32_t)r; q.tile_count = (uint32_t)n; }
-    if ((s = check_params(g->ctx[r], p[r].data(), n_frames, r, n, sh[r]))) return gfail(g->ctx[r], s);
+    if ((s = check_params(g->ctx[r], p[r].data(), n_frames, r, n, sh[r], temporal))) return gfail(g->ctx[r], s);
     if (rgba8 && sh[r].planes) { g->err = "flx_group_render_rgba8: filter frames are gathered as their five render targets (present the float frame)"; return FLX_ERR_INVALID; }
     sh[r].rgba8 = rgba8;
   }
@@ -500,8 +509,9 @@ extern "C" flx_status flx_group_render_rgba8(flx_group *g, const flx_frame_param
  * the frame to every context's frame server (flx_server.hip) and returns; each server renders its context's row strips and resolves them straight into the
  * ONE image the group owns — pinned host memory every GPU writes over its own PCIe link (FLX_FRAME_FLOAT), or context 0's device memory through the peer
  * mapping (FLX_FRAME_DEVICE).  flx_group_frame_end waits for every server's word and hands the image out: no exchange, no reassembly kernel, no copy, and no
- * host synchronisation with any stream.  Frames the server does not take (filter / temporal frames, scenes of <= 128 entries, strips that are no multiple of
- * 8 rows) are rendered synchronously by flx_group_render at flx_group_frame_begin and handed out by the matching _end. */
+ * host synchronisation with any stream.  Float frames the server does not take (temporal frames, scenes of <= 128 entries, strips that are no multiple of
+ * 8 rows, a scene that moved) run on the contexts' two lanes; filter frames, and the canvas' bytes of such frames, are rendered synchronously by group_render
+ * at flx_group_frame_begin.  Either way the matching _end hands them out.  Temporal frames keep their history per context: every context that of its strips. */
 extern "C" flx_status flx_group_set_frame_lanes(flx_group *g, int lanes) {
   if (!g) return FLX_ERR_INVALID;
   if (lanes < 2 || lanes > 3) { g->err = "flx_group_set_frame_lanes: 2 or 3 frames in flight"; return FLX_ERR_INVALID; }
@@ -580,9 +590,9 @@ extern "C" flx_status flx_group_frame_begin(flx_group *g, const flx_frame_params
   /* ... as floats on the contexts' two lanes (every lane keeps its own copy of the lights and transforms; nothing waits for a GPU here), its strips copied into the frame's
    * image when the frame is taken; the canvas' bytes through flx_group_render_rgba8 */
   if (moved) server = false;
-  /* (... and so does every other float frame the servers do not take — a scene of <= 128 entries, strips that are no multiple of 8 rows —; filter and temporal frames need
-   * the whole frame in one context: flx_group_render) */
-  const bool lanes = !server && format == FLX_FRAME_FLOAT && !params->use_filter && !params->is_temporal;
+  /* (... and so does every other float frame the servers do not take — a scene of <= 128 entries, strips that are no multiple of 8 rows, a temporal frame, which
+   * every context begins on its first lane, where the history of its strips lives —; the denoise chain of filter frames needs the whole frame in one context) */
+  const bool lanes = !server && format == FLX_FRAME_FLOAT && !params->use_filter;
   auto &slot = g->fifo[g->fifo_n];
   if (!server && format == FLX_FRAME_DEVICE) { g->err = "flx_group_frame_begin: FLX_FRAME_DEVICE takes only frames the frame server takes (flx_frame_server_takes) on GPUs that can write context 0's memory; FLX_FRAME_FLOAT takes every frame"; return FLX_ERR_INVALID; }
   if (!server) {
@@ -617,11 +627,11 @@ extern "C" flx_status flx_group_frame_begin(flx_group *g, const flx_frame_params
        * anything else is gathered as RGBA8 (flx_group_render_rgba8) */
       if (params->use_filter || params->is_temporal) {
         std::vector<float> tmp(pixels * 4u);
-        if ((s = flx_group_render(g, params, 1, tile_rows, tmp.data(), nullptr))) return s;
+        if ((s = group_render(g, params, 1, tile_rows, tmp.data(), nullptr, false, true))) return s;
         if ((s = flx_present(g->ctx[0], params->width, params->height, tmp.data(), (uint8_t *)g->h_sync[b]))) { g->err = flx_last_error(g->ctx[0]); return s; }
       } else if ((s = flx_group_render_rgba8(g, params, 1, tile_rows, (uint8_t *)g->h_sync[b], nullptr))) return s;
     } else
-    if ((s = flx_group_render(g, params, 1, tile_rows, (float *)g->h_sync[b], nullptr))) return s;
+    if ((s = group_render(g, params, 1, tile_rows, (float *)g->h_sync[b], nullptr, false, true))) return s;
     slot.kind = 0; slot.bytes = pixels * (format == FLX_FRAME_RGBA8 ? sizeof(uint32_t) : sizeof(float4));
     slot.pixels = (const void *)g->h_sync[b];
     slot.ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -663,6 +673,9 @@ extern "C" flx_status flx_group_frame_begin(flx_group *g, const flx_frame_params
   g->fifo_n++;
   return FLX_OK;
 }
+
+/* flx_temporal_reset on every context: the next temporal frame starts from zero history */
+extern "C" flx_status flx_group_temporal_reset(flx_group *g) { FLX_GROUP_EACH(g, flx_temporal_reset(c)); }
 
 extern "C" flx_status flx_group_frame_end(flx_group *g, const void **pixels, size_t *bytes, float *ms) {
   if (!g) return FLX_ERR_INVALID;

@@ -98,11 +98,19 @@ void launch_quantize(const float4 *src, uint32_t *dst, size_t n, hipStream_t str
 void launch_angle_tan(const DeviceScene &sc, float4 *out, hipStream_t stream);      /* DeviceScene::angle_tan for the scene as it stands */
 /* the chain over planes whose slot 0 (R[0], Ip[0], O[0], Id[0], OId) holds the frame */
 void launch_filter_chain(const FilterPlanes &pl, float4 *out, int W, int H, int hdr, hipStream_t stream);
-/* temporal accumulation (pathtracerWGL2.js:571-662) over rings of n RGBA8 planes, slot 0 = newest:
- * without filter -> canvas float4 `out`; with filter -> dColor / dIp (RenderTexture[0] / IpRenderTexture[0]). */
-struct TemporalRings { const uint32_t *c[16], *ip[16], *id[16], *oid[16]; int n; };
-void launch_temporal(const TemporalRings &rings, int W, int H, int hdr, int use_filter, uint32_t *dColor, uint32_t *dIp, float4 *out,
-                     hipStream_t stream);
+/* temporal accumulation (pathtracerWGL2.js:571-662), one pass after the trace of a temporal frame over its `pixels` in storage order (a whole frame, or a
+ * context's packed strips): the float G-buffers of the new frame are stored as the ring-head planes ring_*[0] (RGBA8, k_quantize's bytes) and averaged with
+ * the n - 1 older slots ring_*[1 .. n - 1].  Without the filter (dColor null) -> the canvas float4 `out`; with it -> dColor / dIp (RenderTexture[0] /
+ * IpRenderTexture[0]) and dOColor / dId / dOId, the other render targets the chain reads. */
+struct TemporalPass {
+  const float4 *color, *color_ip, *location_id, *original_id, *original_color, *id;
+  uint32_t *ring_c[16], *ring_ip[16], *ring_id[16], *ring_oid[16];
+  int n, hdr;
+  size_t pixels;
+  float4 *out;
+  uint32_t *dColor, *dIp, *dOColor, *dId, *dOId;
+};
+void launch_temporal(const TemporalPass &pass, hipStream_t stream);
 /* the rasterizer renderer (flx_raster.hip): one frame of k_raster into float4 out[rows][width] (the RGBA8 drawing buffer's values as float32) */
 void launch_raster(const DeviceScene &sc, const DeviceFrame &fr, int hdr, float4 *out, unsigned long long *counters, hipStream_t stream);
 /* ... into the RGBA8 words k_quantize would store for that frame (uncounted) */

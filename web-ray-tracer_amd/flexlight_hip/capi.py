@@ -26,7 +26,7 @@ EXPORTS = [
     "flx_frame_begin", "flx_frame_end", "flx_frames_in_flight", "flx_set_frame_lanes", "flx_set_server_moving_scenes", "flx_server_moving", "flx_get_tail_diag", "flx_set_frame_chain", "flx_last_chained", "flx_debug_inject_fault", "flx_get_server_stats", "flx_get_server_dump",
     "flx_render_gathered_root_device", "flx_comm_count", "flx_frame_begin_gathered", "flx_group_set_gather", "flx_frame_host_slots", "flx_set_wavefront_organisation", "flx_set_frame_front", "flx_last_organisation",
     "flx_group_scene_upload", "flx_group_transforms_upload", "flx_group_lights_upload", "flx_group_atlas_upload", "flx_group_scene_upload_view", "flx_group_render",
-    "flx_group_frame_begin", "flx_group_frame_end", "flx_group_frames_in_flight", "flx_group_set_frame_lanes",
+    "flx_group_frame_begin", "flx_group_frame_end", "flx_group_frames_in_flight", "flx_group_set_frame_lanes", "flx_group_temporal_reset",
     "flx_frame_server_takes", "flx_frame_target_set", "flx_frame_target_index", "flx_debug_set_server_groups",
     "flx_share_create", "flx_share_join", "flx_share_leave", "flx_frame_begin_shared", "flx_frame_end_shared",
     "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_sample_parallel", "flx_debug_last_trace_kernel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
@@ -149,6 +149,7 @@ def _load():
         "flx_group_frame_end": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
         "flx_group_frames_in_flight": (C.c_int, [vp]),
         "flx_group_set_frame_lanes": (C.c_int, [vp, C.c_int]),
+        "flx_group_temporal_reset": (C.c_int, [vp]),
         "flx_frame_server_takes": (C.c_int, [vp, C.POINTER(FrameParams)]),
         "flx_frame_target_set": (C.c_int, [vp, C.POINTER(vp), u32]),
         "flx_frame_target_index": (C.c_int, [vp]),
@@ -728,6 +729,10 @@ class Group:
 
     def frames_in_flight(self):
         return int(LIB.flx_group_frames_in_flight(self._h))
+
+    def temporal_reset(self):
+        """every context forgets the history of its strips (flx_temporal_reset on each): the next temporal frame starts afresh"""
+        self._check(LIB.flx_group_temporal_reset(self._h), "flx_group_temporal_reset")
 
     def frame_begin(self, params, tile_rows=8, device=False, rgba8=False):
         self._pending = getattr(self, "_pending", [])

@@ -41,7 +41,8 @@ class PathTracerHIP {
     this._tile = (options && options.tile) || null;      // {rows, index, count}: this context's strips of the frame
     /* several GPUs in this process (SURVEY.md 8e; not in the reference, which has one WebGL2 context): devices: N = GPUs 0 .. N - 1,
      * or a list of device numbers (a number may repeat: a rehearsal on a one-GPU box).  The frame is cut into strips of tileRows
-     * rows dealt round robin to the GPUs and gathered inside the library (flx_group_render: RCCL all-gather + reassembly). */
+     * rows dealt round robin to the GPUs and gathered inside the library (flx_group_render: RCCL all-gather + reassembly).  With config.temporal
+     * every GPU keeps the history of its own strips, and frames go through the group's frame loop (flx_group_frame_begin / _end). */
     const dv = options && options.devices;
     this._devices = Array.isArray(dv) ? dv.slice() : (dv > 1 ? Array.from({ length: dv }, (_, i) => i) : null);
     this._tileRows = (options && options.tileRows) || 8;
@@ -213,7 +214,18 @@ class PathTracerHIP {
     const n = rows * p.width * 4;
     let radiance = (options && options.reuse && this._out && this._out.length === n) ? this._out : new Float32Array(n);
     this._out = radiance;
-    const info = gpu.render(p, radiance, !!(options && options.counters));
+    let info;
+    if (this._devices && this.config.temporal) {
+      /* a temporal frame on a group of GPUs runs in the library's frame loop, where every GPU keeps the history of its own strips (flx_group_render
+       * is stateless and refuses it): the frames the loop has in flight are taken first, then this one is begun and taken */
+      if (options && options.counters) throw new Error('renderFrame: temporal frames on a group of GPUs are not counted');
+      const n = native(), g = this._group;
+      while (n.groupFramesInFlight(g) > 0) n.groupFrameEnd(g, this.present8);
+      n.groupFrameBegin(g, p, this._tileRows, false);
+      const r = n.groupFrameEnd(g, false);
+      radiance.set(r.pixels);
+      info = { frameMs: r.gpuMs };
+    } else info = gpu.render(p, radiance, !!(options && options.counters));
     if (aa && rows === p.height) {                        // the pass reads neighbouring texels: whole frames only (pathtracerWGL2.js:552-553)
       if (this._devices) throw new Error('antialiasing passes run on one context: use a single device');
       const out = new Float32Array(radiance.length);

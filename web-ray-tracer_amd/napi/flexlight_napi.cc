@@ -995,6 +995,16 @@ static napi_value GroupSetFrameLanes(napi_env env, napi_callback_info info) {
   detach_group_views(env, box);            /* (the images are made again for the new depth) */
   return nullptr;
 }
+/* groupTemporalReset(handle): every context of the group forgets the history of its strips (flx_group_temporal_reset) */
+static napi_value GroupTemporalReset(napi_env env, napi_callback_info info) {
+  napi_value argv[1];
+  if (!get_args(env, info, 1, argv)) return nullptr;
+  flx_group *g = get_group(env, argv[0]);
+  if (!g) return nullptr;
+  flx_status rc = flx_group_temporal_reset(g);
+  if (rc != FLX_OK) return gfail(env, g, "flx_group_temporal_reset", rc);
+  return nullptr;
+}
 
 static napi_value Version(napi_env env, napi_callback_info) {
   napi_value v;
@@ -1014,7 +1024,7 @@ static napi_value Init(napi_env env, napi_value exports) {
     { "createGroup", CreateGroup }, { "destroyGroup", DestroyGroup }, { "groupInfo", GroupInfo }, { "groupUploadScene", GroupUploadScene },
     { "groupUploadTransforms", GroupUploadTransforms }, { "groupUploadLights", GroupUploadLights }, { "groupUploadAtlas", GroupUploadAtlas },
     { "groupRender", GroupRender }, { "groupRenderRgba8", GroupRenderRgba8 }, { "groupFrameBegin", GroupFrameBegin }, { "groupFrameEnd", GroupFrameEnd }, { "groupFramesInFlight", GroupFramesInFlight },
-    { "groupSetFrameLanes", GroupSetFrameLanes },
+    { "groupSetFrameLanes", GroupSetFrameLanes }, { "groupTemporalReset", GroupTemporalReset },
   };
   for (const auto &f : fns) {
     napi_value fn;
