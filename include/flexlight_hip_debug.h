@@ -112,9 +112,13 @@ flx_status flx_debug_math(flx_context *ctx, int fn, const float *a, const float 
  * answers computed from the shader text (tests/golden/intersect_kat.json.gz).  fn 0: moellerTrumbore (fragment:123-140) through the walk kernels'
  * routine over stored edges (exact 1/det from v_rcp_f32, branch-free acceptance), 1: moellerTrumboreCull (:143-158) through the same routine, 2: rayCuboid
  * (:161-167) through the walk kernels' box test (interval test, exact quotients by reciprocal, IEEE division where their preconditions fail); 3, 4, 5: the
- * same three as the per-pixel kernel calls them.  Rows: triangles 16 floats (a, b, c, origin, direction, l), boxes 13 (l, origin, direction, min, max);
+ * same three as the per-pixel kernel calls them; 6: fn 2 for a scene whose boxes are NOT bounded (walk_fast_boxes = 0: every quotient by IEEE division) — fn 2 stands for a
+ * scene that is, so its rows must keep flx_scene_upload's bound: every box coordinate finite with |x| <= 2^59 (tests/golden/intersect_edge_kat.json.gz).  Rows: triangles 16 floats (a, b, c, origin, direction, l), boxes 13 (l, origin, direction, min, max);
  * out: 3 floats per row for fn 0 and 3 ((s, u, v) of a hit, zeros otherwise), else one float 0 / 1. */
 flx_status flx_debug_intersect(flx_context *ctx, int fn, const float *in, float *out, uint32_t n);
+/* The uploaded scene's walk_fast_boxes, read-only: 1 when every coordinate of every box entry (type 1) is finite with |x| <= 2^59 — the precondition under which the
+ * walk kernels take their box quotients through reciprocals; triangle entries do not count. */
+flx_status flx_debug_walk_fast_boxes(flx_context *ctx, int *fast);
 /* Walk n rays through the uploaded scene on the GPU, AS THE KERNELS DO, one ray per lane: rayTracer (fragment:172-227) and shadowTest (:230-279) of each ray;
  * used by tests to hold the device walks against literal answers computed from the shader text (tests/golden/walk_kat.json.gz).  variant 0: the wavefront
  * pipeline's lane walk over the threaded, hot-first copy with the rays pre-transformed into every object space; 1: the per-pixel / persistent kernels' lane

@@ -58,7 +58,7 @@ def _rotation(rng):
 
 
 def make(seed=0, n_objects=3, tris_per_object=40, n_transforms=3, n_lights=2, textured=True, exact_multiple=False,
-         degenerate=0, width=96, height=64, samples=2, bounces=3, axis_aligned_view=False):
+         degenerate=0, width=96, height=64, samples=2, bounces=3, axis_aligned_view=False, floor_far=40.0):
     rng = np.random.default_rng(seed)
     # transforms: number 0 is the identity (scene.js:590-593); arrays as Transform.buildWGL2Arrays lays them out
     rotation = np.zeros((n_transforms, 24), np.float32)
@@ -99,7 +99,8 @@ def make(seed=0, n_objects=3, tris_per_object=40, n_transforms=3, n_lights=2, te
             tris.append(("tri", transform, np.concatenate([a, b, c]), attrs))
         objects.append(_bvh(tris, transform, rng))
     floor = []
-    for quad in ([[-30, -6, -5], [30, -6, -5], [30, -6, 40]], [[30, -6, 40], [-30, -6, 40], [-30, -6, -5]]):
+    far = floor_far                                            # (beyond 2^59 the root box leaves the bound of the walk kernels' reciprocal box test: walk_fast_boxes = 0)
+    for quad in ([[-30, -6, -5], [30, -6, -5], [30, -6, far]], [[30, -6, far], [-30, -6, far], [-30, -6, -5]]):
         attrs = np.zeros(28, np.float32)
         attrs[0:9] = np.tile([0, 1, 0], 3)
         attrs[15:18] = -1

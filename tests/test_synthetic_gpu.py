@@ -1,7 +1,8 @@
 """Parity on synthetic scenes that exercise what the BASELINE scenes do not: many rotated / scaled transforms
 (more than the walk kernel can pre-transform in LDS -> its on-the-fly variant), zero and several lights,
 multi-cell texture atlases, translucent / emissive materials, degenerate triangles, an entry array without
-terminator, axis-aligned rays (zero direction components -> the IEEE-division path of the box test)."""
+terminator, axis-aligned rays (zero direction components -> the IEEE-division path of the box test), a root box beyond the bound of the
+reciprocal box test."""
 import numpy as np
 import pytest
 
@@ -18,6 +19,9 @@ CASES = {
     "degenerate_untextured": dict(seed=5, n_objects=2, tris_per_object=30, n_transforms=1, n_lights=1, textured=False, degenerate=6),
     "one_space_axis_aligned": dict(seed=7, n_objects=2, tris_per_object=24, n_transforms=1, n_lights=2, axis_aligned_view=True, width=65, height=33),
     "axis_aligned_view": dict(seed=6, n_objects=3, tris_per_object=30, n_transforms=2, n_lights=2, axis_aligned_view=True, width=65, height=33),
+    # a far floor triangle: the root box reaches 2^62 on one axis, beyond the 2^59 under which the walk kernels may take box quotients through reciprocals
+    # (flx_scene_upload clears walk_fast_boxes: every box test of the frame divides)
+    "unbounded_root_box": dict(seed=8, n_objects=3, tris_per_object=30, n_transforms=2, n_lights=2, floor_far=2.0 ** 62),
 }
 
 
@@ -27,6 +31,7 @@ def test_synthetic_scene_matches_oracle(hip, oracle, case, pipeline):
     sc = synth_scene.make(**CASES[case])
     p = sc.frame_params(use_filter=0)
     hip.update_scene(sc)
+    assert hip.walk_fast_boxes() == (0 if case == "unbounded_root_box" else 1)
     hip.set_pipeline(pipeline)
     want, want_cnt, _ = oracle.render(sc, p)
     try:

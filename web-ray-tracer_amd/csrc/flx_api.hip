@@ -2269,10 +2269,10 @@ struct DeviceScratch {                 /* a device buffer of a debug hook */
 
 extern "C" flx_status flx_debug_intersect(flx_context *ctx, int fn, const float *in, float *out, uint32_t n) {
   if (!ctx || !in || !out) return FLX_ERR_INVALID;
-  if (fn < 0 || fn > 5) return fail(ctx, FLX_ERR_INVALID, "flx_debug_intersect: fn 0 .. 5");
+  if (fn < 0 || fn > 6) return fail(ctx, FLX_ERR_INVALID, "flx_debug_intersect: fn 0 .. 6");
   if (n == 0) return FLX_OK;
   FLX_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t nin = (size_t)n * ((fn == 2 || fn == 5) ? 13u : 16u), nout = (size_t)n * ((fn == 0 || fn == 3) ? 3u : 1u);
+  const size_t nin = (size_t)n * ((fn == 2 || fn == 5 || fn == 6) ? 13u : 16u), nout = (size_t)n * ((fn == 0 || fn == 3) ? 3u : 1u);
   DeviceScratch d_in, d_out;                               /* freed on every way out */
   FLX_HIP(ctx, hipMalloc(&d_in.p, nin * 4));
   FLX_HIP(ctx, hipMalloc(&d_out.p, nout * 4));
@@ -2281,6 +2281,13 @@ extern "C" flx_status flx_debug_intersect(flx_context *ctx, int fn, const float 
   FLX_HIP(ctx, hipGetLastError());
   FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   FLX_HIP(ctx, hipMemcpy(out, d_out.p, nout * 4, hipMemcpyDeviceToHost));
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_debug_walk_fast_boxes(flx_context *ctx, int *fast) {
+  if (!ctx || !fast) return FLX_ERR_INVALID;
+  if (!ctx->have_scene) return fail(ctx, FLX_ERR_INVALID, "flx_debug_walk_fast_boxes: no scene uploaded");
+  *fast = ctx->walk_fast_boxes != 0u ? 1 : 0;
   return FLX_OK;
 }
 

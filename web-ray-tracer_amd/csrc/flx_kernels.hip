@@ -714,14 +714,14 @@ __global__ void k_debug_intersect(int fn, const float *__restrict__ in, float *_
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   DeviceScene sc = {};
-  sc.walk_fast_boxes = 1u;                                    /* the rows' boxes are small: the precondition of the reciprocal box test holds */
-  if (fn == 2 || fn == 5) {                                   /* rayCuboid: l, origin, dir, min, max */
+  sc.walk_fast_boxes = fn == 6 ? 0u : 1u;                     /* fn 2: the caller's rows keep the precondition of the reciprocal box test (flx_scene_upload's bound); fn 6: a scene that does not */
+  if (fn == 2 || fn == 5 || fn == 6) {                                   /* rayCuboid: l, origin, dir, min, max */
     const float *r = in + (size_t)i * 13u;
     WalkState w;
     w.tR.origin = F3(r[1], r[2], r[3]); w.tR.dir = F3(r[4], r[5], r[6]);
     reciprocalOfDir(sc, w.tR.dir, w.tR.origin, w.inv, w.fastDiv);
     const f3 lo = F3(r[7], r[8], r[9]), hi = F3(r[10], r[11], r[12]);
-    out[i] = (fn == 2 ? rayCuboidFast(r[0], w, lo, hi) : rayCuboid(r[0], w.tR, lo, hi)) ? 1.0f : 0.0f;
+    out[i] = (fn != 5 ? rayCuboidFast(r[0], w, lo, hi) : rayCuboid(r[0], w.tR, lo, hi)) ? 1.0f : 0.0f;
     return;
   }
   const float *r = in + (size_t)i * 16u;                      /* triangles: a, b, c, origin, dir, l */

@@ -30,7 +30,7 @@ EXPORTS = [
     "flx_frame_server_takes", "flx_frame_target_set", "flx_frame_target_index", "flx_debug_set_server_groups",
     "flx_share_create", "flx_share_join", "flx_share_leave", "flx_frame_begin_shared", "flx_frame_end_shared",
     "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_sample_parallel", "flx_debug_last_trace_kernel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
-    "flx_raster_render", "flx_debug_walk_staged", "flx_debug_last_walk_lds",
+    "flx_raster_render", "flx_debug_walk_staged", "flx_debug_last_walk_lds", "flx_debug_walk_fast_boxes",
 ]
 
 
@@ -160,6 +160,7 @@ def _load():
         "flx_debug_set_sample_parallel": (C.c_int, [vp, C.c_int]),
         "flx_debug_last_trace_kernel": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "flx_debug_walk_staged": (C.c_int, [vp, u32, C.POINTER(C.c_float), C.POINTER(C.c_float), u32]),
+        "flx_debug_walk_fast_boxes": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "flx_debug_last_walk_lds": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_debug_set_adaptive_order": (C.c_int, [vp, C.c_int]),
         "flx_debug_tile_order_of": (C.c_int, [vp, C.POINTER(C.c_float), u32, C.c_int, C.POINTER(u32)]),
@@ -497,12 +498,18 @@ class Context:
         self._check(LIB.flx_temporal_reset(self._h), "flx_temporal_reset")
 
     def debug_intersect(self, fn, rows):
-        """flx_debug_intersect: rows [n, 16] (triangles: fn 0, 1, 3, 4) or [n, 13] (boxes: fn 2, 5) float32 -> [n, 3] (fn 0, 3) or [n] float32"""
+        """flx_debug_intersect: rows [n, 16] (triangles: fn 0, 1, 3, 4) or [n, 13] (boxes: fn 2, 5; 6: fn 2 with walk_fast_boxes off) float32 -> [n, 3] (fn 0, 3) or [n] float32"""
         rows = np.ascontiguousarray(rows, np.float32)
         n = rows.shape[0]
         out = np.zeros((n, 3) if fn in (0, 3) else (n,), np.float32)
         self._check(LIB.flx_debug_intersect(self._h, int(fn), _fp(rows), _fp(out), n), "flx_debug_intersect")
         return out
+
+    def walk_fast_boxes(self):
+        """flx_debug_walk_fast_boxes: 1 when every box coordinate of the uploaded scene is finite with |x| <= 2^59 (the walk kernels' reciprocal box test is allowed), else 0"""
+        out = C.c_int(-1)
+        self._check(LIB.flx_debug_walk_fast_boxes(self._h, C.byref(out)), "flx_debug_walk_fast_boxes")
+        return out.value
 
     def debug_walk(self, variant, rays):
         """flx_debug_walk: rays [n, 7] float32 (origin, direction, l) -> [n, 8] float32 (s, u, v, 2 x transform, entry, entries fetched, shadowed, entries fetched)"""
