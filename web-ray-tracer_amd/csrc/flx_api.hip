@@ -15,7 +15,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -68,7 +67,7 @@ extern "C" flx_status flx_context_create(int device, flx_context **out) {
   ctx->device = device;
   auto bail = [&](const char *what, hipError_t err) {
     g_create_error = std::string(what) + ": " + hipGetErrorString(err);
-    delete ctx;
+    flx_context_destroy(ctx);               /* (whatever it has so far) */
     return FLX_ERR_DEVICE;
   };
   if ((e = hipSetDevice(device)) != hipSuccess) return bail("hipSetDevice", e);
@@ -79,13 +78,15 @@ extern "C" flx_status flx_context_create(int device, flx_context **out) {
   if ((e = hipEventCreate(&ctx->ev_frame1)) != hipSuccess) return bail("hipEventCreate", e);
   if ((e = hipEventCreate(&ctx->ev_k0)) != hipSuccess) return bail("hipEventCreate", e);
   if ((e = hipEventCreate(&ctx->ev_k1)) != hipSuccess) return bail("hipEventCreate", e);
-  if ((e = hipHostMalloc((void **)&ctx->h_dev_error, 64, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess) return bail("hipHostMalloc", e);
+  if (ctx->h_dev_error.ensure(ctx, 16, hipHostMallocMapped | hipHostMallocCoherent) || ctx->d_counters.ensure(ctx, FLX_COUNTER_SLOTS) || ctx->d_queue.ensure(ctx, 1) ||
+      ctx->d_wfcounts.ensure(ctx, WF_MAX_GROUPS * 2 * (WF_MAX_BOUNCES + 2))) {
+    g_create_error = ctx->err;
+    flx_context_destroy(ctx);
+    return FLX_ERR_DEVICE;
+  }
   ctx->h_dev_error[0] = 0u;
   if ((e = hipHostGetDevicePointer((void **)&ctx->d_dev_error, ctx->h_dev_error, 0)) != hipSuccess) return bail("hipHostGetDevicePointer", e);
-  if ((e = hipMalloc(&ctx->d_counters, FLX_COUNTER_SLOTS * sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
   if ((e = hipMemset(ctx->d_counters, 0, FLX_COUNTER_SLOTS * sizeof(unsigned long long))) != hipSuccess) return bail("hipMemset", e);
-  if ((e = hipMalloc(&ctx->d_queue, sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
-  if ((e = hipMalloc(&ctx->d_wfcounts, WF_MAX_GROUPS * 2 * (WF_MAX_BOUNCES + 2) * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
   for (int i = 0; i < 3; i++) {
     if ((e = hipStreamCreateWithFlags(&ctx->aux_stream[i], hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
     if ((e = hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
@@ -102,41 +103,18 @@ extern "C" void flx_context_destroy(flx_context *ctx) {
   if (ctx->sv_running && ctx->h_sv_mail) { __atomic_store_n(&ctx->h_sv_mail->stopAfter, ctx->sv_next_seq - 1u, __ATOMIC_RELEASE); ctx->sv_running = false; (void)hipStreamSynchronize(ctx->sv_stream); }
   (void)hipStreamSynchronize(ctx->stream);
   if (ctx->twin) { flx_context_destroy(ctx->twin); ctx->twin = nullptr; }
-  if (ctx->is_twin) {                      /* the static scene arrays belong to the primary context */
-    ctx->d_geometry = ctx->d_attributes = nullptr; ctx->d_ids = nullptr; ctx->d_walk = nullptr; ctx->d_fwd = nullptr;
-    ctx->d_atlas[0] = ctx->d_atlas[1] = ctx->d_atlas[2] = nullptr;
-  }
   (void)flx_comm_destroy(ctx);
-  void *bufs[] = { ctx->d_geometry, ctx->d_attributes, ctx->d_rotation, ctx->d_shift, ctx->d_ids, ctx->d_lights,
-                   ctx->d_atlas[0], ctx->d_atlas[1], ctx->d_atlas[2], ctx->d_out, ctx->d_gb[0], ctx->d_gb[1], ctx->d_gb[2],
-                   ctx->d_gb[3], ctx->d_gb[4], ctx->d_gb[5], ctx->d_counters, ctx->d_hits, ctx->d_samples, ctx->d_last, ctx->d_queue,
-                   ctx->d_send, ctx->d_send8, ctx->d_recv, ctx->d_frames, ctx->d_gplanes, ctx->d_angle_tan, ctx->d_rec, ctx->d_rec0, ctx->d_pix0, ctx->d_tail_pool, ctx->d_live[0], ctx->d_live[1], ctx->d_wfcounts, ctx->d_walk, ctx->d_fwd, ctx->d_frame_rings, ctx->d_qbatch, ctx->d_tile_order, ctx->d_tile_cost, ctx->d_tile_time, ctx->d_auto_order,
-                   ctx->d_planes[0], ctx->d_planes[1], ctx->d_planes[2], ctx->d_planes[3], ctx->d_planes[4], ctx->d_planes[5], ctx->d_planes[6],
-                   ctx->d_planes[7], ctx->d_planes[8], ctx->d_planes[9], ctx->d_planes[10], ctx->d_planes[11], ctx->d_planes[12] };
-  for (void *b : bufs) if (b) (void)hipFree(b);
-  for (auto &ring : ctx->d_ring) for (uint32_t *pl : ring) if (pl) (void)hipFree(pl);
-  for (uint32_t *pl : ctx->d_aa) if (pl) (void)hipFree(pl);
-  for (float4 *b : ctx->d_aa_io) if (b) (void)hipFree(b);
   for (hipEvent_t ev : { ctx->ev_frame0, ctx->ev_frame1, ctx->ev_k0, ctx->ev_k1 }) if (ev) (void)hipEventDestroy(ev);
   for (int i = 0; i < 3; i++) { if (ctx->aux_stream[i]) (void)hipStreamDestroy(ctx->aux_stream[i]); if (ctx->ev_join[i]) (void)hipEventDestroy(ctx->ev_join[i]); }
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
-  for (int i = 0; i < 3; i++) {
-    if (ctx->d_slot[i]) (void)hipFree(ctx->d_slot[i]);
-    if (ctx->d_slot8[i]) (void)hipFree(ctx->d_slot8[i]);
-    if (ctx->h_slot[i]) (void)hipHostFree(ctx->h_slot[i]);
+  for (int i = 0; i < 3; i++)
     for (hipEvent_t ev : { ctx->ev_slot_start[i], ctx->ev_slot_traced[i], ctx->ev_slot_done[i] }) if (ev) (void)hipEventDestroy(ev);
-  }
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   for (hipEvent_t ev : ctx->stage_done) if (ev) (void)hipEventDestroy(ev);
-  if (ctx->stage) (void)hipHostFree(ctx->stage);
-  if (ctx->h_sv_mail) (void)hipHostFree(ctx->h_sv_mail);
-  for (void *b : { (void *)ctx->d_sv_slots, (void *)ctx->d_sv_relay, (void *)ctx->d_sv_rings, (void *)ctx->d_sv_stats, (void *)ctx->d_sv_out, (void *)ctx->d_sv_tiles, (void *)ctx->d_sv_versions }) if (b) (void)hipFree(b);
   if (ctx->sv_stream) (void)hipStreamDestroy(ctx->sv_stream);
-  if (ctx->h_dev_error) (void)hipHostFree(ctx->h_dev_error);
-
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-  delete ctx;
+  delete ctx;                              /* its buffers go with it, on its device (set above; a twin's views of this context's scene arrays free nothing) */
 }
 
 /* Scene arrays live in device buffers that persist across uploads: an upload of the same or a smaller size reuses the
@@ -164,43 +142,40 @@ static flx_status shared_upload_end(flx_context *ctx) {
 }
 
 template <typename T>
-static flx_status upload(flx_context *ctx, T **dst, const void *src, size_t bytes) {
+static flx_status upload(flx_context *ctx, DeviceBuffer<T> &dst, const void *src, size_t bytes) {
   { flx_status ss = flx_server_stop(ctx); if (ss) return ss; }      /* (a running frame server reads the scene) */
   ctx->structure_version++;              /* (the uploads a launch for a scene that moves goes on over do not come through here: flx_transforms_upload) */
   ctx->scene_version++;                  /* (the frame server's launch does not go on over a changed scene) */
-  size_t &cap = ctx->upload_capacity[(void **)dst];
   if (bytes == 0) {                      /* "none": the kernels test the pointer */
-    if (*dst && ctx->twin) FLX_HIP(ctx, hipStreamSynchronize(ctx->twin->stream));
-    if (*dst) { FLX_HIP(ctx, hipFree(*dst)); *dst = nullptr; }
-    cap = 0;
-    return FLX_OK;
+    if (dst && ctx->twin) FLX_HIP(ctx, hipStreamSynchronize(ctx->twin->stream));
+    return dst.release(ctx);
   }
-  if (bytes > cap || !*dst) {
-    if (*dst) {
+  const size_t count = (bytes + sizeof(T) - 1) / sizeof(T);
+  if (!dst.fits(count)) {
+    if (dst) {
       FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
       if (ctx->twin) FLX_HIP(ctx, hipStreamSynchronize(ctx->twin->stream));      /* (the frame loop's second lane may be reading a shared array) */
-      FLX_HIP(ctx, hipFree(*dst)); *dst = nullptr;
     }
-    cap = 0;
-    FLX_HIP(ctx, hipMalloc(dst, bytes));
-    cap = bytes;
+    flx_status s = dst.ensure(ctx, count);
+    if (s) return s;
   }
   if (bytes <= STAGE_SLOT_BYTES) {
     if (!ctx->stage) {
-      FLX_HIP(ctx, hipHostMalloc((void **)&ctx->stage, STAGE_SLOT_BYTES * STAGE_SLOTS, hipHostMallocDefault));
+      flx_status s = ctx->stage.ensure(ctx, STAGE_SLOT_BYTES * STAGE_SLOTS, hipHostMallocDefault);
+      if (s) return s;
       for (auto &ev : ctx->stage_done) FLX_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
     const int k = ctx->stage_next;
     ctx->stage_next = (k + 1) % STAGE_SLOTS;
     if (ctx->stage_used[k]) FLX_HIP(ctx, hipEventSynchronize(ctx->stage_done[k]));      /* the copy that last read this slot (eight uploads ago) */
     memcpy(ctx->stage + (size_t)k * STAGE_SLOT_BYTES, src, bytes);
-    FLX_HIP(ctx, hipMemcpyAsync(*dst, ctx->stage + (size_t)k * STAGE_SLOT_BYTES, bytes, hipMemcpyHostToDevice, ctx->stream));
+    FLX_HIP(ctx, hipMemcpyAsync(dst, ctx->stage + (size_t)k * STAGE_SLOT_BYTES, bytes, hipMemcpyHostToDevice, ctx->stream));
     FLX_HIP(ctx, hipEventRecord(ctx->stage_done[k], ctx->stream));
     ctx->stage_used[k] = true;
     return FLX_OK;
   }
   if (ctx->twin) FLX_HIP(ctx, hipStreamSynchronize(ctx->twin->stream));      /* a scene array the second lane may still be reading */
-  FLX_HIP(ctx, hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+  FLX_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
   FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));          /* the caller's buffer is not retained */
   return FLX_OK;
 }
@@ -352,13 +327,13 @@ extern "C" flx_status flx_scene_upload(flx_context *ctx, const float *geometry, 
   ctx->have_scene = false;
   ctx->last_walk_lds = WalkLdsLaunch();
   ctx->geometry_version++;
-  if ((s = upload(ctx, &ctx->d_geometry, geometry, (size_t)n_entries_padded * 48))) return s;
-  if ((s = upload(ctx, &ctx->d_attributes, attributes, (size_t)n_entries_padded * 112))) return s;
-  if ((s = upload(ctx, &ctx->d_ids, ids, (size_t)n_ids * 4))) return s;
+  if ((s = upload(ctx, ctx->d_geometry, geometry, (size_t)n_entries_padded * 48))) return s;
+  if ((s = upload(ctx, ctx->d_attributes, attributes, (size_t)n_entries_padded * 112))) return s;
+  if ((s = upload(ctx, ctx->d_ids, ids, (size_t)n_ids * 4))) return s;
   {
     std::vector<float> threaded;
     build_threaded(geometry, n_entries_padded, threaded, ctx->walk_entries, ctx->walk_hot, ctx->walk_root);
-    if ((s = upload(ctx, &ctx->d_walk, threaded.data(), threaded.size() * sizeof(float)))) return s;
+    if ((s = upload(ctx, ctx->d_walk, threaded.data(), threaded.size() * sizeof(float)))) return s;
     /* precondition of the walk kernel's fast box test (flx_device.h: rayCuboidR): bounded, finite AABBs */
     bool bounded = true;
     for (uint32_t i = 0; i < n_entries_padded && bounded; i++) {
@@ -372,7 +347,7 @@ extern "C" flx_status flx_scene_upload(flx_context *ctx, const float *geometry, 
     {
       std::vector<float> fwd;
       build_lockstep(geometry, n_entries_padded, fwd, ctx->fwd_entries, ctx->fwd_root, ctx->lock_boxes);
-      if ((s = upload(ctx, &ctx->d_fwd, fwd.data(), fwd.size() * sizeof(float)))) return s;
+      if ((s = upload(ctx, ctx->d_fwd, fwd.data(), fwd.size() * sizeof(float)))) return s;
       ctx->lock_ok = max_transform == 0 && ctx->fwd_entries <= FLX_LOCK_MAX;
     }
   }
@@ -409,8 +384,8 @@ extern "C" flx_status flx_transforms_upload(flx_context *ctx, const float *rotat
   }
   ctx->have_transforms = false;             /* (until both arrays are in: a failed upload must not pass for the arrays it replaced) */
   ctx->transforms_version++;
-  if ((s = upload(ctx, &ctx->d_rotation, rotation, (size_t)n_transforms * 96))) return s;
-  if ((s = upload(ctx, &ctx->d_shift, shift, (size_t)n_transforms * 32))) return s;
+  if ((s = upload(ctx, ctx->d_rotation, rotation, (size_t)n_transforms * 96))) return s;
+  if ((s = upload(ctx, ctx->d_shift, shift, (size_t)n_transforms * 32))) return s;
   ctx->dyn_device_stale &= ~1u;
   ctx->n_transforms = n_transforms;
   ctx->have_transforms = true;
@@ -438,7 +413,7 @@ extern "C" flx_status flx_lights_upload(flx_context *ctx, const float *lights, u
     return FLX_OK;
   }
   ctx->have_lights = false;
-  if ((s = upload(ctx, &ctx->d_lights, lights, (size_t)n_lights * 24))) return s;
+  if ((s = upload(ctx, ctx->d_lights, lights, (size_t)n_lights * 24))) return s;
   ctx->dyn_device_stale &= ~2u;
   ctx->n_lights = n_lights;
   if (!ctx->is_twin) { ctx->h_lights.assign(lights, lights + (size_t)n_lights * 6); ctx->dyn_version++; ctx->have_lights = true; }
@@ -452,7 +427,7 @@ extern "C" flx_status flx_atlas_upload(flx_context *ctx, int which, const uint8_
   size_t bytes = rgba ? (size_t)width * height * 4 : 0;
   flx_status s;
   if ((s = shared_upload_begin(ctx))) return s;
-  if ((s = upload(ctx, &ctx->d_atlas[which], rgba, bytes))) return s;
+  if ((s = upload(ctx, ctx->d_atlas[which], rgba, bytes))) return s;
   ctx->atlas_w[which] = bytes ? width : 0;
   ctx->atlas_h[which] = bytes ? height : 0;
   return shared_upload_end(ctx);
@@ -593,14 +568,6 @@ flx_status flx_check_device_error(flx_context *ctx) {
   return flx_fail(ctx, FLX_ERR_DEVICE, full.c_str());
 }
 
-flx_status flx_ensure_pixels(flx_context *ctx, float4 **buf, size_t *cap, size_t pixels) {
-  if (*cap >= pixels && *buf) return FLX_OK;
-  if (*buf) { FLX_HIP(ctx, hipFree(*buf)); *buf = nullptr; *cap = 0; }
-  FLX_HIP(ctx, hipMalloc(buf, pixels * sizeof(float4)));
-  *cap = pixels;
-  return FLX_OK;
-}
-
 /* The buffers pipelines 2 and 3 need for this frame (or batch of frames): sized before anything is freed or allocated, so that a batch that is too
  * large is refused with a message that says what to do and the context keeps the buffers it has.  -> the chains of the bounce loop (pipeline 3). */
 static flx_status ensure_workspace(flx_context *ctx, const DeviceFrame &fr, int pipeline, bool counted, int &wf_chains) {
@@ -615,14 +582,14 @@ static flx_status ensure_workspace(flx_context *ctx, const DeviceFrame &fr, int 
     {
       const size_t items = (size_t)path_item_count64(fr);
       struct { size_t need, have; } w[] = {
-        { P, ctx->hits_capacity }, { P, ctx->last_capacity }, { P * (size_t)fr.samples, ctx->samples_capacity },
-        { pipeline == 3 ? items * 8 : 0, ctx->rec_capacity }, { pipeline == 3 ? items * 3 : 0, ctx->rec0_capacity },
-        { pipeline == 3 ? items / (size_t)fr.samples * 3 : 0, ctx->pix0_capacity } };
+        { P, ctx->d_hits.capacity() }, { P, ctx->d_last.capacity() }, { P * (size_t)fr.samples, ctx->d_samples.capacity() },
+        { pipeline == 3 ? items * 8 : 0, ctx->d_rec.capacity() }, { pipeline == 3 ? items * 3 : 0, ctx->d_rec0.capacity() },
+        { pipeline == 3 ? items / (size_t)fr.samples * 3 : 0, ctx->d_pix0.capacity() } };
       size_t grow = 0, freed = 0;
       for (auto &b : w) if (b.need > b.have) { grow += b.need * sizeof(float4); freed += b.have * sizeof(float4); }
       if (pipeline == 3) {
         const size_t live = wavefront_live_capacity(fr, cus) * (size_t)(ctx->wf_groups < 1 ? 1 : (ctx->wf_groups > WF_MAX_GROUPS ? WF_MAX_GROUPS : ctx->wf_groups));      /* what the allocation below asks for */
-        if (live > ctx->live_capacity) { grow += 2 * live * sizeof(uint32_t); freed += 2 * ctx->live_capacity * sizeof(uint32_t); }
+        for (auto &list : ctx->d_live) if (!list.fits(live)) { grow += live * sizeof(uint32_t); freed += list.capacity() * sizeof(uint32_t); }
       }
       size_t memFree = 0, memTotal = 0;
       if (grow && hipMemGetInfo(&memFree, &memTotal) == hipSuccess && grow > memFree + freed) {
@@ -632,15 +599,15 @@ static flx_status ensure_workspace(flx_context *ctx, const DeviceFrame &fr, int 
         return fail(ctx, FLX_ERR_DEVICE, msg);
       }
     }
-    if ((s = flx_ensure_pixels(ctx, &ctx->d_hits, &ctx->hits_capacity, P))) return s;
-    if ((s = flx_ensure_pixels(ctx, &ctx->d_last, &ctx->last_capacity, P))) return s;
-    if ((s = flx_ensure_pixels(ctx, &ctx->d_samples, &ctx->samples_capacity, P * (size_t)fr.samples))) return s;
+    if ((s = ctx->d_hits.ensure(ctx, P))) return s;
+    if ((s = ctx->d_last.ensure(ctx, P))) return s;
+    if ((s = ctx->d_samples.ensure(ctx, P * (size_t)fr.samples))) return s;
   }
   if (pipeline == 3) {
     flx_status s;
-    if ((s = flx_ensure_pixels(ctx, &ctx->d_rec, &ctx->rec_capacity, (size_t)path_item_count(fr) * 8))) return s;
-    if ((s = flx_ensure_pixels(ctx, &ctx->d_rec0, &ctx->rec0_capacity, (size_t)path_item_count(fr) * 3))) return s;
-    if ((s = flx_ensure_pixels(ctx, &ctx->d_pix0, &ctx->pix0_capacity, (size_t)path_item_count(fr) / (size_t)fr.samples * 3))) return s;      /* 64 per screen tile */
+    if ((s = ctx->d_rec.ensure(ctx, (size_t)path_item_count(fr) * 8))) return s;
+    if ((s = ctx->d_rec0.ensure(ctx, (size_t)path_item_count(fr) * 3))) return s;
+    if ((s = ctx->d_pix0.ensure(ctx, (size_t)path_item_count(fr) / (size_t)fr.samples * 3))) return s;      /* 64 per screen tile */
     /* the live lists are cut into one slice per chain of the bounce loop (flx_set_wavefront_groups; counted frames run one
      * chain), each able to hold the whole frame */
     wf_chains = ctx->wf_groups < 1 ? 1 : (ctx->wf_groups > WF_MAX_GROUPS ? WF_MAX_GROUPS : ctx->wf_groups);
@@ -649,14 +616,7 @@ static flx_status ensure_workspace(flx_context *ctx, const DeviceFrame &fr, int 
       if ((uint32_t)wf_chains > tiles || counted) wf_chains = 1;
     }
     const size_t need = wavefront_live_capacity(fr, cus) * (size_t)wf_chains;
-    if (ctx->live_capacity < need) {
-      ctx->live_capacity = 0;               /* a failed allocation below must not leave the old size standing over freed lists */
-      for (int i = 0; i < 2; i++) {
-        if (ctx->d_live[i]) { FLX_HIP(ctx, hipFree(ctx->d_live[i])); ctx->d_live[i] = nullptr; }
-        FLX_HIP(ctx, hipMalloc(&ctx->d_live[i], need * sizeof(uint32_t)));
-      }
-      ctx->live_capacity = need;
-    }
+    for (auto &list : ctx->d_live) if ((s = list.ensure(ctx, need))) return s;
   }
   return FLX_OK;
 }
@@ -667,7 +627,7 @@ static flx_status angle_table(flx_context *ctx, DeviceScene &scT) {
   if (ctx->angle_table && ctx->n_entries != 0u) {
     const uint64_t key = ((uint64_t)ctx->geometry_version << 32) | ctx->transforms_version;
     if (key != ctx->angle_key || !ctx->d_angle_tan) {
-      flx_status es = flx_ensure_pixels(ctx, &ctx->d_angle_tan, &ctx->angle_capacity, ctx->n_entries);
+      flx_status es = ctx->d_angle_tan.ensure(ctx, ctx->n_entries);
       if (es) return es;
       launch_angle_tan(scT, ctx->d_angle_tan, ctx->stream);
       FLX_HIP(ctx, hipGetLastError());
@@ -741,12 +701,13 @@ flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFr
   } else {
     FLX_HIP(ctx, hipMemsetAsync(ctx->d_wfcounts, 0, WF_MAX_GROUPS * 2 * (WF_MAX_BOUNCES + 2) * sizeof(uint32_t), ctx->stream));
     /* scratch of the walk kernel's tail consolidation: one slice per chain and possible walk workgroup */
-    if (!ctx->d_tail_pool) FLX_HIP(ctx, hipMalloc(&ctx->d_tail_pool, (size_t)WF_MAX_GROUPS * cus * 8u * WF_TAIL_POOL_F4 * sizeof(float4)));
+    { flx_status s = ctx->d_tail_pool.ensure(ctx, (size_t)WF_MAX_GROUPS * cus * 8u * WF_TAIL_POOL_F4); if (s) return s; }
     /* the frame kernel's rings: one slice per chain that can run (48 MB each at 256 CUs), WF_INVALID everywhere — a launch leaves them so */
     if (ctx->frame_rings_chains < wf_chains) {
-      if (ctx->d_frame_rings) { FLX_HIP(ctx, hipStreamSynchronize(ctx->stream)); FLX_HIP(ctx, hipFree(ctx->d_frame_rings)); ctx->d_frame_rings = nullptr; ctx->frame_rings_chains = 0; }
+      if (ctx->d_frame_rings) FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      ctx->frame_rings_chains = 0;
       const size_t words = (size_t)wf_chains * cus * WF_FRAME_RINGS * WF_FRAME_RING;
-      FLX_HIP(ctx, hipMalloc(&ctx->d_frame_rings, words * sizeof(uint32_t)));
+      { flx_status s = ctx->d_frame_rings.ensure(ctx, words); if (s) return s; }
       FLX_HIP(ctx, hipMemsetAsync(ctx->d_frame_rings, 0xff, words * sizeof(uint32_t), ctx->stream));
       ctx->frame_rings_chains = wf_chains;
     }
@@ -775,19 +736,17 @@ flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFr
      * profiles/r05_tile_order.txt) — k_resolve measures, k_tile_order sorts (below); the order is used, and the cost stamped, by the frame kernel only: `measured` */
     const bool adaptive = ctx->adaptive_order && (!front || tiles < (uint32_t)FLX_ADAPTIVE_FRONT_MAX_TILES_PER_CU * cus) && groups == 1 && fr.frames <= 1u && !ctx->d_tile_order && cnt == nullptr;
     const int orderMode = 1;                                  /* sixteen classes, heaviest first (k_tile_order) */
-    if (adaptive && ctx->tile_time_cap < tiles) {
+    if (adaptive && !(ctx->d_tile_time.fits(tiles) && ctx->d_auto_order.fits(tiles))) {
       FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      for (void *b : { (void *)ctx->d_tile_time, (void *)ctx->d_auto_order }) if (b) (void)hipFree(b);
-      ctx->d_tile_time = nullptr; ctx->d_auto_order = nullptr; ctx->tile_time_cap = 0; ctx->auto_order_tiles = 0;
-      FLX_HIP(ctx, hipMalloc(&ctx->d_tile_time, (size_t)tiles * sizeof(float)));
-      FLX_HIP(ctx, hipMalloc(&ctx->d_auto_order, (size_t)tiles * sizeof(uint32_t)));
-      ctx->tile_time_cap = tiles;
+      ctx->auto_order_tiles = 0;
+      flx_status s;
+      if ((s = ctx->d_tile_time.ensure(ctx, tiles)) || (s = ctx->d_auto_order.ensure(ctx, tiles))) return s;
     }
     if (adaptive && !(ctx->auto_order_tiles == tiles && ctx->auto_order_width == fr.width && ctx->auto_order_rows == fr.rows && ctx->auto_order_mode == orderMode)) {
       ctx->auto_order_tiles = 0;                              /* another shape: this frame in screen order, measured from zero */
       FLX_HIP(ctx, hipMemsetAsync(ctx->d_tile_time, 0, (size_t)tiles * sizeof(float), ctx->stream));
     }
-    const size_t listSlice = ctx->live_capacity / (size_t)groups;
+    const size_t listSlice = std::min(ctx->d_live[0].capacity(), ctx->d_live[1].capacity()) / (size_t)groups;
     if (groups > 1) {
       FLX_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
       for (int g = 1; g < groups; g++) FLX_HIP(ctx, hipStreamWaitEvent(ctx->aux_stream[g - 1], ctx->ev_fork, 0));
@@ -803,8 +762,8 @@ flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFr
       wb.tileOrder = (groups == 1 && ctx->d_tile_order && ctx->tile_order_n == tiles) ? ctx->d_tile_order : nullptr;
       if (!wb.tileOrder && adaptive && ctx->auto_order_tiles == tiles && ctx->auto_order_width == fr.width && ctx->auto_order_rows == fr.rows && ctx->auto_order_mode == orderMode)
         wb.tileOrder = ctx->d_auto_order;                     /* made by the last frame of this shape */
-      wb.tileCost = (cnt && ctx->d_tile_cost && ctx->tile_cost_n >= tiles) ? ctx->d_tile_cost : nullptr;
-      wb.tileCostPrimary = (wb.tileCost && ctx->tile_cost_n >= 2u * tiles) ? 1u : 0u;
+      wb.tileCost = (cnt && ctx->d_tile_cost && ctx->d_tile_cost.capacity() >= tiles) ? ctx->d_tile_cost : nullptr;
+      wb.tileCostPrimary = (wb.tileCost && ctx->d_tile_cost.capacity() >= 2u * tiles) ? 1u : 0u;
       wb.live[0] = ctx->d_live[0] + listSlice * g; wb.live[1] = ctx->d_live[1] + listSlice * g;
       wb.counts = ctx->d_wfcounts + (size_t)g * 2 * (WF_MAX_BOUNCES + 2); wb.walkQueue = wb.counts + (WF_MAX_BOUNCES + 2);
       wb.item_base = t0 * perTile; wb.item_count = (t1 - t0) * perTile;
@@ -869,9 +828,9 @@ static flx_status run_post_frame(flx_context *ctx, const DeviceScene &sc, const 
     if (ctx->ring_n != N || ctx->ring_w != fr.width || ctx->ring_h != fr.height ||
         ctx->ring_tile_rows != fr.tile_rows || ctx->ring_tile_index != fr.tile_index || ctx->ring_tile_count != fr.tile_count) {
       ctx->ring_n = 0;                     /* (re)allocation in progress: a failure below leaves no size to match */
-      for (auto &ring : ctx->d_ring) for (uint32_t *&plane : ring) if (plane) { FLX_HIP(ctx, hipFree(plane)); plane = nullptr; }
+      for (auto &ring : ctx->d_ring) for (auto &plane : ring) if ((s = plane.release(ctx))) return s;
       for (int r = 0; r < 4; r++) for (int i = 0; i < N; i++) {
-        FLX_HIP(ctx, hipMalloc(&ctx->d_ring[r][i], pixels * sizeof(uint32_t)));
+        if ((s = ctx->d_ring[r][i].ensure(ctx, pixels))) return s;
         FLX_HIP(ctx, hipMemsetAsync(ctx->d_ring[r][i], 0, pixels * sizeof(uint32_t), ctx->stream));
       }
       ctx->ring_n = N; ctx->ring_head = 0; ctx->ring_w = fr.width; ctx->ring_h = fr.height;
@@ -923,9 +882,9 @@ extern "C" flx_status flx_temporal_reset(flx_context *ctx) {
   if (!ctx) return FLX_ERR_INVALID;
   FLX_HIP(ctx, hipSetDevice(ctx->device));
   FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (auto &ring : ctx->d_ring) for (uint32_t *&plane : ring) if (plane) { FLX_HIP(ctx, hipFree(plane)); plane = nullptr; }
   ctx->ring_n = 0; ctx->ring_head = 0; ctx->ring_w = ctx->ring_h = 0;
   ctx->ring_tile_rows = ctx->ring_tile_index = ctx->ring_tile_count = 0;
+  for (auto &ring : ctx->d_ring) for (auto &plane : ring) { flx_status s = plane.release(ctx); if (s) return s; }
   return FLX_OK;
 }
 
@@ -940,11 +899,10 @@ extern "C" flx_status flx_set_wavefront_groups(flx_context *ctx, int groups) {
 static flx_status aa_prepare(flx_context *ctx, uint32_t w, uint32_t h) {
   if (w == 0 || h == 0) return fail(ctx, FLX_ERR_INVALID, "anti-aliasing pass: empty frame");
   const size_t pixels = (size_t)w * h;
-  if (ctx->aa_capacity < pixels) {
-    ctx->aa_capacity = 0;
-    for (auto &pl : ctx->d_aa) { if (pl) { FLX_HIP(ctx, hipFree(pl)); pl = nullptr; } FLX_HIP(ctx, hipMalloc(&pl, pixels * sizeof(uint32_t))); }
-    ctx->aa_capacity = pixels;
-    ctx->aa_w = 0;
+  for (auto &pl : ctx->d_aa) {
+    if (!pl.fits(pixels)) ctx->aa_w = 0;              /* a new plane: the ring starts again, as for a new size */
+    flx_status s = pl.ensure(ctx, pixels);
+    if (s) return s;
   }
   if (ctx->aa_w != w || ctx->aa_h != h) {            /* new size: the ring starts from zero textures, like buildTexture() */
     ctx->aa_w = w; ctx->aa_h = h; ctx->taa_head = 0; ctx->taa_filled = 0;
@@ -994,11 +952,7 @@ static flx_status aa_host(flx_context *ctx, int which, uint32_t width, uint32_t 
   FLX_HIP(ctx, hipSetDevice(ctx->device));
   const size_t pixels = (size_t)width * height;
   if (pixels == 0) return fail(ctx, FLX_ERR_INVALID, "anti-aliasing pass: empty frame");
-  if (ctx->aa_io_capacity < pixels) {
-    ctx->aa_io_capacity = 0;
-    for (auto &b : ctx->d_aa_io) { if (b) { FLX_HIP(ctx, hipFree(b)); b = nullptr; } FLX_HIP(ctx, hipMalloc(&b, pixels * sizeof(float4))); }
-    ctx->aa_io_capacity = pixels;
-  }
+  for (auto &b : ctx->d_aa_io) { flx_status es = b.ensure(ctx, pixels); if (es) return es; }
   FLX_HIP(ctx, hipMemcpyAsync(ctx->d_aa_io[0], in_rgba, pixels * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
   flx_status s = which == 0 ? flx_fxaa_device(ctx, width, height, ctx->d_aa_io[0], ctx->d_aa_io[1]) : flx_taa_device(ctx, width, height, ctx->d_aa_io[0], ctx->d_aa_io[1]);
   if (s) return s;
@@ -1024,11 +978,7 @@ extern "C" flx_status flx_present(flx_context *ctx, uint32_t width, uint32_t hei
   FLX_HIP(ctx, hipSetDevice(ctx->device));
   const size_t pixels = (size_t)width * height;
   if (pixels == 0) return fail(ctx, FLX_ERR_INVALID, "flx_present: empty frame");
-  if (ctx->aa_io_capacity < pixels) {
-    ctx->aa_io_capacity = 0;
-    for (auto &b : ctx->d_aa_io) { if (b) { FLX_HIP(ctx, hipFree(b)); b = nullptr; } FLX_HIP(ctx, hipMalloc(&b, pixels * sizeof(float4))); }
-    ctx->aa_io_capacity = pixels;
-  }
+  for (auto &b : ctx->d_aa_io) { flx_status es = b.ensure(ctx, pixels); if (es) return es; }
   FLX_HIP(ctx, hipMemcpyAsync(ctx->d_aa_io[0], in_rgba, pixels * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
   flx_status s = flx_present_device(ctx, width, height, ctx->d_aa_io[0], ctx->d_aa_io[1]);
   if (s) return s;
@@ -1154,18 +1104,15 @@ static flx_status run_filter_batch(flx_context *ctx, const DeviceScene &sc, cons
   flx_status s;
   /* the five RGBA8 render targets of every frame of the batch: 20 bytes per pixel (not the float G-buffers' 96), refused with
    * advice when they do not fit */
-  if (ctx->qbatch_capacity < pixels) {
+  if (ctx->d_qbatch.capacity() < 5 * pixels) {
     const size_t need = 5 * pixels * sizeof(uint32_t);
     size_t memFree = 0, memTotal = 0;
-    if (hipMemGetInfo(&memFree, &memTotal) == hipSuccess && need > memFree + 5 * ctx->qbatch_capacity * sizeof(uint32_t)) {
+    if (hipMemGetInfo(&memFree, &memTotal) == hipSuccess && need > memFree + ctx->d_qbatch.capacity() * sizeof(uint32_t)) {
       char msg[200];
       snprintf(msg, sizeof msg, "the render targets of this batch of filter frames need %.1f GB of device memory, %.1f GB are free: render fewer frames per batch", need / 1e9, memFree / 1e9);
       return fail(ctx, FLX_ERR_DEVICE, msg);
     }
-    ctx->qbatch_capacity = 0;
-    if (ctx->d_qbatch) { FLX_HIP(ctx, hipFree(ctx->d_qbatch)); ctx->d_qbatch = nullptr; }
-    FLX_HIP(ctx, hipMalloc(&ctx->d_qbatch, need));
-    ctx->qbatch_capacity = pixels;
+    if ((s = ctx->d_qbatch.ensure(ctx, 5 * pixels))) return s;
   }
   if ((s = ensure_post_buffers(ctx, per, false, true))) return s;
   FilterPlanes pl;
@@ -1210,7 +1157,7 @@ extern "C" flx_status flx_render_batch(flx_context *ctx, const flx_frame_params 
   if (s) return s;
   const size_t pixels = (size_t)fr.rows * fr.width;
   if (pixels == 0) return FLX_OK;
-  if ((s = flx_ensure_pixels(ctx, &ctx->d_out, &ctx->out_capacity, pixels))) return s;
+  if ((s = ctx->d_out.ensure(ctx, pixels))) return s;
   const bool saved = ctx->counters_enabled;
   if (counters) ctx->counters_enabled = true;
   if (params->use_filter) {
@@ -1235,23 +1182,8 @@ extern "C" flx_status flx_render_batch(flx_context *ctx, const flx_frame_params 
 /* ---- filter frames across GPUs: the trace is per pixel and shards by row strips, the denoise chain is not ---- */
 static flx_status ensure_post_buffers(flx_context *ctx, size_t pixels, bool gbuffers, bool planes) {
   flx_status s;
-  if (gbuffers && ctx->gb_capacity < pixels) {
-    ctx->gb_capacity = 0;                 /* a failed allocation below must not leave the old size standing */
-    for (int i = 0; i < 6; i++) {
-      size_t cap = 0;
-      if (ctx->d_gb[i]) { FLX_HIP(ctx, hipFree(ctx->d_gb[i])); ctx->d_gb[i] = nullptr; }
-      if ((s = flx_ensure_pixels(ctx, &ctx->d_gb[i], &cap, pixels))) return s;
-    }
-    ctx->gb_capacity = pixels;
-  }
-  if (planes && ctx->planes_capacity < pixels) {
-    ctx->planes_capacity = 0;                 /* a failed allocation below must not leave the old size standing */
-    for (int i = 0; i < 13; i++) {
-      if (ctx->d_planes[i]) { FLX_HIP(ctx, hipFree(ctx->d_planes[i])); ctx->d_planes[i] = nullptr; }
-      FLX_HIP(ctx, hipMalloc(&ctx->d_planes[i], pixels * sizeof(uint32_t)));
-    }
-    ctx->planes_capacity = pixels;
-  }
+  if (gbuffers) for (auto &b : ctx->d_gb) if ((s = b.ensure(ctx, pixels))) return s;
+  if (planes) for (auto &b : ctx->d_planes) if ((s = b.ensure(ctx, pixels))) return s;
   return FLX_OK;
 }
 
@@ -1324,7 +1256,7 @@ extern "C" flx_status flx_render(flx_context *ctx, const flx_frame_params *param
   if (gbuffers && !params->use_filter && !params->is_temporal) return fail(ctx, FLX_ERR_INVALID, "flx_render: G-buffers are only produced with use_filter = 1 or is_temporal = 1");
   const size_t pixels = (size_t)fr.rows * fr.width;
   if (pixels == 0) return FLX_OK;
-  if ((s = flx_ensure_pixels(ctx, &ctx->d_out, &ctx->out_capacity, pixels))) return s;
+  if ((s = ctx->d_out.ensure(ctx, pixels))) return s;
   const bool saved = ctx->counters_enabled;
   if (counters) ctx->counters_enabled = true;
   if (params->use_filter || params->is_temporal) {
@@ -1375,7 +1307,7 @@ extern "C" flx_status flx_raster_render(flx_context *ctx, const flx_frame_params
   const size_t pixels = (size_t)fr.rows * fr.width;
   float4 *dst = (float4 *)d_out_rgba;
   if (!dst && pixels) {
-    if ((s = flx_ensure_pixels(ctx, &ctx->d_out, &ctx->out_capacity, pixels))) return s;
+    if ((s = ctx->d_out.ensure(ctx, pixels))) return s;
     dst = ctx->d_out;
   }
   unsigned long long *cnt = counters ? ctx->d_counters : nullptr;
@@ -1411,10 +1343,10 @@ extern "C" flx_status flx_raster_render(flx_context *ctx, const flx_frame_params
 static void mirror_scene(flx_context *ctx) {
   flx_context *t = ctx->twin;
   if (!t) return;
-  t->d_geometry = ctx->d_geometry; t->d_attributes = ctx->d_attributes; t->d_ids = ctx->d_ids; t->d_walk = ctx->d_walk;
-  t->d_fwd = ctx->d_fwd; t->fwd_entries = ctx->fwd_entries; t->fwd_root = ctx->fwd_root; t->lock_ok = ctx->lock_ok; t->lock_use = ctx->lock_use; t->lock_boxes = ctx->lock_boxes;
+  t->d_geometry.borrow(ctx->d_geometry); t->d_attributes.borrow(ctx->d_attributes); t->d_ids.borrow(ctx->d_ids); t->d_walk.borrow(ctx->d_walk);
+  t->d_fwd.borrow(ctx->d_fwd); t->fwd_entries = ctx->fwd_entries; t->fwd_root = ctx->fwd_root; t->lock_ok = ctx->lock_ok; t->lock_use = ctx->lock_use; t->lock_boxes = ctx->lock_boxes;
   t->walk_entries = ctx->walk_entries; t->walk_hot = ctx->walk_hot; t->walk_root = ctx->walk_root; t->walk_fast_boxes = ctx->walk_fast_boxes;
-  for (int i = 0; i < 3; i++) { t->d_atlas[i] = ctx->d_atlas[i]; t->atlas_w[i] = ctx->atlas_w[i]; t->atlas_h[i] = ctx->atlas_h[i]; }
+  for (int i = 0; i < 3; i++) { t->d_atlas[i].borrow(ctx->d_atlas[i]); t->atlas_w[i] = ctx->atlas_w[i]; t->atlas_h[i] = ctx->atlas_h[i]; }
   t->n_entries = ctx->n_entries; t->n_ids = ctx->n_ids; t->max_transform = ctx->max_transform; t->have_scene = ctx->have_scene;
   t->geometry_version = ctx->geometry_version; t->angle_table = ctx->angle_table;      /* (the lane's own angle table follows: flx_make_frame) */
 }
@@ -1477,12 +1409,12 @@ static flx_status dyn_flush(flx_context *ctx) {
   const uint32_t tv = ctx->transforms_version;
   if (stale & 1u) {
     const std::vector<float> r = ctx->h_rotation, sh = ctx->h_shift;
-    if ((s = upload(ctx, &ctx->d_rotation, r.data(), r.size() * sizeof(float)))) return s;
-    if ((s = upload(ctx, &ctx->d_shift, sh.data(), sh.size() * sizeof(float)))) return s;
+    if ((s = upload(ctx, ctx->d_rotation, r.data(), r.size() * sizeof(float)))) return s;
+    if ((s = upload(ctx, ctx->d_shift, sh.data(), sh.size() * sizeof(float)))) return s;
   }
   if (stale & 2u) {
     const std::vector<float> l = ctx->h_lights;
-    if ((s = upload(ctx, &ctx->d_lights, l.data(), l.size() * sizeof(float)))) return s;
+    if ((s = upload(ctx, ctx->d_lights, l.data(), l.size() * sizeof(float)))) return s;
   }
   ctx->scene_version = sv; ctx->dyn_version = dv; ctx->transforms_version = tv;      /* (the same contents the versions were counted for) */
   return FLX_OK;
@@ -1519,27 +1451,24 @@ static flx_status server_allocate(flx_context *ctx, const DeviceFrame &frOne, ui
      * their own: the launch goes to the lowest. */
     int prLow = 0, prHigh = 0;
     FLX_HIP(ctx, hipDeviceGetStreamPriorityRange(&prLow, &prHigh));
-    FLX_HIP(ctx, hipStreamCreateWithPriority(&ctx->sv_stream, hipStreamNonBlocking, prLow));
-    FLX_HIP(ctx, hipMalloc(&ctx->d_sv_slots, SV_MAX_DEPTH * sizeof(ServerSlot)));
-    FLX_HIP(ctx, hipHostMalloc((void **)&ctx->h_sv_mail, sizeof(ServerMail), hipHostMallocMapped | hipHostMallocCoherent));
+    if (!ctx->sv_stream) FLX_HIP(ctx, hipStreamCreateWithPriority(&ctx->sv_stream, hipStreamNonBlocking, prLow));
+    if ((s = ctx->h_sv_mail.ensure(ctx, 1, hipHostMallocMapped | hipHostMallocCoherent))) return s;
     memset(ctx->h_sv_mail, 0, sizeof(ServerMail));
     FLX_HIP(ctx, hipHostGetDevicePointer((void **)&ctx->d_sv_mail, ctx->h_sv_mail, 0));
-    FLX_HIP(ctx, hipMalloc(&ctx->d_sv_relay, sizeof(ServerMail)));
+    if ((s = ctx->d_sv_relay.ensure(ctx, 1))) return s;
     const size_t ringWords = (size_t)cus * server_rings_per_group();
-    FLX_HIP(ctx, hipMalloc(&ctx->d_sv_rings, ringWords * sizeof(uint32_t)));
+    if ((s = ctx->d_sv_rings.ensure(ctx, ringWords))) return s;
     FLX_HIP(ctx, hipMemsetAsync(ctx->d_sv_rings, 0xff, ringWords * sizeof(uint32_t), ctx->stream));      /* WF_INVALID everywhere; a launch leaves them so */
-    FLX_HIP(ctx, hipMalloc(&ctx->d_sv_stats, SV_STAT_TOTAL * sizeof(unsigned long long)));
-    FLX_HIP(ctx, hipMalloc(&ctx->d_sv_versions, (size_t)cus * SV_MAX_DEPTH * SV_BLOB_WORDS * sizeof(uint32_t)));      /* (3 MB at 256 CUs) */
+    if ((s = ctx->d_sv_stats.ensure(ctx, SV_STAT_TOTAL))) return s;
+    if ((s = ctx->d_sv_versions.ensure(ctx, (size_t)cus * SV_MAX_DEPTH * SV_BLOB_WORDS))) return s;      /* (3 MB at 256 CUs) */
+    if ((s = ctx->d_sv_slots.ensure(ctx, SV_MAX_DEPTH))) return s;      /* (last: this block runs until it is there) */
   }
   int chains = 1;
   if ((s = ensure_workspace(ctx, fr, 3, false, chains))) return s;
   const size_t P1 = (size_t)frOne.rows * frOne.width;
-  if (!ctx->sv_target_slots && ctx->sv_out_capacity < SV_MAX_DEPTH * P1) {      /* (with a frame target the launch resolves into the caller's images) */
+  if (!ctx->sv_target_slots && ctx->d_sv_out.capacity() < SV_MAX_DEPTH * P1) {      /* (with a frame target the launch resolves into the caller's images) */
     FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->sv_out_capacity = 0;
-    if (ctx->d_sv_out) { FLX_HIP(ctx, hipFree(ctx->d_sv_out)); ctx->d_sv_out = nullptr; }
-    FLX_HIP(ctx, hipMalloc(&ctx->d_sv_out, SV_MAX_DEPTH * P1 * sizeof(float4)));
-    ctx->sv_out_capacity = SV_MAX_DEPTH * P1;
+    if ((s = ctx->d_sv_out.ensure(ctx, SV_MAX_DEPTH * P1))) return s;
   }
   /* a workgroup's list of the screen tiles it made of a frame: a few times its even share (its tiles come to it as it asks for them) */
   const size_t tilesPerSlot0 = itemsPerSlot / ((size_t)fr.samples * 64u);
@@ -1548,8 +1477,7 @@ static flx_status server_allocate(flx_context *ctx, const DeviceFrame &frOne, ui
   if (tcap < FLX_SERVER_TILE_LIST_MIN) tcap = FLX_SERVER_TILE_LIST_MIN;
   if (ctx->sv_tile_cap < tcap) {
     ctx->sv_tile_cap = 0;
-    if (ctx->d_sv_tiles) { FLX_HIP(ctx, hipFree(ctx->d_sv_tiles)); ctx->d_sv_tiles = nullptr; }
-    FLX_HIP(ctx, hipMalloc(&ctx->d_sv_tiles, (size_t)cus * SV_MAX_DEPTH * tcap * sizeof(uint32_t)));
+    if ((s = ctx->d_sv_tiles.ensure(ctx, (size_t)cus * SV_MAX_DEPTH * tcap))) return s;
     ctx->sv_tile_cap = tcap;
   }
   if (!ctx->copy_stream) {
@@ -1662,7 +1590,7 @@ static flx_status server_post(flx_context *ctx, const flx_frame_params *params, 
     if (ver) {
       const size_t versions = (size_t)cusWalk * depth;
       sa.blobWords = server_blob_words(ctx->n_transforms, ctx->n_lights);
-      scL.rotation = (const float4 *)ctx->d_sv_versions;
+      scL.rotation = (const float4 *)ctx->d_sv_versions.get();
       scL.shift = (const float4 *)(ctx->d_sv_versions + versions * ctx->n_transforms * 24u);
       scL.lights = (const float *)(ctx->d_sv_versions + versions * ctx->n_transforms * 32u);
     }
@@ -1759,21 +1687,11 @@ static flx_status frame_begin_on(flx_context *ctx, const flx_frame_params *param
   /* (hipMalloc / hipFree / hipHostMalloc wait for the device: with the frame server's launch running they would wait for its end — which waits for this
    * frame.  A slot that has to grow ends the launch first; the next frame starts another.) */
   const bool served = chained == 2 && !gathered && pixels;      /* (a frame of the server is handed out from the launch's own images, or the caller's: it needs no device slot) */
-  if (ctx->sv_running && ((!served && (ctx->slot_capacity[k] < (pixels ? pixels : 1) || !ctx->d_slot[k])) || (format != FLX_FRAME_DEVICE && (ctx->h_slot_capacity[k] < bytes || !ctx->h_slot[k]))))
+  if (ctx->sv_running && ((!served && !ctx->d_slot[k].fits(pixels)) || (format != FLX_FRAME_DEVICE && !ctx->h_slot[k].fits(bytes))))
     if ((s = flx_server_stop(ctx))) return s;
-  if (!served && (s = flx_ensure_pixels(ctx, &ctx->d_slot[k], &ctx->slot_capacity[k], pixels ? pixels : 1))) return s;
-  if (format == FLX_FRAME_RGBA8 && !served && ctx->slot8_capacity[k] < pixels) {      /* (a frame of the server is quantised where it is resolved) */
-    ctx->slot8_capacity[k] = 0;
-    if (ctx->d_slot8[k]) { FLX_HIP(ctx, hipFree(ctx->d_slot8[k])); ctx->d_slot8[k] = nullptr; }
-    FLX_HIP(ctx, hipMalloc(&ctx->d_slot8[k], (pixels ? pixels : 1) * sizeof(uint32_t)));
-    ctx->slot8_capacity[k] = pixels;
-  }
-  if (format != FLX_FRAME_DEVICE && (ctx->h_slot_capacity[k] < bytes || !ctx->h_slot[k])) {
-    ctx->h_slot_capacity[k] = 0;
-    if (ctx->h_slot[k]) { FLX_HIP(ctx, hipHostFree(ctx->h_slot[k])); ctx->h_slot[k] = nullptr; }
-    FLX_HIP(ctx, hipHostMalloc(&ctx->h_slot[k], bytes ? bytes : 16, hipHostMallocDefault));
-    ctx->h_slot_capacity[k] = bytes;
-  }
+  if (!served && (s = ctx->d_slot[k].ensure(ctx, pixels))) return s;
+  if (format == FLX_FRAME_RGBA8 && !served && pixels && (s = ctx->d_slot8[k].ensure(ctx, pixels))) return s;      /* (a frame of the server is quantised where it is resolved) */
+  if (format != FLX_FRAME_DEVICE && !ctx->h_slot[k].fits(bytes) && (s = ctx->h_slot[k].ensure(ctx, bytes ? bytes : 16, hipHostMallocDefault))) return s;
   if (served) {
     /* the frame server: the frame is posted to the running launch; flx_frame_end takes it (server_take) */
     uint32_t seq = 0, sslot = 0;
@@ -1942,16 +1860,15 @@ extern "C" flx_status flx_debug_set_tile_order(flx_context *ctx, const uint32_t 
   if (s) return s;
   FLX_HIP(ctx, hipSetDevice(ctx->device));
   FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->d_tile_order) { (void)hipFree(ctx->d_tile_order); ctx->d_tile_order = nullptr; }
   ctx->tile_order_n = 0;
-  if (n == 0u) return FLX_OK;
+  if ((s = ctx->d_tile_order.release(ctx)) || n == 0u) return s;
   if (!order) return fail(ctx, FLX_ERR_INVALID, "flx_debug_set_tile_order: no order");
   std::vector<uint8_t> seen(n, 0);
   for (uint32_t q = 0; q < n; q++) {
     if (order[q] >= n || seen[order[q]]) return fail(ctx, FLX_ERR_INVALID, "flx_debug_set_tile_order: not a permutation of the frame's tiles");
     seen[order[q]] = 1;
   }
-  FLX_HIP(ctx, hipMalloc(&ctx->d_tile_order, (size_t)n * sizeof(uint32_t)));
+  if ((s = ctx->d_tile_order.ensure(ctx, n))) return s;
   FLX_HIP(ctx, hipMemcpy(ctx->d_tile_order, order, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
   ctx->tile_order_n = n;
   return FLX_OK;
@@ -1970,16 +1887,15 @@ extern "C" flx_status flx_debug_tile_order_of(flx_context *ctx, const float *cos
   if (!ctx || !cost || !order || n == 0u) return FLX_ERR_INVALID;
   if (mode < 0 || mode > 1) return fail(ctx, FLX_ERR_INVALID, "flx_debug_tile_order_of: mode 0 (the lightest tenth last) or 1 (sixteen classes, heaviest first)");
   FLX_HIP(ctx, hipSetDevice(ctx->device));
-  float *d_c = nullptr; uint32_t *d_o = nullptr;
-  FLX_HIP(ctx, hipMalloc(&d_c, (size_t)n * sizeof(float)));
-  if (hipMalloc(&d_o, (size_t)n * sizeof(uint32_t)) != hipSuccess) { (void)hipFree(d_c); return fail(ctx, FLX_ERR_DEVICE, "flx_debug_tile_order_of: hipMalloc"); }
-  hipError_t e = hipMemcpy(d_c, cost, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d_o, 0xff, (size_t)n * sizeof(uint32_t));
-  if (e == hipSuccess) { launch_tile_order(d_c, d_o, n, mode, ctx->stream); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = hipMemcpy(order, d_o, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-  (void)hipFree(d_c); (void)hipFree(d_o);
-  if (e != hipSuccess) return fail(ctx, FLX_ERR_DEVICE, hipGetErrorString(e));
+  DeviceBuffer<float> d_c; DeviceBuffer<uint32_t> d_o;      /* freed on every way out */
+  flx_status s;
+  if ((s = d_c.ensure(ctx, n)) || (s = d_o.ensure(ctx, n))) return s;
+  FLX_HIP(ctx, hipMemcpy(d_c, cost, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  FLX_HIP(ctx, hipMemset(d_o, 0xff, (size_t)n * sizeof(uint32_t)));
+  launch_tile_order(d_c, d_o, n, mode, ctx->stream);
+  FLX_HIP(ctx, hipGetLastError());
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  FLX_HIP(ctx, hipMemcpy(order, d_o, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return FLX_OK;
 }
 /* Counted frames add, per 8 x 8 screen tile, the entries its paths' walks visited (bounce loop only): n > 0 turns that on for frames of up to n tiles and zeroes the sums,
@@ -1989,13 +1905,14 @@ extern "C" flx_status flx_debug_tile_cost(flx_context *ctx, unsigned long long *
   if (ctx->fifo_n) return fail(ctx, FLX_ERR_INVALID, "flx_debug_tile_cost: frames are in flight");
   FLX_HIP(ctx, hipSetDevice(ctx->device));
   FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (out && ctx->d_tile_cost) FLX_HIP(ctx, hipMemcpy(out, ctx->d_tile_cost, (size_t)(n && n < ctx->tile_cost_n ? n : ctx->tile_cost_n) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  if (n != ctx->tile_cost_n) {
-    if (ctx->d_tile_cost) { (void)hipFree(ctx->d_tile_cost); ctx->d_tile_cost = nullptr; }
-    ctx->tile_cost_n = 0;
-    if (n) { FLX_HIP(ctx, hipMalloc(&ctx->d_tile_cost, (size_t)n * sizeof(unsigned long long))); ctx->tile_cost_n = n; }
+  const size_t had = ctx->d_tile_cost.capacity();
+  if (out && had) FLX_HIP(ctx, hipMemcpy(out, ctx->d_tile_cost, (n && n < had ? n : had) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (n != had) {
+    flx_status s = ctx->d_tile_cost.release(ctx);
+    if (!s && n) s = ctx->d_tile_cost.ensure(ctx, n);
+    if (s) return s;
   }
-  if (ctx->d_tile_cost) FLX_HIP(ctx, hipMemset(ctx->d_tile_cost, 0, (size_t)ctx->tile_cost_n * sizeof(unsigned long long)));
+  if (n) FLX_HIP(ctx, hipMemset(ctx->d_tile_cost, 0, (size_t)n * sizeof(unsigned long long)));
   return FLX_OK;
 }
 /* the shading's per-triangle table (DeviceScene::angle_tan) off: every shade computes the values itself, as before round 4 — for A/B runs and the test that both agree */
@@ -2246,26 +2163,20 @@ extern "C" flx_status flx_debug_math(flx_context *ctx, int fn, const float *a, c
   if (!ctx || !a || !out) return FLX_ERR_INVALID;
   if (n == 0) return FLX_OK;
   FLX_HIP(ctx, hipSetDevice(ctx->device));
-  float *d_a = nullptr, *d_b = nullptr, *d_o = nullptr;
-  FLX_HIP(ctx, hipMalloc(&d_a, (size_t)n * 4));
-  FLX_HIP(ctx, hipMalloc(&d_o, (size_t)n * 4));
+  DeviceBuffer<float> d_a, d_b, d_o;                       /* freed on every way out */
+  flx_status s;
+  if ((s = d_a.ensure(ctx, n)) || (s = d_o.ensure(ctx, n))) return s;
   FLX_HIP(ctx, hipMemcpy(d_a, a, (size_t)n * 4, hipMemcpyHostToDevice));
   if (b) {
-    FLX_HIP(ctx, hipMalloc(&d_b, (size_t)n * 4));
+    if ((s = d_b.ensure(ctx, n))) return s;
     FLX_HIP(ctx, hipMemcpy(d_b, b, (size_t)n * 4, hipMemcpyHostToDevice));
   }
   launch_debug_math(fn, d_a, d_b, d_o, n, ctx->stream);
   FLX_HIP(ctx, hipGetLastError());
   FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   FLX_HIP(ctx, hipMemcpy(out, d_o, (size_t)n * 4, hipMemcpyDeviceToHost));
-  (void)hipFree(d_a); (void)hipFree(d_o); if (d_b) (void)hipFree(d_b);
   return FLX_OK;
 }
-
-struct DeviceScratch {                 /* a device buffer of a debug hook */
-  void *p = nullptr;
-  ~DeviceScratch() { if (p) (void)hipFree(p); }
-};
 
 extern "C" flx_status flx_debug_intersect(flx_context *ctx, int fn, const float *in, float *out, uint32_t n) {
   if (!ctx || !in || !out) return FLX_ERR_INVALID;
@@ -2273,14 +2184,14 @@ extern "C" flx_status flx_debug_intersect(flx_context *ctx, int fn, const float 
   if (n == 0) return FLX_OK;
   FLX_HIP(ctx, hipSetDevice(ctx->device));
   const size_t nin = (size_t)n * ((fn == 2 || fn == 5 || fn == 6) ? 13u : 16u), nout = (size_t)n * ((fn == 0 || fn == 3) ? 3u : 1u);
-  DeviceScratch d_in, d_out;                               /* freed on every way out */
-  FLX_HIP(ctx, hipMalloc(&d_in.p, nin * 4));
-  FLX_HIP(ctx, hipMalloc(&d_out.p, nout * 4));
-  FLX_HIP(ctx, hipMemcpy(d_in.p, in, nin * 4, hipMemcpyHostToDevice));
-  launch_debug_intersect(fn, (const float *)d_in.p, (float *)d_out.p, n, ctx->stream);
+  DeviceBuffer<float> d_in, d_out;                         /* freed on every way out */
+  flx_status s;
+  if ((s = d_in.ensure(ctx, nin)) || (s = d_out.ensure(ctx, nout))) return s;
+  FLX_HIP(ctx, hipMemcpy(d_in, in, nin * 4, hipMemcpyHostToDevice));
+  launch_debug_intersect(fn, d_in, d_out, n, ctx->stream);
   FLX_HIP(ctx, hipGetLastError());
   FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  FLX_HIP(ctx, hipMemcpy(out, d_out.p, nout * 4, hipMemcpyDeviceToHost));
+  FLX_HIP(ctx, hipMemcpy(out, d_out, nout * 4, hipMemcpyDeviceToHost));
   return FLX_OK;
 }
 
@@ -2302,15 +2213,14 @@ extern "C" flx_status flx_debug_walk(flx_context *ctx, int variant, const float 
   DeviceScene sc; DeviceFrame fr;
   flx_status st = flx_make_frame(ctx, &p, sc, fr);
   if (st != FLX_OK) return st;
-  DeviceScratch d_in, d_out;                               /* freed on every way out */
-  FLX_HIP(ctx, hipMalloc(&d_in.p, (size_t)n * 7 * 4));
-  FLX_HIP(ctx, hipMalloc(&d_out.p, (size_t)n * 8 * 4));
-  FLX_HIP(ctx, hipMemcpy(d_in.p, rays, (size_t)n * 7 * 4, hipMemcpyHostToDevice));
-  const bool ok = launch_debug_walk(variant, sc, (const float *)d_in.p, (float *)d_out.p, n, ctx->stream);
+  DeviceBuffer<float> d_in, d_out;                         /* freed on every way out */
+  if ((st = d_in.ensure(ctx, (size_t)n * 7)) || (st = d_out.ensure(ctx, (size_t)n * 8))) return st;
+  FLX_HIP(ctx, hipMemcpy(d_in, rays, (size_t)n * 7 * 4, hipMemcpyHostToDevice));
+  const bool ok = launch_debug_walk(variant, sc, d_in, d_out, n, ctx->stream);
   if (ok) {
     FLX_HIP(ctx, hipGetLastError());
     FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    FLX_HIP(ctx, hipMemcpy(out, d_out.p, (size_t)n * 8 * 4, hipMemcpyDeviceToHost));
+    FLX_HIP(ctx, hipMemcpy(out, d_out, (size_t)n * 8 * 4, hipMemcpyDeviceToHost));
   }
   return ok ? FLX_OK : fail(ctx, FLX_ERR_INVALID, "flx_debug_walk: this scene does not have that walk (variant 2 needs the lockstep copy: at most 128 entries in one object space)");
 }
@@ -2326,15 +2236,14 @@ extern "C" flx_status flx_debug_walk_staged(flx_context *ctx, uint32_t lds_count
   flx_status st = flx_make_frame(ctx, &p, sc, fr);
   if (st != FLX_OK) return st;
   const uint32_t staged = lds_count < sc.walk_hot ? lds_count : sc.walk_hot;
-  DeviceScratch d_in, d_out;                               /* freed on every way out */
-  FLX_HIP(ctx, hipMalloc(&d_in.p, (size_t)n * 7 * 4));
-  FLX_HIP(ctx, hipMalloc(&d_out.p, (size_t)n * 10 * 4));
-  FLX_HIP(ctx, hipMemcpy(d_in.p, rays, (size_t)n * 7 * 4, hipMemcpyHostToDevice));
-  if (!launch_debug_walk_staged(sc, staged, (const float *)d_in.p, (float *)d_out.p, n, ctx->stream))
+  DeviceBuffer<float> d_in, d_out;                         /* freed on every way out */
+  if ((st = d_in.ensure(ctx, (size_t)n * 7)) || (st = d_out.ensure(ctx, (size_t)n * 10))) return st;
+  FLX_HIP(ctx, hipMemcpy(d_in, rays, (size_t)n * 7 * 4, hipMemcpyHostToDevice));
+  if (!launch_debug_walk_staged(sc, staged, d_in, d_out, n, ctx->stream))
     return fail(ctx, FLX_ERR_INVALID, "flx_debug_walk_staged: the staged entries, the transforms and the rays need more LDS than the kernel may have (160 KB)");
   FLX_HIP(ctx, hipGetLastError());
   FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  FLX_HIP(ctx, hipMemcpy(out, d_out.p, (size_t)n * 10 * 4, hipMemcpyDeviceToHost));
+  FLX_HIP(ctx, hipMemcpy(out, d_out, (size_t)n * 10 * 4, hipMemcpyDeviceToHost));
   return FLX_OK;
 }
 

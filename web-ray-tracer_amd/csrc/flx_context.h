@@ -7,7 +7,6 @@
 
 #include <chrono>
 #include <cstdint>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -33,21 +32,58 @@ constexpr int FLX_COUNTER_SLOTS = 80;          /* 8 work counters + 32 scheduler
 
 extern thread_local std::string g_create_error;
 
+struct flx_context;
+
+/* The memory of a context (and of a debug hook's call): `capacity()` elements of T in device memory or, Pinned, in page-locked host memory.  It owns what it
+ * allocated and frees it when it goes; it moves and is not copied.  The one exception is a view made by borrow(): the frame loop's second lane reads the first
+ * lane's static scene arrays through such views and never frees them.  It converts to T *, so launches and copies take it as they took the pointer. */
+template <typename T, bool Pinned = false> struct Buffer {
+  Buffer() = default;
+  Buffer(Buffer &&o) noexcept : p(o.p), n(o.n), owned(o.owned) { o.p = nullptr; o.n = 0; o.owned = true; }
+  Buffer &operator=(Buffer &&o) noexcept {
+    if (this != &o) { (void)hip_free(); p = o.p; n = o.n; owned = o.owned; o.p = nullptr; o.n = 0; o.owned = true; }
+    return *this;
+  }
+  ~Buffer() { (void)hip_free(); }
+  operator T *() const { return p; }
+  T *get() const { return p; }
+  T *operator->() const { return p; }
+  size_t capacity() const { return n; }
+  bool fits(size_t count) const { return p && n >= count; }
+  /* Room for `count` elements (for one where count is 0, so that there is a pointer to hand on): kept when it fits(); else freed FIRST and then allocated — a frame
+   * that grows does not hold both sizes at once.  A failure sets ctx->err like FLX_HIP and leaves the buffer empty: no stale capacity over freed memory.  Neither
+   * waits for the work in flight on purpose: who must, does so before the call.  pinned_flags: hipHostMalloc's. */
+  flx_status ensure(flx_context *ctx, size_t count, unsigned pinned_flags = 0);
+  flx_status release(flx_context *ctx);      /* empty from here on (also where the free fails) */
+  void borrow(const Buffer &o) { (void)hip_free(); p = o.p; n = o.n; owned = false; }
+ private:
+  T *p = nullptr;
+  size_t n = 0;
+  bool owned = true;
+  hipError_t hip_free() {
+    T *mine = owned ? p : nullptr;
+    p = nullptr; n = 0; owned = true;
+    return !mine ? hipSuccess : Pinned ? hipHostFree(mine) : hipFree(mine);
+  }
+};
+template <typename T> using DeviceBuffer = Buffer<T, false>;
+template <typename T> using PinnedBuffer = Buffer<T, true>;
+
 struct flx_context {
   int device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
   std::string err;
   hipDeviceProp_t prop;
   /* resident scene */
-  float4 *d_geometry = nullptr, *d_attributes = nullptr, *d_rotation = nullptr, *d_shift = nullptr;
-  float4 *d_walk = nullptr;                      /* threaded hot-first copy of the skip list */
+  DeviceBuffer<float4> d_geometry, d_attributes, d_rotation, d_shift;      /* (a twin: geometry, attributes, ids, walk, fwd and the atlases are views of the primary's: mirror_scene) */
+  DeviceBuffer<float4> d_walk;                     /* threaded hot-first copy of the skip list */
   uint32_t walk_entries = 0, walk_hot = 0, walk_root = 0, walk_fast_boxes = 0;
-  float4 *d_fwd = nullptr;                       /* the live entries in the reference's order (every successor further on): primary walk, lockstep walk */
+  DeviceBuffer<float4> d_fwd;                      /* the live entries in the reference's order (every successor further on): primary walk, lockstep walk */
   uint32_t fwd_entries = 0, fwd_root = 0, lock_boxes = 0;
   int last_organisation = 0;                     /* flx_last_organisation: what launch_wavefront ran for the last frame (0: another pipeline) */
   flx::WalkLdsLaunch last_walk_lds;                /* flx_debug_last_walk_lds: what the last wavefront or server launch staged of the tree's top (zeros: none since the scene upload) */
   int frame_front = 1;                           /* flx_set_frame_front: the frame kernel traces the primary rays and shades bounce 0 itself (0 two kernels in front, 1 automatic, 2 inside wherever the frame kernel runs, 3 one kernel in front) */
-  uint32_t *d_frame_rings = nullptr;             /* k_wf_frame: per chain and workgroup three rings of WF_FRAME_RING path ids */
+  DeviceBuffer<uint32_t> d_frame_rings;            /* k_wf_frame: per chain and workgroup three rings of WF_FRAME_RING path ids */
   int frame_rings_chains = 0;                    /* chains it has slices for */
   int wf_organisation = 0;                       /* wavefront pipeline: 0 automatic, 1 rounds, 2 frame kernel (flx_set_wavefront_organisation) */
   bool lock_ok = false;                          /* the scene is small and in one object space: its bounce walks may go in lockstep */
@@ -57,59 +93,48 @@ struct flx_context {
   /* Adaptive tile order (flx_debug_set_adaptive_order; on by default): k_resolve sums what every screen tile's paths cost (time in walk lanes), k_tile_order makes the
    * next frame's draw order of it — the lightest tiles last, so that the launch does not end in the chains of a heavy tile's paths.  Frames do not depend on the order. */
   int adaptive_order = 1;
-  float *d_tile_time = nullptr; uint32_t *d_auto_order = nullptr; uint32_t tile_time_cap = 0;
+  DeviceBuffer<float> d_tile_time; DeviceBuffer<uint32_t> d_auto_order;
   uint32_t auto_order_tiles = 0, auto_order_width = 0, auto_order_rows = 0; int auto_order_mode = -1;      /* the frame shape d_auto_order is for (0 tiles: none yet) */
-  uint32_t *d_tile_order = nullptr; uint32_t tile_order_n = 0;      /* flx_debug_set_tile_order: the frame kernel's draw order over the frame's screen tiles */
-  unsigned long long *d_tile_cost = nullptr; uint32_t tile_cost_n = 0;      /* flx_debug_tile_cost: counted frames' visits per screen tile */
-  int32_t *d_ids = nullptr;
-  float *d_lights = nullptr;
-  uchar4 *d_atlas[3] = { nullptr, nullptr, nullptr };
+  DeviceBuffer<uint32_t> d_tile_order; uint32_t tile_order_n = 0;      /* flx_debug_set_tile_order: the frame kernel's draw order over the tile_order_n screen tiles of a frame (used for frames of as many) */
+  DeviceBuffer<unsigned long long> d_tile_cost;      /* flx_debug_tile_cost: counted frames' visits per screen tile, for frames of up to capacity() tiles */
+  DeviceBuffer<int32_t> d_ids;
+  DeviceBuffer<float> d_lights;
+  DeviceBuffer<uchar4> d_atlas[3];
   uint32_t atlas_w[3] = { 0, 0, 0 }, atlas_h[3] = { 0, 0, 0 };
   uint32_t n_entries = 0, n_ids = 0, n_transforms = 0, n_lights = 0;
   uint32_t max_transform = 0;                   /* largest transform number an entry names */
   bool have_scene = false, have_transforms = false, have_lights = false;
   /* DeviceScene::angle_tan: per triangle, from the geometry / attribute arrays and this context's transforms; made again (on this context's stream, in front of
    * the frame that needs it) when any of them changed: angle_key = the versions it was made from */
-  float4 *d_angle_tan = nullptr;
-  size_t angle_capacity = 0;
+  DeviceBuffer<float4> d_angle_tan;
   uint64_t angle_key = ~0ull;
   uint32_t geometry_version = 0;                 /* counts uploads of the geometry / attribute arrays (the second lane copies the primary's: mirror_scene) */
   uint32_t transforms_version = 0;               /* counts uploads of this context's transforms */
   int angle_table = 1;                           /* flx_debug: 0 = the shading computes the values itself */
   /* frame workspace */
-  float4 *d_out = nullptr;
-  size_t out_capacity = 0;                       /* pixels */
-  float4 *d_gb[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-  size_t gb_capacity = 0;
-  uint32_t *d_planes[13] = {};                   /* the filter chain's RGBA8 render targets */
-  uint32_t *d_qbatch = nullptr;                  /* batches of filter frames: the five render targets of every frame, 5 x pixels */
-  size_t qbatch_capacity = 0;                    /* pixels */
-  size_t planes_capacity = 0;
+  DeviceBuffer<float4> d_out;
+  DeviceBuffer<float4> d_gb[6];
+  DeviceBuffer<uint32_t> d_planes[13];                /* the filter chain's RGBA8 render targets */
+  DeviceBuffer<uint32_t> d_qbatch;               /* batches of filter frames: the five render targets of every frame, 5 x pixels */
   /* temporal history: rings of RGBA8 planes (colour, colour ip, location id, original id), newest at ring_head, of the rows this
    * context traces (packed strips of a tiled frame): for frames of ring_n slots, ring_w x ring_h and the (normalised) tile policy ring_tile_* */
-  uint32_t *d_ring[4][16] = {};
+  DeviceBuffer<uint32_t> d_ring[4][16];
   int ring_n = 0, ring_head = 0;
   uint32_t ring_w = 0, ring_h = 0;
   uint32_t ring_tile_rows = 0, ring_tile_index = 0, ring_tile_count = 0;
   /* v2 pipeline workspace: primary hits, per-(sample,pixel) radiance, last sample's originalColor, item queue */
-  float4 *d_hits = nullptr, *d_samples = nullptr, *d_last = nullptr;
-  size_t hits_capacity = 0, samples_capacity = 0, last_capacity = 0;
-  uint32_t *d_queue = nullptr;
+  DeviceBuffer<float4> d_hits, d_samples, d_last;
+  DeviceBuffer<uint32_t> d_queue;
   /* pipeline 3 (wavefront) workspace */
-  float4 *d_rec = nullptr;
-  float4 *d_tail_pool = nullptr;                 /* per walk workgroup: WF_TAIL_POOL_F4 float4 */
-  uint32_t *d_aa[10] = {};                       /* RGBA8 planes of the anti-aliasing passes: [0..8] the TAA ring, [9] FXAA's input */
-  size_t aa_capacity = 0;
+  DeviceBuffer<float4> d_rec;                      /* 8 float4 per path */
+  DeviceBuffer<float4> d_tail_pool;               /* per walk workgroup: WF_TAIL_POOL_F4 float4 */
+  DeviceBuffer<uint32_t> d_aa[10];                 /* RGBA8 planes of the anti-aliasing passes: [0..8] the TAA ring, [9] FXAA's input */
   uint32_t aa_w = 0, aa_h = 0;
   int taa_head = 0, taa_filled = 0;
-  float4 *d_aa_io[2] = {};                       /* staging for the host-pointer variants */
-  size_t aa_io_capacity = 0;
-  float4 *d_rec0 = nullptr, *d_pix0 = nullptr;   /* compact bounce-0 records: 3 float4 per path, 3 float4 per pixel */
-  size_t rec0_capacity = 0, pix0_capacity = 0;
-  size_t rec_capacity = 0;                       /* float4 units */
-  uint32_t *d_live[2] = { nullptr, nullptr };
-  size_t live_capacity = 0;
-  uint32_t *d_wfcounts = nullptr;                /* per chain: counts, walkQueue, [WF_MAX_BOUNCES + 2] each */
+  DeviceBuffer<float4> d_aa_io[2];                /* staging for the host-pointer variants */
+  DeviceBuffer<float4> d_rec0, d_pix0;           /* compact bounce-0 records: 3 float4 per path, 3 float4 per pixel */
+  DeviceBuffer<uint32_t> d_live[2];              /* (both of one size) */
+  DeviceBuffer<uint32_t> d_wfcounts;               /* per chain: counts, walkQueue, [WF_MAX_BOUNCES + 2] each */
   int pipeline = 0;                              /* 0 auto, 1 per-pixel megakernel, 2 persistent paths, 3 wavefront */
   int last_pipeline = 0;                         /* what the last frame ran */
   flx::TraceKernel last_trace = { -1, -1, -1 };     /* ... and which per-pixel kernel, where that was pipeline 1 (all -1 otherwise) */
@@ -117,9 +142,9 @@ struct flx_context {
   hipStream_t aux_stream[3] = { nullptr, nullptr, nullptr };
   hipEvent_t ev_fork = nullptr, ev_join[3] = { nullptr, nullptr, nullptr };
   /* device error word: pinned, device-mapped; a frame kernel's watchdog that trips sets WF_ERR_* bits in it and the host returns FLX_ERR_DEVICE where it next waits */
-  uint32_t *h_dev_error = nullptr, *d_dev_error = nullptr;
+  PinnedBuffer<uint32_t> h_dev_error; uint32_t *d_dev_error = nullptr;      /* (its device address) */
   uint32_t inject_watchdog = 0, inject_flags = 0; /* flx_debug_inject_fault */
-  unsigned long long *d_counters = nullptr;
+  DeviceBuffer<unsigned long long> d_counters;
   bool counters_enabled = false;
   flx_counters last_counters = {};
   hipEvent_t ev_frame0 = nullptr, ev_frame1 = nullptr, ev_k0 = nullptr, ev_k1 = nullptr;
@@ -130,22 +155,15 @@ struct flx_context {
   int last_gather_root = -1;                     /* how the last gathered frame was exchanged: -1 all-gather, else the receiving rank */
   int comm_rank = 0, comm_size = 1;
   bool comm_owned = false;                       /* made by flx_comm_init_rank (else by a group's ncclCommInitAll) */
-  float4 *d_send = nullptr, *d_recv = nullptr;   /* this rank's packed strips; every rank's */
-  size_t send_capacity = 0, recv_capacity = 0;   /* float4 units */
-  float4 *d_send8 = nullptr;                     /* this rank's strips as RGBA8 texels (flx_render_gathered_rgba8_device) */
-  size_t send8_capacity = 0;
-  float4 *d_frames = nullptr;                    /* group mode: the gathered frames in image order */
-  size_t frames_capacity = 0;
-  float4 *d_gplanes = nullptr;                   /* filter frames: the five gathered render targets in image order */
-  size_t gplanes_capacity = 0;
+  DeviceBuffer<float4> d_send, d_recv;           /* this rank's packed strips; every rank's */
+  DeviceBuffer<float4> d_send8;                  /* this rank's strips as RGBA8 texels (flx_render_gathered_rgba8_device), counted in float4 */
+  DeviceBuffer<float4> d_frames;                 /* group mode: the gathered frames in image order */
+  DeviceBuffer<float4> d_gplanes;                /* filter frames: the five gathered render targets in image order, counted in float4 */
   /* the frame loop (flx_frame_begin / flx_frame_end): two slots of device output + pinned host memory, a copy stream */
   /* (three slots where flx_set_frame_lanes(3) lets three chained frames be in flight, two otherwise) */
-  float4 *d_slot[3] = { nullptr, nullptr, nullptr };
-  size_t slot_capacity[3] = { 0, 0, 0 };         /* pixels */
-  uint32_t *d_slot8[3] = { nullptr, nullptr, nullptr };
-  size_t slot8_capacity[3] = { 0, 0, 0 };
-  void *h_slot[3] = { nullptr, nullptr, nullptr };
-  size_t h_slot_capacity[3] = { 0, 0, 0 };       /* bytes */
+  DeviceBuffer<float4> d_slot[3];
+  DeviceBuffer<uint32_t> d_slot8[3];
+  PinnedBuffer<uint8_t> h_slot[3];               /* bytes */
   size_t slot_bytes[3] = { 0, 0, 0 };
   hipStream_t copy_stream = nullptr;
   hipEvent_t ev_slot_start[3] = {}, ev_slot_traced[3] = {}, ev_slot_done[3] = {};
@@ -165,16 +183,17 @@ struct flx_context {
   uint64_t begin_scene_version = 0;              /* ... as the last flx_frame_begin found it (0: no frame begun yet) */
   int last_chained = 0;                          /* flx_last_chained: 0 the last frame of the loop was not chained, 3 the frame server took it */
   /* the frame server (flx_server.hip): one persistent launch renders the loop's frames as they are posted (flx_set_frame_chain mode 2) */
-  flx::ServerSlot *d_sv_slots = nullptr;
-  flx::ServerMail *h_sv_mail = nullptr, *d_sv_mail = nullptr, *d_sv_relay = nullptr;      /* pinned host memory (and its device address); device memory */
-  uint32_t *d_sv_rings = nullptr;
-  float4 *d_sv_out = nullptr;                    /* the launch's resolved frames: [slot] x sv_out_pixels */
-  size_t sv_out_capacity = 0, sv_out_pixels = 0;
-  uint32_t *d_sv_tiles = nullptr;                /* [workgroup][slot] x sv_tile_cap: the screen tiles a workgroup made of a frame */
-  size_t sv_tile_cap = 0;
+  DeviceBuffer<flx::ServerSlot> d_sv_slots;
+  PinnedBuffer<flx::ServerMail> h_sv_mail; flx::ServerMail *d_sv_mail = nullptr;      /* pinned host memory and its device address */
+  DeviceBuffer<flx::ServerMail> d_sv_relay;
+  DeviceBuffer<uint32_t> d_sv_rings;
+  DeviceBuffer<float4> d_sv_out;                 /* the launch's resolved frames: [slot] x sv_out_pixels */
+  size_t sv_out_pixels = 0;
+  DeviceBuffer<uint32_t> d_sv_tiles;              /* [workgroup][slot] x sv_tile_cap: the screen tiles a workgroup made of a frame */
+  size_t sv_tile_cap = 0;                        /* ... the length of one such list, as the launch is told it */
   float slot_latency_ms[3] = { -1.f, -1.f, -1.f }; /* server frames: post .. complete on the host's clock (flx_frame_end's gpu_ms); < 0: timed by events */
   const void *slot_dev_ptr[3] = { nullptr, nullptr, nullptr };      /* where the frame of an output slot really is in device memory when that is not d_slot[k] (server frames) */
-  unsigned long long *d_sv_stats = nullptr;
+  DeviceBuffer<unsigned long long> d_sv_stats;
   hipStream_t sv_stream = nullptr;
   bool sv_running = false;
   uint32_t sv_depth = 0, sv_next_seq = 0, sv_next_slot = 0, sv_counter = 0;
@@ -188,7 +207,7 @@ struct flx_context {
   uint32_t dyn_device_stale = 0;                 /* bit 0 / 1: d_rotation + d_shift / d_lights are behind h_rotation .. (uploads the launch went on over): dyn_flush */
   bool sv_want_ver = false;                      /* the scene has moved since it was uploaded: the next launch does */
   int sv_moving = 1;                             /* flx_set_server_moving_scenes: 0 = never (every changed upload ends the launch, as before round 4) */
-  uint32_t *d_sv_versions = nullptr;             /* [3 arrays][workgroup x depth + slot]: the launch's versions of rotation / shift / lights */
+  DeviceBuffer<uint32_t> d_sv_versions;          /* [3 arrays][workgroup x depth + slot]: the launch's versions of rotation / shift / lights */
   bool sv_out8 = false;                          /* the running launch resolves RGBA8 (ServerArgs::out8) */
   bool sv_target8 = false;                       /* flx_frame_target_set8: the target images are uint32 RGBA8 per pixel */
   float4 *sv_target[3] = { nullptr, nullptr, nullptr };      /* flx_frame_target_set: whole images the launch resolves this context's strips into (a peer GPU's memory, pinned host memory, ..) */
@@ -197,9 +216,8 @@ struct flx_context {
   flx_share *share = nullptr;
   uint32_t sv_groups = 0;                        /* flx_debug_set_server_groups: workgroups of the launch (0: one per CU) — two launches beside each other on one GPU, to rehearse a device group */
   struct { bool valid; uint32_t seq, slot; int format; flx::DeviceFrame fr; std::chrono::steady_clock::time_point posted; } sv_pending[3] = {};      /* per output slot: the server frame that will land there */
-  /* uploads: capacity of every persistent scene buffer (keyed by the address of its pointer), pinned staging ring */
-  std::map<void **, size_t> upload_capacity;
-  uint8_t *stage = nullptr;
+  /* uploads: pinned staging ring */
+  PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};
   bool stage_used[8] = {};
   int stage_next = 0;
@@ -216,6 +234,20 @@ struct flx_context {
 
 flx_status flx_fail(flx_context *ctx, flx_status code, const char *msg);
 
+template <typename T, bool Pinned> flx_status Buffer<T, Pinned>::release(flx_context *ctx) {
+  FLX_HIP(ctx, hip_free());
+  return FLX_OK;
+}
+template <typename T, bool Pinned> flx_status Buffer<T, Pinned>::ensure(flx_context *ctx, size_t count, unsigned pinned_flags) {
+  if (fits(count)) return FLX_OK;
+  FLX_HIP(ctx, hip_free());
+  const size_t elements = count ? count : 1;
+  void *q = nullptr;
+  FLX_HIP(ctx, Pinned ? hipHostMalloc(&q, elements * sizeof(T), pinned_flags) : hipMalloc(&q, elements * sizeof(T)));
+  p = (T *)q; n = elements;
+  return FLX_OK;
+}
+
 
 /* flx_group.hip: this context's strips traced, exchanged over its communicator (root < 0: all-gather; else only `root` receives) and
  * put in image order, all enqueued on its stream */
@@ -225,7 +257,6 @@ flx_status flx_gather_enqueue(flx_context *ctx, const flx_frame_params *params, 
 flx_status flx_make_frame(flx_context *ctx, const flx_frame_params *p, flx::DeviceScene &sc, flx::DeviceFrame &fr);
 flx_status flx_make_batch(flx_context *ctx, const flx_frame_params *params, uint32_t n_frames, flx::DeviceScene &sc, flx::DeviceFrame &fr);
 flx_status flx_run_frame(flx_context *ctx, const flx::DeviceScene &sc, const flx::DeviceFrame &fr, float4 *d_out, const flx::GBufferPtrs &gb);
-flx_status flx_ensure_pixels(flx_context *ctx, float4 **buf, size_t *cap, size_t pixels);
 int flx_server_takes_moving_scene(const flx_context *ctx);                       /* the scene has moved and its lights and transforms fit a post: the server's launches take them per frame */
 int flx_server_continues(flx_context *ctx, const flx_frame_params *params);      /* the running launch of the frame server takes this frame as it is */
 flx_status flx_server_prepare(flx_context *ctx, const flx_frame_params *params); /* the launch ends; everything a launch for frames like this needs is allocated */

@@ -117,14 +117,12 @@ flx_status check_params(flx_context *ctx, const flx_frame_params *params, uint32
   return FLX_OK;
 }
 
-flx_status ensure_f4(flx_context *ctx, float4 **buf, size_t *cap, size_t n) { return flx_ensure_pixels(ctx, buf, cap, n ? n : 1); }
-
 /* step 1: this context's strips -> ctx->d_send (enqueued, no host sync) */
 flx_status trace_share(flx_context *ctx, const flx_frame_params *params, const Share &sh) {
   FLX_HIP(ctx, hipSetDevice(ctx->device));
   flx_status s;
-  if ((s = ensure_f4(ctx, &ctx->d_send, &ctx->send_capacity, sh.slot))) return s;
-  if ((s = ensure_f4(ctx, &ctx->d_recv, &ctx->recv_capacity, sh.slot * sh.n))) return s;
+  if ((s = ctx->d_send.ensure(ctx, sh.slot))) return s;
+  if ((s = ctx->d_recv.ensure(ctx, sh.slot * sh.n))) return s;
   if (params->is_temporal) {
     /* (one frame: check_params) the temporal pass over this context's history of its strips — the five render targets of a filter frame after it, or the frame's strips */
     if (sh.planes) return flx_temporal_planes_enqueue(ctx, params, ctx->d_send);
@@ -134,8 +132,8 @@ flx_status trace_share(flx_context *ctx, const flx_frame_params *params, const S
   if (sh.rgba8) {
     /* floor(clamp(x) * 255 + 0.5) per channel — flx_present's store, texel by texel: the same bytes whether a strip is quantised here or the frame after
      * the exchange.  (The padding rows of a rank with a strip less hold whatever was there: nobody reads them.) */
-    if ((s = ensure_f4(ctx, &ctx->d_send8, &ctx->send8_capacity, (sh.slot + 3u) / 4u))) return s;
-    launch_quantize(ctx->d_send, (uint32_t *)ctx->d_send8, sh.slot, ctx->stream);
+    if ((s = ctx->d_send8.ensure(ctx, (sh.slot + 3u) / 4u))) return s;
+    launch_quantize(ctx->d_send, (uint32_t *)ctx->d_send8.get(), sh.slot, ctx->stream);
     FLX_HIP(ctx, hipGetLastError());
   }
   return FLX_OK;
@@ -143,7 +141,7 @@ flx_status trace_share(flx_context *ctx, const flx_frame_params *params, const S
 /* what a context sends (and how many 4-byte words per rank): its float4 strips, the five planes of a filter frame, or its RGBA8 strips */
 inline const void *share_send(const flx_context *ctx, const Share &sh) { return sh.rgba8 ? (const void *)ctx->d_send8 : (const void *)ctx->d_send; }
 inline size_t share_words(const Share &sh) { return sh.rgba8 ? sh.slot : sh.slot * 4u; }
-inline void *share_recv(flx_context *ctx, const Share &sh, int r) { return (char *)ctx->d_recv + (size_t)r * share_words(sh) * 4u; }
+inline void *share_recv(flx_context *ctx, const Share &sh, int r) { return (char *)ctx->d_recv.get() + (size_t)r * share_words(sh) * 4u; }
 
 /* step 3: gathered strips -> frames in image order (+ the denoise chain for filter frames), on the context's stream */
 flx_status finish_share(flx_context *ctx, const flx_frame_params *params, const Share &sh, void *d_frames) {
@@ -151,9 +149,9 @@ flx_status finish_share(flx_context *ctx, const flx_frame_params *params, const 
   if (sh.planes) {
     flx_status s;
     const size_t words = 5u * (size_t)sh.height * sh.width;
-    if ((s = ensure_f4(ctx, &ctx->d_gplanes, &ctx->gplanes_capacity, (words + 3u) / 4u))) return s;
-    hipLaunchKernelGGL(k_reassemble_planes, dim3((uint32_t)((words + 255u) / 256u)), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->d_recv,
-                       (uint32_t *)ctx->d_gplanes, sh.width, sh.height, sh.tile_rows, sh.n, sh.slot * 4u);
+    if ((s = ctx->d_gplanes.ensure(ctx, (words + 3u) / 4u))) return s;
+    hipLaunchKernelGGL(k_reassemble_planes, dim3((uint32_t)((words + 255u) / 256u)), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->d_recv.get(),
+                       (uint32_t *)ctx->d_gplanes.get(), sh.width, sh.height, sh.tile_rows, sh.n, sh.slot * 4u);
     FLX_HIP(ctx, hipGetLastError());
     flx_frame_params whole = *params;
     whole.tile_rows = whole.tile_index = whole.tile_count = 0;
@@ -161,7 +159,7 @@ flx_status finish_share(flx_context *ctx, const flx_frame_params *params, const 
   }
   const size_t total = (size_t)sh.frames * sh.height * sh.width;
   if (sh.rgba8)
-    hipLaunchKernelGGL(k_reassemble8, dim3((uint32_t)((total + 255u) / 256u)), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->d_recv, (uint32_t *)d_frames, sh.width,
+    hipLaunchKernelGGL(k_reassemble8, dim3((uint32_t)((total + 255u) / 256u)), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->d_recv.get(), (uint32_t *)d_frames, sh.width,
                        sh.height, sh.frames, sh.tile_rows, sh.n, sh.slot);
   else
   hipLaunchKernelGGL(k_reassemble, dim3((uint32_t)((total + 255u) / 256u)), dim3(256), 0, ctx->stream, ctx->d_recv, (float4 *)d_frames, sh.width, sh.height,
@@ -478,7 +476,7 @@ static flx_status group_render(flx_group *g, const flx_frame_params *params, uin
   /* 3. context 0 puts the rows in image order (and runs the denoise chain of a filter frame); the frames go to the host */
   flx_context *c0 = g->ctx[0];
   const size_t pixels = (size_t)n_frames * params->height * params->width;
-  if ((s = ensure_f4(c0, &c0->d_frames, &c0->frames_capacity, pixels))) return gfail(c0, s);
+  if ((s = c0->d_frames.ensure(c0, pixels))) return gfail(c0, s);
   if ((s = finish_share(c0, p[0].data(), sh[0], c0->d_frames))) return gfail(c0, s);
   (void)hipSetDevice(c0->device);
   if (hipMemcpyAsync(out_rgba, c0->d_frames, pixels * (rgba8 ? sizeof(uint32_t) : sizeof(float4)), hipMemcpyDeviceToHost, c0->stream) != hipSuccess) return gfail(nullptr, FLX_ERR_DEVICE);
