@@ -113,6 +113,7 @@ flx_status flx_lights_upload(flx_context *ctx, const float *lights, uint32_t n_l
 flx_status flx_atlas_upload(flx_context *ctx, int which, const uint8_t *rgba, uint32_t width, uint32_t height);
 /* All of the above from one view. */
 flx_status flx_scene_upload_view(flx_context *ctx, const flx_scene_view *scene);
+/* (A scene whose VERTICES move need not come through here again: flx_scene_update, flexlight_hip_debug.h, takes the rows that changed.) */
 
 /* ---- one frame ---------------------------------------------------------------------------------- */
 /* Number of image rows the tile policy of `params` assigns to this context (whole frame: height). */

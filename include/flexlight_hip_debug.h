@@ -119,6 +119,26 @@ flx_status flx_debug_intersect(flx_context *ctx, int fn, const float *in, float 
 /* The uploaded scene's walk_fast_boxes, read-only: 1 when every coordinate of every box entry (type 1) is finite with |x| <= 2^59 — the precondition under which the
  * walk kernels take their box quotients through reciprocals; triangle entries do not count. */
 flx_status flx_debug_walk_fast_boxes(flx_context *ctx, int *fast);
+/* ---- vertex updates ------------------------------------------------------------------------------- */
+/* Beyond the drop-in boundary, like everything in this header: a host that only knows flx_scene_upload renders every scene (the reference's updateScene() is that
+ * call), this is the shorter way for a scene whose topology stands still.  (Declared here and not in flexlight_hip.h because that header is held at the 80
+ * functions it has: tests/test_capi_cpu.py.  The JavaScript renderers, the N-API addon and capi.py bind it like any other call.) */
+/* A scene whose VERTICES move (a cloth, a wave surface, a morphing mesh: the application sets primitive.vertices and calls renderer.updateScene()).
+ * Replace rows [first_entry, first_entry + n_entries) of the uploaded scene and refit every box.  The rows must keep what
+ * the scene holds in words 6 (skip count, boxes), 9 (transform number) and 10 (kind).  Words 0..5 of box rows are ignored:
+ * the device computes them — the componentwise min / max of the vertices of all triangle rows the box skips over, which is what the
+ * flatten computes (modules/scene.js:242-256, 269-279), bit for bit; a box that skips nothing, or nothing but boxes, keeps its six floats.
+ * attributes may be NULL: the attribute rows stay.  The caller's buffers are free when the call returns.  A frame begun before the call
+ * renders the old geometry, a frame begun after it the new.  FLX_ERR_INVALID (and the scene exactly what it was) for a range that leaves
+ * the array, a changed metadata word, a vertex that is not finite, and for a scene that was uploaded with a NaN vertex (Math.min would
+ * carry it into the boxes above; the device's min does not); FLX_ERR_NO_SCENE before flx_scene_upload. */
+flx_status flx_scene_update(flx_context *ctx, uint32_t first_entry, uint32_t n_entries,
+                            const float *geometry /* n_entries * 12 */, const float *attributes /* n_entries * 28 or NULL */);
+flx_status flx_group_scene_update(flx_group *group, uint32_t first_entry, uint32_t n_entries, const float *geometry, const float *attributes);
+/* The uploaded scene as the device holds it, after everything enqueued so far: which 0 the geometry rows (12 floats per entry), 1 the attribute rows (28),
+ * 2 the threaded hot-first copy (12 per entry of walk_entries), 3 the forward-ordered copy (12 per entry of fwd_entries: flx_debug_last_walk_lds' out[5], out[6]).
+ * The first n_floats floats of the array; FLX_ERR_INVALID beyond its end.  Tests compare flx_scene_update's arrays with a fresh upload's. */
+flx_status flx_debug_scene_read(flx_context *ctx, int which, float *out, uint32_t n_floats);
 /* Walk n rays through the uploaded scene on the GPU, AS THE KERNELS DO, one ray per lane: rayTracer (fragment:172-227) and shadowTest (:230-279) of each ray;
  * used by tests to hold the device walks against literal answers computed from the shader text (tests/golden/walk_kat.json.gz).  variant 0: the wavefront
  * pipeline's lane walk over the threaded, hot-first copy with the rays pre-transformed into every object space; 1: the per-pixel / persistent kernels' lane

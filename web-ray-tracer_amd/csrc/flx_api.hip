@@ -112,6 +112,7 @@ extern "C" void flx_context_destroy(flx_context *ctx) {
     for (hipEvent_t ev : { ctx->ev_slot_start[i], ctx->ev_slot_traced[i], ctx->ev_slot_done[i] }) if (ev) (void)hipEventDestroy(ev);
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   for (hipEvent_t ev : ctx->stage_done) if (ev) (void)hipEventDestroy(ev);
+  if (ctx->update_done) (void)hipEventDestroy(ctx->update_done);
   if (ctx->sv_stream) (void)hipStreamDestroy(ctx->sv_stream);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;                              /* its buffers go with it, on its device (set above; a twin's views of this context's scene arrays free nothing) */
@@ -308,8 +309,12 @@ extern "C" flx_status flx_scene_upload(flx_context *ctx, const float *geometry, 
   /* Validate the skip list on the host: a skip that leaves the array would make the walk read out of
    * bounds on the GPU (the shader's texelFetch would be robust-access clamped; we refuse instead). */
   uint32_t max_transform = 0;
+  std::vector<uint32_t> entry_meta((size_t)n_entries_padded * 3);      /* what flx_scene_update holds its rows against */
+  bool has_nan = false;
   for (uint32_t i = 0; i < n_entries_padded; i++) {
     const float *e = geometry + (size_t)i * 12;
+    memcpy(&entry_meta[(size_t)i * 3], e + 6, 4); memcpy(&entry_meta[(size_t)i * 3 + 1], e + 9, 8);
+    if (e[10] == 2.0f) for (int k = 0; k < 9; k++) if (e[k] != e[k]) has_nan = true;
     if (e[10] != 0.0f) {
       if (!(e[9] >= 0.0f && e[9] < 1048576.0f)) return fail(ctx, FLX_ERR_INVALID, "flx_scene_upload: transform number out of range");
       if ((uint32_t)e[9] > max_transform) max_transform = (uint32_t)e[9];
@@ -354,9 +359,70 @@ extern "C" flx_status flx_scene_upload(flx_context *ctx, const float *geometry, 
   ctx->n_entries = n_entries_padded;
   ctx->n_ids = n_ids;
   ctx->max_transform = max_transform;
+  ctx->h_entry_meta.swap(entry_meta);
+  ctx->scene_has_nan = has_nan;
   if ((s = shared_upload_end(ctx))) return s;
   ctx->have_scene = true;
   return FLX_OK;
+}
+
+/* Rows of the uploaded scene replaced (vertices that moved, their attribute rows), every box refitted and both derived copies brought up to date ON THE DEVICE
+ * (flx_refit.hip).  The links, the storage order and the ids of the scene depend on entry kinds, skip counts and transform numbers alone, and those stay: nothing
+ * is sorted or threaded again, and only the rows cross the bus.  Ordered like an upload() of a shared scene array — the frame server's launch ends, the second
+ * lane's frames in flight are waited for, the result is complete before the call returns where there is a second lane — but NOT behind a wait for this context's
+ * own frames in flight: the copies and kernels are enqueued on its stream, after them.  Everything that can refuse the rows is checked before anything is touched. */
+extern "C" flx_status flx_scene_update(flx_context *ctx, uint32_t first_entry, uint32_t n_entries, const float *geometry, const float *attributes) {
+  if (!ctx) return FLX_ERR_INVALID;
+  if (!ctx->have_scene) return fail(ctx, FLX_ERR_NO_SCENE, "flx_scene_update before flx_scene_upload");
+  if ((uint64_t)first_entry + n_entries > ctx->n_entries) return fail(ctx, FLX_ERR_INVALID, "flx_scene_update: the rows leave the entry array");
+  if (n_entries == 0) return FLX_OK;
+  if (!geometry) return fail(ctx, FLX_ERR_INVALID, "flx_scene_update: geometry is NULL");
+  if (ctx->scene_has_nan) return fail(ctx, FLX_ERR_INVALID, "flx_scene_update: the uploaded scene has a NaN vertex (its boxes cannot be refitted as the flatten makes them)");
+  bool bounded = true;
+  for (uint32_t r = 0; r < n_entries; r++) {
+    const float *e = geometry + (size_t)r * 12;
+    const uint32_t *m = &ctx->h_entry_meta[((size_t)first_entry + r) * 3];
+    uint32_t w6, w9, w10;
+    memcpy(&w6, e + 6, 4); memcpy(&w9, e + 9, 4); memcpy(&w10, e + 10, 4);
+    if (w10 != m[2]) return fail(ctx, FLX_ERR_INVALID, "flx_scene_update: a row changes its kind (word 10)");
+    if (e[10] == 0.0f) continue;
+    if (w9 != m[1]) return fail(ctx, FLX_ERR_INVALID, "flx_scene_update: a row changes its transform number (word 9)");
+    if (e[10] == 1.0f) {
+      if (w6 != m[0]) return fail(ctx, FLX_ERR_INVALID, "flx_scene_update: a box row changes its skip count (word 6)");
+    } else {
+      for (int k = 0; k < 9; k++) {
+        if (!std::isfinite(e[k])) return fail(ctx, FLX_ERR_INVALID, "flx_scene_update: a vertex is not finite");
+        if (!(std::fabs(e[k]) <= 5.764607523034235e17f)) bounded = false;      /* (the boxes are min / max of vertices: flx_scene_upload's bound of the fast box test) */
+      }
+    }
+  }
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  flx_status s;
+  /* everything the update needs is there before the first copy: a failed allocation leaves the scene as it was */
+  const size_t gfloats = (size_t)n_entries * 12, afloats = attributes ? (size_t)n_entries * 28 : 0;
+  if (ctx->update_pending) { FLX_HIP(ctx, hipEventSynchronize(ctx->update_done)); ctx->update_pending = false; }      /* (the copies of the last update read h_update) */
+  if (!ctx->update_done) FLX_HIP(ctx, hipEventCreateWithFlags(&ctx->update_done, hipEventDisableTiming));
+  if ((s = ctx->h_update.ensure(ctx, gfloats + afloats, hipHostMallocDefault))) return s;
+  if (!ctx->d_update_rows.fits((size_t)n_entries * 3) || !ctx->d_refit.fits(refit_workspace_words(ctx->n_entries))) {
+    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));      /* (an earlier update's kernels may still read what is freed here) */
+    if ((s = ctx->d_update_rows.ensure(ctx, (size_t)n_entries * 3)) || (s = ctx->d_refit.ensure(ctx, refit_workspace_words(ctx->n_entries)))) return s;
+  }
+  memcpy(ctx->h_update, geometry, gfloats * 4);
+  if (attributes) memcpy(ctx->h_update + gfloats, attributes, afloats * 4);
+  if ((s = flx_server_stop(ctx))) return s;          /* (a running frame server reads the scene) */
+  if ((s = shared_upload_begin(ctx))) return s;
+  ctx->geometry_version++; ctx->scene_version++; ctx->structure_version++;
+  if (!bounded) ctx->walk_fast_boxes = 0u;          /* until the next flx_scene_upload: both box tests give the same bits under the precondition */
+  FLX_HIP(ctx, hipMemcpyAsync(ctx->d_update_rows, ctx->h_update, gfloats * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (attributes) FLX_HIP(ctx, hipMemcpyAsync(ctx->d_attributes + (size_t)first_entry * 7, ctx->h_update + gfloats, afloats * 4, hipMemcpyHostToDevice, ctx->stream));
+  FLX_HIP(ctx, hipEventRecord(ctx->update_done, ctx->stream));
+  ctx->update_pending = true;
+  launch_scene_rows(ctx->d_update_rows, ctx->d_geometry, first_entry, n_entries, ctx->stream);
+  launch_refit(ctx->d_geometry, ctx->n_entries, ctx->d_refit, ctx->stream);
+  launch_rederive(ctx->d_geometry, ctx->n_entries, ctx->d_walk, ctx->walk_entries, ctx->stream);
+  launch_rederive(ctx->d_geometry, ctx->n_entries, ctx->d_fwd, ctx->fwd_entries, ctx->stream);
+  FLX_HIP(ctx, hipGetLastError());
+  return shared_upload_end(ctx);
 }
 
 extern "C" flx_status flx_transforms_upload(flx_context *ctx, const float *rotation, const float *shift, uint32_t n_transforms) {
@@ -2199,6 +2265,20 @@ extern "C" flx_status flx_debug_walk_fast_boxes(flx_context *ctx, int *fast) {
   if (!ctx || !fast) return FLX_ERR_INVALID;
   if (!ctx->have_scene) return fail(ctx, FLX_ERR_INVALID, "flx_debug_walk_fast_boxes: no scene uploaded");
   *fast = ctx->walk_fast_boxes != 0u ? 1 : 0;
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_debug_scene_read(flx_context *ctx, int which, float *out, uint32_t n_floats) {
+  if (!ctx || !out) return FLX_ERR_INVALID;
+  if (!ctx->have_scene) return fail(ctx, FLX_ERR_NO_SCENE, "flx_debug_scene_read: no scene uploaded");
+  if (which < 0 || which > 3) return fail(ctx, FLX_ERR_INVALID, "flx_debug_scene_read: which 0 .. 3");
+  const float4 *src = which == 0 ? ctx->d_geometry : which == 1 ? ctx->d_attributes : which == 2 ? ctx->d_walk : ctx->d_fwd;
+  const size_t have = which == 0 ? (size_t)ctx->n_entries * 12 : which == 1 ? (size_t)ctx->n_entries * 28 : which == 2 ? (size_t)ctx->walk_entries * 12 : (size_t)ctx->fwd_entries * 12;
+  if (n_floats > have) return fail(ctx, FLX_ERR_INVALID, "flx_debug_scene_read: more floats than the array has");
+  if (n_floats == 0) return FLX_OK;
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  FLX_HIP(ctx, hipMemcpy(out, src, (size_t)n_floats * 4, hipMemcpyDeviceToHost));
   return FLX_OK;
 }
 

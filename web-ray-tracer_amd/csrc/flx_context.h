@@ -104,6 +104,17 @@ struct flx_context {
   uint32_t n_entries = 0, n_ids = 0, n_transforms = 0, n_lights = 0;
   uint32_t max_transform = 0;                   /* largest transform number an entry names */
   bool have_scene = false, have_transforms = false, have_lights = false;
+  /* flx_scene_update (rows of the uploaded scene replaced, the boxes refitted on the device: flx_refit.hip).  What the host must know of the scene to check the rows it
+   * is given without reading the device: the bits of words 6, 9 and 10 of every entry, kept at flx_scene_upload; whether a triangle of the upload had a NaN vertex
+   * (the refit's min / max would not carry it into the boxes as Math.min does: such a scene takes no updates).  The rows go through pinned memory of the context's
+   * (update_done: the copies that last read it) into d_update_rows, from where a kernel scatters them; d_refit is the refit's workspace. */
+  std::vector<uint32_t> h_entry_meta;
+  bool scene_has_nan = false;
+  PinnedBuffer<float> h_update;
+  hipEvent_t update_done = nullptr;
+  bool update_pending = false;
+  DeviceBuffer<float4> d_update_rows;
+  DeviceBuffer<uint32_t> d_refit;
   /* DeviceScene::angle_tan: per triangle, from the geometry / attribute arrays and this context's transforms; made again (on this context's stream, in front of
    * the frame that needs it) when any of them changed: angle_key = the versions it was made from */
   DeviceBuffer<float4> d_angle_tan;

@@ -417,6 +417,9 @@ extern "C" flx_status flx_group_lights_upload(flx_group *g, const float *lights,
 extern "C" flx_status flx_group_atlas_upload(flx_group *g, int which, const uint8_t *rgba, uint32_t width, uint32_t height) {
   FLX_GROUP_EACH(g, flx_atlas_upload(c, which, rgba, width, height));
 }
+extern "C" flx_status flx_group_scene_update(flx_group *g, uint32_t first_entry, uint32_t n_entries, const float *geometry, const float *attributes) {
+  FLX_GROUP_EACH(g, flx_scene_update(c, first_entry, n_entries, geometry, attributes));
+}
 extern "C" flx_status flx_group_scene_upload_view(flx_group *g, const flx_scene_view *scene) { FLX_GROUP_EACH(g, flx_scene_upload_view(c, scene)); }
 
 /* n_frames frames (a batch; 1 = one frame) of a camera path on all contexts of the group; the frames arrive on the host. */

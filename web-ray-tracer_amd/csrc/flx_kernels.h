@@ -115,6 +115,14 @@ void launch_temporal(const TemporalPass &pass, hipStream_t stream);
 void launch_raster(const DeviceScene &sc, const DeviceFrame &fr, int hdr, float4 *out, unsigned long long *counters, hipStream_t stream);
 /* ... into the RGBA8 words k_quantize would store for that frame (uncounted) */
 void launch_raster(const DeviceScene &sc, const DeviceFrame &fr, int hdr, uint32_t *out8, hipStream_t stream);
+/* flx_scene_update (flx_refit.hip).  n_rows rows (3 float4 each) -> geometry rows [first, first + n_rows); a box row keeps its words 0..5 */
+void launch_scene_rows(const float4 *rows, float4 *geometry, uint32_t first, uint32_t n_rows, hipStream_t stream);
+/* words 0..5 of every box row with a skip count s > 0 = min / max over the vertices of the triangle rows in (i, i + s], -0 below +0 (a box over no triangle keeps
+ * its floats); work: refit_workspace_words(n_entries) words */
+size_t refit_workspace_words(uint32_t n_entries);
+void launch_refit(float4 *geometry, uint32_t n_entries, uint32_t *work, hipStream_t stream);
+/* the threaded or the forward-ordered copy (`entries` of them) follows the geometry rows: the six floats of a box, a triangle's vertex and two edges; links and meta words stay */
+void launch_rederive(const float4 *geometry, uint32_t n_entries, float4 *copy, uint32_t entries, hipStream_t stream);
 void launch_debug_math(int fn, const float *a, const float *b, float *out, uint32_t n, hipStream_t stream);
 void launch_debug_intersect(int fn, const float *in, float *out, uint32_t n, hipStream_t stream);
 bool launch_debug_walk(int variant, const DeviceScene &sc, const float *in, float *out, uint32_t n, hipStream_t stream);      /* false: the scene does not allow that variant */

@@ -31,6 +31,7 @@ EXPORTS = [
     "flx_share_create", "flx_share_join", "flx_share_leave", "flx_frame_begin_shared", "flx_frame_end_shared",
     "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_sample_parallel", "flx_debug_last_trace_kernel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
     "flx_raster_render", "flx_debug_walk_staged", "flx_debug_last_walk_lds", "flx_debug_walk_fast_boxes",
+    "flx_scene_update", "flx_group_scene_update", "flx_debug_scene_read",
 ]
 
 
@@ -58,6 +59,9 @@ def _load():
         "flx_context_destroy": (None, [vp]),
         "flx_last_error": (C.c_char_p, [vp]),
         "flx_scene_upload": (C.c_int, [vp, fp, fp, u32, C.POINTER(C.c_int32), u32]),
+        "flx_scene_update": (C.c_int, [vp, u32, u32, fp, fp]),
+        "flx_group_scene_update": (C.c_int, [vp, u32, u32, fp, fp]),
+        "flx_debug_scene_read": (C.c_int, [vp, C.c_int, fp, u32]),
         "flx_transforms_upload": (C.c_int, [vp, fp, fp, u32]),
         "flx_lights_upload": (C.c_int, [vp, fp, u32]),
         "flx_atlas_upload": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint8), u32, u32]),
@@ -187,6 +191,16 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _rows(geometry, attributes):
+    """geometry [n, 12] and attributes [n, 28] or None of update_scene_rows, contiguous float32 -> (geometry, attributes, n)"""
+    geometry = np.ascontiguousarray(geometry, np.float32).reshape(-1, 12)
+    if attributes is not None:
+        attributes = np.ascontiguousarray(attributes, np.float32).reshape(-1, 28)
+        if attributes.shape[0] != geometry.shape[0]:
+            raise ValueError("update_scene_rows: as many attribute rows as geometry rows")
+    return geometry, attributes, geometry.shape[0]
+
+
 class Context:
     """One GPU context (flx_context).  Mirrors the life cycle of the reference renderer object:
     construct -> updateScene()/updatePrimaryLightSources() -> render frames -> halt()."""
@@ -230,6 +244,24 @@ class Context:
 
     def upload_view(self, view):
         self._check(LIB.flx_scene_upload_view(self._h, C.byref(view)), "flx_scene_upload_view")
+
+    def update_scene_rows(self, first, geometry, attributes=None):
+        """flx_scene_update: rows [first, first + n) of the uploaded scene replaced (12 floats of geometry each, 28 of attributes or None:
+        they stay), every box refitted on the device."""
+        geometry, attributes, n = _rows(geometry, attributes)
+        self._check(LIB.flx_scene_update(self._h, first, n, _fp(geometry), None if attributes is None else _fp(attributes)), "flx_scene_update")
+
+    def scene_read(self, which, rows=None):
+        """flx_debug_scene_read: the device's 'geometry' [rows, 12], 'attributes' [rows, 28], 'walk' (the threaded copy) or 'fwd' (the forward-ordered
+        copy) [rows, 12]; rows: the first so many entries (the copies: all of them when None)."""
+        k = ("geometry", "attributes", "walk", "fwd").index(which)
+        if rows is None:
+            if k < 2:
+                raise ValueError("scene_read: rows of the geometry / attribute array wanted")
+            rows = self.last_walk_lds()["walk_entries" if k == 2 else "fwd_entries"]
+        out = np.zeros((rows, 28 if k == 1 else 12), np.float32)
+        self._check(LIB.flx_debug_scene_read(self._h, k, _fp(out), out.size), "flx_debug_scene_read")
+        return out
 
     def update_primary_light_sources(self, lights):
         lights = np.ascontiguousarray(lights, np.float32).reshape(-1)
@@ -698,6 +730,10 @@ class Group:
     def update_scene(self, scene):
         view = scene.view()
         self._check(LIB.flx_group_scene_upload_view(self._h, C.byref(view)), "flx_group_scene_upload_view")
+
+    def update_scene_rows(self, first, geometry, attributes=None):
+        geometry, attributes, n = _rows(geometry, attributes)
+        self._check(LIB.flx_group_scene_update(self._h, first, n, _fp(geometry), None if attributes is None else _fp(attributes)), "flx_group_scene_update")
 
     def update_primary_light_sources(self, lights):
         lights = np.ascontiguousarray(lights, np.float32).reshape(-1)

@@ -72,7 +72,7 @@ class PathTracerHIP {
       if (!this._group) this._group = n.createGroup(this._devices);
       const g = this._group;
       return {
-        uploadScene: (a, b, c) => n.groupUploadScene(g, a, b, c), uploadTransforms: (a, b) => n.groupUploadTransforms(g, a, b),
+        uploadScene: (a, b, c) => n.groupUploadScene(g, a, b, c), updateSceneRows: (f, a, b) => n.groupUpdateSceneRows(g, f, a, b), uploadTransforms: (a, b) => n.groupUploadTransforms(g, a, b),
         uploadLights: a => n.groupUploadLights(g, a), uploadAtlas: (w, px, x, y) => n.groupUploadAtlas(g, w, px, x, y),
         render: (p, out, counters) => n.groupRender(g, [p], this._tileRows, out, counters),
         renderBatch: (ps, out, counters) => n.groupRender(g, ps, this._tileRows, out, counters),
@@ -81,7 +81,7 @@ class PathTracerHIP {
     }
     const c = this._context();
     return {
-      uploadScene: (a, b, d) => n.uploadScene(c, a, b, d), uploadTransforms: (a, b) => n.uploadTransforms(c, a, b),
+      uploadScene: (a, b, d) => n.uploadScene(c, a, b, d), updateSceneRows: (f, a, b) => n.updateSceneRows(c, f, a, b), uploadTransforms: (a, b) => n.uploadTransforms(c, a, b),
       uploadLights: a => n.uploadLights(c, a), uploadAtlas: (w, px, x, y) => n.uploadAtlas(c, w, px, x, y),
       render: (p, out, counters) => n.render(c, p, out, counters), renderBatch: (ps, out, counters) => n.renderBatch(c, ps, out, counters),
       rows: p => n.tileRowCount(p)
@@ -108,15 +108,32 @@ class PathTracerHIP {
       this._group = null;
     }
     this._haveScene = false;
+    this._built = null;
     this._atlasLists = [null, null, null];
     this._inFlight = 0;
     this._lanesSet = undefined;
   }
 
-  async updateScene () {                                  // pathtracerWGL2.js:167-189
+  /* The application moved something and says so (pathtracerWGL2.js:167-189).  Where only vertices and attributes moved — the same rows, kinds, skip counts,
+   * transform numbers and ids as the arrays uploaded last (sceneFile.changedRows) — the changed rows go to the device, which refits the boxes itself
+   * (flx_scene_update); anything else is the whole upload.  lastSceneUpload: 'full' | 'rows' | 'none' (nothing differed: nothing was sent). */
+  async updateScene () {
     const built = await this.scene.generateArraysFromGraph();
+    const rows = this._haveScene ? sceneFile.changedRows(this._built, built) : null;
+    if (!rows) return this._uploadBuilt(built);
+    if (rows.count > 0) {
+      this._gpu().updateSceneRows(rows.first, built.geometryBuffer.subarray(rows.first * 12, (rows.first + rows.count) * 12),
+        built.sceneBuffer.subarray(rows.first * 28, (rows.first + rows.count) * 28));
+    }
+    this._built = built;
+    this.lastSceneUpload = rows.count > 0 ? 'rows' : 'none';
+  }
+
+  _uploadBuilt (built) {
     this._gpu().uploadScene(built.geometryBuffer, built.sceneBuffer, built.idBuffer);
+    this._built = built;                                 // (what the device holds: the next updateScene() compares with it)
     this._haveScene = true;
+    this.lastSceneUpload = 'full';
   }
 
   async updatePrimaryLightSources () {                    // pathtracerWGL2.js:143-165
@@ -191,11 +208,7 @@ class PathTracerHIP {
   /* scene arrays of this frame: scene once, then what the reference re-derives every frame (pathtracerWGL2.js:258-262, 361-365) */
   _uploadFrameState () {
     const gpu = this._gpu();
-    if (!this._haveScene) {
-      const built = this.scene.generateArraysFromGraph();
-      gpu.uploadScene(built.geometryBuffer, built.sceneBuffer, built.idBuffer);
-      this._haveScene = true;
-    }
+    if (!this._haveScene) this._uploadBuilt(this.scene.generateArraysFromGraph());
     this._updateAtlases();
     gpu.uploadLights(sceneFile.buildLightArray(this.scene));
     const tr = Transform.buildWGL2Arrays();

@@ -47,14 +47,30 @@ class RasterizerHIP {
       this._ctx = null;
     }
     this._haveScene = false;
+    this._built = null;
     this._atlasLists = [null, null, null];
     this._pending = [];                                  // (frames in flight: the library waits for them as the context goes)
   }
 
-  async updateScene () {                                  // rasterizerWGL2.js:150-190
+  /* rasterizerWGL2.js:150-190; as PathTracerHIP.updateScene(): the changed rows alone where only vertices and attributes moved (flx_scene_update refits the
+   * boxes on the device), the whole upload otherwise.  lastSceneUpload: 'full' | 'rows' | 'none'. */
+  async updateScene () {
     const built = await this.scene.generateArraysFromGraph();
+    const rows = this._haveScene ? sceneFile.changedRows(this._built, built) : null;
+    if (!rows) return this._uploadBuilt(built);
+    if (rows.count > 0) {
+      native().updateSceneRows(this._context(), rows.first, built.geometryBuffer.subarray(rows.first * 12, (rows.first + rows.count) * 12),
+        built.sceneBuffer.subarray(rows.first * 28, (rows.first + rows.count) * 28));
+    }
+    this._built = built;
+    this.lastSceneUpload = rows.count > 0 ? 'rows' : 'none';
+  }
+
+  _uploadBuilt (built) {
     native().uploadScene(this._context(), built.geometryBuffer, built.sceneBuffer, built.idBuffer);
+    this._built = built;                                 // (what the device holds: the next updateScene() compares with it)
     this._haveScene = true;
+    this.lastSceneUpload = 'full';
   }
 
   async updatePrimaryLightSources () {                    // rasterizerWGL2.js:125-148
@@ -122,11 +138,7 @@ class RasterizerHIP {
    * radiance holds the RGBA8 drawing buffer's bytes as k / 255 (after an anti-aliasing pass: that pass's output). */
   _uploadFrameState () {
     const n = native(), c = this._context();
-    if (!this._haveScene) {
-      const built = this.scene.generateArraysFromGraph();
-      n.uploadScene(c, built.geometryBuffer, built.sceneBuffer, built.idBuffer);
-      this._haveScene = true;
-    }
+    if (!this._haveScene) this._uploadBuilt(this.scene.generateArraysFromGraph());
     this._updateAtlases();
     n.uploadLights(c, sceneFile.buildLightArray(this.scene));
     const tr = Transform.buildWGL2Arrays();

@@ -123,4 +123,44 @@ function sceneFromFlxs (file) {
   };
 }
 
-module.exports = { buildLightArray, buildAtlas, buildViewMatrix, assemble, save, sceneFromFlxs };
+/* Which rows of the flattened scene changed between two generateArraysFromGraph() results — for flx_scene_update, which takes rows whose
+ * vertices or attributes moved and refits the boxes on the device.  null: the row path does not apply — no earlier arrays (or the very same
+ * array objects: nothing to compare with), different lengths, different ids, a difference in what fixes the topology (word 10, the kind, of any
+ * row; word 9, the transform number, of a box or triangle; word 6, the skip count, of a box), or a vertex in the span that is not finite (the
+ * library refuses those).  Otherwise {first, count}: the ONE span from the first to the last differing row; count 0 when nothing differs.
+ * Words 0..5 of a box row do not count: they follow from the vertices, and the device computes them.  Compared as bits. */
+function changedRows (oldBuilt, newBuilt) {
+  if (!oldBuilt || !newBuilt) return null;
+  const g0 = oldBuilt.geometryBuffer, g1 = newBuilt.geometryBuffer, a0 = oldBuilt.sceneBuffer, a1 = newBuilt.sceneBuffer;
+  const i0 = oldBuilt.idBuffer, i1 = newBuilt.idBuffer;
+  if (g0 === g1 || a0 === a1) return null;
+  if (g0.length !== g1.length || a0.length !== a1.length || i0.length !== i1.length || g0.length % 12 !== 0 || a0.length / 28 !== g0.length / 12) return null;
+  for (let i = 0; i < i0.length; i++) if (i0[i] !== i1[i]) return null;
+  const words = f => new Int32Array(f.buffer, f.byteOffset, f.length);
+  const G0 = words(g0), G1 = words(g1), A0 = words(a0), A1 = words(a1);
+  const n = g0.length / 12;
+  const rowDiffers = r => {
+    const g = r * 12, a = r * 28;
+    for (let k = g1[g + 10] === 1 ? 6 : 0; k < 12; k++) if (G0[g + k] !== G1[g + k]) return true;
+    for (let k = 0; k < 28; k++) if (A0[a + k] !== A1[a + k]) return true;
+    return false;
+  };
+  for (let r = 0; r < n; r++) {
+    const g = r * 12;
+    if (G0[g + 10] !== G1[g + 10]) return null;
+    const kind = g1[g + 10];
+    if (kind !== 0 && G0[g + 9] !== G1[g + 9]) return null;
+    if (kind === 1 && G0[g + 6] !== G1[g + 6]) return null;
+  }
+  let first = 0, last = n - 1;
+  while (first < n && !rowDiffers(first)) first++;
+  if (first === n) return { first: 0, count: 0 };
+  while (!rowDiffers(last)) last--;
+  for (let r = first; r <= last; r++) {
+    if (g1[r * 12 + 10] !== 2) continue;
+    for (let k = 0; k < 9; k++) if (!Number.isFinite(g1[r * 12 + k])) return null;
+  }
+  return { first, count: last - first + 1 };
+}
+
+module.exports = { buildLightArray, buildAtlas, buildViewMatrix, assemble, save, sceneFromFlxs, changedRows };

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "flexlight_hip.h"
+#include "flexlight_hip_debug.h"      /* flx_scene_update */
 
 #define NAPI_OK(env, call)                                                     \
   do {                                                                         \
@@ -166,6 +167,28 @@ static napi_value UploadScene(napi_env env, napi_callback_info info) {
   if (ng % 12 != 0 || na / 28 != ng / 12 || na % 28 != 0) { napi_throw_range_error(env, nullptr, "geometry needs 12 and attributes 28 floats per entry"); return nullptr; }
   flx_status rc = flx_scene_upload(ctx, (const float *)g, (const float *)a, (uint32_t)(ng / 12), (const int32_t *)ids, (uint32_t)nids);
   if (rc != FLX_OK) return fail(env, ctx, "flx_scene_upload", rc);
+  return nullptr;
+}
+
+/* the arguments of updateSceneRows / groupUpdateSceneRows after the handle: first, geometry Float32Array(12 n), attributes Float32Array(28 n) | null */
+static bool row_args(napi_env env, napi_value *argv, uint32_t *first, const float **g, const float **a, uint32_t *n) {
+  void *pg, *pa; size_t ng, na;
+  if (napi_get_value_uint32(env, argv[0], first) != napi_ok) { napi_throw_type_error(env, nullptr, "updateSceneRows: first is not a number"); return false; }
+  if (!typed(env, argv[1], napi_float32_array, &pg, &ng) || !typed(env, argv[2], napi_float32_array, &pa, &na)) return false;
+  if (ng % 12 != 0 || (pa && (na % 28 != 0 || na / 28 != ng / 12))) { napi_throw_range_error(env, nullptr, "geometry needs 12 and attributes 28 floats per row"); return false; }
+  *g = (const float *)pg; *a = (const float *)pa; *n = (uint32_t)(ng / 12);
+  return true;
+}
+/* updateSceneRows(handle, first, geometry, attributes | null): flx_scene_update */
+static napi_value UpdateSceneRows(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  uint32_t first, n; const float *g, *a;
+  if (!row_args(env, argv + 1, &first, &g, &a, &n)) return nullptr;
+  flx_status rc = flx_scene_update(ctx, first, n, g, a);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_scene_update", rc);
   return nullptr;
 }
 
@@ -754,6 +777,17 @@ static napi_value GroupUploadScene(napi_env env, napi_callback_info info) {
   if (rc != FLX_OK) return gfail(env, grp, "flx_group_scene_upload", rc);
   return nullptr;
 }
+static napi_value GroupUpdateSceneRows(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  flx_group *grp = get_group(env, argv[0]);
+  if (!grp) return nullptr;
+  uint32_t first, n; const float *g, *a;
+  if (!row_args(env, argv + 1, &first, &g, &a, &n)) return nullptr;
+  flx_status rc = flx_group_scene_update(grp, first, n, g, a);
+  if (rc != FLX_OK) return gfail(env, grp, "flx_group_scene_update", rc);
+  return nullptr;
+}
 static napi_value GroupUploadTransforms(napi_env env, napi_callback_info info) {
   napi_value argv[3];
   if (!get_args(env, info, 3, argv)) return nullptr;
@@ -1014,7 +1048,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
