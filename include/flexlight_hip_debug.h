@@ -135,6 +135,18 @@ flx_status flx_debug_walk_fast_boxes(flx_context *ctx, int *fast);
 flx_status flx_scene_update(flx_context *ctx, uint32_t first_entry, uint32_t n_entries,
                             const float *geometry /* n_entries * 12 */, const float *attributes /* n_entries * 28 or NULL */);
 flx_status flx_group_scene_update(flx_group *group, uint32_t first_entry, uint32_t n_entries, const float *geometry, const float *attributes);
+/* flx_scene_update for rows that are ALREADY ON THE DEVICE (a simulation kernel's output, a torch tensor, another library's buffer): d_geometry and d_attributes
+ * are pointers into device memory of ctx's device, 16-byte aligned (FLX_ERR_INVALID otherwise: a host pointer, another device's memory, an allocation that ends
+ * before the rows do).  A kernel holds the rows against the scene where flx_scene_update's loop does so on the host: the same refusals with the same messages, the
+ * first offending row and its first rule, and a refused call leaves the scene exactly as it was.  producer_stream: the hipStream_t on which the rows were written —
+ * the check waits for what is enqueued there at the time of the call — or NULL: the rows are complete (NULL does not name the legacy default stream).  The check
+ * runs on a stream of the context's own and the host waits for it alone, not for the context's frames in flight; the rows are copied into the context's memory
+ * by then, so the caller's buffers are free when the call returns.  Everything else is flx_scene_update.  A group keeps the host call (flx_group_scene_update): the
+ * rows live on one device, its contexts on several. */
+flx_status flx_scene_update_device(flx_context *ctx, uint32_t first_entry, uint32_t n_entries,
+                                   const void *d_geometry /* n_entries * 12 floats, on ctx's device */,
+                                   const void *d_attributes /* n_entries * 28 floats or NULL */,
+                                   void *producer_stream /* hipStream_t that wrote the rows, or NULL: they are complete */);
 /* The uploaded scene as the device holds it, after everything enqueued so far: which 0 the geometry rows (12 floats per entry), 1 the attribute rows (28),
  * 2 the threaded hot-first copy (12 per entry of walk_entries), 3 the forward-ordered copy (12 per entry of fwd_entries: flx_debug_last_walk_lds' out[5], out[6]).
  * The first n_floats floats of the array; FLX_ERR_INVALID beyond its end.  Tests compare flx_scene_update's arrays with a fresh upload's. */

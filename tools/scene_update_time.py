@@ -4,14 +4,21 @@ copies) against flx_scene_update of the rows that moved (the monkey's; all rows)
 Per call: the host's wall clock inside the call, the wall clock until the device has finished (call + flx_sync), and the GPU time between two events recorded
 on the context's stream around the call.  Warm-up, then REPEATS calls of each kind in turn (alternating, so that a drift of the machine hits all alike); median
 and spread.  The yardsticks are measured in the same run: the full upload, and one 1080p frame of the scene.  GPU box.
+--device-rows: flx_scene_update_device beside them, the rows in torch tensors on the device (made before the clock starts: that is where such an application
+has them); the host-row kinds are measured again in the same run, and the lines are APPENDED to the file.  (The events stand on the context's stream: the check
+kernel, which runs on a stream of its own and is waited for inside the call, shows in the host's columns.)
 
-usage: scene_update_time.py [--out profiles/scene_update.txt] [--repeats 25]"""
+usage: scene_update_time.py [--out profiles/scene_update.txt] [--repeats 25] [--device-rows]"""
 import ctypes as C
 import os
 import sys
 import time
 
 import numpy as np
+
+DEVICE_ROWS = "--device-rows" in sys.argv
+if DEVICE_ROWS:
+    import torch                               # (before the library: INTEGRATION.md, Build)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "web-ray-tracer_amd"))
@@ -94,6 +101,19 @@ kinds = [
     ("flx_scene_update, the monkey's rows, geometry only", lambda v: rows(v, first, count, False)),
     ("flx_scene_update, all rows", lambda v: rows(v, 0, n)),
 ]
+if DEVICE_ROWS:
+    on_device = [(torch.from_numpy(v.arrays["geometry"].reshape(-1, 12)).cuda(), torch.from_numpy(v.arrays["attributes"].reshape(-1, 28)).cuda()) for v in versions]
+
+    def device_rows(v, lo, cnt, attributes=True):
+        g, a = on_device[versions.index(v)]
+        ctx.update_scene_rows_device(lo, g[lo:lo + cnt], a[lo:lo + cnt] if attributes else None)
+
+    kinds += [
+        ("flx_scene_update_device, the monkey's rows", lambda v: device_rows(v, first, count)),
+        ("flx_scene_update_device, the monkey's rows, geometry only", lambda v: device_rows(v, first, count, False)),
+        ("flx_scene_update_device, all rows", lambda v: device_rows(v, 0, n)),
+        ("flx_scene_update_device, all rows, geometry only", lambda v: device_rows(v, 0, n, False)),
+    ]
 samples = {label: [] for label, _ in kinds}
 for rep in range(WARMUP + REPEATS):
     v = versions[rep % len(versions)]
@@ -109,22 +129,26 @@ for rep in range(WARMUP + 7):
         frame.append((time.perf_counter() - t0) * 1e3)
 gpu_frame = ctx.last_frame_ms()[0]
 
-lines = ["scene updates on %s: %d entries (%d padded rows), the monkey's rows [%d, %d) = %d rows; %d calls of each kind after %d warm-up rounds, alternating"
-         % (ctx.device_info()[0], sc.meta["textureLength"], n, first, first + count, count, REPEATS, WARMUP),
+lines = ["%sscene updates on %s: %d entries (%d padded rows), the monkey's rows [%d, %d) = %d rows; %d calls of each kind after %d warm-up rounds, alternating"
+         % ("\nrows in device memory (--device-rows), the host-row kinds measured again beside them\n" if DEVICE_ROWS else "", ctx.device_info()[0], sc.meta["textureLength"], n, first, first + count, count, REPEATS, WARMUP),
          "ms: median (min .. max)",
-         "%-52s %-26s %-26s %-26s" % ("", "host, inside the call", "host, call + flx_sync", "GPU, events around the call")]
+         "%-58s %-26s %-26s %-26s" % ("", "host, inside the call", "host, call + flx_sync", "GPU, events around the call")]
 med = {}
 for label, _ in kinds:
     a = np.array(samples[label])
     med[label] = np.median(a, axis=0)
-    lines.append("%-52s " % label + " ".join("%-26s" % ("%.3f (%.3f .. %.3f)" % (np.median(a[:, k]), a[:, k].min(), a[:, k].max())) for k in range(3)))
+    lines.append("%-58s " % label + " ".join("%-26s" % ("%.3f (%.3f .. %.3f)" % (np.median(a[:, k]), a[:, k].min(), a[:, k].max())) for k in range(3)))
 lines.append("one 1920x1080 frame of the scene (flx_render, host wall clock incl. the copy out): median %.3f ms; GPU time of the last one %.3f ms" % (np.median(frame), gpu_frame))
 up, mk, al = med[kinds[0][0]][1], med[kinds[1][0]][1], med[kinds[3][0]][1]
 lines.append("the monkey's rows take %.1f %% of the full upload's time (call + sync), all rows %.1f %%; the frame's GPU time is %.3f ms: the monkey update is %s it, the update of all rows %s it"
              % (100 * mk / up, 100 * al / up, gpu_frame, "below" if mk < gpu_frame else "ABOVE", "below" if al < gpu_frame else "ABOVE"))
+if DEVICE_ROWS:
+    for what, host, dev in (("the monkey's rows", kinds[1][0], kinds[4][0]), ("all rows", kinds[3][0], kinds[6][0])):
+        lines.append("%s from device memory take %.3f ms against %.3f ms from host memory (call + sync): %.2f x"
+                     % (what, med[dev][1], med[host][1], med[host][1] / med[dev][1]))
 text = "\n".join(lines) + "\n"
 print(text)
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-with open(out_path, "w") as fh:
+with open(out_path, "a" if DEVICE_ROWS else "w") as fh:
     fh.write(text)
 ctx.close()

@@ -112,7 +112,8 @@ extern "C" void flx_context_destroy(flx_context *ctx) {
     for (hipEvent_t ev : { ctx->ev_slot_start[i], ctx->ev_slot_traced[i], ctx->ev_slot_done[i] }) if (ev) (void)hipEventDestroy(ev);
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   for (hipEvent_t ev : ctx->stage_done) if (ev) (void)hipEventDestroy(ev);
-  if (ctx->update_done) (void)hipEventDestroy(ctx->update_done);
+  if (ctx->update_stream) { (void)hipStreamSynchronize(ctx->update_stream); (void)hipStreamDestroy(ctx->update_stream); }
+  for (hipEvent_t ev : { ctx->update_done, ctx->update_checked, ctx->update_produced, ctx->geometry_uploaded }) if (ev) (void)hipEventDestroy(ev);
   if (ctx->sv_stream) (void)hipStreamDestroy(ctx->sv_stream);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;                              /* its buffers go with it, on its device (set above; a twin's views of this context's scene arrays free nothing) */
@@ -333,6 +334,8 @@ extern "C" flx_status flx_scene_upload(flx_context *ctx, const float *geometry, 
   ctx->last_walk_lds = WalkLdsLaunch();
   ctx->geometry_version++;
   if ((s = upload(ctx, ctx->d_geometry, geometry, (size_t)n_entries_padded * 48))) return s;
+  if (!ctx->geometry_uploaded) FLX_HIP(ctx, hipEventCreateWithFlags(&ctx->geometry_uploaded, hipEventDisableTiming));
+  FLX_HIP(ctx, hipEventRecord(ctx->geometry_uploaded, ctx->stream));      /* (a small array is copied in stream order: flx_scene_update_device's check reads it on another stream) */
   if ((s = upload(ctx, ctx->d_attributes, attributes, (size_t)n_entries_padded * 112))) return s;
   if ((s = upload(ctx, ctx->d_ids, ids, (size_t)n_ids * 4))) return s;
   {
@@ -415,9 +418,82 @@ extern "C" flx_status flx_scene_update(flx_context *ctx, uint32_t first_entry, u
   if (!bounded) ctx->walk_fast_boxes = 0u;          /* until the next flx_scene_upload: both box tests give the same bits under the precondition */
   FLX_HIP(ctx, hipMemcpyAsync(ctx->d_update_rows, ctx->h_update, gfloats * 4, hipMemcpyHostToDevice, ctx->stream));
   if (attributes) FLX_HIP(ctx, hipMemcpyAsync(ctx->d_attributes + (size_t)first_entry * 7, ctx->h_update + gfloats, afloats * 4, hipMemcpyHostToDevice, ctx->stream));
-  FLX_HIP(ctx, hipEventRecord(ctx->update_done, ctx->stream));
-  ctx->update_pending = true;
   launch_scene_rows(ctx->d_update_rows, ctx->d_geometry, first_entry, n_entries, ctx->stream);
+  FLX_HIP(ctx, hipEventRecord(ctx->update_done, ctx->stream));      /* (after the scatter: flx_scene_update_device writes d_update_rows on a stream of its own) */
+  ctx->update_pending = true;
+  launch_refit(ctx->d_geometry, ctx->n_entries, ctx->d_refit, ctx->stream);
+  launch_rederive(ctx->d_geometry, ctx->n_entries, ctx->d_walk, ctx->walk_entries, ctx->stream);
+  launch_rederive(ctx->d_geometry, ctx->n_entries, ctx->d_fwd, ctx->fwd_entries, ctx->stream);
+  FLX_HIP(ctx, hipGetLastError());
+  return shared_upload_end(ctx);
+}
+
+/* whether [p, p + bytes) is device memory of this context's device, 16-byte aligned */
+static bool rows_on_device(const flx_context *ctx, const void *p, size_t bytes) {
+  hipPointerAttribute_t at;
+  if (((uintptr_t)p & 15u) || hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  if (at.type != hipMemoryTypeDevice || at.device != ctx->device) return false;
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return (uintptr_t)p - (uintptr_t)base + bytes <= size;
+}
+
+/* flx_scene_update for rows in device memory.  What the host's loop over the rows decides there, k_rows_check_stage (flx_refit.hip) decides here, on update_stream:
+ * the host waits for that stream alone — the frames in flight on ctx->stream go on — and reads the verdict.  The same pass has copied the rows into the stage, so
+ * from the verdict on this is flx_scene_update from flx_server_stop on.  Nothing of the scene has been touched and nothing is enqueued on ctx->stream when a row
+ * is refused. */
+extern "C" flx_status flx_scene_update_device(flx_context *ctx, uint32_t first_entry, uint32_t n_entries, const void *d_geometry, const void *d_attributes,
+                                              void *producer_stream) {
+  if (!ctx) return FLX_ERR_INVALID;
+  if (!ctx->have_scene) return fail(ctx, FLX_ERR_NO_SCENE, "flx_scene_update before flx_scene_upload");
+  if ((uint64_t)first_entry + n_entries > ctx->n_entries) return fail(ctx, FLX_ERR_INVALID, "flx_scene_update: the rows leave the entry array");
+  if (n_entries == 0) return FLX_OK;
+  if (!d_geometry) return fail(ctx, FLX_ERR_INVALID, "flx_scene_update: geometry is NULL");
+  if (ctx->scene_has_nan) return fail(ctx, FLX_ERR_INVALID, "flx_scene_update: the uploaded scene has a NaN vertex (its boxes cannot be refitted as the flatten makes them)");
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  if (!rows_on_device(ctx, d_geometry, (size_t)n_entries * 48) || (d_attributes && !rows_on_device(ctx, d_attributes, (size_t)n_entries * 112)))
+    return fail(ctx, FLX_ERR_INVALID, "flx_scene_update_device: the rows are not in memory of the context's device, 16-byte aligned");
+  flx_status s;
+  /* everything the update needs is there before anything is enqueued: a failed allocation leaves the scene as it was */
+  if (ctx->update_pending) { FLX_HIP(ctx, hipEventSynchronize(ctx->update_done)); ctx->update_pending = false; }      /* (the last update's scatter reads the stage) */
+  if (!ctx->update_stream) FLX_HIP(ctx, hipStreamCreateWithFlags(&ctx->update_stream, hipStreamNonBlocking));
+  for (hipEvent_t *ev : { &ctx->update_done, &ctx->update_checked, &ctx->update_produced }) if (!*ev) FLX_HIP(ctx, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+  if ((s = ctx->d_update_verdict.ensure(ctx, 4)) || (s = ctx->h_update_verdict.ensure(ctx, 4, hipHostMallocDefault))) return s;
+  if (!ctx->d_update_rows.fits((size_t)n_entries * 3) || (d_attributes && !ctx->d_update_attributes.fits((size_t)n_entries * 7)) ||
+      !ctx->d_refit.fits(refit_workspace_words(ctx->n_entries))) {
+    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));      /* (an earlier update's kernels and copies may still read what is freed here) */
+    if ((s = ctx->d_update_rows.ensure(ctx, (size_t)n_entries * 3)) || (d_attributes && (s = ctx->d_update_attributes.ensure(ctx, (size_t)n_entries * 7))) ||
+        (s = ctx->d_refit.ensure(ctx, refit_workspace_words(ctx->n_entries)))) return s;
+  }
+  if (producer_stream) {
+    FLX_HIP(ctx, hipEventRecord(ctx->update_produced, (hipStream_t)producer_stream));
+    FLX_HIP(ctx, hipStreamWaitEvent(ctx->update_stream, ctx->update_produced, 0));
+  }
+  FLX_HIP(ctx, hipStreamWaitEvent(ctx->update_stream, ctx->geometry_uploaded, 0));      /* (words 6, 9 and 10 of d_geometry: written by flx_scene_upload alone) */
+  FLX_HIP(ctx, hipMemsetAsync(ctx->d_update_verdict, 0xff, 16, ctx->update_stream));
+  launch_rows_check_stage((const float4 *)d_geometry, (const float4 *)d_attributes, ctx->d_geometry, first_entry, n_entries, ctx->d_update_rows,
+                          ctx->d_update_attributes, ctx->d_update_verdict, ctx->update_stream);
+  FLX_HIP(ctx, hipGetLastError());
+  FLX_HIP(ctx, hipMemcpyAsync(ctx->h_update_verdict, ctx->d_update_verdict, 16, hipMemcpyDeviceToHost, ctx->update_stream));
+  FLX_HIP(ctx, hipEventRecord(ctx->update_checked, ctx->update_stream));
+  FLX_HIP(ctx, hipEventSynchronize(ctx->update_checked));
+  const uint32_t verdict = ctx->h_update_verdict[0];
+  if (verdict != 0xffffffffu) {
+    static const char *const refusal[4] = { "flx_scene_update: a row changes its kind (word 10)", "flx_scene_update: a row changes its transform number (word 9)",
+                                            "flx_scene_update: a box row changes its skip count (word 6)", "flx_scene_update: a vertex is not finite" };
+    return fail(ctx, FLX_ERR_INVALID, refusal[verdict & 3u]);
+  }
+  const bool bounded = ctx->h_update_verdict[1] != 0u;
+  if ((s = flx_server_stop(ctx))) return s;          /* (a running frame server reads the scene) */
+  if ((s = shared_upload_begin(ctx))) return s;
+  ctx->geometry_version++; ctx->scene_version++; ctx->structure_version++;
+  if (!bounded) ctx->walk_fast_boxes = 0u;
+  FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->update_checked, 0));      /* the stage is complete */
+  if (d_attributes) FLX_HIP(ctx, hipMemcpyAsync(ctx->d_attributes + (size_t)first_entry * 7, ctx->d_update_attributes, (size_t)n_entries * 112, hipMemcpyDeviceToDevice, ctx->stream));
+  launch_scene_rows(ctx->d_update_rows, ctx->d_geometry, first_entry, n_entries, ctx->stream);
+  FLX_HIP(ctx, hipEventRecord(ctx->update_done, ctx->stream));      /* the stage has been consumed: the next update of either kind waits for this before it overwrites it */
+  ctx->update_pending = true;
   launch_refit(ctx->d_geometry, ctx->n_entries, ctx->d_refit, ctx->stream);
   launch_rederive(ctx->d_geometry, ctx->n_entries, ctx->d_walk, ctx->walk_entries, ctx->stream);
   launch_rederive(ctx->d_geometry, ctx->n_entries, ctx->d_fwd, ctx->fwd_entries, ctx->stream);

@@ -107,13 +107,20 @@ struct flx_context {
   /* flx_scene_update (rows of the uploaded scene replaced, the boxes refitted on the device: flx_refit.hip).  What the host must know of the scene to check the rows it
    * is given without reading the device: the bits of words 6, 9 and 10 of every entry, kept at flx_scene_upload; whether a triangle of the upload had a NaN vertex
    * (the refit's min / max would not carry it into the boxes as Math.min does: such a scene takes no updates).  The rows go through pinned memory of the context's
-   * (update_done: the copies that last read it) into d_update_rows, from where a kernel scatters them; d_refit is the refit's workspace. */
+   * into d_update_rows, from where a kernel scatters them (update_done: that kernel, and with it whatever last read the stage); d_refit is the refit's workspace.
+   * flx_scene_update_device's rows are in device memory already: a kernel on update_stream checks them against d_geometry and copies them into d_update_rows and
+   * d_update_attributes; its verdict (d_update_verdict, two words) comes back through h_update_verdict, update_checked follows that copy, update_produced is
+   * recorded on the caller's stream.  geometry_uploaded follows flx_scene_upload's copy of the geometry array, which the check reads. */
   std::vector<uint32_t> h_entry_meta;
   bool scene_has_nan = false;
   PinnedBuffer<float> h_update;
   hipEvent_t update_done = nullptr;
   bool update_pending = false;
-  DeviceBuffer<float4> d_update_rows;
+  DeviceBuffer<float4> d_update_rows, d_update_attributes;
+  DeviceBuffer<uint32_t> d_update_verdict;
+  PinnedBuffer<uint32_t> h_update_verdict;
+  hipStream_t update_stream = nullptr;
+  hipEvent_t update_checked = nullptr, update_produced = nullptr, geometry_uploaded = nullptr;
   DeviceBuffer<uint32_t> d_refit;
   /* DeviceScene::angle_tan: per triangle, from the geometry / attribute arrays and this context's transforms; made again (on this context's stream, in front of
    * the frame that needs it) when any of them changed: angle_key = the versions it was made from */

@@ -117,6 +117,11 @@ void launch_raster(const DeviceScene &sc, const DeviceFrame &fr, int hdr, float4
 void launch_raster(const DeviceScene &sc, const DeviceFrame &fr, int hdr, uint32_t *out8, hipStream_t stream);
 /* flx_scene_update (flx_refit.hip).  n_rows rows (3 float4 each) -> geometry rows [first, first + n_rows); a box row keeps its words 0..5 */
 void launch_scene_rows(const float4 *rows, float4 *geometry, uint32_t first, uint32_t n_rows, hipStream_t stream);
+/* flx_scene_update_device.  n_rows rows in device memory (and their 7 float4 of attributes each, or nullptr) copied into stage_rows / stage_attributes and held
+ * against geometry rows [first, first + n_rows) by flx_scene_update's rules.  verdict: two words, both ~0 before the launch; [0] <- the least
+ * row * 4 + rule (0 kind, 1 transform number, 2 skip count, 3 a vertex not finite) of a row that offends, [1] <- 0 if a vertex lies beyond the fast box bound */
+void launch_rows_check_stage(const float4 *rows, const float4 *attributes, const float4 *geometry, uint32_t first, uint32_t n_rows, float4 *stage_rows,
+                             float4 *stage_attributes, uint32_t *verdict, hipStream_t stream);
 /* words 0..5 of every box row with a skip count s > 0 = min / max over the vertices of the triangle rows in (i, i + s], -0 below +0 (a box over no triangle keeps
  * its floats); work: refit_workspace_words(n_entries) words */
 size_t refit_workspace_words(uint32_t n_entries);

@@ -11,6 +11,9 @@
  * Bounds are kept as ORDERED KEYS — the float's bits with the sign folded so that unsigned comparison is the total order -inf < .. < -0 < +0 < .. < +inf,
  * which is how Math.min / Math.max order equal-comparing zeros — so min / max are integer operations and the key maps back to the very float.  (NaN has no
  * place in that order as Math.min treats it: the host refuses NaN vertices.)  No atomics, no level-per-launch climb of the tree.
+ *
+ * flx_scene_update_device hands the rows over in device memory: k_rows_check_stage holds them against the scene as flx_scene_update's loop does on the host,
+ * and copies them into the context's stage in the same pass.
  */
 #include <hip/hip_runtime.h>
 
@@ -220,6 +223,62 @@ __global__ __launch_bounds__(RB) void k_rederive(const float4 *__restrict__ geom
   }
 }
 
+/* flx_scene_update_device: the caller's rows are in device memory.  One streaming pass, a lane per float4: the first 3 * n_rows lanes take the geometry rows, the
+ * 7 * n_rows behind them the attribute rows (where given).  Every float4 goes into the context's stage as it is, and the geometry lanes hold their part of the row
+ * against the scene's own array by flx_scene_update's rules, compared as bits like there:
+ *   0  word 10 (kind) differs;  for kind != 0:  1  word 9 (transform number) differs;  a box:  2  word 6 (skip count) differs;  otherwise:  3  a vertex word
+ *   that is not finite.
+ * The host's loop returns at the first offending row and, within it, at the first of these rules in this order: that is the least row * 4 + rule, so
+ * verdict[0] takes an unsigned min of it (set to ~0 before the launch: no row offends).  verdict[1], set to ~0 likewise, becomes 0 when a vertex lies beyond
+ * the fast box test's bound.  A wave reduces its lanes' keys before one of them issues the atomic, and only where there is something to report.
+ * (Words 6, 9 and 10 of the scene's array hold the same bits from one flx_scene_upload to the next, whatever updates run beside this kernel.) */
+__global__ __launch_bounds__(RB) void k_rows_check_stage(const float4 *__restrict__ rows, const float4 *__restrict__ attributes, const float4 *__restrict__ geometry,
+                                                         uint32_t first, uint32_t n_rows, float4 *__restrict__ stage_rows, float4 *__restrict__ stage_attributes,
+                                                         uint32_t *__restrict__ verdict) {
+  const uint32_t q = blockIdx.x * RB + threadIdx.x;      /* (n_rows < 2^28: 10 * n_rows fits) */
+  const uint32_t gcount = n_rows * 3u;
+  uint32_t key = 0xffffffffu;
+  bool beyond = false;
+  if (q < gcount) {
+    const float4 v = rows[q];
+    stage_rows[q] = v;
+    const uint32_t row = q / 3u, part = q - row * 3u;
+    const float4 last = part == 2u ? v : rows[row * 3u + 2u];      /* words 8 .. 11: the kind the row claims decides what is looked at */
+    const float kind = last.z;
+    const size_t at = ((size_t)first + row) * 3 + part;
+    uint32_t rule = 4u;
+    if (part == 2u) {
+      const float4 have = geometry[at];
+      if (__float_as_uint(v.z) != __float_as_uint(have.z)) rule = 0u;
+      else if (kind != 0.0f && __float_as_uint(v.y) != __float_as_uint(have.y)) rule = 1u;
+    }
+    if (kind == 1.0f) {
+      if (part == 1u && __float_as_uint(v.z) != __float_as_uint(geometry[at].z)) rule = min(rule, 2u);
+    } else if (kind != 0.0f) {                     /* nine vertex words: 0 .. 3, 4 .. 7, 8 */
+      const float w[4] = { v.x, v.y, v.z, v.w };
+      const int words = part == 2u ? 1 : 4;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        if (k < words) {
+          const float a = fabsf(w[k]);
+          if (!(a < __builtin_inff())) rule = min(rule, 3u);      /* inf and NaN */
+          if (!(a <= 5.764607523034235e17f)) beyond = true;
+        }
+      }
+    }
+    if (rule < 4u) key = row * 4u + rule;
+  } else if (attributes && q - gcount < n_rows * 7u) {
+    stage_attributes[q - gcount] = attributes[q - gcount];
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) key = min(key, (uint32_t)__shfl_xor((int)key, d));
+  const bool anyBeyond = __any(beyond);
+  if ((threadIdx.x & 63u) == 0u) {
+    if (key != 0xffffffffu) atomicMin(&verdict[0], key);
+    if (anyBeyond) atomicMin(&verdict[1], 0u);
+  }
+}
+
 struct RefitWork { uint32_t *pre0, *suf0, *tot0, *pre1, *suf1, *tot1; uint32_t nb0, nb1; size_t words; };
 RefitWork refit_layout(uint32_t n, uint32_t *base) {
   RefitWork w;
@@ -238,6 +297,13 @@ size_t refit_workspace_words(uint32_t n_entries) { return refit_layout(n_entries
 void launch_scene_rows(const float4 *rows, float4 *geometry, uint32_t first, uint32_t n_rows, hipStream_t stream) {
   const uint32_t count = n_rows * 3u;              /* (n_rows < 2^28: flx_scene_upload) */
   if (count) hipLaunchKernelGGL(k_scene_rows, dim3((count + RB - 1) / RB), dim3(RB), 0, stream, rows, geometry, first, count);
+}
+
+void launch_rows_check_stage(const float4 *rows, const float4 *attributes, const float4 *geometry, uint32_t first, uint32_t n_rows, float4 *stage_rows,
+                             float4 *stage_attributes, uint32_t *verdict, hipStream_t stream) {
+  const uint32_t count = n_rows * (attributes ? 10u : 3u);
+  if (count) hipLaunchKernelGGL(k_rows_check_stage, dim3((count + RB - 1) / RB), dim3(RB), 0, stream, rows, attributes, geometry, first, n_rows, stage_rows,
+                                stage_attributes, verdict);
 }
 
 void launch_refit(float4 *geometry, uint32_t n_entries, uint32_t *work, hipStream_t stream) {

@@ -31,7 +31,7 @@ EXPORTS = [
     "flx_share_create", "flx_share_join", "flx_share_leave", "flx_frame_begin_shared", "flx_frame_end_shared",
     "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_sample_parallel", "flx_debug_last_trace_kernel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
     "flx_raster_render", "flx_debug_walk_staged", "flx_debug_last_walk_lds", "flx_debug_walk_fast_boxes",
-    "flx_scene_update", "flx_group_scene_update", "flx_debug_scene_read",
+    "flx_scene_update", "flx_group_scene_update", "flx_debug_scene_read", "flx_scene_update_device",
 ]
 
 
@@ -61,6 +61,7 @@ def _load():
         "flx_scene_upload": (C.c_int, [vp, fp, fp, u32, C.POINTER(C.c_int32), u32]),
         "flx_scene_update": (C.c_int, [vp, u32, u32, fp, fp]),
         "flx_group_scene_update": (C.c_int, [vp, u32, u32, fp, fp]),
+        "flx_scene_update_device": (C.c_int, [vp, u32, u32, vp, vp, vp]),
         "flx_debug_scene_read": (C.c_int, [vp, C.c_int, fp, u32]),
         "flx_transforms_upload": (C.c_int, [vp, fp, fp, u32]),
         "flx_lights_upload": (C.c_int, [vp, fp, u32]),
@@ -201,6 +202,21 @@ def _rows(geometry, attributes):
     return geometry, attributes, geometry.shape[0]
 
 
+def _device_rows(x, width, device, what):
+    """rows of update_scene_rows_device -> (device address, row count): a torch tensor [n, width] (float32, contiguous, on cuda:`device`) or (address, n)"""
+    if isinstance(x, tuple):
+        address, n = x
+        return int(address), int(n)
+    import torch                               # (here and not at the top: capi imports without torch)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("update_scene_rows_device: %s is a torch tensor or (address, rows)" % what)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != width or not x.is_contiguous():
+        raise ValueError("update_scene_rows_device: %s is a contiguous float32 tensor [n, %d]" % (what, width))
+    if x.device.type != "cuda" or x.device.index != device:
+        raise ValueError("update_scene_rows_device: %s is on %s, the context on cuda:%d" % (what, x.device, device))
+    return x.data_ptr(), x.shape[0]
+
+
 class Context:
     """One GPU context (flx_context).  Mirrors the life cycle of the reference renderer object:
     construct -> updateScene()/updatePrimaryLightSources() -> render frames -> halt()."""
@@ -211,6 +227,7 @@ class Context:
         if rc != 0:
             raise FlexLightHipError("flx_context_create(%d) failed (%d): %s" % (device, rc, LIB.flx_last_error(None).decode()))
         self._h = h
+        self._device = device
         self._pending = []                     # the frame loop's frames in flight, oldest first (frame_begin / frame_end)
 
     def close(self):
@@ -250,6 +267,25 @@ class Context:
         they stay), every box refitted on the device."""
         geometry, attributes, n = _rows(geometry, attributes)
         self._check(LIB.flx_scene_update(self._h, first, n, _fp(geometry), None if attributes is None else _fp(attributes)), "flx_scene_update")
+
+    def update_scene_rows_device(self, first, geometry, attributes=None, stream=None):
+        """flx_scene_update_device: update_scene_rows for rows that are in device memory.  geometry: a torch tensor [n, 12] (float32, contiguous, on the
+        context's device) or (address, n); attributes: None (they stay), a tensor [n, 28] or (address, n).  stream: the torch.cuda.Stream (or the raw
+        hipStream_t) on which the rows were written, which the check then waits for; None: the rows are complete.  The C call cannot name the legacy default
+        stream (its handle is 0, which means None there): a torch stream with that handle is synchronised here instead."""
+        g, n = _device_rows(geometry, 12, self._device, "geometry")
+        a = None
+        if attributes is not None:
+            a, rows = _device_rows(attributes, 28, self._device, "attributes")
+            if rows != n:
+                raise ValueError("update_scene_rows_device: as many attribute rows as geometry rows")
+        if stream is not None and not isinstance(stream, int):
+            handle = stream.cuda_stream
+            if handle == 0:
+                stream.synchronize()
+            stream = handle
+        self._check(LIB.flx_scene_update_device(self._h, first, n, C.c_void_p(g), C.c_void_p(a) if a is not None else None,
+                                                C.c_void_p(stream) if stream else None), "flx_scene_update_device")
 
     def scene_read(self, which, rows=None):
         """flx_debug_scene_read: the device's 'geometry' [rows, 12], 'attributes' [rows, 28], 'walk' (the threaded copy) or 'fwd' (the forward-ordered
