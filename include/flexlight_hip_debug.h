@@ -147,6 +147,25 @@ flx_status flx_scene_update_device(flx_context *ctx, uint32_t first_entry, uint3
                                    const void *d_geometry /* n_entries * 12 floats, on ctx's device */,
                                    const void *d_attributes /* n_entries * 28 floats or NULL */,
                                    void *producer_stream /* hipStream_t that wrote the rows, or NULL: they are complete */);
+/* flx_scene_upload for arrays that are ALREADY ON THE DEVICE (a mesh a simulation or a torch op produced, a tree rebuilt there): geometry, attributes and ids are
+ * pointers into device memory of ctx's device, 16-byte aligned, each allocation long enough for its array (FLX_ERR_INVALID with a message of its own otherwise; d_ids
+ * may be NULL when n_ids is 0).  Everything flx_scene_upload decides and derives on the host — the refusals, max_transform, the NaN and bounded-box flags, the
+ * threaded hot-first copy, the forward-ordered copy — kernels decide and derive (csrc/flx_derive.hip), with the same results: the same refusals in the same order
+ * with the same messages (an empty scene; more than 2^28 - 1 entries; then the first offending entry and, within it, the first of: transform number out of range,
+ * skip count leaves the array, type not 0, 1 or 2), and for every properly nested skip list the same four device arrays bit for bit, hence the same frames.  A
+ * list that is not properly nested (a box whose range ends inside another's) still gives a valid scene, every link naming the entry's original successor and every
+ * walk visiting the same entries, but the storage order of the threaded copy may differ from the host's.  A refused call leaves the context's scene exactly as it
+ * was, still renderable.  No array crosses the bus in either direction: eight words of scalars come back.  The scans behind the derivation recurse on their block
+ * totals, a launch per level: any n_entries_padded flx_scene_upload takes.  producer_stream: as for flx_scene_update_device.  Ordered like flx_scene_upload: a
+ * frame begun before the call renders the old scene, a frame begun after it the new; the call waits for the context's stream before it returns, and the caller's
+ * arrays are free then.  flx_scene_update and flx_scene_update_device work afterwards as after flx_scene_upload (the first update of HOST rows fetches the 12 bytes
+ * per entry it holds its rows against).  A group keeps the host call (flx_group_scene_upload): the arrays live on one device, its contexts on several. */
+flx_status flx_scene_upload_device(flx_context *ctx,
+                                   const void *d_geometry   /* n_entries_padded * 12 floats, on ctx's device */,
+                                   const void *d_attributes /* n_entries_padded * 28 floats */,
+                                   uint32_t n_entries_padded,
+                                   const void *d_ids /* n_ids int32, or NULL when n_ids == 0 */, uint32_t n_ids,
+                                   void *producer_stream /* hipStream_t that wrote the arrays, or NULL: complete */);
 /* The uploaded scene as the device holds it, after everything enqueued so far: which 0 the geometry rows (12 floats per entry), 1 the attribute rows (28),
  * 2 the threaded hot-first copy (12 per entry of walk_entries), 3 the forward-ordered copy (12 per entry of fwd_entries: flx_debug_last_walk_lds' out[5], out[6]).
  * The first n_floats floats of the array; FLX_ERR_INVALID beyond its end.  Tests compare flx_scene_update's arrays with a fresh upload's. */

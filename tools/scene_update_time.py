@@ -7,8 +7,11 @@ and spread.  The yardsticks are measured in the same run: the full upload, and o
 --device-rows: flx_scene_update_device beside them, the rows in torch tensors on the device (made before the clock starts: that is where such an application
 has them); the host-row kinds are measured again in the same run, and the lines are APPENDED to the file.  (The events stand on the context's stream: the check
 kernel, which runs on a stream of its own and is waited for inside the call, shows in the host's columns.)
+--device-upload: flx_scene_upload_device of the whole scene, its three arrays in torch tensors on the device (made before the clock starts), beside the host's
+flx_scene_upload of the same scenes in the same run, alternating; only these two kinds, and the lines are APPENDED to the file.  (Its check runs on a stream of
+its own like flx_scene_update_device's, and the call ends with a wait for the context's stream: the host's columns are the ones to read.)
 
-usage: scene_update_time.py [--out profiles/scene_update.txt] [--repeats 25] [--device-rows]"""
+usage: scene_update_time.py [--out profiles/scene_update.txt] [--repeats 25] [--device-rows | --device-upload]"""
 import ctypes as C
 import os
 import sys
@@ -17,7 +20,8 @@ import time
 import numpy as np
 
 DEVICE_ROWS = "--device-rows" in sys.argv
-if DEVICE_ROWS:
+DEVICE_UPLOAD = "--device-upload" in sys.argv
+if DEVICE_ROWS or DEVICE_UPLOAD:
     import torch                               # (before the library: INTEGRATION.md, Build)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -114,6 +118,10 @@ if DEVICE_ROWS:
         ("flx_scene_update_device, all rows", lambda v: device_rows(v, 0, n)),
         ("flx_scene_update_device, all rows, geometry only", lambda v: device_rows(v, 0, n, False)),
     ]
+if DEVICE_UPLOAD:
+    arrays_on_device = [(torch.from_numpy(v.arrays["geometry"].reshape(-1, 12)).cuda(), torch.from_numpy(v.arrays["attributes"].reshape(-1, 28)).cuda(),
+                         torch.from_numpy(v.arrays["ids"]).cuda()) for v in versions]
+    kinds = kinds[:1] + [("flx_scene_upload_device, the whole scene", lambda v: ctx.upload_scene_device(*arrays_on_device[versions.index(v)]))]
 samples = {label: [] for label, _ in kinds}
 for rep in range(WARMUP + REPEATS):
     v = versions[rep % len(versions)]
@@ -130,7 +138,8 @@ for rep in range(WARMUP + 7):
 gpu_frame = ctx.last_frame_ms()[0]
 
 lines = ["%sscene updates on %s: %d entries (%d padded rows), the monkey's rows [%d, %d) = %d rows; %d calls of each kind after %d warm-up rounds, alternating"
-         % ("\nrows in device memory (--device-rows), the host-row kinds measured again beside them\n" if DEVICE_ROWS else "", ctx.device_info()[0], sc.meta["textureLength"], n, first, first + count, count, REPEATS, WARMUP),
+         % ("\nrows in device memory (--device-rows), the host-row kinds measured again beside them\n" if DEVICE_ROWS else
+            "\nthe whole scene from device memory (--device-upload), the host upload measured beside it\n" if DEVICE_UPLOAD else "", ctx.device_info()[0], sc.meta["textureLength"], n, first, first + count, count, REPEATS, WARMUP),
          "ms: median (min .. max)",
          "%-58s %-26s %-26s %-26s" % ("", "host, inside the call", "host, call + flx_sync", "GPU, events around the call")]
 med = {}
@@ -139,9 +148,14 @@ for label, _ in kinds:
     med[label] = np.median(a, axis=0)
     lines.append("%-58s " % label + " ".join("%-26s" % ("%.3f (%.3f .. %.3f)" % (np.median(a[:, k]), a[:, k].min(), a[:, k].max())) for k in range(3)))
 lines.append("one 1920x1080 frame of the scene (flx_render, host wall clock incl. the copy out): median %.3f ms; GPU time of the last one %.3f ms" % (np.median(frame), gpu_frame))
-up, mk, al = med[kinds[0][0]][1], med[kinds[1][0]][1], med[kinds[3][0]][1]
-lines.append("the monkey's rows take %.1f %% of the full upload's time (call + sync), all rows %.1f %%; the frame's GPU time is %.3f ms: the monkey update is %s it, the update of all rows %s it"
-             % (100 * mk / up, 100 * al / up, gpu_frame, "below" if mk < gpu_frame else "ABOVE", "below" if al < gpu_frame else "ABOVE"))
+if DEVICE_UPLOAD:
+    host_ms, device_ms = med[kinds[0][0]][1], med[kinds[1][0]][1]
+    lines.append("the whole scene from device memory takes %.3f ms against %.3f ms from host memory (call + sync): %.2f x; the frame's GPU time is %.3f ms"
+                 % (device_ms, host_ms, host_ms / device_ms, gpu_frame))
+else:
+    up, mk, al = med[kinds[0][0]][1], med[kinds[1][0]][1], med[kinds[3][0]][1]
+    lines.append("the monkey's rows take %.1f %% of the full upload's time (call + sync), all rows %.1f %%; the frame's GPU time is %.3f ms: the monkey update is %s it, the update of all rows %s it"
+                 % (100 * mk / up, 100 * al / up, gpu_frame, "below" if mk < gpu_frame else "ABOVE", "below" if al < gpu_frame else "ABOVE"))
 if DEVICE_ROWS:
     for what, host, dev in (("the monkey's rows", kinds[1][0], kinds[4][0]), ("all rows", kinds[3][0], kinds[6][0])):
         lines.append("%s from device memory take %.3f ms against %.3f ms from host memory (call + sync): %.2f x"
@@ -149,6 +163,6 @@ if DEVICE_ROWS:
 text = "\n".join(lines) + "\n"
 print(text)
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-with open(out_path, "a" if DEVICE_ROWS else "w") as fh:
+with open(out_path, "a" if DEVICE_ROWS or DEVICE_UPLOAD else "w") as fh:
     fh.write(text)
 ctx.close()

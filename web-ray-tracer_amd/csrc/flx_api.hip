@@ -363,9 +363,28 @@ extern "C" flx_status flx_scene_upload(flx_context *ctx, const float *geometry, 
   ctx->n_ids = n_ids;
   ctx->max_transform = max_transform;
   ctx->h_entry_meta.swap(entry_meta);
+  ctx->entry_meta_stale = false;
   ctx->scene_has_nan = has_nan;
   if ((s = shared_upload_end(ctx))) return s;
   ctx->have_scene = true;
+  return FLX_OK;
+}
+
+/* h_entry_meta after flx_scene_upload_device, which leaves it on the device: words 6, 9 and 10 of every entry, compacted by a kernel and copied back, at the first
+ * update of host rows (rows in device memory are held against d_geometry itself).  On update_stream, behind the upload's copy of the geometry: the frames in flight
+ * on the context's stream go on. */
+static flx_status fetch_entry_meta(flx_context *ctx) {
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  flx_status s;
+  if ((s = ctx->d_derive.ensure(ctx, std::max(derive_workspace_words(ctx->n_entries), (size_t)ctx->n_entries * 3)))) return s;
+  if (!ctx->update_stream) FLX_HIP(ctx, hipStreamCreateWithFlags(&ctx->update_stream, hipStreamNonBlocking));
+  FLX_HIP(ctx, hipStreamWaitEvent(ctx->update_stream, ctx->geometry_uploaded, 0));
+  launch_entry_meta(ctx->d_geometry, ctx->n_entries, ctx->d_derive, ctx->update_stream);
+  FLX_HIP(ctx, hipGetLastError());
+  ctx->h_entry_meta.resize((size_t)ctx->n_entries * 3);
+  FLX_HIP(ctx, hipMemcpyAsync(ctx->h_entry_meta.data(), ctx->d_derive, (size_t)ctx->n_entries * 12, hipMemcpyDeviceToHost, ctx->update_stream));
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->update_stream));
+  ctx->entry_meta_stale = false;
   return FLX_OK;
 }
 
@@ -382,6 +401,7 @@ extern "C" flx_status flx_scene_update(flx_context *ctx, uint32_t first_entry, u
   if (!geometry) return fail(ctx, FLX_ERR_INVALID, "flx_scene_update: geometry is NULL");
   if (ctx->scene_has_nan) return fail(ctx, FLX_ERR_INVALID, "flx_scene_update: the uploaded scene has a NaN vertex (its boxes cannot be refitted as the flatten makes them)");
   bool bounded = true;
+  if (ctx->entry_meta_stale) { flx_status fs = fetch_entry_meta(ctx); if (fs) return fs; }      /* (the scene came through flx_scene_upload_device) */
   for (uint32_t r = 0; r < n_entries; r++) {
     const float *e = geometry + (size_t)r * 12;
     const uint32_t *m = &ctx->h_entry_meta[((size_t)first_entry + r) * 3];
@@ -499,6 +519,101 @@ extern "C" flx_status flx_scene_update_device(flx_context *ctx, uint32_t first_e
   launch_rederive(ctx->d_geometry, ctx->n_entries, ctx->d_fwd, ctx->fwd_entries, ctx->stream);
   FLX_HIP(ctx, hipGetLastError());
   return shared_upload_end(ctx);
+}
+
+/* upload() for an array that is in device memory already: the same order (the frame server ends, the versions count, a buffer that must grow waits for its readers),
+ * a copy on the device in stream order, and no wait behind it: flx_scene_upload_device waits once, at its end. */
+template <typename T>
+static flx_status upload_from_device(flx_context *ctx, DeviceBuffer<T> &dst, const void *d_src, size_t bytes) {
+  { flx_status ss = flx_server_stop(ctx); if (ss) return ss; }
+  ctx->structure_version++;
+  ctx->scene_version++;
+  if (bytes == 0) {
+    if (dst && ctx->twin) FLX_HIP(ctx, hipStreamSynchronize(ctx->twin->stream));
+    return dst.release(ctx);
+  }
+  const size_t count = (bytes + sizeof(T) - 1) / sizeof(T);
+  if (!dst.fits(count)) {
+    if (dst) {
+      FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      if (ctx->twin) FLX_HIP(ctx, hipStreamSynchronize(ctx->twin->stream));
+    }
+    flx_status s = dst.ensure(ctx, count);
+    if (s) return s;
+  }
+  if (d_src) FLX_HIP(ctx, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToDevice, ctx->stream));      /* (nullptr: room only, a kernel fills it) */
+  return FLX_OK;
+}
+
+/* flx_scene_upload for arrays in device memory.  What the host's loop over the entries decides, k_derive_check (flx_derive.hip) decides on update_stream, into the
+ * derive workspace alone: the host waits for that stream, reads the record of scalars, and a refused array has touched nothing of the context's scene and enqueued
+ * nothing on its stream.  From there on this is flx_scene_upload with copies on the device for its copies across the bus and launch_derive_copies for
+ * build_threaded and build_lockstep; one wait for the context's stream at the end, so that the caller's arrays are free (and a second lane finds the scene
+ * complete).  h_entry_meta stays on the device until a flx_scene_update of host rows asks for it (fetch_entry_meta). */
+extern "C" flx_status flx_scene_upload_device(flx_context *ctx, const void *d_geometry, const void *d_attributes, uint32_t n_entries_padded, const void *d_ids,
+                                              uint32_t n_ids, void *producer_stream) {
+  if (!ctx) return FLX_ERR_INVALID;
+  if (!d_geometry || !d_attributes || n_entries_padded == 0) return fail(ctx, FLX_ERR_INVALID, "flx_scene_upload: empty scene");
+  if (n_ids && !d_ids) return fail(ctx, FLX_ERR_INVALID, "flx_scene_upload: ids is NULL");
+  if (n_entries_padded > LINK_INDEX) return fail(ctx, FLX_ERR_INVALID, "flx_scene_upload: more than 2^28 - 1 entries");
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  if (!rows_on_device(ctx, d_geometry, (size_t)n_entries_padded * 48) || !rows_on_device(ctx, d_attributes, (size_t)n_entries_padded * 112) ||
+      (n_ids && !rows_on_device(ctx, d_ids, (size_t)n_ids * 4)))
+    return fail(ctx, FLX_ERR_INVALID, "flx_scene_upload_device: the arrays are not in memory of the context's device, 16-byte aligned");
+  ctx->sv_want_ver = false;                 /* (another scene: it has not moved yet) */
+  flx_status s;
+  if (!ctx->update_stream) FLX_HIP(ctx, hipStreamCreateWithFlags(&ctx->update_stream, hipStreamNonBlocking));
+  for (hipEvent_t *ev : { &ctx->update_checked, &ctx->update_produced, &ctx->geometry_uploaded }) if (!*ev) FLX_HIP(ctx, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+  /* (nothing in flight uses the workspace: this call and fetch_entry_meta end with a wait) */
+  if ((s = ctx->d_derive.ensure(ctx, derive_workspace_words(n_entries_padded))) || (s = ctx->h_derive_record.ensure(ctx, DERIVE_RECORD_WORDS, hipHostMallocDefault))) return s;
+  if (producer_stream) {
+    FLX_HIP(ctx, hipEventRecord(ctx->update_produced, (hipStream_t)producer_stream));
+    FLX_HIP(ctx, hipStreamWaitEvent(ctx->update_stream, ctx->update_produced, 0));
+  }
+  FLX_HIP(ctx, launch_derive_check((const float4 *)d_geometry, n_entries_padded, ctx->d_derive, ctx->update_stream));
+  FLX_HIP(ctx, hipMemcpyAsync(ctx->h_derive_record, ctx->d_derive, DERIVE_RECORD_WORDS * 4, hipMemcpyDeviceToHost, ctx->update_stream));
+  FLX_HIP(ctx, hipEventRecord(ctx->update_checked, ctx->update_stream));
+  FLX_HIP(ctx, hipEventSynchronize(ctx->update_checked));
+  const uint32_t *rec = ctx->h_derive_record;
+  if (rec[0] != 0u) {
+    static const char *const refusal[3] = { "flx_scene_upload: transform number out of range", "flx_scene_upload: AABB skip count leaves the entry array",
+                                            "flx_scene_upload: entry type is not 0, 1 or 2" };
+    const uint32_t rule = ~rec[0] & 3u;
+    return fail(ctx, FLX_ERR_INVALID, refusal[rule < 3u ? rule : 2u]);
+  }
+  const uint32_t max_transform = rec[1], live = rec[5], meta0 = rec[6];
+  const bool has_nan = rec[2] != 0u, bounded = rec[3] == 0u;
+  if ((s = shared_upload_begin(ctx))) return s;
+  ctx->have_scene = false;
+  ctx->last_walk_lds = WalkLdsLaunch();
+  ctx->geometry_version++;
+  if ((s = upload_from_device(ctx, ctx->d_geometry, d_geometry, (size_t)n_entries_padded * 48))) return s;
+  FLX_HIP(ctx, hipEventRecord(ctx->geometry_uploaded, ctx->stream));      /* (flx_scene_update_device's check reads the array on another stream) */
+  if ((s = upload_from_device(ctx, ctx->d_attributes, d_attributes, (size_t)n_entries_padded * 112))) return s;
+  if ((s = upload_from_device(ctx, ctx->d_ids, d_ids, (size_t)n_ids * 4))) return s;
+  /* both copies hold the live entries and one shared terminator; entry 0 is the shallowest entry with the lowest index: hot, the threaded copy's entry 1 */
+  ctx->walk_entries = live + 1u;
+  ctx->walk_hot = std::min(live, 4096u) + 1u;
+  ctx->walk_root = meta0 == 0u ? 0u : 1u | (meta0 & 3u) << LINK_KIND_SHIFT | ((meta0 >> 2) != 0u ? LINK_XFORM : 0u);
+  ctx->fwd_entries = live + 1u;
+  ctx->fwd_root = meta0 == 0u ? live : 0u;
+  ctx->lock_boxes = rec[4];
+  if ((s = upload_from_device(ctx, ctx->d_walk, nullptr, (size_t)ctx->walk_entries * 48))) return s;
+  if ((s = upload_from_device(ctx, ctx->d_fwd, nullptr, (size_t)ctx->fwd_entries * 48))) return s;
+  FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->update_checked, 0));      /* the workspace as the check left it */
+  launch_derive_copies(ctx->d_geometry, n_entries_padded, live, ctx->d_derive, ctx->d_walk, ctx->d_fwd, ctx->stream);
+  FLX_HIP(ctx, hipGetLastError());
+  ctx->walk_fast_boxes = bounded ? 1u : 0u;
+  ctx->lock_ok = max_transform == 0 && ctx->fwd_entries <= FLX_LOCK_MAX;
+  ctx->n_entries = n_entries_padded;
+  ctx->n_ids = n_ids;
+  ctx->max_transform = max_transform;
+  ctx->h_entry_meta.clear();
+  ctx->entry_meta_stale = true;
+  ctx->scene_has_nan = has_nan;
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));          /* the caller's arrays are not retained (and: shared_upload_end) */
+  ctx->have_scene = true;
+  return FLX_OK;
 }
 
 extern "C" flx_status flx_transforms_upload(flx_context *ctx, const float *rotation, const float *shift, uint32_t n_transforms) {

@@ -122,6 +122,11 @@ struct flx_context {
   hipStream_t update_stream = nullptr;
   hipEvent_t update_checked = nullptr, update_produced = nullptr, geometry_uploaded = nullptr;
   DeviceBuffer<uint32_t> d_refit;
+  /* flx_scene_upload_device (flx_derive.hip): its workspace, whose first words are the record of scalars that comes back through h_derive_record.  Such an upload
+   * leaves h_entry_meta on the device: entry_meta_stale, and the first flx_scene_update of host rows fetches it (fetch_entry_meta), 12 bytes per entry. */
+  DeviceBuffer<uint32_t> d_derive;
+  PinnedBuffer<uint32_t> h_derive_record;
+  bool entry_meta_stale = false;
   /* DeviceScene::angle_tan: per triangle, from the geometry / attribute arrays and this context's transforms; made again (on this context's stream, in front of
    * the frame that needs it) when any of them changed: angle_key = the versions it was made from */
   DeviceBuffer<float4> d_angle_tan;

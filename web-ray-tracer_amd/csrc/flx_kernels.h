@@ -128,6 +128,19 @@ size_t refit_workspace_words(uint32_t n_entries);
 void launch_refit(float4 *geometry, uint32_t n_entries, uint32_t *work, hipStream_t stream);
 /* the threaded or the forward-ordered copy (`entries` of them) follows the geometry rows: the six floats of a box, a triangle's vertex and two edges; links and meta words stay */
 void launch_rederive(const float4 *geometry, uint32_t n_entries, float4 *copy, uint32_t entries, hipStream_t stream);
+/* flx_scene_upload_device (flx_derive.hip): flx_scene_upload's decisions and both derived copies from an entry array in device memory.  work: derive_workspace_words(n_entries)
+ * words, the record in its first DERIVE_RECORD_WORDS.  launch_derive_check fills the record: [0] 0 where no entry offends, else ~(entry * 4 + rule) of the first entry
+ * the host's loop refuses and its first rule there (0 transform number out of range, 1 skip count leaves the array, 2 type not 0, 1 or 2); [1] max_transform;
+ * [2] a triangle has a NaN vertex; [3] a box coordinate is not finite or beyond 2^59; [4] boxes; [5] live (non-terminator) entries; [6] entry 0's meta word.
+ * It touches the workspace alone.  launch_derive_copies, for an array that passed: walk <- build_threaded's copy (live + 1 entries, min(4096, live) + 1 of them hot),
+ * fwd <- build_lockstep's (live + 1), bit for bit for a properly nested skip list; no kernel waits for another workgroup, every scan is a launch per level and
+ * recurses on its block totals: any entry count flx_scene_upload takes. */
+constexpr uint32_t DERIVE_RECORD_WORDS = 8;
+size_t derive_workspace_words(uint32_t n_entries);
+hipError_t launch_derive_check(const float4 *geometry, uint32_t n_entries, uint32_t *work, hipStream_t stream);
+void launch_derive_copies(const float4 *geometry, uint32_t n_entries, uint32_t live, uint32_t *work, float4 *walk, float4 *fwd, hipStream_t stream);
+/* out <- words 6, 9 and 10 of every entry (3 words each): what flx_scene_update holds host rows against */
+void launch_entry_meta(const float4 *geometry, uint32_t n_entries, uint32_t *out, hipStream_t stream);
 void launch_debug_math(int fn, const float *a, const float *b, float *out, uint32_t n, hipStream_t stream);
 void launch_debug_intersect(int fn, const float *in, float *out, uint32_t n, hipStream_t stream);
 bool launch_debug_walk(int variant, const DeviceScene &sc, const float *in, float *out, uint32_t n, hipStream_t stream);      /* false: the scene does not allow that variant */

@@ -31,7 +31,7 @@ EXPORTS = [
     "flx_share_create", "flx_share_join", "flx_share_leave", "flx_frame_begin_shared", "flx_frame_end_shared",
     "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_sample_parallel", "flx_debug_last_trace_kernel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
     "flx_raster_render", "flx_debug_walk_staged", "flx_debug_last_walk_lds", "flx_debug_walk_fast_boxes",
-    "flx_scene_update", "flx_group_scene_update", "flx_debug_scene_read", "flx_scene_update_device",
+    "flx_scene_update", "flx_group_scene_update", "flx_debug_scene_read", "flx_scene_update_device", "flx_scene_upload_device",
 ]
 
 
@@ -62,6 +62,7 @@ def _load():
         "flx_scene_update": (C.c_int, [vp, u32, u32, fp, fp]),
         "flx_group_scene_update": (C.c_int, [vp, u32, u32, fp, fp]),
         "flx_scene_update_device": (C.c_int, [vp, u32, u32, vp, vp, vp]),
+        "flx_scene_upload_device": (C.c_int, [vp, vp, vp, u32, vp, u32, vp]),
         "flx_debug_scene_read": (C.c_int, [vp, C.c_int, fp, u32]),
         "flx_transforms_upload": (C.c_int, [vp, fp, fp, u32]),
         "flx_lights_upload": (C.c_int, [vp, fp, u32]),
@@ -217,6 +218,22 @@ def _device_rows(x, width, device, what):
     return x.data_ptr(), x.shape[0]
 
 
+def _device_array(x, dtype_name, width, device, what):
+    """an array of upload_scene_device -> (device address, rows): a contiguous torch tensor [n, width] (or [n] where width is None) on cuda:`device`, or (address, n)"""
+    if isinstance(x, tuple):
+        address, n = x
+        return int(address), int(n)
+    import torch                               # (here and not at the top: capi imports without torch)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("upload_scene_device: %s is a torch tensor or (address, rows)" % what)
+    shape_ok = x.dim() == 1 if width is None else (x.dim() == 2 and x.shape[1] == width)
+    if x.dtype != getattr(torch, dtype_name) or not shape_ok or not x.is_contiguous():
+        raise ValueError("upload_scene_device: %s is a contiguous %s tensor %s" % (what, dtype_name, "[n]" if width is None else "[n, %d]" % width))
+    if x.device.type != "cuda" or x.device.index != device:
+        raise ValueError("upload_scene_device: %s is on %s, the context on cuda:%d" % (what, x.device, device))
+    return x.data_ptr(), x.shape[0]
+
+
 class Context:
     """One GPU context (flx_context).  Mirrors the life cycle of the reference renderer object:
     construct -> updateScene()/updatePrimaryLightSources() -> render frames -> halt()."""
@@ -261,6 +278,23 @@ class Context:
 
     def upload_view(self, view):
         self._check(LIB.flx_scene_upload_view(self._h, C.byref(view)), "flx_scene_upload_view")
+
+    def upload_scene_device(self, geometry, attributes, ids=None, stream=None):
+        """flx_scene_upload_device: flx_scene_upload for arrays that are in device memory.  geometry: a torch tensor [n, 12] (float32, contiguous, on the context's
+        device) or (address, n); attributes: [n, 28] likewise; ids: None (no ids), an int32 tensor [k] or (address, k).  stream: as for update_scene_rows_device.
+        Transforms, lights and atlases go their usual ways (update_transforms, ...)."""
+        g, n = _device_array(geometry, "float32", 12, self._device, "geometry")
+        a, rows = _device_array(attributes, "float32", 28, self._device, "attributes")
+        if rows != n:
+            raise ValueError("upload_scene_device: as many attribute rows as geometry rows")
+        i, k = (None, 0) if ids is None else _device_array(ids, "int32", None, self._device, "ids")
+        if stream is not None and not isinstance(stream, int):
+            handle = stream.cuda_stream
+            if handle == 0:
+                stream.synchronize()
+            stream = handle
+        self._check(LIB.flx_scene_upload_device(self._h, C.c_void_p(g), C.c_void_p(a), n, C.c_void_p(i) if k else None, k,
+                                                C.c_void_p(stream) if stream else None), "flx_scene_upload_device")
 
     def update_scene_rows(self, first, geometry, attributes=None):
         """flx_scene_update: rows [first, first + n) of the uploaded scene replaced (12 floats of geometry each, 28 of attributes or None:
