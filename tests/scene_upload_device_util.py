@@ -17,7 +17,7 @@ FAST_BOX_BOUND = np.float32(5.764607523034235e17)                   # 2^59
 
 
 def offences(geometry):
-    """THE TABLE k_derive_check implements: {entry * 4 + rule} of every (entry, rule) that offends, by the host loop's tests (flx_api.hip: flx_scene_upload): a
+    """THE TABLE k_derive_check implements: {entry * 4 + rule} of every (entry, rule) that offends, by the host loop's tests (flx_scene.hip: flx_scene_upload): a
     live entry's transform number must lie in [0, 2^20); a box's skip count must be >= 0 and keep entry + skip inside the array; an entry that is no box must
     be a terminator or a triangle.  NaN fails every comparison, as in C."""
     g = np.ascontiguousarray(geometry, np.float32).reshape(-1, 12)

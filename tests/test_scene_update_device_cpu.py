@@ -1,6 +1,6 @@
 """flx_scene_update_device without a GPU: where it is declared and bound, that capi still imports without torch, and the table of refusals its kernel implements
 (scene_update_device_util.offences: a key row * 4 + rule per offence, the least key decides) against the host call it stands in for.  flx_scene_update needs a
-context, hence a GPU, so here its messages and their order are read from its source text (csrc/flx_api.hip); tests/test_scene_update_device_gpu.py runs the
+context, hence a GPU, so here its messages and their order are read from its source text (csrc/flx_scene.hip); tests/test_scene_update_device_gpu.py runs the
 two calls beside each other."""
 import os
 import re
@@ -26,11 +26,21 @@ def declared(header):
     return set(re.findall(r"\b(flx_[a-z0-9_]+)\s*\(", text))
 
 
+SCENE_HIP = ("web-ray-tracer_amd", "csrc", "flx_scene.hip")
+
+
 def body_of(name):
-    """the text of the C function `name` in flx_api.hip, up to the next function at file level"""
-    text = read("web-ray-tracer_amd", "csrc", "flx_api.hip")
+    """the text of the C function `name` in flx_scene.hip, up to the next function of the C ABI"""
+    text = read(*SCENE_HIP)
     start = text.index('extern "C" flx_status %s(' % name)
     return text[start:text.index('\nextern "C"', start + 1)]
+
+
+def static_body_of(name):
+    """the text of the file's own function `name`, up to its closing brace"""
+    text = read(*SCENE_HIP)
+    start = text.index("static flx_status %s(" % name)
+    return text[start:text.index("\n}\n", start)]
 
 
 def test_the_function_is_declared_beside_flx_scene_update_and_not_in_the_boundary_header():
@@ -54,16 +64,27 @@ def test_capi_imports_without_torch():
 
 
 def test_the_messages_are_the_host_calls_in_the_host_calls_order():
+    text = read(*SCENE_HIP)
+    table = text[text.index("SCENE_UPDATE_REFUSAL[4] = {"):]
+    assert tuple(re.findall(r'"([^"]*)"', table[:table.index("};")])) == MESSAGES             # the one table, in the order of the kernel's rule numbers
+    rules = text[text.index("enum UpdateRule {"):]
+    assert re.findall(r"\w+", rules[rules.index("{"):rules.index("}")]) == ["UPDATE_RULE_KIND", "UPDATE_RULE_TRANSFORM", "UPDATE_RULE_SKIP", "UPDATE_RULE_FINITE"]
     host = body_of("flx_scene_update")
     loop = host[host.index("for (uint32_t r = 0; r < n_entries; r++)"):host.index("FLX_HIP(ctx, hipSetDevice")]
-    assert tuple(re.findall(r'fail\(ctx, FLX_ERR_INVALID, "([^"]*)"\)', loop)) == MESSAGES      # kind, transform number, skip count, vertex: as the loop meets them
+    assert loop.count("fail(") == 4
+    assert re.findall(r"fail\(ctx, FLX_ERR_INVALID, SCENE_UPDATE_REFUSAL\[UPDATE_RULE_(\w+)\]\)", loop) == ["KIND", "TRANSFORM", "SKIP", "FINITE"]      # as the loop meets them
     device = body_of("flx_scene_update_device")
-    table = device[device.index("refusal[4]"):]
-    assert tuple(re.findall(r'"(flx_scene_update: [^"]*)"', table[:table.index("};")])) == MESSAGES
-    assert "refusal[verdict & 3u]" in device
-    # what is refused before a row is looked at: the same statuses and texts, in the same order
-    checks = lambda body, end: re.findall(r'fail\(ctx, (FLX_ERR_[A-Z_]+), "([^"]*)"\)', body[:body.index(end)])
-    assert checks(device, "hipSetDevice") == checks(host, "bool bounded") and len(checks(host, "bool bounded")) == 4
+    assert "fail(ctx, FLX_ERR_INVALID, SCENE_UPDATE_REFUSAL[verdict & 3u])" in device
+    for message in MESSAGES:
+        assert text.count(message) == 1
+    # what is refused before a row is looked at: one function holds the statuses and texts, in this order, and both calls begin with it
+    checks = re.findall(r'fail\(ctx, (FLX_ERR_[A-Z_]+), "([^"]*)"\)', static_body_of("update_refused"))
+    assert checks == [("FLX_ERR_NO_SCENE", "flx_scene_update before flx_scene_upload"), ("FLX_ERR_INVALID", "flx_scene_update: the rows leave the entry array"),
+                      ("FLX_ERR_INVALID", "flx_scene_update: geometry is NULL"),
+                      ("FLX_ERR_INVALID", "flx_scene_update: the uploaded scene has a NaN vertex (its boxes cannot be refitted as the flatten makes them)")]
+    for body in (host, device):
+        assert 0 < body.index("update_refused(ctx, first_entry, n_entries, ") < body.index("hipSetDevice")
+        assert 'fail(ctx, FLX_ERR_INVALID, "flx_scene_update:' not in body and "FLX_ERR_NO_SCENE" not in body
 
 
 def test_the_table_refuses_the_cases_and_takes_the_lowest_key():

@@ -1,6 +1,6 @@
 """flx_scene_upload_device without a GPU: where it is declared and bound, that capi still imports without torch, and the table of refusals its kernel implements
 (scene_upload_device_util.offences: a key entry * 4 + rule per offence, the least key decides) against hand-written cases and against the text of the host loop it
-stands in for (csrc/flx_api.hip).  tests/test_scene_upload_device_gpu.py runs the two calls beside each other."""
+stands in for (csrc/flx_scene.hip).  tests/test_scene_upload_device_gpu.py runs the two calls beside each other."""
 import os
 import re
 import subprocess
@@ -26,10 +26,19 @@ def declared(header):
     return set(re.findall(r"\b(flx_[a-z0-9_]+)\s*\(", text))
 
 
+SCENE_HIP = ("web-ray-tracer_amd", "csrc", "flx_scene.hip")
+
+
 def body_of(name):
-    text = read("web-ray-tracer_amd", "csrc", "flx_api.hip")
+    text = read(*SCENE_HIP)
     start = text.index('extern "C" flx_status %s(' % name)
     return text[start:text.index('\nextern "C"', start + 1)]
+
+
+def static_body_of(name):
+    text = read(*SCENE_HIP)
+    start = text.index("static flx_status %s(" % name)
+    return text[start:text.index("\n}\n", start)]
 
 
 def test_the_library_exports_it_and_capi_binds_it():
@@ -54,15 +63,26 @@ def test_capi_imports_without_torch():
 
 
 def test_the_messages_are_the_host_calls_in_the_host_calls_order():
+    text = read(*SCENE_HIP)
+    table = text[text.index("SCENE_UPLOAD_REFUSAL[3] = {"):]
+    assert tuple(re.findall(r'"([^"]*)"', table[:table.index("};")])) == MESSAGES             # the one table, in the order of the kernel's rule numbers
+    rules = text[text.index("enum UploadRule {"):]
+    assert re.findall(r"\w+", rules[rules.index("{"):rules.index("}")]) == ["UPLOAD_RULE_TRANSFORM", "UPLOAD_RULE_SKIP", "UPLOAD_RULE_TYPE"]
     host = body_of("flx_scene_upload")
     loop = host[host.index("for (uint32_t i = 0; i < n_entries_padded; i++)"):host.index("flx_status s;")]
-    assert tuple(re.findall(r'fail\(ctx, FLX_ERR_INVALID, "([^"]*)"\)', loop)) == MESSAGES
+    assert loop.count("fail(") == 3
+    assert re.findall(r"fail\(ctx, FLX_ERR_INVALID, SCENE_UPLOAD_REFUSAL\[UPLOAD_RULE_(\w+)\]\)", loop) == ["TRANSFORM", "SKIP", "TYPE"]      # as the loop meets them
     device = body_of("flx_scene_upload_device")
-    table = device[device.index("refusal[3]"):]
-    assert tuple(re.findall(r'"(flx_scene_upload: [^"]*)"', table[:table.index("};")])) == MESSAGES
-    # what is refused before an entry is looked at: the same statuses and texts, in the same order
-    checks = lambda body: re.findall(r'fail\(ctx, (FLX_ERR_[A-Z_]+), "([^"]*)"\)', body[:body.index("hipSetDevice")])
-    assert checks(device) == checks(host) and len(checks(host)) == 3
+    assert "fail(ctx, FLX_ERR_INVALID, SCENE_UPLOAD_REFUSAL[rule < 3u ? rule : 2u])" in device and "rule = ~rec[0] & 3u" in device
+    for message in MESSAGES:
+        assert text.count(message) == 1
+    # what is refused before an entry is looked at: one function holds the statuses and texts, in this order, and both calls begin with it
+    checks = re.findall(r'fail\(ctx, (FLX_ERR_[A-Z_]+), "([^"]*)"\)', static_body_of("upload_refused"))
+    assert checks == [("FLX_ERR_INVALID", "flx_scene_upload: empty scene"), ("FLX_ERR_INVALID", "flx_scene_upload: ids is NULL"),
+                      ("FLX_ERR_INVALID", "flx_scene_upload: more than 2^28 - 1 entries")]
+    for body in (host, device):
+        before = body[:body.index("hipSetDevice")]
+        assert "upload_refused(ctx, " in before and 'fail(ctx, FLX_ERR_INVALID, "' not in before
 
 
 def base():

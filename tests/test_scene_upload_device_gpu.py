@@ -18,6 +18,7 @@ import synth_scene
 from flexlight_hip import capi
 from flexlight_hip.scene_io import Scene
 from parity_util import bit_mismatches
+from scene_update_device_util import KIND, MESSAGES as UPDATE_MESSAGES
 from scene_update_util import bits, moved, rows_for_update
 from scene_upload_device_util import (FAST_BOX_BOUND, MESSAGES, POINTER_MESSAGE, POSITIONS, REFUSAL_ENTRIES, SKIP, TRANSFORM, TYPE, decoy, fractional_words,
                                       last_box_reaches_the_end, offend, one_triangle, overlapping_boxes, refusal, rows, scene_of, terminator_in_the_middle)
@@ -330,6 +331,31 @@ def test_row_updates_after_a_device_upload_equal_a_fresh_host_upload(device_rows
         with pytest.raises(capi.FlexLightHipError, match="not finite"):
             ctx.update_scene_rows_device(live, on_device(bad))
         assert_states_equal(state_of(ctx, new), state_of(fresh, new))
+
+
+def test_a_host_upload_over_a_device_upload_then_takes_rows_of_both_kinds():
+    """One context: a device upload (h_entry_meta left on the device), a HOST upload of another scene over it (h_entry_meta back on the host), then rows from host
+    memory into one span and rows from device memory into the rest, through the one stage and the events made once; 257 and 300 entries: either side of the
+    256-entry blocks of the refit and derive kernels.  A refused row in between says what the table says and changes nothing."""
+    base, new = sized(300, 3), moved(sized(300, 3), 33)
+    n, mid = entries(new), 137
+    g, a = rows_for_update(new, 0, n)
+    with capi.Context(0) as ctx, capi.Context(0) as fresh:
+        upload_device(ctx, sized(257, 3))
+        ctx.update_scene(base)
+        ctx.update_scene_rows(0, g[:mid], a[:mid])
+        before = state_of(ctx, new)
+        live = mid + int(np.flatnonzero(g[mid:, 10] == 2)[3])
+        bad = g[live:live + 1].copy()
+        bad[0, 10] = 1.0
+        assert capi.LIB.flx_scene_update(ctx._h, live, 1, capi._fp(bad), None) == INVALID
+        assert capi.LIB.flx_last_error(ctx._h).decode() == UPDATE_MESSAGES[KIND]
+        assert_states_equal(state_of(ctx, new), before)
+        ctx.update_scene_rows_device(mid, on_device(g[mid:]), on_device(a[mid:]))
+        fresh.update_scene(new)
+        assert_states_equal(state_of(ctx, new), state_of(fresh, new))
+        p = new.frame_params(width=W, height=H)
+        assert bit_mismatches(ctx.render(p)[0], fresh.render(p)[0]) == 0
 
 
 # ---- ordering -------------------------------------------------------------------------------------------------------------------------------------------

@@ -88,7 +88,7 @@ def cap(hip, family, n_transforms):
 # ---- rays and the oracle's walks ---------------------------------------------------------------------------------------------------------------------
 
 def threaded_order(g):
-    """original entry index of every threaded index, as build_threaded (csrc/flx_api.hip) lays them out: the shared terminator, the shallowest 4096 entries
+    """original entry index of every threaded index, as build_threaded (csrc/flx_scene.hip) lays them out: the shared terminator, the shallowest 4096 entries
     (stable by depth), the rest in original order"""
     depth, stack = np.zeros(g.shape[0], np.int64), []
     for i in range(g.shape[0]):

@@ -1,5 +1,5 @@
-/* flx_context.h — the context behind the C ABI and the internal helpers flx_api.hip shares with flx_group.hip (the RCCL
- * gather across contexts).  Private to the library. */
+/* flx_context.h — the context behind the C ABI and the internal helpers flx_api.hip shares with flx_scene.hip and flx_group.hip (the
+ * RCCL gather across contexts).  Private to the library. */
 #ifndef FLX_CONTEXT_H
 #define FLX_CONTEXT_H
 
@@ -110,7 +110,8 @@ struct flx_context {
    * into d_update_rows, from where a kernel scatters them (update_done: that kernel, and with it whatever last read the stage); d_refit is the refit's workspace.
    * flx_scene_update_device's rows are in device memory already: a kernel on update_stream checks them against d_geometry and copies them into d_update_rows and
    * d_update_attributes; its verdict (d_update_verdict, two words) comes back through h_update_verdict, update_checked follows that copy, update_produced is
-   * recorded on the caller's stream.  geometry_uploaded follows flx_scene_upload's copy of the geometry array, which the check reads. */
+   * recorded on the caller's stream.  geometry_uploaded follows flx_scene_upload's copy of the geometry array, which the check reads.  The stream and the four
+   * events are made in one place, at the first call that needs one (flx_scene.hip: ensure_side_stream). */
   std::vector<uint32_t> h_entry_meta;
   bool scene_has_nan = false;
   PinnedBuffer<float> h_update;
@@ -284,6 +285,7 @@ int flx_server_takes_moving_scene(const flx_context *ctx);                      
 int flx_server_continues(flx_context *ctx, const flx_frame_params *params);      /* the running launch of the frame server takes this frame as it is */
 flx_status flx_server_prepare(flx_context *ctx, const flx_frame_params *params); /* the launch ends; everything a launch for frames like this needs is allocated */
 flx_status flx_server_stop(flx_context *ctx);      /* the frame server's launch ends (after the frames posted to it), the frames in flight are resolved into their output slots */
+flx_status flx_dyn_flush(flx_context *ctx);        /* flx_scene.hip: the device's transforms and lights follow the host's copies, where a launch went on over their uploads */
 flx_status flx_check_device_error(flx_context *ctx);      /* FLX_ERR_DEVICE (and the word cleared) if a frame kernel's watchdog has tripped since the last check */
 /* a temporal filter frame's strips (params->tile_*; use_filter = 1, is_temporal = 1): traced, the temporal pass over this context's history,
  * the five render targets the chain reads stored to d_planes = uint32[5][rows][width] (flx_render_planes_device's layout); enqueued on its stream */

@@ -1,5 +1,5 @@
 /*
- * flx_derive.hip — flx_scene_upload_device's kernels: what flx_scene_upload decides and derives on the host (flx_api.hip: its loop over the entries,
+ * flx_derive.hip — flx_scene_upload_device's kernels: what flx_scene_upload decides and derives on the host (flx_scene.hip: its loop over the entries,
  * build_threaded, build_lockstep), decided and derived from an entry array that is in device memory.
  *
  *   k_derive_check      a lane per entry: the host loop's refusals as the least key entry * 4 + rule, max_transform, has_nan, bounded, the counts of boxes and
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(DB) void k_derive_check(const float4 *__restrict__ 
     }
     if (box) {
 #pragma unroll
-      for (int k = 0; k < 6; k++) unbounded = unbounded || !(fabsf(w[k]) <= 5.764607523034235e17f);
+      for (int k = 0; k < 6; k++) unbounded = unbounded || !(fabsf(w[k]) <= FLX_FAST_BOX_BOUND);
     }
     const uint32_t m = !live ? 0u : (box ? 1u : 2u) | transform << 2;
     meta[i] = m;

@@ -8,6 +8,7 @@
 #define FLX_PATHS_ANGLE_TABLE 1        /* k_paths reads the shading's per-triangle table too (DeviceScene::angle_tan): at the seven waves per SIMD it ran at first the table's dependent load cost it 1 %,
                                         * at four it gains 5 % — theater 9.29 -> 8.80 ms (profiles/r04_paths_occupancy.txt) */
 #endif
+#define FLX_FAST_BOX_BOUND 5.764607523034235e17f      /* 2^59: rayCuboidR's precondition, flx_device.h */
 namespace flx {
 
 struct GBufferPtrs {

@@ -640,7 +640,7 @@ __global__ __launch_bounds__(256) void k_angle_tan(DeviceScene sc, float4 *__res
   if (i >= sc.n_entries) return;
   float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   const float kind = sc.geometry[3 * (size_t)i + 2].z;
-  if (kind != 0.0f && kind != 1.0f) {                         /* a triangle entry (1: a box, 0: the end of the list / padding) — flx_api.hip: build_threaded reads the kind the same way */
+  if (kind != 0.0f && kind != 1.0f) {                         /* a triangle entry (1: a box, 0: the end of the list / padding) — flx_scene.hip: build_threaded reads the kind the same way */
     const f3 t = triangleAngleTanOf(sc, (int)i);
     r = make_float4(t.x, t.y, t.z, 0.0f);
   }

@@ -262,7 +262,7 @@ __global__ __launch_bounds__(RB) void k_rows_check_stage(const float4 *__restric
         if (k < words) {
           const float a = fabsf(w[k]);
           if (!(a < __builtin_inff())) rule = min(rule, 3u);      /* inf and NaN */
-          if (!(a <= 5.764607523034235e17f)) beyond = true;
+          if (!(a <= FLX_FAST_BOX_BOUND)) beyond = true;
         }
       }
     }
