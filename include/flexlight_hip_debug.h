@@ -166,6 +166,29 @@ flx_status flx_scene_upload_device(flx_context *ctx,
                                    uint32_t n_entries_padded,
                                    const void *d_ids /* n_ids int32, or NULL when n_ids == 0 */, uint32_t n_ids,
                                    void *producer_stream /* hipStream_t that wrote the arrays, or NULL: complete */);
+/* A mesh's block of the entry array BUILT ON THE DEVICE from triangles that are in device memory (a simulation's output, a torch op's, a mesh whose topology
+ * changes): what flx_mesh_import_obj + flx_mesh_flatten make on the host of the same triangles in the same order — the reference's generateBVH: leaves of at most
+ * 4, a split at the bounding's centre on the axis with the fewest straddlers, three stable buckets, depth <= log2(n) + 8 — the same rows in the same order, bit
+ * for bit (where no box holds both a -0 and a +0 on one axis: the refit orders them, Math.min does not), and the same ids.  Primitives are single triangles; the
+ * reference's two-triangle planes are not built here.
+ * flx_tree_build_device builds the tree of n_triangles geometry rows of kind 2 (9 vertex words, word 9 the transform number, word 10 = 2) level by level
+ * (csrc/flx_build.hip) and keeps it in the context: the permutation, the nodes, the entry indices.  It runs on a stream of the context's own, touches nothing of
+ * the uploaded scene, waits for no frame in flight, and returns when the host knows *n_entries = boxes + triangles: one wait per level of the tree.  The caller's
+ * rows are free then.  producer_stream: as for flx_scene_update_device.  FLX_ERR_INVALID, each with a message of its own, and no tree kept: n_triangles 0 or above
+ * 2^24; rows not in memory of ctx's device, not 16-byte aligned or in too short an allocation; then the first offending row and within it the first of: word 10
+ * is not 2, word 9 differs from row 0's or is no whole number in [0, 2^20), a vertex is not finite; a tree of more than 2^28 - 1 entries.
+ * flx_tree_emit_device writes the block of the last successful build: geometry and attribute rows of the boxes (attribute rows of zeros; the six floats by the
+ * refit flx_scene_update runs) and of the triangles (copied unchanged; d_attributes NULL: zeros), ids[k] = the entry, counted from the block's first, of the k-th
+ * triangle in emission order.  d_triangles: the rows the tree was built from (their count is what can be checked); every array in memory of ctx's device,
+ * 16-byte aligned, long enough for the build's counts, and complete.  It returns when the arrays are complete and may be called again.  FLX_ERR_INVALID without a
+ * successful build.  The block is ready to be spliced into an entry array (ids offset by its first entry) and handed to flx_scene_upload_device. */
+flx_status flx_tree_build_device(flx_context *ctx,
+                                 const void *d_triangles /* n_triangles * 12 floats, on ctx's device, in the order the host builder would be given them */,
+                                 uint32_t n_triangles, void *producer_stream /* hipStream_t that wrote the rows, or NULL: complete */,
+                                 uint32_t *n_entries /* out: boxes + triangles */);
+flx_status flx_tree_emit_device(flx_context *ctx, const void *d_triangles,
+                                const void *d_attributes /* n_triangles * 28 floats, or NULL: attribute rows of zeros */,
+                                void *d_geometry /* n_entries * 12 floats */, void *d_attributes_out /* n_entries * 28 floats */, void *d_ids /* n_triangles int32 */);
 /* The uploaded scene as the device holds it, after everything enqueued so far: which 0 the geometry rows (12 floats per entry), 1 the attribute rows (28),
  * 2 the threaded hot-first copy (12 per entry of walk_entries), 3 the forward-ordered copy (12 per entry of fwd_entries: flx_debug_last_walk_lds' out[5], out[6]).
  * The first n_floats floats of the array; FLX_ERR_INVALID beyond its end.  Tests compare flx_scene_update's arrays with a fresh upload's. */

@@ -128,6 +128,16 @@ struct flx_context {
   DeviceBuffer<uint32_t> d_derive;
   PinnedBuffer<uint32_t> h_derive_record;
   bool entry_meta_stale = false;
+  /* flx_tree_build_device (flx_build.hip): the tree of the last successful build — the permutation, the nodes, the entry indices — which flx_tree_emit_device writes
+   * out; the arrays per triangle, the arrays per node (node_capacity of them: grown by doubling), the refit's workspace for the emitted block.  All of it is used
+   * on update_stream alone.  h_tree_record: the refusals' verdict and, level by level, the number of children. */
+  struct {
+    DeviceBuffer<float2> tbox; DeviceBuffer<uint32_t> perm[2], owner[2], open, bucket, entry, keys, verdict, refit; DeviceBuffer<uint2> x, y, totals;
+    DeviceBuffer<uint4> node, cnt; DeviceBuffer<double> centre;
+    size_t node_capacity = 0;
+    uint32_t n_triangles = 0, n_nodes = 0; int current = 0; float transform = 0.0f; bool valid = false;
+  } tree;
+  PinnedBuffer<uint32_t> h_tree_record;
   /* DeviceScene::angle_tan: per triangle, from the geometry / attribute arrays and this context's transforms; made again (on this context's stream, in front of
    * the frame that needs it) when any of them changed: angle_key = the versions it was made from */
   DeviceBuffer<float4> d_angle_tan;

@@ -54,9 +54,7 @@ Work layout(uint32_t n, uint32_t *w) {
   k.below = (uint2 *)take(HOT_MAX * 2);
   k.meta = take(n); k.index = take(n);
   k.x = (uint2 *)take((size_t)n * 2); k.y = (uint2 *)take((size_t)n * 2);
-  size_t totals = 0;
-  for (size_t m = n; m > 1; ) { m = (m + DB - 1) / DB; totals += (m + 1) & ~(size_t)1; }
-  k.totals = (uint2 *)take(totals * 2 + 4);
+  k.totals = (uint2 *)take(scan_totals_items(n) * 2);
   k.words = at;
   return k;
 }
@@ -300,6 +298,14 @@ void exclusiveScan(uint2 *x, uint32_t m, uint2 *totals, hipStream_t stream) {
 }
 
 }  // namespace
+
+/* every level's block totals, each level's at an even item, and two items beyond (a single block writes its total too) */
+size_t scan_totals_items(uint32_t m) {
+  size_t totals = 0;
+  for (size_t k = m; k > 1; ) { k = (k + DB - 1) / DB; totals += (k + 1) & ~(size_t)1; }
+  return totals + 2;
+}
+void launch_exclusive_scan(uint2 *x, uint32_t m, uint2 *totals, hipStream_t stream) { exclusiveScan(x, m, totals, stream); }
 
 size_t derive_workspace_words(uint32_t n_entries) { return layout(n_entries, nullptr).words; }
 

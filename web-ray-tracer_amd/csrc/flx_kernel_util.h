@@ -65,6 +65,16 @@ __device__ __forceinline__ float4 resolve_pixel(const DeviceFrame &fr, const flo
   return color;
 }
 
+/* ORDERED KEYS: a float's bits with the sign folded so that unsigned comparison is the total order -inf < .. < -0 < +0 < .. < +inf, and the key maps back to the very
+ * float: min / max over floats as integer operations (integer atomics too).  The box refit (flx_refit.hip) and the tree build (flx_build.hip) share them: a built
+ * tree's boxes are the refit's.  KEY_NONE_*: the identities of min / max over keys, "no vertex". */
+constexpr uint32_t KEY_NONE_LO = 0xffffffffu, KEY_NONE_HI = 0u;
+__device__ __forceinline__ uint32_t keyOf(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float floatOf(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
 /* rank of this lane among the set bits of `mask` below it */
 __device__ __forceinline__ uint32_t lane_rank(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));

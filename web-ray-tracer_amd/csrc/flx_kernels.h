@@ -142,6 +142,28 @@ hipError_t launch_derive_check(const float4 *geometry, uint32_t n_entries, uint3
 void launch_derive_copies(const float4 *geometry, uint32_t n_entries, uint32_t live, uint32_t *work, float4 *walk, float4 *fwd, hipStream_t stream);
 /* out <- words 6, 9 and 10 of every entry (3 words each): what flx_scene_update holds host rows against */
 void launch_entry_meta(const float4 *geometry, uint32_t n_entries, uint32_t *out, hipStream_t stream);
+/* x[0 .. m) <- its exclusive prefix, both words (wrapping sums), as flx_scene_upload_device's scans: a launch per level of block totals.  totals: scan_totals_items(m) items */
+size_t scan_totals_items(uint32_t m);
+void launch_exclusive_scan(uint2 *x, uint32_t m, uint2 *totals, hipStream_t stream);
+/* flx_tree_build_device / flx_tree_emit_device (flx_build.hip): flx_mesh.hip's tree over n triangle rows, level by level.  Per triangle or position: tbox (its bounds:
+ * (min, max) per axis), perm / owner and their next level's (the triangle at a position; the node it stands in while that node may split), open (nodes that start
+ * there: n + 1), bucket, entry, x (n + 1).  Per node, `capacity` of them: node (first, count, ancestors starting at first, axis or 3: a leaf; after
+ * launch_tree_index: its entry, the entries beneath it), keys (6), centre (3), cnt, y (capacity + 1).  totals: room for the scans of x and of y. */
+struct TreeArrays {
+  float2 *tbox; uint32_t *perm, *permNext, *owner, *ownerNext, *open, *bucket, *entry; uint2 *x, *y, *totals;
+  uint4 *node, *cnt; uint32_t *keys; double *centre;
+};
+/* verdict[0] (~0 before) <- the least row * 4 + rule of a refused row (0 word 10 is not 2, 1 word 9 differs from row 0's or is no whole number in [0, 2^20), 2 a vertex is not
+ * finite); the bounds, the identity permutation, the root (open zeroed before) */
+void launch_tree_check(const float4 *rows, uint32_t n, uint32_t *verdict, const TreeArrays &t, hipStream_t stream);
+/* the level's nodes [base, base + m) decide and count their children: y[m].x <- how many the level has; then, with room for them: their ranges, the next level's perm / owner */
+void launch_tree_level(const TreeArrays &t, uint32_t n, uint32_t base, uint32_t m, uint32_t depth, double maxDepth, hipStream_t stream);
+void launch_tree_children(const TreeArrays &t, uint32_t n, uint32_t base, uint32_t m, hipStream_t stream);
+/* entry[p] and (entry, entries beneath) of every node, from the scan of open */
+void launch_tree_index(const TreeArrays &t, uint32_t n, uint32_t nodes, hipStream_t stream);
+/* the block's n + nodes rows of both arrays (a box row's words 0..5: launch_refit's) and the ids */
+void launch_tree_emit(const float4 *rows, const float4 *attributes, const TreeArrays &t, uint32_t n, uint32_t nodes, float transform, float4 *geometry,
+                      float4 *attributesOut, int32_t *ids, hipStream_t stream);
 void launch_debug_math(int fn, const float *a, const float *b, float *out, uint32_t n, hipStream_t stream);
 void launch_debug_intersect(int fn, const float *in, float *out, uint32_t n, hipStream_t stream);
 bool launch_debug_walk(int variant, const DeviceScene &sc, const float *in, float *out, uint32_t n, hipStream_t stream);      /* false: the scene does not allow that variant */

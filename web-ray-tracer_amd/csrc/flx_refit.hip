@@ -18,22 +18,15 @@
 #include <hip/hip_runtime.h>
 
 #include "flx_kernels.h"
+#include "flx_kernel_util.h"
 
 namespace flx {
 
 namespace {
 
 constexpr uint32_t RB = 256;                       /* entries per block, blocks per superblock, threads per workgroup */
-constexpr uint32_t KEY_NONE_LO = 0xffffffffu;      /* identities of min / max over keys: "no vertex" */
-constexpr uint32_t KEY_NONE_HI = 0u;
+struct Bounds { uint32_t k[6]; };                  /* keys (flx_kernel_util.h): min x y z, max x y z */
 
-struct Bounds { uint32_t k[6]; };                  /* keys: min x y z, max x y z */
-
-__device__ __forceinline__ uint32_t keyOf(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float floatOf(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 __device__ __forceinline__ Bounds none() { return Bounds{ { KEY_NONE_LO, KEY_NONE_LO, KEY_NONE_LO, KEY_NONE_HI, KEY_NONE_HI, KEY_NONE_HI } }; }
 __device__ __forceinline__ void join(Bounds &a, const Bounds &b) {
 #pragma unroll

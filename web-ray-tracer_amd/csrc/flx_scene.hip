@@ -493,6 +493,123 @@ extern "C" flx_status flx_scene_update_device(flx_context *ctx, uint32_t first_e
   return commit_rows(ctx, first_entry, n_entries, ctx->h_update_verdict[1] != 0u, d_attributes ? ROWS_DEVICE : ROWS_NONE, ctx->update_checked);
 }
 
+/* ---- a mesh's box tree, built on the device (flx_build.hip) ----------------------------------------------------------------------------------------------
+ * Why a row is refused, in the order they are met within a row; the values are k_tree_check's rule numbers. */
+constexpr uint32_t TREE_MAX_TRIANGLES = 1u << 24;
+static const char *const TREE_BUILD_REFUSAL[3] = { "flx_tree_build_device: a row is not a triangle (word 10 is not 2)",
+                                                   "flx_tree_build_device: a row's transform number (word 9) differs from row 0's or is no whole number in [0, 2^20)",
+                                                   "flx_tree_build_device: a vertex is not finite" };
+
+static TreeArrays tree_arrays(flx_context *ctx) {
+  auto &t = ctx->tree;
+  return TreeArrays{ t.tbox, t.perm[t.current], t.perm[t.current ^ 1], t.owner[t.current], t.owner[t.current ^ 1], t.open, t.bucket, t.entry, t.x, t.y, t.totals,
+                     t.node, t.cnt, t.keys, t.centre };
+}
+
+/* the arrays per node, for `capacity` nodes; what they hold of the first `kept` nodes stays (a copy on update_stream, waited for before the old arrays go) */
+template <typename T>
+static flx_status tree_grow(flx_context *ctx, DeviceBuffer<T> &buffer, size_t kept, size_t items) {
+  DeviceBuffer<T> bigger;
+  flx_status s = bigger.ensure(ctx, items);
+  if (s) return s;
+  if (kept) {
+    FLX_HIP(ctx, hipMemcpyAsync(bigger, buffer, kept * sizeof(T), hipMemcpyDeviceToDevice, ctx->update_stream));
+    FLX_HIP(ctx, hipStreamSynchronize(ctx->update_stream));
+  }
+  buffer = std::move(bigger);
+  return FLX_OK;
+}
+static flx_status tree_node_room(flx_context *ctx, uint32_t n_triangles, size_t kept, size_t capacity) {
+  auto &t = ctx->tree;
+  flx_status s;
+  if (t.node_capacity < capacity || !t.node) {
+    if (kept == 0) { t.node.release(ctx); t.cnt.release(ctx); t.keys.release(ctx); t.centre.release(ctx); t.y.release(ctx); }      /* (nothing to carry: not both sizes at once) */
+    if ((s = tree_grow(ctx, t.node, kept, capacity)) || (s = tree_grow(ctx, t.cnt, kept, capacity)) || (s = tree_grow(ctx, t.keys, kept * 6, capacity * 6)) ||
+        (s = tree_grow(ctx, t.centre, 0, capacity * 3)) || (s = tree_grow(ctx, t.y, kept ? kept + 1 : 0, capacity + 1))) { t.node_capacity = 0; return s; }
+    t.node_capacity = capacity;
+  }
+  return t.totals.ensure(ctx, std::max(scan_totals_items(n_triangles + 1u), scan_totals_items((uint32_t)t.node_capacity + 1u)));
+}
+
+/* The host's split, a level per round: the level's kernels, then the host waits — on update_stream alone, the frames in flight go on — for the number of children
+ * the level has, makes room for them where the node arrays are full, and launches what makes them.  The first wait brings the refusals' verdict too.  A refused
+ * or failed build leaves no tree (flx_tree_emit_device is refused); the uploaded scene is not touched in any case. */
+extern "C" flx_status flx_tree_build_device(flx_context *ctx, const void *d_triangles, uint32_t n_triangles, void *producer_stream, uint32_t *n_entries) {
+  if (!ctx) return FLX_ERR_INVALID;
+  auto &t = ctx->tree;
+  t.valid = false;
+  if (!d_triangles || !n_entries) return fail(ctx, FLX_ERR_INVALID, "flx_tree_build_device: d_triangles or n_entries is NULL");
+  if (n_triangles == 0 || n_triangles > TREE_MAX_TRIANGLES) return fail(ctx, FLX_ERR_INVALID, "flx_tree_build_device: n_triangles is 0 or above 2^24");
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  if (!rows_on_device(ctx, d_triangles, (size_t)n_triangles * 48))
+    return fail(ctx, FLX_ERR_INVALID, "flx_tree_build_device: the rows are not in memory of the context's device, 16-byte aligned");
+  const uint32_t n = n_triangles;
+  flx_status s;
+  if ((s = ensure_side_stream(ctx))) return s;
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->update_stream));      /* (the last build's index kernels, an emit's refit: before an array of theirs is replaced) */
+  if ((s = t.tbox.ensure(ctx, (size_t)n * 3)) || (s = t.perm[0].ensure(ctx, n)) || (s = t.perm[1].ensure(ctx, n)) || (s = t.owner[0].ensure(ctx, n)) ||
+      (s = t.owner[1].ensure(ctx, n)) || (s = t.open.ensure(ctx, (size_t)n + 1)) || (s = t.bucket.ensure(ctx, n)) || (s = t.entry.ensure(ctx, n)) ||
+      (s = t.x.ensure(ctx, (size_t)n + 1)) || (s = t.verdict.ensure(ctx, 4)) || (s = ctx->h_tree_record.ensure(ctx, 4, hipHostMallocDefault)) ||
+      (s = tree_node_room(ctx, n, 0, std::max(t.node_capacity, (size_t)n + 64))))
+    return s;
+  if ((s = check_on_side_stream(ctx, producer_stream))) return s;
+  hipStream_t stream = ctx->update_stream;
+  uint32_t *const rec = ctx->h_tree_record;
+  t.current = 0;
+  FLX_HIP(ctx, hipMemsetAsync(t.verdict, 0xff, 16, stream));
+  FLX_HIP(ctx, hipMemsetAsync(t.open, 0, ((size_t)n + 1) * 4, stream));
+  launch_tree_check((const float4 *)d_triangles, n, t.verdict, tree_arrays(ctx), stream);
+  FLX_HIP(ctx, hipMemcpyAsync(rec, t.verdict, 4, hipMemcpyDeviceToHost, stream));
+  FLX_HIP(ctx, hipMemcpyAsync(rec + 1, (const char *)d_triangles + 36, 4, hipMemcpyDeviceToHost, stream));      /* row 0's word 9: the boxes' */
+  const double maxDepth = std::log2((double)n) + 8.0;          /* flx_mesh.hip: importObj */
+  uint32_t base = 0, m = 1, total = 1;
+  for (uint32_t depth = 0; ; depth++) {
+    launch_tree_level(tree_arrays(ctx), n, base, m, depth, maxDepth, stream);
+    FLX_HIP(ctx, hipGetLastError());
+    FLX_HIP(ctx, hipMemcpyAsync(rec + 2, t.y.get() + m, 8, hipMemcpyDeviceToHost, stream));
+    if ((s = await_check(ctx))) return s;
+    if (depth == 0 && rec[0] != 0xffffffffu) return fail(ctx, FLX_ERR_INVALID, TREE_BUILD_REFUSAL[std::min(rec[0] & 3u, 2u)]);
+    const uint32_t children = rec[2];
+    if (children == 0) break;
+    if ((uint64_t)n + total + children > LINK_INDEX) return fail(ctx, FLX_ERR_INVALID, "flx_tree_build_device: the tree has more than 2^28 - 1 entries");
+    if ((size_t)total + children > t.node_capacity &&
+        (s = tree_node_room(ctx, n, total, std::max(t.node_capacity * 2, (size_t)total + children)))) return s;
+    launch_tree_children(tree_arrays(ctx), n, base, m, stream);
+    t.current ^= 1;
+    base += m; m = children; total += children;
+  }
+  launch_tree_index(tree_arrays(ctx), n, total, stream);
+  FLX_HIP(ctx, hipGetLastError());
+  t.n_triangles = n; t.n_nodes = total;
+  memcpy(&t.transform, rec + 1, 4);
+  t.valid = true;
+  *n_entries = n + total;
+  return FLX_OK;
+}
+
+/* the last build's block: rows and ids, the boxes' floats by the refit that flx_scene_update runs; on update_stream, waited for */
+extern "C" flx_status flx_tree_emit_device(flx_context *ctx, const void *d_triangles, const void *d_attributes, void *d_geometry, void *d_attributes_out, void *d_ids) {
+  if (!ctx) return FLX_ERR_INVALID;
+  auto &t = ctx->tree;
+  if (!t.valid) return fail(ctx, FLX_ERR_INVALID, "flx_tree_emit_device without a successful flx_tree_build_device");
+  if (!d_triangles || !d_geometry || !d_attributes_out || !d_ids) return fail(ctx, FLX_ERR_INVALID, "flx_tree_emit_device: an array is NULL");
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  const uint32_t n = t.n_triangles, entries = n + t.n_nodes;
+  if (!rows_on_device(ctx, d_triangles, (size_t)n * 48))
+    return fail(ctx, FLX_ERR_INVALID, "flx_tree_emit_device: d_triangles is not the build's n_triangles rows in memory of the context's device, 16-byte aligned");
+  if ((d_attributes && !rows_on_device(ctx, d_attributes, (size_t)n * 112)) || !rows_on_device(ctx, d_geometry, (size_t)entries * 48) ||
+      !rows_on_device(ctx, d_attributes_out, (size_t)entries * 112) || !rows_on_device(ctx, d_ids, (size_t)n * 4))
+    return fail(ctx, FLX_ERR_INVALID, "flx_tree_emit_device: an array is not in memory of the context's device, 16-byte aligned, or too short for the build");
+  flx_status s;
+  if ((s = t.refit.ensure(ctx, refit_workspace_words(entries)))) return s;      /* (the last emit was waited for) */
+  launch_tree_emit((const float4 *)d_triangles, (const float4 *)d_attributes, tree_arrays(ctx), n, t.n_nodes, t.transform, (float4 *)d_geometry,
+                   (float4 *)d_attributes_out, (int32_t *)d_ids, ctx->update_stream);
+  launch_refit((float4 *)d_geometry, entries, t.refit, ctx->update_stream);
+  FLX_HIP(ctx, hipGetLastError());
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->update_stream));
+  return FLX_OK;
+}
+
 extern "C" flx_status flx_transforms_upload(flx_context *ctx, const float *rotation, const float *shift, uint32_t n_transforms) {
   if (!ctx) return FLX_ERR_INVALID;
   if (!rotation || !shift || n_transforms == 0) return fail(ctx, FLX_ERR_INVALID, "flx_transforms_upload: need at least the identity transform");

@@ -32,6 +32,7 @@ EXPORTS = [
     "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_sample_parallel", "flx_debug_last_trace_kernel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
     "flx_raster_render", "flx_debug_walk_staged", "flx_debug_last_walk_lds", "flx_debug_walk_fast_boxes",
     "flx_scene_update", "flx_group_scene_update", "flx_debug_scene_read", "flx_scene_update_device", "flx_scene_upload_device",
+    "flx_tree_build_device", "flx_tree_emit_device",
 ]
 
 
@@ -63,6 +64,8 @@ def _load():
         "flx_group_scene_update": (C.c_int, [vp, u32, u32, fp, fp]),
         "flx_scene_update_device": (C.c_int, [vp, u32, u32, vp, vp, vp]),
         "flx_scene_upload_device": (C.c_int, [vp, vp, vp, u32, vp, u32, vp]),
+        "flx_tree_build_device": (C.c_int, [vp, vp, u32, vp, C.POINTER(u32)]),
+        "flx_tree_emit_device": (C.c_int, [vp, vp, vp, vp, vp, vp]),
         "flx_debug_scene_read": (C.c_int, [vp, C.c_int, fp, u32]),
         "flx_transforms_upload": (C.c_int, [vp, fp, fp, u32]),
         "flx_lights_upload": (C.c_int, [vp, fp, u32]),
@@ -295,6 +298,34 @@ class Context:
             stream = handle
         self._check(LIB.flx_scene_upload_device(self._h, C.c_void_p(g), C.c_void_p(a), n, C.c_void_p(i) if k else None, k,
                                                 C.c_void_p(stream) if stream else None), "flx_scene_upload_device")
+
+    def build_tree_device(self, triangles, attributes=None, stream=None):
+        """flx_tree_build_device + flx_tree_emit_device: the block of the entry array that Mesh(...).flatten() makes of the same triangles in the same order, built on
+        the device.  triangles: a torch tensor [n, 12] (float32, contiguous, on the context's device): geometry rows of kind 2; attributes: None (attribute rows of
+        zeros) or a tensor [n, 28], complete at the call.  stream: as for update_scene_rows_device, for the triangles.  -> (geometry [entries, 12], attributes
+        [entries, 28], ids [n] int32), torch tensors on the device, complete; ids count from the block's first entry."""
+        import torch
+        g, n = _device_array(triangles, "float32", 12, self._device, "triangles")
+        a = None
+        if attributes is not None:
+            a, rows = _device_array(attributes, "float32", 28, self._device, "attributes")
+            if rows != n:
+                raise ValueError("build_tree_device: as many attribute rows as triangles")
+        if stream is not None and not isinstance(stream, int):
+            handle = stream.cuda_stream
+            if handle == 0:
+                stream.synchronize()
+            stream = handle
+        entries = C.c_uint32(0)
+        self._check(LIB.flx_tree_build_device(self._h, C.c_void_p(g), n, C.c_void_p(stream) if stream else None, C.byref(entries)), "flx_tree_build_device")
+        device = torch.device("cuda", self._device)
+        geometry = torch.empty((entries.value, 12), dtype=torch.float32, device=device)
+        out = torch.empty((entries.value, 28), dtype=torch.float32, device=device)
+        ids = torch.empty(n, dtype=torch.int32, device=device)
+        torch.cuda.current_stream(device).synchronize()      # (the library writes them on a stream of its own: whatever last used that memory is done)
+        self._check(LIB.flx_tree_emit_device(self._h, C.c_void_p(g), C.c_void_p(a) if a is not None else None, C.c_void_p(geometry.data_ptr()),
+                                             C.c_void_p(out.data_ptr()), C.c_void_p(ids.data_ptr())), "flx_tree_emit_device")
+        return geometry, out, ids
 
     def update_scene_rows(self, first, geometry, attributes=None):
         """flx_scene_update: rows [first, first + n) of the uploaded scene replaced (12 floats of geometry each, 28 of attributes or None:
