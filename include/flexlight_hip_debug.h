@@ -181,7 +181,8 @@ flx_status flx_scene_upload_device(flx_context *ctx,
  * refit flx_scene_update runs) and of the triangles (copied unchanged; d_attributes NULL: zeros), ids[k] = the entry, counted from the block's first, of the k-th
  * triangle in emission order.  d_triangles: the rows the tree was built from (their count is what can be checked); every array in memory of ctx's device,
  * 16-byte aligned, long enough for the build's counts, and complete.  It returns when the arrays are complete and may be called again.  FLX_ERR_INVALID without a
- * successful build.  The block is ready to be spliced into an entry array (ids offset by its first entry) and handed to flx_scene_upload_device. */
+ * successful build.  The block is ready to be spliced into the resident scene by flx_scene_splice_device (or, by hand, into an entry array, ids offset by its first
+ * entry, for flx_scene_upload_device). */
 flx_status flx_tree_build_device(flx_context *ctx,
                                  const void *d_triangles /* n_triangles * 12 floats, on ctx's device, in the order the host builder would be given them */,
                                  uint32_t n_triangles, void *producer_stream /* hipStream_t that wrote the rows, or NULL: complete */,
@@ -189,8 +190,41 @@ flx_status flx_tree_build_device(flx_context *ctx,
 flx_status flx_tree_emit_device(flx_context *ctx, const void *d_triangles,
                                 const void *d_attributes /* n_triangles * 28 floats, or NULL: attribute rows of zeros */,
                                 void *d_geometry /* n_entries * 12 floats */, void *d_attributes_out /* n_entries * 28 floats */, void *d_ids /* n_triangles int32 */);
+/* A block of the RESIDENT scene replaced, inserted or removed in device memory: the step between "a tree can be built on the device" (flx_tree_emit_device's
+ * block) and "a mesh of my scene can change shape on the device".  The caller keeps no copy of the scene's arrays: the context holds them.
+ * Rows [first_entry, first_entry + n_old) go (n_old 0: an insertion in front of first_entry), the n_new rows of d_geometry / d_attributes come (n_new 0, the
+ * pointers ignored: a removal).  parent_entry names the box that DIRECTLY holds that range, FLX_NO_PARENT: it stands at top level.  With end = 1 + the last
+ * resident entry whose word 10 is not 0 (the reference's textureLength; a kernel finds it) and delta = n_new - n_old, the resident scene becomes what
+ * flx_scene_upload makes of this array: rows [0, first_entry) as they are; the new rows; the old rows [first_entry + n_old, end), moved by delta; rows of zeros up
+ * to the next multiple of 256 entries; word 6 (the skip count) of parent_entry and of every box whose range holds parent_entry grown by delta, in integer
+ * arithmetic; and every box refitted as flx_scene_update refits them, over the whole array — the ancestors' six floats are then what a fresh flatten computes
+ * (modules/scene.js:242-256), bit for bit; a box that skips nothing, or only boxes, keeps its six floats.  The id list becomes the old ids below first_entry, then
+ * d_ids' n_new_ids ids plus first_entry (they count from the block's first entry, as flx_tree_emit_device writes them; NULL / 0: none), then the old ids at or
+ * above first_entry + n_old plus delta; old ids of the replaced rows are dropped.  Both derived copies, max_transform, the NaN and bounded flags and the lockstep
+ * eligibility are derived of the assembled arrays as flx_scene_upload_device derives them.  A parent left without children stays, a box with skip count 0 (the
+ * reference's flatten would not emit it): removing it is a splice of the parent itself.
+ * Refusals: FLX_ERR_NO_SCENE before an upload; FLX_ERR_INVALID, each with a message of its own and the resident scene — arrays, ids, frames — exactly what it
+ * was: n_old and n_new both 0; an array not in memory of ctx's device, not 16-byte aligned or in too short an allocation; first_entry + n_old beyond end; end +
+ * delta 0 or above 2^24 (a larger skip count is no exact float); a scene uploaded with a NaN vertex (as flx_scene_update); then what a kernel over the resident
+ * geometry and ids finds, the first offending entry and its first rule: (a) parent_entry is no box, or its range (parent, parent + skip] does not hold the
+ * replaced rows — for an insertion: first_entry > parent + skip + 1; first_entry == parent + skip + 1 appends to the parent — (a parent_entry that does not lie
+ * in front of first_entry offends at entry first_entry); (b) a box between parent_entry and first_entry (FLX_NO_PARENT: any box in front of first_entry) reaches
+ * first_entry: parent_entry is not the direct parent; (c) a box among the replaced rows reaches beyond them; (d) the resident id list is not non-decreasing, as
+ * every list of the flatten is (the id that falls below its predecessor offends at the entry it names).  Last, the assembled array passes flx_scene_upload's
+ * validation: a block with a bad transform number, skip count or type is refused with that call's three messages.
+ * Ordered like flx_scene_upload_device: the checks run beside the frames in flight, the assembly behind them into fresh memory (never in place under a frame that
+ * reads the old arrays); a frame begun before the call renders the old scene, a frame begun after it the new; the frame server's launch ends; the call waits for
+ * the context's stream, and the caller's arrays are free when it returns.  flx_scene_update and flx_scene_update_device work afterwards as after an upload.
+ * producer_stream: as for flx_scene_update_device, for all three arrays.  A group keeps the host calls (flx_group_scene_upload): the arrays live on one device,
+ * its contexts on several; and there is no JavaScript binding: JavaScript has no device pointers. */
+#define FLX_NO_PARENT 0xffffffffu
+flx_status flx_scene_splice_device(flx_context *ctx, uint32_t first_entry, uint32_t n_old, uint32_t parent_entry,
+                                   const void *d_geometry /* n_new * 12 floats, on ctx's device */, const void *d_attributes /* n_new * 28 floats */, uint32_t n_new,
+                                   const void *d_ids /* n_new_ids int32, relative to the block's first entry, or NULL */, uint32_t n_new_ids,
+                                   void *producer_stream /* hipStream_t that wrote the arrays, or NULL: complete */);
 /* The uploaded scene as the device holds it, after everything enqueued so far: which 0 the geometry rows (12 floats per entry), 1 the attribute rows (28),
- * 2 the threaded hot-first copy (12 per entry of walk_entries), 3 the forward-ordered copy (12 per entry of fwd_entries: flx_debug_last_walk_lds' out[5], out[6]).
+ * 2 the threaded hot-first copy (12 per entry of walk_entries), 3 the forward-ordered copy (12 per entry of fwd_entries: flx_debug_last_walk_lds' out[5], out[6]),
+ * 4 the id list (an int32 in every 4 bytes of out, n_ids of them).
  * The first n_floats floats of the array; FLX_ERR_INVALID beyond its end.  Tests compare flx_scene_update's arrays with a fresh upload's. */
 flx_status flx_debug_scene_read(flx_context *ctx, int which, float *out, uint32_t n_floats);
 /* Walk n rays through the uploaded scene on the GPU, AS THE KERNELS DO, one ray per lane: rayTracer (fragment:172-227) and shadowTest (:230-279) of each ray;

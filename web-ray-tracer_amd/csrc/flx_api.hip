@@ -1859,9 +1859,10 @@ extern "C" flx_status flx_debug_walk_fast_boxes(flx_context *ctx, int *fast) {
 extern "C" flx_status flx_debug_scene_read(flx_context *ctx, int which, float *out, uint32_t n_floats) {
   if (!ctx || !out) return FLX_ERR_INVALID;
   if (!ctx->have_scene) return fail(ctx, FLX_ERR_NO_SCENE, "flx_debug_scene_read: no scene uploaded");
-  if (which < 0 || which > 3) return fail(ctx, FLX_ERR_INVALID, "flx_debug_scene_read: which 0 .. 3");
-  const float4 *src = which == 0 ? ctx->d_geometry : which == 1 ? ctx->d_attributes : which == 2 ? ctx->d_walk : ctx->d_fwd;
-  const size_t have = which == 0 ? (size_t)ctx->n_entries * 12 : which == 1 ? (size_t)ctx->n_entries * 28 : which == 2 ? (size_t)ctx->walk_entries * 12 : (size_t)ctx->fwd_entries * 12;
+  if (which < 0 || which > 4) return fail(ctx, FLX_ERR_INVALID, "flx_debug_scene_read: which 0 .. 4");
+  const void *src = which == 0 ? ctx->d_geometry.get() : which == 1 ? ctx->d_attributes.get() : which == 2 ? ctx->d_walk.get() : which == 3 ? ctx->d_fwd.get() : (const void *)ctx->d_ids.get();
+  const size_t have = which == 0 ? (size_t)ctx->n_entries * 12 : which == 1 ? (size_t)ctx->n_entries * 28 : which == 2 ? (size_t)ctx->walk_entries * 12 :
+                      which == 3 ? (size_t)ctx->fwd_entries * 12 : (size_t)ctx->n_ids;      /* (the ids: an int32 each) */
   if (n_floats > have) return fail(ctx, FLX_ERR_INVALID, "flx_debug_scene_read: more floats than the array has");
   if (n_floats == 0) return FLX_OK;
   FLX_HIP(ctx, hipSetDevice(ctx->device));

@@ -164,6 +164,20 @@ void launch_tree_index(const TreeArrays &t, uint32_t n, uint32_t nodes, hipStrea
 /* the block's n + nodes rows of both arrays (a box row's words 0..5: launch_refit's) and the ids */
 void launch_tree_emit(const float4 *rows, const float4 *attributes, const TreeArrays &t, uint32_t n, uint32_t nodes, float transform, float4 *geometry,
                       float4 *attributesOut, int32_t *ids, hipStream_t stream);
+/* flx_scene_splice_device (flx_splice.hip).  launch_splice_check, over the resident geometry (n_entries rows) and ids, fills the record (SPLICE_RECORD_WORDS, zeroed
+ * before): [0] 0 where nothing offends, else ~(entry * 4 + rule) of the first offending entry and its first rule (0 the parent, 1 not the direct parent, 2 a box cut
+ * in two, 3 the ids are out of order); [1] end: 1 + the last entry whose word 10 is not 0; [2] ids below first; [3] ids at or above first + n_old.  first + n_old
+ * <= n_entries.  launch_splice_rows assembles both arrays (n_padded rows each, fresh memory): rows [0, first) of the old, n_new of the block, the old rows
+ * [first + n_old, end) — end_new = end + n_new - n_old —, zeros; word 6 of the parent and of the boxes that hold it grows by n_new - n_old.  launch_splice_ids: the
+ * first `below` old ids, the block's plus first, the last `above` old ids plus delta. */
+enum { SPLICE_REC_VERDICT = 0, SPLICE_REC_END, SPLICE_REC_IDS_BELOW, SPLICE_REC_IDS_ABOVE, SPLICE_RECORD_WORDS };
+struct SpliceShape { uint32_t first, n_old, n_new, parent, end_new, n_padded; };
+void launch_splice_check(const float4 *geometry, uint32_t n_entries, const int32_t *ids, uint32_t n_ids, uint32_t first, uint32_t n_old, uint32_t parent, uint32_t *record,
+                         hipStream_t stream);
+void launch_splice_rows(const float4 *geometry, const float4 *attributes, const float4 *blockGeometry, const float4 *blockAttributes, const SpliceShape &shape,
+                        float4 *geometryOut, float4 *attributesOut, hipStream_t stream);
+void launch_splice_ids(const int32_t *ids, uint32_t n_ids, const int32_t *blockIds, uint32_t n_block, uint32_t below, uint32_t above, uint32_t first, int32_t delta,
+                       int32_t *out, hipStream_t stream);
 void launch_debug_math(int fn, const float *a, const float *b, float *out, uint32_t n, hipStream_t stream);
 void launch_debug_intersect(int fn, const float *in, float *out, uint32_t n, hipStream_t stream);
 bool launch_debug_walk(int variant, const DeviceScene &sc, const float *in, float *out, uint32_t n, hipStream_t stream);      /* false: the scene does not allow that variant */

@@ -301,9 +301,10 @@ extern "C" flx_status flx_scene_upload(flx_context *ctx, const float *geometry, 
   if ((s = ensure_side_stream(ctx)) || (s = shared_upload_begin(ctx))) return s;
   begin_scene(ctx);
   if ((s = upload(ctx, ctx->d_geometry, geometry, (size_t)n_entries_padded * 48))) return s;
-  FLX_HIP(ctx, hipEventRecord(ctx->geometry_uploaded, ctx->stream));      /* (a small array is copied in stream order: flx_scene_update_device's check reads it on another stream) */
   if ((s = upload(ctx, ctx->d_attributes, attributes, (size_t)n_entries_padded * 112))) return s;
   if ((s = upload(ctx, ctx->d_ids, ids, (size_t)n_ids * 4))) return s;
+  /* (a small array is copied in stream order: flx_scene_update_device's check reads the geometry on another stream, flx_scene_splice_device's the ids too) */
+  FLX_HIP(ctx, hipEventRecord(ctx->geometry_uploaded, ctx->stream));
   std::vector<float> copy;
   build_threaded(geometry, n_entries_padded, copy, facts.walk_entries, facts.walk_hot, facts.walk_root);
   if ((s = upload(ctx, ctx->d_walk, copy.data(), copy.size() * sizeof(float)))) return s;
@@ -314,6 +315,31 @@ extern "C" flx_status flx_scene_upload(flx_context *ctx, const float *geometry, 
   adopt_scene(ctx, n_entries_padded, n_ids, facts);
   ctx->h_entry_meta.swap(entry_meta); ctx->entry_meta_stale = false;
   if ((s = shared_upload_end(ctx))) return s;
+  ctx->have_scene = true;
+  return FLX_OK;
+}
+
+/* The tail of every change of the scene that is made in device memory (flx_scene_upload_device, flx_scene_splice_device): d_geometry, d_attributes and d_ids hold
+ * the new arrays, or will in stream order; rec is the record k_derive_check made of d_geometry's contents, and the derive workspace stands as that check left it,
+ * behind `checked` where it ran on another stream than the context's (nullptr: on the context's).  Room for both derived copies, launch_derive_copies for
+ * build_threaded and build_lockstep, the context's scalars, and one wait for the context's stream. */
+static flx_status derive_and_adopt(flx_context *ctx, uint32_t n_entries_padded, uint32_t n_ids, const uint32_t *rec, hipEvent_t checked) {
+  const uint32_t live = rec[5], meta0 = rec[6];
+  SceneFacts facts;
+  facts.max_transform = rec[1]; facts.has_nan = rec[2] != 0u; facts.bounded = rec[3] == 0u; facts.lock_boxes = rec[4];
+  /* both copies hold the live entries and one shared terminator; entry 0 is the shallowest entry with the lowest index: hot, the threaded copy's entry 1 */
+  facts.walk_entries = facts.fwd_entries = live + 1u; facts.walk_hot = std::min(live, HOT_MAX) + 1u;
+  facts.walk_root = meta0 == 0u ? 0u : 1u | (meta0 & 3u) << LINK_KIND_SHIFT | ((meta0 >> 2) != 0u ? LINK_XFORM : 0u);
+  facts.fwd_root = meta0 == 0u ? live : 0u;
+  flx_status s;
+  if ((s = upload_from_device(ctx, ctx->d_walk, nullptr, (size_t)facts.walk_entries * 48))) return s;
+  if ((s = upload_from_device(ctx, ctx->d_fwd, nullptr, (size_t)facts.fwd_entries * 48))) return s;
+  if (checked) FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, checked, 0));      /* the workspace as the check left it */
+  launch_derive_copies(ctx->d_geometry, n_entries_padded, live, ctx->d_derive, ctx->d_walk, ctx->d_fwd, ctx->stream);
+  FLX_HIP(ctx, hipGetLastError());
+  adopt_scene(ctx, n_entries_padded, n_ids, facts);
+  ctx->h_entry_meta.clear(); ctx->entry_meta_stale = true;      /* (it stays on the device until a flx_scene_update of host rows asks for it: fetch_entry_meta) */
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));          /* the caller's arrays are not retained (and: shared_upload_end) */
   ctx->have_scene = true;
   return FLX_OK;
 }
@@ -338,30 +364,100 @@ extern "C" flx_status flx_scene_upload_device(flx_context *ctx, const void *d_ge
   FLX_HIP(ctx, hipMemcpyAsync(ctx->h_derive_record, ctx->d_derive, DERIVE_RECORD_WORDS * 4, hipMemcpyDeviceToHost, ctx->update_stream));
   if ((s = await_check(ctx))) return s;
   const uint32_t *rec = ctx->h_derive_record;
-  const uint32_t rule = ~rec[0] & 3u, live = rec[5], meta0 = rec[6];
+  const uint32_t rule = ~rec[0] & 3u;
   if (rec[0] != 0u) return fail(ctx, FLX_ERR_INVALID, SCENE_UPLOAD_REFUSAL[rule < 3u ? rule : 2u]);
-  SceneFacts facts;
-  facts.max_transform = rec[1]; facts.has_nan = rec[2] != 0u; facts.bounded = rec[3] == 0u; facts.lock_boxes = rec[4];
-  /* both copies hold the live entries and one shared terminator; entry 0 is the shallowest entry with the lowest index: hot, the threaded copy's entry 1 */
-  facts.walk_entries = facts.fwd_entries = live + 1u; facts.walk_hot = std::min(live, HOT_MAX) + 1u;
-  facts.walk_root = meta0 == 0u ? 0u : 1u | (meta0 & 3u) << LINK_KIND_SHIFT | ((meta0 >> 2) != 0u ? LINK_XFORM : 0u);
-  facts.fwd_root = meta0 == 0u ? live : 0u;
   if ((s = shared_upload_begin(ctx))) return s;
   begin_scene(ctx);
   if ((s = upload_from_device(ctx, ctx->d_geometry, d_geometry, (size_t)n_entries_padded * 48))) return s;
   FLX_HIP(ctx, hipEventRecord(ctx->geometry_uploaded, ctx->stream));      /* (flx_scene_update_device's check reads the array on another stream) */
   if ((s = upload_from_device(ctx, ctx->d_attributes, d_attributes, (size_t)n_entries_padded * 112))) return s;
   if ((s = upload_from_device(ctx, ctx->d_ids, d_ids, (size_t)n_ids * 4))) return s;
-  if ((s = upload_from_device(ctx, ctx->d_walk, nullptr, (size_t)facts.walk_entries * 48))) return s;
-  if ((s = upload_from_device(ctx, ctx->d_fwd, nullptr, (size_t)facts.fwd_entries * 48))) return s;
-  FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->update_checked, 0));      /* the workspace as the check left it */
-  launch_derive_copies(ctx->d_geometry, n_entries_padded, live, ctx->d_derive, ctx->d_walk, ctx->d_fwd, ctx->stream);
-  FLX_HIP(ctx, hipGetLastError());
-  adopt_scene(ctx, n_entries_padded, n_ids, facts);
-  ctx->h_entry_meta.clear(); ctx->entry_meta_stale = true;      /* (it stays on the device until a flx_scene_update of host rows asks for it: fetch_entry_meta) */
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));          /* the caller's arrays are not retained (and: shared_upload_end) */
-  ctx->have_scene = true;
+  return derive_and_adopt(ctx, n_entries_padded, n_ids, rec, ctx->update_checked);
+}
+
+/* Why a splice is refused by what the resident scene holds; the values are k_splice_check's rule numbers (flx_splice.hip). */
+static const char *const SCENE_SPLICE_REFUSAL[4] = {
+  "flx_scene_splice_device: parent_entry is not a box in front of first_entry whose range holds the replaced rows",
+  "flx_scene_splice_device: a box between parent_entry and first_entry reaches first_entry (parent_entry is not the direct parent)",
+  "flx_scene_splice_device: a box among the replaced rows reaches beyond them",
+  "flx_scene_splice_device: the resident id list is not non-decreasing" };
+
+/* k_derive_check over an array assembled on the context's stream, there, and the host waits for its record */
+static flx_status check_assembled(flx_context *ctx, const float4 *geometry, uint32_t n_entries_padded) {
+  FLX_HIP(ctx, launch_derive_check(geometry, n_entries_padded, ctx->d_derive, ctx->stream));
+  FLX_HIP(ctx, hipMemcpyAsync(ctx->h_derive_record, ctx->d_derive, DERIVE_RECORD_WORDS * 4, hipMemcpyDeviceToHost, ctx->stream));
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return FLX_OK;
+}
+
+/* A block of the resident scene replaced, inserted or removed in device memory.  Three steps, each behind a verdict:
+ *   1. k_splice_check (flx_splice.hip) on update_stream, over the resident geometry and ids, into four words: the host waits for that stream alone — the frames in
+ *      flight go on — and knows `end`, the id counts and whether a rule of the splice is broken;
+ *   2. on the context's stream, behind the frames in flight (they read the old arrays to their end): the assembly of both arrays and of the ids into FRESH
+ *      memory, and flx_scene_upload's validation of the assembled array (launch_derive_check); the host waits for the stream and the verdict;
+ *   3. the refit of every box of the assembled array (only now: it follows skip counts), the check once more for what it says of the refitted boxes (the bounded
+ *      flag) and as the base of the derivation; the fresh arrays become the context's, the old ones are freed, and the rest is flx_scene_upload_device's tail.
+ * Until step 3 a refusal has touched the workspaces and the fresh arrays alone, which go with it.  The frame server's launch ends before step 2. */
+extern "C" flx_status flx_scene_splice_device(flx_context *ctx, uint32_t first_entry, uint32_t n_old, uint32_t parent_entry, const void *d_geometry,
+                                              const void *d_attributes, uint32_t n_new, const void *d_ids, uint32_t n_new_ids, void *producer_stream) {
+  if (!ctx) return FLX_ERR_INVALID;
+  if (!ctx->have_scene) return fail(ctx, FLX_ERR_NO_SCENE, "flx_scene_splice_device before flx_scene_upload");
+  if (n_old == 0 && n_new == 0) return fail(ctx, FLX_ERR_INVALID, "flx_scene_splice_device: n_old and n_new are both 0");
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  if ((n_new && (!d_geometry || !d_attributes || !rows_on_device(ctx, d_geometry, (size_t)n_new * 48) || !rows_on_device(ctx, d_attributes, (size_t)n_new * 112))) ||
+      (n_new_ids && (!d_ids || !rows_on_device(ctx, d_ids, (size_t)n_new_ids * 4))))
+    return fail(ctx, FLX_ERR_INVALID, "flx_scene_splice_device: an array is not in memory of the context's device, 16-byte aligned, or too short");
+  static const char *const beyond = "flx_scene_splice_device: the replaced rows leave the scene (first_entry + n_old lies beyond its last entry)";
+  if ((uint64_t)first_entry + n_old > ctx->n_entries) return fail(ctx, FLX_ERR_INVALID, beyond);      /* (end <= n_entries: the kernel's lanes may rely on it) */
+  if (ctx->scene_has_nan)
+    return fail(ctx, FLX_ERR_INVALID, "flx_scene_splice_device: the uploaded scene has a NaN vertex (its boxes cannot be refitted as the flatten makes them)");
+  flx_status s;
+  if ((s = ctx->d_update_verdict.ensure(ctx, SPLICE_RECORD_WORDS)) || (s = ctx->h_update_verdict.ensure(ctx, SPLICE_RECORD_WORDS, hipHostMallocDefault))) return s;
+  if ((s = check_on_side_stream(ctx, producer_stream))) return s;
+  FLX_HIP(ctx, hipStreamWaitEvent(ctx->update_stream, ctx->geometry_uploaded, 0));      /* (words 6 and 10 and the ids: written by an upload alone) */
+  FLX_HIP(ctx, hipMemsetAsync(ctx->d_update_verdict, 0, SPLICE_RECORD_WORDS * 4, ctx->update_stream));
+  launch_splice_check(ctx->d_geometry, ctx->n_entries, ctx->d_ids, ctx->n_ids, first_entry, n_old, parent_entry, ctx->d_update_verdict, ctx->update_stream);
+  FLX_HIP(ctx, hipGetLastError());
+  FLX_HIP(ctx, hipMemcpyAsync(ctx->h_update_verdict, ctx->d_update_verdict, SPLICE_RECORD_WORDS * 4, hipMemcpyDeviceToHost, ctx->update_stream));
+  if ((s = await_check(ctx))) return s;
+  const uint32_t verdict = ctx->h_update_verdict[SPLICE_REC_VERDICT], end = ctx->h_update_verdict[SPLICE_REC_END];
+  const uint32_t below = ctx->h_update_verdict[SPLICE_REC_IDS_BELOW], above = ctx->h_update_verdict[SPLICE_REC_IDS_ABOVE];
+  if ((uint64_t)first_entry + n_old > end) return fail(ctx, FLX_ERR_INVALID, beyond);
+  const int64_t end_new = (int64_t)end + (int64_t)n_new - (int64_t)n_old;
+  if (end_new <= 0 || end_new > (int64_t)1 << 24)      /* (a skip count beyond 2^24 is no exact float any more) */
+    return fail(ctx, FLX_ERR_INVALID, "flx_scene_splice_device: the scene would have no entry, or more than 2^24");
+  if (verdict != 0u) return fail(ctx, FLX_ERR_INVALID, SCENE_SPLICE_REFUSAL[~verdict & 3u]);
+  /* everything the next steps need is there before anything is enqueued */
+  const uint32_t n_padded = ((uint32_t)end_new + 255u) / 256u * 256u, n_ids = below + n_new_ids + above;
+  const SpliceShape shape = { first_entry, n_old, n_new, parent_entry, (uint32_t)end_new, n_padded };
+  DeviceBuffer<float4> geometry, attributes;
+  DeviceBuffer<int32_t> ids;
+  if ((s = geometry.ensure(ctx, (size_t)n_padded * 3)) || (s = attributes.ensure(ctx, (size_t)n_padded * 7)) || (n_ids && (s = ids.ensure(ctx, n_ids)))) return s;
+  /* (nothing in flight uses the derive workspace: flx_scene_upload_device, this call and fetch_entry_meta end with a wait) */
+  if ((s = ctx->d_derive.ensure(ctx, derive_workspace_words(n_padded))) || (s = ctx->h_derive_record.ensure(ctx, DERIVE_RECORD_WORDS, hipHostMallocDefault))) return s;
+  if (!ctx->d_refit.fits(refit_workspace_words(n_padded))) {
+    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));      /* (an earlier update's refit may still use it) */
+    if ((s = ctx->d_refit.ensure(ctx, refit_workspace_words(n_padded)))) return s;
+  }
+  if ((s = flx_server_stop(ctx))) return s;      /* (its launch would keep the kernels below waiting; it ends at any change of the scene) */
+  FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->update_checked, 0));      /* the caller's rows: update_stream waited for their producer */
+  launch_splice_rows(ctx->d_geometry, ctx->d_attributes, (const float4 *)d_geometry, (const float4 *)d_attributes, shape, geometry, attributes, ctx->stream);
+  launch_splice_ids(ctx->d_ids, ctx->n_ids, (const int32_t *)d_ids, n_new_ids, below, above, first_entry, (int32_t)n_new - (int32_t)n_old, ids, ctx->stream);
+  FLX_HIP(ctx, hipGetLastError());
+  const uint32_t *rec = ctx->h_derive_record;
+  if ((s = check_assembled(ctx, geometry, n_padded))) return s;
+  if (rec[0] != 0u) return fail(ctx, FLX_ERR_INVALID, SCENE_UPLOAD_REFUSAL[std::min(~rec[0] & 3u, 2u)]);
+  launch_refit(geometry, n_padded, ctx->d_refit, ctx->stream);      /* (every skip count keeps inside the array: checked) */
+  if ((s = check_assembled(ctx, geometry, n_padded))) return s;
+  /* the caller's arrays are free from here; the fresh ones become the scene's, as an upload's copies would have filled them */
+  ctx->sv_want_ver = false;                 /* (another scene: it has not moved yet) */
+  if ((s = shared_upload_begin(ctx))) return s;      /* (the second lane's frames in flight read the old arrays) */
+  begin_scene(ctx);
+  ctx->d_geometry = std::move(geometry); ctx->d_attributes = std::move(attributes);
+  if (n_ids) ctx->d_ids = std::move(ids);
+  else if ((s = ctx->d_ids.release(ctx))) return s;
+  FLX_HIP(ctx, hipEventRecord(ctx->geometry_uploaded, ctx->stream));
+  return derive_and_adopt(ctx, n_padded, n_ids, rec, nullptr);
 }
 
 /* h_entry_meta after flx_scene_upload_device, which leaves it on the device: words 6, 9 and 10 of every entry, compacted by a kernel and copied back, at the first

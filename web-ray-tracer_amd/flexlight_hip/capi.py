@@ -32,12 +32,13 @@ EXPORTS = [
     "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_sample_parallel", "flx_debug_last_trace_kernel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
     "flx_raster_render", "flx_debug_walk_staged", "flx_debug_last_walk_lds", "flx_debug_walk_fast_boxes",
     "flx_scene_update", "flx_group_scene_update", "flx_debug_scene_read", "flx_scene_update_device", "flx_scene_upload_device",
-    "flx_tree_build_device", "flx_tree_emit_device",
+    "flx_tree_build_device", "flx_tree_emit_device", "flx_scene_splice_device",
 ]
 
 
 
 SHARE_HANDLE_BYTES = 128      # FLX_SHARE_HANDLE_BYTES
+NO_PARENT = 0xffffffff         # FLX_NO_PARENT of include/flexlight_hip_debug.h
 FRAME_FXAA = 0x10              # FLX_FRAME_FXAA: flags of flx_frame_begin's format
 FRAME_TAA = 0x20               # FLX_FRAME_TAA
 FRAME_RASTERIZER = 0x100       # FLX_FRAME_RASTERIZER
@@ -66,6 +67,7 @@ def _load():
         "flx_scene_upload_device": (C.c_int, [vp, vp, vp, u32, vp, u32, vp]),
         "flx_tree_build_device": (C.c_int, [vp, vp, u32, vp, C.POINTER(u32)]),
         "flx_tree_emit_device": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+        "flx_scene_splice_device": (C.c_int, [vp, u32, u32, u32, vp, vp, u32, vp, u32, vp]),
         "flx_debug_scene_read": (C.c_int, [vp, C.c_int, fp, u32]),
         "flx_transforms_upload": (C.c_int, [vp, fp, fp, u32]),
         "flx_lights_upload": (C.c_int, [vp, fp, u32]),
@@ -327,6 +329,36 @@ class Context:
                                              C.c_void_p(out.data_ptr()), C.c_void_p(ids.data_ptr())), "flx_tree_emit_device")
         return geometry, out, ids
 
+    def splice_scene_device(self, first, n_old, parent, geometry, attributes, ids=None, stream=None):
+        """flx_scene_splice_device: rows [first, first + n_old) of the RESIDENT scene replaced by a block that is in device memory (n_old 0: the block is
+        inserted in front of `first`).  parent: the entry of the box that directly holds the range, None (or NO_PARENT): top level.  geometry: a torch tensor
+        [n, 12] (float32, contiguous, on the context's device) or (address, n), attributes [n, 28] likewise; both None: a removal.  ids: None, an int32 tensor [k]
+        or (address, k): the block's ids, counted from its first entry (build_tree_device's).  stream: as for update_scene_rows_device, for all three arrays.
+        One context's call: a group keeps the host calls."""
+        g, n, a, i, k = None, 0, None, None, 0
+        if geometry is not None or attributes is not None:
+            g, n = _device_array(geometry, "float32", 12, self._device, "geometry")
+            a, rows = _device_array(attributes, "float32", 28, self._device, "attributes")
+            if rows != n:
+                raise ValueError("splice_scene_device: as many attribute rows as geometry rows")
+        if ids is not None:
+            i, k = _device_array(ids, "int32", None, self._device, "ids")
+        if stream is not None and not isinstance(stream, int):
+            handle = stream.cuda_stream
+            if handle == 0:
+                stream.synchronize()
+            stream = handle
+        self._check(LIB.flx_scene_splice_device(self._h, first, n_old, NO_PARENT if parent is None else parent, C.c_void_p(g) if n else None,
+                                                C.c_void_p(a) if n else None, n, C.c_void_p(i) if k else None, k, C.c_void_p(stream) if stream else None),
+                    "flx_scene_splice_device")
+
+    def replace_mesh_device(self, first, n_old, parent, triangles, attributes=None, stream=None):
+        """build_tree_device of the triangles (and their attribute rows), then splice_scene_device of the block it made over rows [first, first + n_old) of the
+        resident scene: a mesh of the scene takes another shape without an array leaving the device.  -> the block's entry count."""
+        geometry, out, ids = self.build_tree_device(triangles, attributes, stream)
+        self.splice_scene_device(first, n_old, parent, geometry, out, ids)      # (the block is complete: flx_tree_emit_device waited)
+        return geometry.shape[0]
+
     def update_scene_rows(self, first, geometry, attributes=None):
         """flx_scene_update: rows [first, first + n) of the uploaded scene replaced (12 floats of geometry each, 28 of attributes or None:
         they stay), every box refitted on the device."""
@@ -354,8 +386,13 @@ class Context:
 
     def scene_read(self, which, rows=None):
         """flx_debug_scene_read: the device's 'geometry' [rows, 12], 'attributes' [rows, 28], 'walk' (the threaded copy) or 'fwd' (the forward-ordered
-        copy) [rows, 12]; rows: the first so many entries (the copies: all of them when None)."""
-        k = ("geometry", "attributes", "walk", "fwd").index(which)
+        copy) [rows, 12], or 'ids' (int32 [rows]); rows: the first so many entries (the copies: all of them when None)."""
+        k = ("geometry", "attributes", "walk", "fwd", "ids").index(which)
+        if k == 4:                                # the id list: int32 [rows]
+            out = np.zeros(rows, np.int32)
+            if rows:
+                self._check(LIB.flx_debug_scene_read(self._h, k, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "flx_debug_scene_read")
+            return out
         if rows is None:
             if k < 2:
                 raise ValueError("scene_read: rows of the geometry / attribute array wanted")
