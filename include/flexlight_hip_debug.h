@@ -113,12 +113,30 @@ flx_status flx_debug_math(flx_context *ctx, int fn, const float *a, const float 
  * routine over stored edges (exact 1/det from v_rcp_f32, branch-free acceptance), 1: moellerTrumboreCull (:143-158) through the same routine, 2: rayCuboid
  * (:161-167) through the walk kernels' box test (interval test, exact quotients by reciprocal, IEEE division where their preconditions fail); 3, 4, 5: the
  * same three as the per-pixel kernel calls them; 6: fn 2 for a scene whose boxes are NOT bounded (walk_fast_boxes = 0: every quotient by IEEE division) — fn 2 stands for a
- * scene that is, so its rows must keep flx_scene_upload's bound: every box coordinate finite with |x| <= 2^59 (tests/golden/intersect_edge_kat.json.gz).  Rows: triangles 16 floats (a, b, c, origin, direction, l), boxes 13 (l, origin, direction, min, max);
+ * scene that is, so its rows must keep flx_scene_upload's bound: every box coordinate finite with |x| <= 2^59 (tests/golden/intersect_edge_kat.json.gz); 7: fn 2 with the
+ * interval test in its single-comparison form, the one the frame kernels take for a scene without a flat box (flx_debug_walk_thick_boxes) — a flat box may be put through it like any other; 8: fn 7 for a scene whose boxes are not bounded, as 6 is to 2.  Rows: triangles 16 floats (a, b, c, origin, direction, l), boxes 13 (l, origin, direction, min, max);
  * out: 3 floats per row for fn 0 and 3 ((s, u, v) of a hit, zeros otherwise), else one float 0 / 1. */
 flx_status flx_debug_intersect(flx_context *ctx, int fn, const float *in, float *out, uint32_t n);
 /* The uploaded scene's walk_fast_boxes, read-only: 1 when every coordinate of every box entry (type 1) is finite with |x| <= 2^59 — the precondition under which the
  * walk kernels take their box quotients through reciprocals; triangle entries do not count. */
 flx_status flx_debug_walk_fast_boxes(flx_context *ctx, int *fast);
+/* The uploaded scene's walk_thick_boxes, read-only: 1 when every box entry (type 1) is KNOWN to have min < max on all three axes.  The frame kernels and the frame server
+ * then decide "surely hit" in their box test from one comparison, lo(tmax) >= hi(tmin), instead of three cross-pair ones; a flat box can never pass that comparison and
+ * would take the exact quotients every time it is hit, so a scene that has one keeps the cross-pair form.  A hint of speed alone — both forms give the reference's
+ * boolean for every box.  flx_scene_upload, flx_scene_upload_device and flx_scene_splice_device look at every box (of the spliced scene: as refitted); flx_scene_update and
+ * flx_scene_update_device refit the boxes on the device without reading them back and clear the hint until the next upload. */
+flx_status flx_debug_walk_thick_boxes(flx_context *ctx, int *thick);
+/* Which form the frame kernels and the frame server take from the next frame on: -1 by the scene's hint (the default), 0 the cross-pair form, 1 the single comparison.
+ * flx_debug_walk's variant 0 and flx_debug_walk_staged — the frame kernels' lane walk, a ray at a time — follow the same choice.  For tests: frames, walks and work
+ * counters are the same in either form on every scene. */
+flx_status flx_debug_set_box_test(flx_context *ctx, int form);
+/* The form compiled into the kernel the last frame kernel or frame server launch ran (what flx_debug_last_walk_lds describes): 0 cross pairs (k_wf_frame_flat,
+ * k_wf_frame_stamped_flat, k_wf_server<., false>), 1 the single comparison (k_wf_frame, k_wf_frame_stamped, k_wf_server<., true>); -1: the rounds or another pipeline ran,
+ * or nothing since the scene upload.  Both give the same frames: this is the one place that tells which ran. */
+flx_status flx_debug_last_box_test(flx_context *ctx, int *form);
+/* Whether every box entry (word 10 == 1) of an entry array has min < max on all three axes — flx_scene_upload's own scan, on the host, no context: n_entries rows of 12
+ * floats.  A NaN corner or min > max is not thick. */
+int flx_debug_boxes_thick(const float *geometry, uint32_t n_entries);
 /* ---- vertex updates ------------------------------------------------------------------------------- */
 /* Beyond the drop-in boundary, like everything in this header: a host that only knows flx_scene_upload renders every scene (the reference's updateScene() is that
  * call), this is the shorter way for a scene whose topology stands still.  (Declared here and not in flexlight_hip.h because that header is held at the 80

@@ -163,6 +163,7 @@ flx_status flx_make_frame(flx_context *ctx, const flx_frame_params *p, DeviceSce
   for (int i = 0; i < 3; i++) { sc.atlas[i] = ctx->d_atlas[i]; sc.atlas_w[i] = ctx->atlas_w[i]; sc.atlas_h[i] = ctx->atlas_h[i]; }
   sc.n_entries = ctx->n_entries; sc.n_lights = ctx->n_lights; sc.n_transforms = ctx->n_transforms;
   sc.walk = ctx->d_walk; sc.walk_entries = ctx->walk_entries; sc.walk_hot = ctx->walk_hot; sc.walk_root = ctx->walk_root; sc.walk_fast_boxes = ctx->walk_fast_boxes;
+  sc.walk_thick_boxes = ctx->box_test < 0 ? ctx->walk_thick_boxes : (uint32_t)ctx->box_test;      /* (either form gives every scene's booleans: flx_device.h, rayCuboidInterval) */
   sc.fwd = ctx->d_fwd; sc.fwd_entries = ctx->fwd_entries; sc.fwd_root = ctx->fwd_root;
   sc.lock = ctx->d_fwd; sc.lock_entries = (ctx->lock_ok && ctx->lock_use) ? ctx->fwd_entries : 0u; sc.lock_root = ctx->fwd_root;
   sc.angle_tan = nullptr;                  /* (the per-pixel kernel's table: flx_run_frame makes it where that kernel is launched) */
@@ -1020,7 +1021,7 @@ static void mirror_scene(flx_context *ctx) {
   if (!t) return;
   t->d_geometry.borrow(ctx->d_geometry); t->d_attributes.borrow(ctx->d_attributes); t->d_ids.borrow(ctx->d_ids); t->d_walk.borrow(ctx->d_walk);
   t->d_fwd.borrow(ctx->d_fwd); t->fwd_entries = ctx->fwd_entries; t->fwd_root = ctx->fwd_root; t->lock_ok = ctx->lock_ok; t->lock_use = ctx->lock_use; t->lock_boxes = ctx->lock_boxes;
-  t->walk_entries = ctx->walk_entries; t->walk_hot = ctx->walk_hot; t->walk_root = ctx->walk_root; t->walk_fast_boxes = ctx->walk_fast_boxes;
+  t->walk_entries = ctx->walk_entries; t->walk_hot = ctx->walk_hot; t->walk_root = ctx->walk_root; t->walk_fast_boxes = ctx->walk_fast_boxes; t->walk_thick_boxes = ctx->walk_thick_boxes; t->box_test = ctx->box_test;
   for (int i = 0; i < 3; i++) { t->d_atlas[i].borrow(ctx->d_atlas[i]); t->atlas_w[i] = ctx->atlas_w[i]; t->atlas_h[i] = ctx->atlas_h[i]; }
   t->n_entries = ctx->n_entries; t->n_ids = ctx->n_ids; t->max_transform = ctx->max_transform; t->have_scene = ctx->have_scene;
   t->geometry_version = ctx->geometry_version; t->angle_table = ctx->angle_table;      /* (the lane's own angle table follows: flx_make_frame) */
@@ -1834,10 +1835,10 @@ extern "C" flx_status flx_debug_math(flx_context *ctx, int fn, const float *a, c
 
 extern "C" flx_status flx_debug_intersect(flx_context *ctx, int fn, const float *in, float *out, uint32_t n) {
   if (!ctx || !in || !out) return FLX_ERR_INVALID;
-  if (fn < 0 || fn > 6) return fail(ctx, FLX_ERR_INVALID, "flx_debug_intersect: fn 0 .. 6");
+  if (fn < 0 || fn > 8) return fail(ctx, FLX_ERR_INVALID, "flx_debug_intersect: fn 0 .. 8");
   if (n == 0) return FLX_OK;
   FLX_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t nin = (size_t)n * ((fn == 2 || fn == 5 || fn == 6) ? 13u : 16u), nout = (size_t)n * ((fn == 0 || fn == 3) ? 3u : 1u);
+  const size_t nin = (size_t)n * ((fn == 2 || fn >= 5) ? 13u : 16u), nout = (size_t)n * ((fn == 0 || fn == 3) ? 3u : 1u);
   DeviceBuffer<float> d_in, d_out;                         /* freed on every way out */
   flx_status s;
   if ((s = d_in.ensure(ctx, nin)) || (s = d_out.ensure(ctx, nout))) return s;
@@ -1853,6 +1854,29 @@ extern "C" flx_status flx_debug_walk_fast_boxes(flx_context *ctx, int *fast) {
   if (!ctx || !fast) return FLX_ERR_INVALID;
   if (!ctx->have_scene) return fail(ctx, FLX_ERR_INVALID, "flx_debug_walk_fast_boxes: no scene uploaded");
   *fast = ctx->walk_fast_boxes != 0u ? 1 : 0;
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_debug_walk_thick_boxes(flx_context *ctx, int *thick) {
+  if (!ctx || !thick) return FLX_ERR_INVALID;
+  if (!ctx->have_scene) return fail(ctx, FLX_ERR_INVALID, "flx_debug_walk_thick_boxes: no scene uploaded");
+  *thick = ctx->walk_thick_boxes != 0u ? 1 : 0;
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_debug_last_box_test(flx_context *ctx, int *form) {
+  if (!ctx || !form) return FLX_ERR_INVALID;
+  *form = ctx->last_walk_lds.boxTest;
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_debug_set_box_test(flx_context *ctx, int form) {
+  if (!ctx) return FLX_ERR_INVALID;
+  if (form < -1 || form > 1) return fail(ctx, FLX_ERR_INVALID, "flx_debug_set_box_test: form -1, 0 or 1");
+  flx_status s;
+  if (form != ctx->box_test && (s = flx_server_stop(ctx))) return s;      /* (a running frame server's launch has its form compiled in) */
+  ctx->box_test = form;
+  if (ctx->twin) ctx->twin->box_test = form;
   return FLX_OK;
 }
 

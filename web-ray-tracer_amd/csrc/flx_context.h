@@ -78,6 +78,8 @@ struct flx_context {
   DeviceBuffer<float4> d_geometry, d_attributes, d_rotation, d_shift;      /* (a twin: geometry, attributes, ids, walk, fwd and the atlases are views of the primary's: mirror_scene) */
   DeviceBuffer<float4> d_walk;                     /* threaded hot-first copy of the skip list */
   uint32_t walk_entries = 0, walk_hot = 0, walk_root = 0, walk_fast_boxes = 0;
+  uint32_t walk_thick_boxes = 0;                   /* every box of the scene is known to have min < max on all three axes (DeviceScene::walk_thick_boxes: a hint of speed alone) */
+  int box_test = -1;                               /* flx_debug_set_box_test: the frame kernels' box test, -1 by walk_thick_boxes, 0 the cross-pair form, 1 the single comparison */
   DeviceBuffer<float4> d_fwd;                      /* the live entries in the reference's order (every successor further on): primary walk, lockstep walk */
   uint32_t fwd_entries = 0, fwd_root = 0, lock_boxes = 0;
   int last_organisation = 0;                     /* flx_last_organisation: what launch_wavefront ran for the last frame (0: another pipeline) */

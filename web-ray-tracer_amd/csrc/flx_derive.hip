@@ -2,7 +2,7 @@
  * flx_derive.hip — flx_scene_upload_device's kernels: what flx_scene_upload decides and derives on the host (flx_scene.hip: its loop over the entries,
  * build_threaded, build_lockstep), decided and derived from an entry array that is in device memory.
  *
- *   k_derive_check      a lane per entry: the host loop's refusals as the least key entry * 4 + rule, max_transform, has_nan, bounded, the counts of boxes and
+ *   k_derive_check      a lane per entry: the host loop's refusals as the least key entry * 4 + rule, max_transform, has_nan, bounded, thick, the counts of boxes and
  *                       of live (non-terminator) entries; meta = type | transform << 2 per entry; and the depth's differences: +1 at i, -1 at i + skip of box i
  *   scans               an exclusive scan over (difference, live) gives (depth, rank among the live entries) per entry: depth[i] = the boxes j < i with
  *                       j + skip_j >= i, which is what build_threaded's stack holds at entry i of a properly nested list
@@ -36,7 +36,7 @@ constexpr uint32_t BINS_PER_THREAD = 17;           /* 256 * 17 >= BINS */
 constexpr uint32_t HIST_GRID = 256;
 
 /* the record (DERIVE_RECORD_WORDS): see flx_kernels.h */
-enum { REC_VERDICT = 0, REC_MAX_TRANSFORM, REC_HAS_NAN, REC_UNBOUNDED, REC_BOXES, REC_LIVE, REC_META0 };
+enum { REC_VERDICT = 0, REC_MAX_TRANSFORM, REC_HAS_NAN, REC_UNBOUNDED, REC_BOXES, REC_LIVE, REC_META0, REC_FLAT };
 /* the threshold: d*, r, hot, entries below d* */
 enum { HP_DEPTH = 0, HP_TAKE, HP_HOT, HP_BELOW };
 
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(DB) void k_derive_check(const float4 *__restrict__ 
                                                      uint2 *__restrict__ x) {
   const uint32_t i = blockIdx.x * DB + threadIdx.x;
   uint32_t notKey = 0u, transform = 0u;
-  bool nan = false, unbounded = false, box = false, live = false;
+  bool nan = false, unbounded = false, flat = false, box = false, live = false;
   if (i < n) {
     const float4 g0 = geometry[(size_t)i * 3], g1 = geometry[(size_t)i * 3 + 1], g2 = geometry[(size_t)i * 3 + 2];
     const float kind = g2.z;
@@ -114,6 +114,7 @@ __global__ __launch_bounds__(DB) void k_derive_check(const float4 *__restrict__ 
     if (box) {
 #pragma unroll
       for (int k = 0; k < 6; k++) unbounded = unbounded || !(fabsf(w[k]) <= FLX_FAST_BOX_BOUND);
+      flat = !(w[0] < w[3] && w[1] < w[4] && w[2] < w[5]);      /* (flx_scene.hip: box_is_thick) */
     }
     const uint32_t m = !live ? 0u : (box ? 1u : 2u) | transform << 2;
     meta[i] = m;
@@ -132,13 +133,14 @@ __global__ __launch_bounds__(DB) void k_derive_check(const float4 *__restrict__ 
     notKey = max(notKey, (uint32_t)__shfl_xor((int)notKey, d));
     transform = max(transform, (uint32_t)__shfl_xor((int)transform, d));
   }
-  const bool anyNan = __any(nan), anyUnbounded = __any(unbounded);
+  const bool anyNan = __any(nan), anyUnbounded = __any(unbounded), anyFlat = __any(flat);
   const uint32_t boxes = (uint32_t)__popcll(__ballot(box)), lives = (uint32_t)__popcll(__ballot(live));
   if ((threadIdx.x & 63u) == 0u) {
     if (notKey) atomicMax(&record[REC_VERDICT], notKey);
     if (transform) atomicMax(&record[REC_MAX_TRANSFORM], transform);
     if (anyNan) atomicOr(&record[REC_HAS_NAN], 1u);
     if (anyUnbounded) atomicOr(&record[REC_UNBOUNDED], 1u);
+    if (anyFlat) atomicOr(&record[REC_FLAT], 1u);
     if (boxes) atomicAdd(&record[REC_BOXES], boxes);
     if (lives) atomicAdd(&record[REC_LIVE], lives);
   }

@@ -77,6 +77,8 @@ struct DeviceScene {
   uint32_t n_entries;           /* padded entry count = loop bound (fragment:181-184) */
   uint32_t n_lights;
   uint32_t n_transforms;
+  uint32_t walk_thick_boxes;    /* (of the threaded copy below; here, in what was padding in front of its pointer: the struct's layout and every kernel's arguments stay as they were)
+                                 * 1: every AABB has min < max on all three axes — a hint of speed alone: the frame kernels take rayCuboidInterval<true> (launch_wavefront, launch_server) */
   /* Threaded copy of the skip list for the walk kernels (built at upload, flx_api.hip: build_threaded):
    * same entries, same logical visit order, but every entry names its successors explicitly, so the
    * array can be stored hot-first (shallow tree levels in front) and its prefix staged in LDS. */
@@ -588,6 +590,9 @@ FLX_DEV void bounceShade(const DeviceScene &sc, const DeviceFrame &fr, PixelStat
   shadeSample(sc, fr, sf, ps, p, camera, cosSampleN, i, so);
 }
 
+#ifndef FLX_BOX_FALLBACK_COUNT
+#define FLX_BOX_FALLBACK_COUNT 0   /* 1: a measuring build — the frame kernel's lanes tally their box tests and those that took the exact quotients (tail diagnostics word 19) */
+#endif
 /* State of one skip-list walk, advanced one entry per walkStep(): the loop bodies of rayTracer
  * (fragment:184-224) and shadowTest (fragment:240-277) with their loop variables made explicit so
  * that a lane can suspend / resume a walk and the scheduler above can refill idle lanes. */
@@ -603,6 +608,9 @@ struct WalkState {
   int tri, hitTI;     /* entry index (-1: none) and 2 * transform number of the closest hit */
   f3 inv;             /* RN(1 / tR.dir), for the threaded walk's box test */
   bool fastDiv;       /* tR is in the range where divByRecip() is proven exact */
+#if FLX_BOX_FALLBACK_COUNT
+  mutable uint32_t boxTests, boxExact;      /* (the frame kernel initialises and reads them; other callers of rayCuboidFast count into words nobody reads) */
+#endif
 };
 
 FLX_DEV void walkStart(WalkState &w, int mode, const Ray &ray, float len) {
@@ -736,7 +744,7 @@ FLX_DEV bool rayCuboidRecip(float l, const WalkState &w, f3 minCorner, f3 maxCor
 /* Primary visibility (the walk of fragment:172-227 with the primary triangle rule) over the threaded copy: explicit successors, stored edges, the box test through the
  * exact reciprocal division.  The entries a ray visits, their order, the arithmetic of every test and the visit count are
  * those of the shader's loop; a pixel's ray changes object space a few times per walk, so that is done in place. */
-FLX_DEV bool rayCuboidFast(float l, const WalkState &w, f3 lo, f3 hi);      /* below: the interval test with the exact quotients as its fallback */
+template <bool THICK = false> FLX_DEV bool rayCuboidFast(float l, const WalkState &w, f3 lo, f3 hi);      /* below: the interval test with the exact quotients as its fallback; THICK: its form for scenes without a flat box */
 FLX_DEV Hit primaryWalkT(const DeviceScene &sc, const Ray &ray, float viewDepthPerS, uint32_t &visits) {
   Hit hit; hit.suv = F3(0.0f, 0.0f, 0.0f); hit.transformId = 0; hit.triangleId = -1;
   WalkState w;
@@ -1121,10 +1129,23 @@ FLX_DEV bool walkArriveP(const float2 *rays, WalkState &w, const WalkEntry &cur,
  *   sure FALSE  hi(tmax') < max(lo(tmin'), BIAS), or lo(tmin') >= l.
  * Anything else — a ray grazing an edge within 2^-21, a direction outside the range, l below 2^-60 — is `unsure` and the caller
  * takes the exact quotients (rayCuboidRecip).  Same boolean as the shader in every case; ~40 instead of ~61 VALU instructions
- * per box test and a dependent chain of 7 instead of 10 (profiles/r02_ab_box_interval.txt). */
+ * per box test and a dependent chain of 7 instead of 10 (profiles/r02_ab_box_interval.txt).
+ *
+ * THICK: the form for scenes none of whose boxes is flat (DeviceScene::walk_thick_boxes).  The three cross pairs give way to ONE
+ * comparison of two values the other conjuncts compute anyway:
+ *   sure TRUE   lo(tmax') >= hi(tmin'), and lo(tmax') >= BIAS, and hi(tmin') < l.
+ * It suffices for ANY box: lo(tmax') <= tmax and tmin <= hi(tmin') (the brackets above), so lo(tmax') >= hi(tmin') gives
+ * tmax >= tmin, which with tmax >= lo(tmax') >= BIAS is the shader's tmax >= max(tmin, BIAS).  (Where tmin' is below 2^-126 the
+ * bracket is off by 2^-149 at most, and tmax >= BIAS lies far above either value.)  It is stronger than the cross pairs: it also
+ * asks the two planes of ONE axis for room, which monotonicity gave for nothing.  A flat box has none: its two quotients on the
+ * flat axis are one value q, so tmax' <= q <= tmin' and lo(tmax') <= tmax' <= tmin' <= hi(tmin'), with equality only where all are
+ * zero or denormal (the FMA rounds back to x), below BIAS.  A flat box is never sure TRUE: every ray that hits it takes the exact quotients — right, but slow.  Sure FALSE and the guards are
+ * the same in both forms, and what is not sure is decided exactly, so the form chosen never changes the boolean: thickness is a
+ * hint of speed alone (6 FMA, 2 maxima and 3 comparisons fewer per test; profiles/box_single_comparison.txt). */
 #ifndef FLX_WF_BOX_INTERVAL
 #define FLX_WF_BOX_INTERVAL 1
 #endif
+template <bool THICK = false>
 FLX_DEV bool rayCuboidInterval(float l, const WalkState &w, f3 minCorner, f3 maxCorner, bool &sure) {
   const f3 o = w.tR.origin, y = w.inv;
   const float qx0 = (minCorner.x - o.x) * y.x, qx1 = (maxCorner.x - o.x) * y.x;
@@ -1134,24 +1155,28 @@ FLX_DEV bool rayCuboidInterval(float l, const WalkState &w, f3 minCorner, f3 max
   const float ny = __builtin_fminf(qy0, qy1), fy = __builtin_fmaxf(qy0, qy1);
   const float nz = __builtin_fminf(qz0, qz1), fz = __builtin_fmaxf(qz0, qz1);
   constexpr float D = 4.76837158203125e-07f;           /* 2^-21 */
-  const float nyz = __builtin_fmaxf(ny, nz), nxz = __builtin_fmaxf(nx, nz), nxy = __builtin_fmaxf(nx, ny);
+  const float nyz = __builtin_fmaxf(ny, nz), nxz = __builtin_fmaxf(nx, nz), nxy = __builtin_fmaxf(nx, ny);      /* (THICK: nyz and nxz are not used) */
   const float tmin = __builtin_fmaxf(nxy, nz), tmax = __builtin_fminf(__builtin_fminf(fx, fy), fz);
   /* (bitwise & and |, not && and ||: straight-line code, the wave would execute both sides of a branch anyway) */
-  const bool cx = __builtin_fmaf(-flx_abs(fx), D, fx) >= __builtin_fmaf(flx_abs(nyz), D, nyz);
-  const bool cy = __builtin_fmaf(-flx_abs(fy), D, fy) >= __builtin_fmaf(flx_abs(nxz), D, nxz);
-  const bool cz = __builtin_fmaf(-flx_abs(fz), D, fz) >= __builtin_fmaf(flx_abs(nxy), D, nxy);
+  const bool cx = THICK || __builtin_fmaf(-flx_abs(fx), D, fx) >= __builtin_fmaf(flx_abs(nyz), D, nyz);      /* (THICK is a constant: no branch, and the statements' order is the cross-pair form's) */
+  const bool cy = THICK || __builtin_fmaf(-flx_abs(fy), D, fy) >= __builtin_fmaf(flx_abs(nxz), D, nxz);
+  const bool cz = THICK || __builtin_fmaf(-flx_abs(fz), D, fz) >= __builtin_fmaf(flx_abs(nxy), D, nxy);
   const float tminHi = __builtin_fmaf(flx_abs(tmin), D, tmin), tminLo = __builtin_fmaf(-flx_abs(tmin), D, tmin);
   const float tmaxHi = __builtin_fmaf(flx_abs(tmax), D, tmax), tmaxLo = __builtin_fmaf(-flx_abs(tmax), D, tmax);
-  const bool sureTrue = cx & cy & cz & (tmaxLo >= BIAS) & (tminHi < l);
+  const bool sureTrue = (THICK ? tmaxLo >= tminHi : cx & cy & cz) & (tmaxLo >= BIAS) & (tminHi < l);
   const bool sureFalse = (tmaxHi < __builtin_fmaxf(tminLo, BIAS)) | (tminLo >= l);
   sure = w.fastDiv & (l >= 8.673617379884035e-19f) & (sureTrue | sureFalse);      /* (NaN anywhere: every comparison false, unsure) */
   return sureTrue;
 }
 /* rayCuboid's boolean: from the interval test where it is sure, from the exact quotients where some lane of the wave is not */
+template <bool THICK>
 FLX_DEV bool rayCuboidFast(float l, const WalkState &w, f3 lo, f3 hi) {
 #if FLX_WF_BOX_INTERVAL
   bool sure;
-  bool hit = rayCuboidInterval(l, w, lo, hi, sure);
+  bool hit = rayCuboidInterval<THICK>(l, w, lo, hi, sure);
+#if FLX_BOX_FALLBACK_COUNT
+  w.boxTests++; if (!sure) w.boxExact++;
+#endif
 #ifndef FLX_BOX_UNSURE_BALLOT
 #define FLX_BOX_UNSURE_BALLOT 0
 #endif
@@ -1168,8 +1193,9 @@ FLX_DEV bool rayCuboidFast(float l, const WalkState &w, f3 lo, f3 hi) {
   return rayCuboidRecip(l, w, lo, hi);
 #endif
 }
+template <bool THICK = false>
 FLX_DEV void walkBoxP(WalkState &w, const WalkEntry &cur) {
-  const bool hit = rayCuboidFast(w.minLen, w, F3(cur.e0.x, cur.e0.y, cur.e0.z), F3(cur.e0.w, cur.e1.x, cur.e1.y));
+  const bool hit = rayCuboidFast<THICK>(w.minLen, w, F3(cur.e0.x, cur.e0.y, cur.e0.z), F3(cur.e0.w, cur.e1.x, cur.e1.y));
   w.i = hit ? __float_as_int(cur.e2.x) : __float_as_int(cur.e2.y);
 }
 

@@ -358,12 +358,13 @@ FLX_DEV void walkLaneSwitch(WalkLane &L) {                  /* the shadow walk i
   }
 }
 /* One entry for a walking lane: the test its entry asks for, then the entry its link names.  (A macro, not a function: as an inlined function the same statements cost
- * the frame kernel's stepping loop six more instructions per trip — two register copies and four mask operations — and the dragon frame 2.4 %: 6.40 -> 6.56 ms.) */
-#define FLX_WALK_LANE_STEP(COUNT_, walkG_, ldsEntries_, ldsCount_, myRays_, L_, cnt_)                                              \
+ * the frame kernel's stepping loop six more instructions per trip — two register copies and four mask operations — and the dragon frame 2.4 %: 6.40 -> 6.56 ms.)
+ * THICK_: the box test's form for a scene without a flat box (rayCuboidInterval<true>, DeviceScene::walk_thick_boxes), a compile-time choice of the kernel launched. */
+#define FLX_WALK_LANE_STEP(COUNT_, THICK_, walkG_, ldsEntries_, ldsCount_, myRays_, L_, cnt_)                                      \
   do {                                                                                                                           \
     if ((L_).st == P_WALKING) {                                                                                                  \
       bool ended_ = false;                                                                                                       \
-      if (FLX_WF_LINK_ISBOX ? walkIsBoxL((L_).w) : walkIsBoxT((L_).cur)) walkBoxP((L_).w, (L_).cur); else ended_ = walkTriT((L_).w, (L_).cur);                             \
+      if (FLX_WF_LINK_ISBOX ? walkIsBoxL((L_).w) : walkIsBoxT((L_).cur)) walkBoxP<THICK_>((L_).w, (L_).cur); else ended_ = walkTriT((L_).w, (L_).cur);                             \
       if (!ended_) ended_ = walkFetchG<COUNT_>(walkG_, ldsEntries_, ldsCount_, myRays_, (L_).w, (L_).cur, cnt_);                 \
       if (ended_) (L_).st = ((L_).w.mode == 0) ? P_SWITCH : P_DONE;                                                              \
     }                                                                                                                            \

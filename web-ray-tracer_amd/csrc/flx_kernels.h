@@ -82,7 +82,7 @@ bool wavefront_front_in_kernel(const DeviceScene &sc, const DeviceFrame &fr, uin
  * kernels' dynamic LDS limit could not be raised on this device */
 /* What a walk launch staged of the tree's top (flx_debug_last_walk_lds): the ldsCount it was given, whether its rays are pre-transformed, and which launch it was
  * (1 rounds, 2 the frame kernel, 3 the frame kernel with the front inside, 4 the frame server) */
-struct WalkLdsLaunch { uint32_t ldsCount = 0, pre = 0, kind = 0, nTransforms = 0; };
+struct WalkLdsLaunch { uint32_t ldsCount = 0, pre = 0, kind = 0, nTransforms = 0; int boxTest = -1; };      /* boxTest: the box test compiled into the frame kernel or server kernel launched, 0 cross pairs, 1 single comparison; -1: none of them ran */
 int launch_wavefront(const DeviceScene &sc, const DeviceFrame &fr, const WavefrontBuffers &wb, uint32_t compute_units, bool count,
                      int organisation, hipEvent_t walk0_begin, hipEvent_t walk0_end, hipStream_t stream, WalkLdsLaunch *ran = nullptr);
 /* denoise chain (flx_filter.hip): 13 RGBA8 planes = the reference's RenderTexture[0..3], IpRenderTexture[0..3],
@@ -132,7 +132,8 @@ void launch_rederive(const float4 *geometry, uint32_t n_entries, float4 *copy, u
 /* flx_scene_upload_device (flx_derive.hip): flx_scene_upload's decisions and both derived copies from an entry array in device memory.  work: derive_workspace_words(n_entries)
  * words, the record in its first DERIVE_RECORD_WORDS.  launch_derive_check fills the record: [0] 0 where no entry offends, else ~(entry * 4 + rule) of the first entry
  * the host's loop refuses and its first rule there (0 transform number out of range, 1 skip count leaves the array, 2 type not 0, 1 or 2); [1] max_transform;
- * [2] a triangle has a NaN vertex; [3] a box coordinate is not finite or beyond 2^59; [4] boxes; [5] live (non-terminator) entries; [6] entry 0's meta word.
+ * [2] a triangle has a NaN vertex; [3] a box coordinate is not finite or beyond 2^59; [4] boxes; [5] live (non-terminator) entries; [6] entry 0's meta word;
+ * [7] a box is flat: not min < max on all three axes (a NaN corner included).
  * It touches the workspace alone.  launch_derive_copies, for an array that passed: walk <- build_threaded's copy (live + 1 entries, min(4096, live) + 1 of them hot),
  * fwd <- build_lockstep's (live + 1), bit for bit for a properly nested skip list; no kernel waits for another workgroup, every scan is a launch per level and
  * recurses on its block totals: any entry count flx_scene_upload takes. */

@@ -714,14 +714,14 @@ __global__ void k_debug_intersect(int fn, const float *__restrict__ in, float *_
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   DeviceScene sc = {};
-  sc.walk_fast_boxes = fn == 6 ? 0u : 1u;                     /* fn 2: the caller's rows keep the precondition of the reciprocal box test (flx_scene_upload's bound); fn 6: a scene that does not */
-  if (fn == 2 || fn == 5 || fn == 6) {                                   /* rayCuboid: l, origin, dir, min, max */
+  sc.walk_fast_boxes = (fn == 6 || fn == 8) ? 0u : 1u;                     /* fn 2: the caller's rows keep the precondition of the reciprocal box test (flx_scene_upload's bound); fn 6: a scene that does not */
+  if (fn == 2 || fn >= 5) {                                              /* rayCuboid: l, origin, dir, min, max */
     const float *r = in + (size_t)i * 13u;
     WalkState w;
     w.tR.origin = F3(r[1], r[2], r[3]); w.tR.dir = F3(r[4], r[5], r[6]);
     reciprocalOfDir(sc, w.tR.dir, w.tR.origin, w.inv, w.fastDiv);
     const f3 lo = F3(r[7], r[8], r[9]), hi = F3(r[10], r[11], r[12]);
-    out[i] = (fn != 5 ? rayCuboidFast(r[0], w, lo, hi) : rayCuboid(r[0], w.tR, lo, hi)) ? 1.0f : 0.0f;
+    out[i] = (fn >= 7 ? rayCuboidFast<true>(r[0], w, lo, hi) : fn != 5 ? rayCuboidFast(r[0], w, lo, hi) : rayCuboid(r[0], w.tR, lo, hi)) ? 1.0f : 0.0f;      /* fn 7, 8: fn 2, 6 in the form for scenes without a flat box */
     return;
   }
   const float *r = in + (size_t)i * 16u;                      /* triangles: a, b, c, origin, dir, l */
@@ -778,7 +778,8 @@ __global__ __launch_bounds__(64) void k_debug_walk(DeviceScene sc, const float *
       reciprocalOfDir(sc, ray.dir, ray.origin, w.inv, w.fastDiv);
       bool ended = !have || walkFetchP<true>(sc, nullptr, 0u, myRays, w, cur, cnt);
       while (!ended) {
-        if (walkIsBoxT(cur)) walkBoxP(w, cur); else ended = walkTriT(w, cur);
+        if (walkIsBoxT(cur)) { if (sc.walk_thick_boxes != 0u) walkBoxP<true>(w, cur); else walkBoxP(w, cur); }      /* (the form the frame kernels would take: flx_debug_set_box_test) */
+        else ended = walkTriT(w, cur);
         if (!ended) ended = walkFetchP<true>(sc, nullptr, 0u, myRays, w, cur, cnt);
       }
       if (shadowMode) shadowed = w.shadowed != 0;
@@ -838,7 +839,8 @@ __global__ __launch_bounds__(64) void k_debug_walk_staged(DeviceScene sc, uint32
       if (!ended && linkKind((uint32_t)w.i) != 3u) { if (linkIndex((uint32_t)w.i) < ldsCount) fromLds++; else fromGlobal++; }      /* (the loop bound: no fetch) */
       if (!ended) ended = walkFetchP<true>(sc, ldsEntries, ldsCount, myRays, w, cur, cnt);
       if (ended) break;
-      if (walkIsBoxT(cur)) walkBoxP(w, cur); else ended = walkTriT(w, cur);
+      if (walkIsBoxT(cur)) { if (sc.walk_thick_boxes != 0u) walkBoxP<true>(w, cur); else walkBoxP(w, cur); }      /* (as k_debug_walk<0>) */
+      else ended = walkTriT(w, cur);
       if (ended) break;
     }
     if (shadowMode) shadowed = w.shadowed != 0;

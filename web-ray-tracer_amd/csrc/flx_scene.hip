@@ -247,7 +247,16 @@ static bool rows_on_device(const flx_context *ctx, const void *p, size_t bytes) 
 struct SceneFacts {
   uint32_t max_transform = 0, walk_entries = 0, walk_hot = 0, walk_root = 0, fwd_entries = 0, fwd_root = 0, lock_boxes = 0;
   bool has_nan = false, bounded = true;          /* a triangle has a NaN vertex (no updates then: flx_context.h); the precondition of the walk's fast box test holds */
+  bool thick = true;                             /* no box is flat (box_is_thick): the frame kernels' box test may take its single-comparison form */
 };
+
+/* A box with room between its two planes on every axis (words 0..2 min, 3..5 max); a NaN corner or min > max has none.  What the scene's walk_thick_boxes asks of every box. */
+static bool box_is_thick(const float *e) { return e[0] < e[3] && e[1] < e[4] && e[2] < e[5]; }
+extern "C" int flx_debug_boxes_thick(const float *geometry, uint32_t n_entries) {
+  if (!geometry) return 0;
+  for (uint32_t i = 0; i < n_entries; i++) if (geometry[(size_t)i * 12 + 10] == 1.0f && !box_is_thick(geometry + (size_t)i * 12)) return 0;
+  return 1;
+}
 
 /* Why an entry array is refused, in the order the host's loop meets the rules within an entry; the values are k_derive_check's rule numbers. */
 enum UploadRule { UPLOAD_RULE_TRANSFORM, UPLOAD_RULE_SKIP, UPLOAD_RULE_TYPE };
@@ -267,6 +276,7 @@ static flx_status upload_refused(flx_context *ctx, const void *geometry, const v
 static void begin_scene(flx_context *ctx) { ctx->have_scene = false; ctx->last_walk_lds = WalkLdsLaunch(); ctx->geometry_version++; }
 static void adopt_scene(flx_context *ctx, uint32_t n_entries_padded, uint32_t n_ids, const SceneFacts &f) {
   ctx->walk_entries = f.walk_entries; ctx->walk_hot = f.walk_hot; ctx->walk_root = f.walk_root; ctx->walk_fast_boxes = f.bounded ? 1u : 0u;
+  ctx->walk_thick_boxes = f.thick ? 1u : 0u;
   ctx->fwd_entries = f.fwd_entries; ctx->fwd_root = f.fwd_root; ctx->lock_boxes = f.lock_boxes;
   ctx->lock_ok = f.max_transform == 0 && f.fwd_entries <= FLX_LOCK_MAX;
   ctx->n_entries = n_entries_padded; ctx->n_ids = n_ids; ctx->max_transform = f.max_transform; ctx->scene_has_nan = f.has_nan;
@@ -293,6 +303,7 @@ extern "C" flx_status flx_scene_upload(flx_context *ctx, const float *geometry, 
       float skip = e[6];
       if (!(skip >= 0.0f) || (double)i + (double)skip >= (double)n_entries_padded) return fail(ctx, FLX_ERR_INVALID, SCENE_UPLOAD_REFUSAL[UPLOAD_RULE_SKIP]);
       for (int k = 0; k < 6; k++) if (!(std::fabs(e[k]) <= FLX_FAST_BOX_BOUND)) facts.bounded = false;
+      if (!box_is_thick(e)) facts.thick = false;
     } else if (e[10] != 0.0f && e[10] != 2.0f) {
       return fail(ctx, FLX_ERR_INVALID, SCENE_UPLOAD_REFUSAL[UPLOAD_RULE_TYPE]);
     }
@@ -326,7 +337,7 @@ extern "C" flx_status flx_scene_upload(flx_context *ctx, const float *geometry, 
 static flx_status derive_and_adopt(flx_context *ctx, uint32_t n_entries_padded, uint32_t n_ids, const uint32_t *rec, hipEvent_t checked) {
   const uint32_t live = rec[5], meta0 = rec[6];
   SceneFacts facts;
-  facts.max_transform = rec[1]; facts.has_nan = rec[2] != 0u; facts.bounded = rec[3] == 0u; facts.lock_boxes = rec[4];
+  facts.max_transform = rec[1]; facts.has_nan = rec[2] != 0u; facts.bounded = rec[3] == 0u; facts.lock_boxes = rec[4]; facts.thick = rec[7] == 0u;
   /* both copies hold the live entries and one shared terminator; entry 0 is the shallowest entry with the lowest index: hot, the threaded copy's entry 1 */
   facts.walk_entries = facts.fwd_entries = live + 1u; facts.walk_hot = std::min(live, HOT_MAX) + 1u;
   facts.walk_root = meta0 == 0u ? 0u : 1u | (meta0 & 3u) << LINK_KIND_SHIFT | ((meta0 >> 2) != 0u ? LINK_XFORM : 0u);
@@ -396,7 +407,7 @@ static flx_status check_assembled(flx_context *ctx, const float4 *geometry, uint
  *   2. on the context's stream, behind the frames in flight (they read the old arrays to their end): the assembly of both arrays and of the ids into FRESH
  *      memory, and flx_scene_upload's validation of the assembled array (launch_derive_check); the host waits for the stream and the verdict;
  *   3. the refit of every box of the assembled array (only now: it follows skip counts), the check once more for what it says of the refitted boxes (the bounded
- *      flag) and as the base of the derivation; the fresh arrays become the context's, the old ones are freed, and the rest is flx_scene_upload_device's tail.
+ *      and the thick flags) and as the base of the derivation; the fresh arrays become the context's, the old ones are freed, and the rest is flx_scene_upload_device's tail.
  * Until step 3 a refusal has touched the workspaces and the fresh arrays alone, which go with it.  The frame server's launch ends before step 2. */
 extern "C" flx_status flx_scene_splice_device(flx_context *ctx, uint32_t first_entry, uint32_t n_old, uint32_t parent_entry, const void *d_geometry,
                                               const void *d_attributes, uint32_t n_new, const void *d_ids, uint32_t n_new_ids, void *producer_stream) {
@@ -520,6 +531,7 @@ static flx_status commit_rows(flx_context *ctx, uint32_t first_entry, uint32_t n
   if ((s = flx_server_stop(ctx)) || (s = shared_upload_begin(ctx))) return s;          /* (a running frame server reads the scene) */
   ctx->geometry_version++; ctx->scene_version++; ctx->structure_version++;
   if (!bounded) ctx->walk_fast_boxes = 0u;          /* until the next flx_scene_upload: both box tests give the same bits under the precondition */
+  ctx->walk_thick_boxes = 0u;                       /* the refit below makes the boxes on the device and nothing reads them back: not known to be thick (a hint of speed alone), until the next upload */
   if (staged) FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, staged, 0));
   else FLX_HIP(ctx, hipMemcpyAsync(ctx->d_update_rows, ctx->h_update, (size_t)n_entries * 48, hipMemcpyHostToDevice, ctx->stream));
   float4 *const rows = ctx->d_attributes + (size_t)first_entry * 7;

@@ -69,7 +69,8 @@ FLX_DEV const ServerArgs &server_args(FrameArgsP p) {
 /* VER: the scene MOVES — the lights and the transforms travel with the frame (ServerMail::blob: the host posts them with the view).  The launch keeps one version
  * of those arrays per (workgroup, slot): DeviceScene::rotation / shift / lights point at the launch's own version buffer, written by the wave that brings the slot's
  * view into the workgroup and read by that workgroup alone (plain loads: one CU, one vector L1; the inverse transforms of the walk waves go to LDS per slot). */
-template <bool VER>
+/* THICK: the walk lanes' box test in its form for a scene none of whose boxes is flat (flx_device.h: rayCuboidInterval; DeviceScene::walk_thick_boxes, chosen by launch_server) */
+template <bool VER, bool THICK>
 __global__ __launch_bounds__(FLX_WF_WALK_THREADS, FLX_WF_WAVES_PER_EU) void k_wf_server(ServerKernelArgs /* read through kernel_frame_args() */, uint32_t ldsCount, uint32_t nTransforms,
                                                                                      uint32_t shadeWaves, uint32_t readyUnits) {
   const FrameArgsP ab = kernel_frame_args();
@@ -507,7 +508,7 @@ __global__ __launch_bounds__(FLX_WF_WALK_THREADS, FLX_WF_WAVES_PER_EU) void k_wf
     /* ---- FLX_WF_INNER entries for every walking lane (the few scene words the fetch needs are read before the loop) ---- */
     {
 #pragma unroll FLX_WF_UNROLL
-      for (int it = 0; it < FLX_WF_INNER; it++) FLX_WALK_LANE_STEP(false, walkGV, ldsEntriesV, ldsCount, myRays, L, cnt);
+      for (int it = 0; it < FLX_WF_INNER; it++) FLX_WALK_LANE_STEP(false, THICK, walkGV, ldsEntriesV, ldsCount, myRays, L, cnt);
     }
   }
   statAdd(SVS_WALK_TRIPS, statTrips); statAdd(SVS_WALK_LANE_TRIPS, statLaneTrips);
@@ -541,17 +542,22 @@ int launch_server(const DeviceScene &sc, const DeviceFrame &fr, const WavefrontB
   static bool ok[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-  std::call_once(once[dev], [&]() { ok[dev] = hipFuncSetAttribute((const void *)k_wf_server<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-                                              hipFuncSetAttribute((const void *)k_wf_server<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess; });
+  static const void *const kernels[2][2] = { { (const void *)k_wf_server<false, false>, (const void *)k_wf_server<false, true> },
+                                             { (const void *)k_wf_server<true, false>, (const void *)k_wf_server<true, true> } };
+  std::call_once(once[dev], [&]() {
+    ok[dev] = true;
+    for (int k = 0; k < 4; k++) ok[dev] = hipFuncSetAttribute(kernels[k >> 1][k & 1], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess && ok[dev];
+  });
   if (!ok[dev]) return -1;
   ServerKernelArgs ka;
   ka.fa.sc = sc; ka.fa.fr = fr; ka.fa.wb = wb; ka.sa = sa;
   const uint32_t tilesPerGroup = sa.tilesPerSlot / compute_units;
   uint32_t readyUnits = tilesPerGroup >= 48u ? (uint32_t)FLX_FRAME_READY_UNITS : tilesPerGroup / 2u;
   readyUnits = readyUnits < (uint32_t)FLX_FRAME_READY_UNITS / 4u ? (uint32_t)FLX_FRAME_READY_UNITS / 4u : (readyUnits > (uint32_t)FLX_FRAME_READY_UNITS ? (uint32_t)FLX_FRAME_READY_UNITS : readyUnits);
-  if (ver) hipLaunchKernelGGL(k_wf_server<true>, dim3(compute_units), dim3(FLX_WF_WALK_THREADS), ldsBytes, stream, ka, ldsCount, sc.n_transforms, shadeWaves, readyUnits);
-  else hipLaunchKernelGGL(k_wf_server<false>, dim3(compute_units), dim3(FLX_WF_WALK_THREADS), ldsBytes, stream, ka, ldsCount, sc.n_transforms, shadeWaves, readyUnits);
-  if (ran) { ran->ldsCount = ldsCount; ran->pre = 1u; ran->kind = 4u; ran->nTransforms = sc.n_transforms; }
+  uint32_t ldsCountArg = ldsCount, nTransformsArg = sc.n_transforms, shadeWavesArg = shadeWaves;
+  void *args[] = { &ka, &ldsCountArg, &nTransformsArg, &shadeWavesArg, &readyUnits };
+  (void)hipLaunchKernel(kernels[ver ? 1 : 0][sc.walk_thick_boxes != 0u ? 1 : 0], dim3(compute_units), dim3(FLX_WF_WALK_THREADS), args, ldsBytes, stream);
+  if (ran) { ran->ldsCount = ldsCount; ran->pre = 1u; ran->kind = 4u; ran->nTransforms = sc.n_transforms; ran->boxTest = sc.walk_thick_boxes != 0u ? 1 : 0; }
   return 0;
 }
 

@@ -805,7 +805,7 @@ __global__ __launch_bounds__(FLX_WF_WALK_THREADS, FLX_WF_WAVES_PER_EU) void k_wf
 #endif
 /* (the kernel's body: STAMP — the walk lanes stamp what a path cost, the measure of the adaptive tile order — is its own instantiation, because the stamp's few instructions
  * re-roll the register allocation of the whole kernel: whole frames run the unstamped code, k_wf_frame<COUNT, true>, the commit-before's to the instruction) */
-template <bool COUNT, bool FRONT, bool STAMP>
+template <bool COUNT, bool FRONT, bool STAMP, bool THICK>
 __device__ __forceinline__ void wf_frame_body(uint32_t total_items, uint32_t ldsCount, uint32_t nTransforms, uint32_t shadeWaves, uint32_t readyUnits) {
   const uint32_t n = total_items;
   if (n == 0u) return;
@@ -961,6 +961,9 @@ __device__ __forceinline__ void wf_frame_body(uint32_t total_items, uint32_t lds
   long long tBlock = 0, tFoldT = 0, tRefillT = 0, tSetupT = 0, tTrips = 0, tAcqT = 0, tFoldOnlyT = 0; unsigned long long nBlocks = 0, nOuter = 0;      /* COUNT builds: where a walk wave's time goes (flx_get_tail_diag 27..33) */
   WalkLane L;                                                  /* the lane's path and its walks (flx_frame_common.h: one body for every persistent kernel) */
   walkLaneInit(L);
+#if FLX_BOX_FALLBACK_COUNT
+  L.w.boxTests = L.w.boxExact = 0u;
+#endif
   uint32_t chunkNext = 0, chunkEnd = 0;
   bool itemsLeft = true;
   uint32_t idleSpins = 0;
@@ -1152,12 +1155,15 @@ __device__ __forceinline__ void wf_frame_body(uint32_t total_items, uint32_t lds
     const long long tT0 = COUNT ? clock64() : 0;
     {
 #pragma unroll FLX_WF_UNROLL
-      for (int it = 0; it < FLX_WF_INNER; it++) FLX_WALK_LANE_STEP(COUNT, FLX_FETCH_G, FLX_FETCH_L, ldsCount, myRays, L, cnt);
+      for (int it = 0; it < FLX_WF_INNER; it++) FLX_WALK_LANE_STEP(COUNT, THICK, FLX_FETCH_G, FLX_FETCH_L, ldsCount, myRays, L, cnt);
     }
     if (COUNT) tTrips += clock64() - tT0;
   }
   FLX_FRAME_ARGS();
   if (COUNT && (cnt.closest_visits | cnt.shadow_visits) != 0u) atomicAdd(wb.counters + 23, (unsigned long long)cnt.closest_visits + cnt.shadow_visits);
+#if FLX_BOX_FALLBACK_COUNT
+  if (COUNT && wave < WALK_WAVES) atomicAdd(wb.counters + 59, (unsigned long long)L.w.boxTests | (unsigned long long)L.w.boxExact << 32);      /* (a frame has fewer than 2^32 box tests) */
+#endif
   if (COUNT && lane == 0) {                                     /* wave lifetimes: sum / max / count (flx_get_tail_diag 24..26) */
     const unsigned long long life = (unsigned long long)(clock64() - tStart);
     atomicAdd(wb.counters + 64, life); atomicMax(wb.counters + 65, life); atomicAdd(wb.counters + 66, 1ull);
@@ -1170,16 +1176,37 @@ __device__ __forceinline__ void wf_frame_body(uint32_t total_items, uint32_t lds
 #undef FLX_FETCH_L
 #undef FLX_FRAME_ARGS
 }
+/* The box test of the walk lanes comes in two forms (flx_device.h: rayCuboidInterval), a compile-time choice: k_wf_frame and k_wf_frame_stamped carry the form for a
+ * scene none of whose boxes is flat (DeviceScene::walk_thick_boxes: one comparison where the other form makes three cross-pair ones — a mesh's tree, the dragon), the
+ * kernels named _flat the form that also decides a flat box without the exact quotients.  Same frames, same counters: the forms differ in speed alone. */
 template <bool COUNT, bool FRONT>
 __global__ __launch_bounds__(FLX_WF_WALK_THREADS, FLX_WF_WAVES_PER_EU) void k_wf_frame(FrameArgs /* read through kernel_frame_args() */, uint32_t total_items,
                                                                                     uint32_t ldsCount, uint32_t nTransforms, uint32_t shadeWaves, uint32_t readyUnits) {
-  wf_frame_body<COUNT, FRONT, !FRONT>(total_items, ldsCount, nTransforms, shadeWaves, readyUnits);      /* (front in its own kernel: thin frames, always stamped) */
+  wf_frame_body<COUNT, FRONT, !FRONT, true>(total_items, ldsCount, nTransforms, shadeWaves, readyUnits);      /* (front in its own kernel: thin frames, always stamped) */
+}
+template <bool COUNT, bool FRONT>
+__global__ __launch_bounds__(FLX_WF_WALK_THREADS, FLX_WF_WAVES_PER_EU) void k_wf_frame_flat(FrameArgs /* read through kernel_frame_args() */, uint32_t total_items,
+                                                                                         uint32_t ldsCount, uint32_t nTransforms, uint32_t shadeWaves, uint32_t readyUnits) {
+  wf_frame_body<COUNT, FRONT, !FRONT, false>(total_items, ldsCount, nTransforms, shadeWaves, readyUnits);
 }
 /* the frame kernel with its front inside AND the cost stamps: frames of fewer than FLX_ADAPTIVE_FRONT_MAX_TILES_PER_CU screen tiles per workgroup (a rank's quarter) */
 template <bool COUNT>
 __global__ __launch_bounds__(FLX_WF_WALK_THREADS, FLX_WF_WAVES_PER_EU) void k_wf_frame_stamped(FrameArgs /* read through kernel_frame_args() */, uint32_t total_items,
                                                                                             uint32_t ldsCount, uint32_t nTransforms, uint32_t shadeWaves, uint32_t readyUnits) {
-  wf_frame_body<COUNT, true, true>(total_items, ldsCount, nTransforms, shadeWaves, readyUnits);
+  wf_frame_body<COUNT, true, true, true>(total_items, ldsCount, nTransforms, shadeWaves, readyUnits);
+}
+template <bool COUNT>
+__global__ __launch_bounds__(FLX_WF_WALK_THREADS, FLX_WF_WAVES_PER_EU) void k_wf_frame_stamped_flat(FrameArgs /* read through kernel_frame_args() */, uint32_t total_items,
+                                                                                                 uint32_t ldsCount, uint32_t nTransforms, uint32_t shadeWaves, uint32_t readyUnits) {
+  wf_frame_body<COUNT, true, true, false>(total_items, ldsCount, nTransforms, shadeWaves, readyUnits);
+}
+/* the frame kernel of a launch: which 0 without the front, 1 with it, 2 with it and the cost stamps */
+static const void *frame_kernel(int which, bool count, bool thick) {
+  static const void *const kernels[3][2][2] = {
+    { { (const void *)k_wf_frame_flat<false, false>, (const void *)k_wf_frame<false, false> }, { (const void *)k_wf_frame_flat<true, false>, (const void *)k_wf_frame<true, false> } },
+    { { (const void *)k_wf_frame_flat<false, true>, (const void *)k_wf_frame<false, true> }, { (const void *)k_wf_frame_flat<true, true>, (const void *)k_wf_frame<true, true> } },
+    { { (const void *)k_wf_frame_stamped_flat<false>, (const void *)k_wf_frame_stamped<false> }, { (const void *)k_wf_frame_stamped_flat<true>, (const void *)k_wf_frame_stamped<true> } } };
+  return kernels[which][count ? 1 : 0][thick ? 1 : 0];
 }
 
 /* Can the frame kernel take this frame?  Its LDS holds the rays of its walk threads, the staged transforms, the two rings and
@@ -1235,9 +1262,9 @@ int launch_wavefront(const DeviceScene &sc, const DeviceFrame &fr, const Wavefro
     uint32_t ldsCountF = 0, ldsBytesF = 0;
     if (wb.frameRings != nullptr && frame_kernel_wanted(sc, fr, wb.item_count, organisation, wb.front != 0u, ldsCountF, ldsBytesF) &&
         dynamic_lds_ready(0, []() {
-          return (int)set_lds_limit((const void *)k_wf_frame<true, false>) & (int)set_lds_limit((const void *)k_wf_frame<false, false>) &
-                 (int)set_lds_limit((const void *)k_wf_frame<true, true>) & (int)set_lds_limit((const void *)k_wf_frame<false, true>) &
-                 (int)set_lds_limit((const void *)k_wf_frame_stamped<true>) & (int)set_lds_limit((const void *)k_wf_frame_stamped<false>);
+          bool ok = true;
+          for (int k = 0; k < 12; k++) ok = set_lds_limit(frame_kernel(k >> 2, (k & 1) != 0, (k & 2) != 0)) && ok;
+          return ok;
         })) {
       const uint32_t total = wb.item_count;
       const uint32_t pixels = total / (uint32_t)(fr.samples > 0 ? fr.samples : 1);
@@ -1260,18 +1287,12 @@ int launch_wavefront(const DeviceScene &sc, const DeviceFrame &fr, const Wavefro
 #endif
       uint32_t readyUnits = tilesPerGroup >= 48u ? (uint32_t)FLX_FRAME_READY_UNITS : tilesPerGroup / FLX_FRAME_READY_DIV;
       readyUnits = readyUnits < (uint32_t)FLX_FRAME_READY_UNITS / 4u ? (uint32_t)FLX_FRAME_READY_UNITS / 4u : (readyUnits > (uint32_t)FLX_FRAME_READY_UNITS ? (uint32_t)FLX_FRAME_READY_UNITS : readyUnits);
-      if (wb.front && wb.stampCosts) {
-        if (count) hipLaunchKernelGGL((k_wf_frame_stamped<true>), grid, block, ldsBytesF, stream, fa, total, ldsCountF, sc.n_transforms, shadeWaves, readyUnits);
-        else hipLaunchKernelGGL((k_wf_frame_stamped<false>), grid, block, ldsBytesF, stream, fa, total, ldsCountF, sc.n_transforms, shadeWaves, readyUnits);
-      } else if (wb.front) {
-        if (count) hipLaunchKernelGGL((k_wf_frame<true, true>), grid, block, ldsBytesF, stream, fa, total, ldsCountF, sc.n_transforms, shadeWaves, readyUnits);
-        else hipLaunchKernelGGL((k_wf_frame<false, true>), grid, block, ldsBytesF, stream, fa, total, ldsCountF, sc.n_transforms, shadeWaves, readyUnits);
-      } else {
-        if (count) hipLaunchKernelGGL((k_wf_frame<true, false>), grid, block, ldsBytesF, stream, fa, total, ldsCountF, sc.n_transforms, shadeWaves, readyUnits);
-        else hipLaunchKernelGGL((k_wf_frame<false, false>), grid, block, ldsBytesF, stream, fa, total, ldsCountF, sc.n_transforms, shadeWaves, readyUnits);
-      }
+      /* (one launch statement for the twelve kernels: by address, the arguments in the kernels' order) */
+      uint32_t totalArg = total, ldsCountArg = ldsCountF, nTransformsArg = sc.n_transforms, shadeWavesArg = shadeWaves;
+      void *args[] = { &fa, &totalArg, &ldsCountArg, &nTransformsArg, &shadeWavesArg, &readyUnits };
+      (void)hipLaunchKernel(frame_kernel(wb.front ? (wb.stampCosts ? 2 : 1) : 0, count, sc.walk_thick_boxes != 0u), grid, block, args, ldsBytesF, stream);
       if (walk0_end) (void)hipEventRecord(walk0_end, stream);
-      if (ran) { ran->ldsCount = ldsCountF; ran->pre = 1u; ran->kind = wb.front ? 3u : 2u; ran->nTransforms = sc.n_transforms; }
+      if (ran) { ran->ldsCount = ldsCountF; ran->pre = 1u; ran->kind = wb.front ? 3u : 2u; ran->nTransforms = sc.n_transforms; ran->boxTest = sc.walk_thick_boxes != 0u ? 1 : 0; }
       return wb.front ? 3 : 2;
     }
   }

@@ -31,6 +31,7 @@ EXPORTS = [
     "flx_share_create", "flx_share_join", "flx_share_leave", "flx_frame_begin_shared", "flx_frame_end_shared",
     "flx_render_gathered_rgba8_device", "flx_group_render_rgba8", "flx_debug_set_angle_table", "flx_frame_target_set8", "flx_debug_set_sample_parallel", "flx_debug_last_trace_kernel", "flx_debug_set_tile_order", "flx_debug_tile_cost", "flx_debug_set_adaptive_order", "flx_debug_tile_order_of",
     "flx_raster_render", "flx_debug_walk_staged", "flx_debug_last_walk_lds", "flx_debug_walk_fast_boxes",
+    "flx_debug_walk_thick_boxes", "flx_debug_set_box_test", "flx_debug_boxes_thick", "flx_debug_last_box_test",
     "flx_scene_update", "flx_group_scene_update", "flx_debug_scene_read", "flx_scene_update_device", "flx_scene_upload_device",
     "flx_tree_build_device", "flx_tree_emit_device", "flx_scene_splice_device",
 ]
@@ -172,6 +173,10 @@ def _load():
         "flx_debug_last_trace_kernel": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "flx_debug_walk_staged": (C.c_int, [vp, u32, C.POINTER(C.c_float), C.POINTER(C.c_float), u32]),
         "flx_debug_walk_fast_boxes": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "flx_debug_walk_thick_boxes": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "flx_debug_set_box_test": (C.c_int, [vp, C.c_int]),
+        "flx_debug_last_box_test": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "flx_debug_boxes_thick": (C.c_int, [fp, u32]),
         "flx_debug_last_walk_lds": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_debug_set_adaptive_order": (C.c_int, [vp, C.c_int]),
         "flx_debug_tile_order_of": (C.c_int, [vp, C.POINTER(C.c_float), u32, C.c_int, C.POINTER(u32)]),
@@ -237,6 +242,12 @@ def _device_array(x, dtype_name, width, device, what):
     if x.device.type != "cuda" or x.device.index != device:
         raise ValueError("upload_scene_device: %s is on %s, the context on cuda:%d" % (what, x.device, device))
     return x.data_ptr(), x.shape[0]
+
+
+def boxes_thick(geometry):
+    """flx_debug_boxes_thick: whether every box row (word 10 == 1) of geometry [n, 12] float32 has min < max on all three axes — flx_scene_upload's scan, no GPU"""
+    geometry = np.ascontiguousarray(geometry, np.float32).reshape(-1, 12)
+    return int(LIB.flx_debug_boxes_thick(_fp(geometry), geometry.shape[0]))
 
 
 class Context:
@@ -668,7 +679,7 @@ class Context:
         self._check(LIB.flx_temporal_reset(self._h), "flx_temporal_reset")
 
     def debug_intersect(self, fn, rows):
-        """flx_debug_intersect: rows [n, 16] (triangles: fn 0, 1, 3, 4) or [n, 13] (boxes: fn 2, 5; 6: fn 2 with walk_fast_boxes off) float32 -> [n, 3] (fn 0, 3) or [n] float32"""
+        """flx_debug_intersect: rows [n, 16] (triangles: fn 0, 1, 3, 4) or [n, 13] (boxes: fn 2, 5; 6: fn 2 with walk_fast_boxes off; 7, 8: fn 2, 6 in the single-comparison form) float32 -> [n, 3] (fn 0, 3) or [n] float32"""
         rows = np.ascontiguousarray(rows, np.float32)
         n = rows.shape[0]
         out = np.zeros((n, 3) if fn in (0, 3) else (n,), np.float32)
@@ -679,6 +690,22 @@ class Context:
         """flx_debug_walk_fast_boxes: 1 when every box coordinate of the uploaded scene is finite with |x| <= 2^59 (the walk kernels' reciprocal box test is allowed), else 0"""
         out = C.c_int(-1)
         self._check(LIB.flx_debug_walk_fast_boxes(self._h, C.byref(out)), "flx_debug_walk_fast_boxes")
+        return out.value
+
+    def walk_thick_boxes(self):
+        """flx_debug_walk_thick_boxes: 1 when every box of the uploaded scene is known to have min < max on all three axes (the frame kernels' box test takes its single-comparison form), else 0"""
+        out = C.c_int(-1)
+        self._check(LIB.flx_debug_walk_thick_boxes(self._h, C.byref(out)), "flx_debug_walk_thick_boxes")
+        return out.value
+
+    def set_box_test(self, form):
+        """flx_debug_set_box_test: the frame kernels' box test, -1 by the scene's walk_thick_boxes, 0 the cross-pair form, 1 the single comparison (same results)"""
+        self._check(LIB.flx_debug_set_box_test(self._h, int(form)), "flx_debug_set_box_test")
+
+    def last_box_test(self):
+        """flx_debug_last_box_test: the box test of the kernel the last frame kernel / frame server launch ran, 0 cross pairs, 1 single comparison; -1 none"""
+        out = C.c_int(-2)
+        self._check(LIB.flx_debug_last_box_test(self._h, C.byref(out)), "flx_debug_last_box_test")
         return out.value
 
     def debug_walk(self, variant, rays):
