@@ -240,6 +240,42 @@ flx_status flx_scene_splice_device(flx_context *ctx, uint32_t first_entry, uint3
                                    const void *d_geometry /* n_new * 12 floats, on ctx's device */, const void *d_attributes /* n_new * 28 floats */, uint32_t n_new,
                                    const void *d_ids /* n_new_ids int32, relative to the block's first entry, or NULL */, uint32_t n_new_ids,
                                    void *producer_stream /* hipStream_t that wrote the arrays, or NULL: complete */);
+/* ---- ray queries ---------------------------------------------------------------------------------- */
+/* Beyond the drop-in boundary, like the vertex updates above, and bound the same way (the N-API addon and the JavaScript renderers bind the host call: castRays).
+ * Rays of the CALLER'S OWN cast at the resident scene: what does this ray hit, is this point lit from there, which object is under the cursor — what every frame asks
+ * through rayTracer and shadowTest, answered by the same walk (the threaded hot-first copy, its top in LDS, lanes refilled as their walks end: csrc/flx_query.hip)
+ * with the oracle's bits.
+ * A RAY ROW is 32 bytes, two 16-byte loads: words 0..2 the origin, 3 `l` (shadowTest's length; unused otherwise), 4..6 the direction, 7 ignored.  The closest-hit
+ * walk starts at the reference's minLen (POW32), as rayTracer does: it takes no length.
+ * A HIT ROW is 32 bytes, two 16-byte vector stores: words 0..2 float s, u, v of the closest hit; 3 int32 its entry index, -1 for none; 4 int32 2 x its transform
+ * number; 5 int32 occluded, 0 or 1; 6 uint32 the entries the closest-hit walk fetched, 7 uint32 those the shadow walk fetched.  A miss has zeros in words 0..2 and
+ * 4 and -1 in word 3 (flx_debug_walk's columns); a walk that was not asked for leaves zeros in its words (-1 in word 3); words 6 and 7 are zero without
+ * FLX_RAYS_COUNT.  With both walks asked for a ray's shadow walk runs first, in a path's order.
+ * s is a WORLD-SPACE parameter of the ray as given: the direction is not normalised, the hit point is origin + s * direction.  FLX_RAYS_OCCLUDED is the renderer's
+ * own predicate with its quirks: one-sided, and `l` is compared in object space after the transformed direction was normalised — it
+ * answers "would the renderer light this point", not a geometric any-hit.
+ * flx_rays_cast_device is ordered like flx_render_device: enqueued on the context's stream with no wait of the host (flx_sync before the hits are read on another
+ * stream), behind every upload, update, splice and frame enqueued before it — it sees the scene as of the call — and frames in flight finish unchanged.  Where the
+ * frame server's launch is running it does what flx_render_device does: the launch ends after the frames posted to it, which are resolved into their output slots
+ * (the host waits for that, and only then).  producer_stream: the hipStream_t on which the rays were written — the query waits for what is enqueued there at the
+ * time of the call — or NULL: they are complete (as for flx_scene_update_device).  The caller keeps both arrays alive until the work is complete.  n == 0: FLX_OK,
+ * nothing enqueued (the scene and `what` are looked at first: no scene or a bad `what` is refused for any n).  flx_rays_cast is the same for host arrays: staged through memory the context owns (grown, never shrunk); it waits and copies the hits out.
+ * Refusals, each with a message of its own and nothing enqueued: FLX_ERR_NO_SCENE before a scene and transforms are up; FLX_ERR_INVALID where `what` has neither
+ * FLX_RAYS_CLOSEST nor FLX_RAYS_OCCLUDED or has an unknown bit; for an array that is not memory of the context's device, not 16-byte aligned or in an allocation
+ * too short for n rows; where the two arrays overlap. */
+#define FLX_RAYS_CLOSEST  1u   /* rayTracer  (fragment:172-227) of every ray */
+#define FLX_RAYS_OCCLUDED 2u   /* shadowTest (fragment:231-280) of every ray, with the row's l */
+#define FLX_RAYS_COUNT    4u   /* also write the entries each walk fetched (a build of the kernel of its own) */
+flx_status flx_rays_cast_device(flx_context *ctx, const void *d_rays /* n * 8 floats, on ctx's device */, void *d_hits /* n * 8 words */, uint32_t n, uint32_t what,
+                                void *producer_stream /* hipStream_t that wrote the rays, or NULL: they are complete */);
+flx_status flx_rays_cast(flx_context *ctx, const float *rays /* n * 8 floats */, void *hits /* n * 8 words */, uint32_t n, uint32_t what);      /* host arrays */
+/* workgroups the query launch takes (0, the default: its own choice — one per compute unit, fewer where the rays do not give every lane one).  For tests: one
+ * workgroup makes every lane take ray after ray. */
+flx_status flx_debug_set_query_groups(flx_context *ctx, uint32_t groups);
+/* The last query launch since the scene upload (zeros if none): out[0] its ldsCount (entries of the tree's top staged in LDS), [1] whether its rays were
+ * pre-transformed (0: transformed on the fly), [2] workgroups launched (1024 lanes each), [3] waves that drew at least one chunk, [4] n, [5] what, [6] the rays of a
+ * chunk (consecutive indices a wave draws with one atomic), [7] draws made, the ones past the last chunk included.  It waits for the context's stream. */
+flx_status flx_debug_last_query(flx_context *ctx, uint32_t out[8]);
 /* The uploaded scene as the device holds it, after everything enqueued so far: which 0 the geometry rows (12 floats per entry), 1 the attribute rows (28),
  * 2 the threaded hot-first copy (12 per entry of walk_entries), 3 the forward-ordered copy (12 per entry of fwd_entries: flx_debug_last_walk_lds' out[5], out[6]),
  * 4 the id list (an int32 in every 4 bytes of out, n_ids of them).

@@ -114,6 +114,7 @@ extern "C" void flx_context_destroy(flx_context *ctx) {
   for (hipEvent_t ev : ctx->stage_done) if (ev) (void)hipEventDestroy(ev);
   if (ctx->update_stream) { (void)hipStreamSynchronize(ctx->update_stream); (void)hipStreamDestroy(ctx->update_stream); }
   for (hipEvent_t ev : { ctx->update_done, ctx->update_checked, ctx->update_produced, ctx->geometry_uploaded }) if (ev) (void)hipEventDestroy(ev);
+  if (ctx->query_produced) (void)hipEventDestroy(ctx->query_produced);
   if (ctx->sv_stream) (void)hipStreamDestroy(ctx->sv_stream);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;                              /* its buffers go with it, on its device (set above; a twin's views of this context's scene arrays free nothing) */
@@ -152,12 +153,8 @@ static void fill_view(const flx_frame_params *p, FrameView &v) {
   v.random_seed = p->random_seed;
 }
 
-flx_status flx_make_frame(flx_context *ctx, const flx_frame_params *p, DeviceScene &sc, DeviceFrame &fr) {
-  if (!p) return fail(ctx, FLX_ERR_INVALID, "frame params are NULL");
-  if (!ctx->have_scene || !ctx->have_transforms) return fail(ctx, FLX_ERR_NO_SCENE, "render before flx_scene_upload / flx_transforms_upload");
-  if (p->width == 0 || p->height == 0 || p->samples < 1 || p->max_reflections < 0 || p->texture_width < 1)
-    return fail(ctx, FLX_ERR_INVALID, "frame params: width/height/samples/texture_width must be positive");
-  if (p->tile_count > 1 && p->tile_index >= p->tile_count) return fail(ctx, FLX_ERR_INVALID, "frame params: tile_index >= tile_count");
+/* the resident scene as the kernels are given it */
+static void fill_scene(flx_context *ctx, DeviceScene &sc) {
   sc.geometry = ctx->d_geometry; sc.attributes = ctx->d_attributes;
   sc.rotation = ctx->d_rotation; sc.shift = ctx->d_shift; sc.lights = ctx->d_lights;
   for (int i = 0; i < 3; i++) { sc.atlas[i] = ctx->d_atlas[i]; sc.atlas_w[i] = ctx->atlas_w[i]; sc.atlas_h[i] = ctx->atlas_h[i]; }
@@ -167,6 +164,22 @@ flx_status flx_make_frame(flx_context *ctx, const flx_frame_params *p, DeviceSce
   sc.fwd = ctx->d_fwd; sc.fwd_entries = ctx->fwd_entries; sc.fwd_root = ctx->fwd_root;
   sc.lock = ctx->d_fwd; sc.lock_entries = (ctx->lock_ok && ctx->lock_use) ? ctx->fwd_entries : 0u; sc.lock_root = ctx->fwd_root;
   sc.angle_tan = nullptr;                  /* (the per-pixel kernel's table: flx_run_frame makes it where that kernel is launched) */
+}
+/* ... for a caller that renders no frame (the ray queries); flx_make_frame's refusals that concern the scene */
+flx_status flx_make_scene(flx_context *ctx, DeviceScene &sc) {
+  if (!ctx->have_scene || !ctx->have_transforms) return fail(ctx, FLX_ERR_NO_SCENE, "no scene and transforms uploaded");
+  fill_scene(ctx, sc);
+  if (ctx->max_transform >= ctx->n_transforms) return fail(ctx, FLX_ERR_INVALID, "scene names a transform that was not uploaded");
+  return FLX_OK;
+}
+
+flx_status flx_make_frame(flx_context *ctx, const flx_frame_params *p, DeviceScene &sc, DeviceFrame &fr) {
+  if (!p) return fail(ctx, FLX_ERR_INVALID, "frame params are NULL");
+  if (!ctx->have_scene || !ctx->have_transforms) return fail(ctx, FLX_ERR_NO_SCENE, "render before flx_scene_upload / flx_transforms_upload");
+  if (p->width == 0 || p->height == 0 || p->samples < 1 || p->max_reflections < 0 || p->texture_width < 1)
+    return fail(ctx, FLX_ERR_INVALID, "frame params: width/height/samples/texture_width must be positive");
+  if (p->tile_count > 1 && p->tile_index >= p->tile_count) return fail(ctx, FLX_ERR_INVALID, "frame params: tile_index >= tile_count");
+  fill_scene(ctx, sc);
   uint32_t tr, ti, tc;
   tile_normalise(p, tr, ti, tc);
   fr.width = p->width; fr.height = p->height;

@@ -252,6 +252,13 @@ struct flx_context {
   flx_share *share = nullptr;
   uint32_t sv_groups = 0;                        /* flx_debug_set_server_groups: workgroups of the launch (0: one per CU) — two launches beside each other on one GPU, to rehearse a device group */
   struct { bool valid; uint32_t seq, slot; int format; flx::DeviceFrame fr; std::chrono::steady_clock::time_point posted; } sv_pending[3] = {};      /* per output slot: the server frame that will land there */
+  /* ray queries (flx_query.hip): the host call's staging, grown and never shrunk; the launch's two device words (the chunk cursor, the waves that drew a chunk);
+   * what the last launch since the scene upload was (flx_debug_last_query) */
+  DeviceBuffer<float4> d_query_rays, d_query_hits;
+  DeviceBuffer<uint32_t> d_query_ctl;
+  hipEvent_t query_produced = nullptr;            /* recorded on the caller's producer_stream, waited for by the context's */
+  flx::QueryLaunch last_query;
+  uint32_t query_groups = 0;                     /* flx_debug_set_query_groups: workgroups of the query launch (0: its own choice) */
   /* uploads: pinned staging ring */
   PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};
@@ -291,12 +298,14 @@ flx_status flx_gather_enqueue(flx_context *ctx, const flx_frame_params *params, 
 
 /* flx_api.hip */
 flx_status flx_make_frame(flx_context *ctx, const flx_frame_params *p, flx::DeviceScene &sc, flx::DeviceFrame &fr);
+flx_status flx_make_scene(flx_context *ctx, flx::DeviceScene &sc);      /* the scene alone, for a call that renders no frame */
 flx_status flx_make_batch(flx_context *ctx, const flx_frame_params *params, uint32_t n_frames, flx::DeviceScene &sc, flx::DeviceFrame &fr);
 flx_status flx_run_frame(flx_context *ctx, const flx::DeviceScene &sc, const flx::DeviceFrame &fr, float4 *d_out, const flx::GBufferPtrs &gb);
 int flx_server_takes_moving_scene(const flx_context *ctx);                       /* the scene has moved and its lights and transforms fit a post: the server's launches take them per frame */
 int flx_server_continues(flx_context *ctx, const flx_frame_params *params);      /* the running launch of the frame server takes this frame as it is */
 flx_status flx_server_prepare(flx_context *ctx, const flx_frame_params *params); /* the launch ends; everything a launch for frames like this needs is allocated */
 flx_status flx_server_stop(flx_context *ctx);      /* the frame server's launch ends (after the frames posted to it), the frames in flight are resolved into their output slots */
+bool flx_rows_on_device(const flx_context *ctx, const void *p, size_t bytes);      /* flx_scene.hip: [p, p + bytes) is memory of the context's device, 16-byte aligned, inside one allocation */
 flx_status flx_dyn_flush(flx_context *ctx);        /* flx_scene.hip: the device's transforms and lights follow the host's copies, where a launch went on over their uploads */
 flx_status flx_check_device_error(flx_context *ctx);      /* FLX_ERR_DEVICE (and the word cleared) if a frame kernel's watchdog has tripped since the last check */
 /* a temporal filter frame's strips (params->tile_*; use_filter = 1, is_temporal = 1): traced, the temporal pass over this context's history,

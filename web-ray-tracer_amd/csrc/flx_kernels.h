@@ -179,6 +179,14 @@ void launch_splice_rows(const float4 *geometry, const float4 *attributes, const 
                         float4 *geometryOut, float4 *attributesOut, hipStream_t stream);
 void launch_splice_ids(const int32_t *ids, uint32_t n_ids, const int32_t *blockIds, uint32_t n_block, uint32_t below, uint32_t above, uint32_t first, int32_t delta,
                        int32_t *out, hipStream_t stream);
+/* ray queries (flx_query.hip): n caller's rays (2 float4 each) walked through the scene by one persistent launch, a hit row (2 float4) per ray; what: FLX_RAYS_*.
+ * ctl: two device words, zeroed in front of the launch on the same stream: [0] the cursor the waves draw chunks of QUERY_CHUNK consecutive rays from, [1] <- waves
+ * that drew at least one.  groups: workgroups wanted (0: one per compute unit, no more than the rays fill).  *ran: what was launched.  false: the kernel cannot have
+ * its LDS on this device. */
+constexpr uint32_t QUERY_CHUNK = 128;
+struct QueryLaunch { uint32_t ldsCount = 0, pre = 0, groups = 0, n = 0, what = 0; };
+bool launch_ray_query(const DeviceScene &sc, const float4 *rays, float4 *hits, uint32_t n, uint32_t what, uint32_t *ctl, uint32_t compute_units, uint32_t groups,
+                      hipStream_t stream, QueryLaunch *ran);
 void launch_debug_math(int fn, const float *a, const float *b, float *out, uint32_t n, hipStream_t stream);
 void launch_debug_intersect(int fn, const float *in, float *out, uint32_t n, hipStream_t stream);
 bool launch_debug_walk(int variant, const DeviceScene &sc, const float *in, float *out, uint32_t n, hipStream_t stream);      /* false: the scene does not allow that variant */

@@ -241,6 +241,7 @@ static bool rows_on_device(const flx_context *ctx, const void *p, size_t bytes) 
   if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
   return (uintptr_t)p - (uintptr_t)base + bytes <= size;
 }
+bool flx_rows_on_device(const flx_context *ctx, const void *p, size_t bytes) { return rows_on_device(ctx, p, bytes); }      /* (flx_query.hip asks the same of its rays and hits) */
 
 /* What an upload learns about its entry array.  flx_scene_upload fills it from its scan and the two builders, flx_scene_upload_device from the record of
  * k_derive_check (flx_derive.hip); the two derivations stay apart, each is the other's oracle (tests/test_scene_upload_device_gpu.py). */
@@ -273,7 +274,7 @@ static flx_status upload_refused(flx_context *ctx, const void *geometry, const v
 }
 
 /* from the first array that changes until adopt_scene the context has no scene */
-static void begin_scene(flx_context *ctx) { ctx->have_scene = false; ctx->last_walk_lds = WalkLdsLaunch(); ctx->geometry_version++; }
+static void begin_scene(flx_context *ctx) { ctx->have_scene = false; ctx->last_walk_lds = WalkLdsLaunch(); ctx->last_query = QueryLaunch(); ctx->geometry_version++; }
 static void adopt_scene(flx_context *ctx, uint32_t n_entries_padded, uint32_t n_ids, const SceneFacts &f) {
   ctx->walk_entries = f.walk_entries; ctx->walk_hot = f.walk_hot; ctx->walk_root = f.walk_root; ctx->walk_fast_boxes = f.bounded ? 1u : 0u;
   ctx->walk_thick_boxes = f.thick ? 1u : 0u;

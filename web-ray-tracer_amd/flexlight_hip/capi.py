@@ -34,12 +34,15 @@ EXPORTS = [
     "flx_debug_walk_thick_boxes", "flx_debug_set_box_test", "flx_debug_boxes_thick", "flx_debug_last_box_test",
     "flx_scene_update", "flx_group_scene_update", "flx_debug_scene_read", "flx_scene_update_device", "flx_scene_upload_device",
     "flx_tree_build_device", "flx_tree_emit_device", "flx_scene_splice_device",
+    "flx_rays_cast_device", "flx_rays_cast", "flx_debug_set_query_groups", "flx_debug_last_query",
 ]
 
 
 
 SHARE_HANDLE_BYTES = 128      # FLX_SHARE_HANDLE_BYTES
 NO_PARENT = 0xffffffff         # FLX_NO_PARENT of include/flexlight_hip_debug.h
+RAYS_CLOSEST, RAYS_OCCLUDED, RAYS_COUNT = 1, 2, 4      # FLX_RAYS_* of include/flexlight_hip_debug.h: what cast_rays asks of every ray
+QUERY_CHUNK = 128              # consecutive rays a wave of the query kernel draws with one atomic (QUERY_CHUNK of csrc/flx_kernels.h; flx_debug_last_query reports it)
 FRAME_FXAA = 0x10              # FLX_FRAME_FXAA: flags of flx_frame_begin's format
 FRAME_TAA = 0x20               # FLX_FRAME_TAA
 FRAME_RASTERIZER = 0x100       # FLX_FRAME_RASTERIZER
@@ -70,6 +73,10 @@ def _load():
         "flx_tree_emit_device": (C.c_int, [vp, vp, vp, vp, vp, vp]),
         "flx_scene_splice_device": (C.c_int, [vp, u32, u32, u32, vp, vp, u32, vp, u32, vp]),
         "flx_debug_scene_read": (C.c_int, [vp, C.c_int, fp, u32]),
+        "flx_rays_cast_device": (C.c_int, [vp, vp, vp, u32, u32, vp]),
+        "flx_rays_cast": (C.c_int, [vp, fp, vp, u32, u32]),
+        "flx_debug_set_query_groups": (C.c_int, [vp, u32]),
+        "flx_debug_last_query": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_transforms_upload": (C.c_int, [vp, fp, fp, u32]),
         "flx_lights_upload": (C.c_int, [vp, fp, u32]),
         "flx_atlas_upload": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint8), u32, u32]),
@@ -244,6 +251,33 @@ def _device_array(x, dtype_name, width, device, what):
     return x.data_ptr(), x.shape[0]
 
 
+def _ray_rows(x, device):
+    """rays of cast_rays_device -> (device address, row count): a torch tensor [n, 8] (float32, contiguous, on cuda:`device`) or (address, n)"""
+    if isinstance(x, tuple):
+        address, n = x
+        return int(address), int(n)
+    import torch                               # (here and not at the top: capi imports without torch)
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("cast_rays_device: rays is a torch tensor or (address, rows)")
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 8 or not x.is_contiguous():
+        raise ValueError("cast_rays_device: rays is a contiguous float32 tensor [n, 8]")
+    if x.device.type != "cuda" or x.device.index != device:
+        raise ValueError("cast_rays_device: rays is on %s, the context on cuda:%d" % (x.device, device))
+    return x.data_ptr(), x.shape[0]
+
+
+def unpack_hits(buf):
+    """hit rows of cast_rays / cast_rays_device (uint8 [n, 32], a numpy array or a torch tensor: a tensor is copied to the host, which waits for the stream it
+    is asked on — flx_sync first where the query ran on another) -> dict: suv float32 [n, 3] (s, u, v of the closest hit), entry int32 [n] (-1: none),
+    transform2 int32 [n] (2 x transform number), occluded int32 [n], visits_closest and visits_shadow uint32 [n] (zeros without RAYS_COUNT)"""
+    if not isinstance(buf, np.ndarray):
+        buf = buf.detach().cpu().numpy()
+    rows = np.ascontiguousarray(buf, np.uint8).reshape(-1, 32)
+    words = rows.view(np.uint32)
+    return {"suv": words[:, 0:3].view(np.float32).copy(), "entry": words[:, 3].view(np.int32).copy(), "transform2": words[:, 4].view(np.int32).copy(),
+            "occluded": words[:, 5].view(np.int32).copy(), "visits_closest": words[:, 6].copy(), "visits_shadow": words[:, 7].copy()}
+
+
 def boxes_thick(geometry):
     """flx_debug_boxes_thick: whether every box row (word 10 == 1) of geometry [n, 12] float32 has min < max on all three axes — flx_scene_upload's scan, no GPU"""
     geometry = np.ascontiguousarray(geometry, np.float32).reshape(-1, 12)
@@ -394,6 +428,49 @@ class Context:
             stream = handle
         self._check(LIB.flx_scene_update_device(self._h, first, n, C.c_void_p(g), C.c_void_p(a) if a is not None else None,
                                                 C.c_void_p(stream) if stream else None), "flx_scene_update_device")
+
+    # -- ray queries --------------------------------------------------------------------------------
+    def cast_rays_device(self, rays, hits=None, what=RAYS_CLOSEST | RAYS_OCCLUDED, stream=None):
+        """flx_rays_cast_device: rays of the caller's own cast at the resident scene, in device memory.  rays: a torch tensor [n, 8] (float32, contiguous, on the
+        context's device: origin, l, direction, one word ignored) or (address, n); hits: None (a new uint8 tensor [n, 32]), such a tensor to write into, or an
+        address (then the address comes back); what: RAYS_CLOSEST | RAYS_OCCLUDED | RAYS_COUNT; stream: the torch.cuda.Stream (or raw hipStream_t) on which the
+        rays were written, as for update_scene_rows_device.  Returns the hit rows ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE: sync() before they are
+        read on another stream (unpack_hits reads them).  Both arrays stay alive until then."""
+        r, n = _ray_rows(rays, self._device)
+        if hits is None:
+            import torch
+            hits = torch.empty((n, 32), dtype=torch.uint8, device="cuda:%d" % self._device)
+        if isinstance(hits, int):
+            h = hits
+        else:
+            if hits.dtype.is_floating_point or hits.device.type != "cuda" or hits.device.index != self._device or not hits.is_contiguous() or hits.numel() * hits.element_size() < n * 32:
+                raise ValueError("cast_rays_device: hits is a contiguous integer tensor of at least n x 32 bytes on the context's device")
+            h = hits.data_ptr()
+        if stream is not None and not isinstance(stream, int):
+            handle = stream.cuda_stream
+            if handle == 0:
+                stream.synchronize()
+            stream = handle
+        self._check(LIB.flx_rays_cast_device(self._h, C.c_void_p(r), C.c_void_p(h), n, int(what), C.c_void_p(stream) if stream else None), "flx_rays_cast_device")
+        return hits
+
+    def cast_rays(self, rays, what=RAYS_CLOSEST | RAYS_OCCLUDED):
+        """flx_rays_cast: rays [n, 8] float32 in host memory (origin, l, direction, one word ignored) -> hit rows uint8 [n, 32], complete (unpack_hits)"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        hits = np.zeros((rays.shape[0], 32), np.uint8)
+        self._check(LIB.flx_rays_cast(self._h, _fp(rays), hits.ctypes.data_as(C.c_void_p), rays.shape[0], int(what)), "flx_rays_cast")
+        return hits
+
+    def set_query_groups(self, groups):
+        """flx_debug_set_query_groups: workgroups of the query launch (0: its own choice)"""
+        self._check(LIB.flx_debug_set_query_groups(self._h, int(groups)), "flx_debug_set_query_groups")
+
+    def last_query(self):
+        """flx_debug_last_query -> dict (zeros when no query ran since the scene upload): lds_count, pre, groups (of 1024 lanes), waves that drew a chunk, n,
+        what, chunk (rays per draw), draws"""
+        out = (C.c_uint32 * 8)()
+        self._check(LIB.flx_debug_last_query(self._h, out), "flx_debug_last_query")
+        return dict(zip(("lds_count", "pre", "groups", "waves", "n", "what", "chunk", "draws"), list(out)))
 
     def scene_read(self, which, rows=None):
         """flx_debug_scene_read: the device's 'geometry' [rows, 12], 'attributes' [rows, 28], 'walk' (the threaded copy) or 'fwd' (the forward-ordered

@@ -28,6 +28,21 @@ function native () {
   return addon;
 }
 
+/* flx_rays_cast on a context whose scene, lights and transforms are up (both renderers' castRays): the hit rows as the library writes them, 8 words a ray
+ * (include/flexlight_hip_debug.h), unpacked into typed arrays */
+function castRaysOn (context, rays, what) {
+  if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('castRays: rays is a Float32Array of 8 floats per ray');
+  const hits = native().castRays(context, rays, what === undefined ? 3 : what);
+  const n = rays.length / 8;
+  const words = new Uint32Array(hits), f = new Float32Array(hits), i32 = new Int32Array(hits);
+  const out = { suv: new Float32Array(3 * n), entry: new Int32Array(n), transform: new Int32Array(n), occluded: new Uint8Array(n) };
+  for (let k = 0; k < n; k++) {
+    out.suv[3 * k] = f[8 * k]; out.suv[3 * k + 1] = f[8 * k + 1]; out.suv[3 * k + 2] = f[8 * k + 2];
+    out.entry[k] = i32[8 * k + 3]; out.transform[k] = i32[8 * k + 4] >> 1; out.occluded[k] = words[8 * k + 5];
+  }
+  return out;
+}
+
 class PathTracerHIP {
   constructor (canvas, scene, camera, config, options) {
     this.type = 'pathtracer';
@@ -216,6 +231,17 @@ class PathTracerHIP {
     return gpu;
   }
 
+  /* Rays of the application's own at the scene as the next frame would see it: picking, visibility (flx_rays_cast, include/flexlight_hip_debug.h "ray queries").
+   * rays: Float32Array, 8 floats per ray — origin x y z, l (the length shadowTest compares; unused otherwise), direction x y z (not normalised: a hit lies at
+   * origin + s * direction), one unused.  what: 1 the closest hit, 2 occluded within l (the renderer's own shadow predicate), 3 both.  Returns
+   * { suv: Float32Array(3 n), entry: Int32Array(n) (the entry index in the flattened scene, -1: none), transform: Int32Array(n) (the transform number),
+   * occluded: Uint8Array(n) }.  It waits for the answer; frames in flight finish unchanged. */
+  castRays (rays, what) {
+    if (this._devices) throw new Error('castRays: one GPU only (a group of GPUs casts no rays)');
+    this._uploadFrameState();
+    return castRaysOn(this._context(), rays, what);
+  }
+
   renderFrame (options) {
     const gpu = this._uploadFrameState();
     const aa = this._antialiasing();
@@ -393,4 +419,4 @@ function taaVectors (n, random) {
   return vecs;
 }
 
-module.exports = { PathTracerHIP, taaVectors, native };
+module.exports = { PathTracerHIP, taaVectors, native, castRaysOn };

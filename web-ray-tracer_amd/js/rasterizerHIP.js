@@ -11,7 +11,7 @@
  */
 const { Transform } = require('./scene.js');
 const sceneFile = require('./sceneFile.js');
-const { native, taaVectors } = require('./pathtracerHIP.js');
+const { native, taaVectors, castRaysOn } = require('./pathtracerHIP.js');
 
 class RasterizerHIP {
   constructor (canvas, scene, camera, config, options) {
@@ -143,6 +143,13 @@ class RasterizerHIP {
     n.uploadLights(c, sceneFile.buildLightArray(this.scene));
     const tr = Transform.buildWGL2Arrays();
     n.uploadTransforms(c, tr[0], tr[1]);
+  }
+
+  /* PathTracerHIP.castRays(): the same call on the same context plumbing — which object is under the cursor of a rasterized view.  (This renderer has one
+   * context and never a group of GPUs: flexlight.js refuses options.devices for it.) */
+  castRays (rays, what) {
+    this._uploadFrameState();
+    return castRaysOn(this._context(), rays, what);
   }
 
   renderFrame (options) {

@@ -192,6 +192,24 @@ static napi_value UpdateSceneRows(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+/* castRays(handle, rays Float32Array(8 n), what) -> ArrayBuffer(32 n): flx_rays_cast, the hit rows as the library writes them (include/flexlight_hip_debug.h) */
+static napi_value CastRays(napi_env env, napi_callback_info info) {
+  napi_value argv[3];
+  if (!get_args(env, info, 3, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  void *rays; size_t len; uint32_t what;
+  if (!typed(env, argv[1], napi_float32_array, &rays, &len)) return nullptr;
+  if (napi_get_value_uint32(env, argv[2], &what) != napi_ok) { napi_throw_type_error(env, nullptr, "castRays: what is not a number"); return nullptr; }
+  if (len % 8 != 0 || len / 8 > 0xffffffffu) { napi_throw_range_error(env, nullptr, "castRays: a ray needs 8 floats (origin, l, direction, one unused)"); return nullptr; }
+  void *hits = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, (len / 8) * 32, &hits, &buf));
+  flx_status rc = flx_rays_cast(ctx, (const float *)rays, hits, (uint32_t)(len / 8), what);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_rays_cast", rc);
+  return buf;
+}
+
 /* uploadTransforms(handle, rotation Float32Array(24 T), shift Float32Array(8 T)) */
 static napi_value UploadTransforms(napi_env env, napi_callback_info info) {
   napi_value argv[3];
@@ -1048,7 +1066,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
