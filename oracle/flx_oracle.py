@@ -32,6 +32,10 @@ def lib():
         _LIB.flx_oracle_filter.restype = C.c_int
         _LIB.flx_oracle_render_sequence.argtypes = [C.POINTER(SceneView), C.POINTER(FrameParams), C.c_int, C.POINTER(C.c_float), C.c_int]
         _LIB.flx_oracle_render_sequence.restype = C.c_int
+        _LIB.flx_oracle_render_sequence_frames.argtypes = [C.POINTER(SceneView), C.POINTER(FrameParams), C.c_int, C.POINTER(C.c_float), C.c_int]
+        _LIB.flx_oracle_render_sequence_frames.restype = C.c_int
+        _LIB.flx_oracle_trace.argtypes = [C.POINTER(SceneView), C.POINTER(FrameParams), C.POINTER(C.c_float), C.POINTER(GBuffers), C.POINTER(Counters), C.c_int]
+        _LIB.flx_oracle_trace.restype = C.c_int
     return _LIB
 
 
@@ -52,7 +56,11 @@ def tile_rows(params):
 
 
 def render(scene, params, gbuffers=False, threads=0):
-    """Returns (rgba [rows, W, 4] float32, counters dict, gbuffers dict or None)."""
+    """Returns (rgba [rows, W, 4] float32, counters dict, gbuffers dict or None).
+
+    A temporal frame (is_temporal = 1) goes through the sequence code as a run of ONE frame: it is traced with random_seed = 0 % N = 0 whatever
+    params.random_seed says, and averaged over an empty history.  Its G-buffers are therefore those of frame 0 of a run, not of the frame params
+    describes: for the G-buffers of frame f of a temporal run, use trace(), which traces params as given."""
     view = scene.view()
     rows = len(tile_rows(params))
     out = np.zeros((rows, params.width, 4), np.float32)
@@ -65,6 +73,32 @@ def render(scene, params, gbuffers=False, threads=0):
     if rc != 0:
         raise RuntimeError("flx_oracle_render failed: %d" % rc)
     return out, cnt.as_dict(), gbs
+
+
+def trace(scene, params, threads=0):
+    """flx_oracle_trace: the path-trace pass alone, from params as given (seed and camera included) -> the six float G-buffers the pass writes,
+    a dict of [rows, W, 4] float32 planes (color, color_ip, original_color, id, original_id, location_id).  No temporal pass, no filter."""
+    view = scene.view()
+    rows = len(tile_rows(params))
+    gbs = {n: np.zeros((rows, params.width, 4), np.float32) for n, _ in GBuffers._fields_}
+    gb = GBuffers(*[_fp(gbs[n]) for n, _ in GBuffers._fields_])
+    rc = lib().flx_oracle_trace(C.byref(view), C.byref(params), None, C.byref(gb), None, threads)
+    if rc != 0:
+        raise RuntimeError("flx_oracle_trace failed: %d" % rc)
+    return gbs
+
+
+def render_sequence_frames(scene, params_list, threads=0):
+    """A temporal run whose frame f is traced from params_list[f] as given (the camera and the seed are the caller's) -> [n, H, W, 4] float32.
+    All frames share width, height, temporal_samples and use_filter, and have is_temporal = 1."""
+    view = scene.view()
+    n = len(params_list)
+    frames = (FrameParams * n)(*[FrameParams.from_buffer_copy(p) for p in params_list])
+    out = np.zeros((n, params_list[0].height, params_list[0].width, 4), np.float32)
+    rc = lib().flx_oracle_render_sequence_frames(C.byref(view), frames, n, _fp(out), threads)
+    if rc != 0:
+        raise RuntimeError("flx_oracle_render_sequence_frames failed: %d" % rc)
+    return out
 
 
 def render_sequence(scene, params, n_frames, threads=0):

@@ -367,9 +367,10 @@ static void temporal_pass(const History *h, int W, int H, int hdr, int use_filte
   }
 }
 
-int flx_oracle_render_sequence_impl(const flx_scene_view *scene, const flx_frame_params *params, int n_frames, float *out_all,
-                                    const flx_gbuffers *gb_last, flx_counters *counters_last, int threads) {
-  if (!scene || !params || n_frames < 1 || !out_all) return FLX_ERR_INVALID;
+/* frame f traced from frames[f] as given; width, height, is_temporal, temporal_samples and use_filter are frames[0]'s (the callers check that all frames share them) */
+static int render_frames(const flx_scene_view *scene, const flx_frame_params *frames, int n_frames, float *out_all,
+                         const flx_gbuffers *gb_last, flx_counters *counters_last, int threads) {
+  const flx_frame_params *params = frames;
   const int W = (int)params->width, H = (int)params->height;
   const size_t px = (size_t)W * H, bytes = px * 4;
   const int temporal = params->is_temporal == 1;
@@ -382,8 +383,7 @@ int flx_oracle_render_sequence_impl(const flx_scene_view *scene, const flx_frame
   flx_gbuffers gb = { g[0], g[1], g[2], g[3], g[4], g[5] };
   int rc = FLX_OK;
   for (int f = 0; f < n_frames && rc == FLX_OK; f++) {
-    flx_frame_params p = *params;
-    if (temporal) p.random_seed = (float)(f % N);
+    const flx_frame_params p = frames[f];
     float *canvas = out_all + (size_t)f * px * 4;
     rc = flx_oracle_trace(scene, &p, NULL, &gb, f == n_frames - 1 ? counters_last : NULL, threads);
     if (rc != FLX_OK) break;
@@ -412,8 +412,32 @@ int flx_oracle_render_sequence_impl(const flx_scene_view *scene, const flx_frame
   return rc;
 }
 
+/* n_frames frames of one set of parameters; a temporal run's frame f is traced with randomSeed = f % N (pathtracerWGL2.js:291, 347) */
+int flx_oracle_render_sequence_impl(const flx_scene_view *scene, const flx_frame_params *params, int n_frames, float *out_all,
+                                    const flx_gbuffers *gb_last, flx_counters *counters_last, int threads) {
+  if (!scene || !params || n_frames < 1 || !out_all) return FLX_ERR_INVALID;
+  const int N = params->temporal_samples <= 0 ? 4 : (params->temporal_samples > 16 ? 16 : params->temporal_samples);
+  flx_frame_params *frames = (flx_frame_params *)malloc(sizeof(flx_frame_params) * (size_t)n_frames);
+  if (!frames) return FLX_ERR_INVALID;
+  for (int f = 0; f < n_frames; f++) {
+    frames[f] = *params;
+    if (params->is_temporal == 1) frames[f].random_seed = (float)(f % N);
+  }
+  const int rc = render_frames(scene, frames, n_frames, out_all, gb_last, counters_last, threads);
+  free(frames);
+  return rc;
+}
+
 int flx_oracle_render_sequence(const flx_scene_view *scene, const flx_frame_params *params, int n_frames, float *out_all, int threads) {
   return flx_oracle_render_sequence_impl(scene, params, n_frames, out_all, NULL, NULL, threads);
+}
+
+int flx_oracle_render_sequence_frames(const flx_scene_view *scene, const flx_frame_params *frames, int n_frames, float *out_all, int threads) {
+  if (!scene || !frames || n_frames < 1 || !out_all) return FLX_ERR_INVALID;
+  for (int f = 0; f < n_frames; f++)
+    if (frames[f].is_temporal != 1 || frames[f].width != frames[0].width || frames[f].height != frames[0].height ||
+        frames[f].temporal_samples != frames[0].temporal_samples || frames[f].use_filter != frames[0].use_filter) return FLX_ERR_INVALID;
+  return render_frames(scene, frames, n_frames, out_all, NULL, NULL, threads);
 }
 
 /* ---- anti-aliasing post passes: modules/fxaa.js:7-137, modules/taa.js:11-59 ---------------------------------

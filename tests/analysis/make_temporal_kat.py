@@ -3,7 +3,11 @@
 isTemporal outputs, fragment:620-646) into the rings of RGBA8 history textures the host rotates (modules/pathtracerWGL2.js:389-402), then averaged by the temporal shader the
 host GENERATES (pathtracerWGL2.js:571-662, here for temporalSamples = 4: its mat4 groups padded with vec4(0), which a background pixel's zero id matches), with the per-frame
 seed frame % temporalSamples (:291, 347).  Pins as in make_filter_kat.py (RGBA8 stores and fetches) and make_pixel_kat.py (the primary hit, from the oracle; relativePosition
-as the same barycentric mix of the object-space vertices); pow correctly rounded.  Writes tests/golden/temporal_kat.json.gz.   usage: make_temporal_kat.py [--check]"""
+as the same barycentric mix of the object-space vertices); pow correctly rounded.  Writes tests/golden/temporal_kat.json.gz.   usage: make_temporal_kat.py [--check]
+
+temporal_shader below is the pass for N = 4 under a still camera, one texel at a time.  tests/temporal_util.py is its any-depth form (temporal_literal: the shader generated for every
+temporalSamples, over whole planes; TemporalRing: the rotation), which tests/test_temporal_literal_cpu.py holds against this table and then uses at the depths and under the motion
+this table does not reach."""
 import gzip, json, os, sys
 import numpy as np
 
