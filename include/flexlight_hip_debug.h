@@ -270,12 +270,50 @@ flx_status flx_rays_cast_device(flx_context *ctx, const void *d_rays /* n * 8 fl
                                 void *producer_stream /* hipStream_t that wrote the rays, or NULL: they are complete */);
 flx_status flx_rays_cast(flx_context *ctx, const float *rays /* n * 8 floats */, void *hits /* n * 8 words */, uint32_t n, uint32_t what);      /* host arrays */
 /* workgroups the query launch takes (0, the default: its own choice — one per compute unit, fewer where the rays do not give every lane one).  For tests: one
- * workgroup makes every lane take ray after ray. */
+ * workgroup makes every lane take ray after ray.  A traced batch (flx_rays_trace_device, below) takes the same number for BOTH of its persistent launches: the first-hit
+ * launch (1024 lanes a workgroup) and the paths kernel (256 lanes a workgroup). */
 flx_status flx_debug_set_query_groups(flx_context *ctx, uint32_t groups);
 /* The last query launch since the scene upload (zeros if none): out[0] its ldsCount (entries of the tree's top staged in LDS), [1] whether its rays were
  * pre-transformed (0: transformed on the fly), [2] workgroups launched (1024 lanes each), [3] waves that drew at least one chunk, [4] n, [5] what, [6] the rays of a
  * chunk (consecutive indices a wave draws with one atomic), [7] draws made, the ones past the last chunk included.  It waits for the context's stream. */
 flx_status flx_debug_last_query(flx_context *ctx, uint32_t out[8]);
+/* RADIANCE along the caller's rays: what the renderer sees along each — another projection (panorama, fisheye, orthographic, a stereo pair), light probes, the
+ * reflection rays of a hybrid renderer, a pipeline that makes its own rays.  For every ray row: hit = rayTracer(origin, direction), the closest hit exactly as
+ * FLX_RAYS_CLOSEST answers it; no hit gives the miss row; otherwise c = the sum over s = 0 .. samples - 1 of lightTrace(hit, direction, origin, cos(float(s)),
+ * max_reflections) added in sample order, then c * (1.0f / (float)samples), then c * originalColor as the LAST sample left it: a frame's pixel without filter and
+ * without temporal (fragment:601-632), with the oracle's bits.  The ray's origin stands wherever lightTrace uses the camera (lastHitPoint, firstRayLength); the
+ * direction is used as given, not normalised, as rayTracer takes it.
+ * A RAY ROW is the query's, 32 bytes: words 0..2 the origin, 3 NOISE X, 4..6 the direction, 7 NOISE Y — the two words a closest-hit query does not read.  noise()
+ * is fed the two noise coordinates where a frame feeds it the pixel's NDC: RAYS WITH EQUAL NOISE COORDINATES DRAW EQUAL RANDOM NUMBERS, so give every ray of a
+ * batch its own (a frame's are spread over [-1, 1)^2; capi.noise_coordinates does that for n rays).
+ * A RADIANCE ROW is 32 bytes, two 16-byte vector stores: words 0..2 float r, g, b; 3 float 1.0 for a hit, 0.0 for a miss (the frame's alpha); 4 float s of the
+ * first hit; 5 int32 its entry, -1 for none; 6 int32 2 x its transform; 7 uint32 the bounce iterations shaded over all samples (the oracle's `shades` for this
+ * ray).  A MISS ROW IS ALL ZEROS with -1 in word 5: as in a frame, where a pixel with no primary hit is (0, 0, 0, 0) — not the ambient light.
+ * Filter and temporal are image-space and have no meaning here; a ray batch has no width, height or camera, hence the params of its own.
+ * Ordering, producer_stream, the frame server, lights and transforms uploaded over a running launch, the staging of the host variant and n == 0 are
+ * flx_rays_cast_device's and flx_rays_cast's, word for word: enqueued on the context's stream with no wait of the host, it sees the scene as of the call, frames in
+ * flight finish unchanged; n == 0: FLX_OK, nothing enqueued (the scene and the params are looked at first).  The batch is cut into slabs of rays so that the
+ * context's scratch (hit rows, samples slots of 16 bytes a ray, grown and never shrunk) has a ceiling: at most 2^24 slots and 2^21 rays a slab, at least 64 rays;
+ * any n works at any sample count the device's memory holds 64 rays' slots of.  (Where that scratch must grow, the host waits for the stream first.)
+ * Refusals, each with a message of its own and nothing enqueued: FLX_ERR_NO_SCENE before a scene and transforms are up; FLX_ERR_INVALID for NULL params, samples < 1,
+ * max_reflections < 0 or texture_width < 1; for an array that is NULL, not memory of the context's device, not 16-byte aligned or in an allocation too short for n
+ * rows; where the two arrays overlap.  A group traces no rays, as it casts none. */
+typedef struct flx_trace_params {
+  int32_t samples, max_reflections;
+  float min_importancy;
+  float ambient[3];
+  float random_seed;
+  int32_t texture_width;
+} flx_trace_params;
+flx_status flx_rays_trace_device(flx_context *ctx, const flx_trace_params *params, const void *d_rays /* n * 8 floats, on ctx's device */, void *d_radiance /* n * 8 words */,
+                                 uint32_t n, void *producer_stream /* hipStream_t that wrote the rays, or NULL: they are complete */);
+flx_status flx_rays_trace(flx_context *ctx, const flx_trace_params *params, const float *rays /* n * 8 floats */, void *radiance /* n * 8 words */, uint32_t n);      /* host arrays */
+/* most rays of a slab of a traced batch (0, the default: the ceiling above).  For tests: a small value makes a batch span several slabs.  flx_debug_set_query_groups
+ * sets the workgroups of a slab's first-hit launch AND of its paths kernel (256 lanes each there). */
+flx_status flx_debug_set_trace_slab(flx_context *ctx, uint32_t rays);
+/* The last traced batch (zeros if none): out[0] its slabs, [1] the rays of a full slab, [2] workgroups of the last slab's paths kernel, [3] whether its bounce walks
+ * went in lockstep, [4] n, [5] samples, [6] workgroups of the last slab's first-hit launch, [7] the items a wave draws with one atomic.  It waits for nothing. */
+flx_status flx_debug_last_trace(flx_context *ctx, uint32_t out[8]);
 /* The uploaded scene as the device holds it, after everything enqueued so far: which 0 the geometry rows (12 floats per entry), 1 the attribute rows (28),
  * 2 the threaded hot-first copy (12 per entry of walk_entries), 3 the forward-ordered copy (12 per entry of fwd_entries: flx_debug_last_walk_lds' out[5], out[6]),
  * 4 the id list (an int32 in every 4 bytes of out, n_ids of them).

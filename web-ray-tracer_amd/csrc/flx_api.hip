@@ -326,6 +326,7 @@ static flx_status angle_table(flx_context *ctx, DeviceScene &scT) {
   }
   return FLX_OK;
 }
+flx_status flx_angle_table(flx_context *ctx, DeviceScene &sc) { return angle_table(ctx, sc); }      /* (flx_rays_trace.hip, which defines FLX_ANGLE_TABLE 1: k_rays_paths' shading loads the table, as k_paths' does) */
 
 flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFrame &fr, float4 *d_out, const GBufferPtrs &gb) {
   { flx_status ss = flx_server_stop(ctx); if (ss) return ss; }      /* (the frame server renders into the same workspace) */

@@ -259,6 +259,12 @@ struct flx_context {
   hipEvent_t query_produced = nullptr;            /* recorded on the caller's producer_stream, waited for by the context's */
   flx::QueryLaunch last_query;
   uint32_t query_groups = 0;                     /* flx_debug_set_query_groups: workgroups of the query launch (0: its own choice) */
+  /* traced ray batches (flx_rays_trace.hip): the scratch of a slab of rays, grown and never shrunk — the first hits' rows, a slot per (sample, ray), the last
+   * sample's originalColor per ray —, the four words of a slab's launches, what the last batch ran (flx_debug_last_trace) */
+  DeviceBuffer<float4> d_trace_hits, d_trace_slots, d_trace_last;
+  DeviceBuffer<uint32_t> d_trace_ctl;
+  struct TraceLaunch { uint32_t slabs = 0, slab = 0, path_groups = 0, lock = 0, n = 0, samples = 0, query_groups = 0; } last_trace_rays;
+  uint32_t trace_slab = 0;                       /* flx_debug_set_trace_slab: most rays of a slab (0: flx_trace_slab_rays' own ceiling) */
   /* uploads: pinned staging ring */
   PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};
@@ -299,6 +305,7 @@ flx_status flx_gather_enqueue(flx_context *ctx, const flx_frame_params *params, 
 /* flx_api.hip */
 flx_status flx_make_frame(flx_context *ctx, const flx_frame_params *p, flx::DeviceScene &sc, flx::DeviceFrame &fr);
 flx_status flx_make_scene(flx_context *ctx, flx::DeviceScene &sc);      /* the scene alone, for a call that renders no frame */
+flx_status flx_angle_table(flx_context *ctx, flx::DeviceScene &sc);     /* sc.angle_tan <- the context's per-triangle table, made again first (on its stream) where the scene or its transforms changed */
 flx_status flx_make_batch(flx_context *ctx, const flx_frame_params *params, uint32_t n_frames, flx::DeviceScene &sc, flx::DeviceFrame &fr);
 flx_status flx_run_frame(flx_context *ctx, const flx::DeviceScene &sc, const flx::DeviceFrame &fr, float4 *d_out, const flx::GBufferPtrs &gb);
 int flx_server_takes_moving_scene(const flx_context *ctx);                       /* the scene has moved and its lights and transforms fit a post: the server's launches take them per frame */

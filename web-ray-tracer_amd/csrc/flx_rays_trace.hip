@@ -1,0 +1,281 @@
+/* flx_rays_trace.hip — radiance along a caller's rays (include/flexlight_hip_debug.h, "ray queries": flx_rays_trace, flx_rays_trace_device).
+ *
+ * What a frame computes for a pixel without filter and without temporal (fragment:601-632), computed for a ray of the caller's own: hit = rayTracer(origin,
+ * direction); the samples' lightTrace(hit, direction, origin, cos(float(s)), max_reflections) added in sample order, averaged, times the originalColor the last
+ * sample left.  The ray's origin stands where a frame has its camera, the row's two noise coordinates where a frame has the pixel's NDC.
+ *
+ * The structure is pipeline 2's (flx_kernels.hip: k_primary -> k_paths -> k_resolve) with rows where it has pixels:
+ *   1. first hits: k_ray_query as it stands (flx_query.hip, what = FLX_RAYS_CLOSEST) into hit rows the context owns — a hit row's first float4 is k_paths'
+ *      (s, u, v, triangle), word 4 the hit's 2 x transform;
+ *   2. k_rays_paths<LOCK>: persistent waves refilled as k_paths refills them.  A work item is (ray, sample); items are numbered [block of 64 consecutive rays]
+ *      [sample][lane], so that the 64 items a wave draws together are one sample of 64 neighbouring rays: the coherence the caller gave survives.  Every loop trip
+ *      is one bounce<false, LOCK>() — one whole iteration of lightTrace, flx_device.h — for every live lane; the loop guard is tested before the first bounce.  A
+ *      finished path writes finalColor + importancyFactor * ambient to its own slot (w: the bounce iterations it shaded, as bits), the last sample's path also
+ *      its originalColor.  bounce() is given a DeviceFrame of one view that holds the params' seed and ambient;
+ *   3. k_rays_resolve: a thread per ray adds the slots in sample order, scales, multiplies by originalColor, adds the bounce counts and writes the radiance row
+ *      with two float4 stores.
+ * The scratch (hit rows, rays x samples slots, an originalColor per ray) is the context's, grown and never shrunk.  The host cuts a batch into SLABS of rays so
+ * that the scratch has a ceiling: flx_trace_slab_rays (flx_query_args.h) — at most 2^24 slots (256 MB) and 2^21 rays a slab, at least 64 rays.  A slab's three
+ * launches follow each other on the context's stream, the cursors zeroed in stream order in front of them.  The paths kernel's cursor counts UNITS of 64 items
+ * (a block of rays x a sample), of which a slab has fewer than 2^31 + 2^18 whatever n and the sample count: any n a uint32_t holds works at any sample count the
+ * memory holds a slab of.  The host waits for nothing — but where the scratch must grow, for the work that may still use it. */
+#include <cstring>
+
+#define FLX_ANGLE_TABLE 1                  /* k_rays_paths reads the shading's per-triangle table (flx_device.h: one definition per translation unit), as k_paths does at the same four waves per SIMD */
+#include "flx_context.h"
+#include "flx_kernel_util.h"
+#include "flx_query_args.h"
+
+using namespace flx;
+
+namespace flx {
+
+constexpr uint32_t TRACE_CHUNK_UNITS = 4;               /* units a wave draws with one atomic, a unit = the 64 items of one (block of rays, sample): 256 items, k_paths' PATH_CHUNK */
+constexpr uint32_t TRACE_WAVES = 4;                    /* waves per SIMD the paths kernel is built for (FLX_PATHS_WAVES: 128 registers) */
+
+struct TraceArgs { DeviceScene sc; DeviceFrame fr; };
+static_assert(sizeof(TraceArgs) + 64 <= 4096, "the paths kernel's arguments fit a 4 KB kernarg segment");
+
+template <bool LOCK>
+__global__ __launch_bounds__(256, TRACE_WAVES) void k_rays_paths(TraceArgs ta, const float4 *__restrict__ rays, const float4 *__restrict__ hits, float4 *__restrict__ slots,
+                                                                 float4 *__restrict__ lastOriginal, uint32_t *__restrict__ queue, uint32_t n, uint32_t units) {
+  const DeviceScene &sc = ta.sc;
+  const DeviceFrame &fr = ta.fr;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t S = (uint32_t)fr.samples;
+  f3 origin = F3(0.0f, 0.0f, 0.0f);           /* of the lane's ray: lightTrace's `camera` */
+  WorkCounters cnt = {};
+  bool alive = false;
+  PathState p;
+  PixelState ps;
+  int bounceIdx = 0;
+  float cosSampleN = 0.0f;
+  uint32_t rayIdx = 0, sampleIdx = 0;
+  uint32_t chunkUnit = 0, chunkNext = 0, chunkEnd = 0;      /* wave-uniform: the chunk's first unit, items of it handed out, its items */
+  bool itemsLeft = true;                                    /* wave-uniform */
+  auto finishPath = [&]() {                                 /* fragment:598 + what main() needs from the last sample */
+    const f3 r = p.finalColor + p.importancyFactor * frame_ambient(fr, 0);
+    slots[(size_t)sampleIdx * n + rayIdx] = make_float4(r.x, r.y, r.z, __uint_as_float((uint32_t)bounceIdx));
+    if (sampleIdx == S - 1u) lastOriginal[rayIdx] = make_float4(ps.originalColor.x, ps.originalColor.y, ps.originalColor.z, 1.0f);
+  };
+
+  for (;;) {
+    /* -- refill: dead lanes draw new items until the wave is full or the queue is dry ------------ */
+    for (;;) {
+      const unsigned long long idle = __ballot(!alive);
+      if (idle == 0ull) break;
+      if (chunkNext == chunkEnd) {
+        if (!itemsLeft) break;
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(queue, TRACE_CHUNK_UNITS);
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (base >= units) { itemsLeft = false; break; }
+        chunkUnit = base;
+        chunkNext = 0;
+        chunkEnd = (units - base > TRACE_CHUNK_UNITS ? TRACE_CHUNK_UNITS : units - base) * 64u;
+      }
+      const uint32_t nIdle = (uint32_t)__popcll(idle);
+      const uint32_t avail = chunkEnd - chunkNext;
+      const uint32_t take = nIdle < avail ? nIdle : avail;
+      const uint32_t rank = lane_rank(idle);
+      if (!alive && rank < take) {
+        const uint32_t j = chunkNext + rank, unit = chunkUnit + (j >> 6);      /* unit = block * S + sample: < units, which the host keeps below 2^32 */
+        const uint32_t block = unit / S, s = unit - block * S;
+        const uint32_t r = block * 64u + (j & 63u);                            /* block < 2^26: no overflow */
+        if (r < n) {
+          const float4 h = hits[(size_t)r * 2u];
+          const int tri = __float_as_int(h.w);
+          if (tri != -1) {
+            const float4 q0 = rays[(size_t)r * 2u], q1 = rays[(size_t)r * 2u + 1u];
+            origin = F3(q0.x, q0.y, q0.z);
+            ps.ndc_x = q0.w; ps.ndc_y = q1.w;
+            ps.seed = fr.view[0].random_seed;
+            ps.firstRayLength = 1.0f; ps.glassFilter = 0.0f; ps.originalRMEx = 0.0f; ps.originalTPOx = 0.0f;
+            ps.renderId.x = ps.renderId.y = ps.renderId.z = ps.renderId.w = 0.0f;
+            ps.renderOriginalId = ps.renderId;
+            ps.originalColor = F3(1.0f, 1.0f, 1.0f);
+            p.dontFilter = true;
+            p.finalColor = F3(0.0f, 0.0f, 0.0f);
+            p.importancyFactor = F3(1.0f, 1.0f, 1.0f);
+            p.ray.origin = origin; p.ray.dir = F3(q1.x, q1.y, q1.z);      /* as given: rayTracer does not normalise it, lightTrace steps along it by s */
+            p.lastHitPoint = origin;
+            p.hit.suv = F3(h.x, h.y, h.z);
+            p.hit.triangleId = tri;
+            p.hit.transformId = __float_as_int(hits[(size_t)r * 2u + 1u].x);
+            cosSampleN = flx_cos((float)s);
+            bounceIdx = 0;
+            rayIdx = r; sampleIdx = s;
+            /* loop guard of fragment:475 before the first bounce (fails only for bounces = 0 or minImportancy > 1) */
+            alive = fr.max_reflections > 0 && length(p.importancyFactor * ps.originalColor) >= fr.min_importancy * SQRT3;
+            if (!alive) finishPath();
+          }
+        }
+      }
+      chunkNext += take;
+    }
+    if (__ballot(alive) == 0ull) break;
+
+    /* -- one bounce for every live lane (fragment:475-596) ------------------------------------------ */
+    if (alive) {
+      bool cont = bounce<false, LOCK>(sc, fr, ps, p, origin, cosSampleN, bounceIdx, cnt);
+      bounceIdx++;
+      if (cont) cont = bounceIdx < fr.max_reflections && length(p.importancyFactor * ps.originalColor) >= fr.min_importancy * SQRT3;
+      if (!cont) { finishPath(); alive = false; }
+    }
+  }
+}
+
+/* fragment:608-632 for a ray (flx_kernel_util.h: resolve_pixel), and the row: r g b, 1.0 | s, entry, 2 x transform, bounce iterations — a miss: zeros, entry -1 */
+__global__ __launch_bounds__(256) void k_rays_resolve(const float4 *__restrict__ hits, const float4 *__restrict__ slots, const float4 *__restrict__ lastOriginal,
+                                                      float4 *__restrict__ out, uint32_t n, int samples) {
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  if (r >= n) return;
+  const float4 h0 = hits[(size_t)r * 2u], h1 = hits[(size_t)r * 2u + 1u];
+  float4 o0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), o1 = make_float4(0.0f, __int_as_float(-1), 0.0f, 0.0f);
+  if (__float_as_int(h0.w) != -1) {
+    f3 finalColor = F3(0.0f, 0.0f, 0.0f);
+    uint32_t shades = 0;
+    for (int s = 0; s < samples; s++) {
+      const float4 c = slots[(size_t)s * n + r];
+      finalColor = finalColor + F3(c.x, c.y, c.z);
+      shades += __float_as_uint(c.w);
+    }
+    const float invSamples = 1.0f / (float)samples;
+    finalColor = finalColor * invSamples;
+    const float4 oc = lastOriginal[r];
+    finalColor = finalColor * F3(oc.x, oc.y, oc.z);
+    o0 = make_float4(finalColor.x, finalColor.y, finalColor.z, 1.0f);
+    o1 = make_float4(h0.x, h0.w, h1.x, __uint_as_float(shades));
+  }
+  out[(size_t)r * 2u] = o0;
+  out[(size_t)r * 2u + 1u] = o1;
+}
+
+}  // namespace flx
+
+/* ---- the calls ------------------------------------------------------------------------------------------------------------------------------------- */
+
+static flx_status fail(flx_context *ctx, flx_status code, const char *msg) { return flx_fail(ctx, code, msg); }
+
+/* what both calls refuse before they look at an array */
+static flx_status trace_refused(flx_context *ctx, const flx_trace_params *p) {
+  if (!ctx->have_scene || !ctx->have_transforms) return fail(ctx, FLX_ERR_NO_SCENE, "flx_rays_trace: no scene and transforms uploaded");
+  switch (flx_trace_args_check(p != nullptr, p ? p->samples : 0, p ? p->max_reflections : 0, p ? p->texture_width : 0, 0u, 0u, 0u)) {
+    case FLX_TRACE_ARGS_OK: return FLX_OK;
+    case FLX_TRACE_PARAMS_NULL: return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace: params is NULL");
+    case FLX_TRACE_SAMPLES: return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace: samples is less than 1");
+    case FLX_TRACE_REFLECTIONS: return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace: max_reflections is negative");
+    default: return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace: texture_width is less than 1");
+  }
+}
+
+/* the frame bounce() is given: one view, the params' seed and ambient; no filter, no temporal */
+static void trace_frame(const flx_trace_params *p, DeviceFrame &fr) {
+  memset(&fr, 0, sizeof fr);
+  fr.width = fr.height = fr.rows = fr.frame_rows = fr.frames = fr.tile_rows = fr.tile_count = 1u;
+  fr.samples = p->samples; fr.max_reflections = p->max_reflections;
+  fr.samples_shift = -1;
+  fr.min_importancy = p->min_importancy;
+  fr.texture_width = (float)p->texture_width;
+  memcpy(fr.view[0].ambient, p->ambient, sizeof fr.view[0].ambient);
+  fr.view[0].random_seed = p->random_seed;
+}
+
+extern "C" flx_status flx_rays_trace_device(flx_context *ctx, const flx_trace_params *params, const void *d_rays, void *d_radiance, uint32_t n, void *producer_stream) {
+  if (!ctx) return FLX_ERR_INVALID;
+  flx_status s = trace_refused(ctx, params);
+  if (s || n == 0) return s;
+  const enum flx_trace_refusal arrays = flx_trace_args_check(1, params->samples, params->max_reflections, params->texture_width, (uint64_t)(uintptr_t)d_rays,
+                                                             (uint64_t)(uintptr_t)d_radiance, n);
+  switch (arrays) {
+    case FLX_TRACE_ARGS_OK: case FLX_TRACE_OVERLAP: break;      /* (overlap: said after the pointers are known to be the device's) */
+    case FLX_TRACE_NULL: return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_device: an array is NULL");
+    default: return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_device: n rows of 32 bytes leave the address space");
+  }
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)n * FLX_QUERY_ROW_BYTES;
+  if (!flx_rows_on_device(ctx, d_rays, bytes))
+    return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_device: the rays are not n rows in memory of the context's device, 16-byte aligned");
+  if (!flx_rows_on_device(ctx, d_radiance, bytes))
+    return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_device: the radiance is not n rows in memory of the context's device, 16-byte aligned");
+  if (arrays == FLX_TRACE_OVERLAP)
+    return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_device: the rays and the radiance overlap");
+  TraceArgs ta;
+  if ((s = flx_make_scene(ctx, ta.sc))) return s;           /* (refuses a scene that names a transform not uploaded) */
+  if ((s = flx_server_stop(ctx))) return s;                 /* as flx_render_device: the frame server's launch ends after the frames posted to it */
+  trace_frame(params, ta.fr);
+  const uint32_t S = (uint32_t)params->samples;
+  const uint32_t slab = flx_trace_slab_rays(S, ctx->trace_slab);
+  const uint32_t most = n < slab ? n : slab;                /* rays of the largest slab */
+  if (!ctx->d_trace_hits.fits((size_t)most * 2u) || !ctx->d_trace_slots.fits((size_t)most * S) || !ctx->d_trace_last.fits(most) || !ctx->d_trace_ctl) {
+    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier batch may still use the scratch that is about to go) */
+    if ((s = ctx->d_trace_hits.ensure(ctx, (size_t)most * 2u)) || (s = ctx->d_trace_slots.ensure(ctx, (size_t)most * S)) || (s = ctx->d_trace_last.ensure(ctx, most)) ||
+        (s = ctx->d_trace_ctl.ensure(ctx, 4)))
+      return s;
+  }
+  if (producer_stream) {
+    if (!ctx->query_produced) FLX_HIP(ctx, hipEventCreateWithFlags(&ctx->query_produced, hipEventDisableTiming));
+    FLX_HIP(ctx, hipEventRecord(ctx->query_produced, (hipStream_t)producer_stream));
+    FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->query_produced, 0));
+  }
+  if ((s = flx_angle_table(ctx, ta.sc))) return s;          /* the shading's per-triangle table, made again first where the scene or the transforms changed: FLX_ANGLE_TABLE above makes this file's bounce() read it */
+  const bool lock = FLX_LOCKSTEP && ta.sc.lock_entries != 0u;
+  const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
+  flx_context::TraceLaunch ran;
+  ran.n = n; ran.samples = S; ran.slab = slab; ran.lock = lock ? 1u : 0u;
+  for (uint64_t first = 0; first < n; first += slab) {
+    const uint32_t m = (uint32_t)(n - first < slab ? n - first : slab);
+    const float4 *rays = (const float4 *)d_rays + first * 2u;
+    float4 *out = (float4 *)d_radiance + first * 2u;
+    /* the words of the slab's launches: [0] the query's chunk cursor, [1] its waves that drew; [2] the paths kernel's unit cursor */
+    FLX_HIP(ctx, hipMemsetAsync(ctx->d_trace_ctl, 0, 4 * sizeof(uint32_t), ctx->stream));
+    QueryLaunch q;
+    if (!launch_ray_query(ta.sc, rays, ctx->d_trace_hits, m, FLX_RAYS_CLOSEST, ctx->d_trace_ctl, cus, ctx->query_groups, ctx->stream, &q))
+      return fail(ctx, FLX_ERR_DEVICE, "flx_rays_trace_device: the query kernel cannot have its LDS on this device");
+    FLX_HIP(ctx, hipGetLastError());
+    /* persistent grid: enough workgroups to fill every CU at the kernel's occupancy, no more than the items fill; flx_debug_set_query_groups sets it too */
+    const uint32_t units = ((m + 63u) >> 6) * S;              /* (block of 64 rays, sample) pairs: below 2^31 + 2^18 by flx_trace_slab_rays' rule; four fill a workgroup */
+    const uint32_t full = (units + 3u) / 4u;
+    const uint32_t blocks = ctx->query_groups ? ctx->query_groups : (full < cus * 8u ? full : cus * 8u);
+    uint32_t *queue = ctx->d_trace_ctl.get() + 2;
+    if (lock) hipLaunchKernelGGL(k_rays_paths<true>, dim3(blocks), dim3(256), 0, ctx->stream, ta, rays, ctx->d_trace_hits.get(), ctx->d_trace_slots.get(), ctx->d_trace_last.get(), queue, m, units);
+    else hipLaunchKernelGGL(k_rays_paths<false>, dim3(blocks), dim3(256), 0, ctx->stream, ta, rays, ctx->d_trace_hits.get(), ctx->d_trace_slots.get(), ctx->d_trace_last.get(), queue, m, units);
+    FLX_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_rays_resolve, dim3((m + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_trace_hits.get(), ctx->d_trace_slots.get(), ctx->d_trace_last.get(), out, m, params->samples);
+    FLX_HIP(ctx, hipGetLastError());
+    ran.slabs++; ran.path_groups = blocks; ran.query_groups = q.groups;
+  }
+  ctx->last_trace_rays = ran;
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_rays_trace(flx_context *ctx, const flx_trace_params *params, const float *rays, void *radiance, uint32_t n) {
+  if (!ctx) return FLX_ERR_INVALID;
+  flx_status s = trace_refused(ctx, params);
+  if (s || n == 0) return s;
+  if (!rays || !radiance) return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace: an array is NULL");
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)n * FLX_QUERY_ROW_BYTES;
+  if (!ctx->d_query_rays.fits((size_t)n * 2u) || !ctx->d_query_hits.fits((size_t)n * 2u)) {
+    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier query may still read or write the staging that is about to go) */
+    if ((s = ctx->d_query_rays.ensure(ctx, (size_t)n * 2u)) || (s = ctx->d_query_hits.ensure(ctx, (size_t)n * 2u))) return s;
+  }
+  FLX_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((s = flx_rays_trace_device(ctx, params, ctx->d_query_rays, ctx->d_query_hits, n, nullptr))) return s;
+  FLX_HIP(ctx, hipMemcpyAsync(radiance, ctx->d_query_hits, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_debug_set_trace_slab(flx_context *ctx, uint32_t rays) {
+  if (!ctx) return FLX_ERR_INVALID;
+  ctx->trace_slab = rays;
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_debug_last_trace(flx_context *ctx, uint32_t out[8]) {
+  if (!ctx || !out) return FLX_ERR_INVALID;
+  const flx_context::TraceLaunch &t = ctx->last_trace_rays;
+  out[0] = t.slabs; out[1] = t.slab; out[2] = t.path_groups; out[3] = t.lock; out[4] = t.n; out[5] = t.samples; out[6] = t.query_groups; out[7] = TRACE_CHUNK_UNITS * 64u;
+  return FLX_OK;
+}

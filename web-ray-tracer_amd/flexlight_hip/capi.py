@@ -35,6 +35,7 @@ EXPORTS = [
     "flx_scene_update", "flx_group_scene_update", "flx_debug_scene_read", "flx_scene_update_device", "flx_scene_upload_device",
     "flx_tree_build_device", "flx_tree_emit_device", "flx_scene_splice_device",
     "flx_rays_cast_device", "flx_rays_cast", "flx_debug_set_query_groups", "flx_debug_last_query",
+    "flx_rays_trace_device", "flx_rays_trace", "flx_debug_set_trace_slab", "flx_debug_last_trace",
 ]
 
 
@@ -51,6 +52,21 @@ MAX_BATCH_FRAMES = 32          # FLX_MAX_BATCH_FRAMES of include/flexlight_hip.h
 
 class FlexLightHipError(RuntimeError):
     pass
+
+
+class TraceParams(C.Structure):
+    """flx_trace_params of include/flexlight_hip_debug.h: what trace_rays takes of a frame's params (a ray batch has no width, height or camera)"""
+    _fields_ = [("samples", C.c_int32), ("max_reflections", C.c_int32), ("min_importancy", C.c_float), ("ambient", C.c_float * 3),
+                ("random_seed", C.c_float), ("texture_width", C.c_int32)]
+
+    def __init__(self, samples=1, max_reflections=5, min_importancy=0.3, ambient=(0.1, 0.1, 0.1), random_seed=0.0, texture_width=32):
+        super().__init__(int(samples), int(max_reflections), float(min_importancy), (C.c_float * 3)(*[float(a) for a in ambient]), float(random_seed),
+                         int(texture_width))
+
+    @classmethod
+    def of_frame(cls, params):
+        """the fields a frame's FrameParams shares with it"""
+        return cls(params.samples, params.max_reflections, params.min_importancy, tuple(params.ambient), params.random_seed, params.texture_width)
 
 
 def _load():
@@ -77,6 +93,10 @@ def _load():
         "flx_rays_cast": (C.c_int, [vp, fp, vp, u32, u32]),
         "flx_debug_set_query_groups": (C.c_int, [vp, u32]),
         "flx_debug_last_query": (C.c_int, [vp, C.POINTER(u32)]),
+        "flx_rays_trace_device": (C.c_int, [vp, C.POINTER(TraceParams), vp, vp, u32, vp]),
+        "flx_rays_trace": (C.c_int, [vp, C.POINTER(TraceParams), fp, vp, u32]),
+        "flx_debug_set_trace_slab": (C.c_int, [vp, u32]),
+        "flx_debug_last_trace": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_transforms_upload": (C.c_int, [vp, fp, fp, u32]),
         "flx_lights_upload": (C.c_int, [vp, fp, u32]),
         "flx_atlas_upload": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint8), u32, u32]),
@@ -251,19 +271,43 @@ def _device_array(x, dtype_name, width, device, what):
     return x.data_ptr(), x.shape[0]
 
 
-def _ray_rows(x, device):
-    """rays of cast_rays_device -> (device address, row count): a torch tensor [n, 8] (float32, contiguous, on cuda:`device`) or (address, n)"""
+def _ray_rows(x, device, call="cast_rays_device"):
+    """rays of cast_rays_device / trace_rays_device -> (device address, row count): a torch tensor [n, 8] (float32, contiguous, on cuda:`device`) or (address, n)"""
     if isinstance(x, tuple):
         address, n = x
         return int(address), int(n)
     import torch                               # (here and not at the top: capi imports without torch)
     if not isinstance(x, torch.Tensor):
-        raise TypeError("cast_rays_device: rays is a torch tensor or (address, rows)")
+        raise TypeError("%s: rays is a torch tensor or (address, rows)" % call)
     if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 8 or not x.is_contiguous():
-        raise ValueError("cast_rays_device: rays is a contiguous float32 tensor [n, 8]")
+        raise ValueError("%s: rays is a contiguous float32 tensor [n, 8]" % call)
     if x.device.type != "cuda" or x.device.index != device:
-        raise ValueError("cast_rays_device: rays is on %s, the context on cuda:%d" % (x.device, device))
+        raise ValueError("%s: rays is on %s, the context on cuda:%d" % (call, x.device, device))
     return x.data_ptr(), x.shape[0]
+
+
+def unpack_radiance(rows):
+    """radiance rows of trace_rays / trace_rays_device (uint8 [n, 32], a numpy array or a torch tensor: a tensor is copied to the host, which waits for the stream
+    it is asked on — sync() first where the batch ran on another) -> dict of columns: rgb float32 [n, 3], alpha float32 [n] (1 a hit, 0 a miss), s float32 [n] (of the
+    first hit), entry int32 [n] (-1: none), transform2 int32 [n] (2 x transform number), shades uint32 [n] (bounce iterations shaded over all samples)"""
+    if not isinstance(rows, np.ndarray):
+        rows = rows.detach().cpu().numpy()
+    words = np.ascontiguousarray(rows, np.uint8).reshape(-1, 32).view(np.uint32)
+    return {"rgb": words[:, 0:3].view(np.float32).copy(), "alpha": words[:, 3].view(np.float32).copy(), "s": words[:, 4].view(np.float32).copy(),
+            "entry": words[:, 5].view(np.int32).copy(), "transform2": words[:, 6].view(np.int32).copy(), "shades": words[:, 7].copy()}
+
+
+def noise_coordinates(n):
+    """float32 [n, 2]: noise coordinates for the n rays of a batch (words 3 and 7 of their rows), spread over [-1, 1)^2 as a frame's pixel centres are — the
+    centres of a grid of ceil(sqrt(n)) columns, row by row.  Rays with equal coordinates draw equal random numbers; these are all different."""
+    n = int(n)
+    cols = max(1, int(np.ceil(np.sqrt(n))))
+    rows = max(1, -(-n // cols))
+    k = np.arange(n)
+    out = np.empty((n, 2), np.float32)
+    out[:, 0] = (((k % cols).astype(np.float32) + np.float32(0.5)) / np.float32(cols)) * np.float32(2.0) - np.float32(1.0)
+    out[:, 1] = (((k // cols).astype(np.float32) + np.float32(0.5)) / np.float32(rows)) * np.float32(2.0) - np.float32(1.0)
+    return out
 
 
 def unpack_hits(buf):
@@ -471,6 +515,50 @@ class Context:
         out = (C.c_uint32 * 8)()
         self._check(LIB.flx_debug_last_query(self._h, out), "flx_debug_last_query")
         return dict(zip(("lds_count", "pre", "groups", "waves", "n", "what", "chunk", "draws"), list(out)))
+
+    def trace_rays_device(self, rays, params, out=None, stream=None):
+        """flx_rays_trace_device: the radiance the renderer sees along rays of the caller's own, in device memory.  rays: a torch tensor [n, 8] (float32, contiguous,
+        on the context's device: origin, noise x, direction, noise y — noise_coordinates) or (address, n); params: TraceParams; out: None (a new uint8 tensor
+        [n, 32]), such a tensor to write into, or an address (then the address comes back); stream: the torch.cuda.Stream (or raw hipStream_t) on which the rays were
+        written, as for cast_rays_device.  Returns the radiance rows ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE: sync() before they are read on another
+        stream (unpack_radiance reads them).  Both arrays stay alive until then."""
+        r, n = _ray_rows(rays, self._device, "trace_rays_device")
+        if params is not None and not isinstance(params, TraceParams):
+            raise TypeError("trace_rays_device: params is a TraceParams")      # (None goes to the library, which refuses it)
+        if out is None:
+            import torch
+            out = torch.empty((n, 32), dtype=torch.uint8, device="cuda:%d" % self._device)
+        if isinstance(out, int):
+            o = out
+        else:
+            if out.dtype.is_floating_point or out.device.type != "cuda" or out.device.index != self._device or not out.is_contiguous() or out.numel() * out.element_size() < n * 32:
+                raise ValueError("trace_rays_device: out is a contiguous integer tensor of at least n x 32 bytes on the context's device")
+            o = out.data_ptr()
+        if stream is not None and not isinstance(stream, int):
+            handle = stream.cuda_stream
+            if handle == 0:
+                stream.synchronize()
+            stream = handle
+        self._check(LIB.flx_rays_trace_device(self._h, C.byref(params) if params is not None else None, C.c_void_p(r), C.c_void_p(o), n, C.c_void_p(stream) if stream else None), "flx_rays_trace_device")
+        return out
+
+    def trace_rays(self, rays, params):
+        """flx_rays_trace: rays [n, 8] float32 in host memory (origin, noise x, direction, noise y) -> radiance rows uint8 [n, 32], complete (unpack_radiance)"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros((rays.shape[0], 32), np.uint8)
+        self._check(LIB.flx_rays_trace(self._h, C.byref(params) if params is not None else None, _fp(rays), out.ctypes.data_as(C.c_void_p), rays.shape[0]), "flx_rays_trace")
+        return out
+
+    def set_trace_slab(self, rays):
+        """flx_debug_set_trace_slab: most rays of a slab of a traced batch (0: the library's ceiling)"""
+        self._check(LIB.flx_debug_set_trace_slab(self._h, int(rays)), "flx_debug_set_trace_slab")
+
+    def last_trace(self):
+        """flx_debug_last_trace -> dict (zeros when no batch was traced): slabs, slab (rays of a full one), path_groups (of 256 lanes, last slab), lockstep, n,
+        samples, query_groups (of 1024 lanes, last slab), chunk (items per draw)"""
+        out = (C.c_uint32 * 8)()
+        self._check(LIB.flx_debug_last_trace(self._h, out), "flx_debug_last_trace")
+        return dict(zip(("slabs", "slab", "path_groups", "lockstep", "n", "samples", "query_groups", "chunk"), list(out)))
 
     def scene_read(self, which, rows=None):
         """flx_debug_scene_read: the device's 'geometry' [rows, 12], 'attributes' [rows, 28], 'walk' (the threaded copy) or 'fwd' (the forward-ordered

@@ -43,6 +43,21 @@ function castRaysOn (context, rays, what) {
   return out;
 }
 
+/* flx_rays_trace on a context whose scene, lights, transforms and atlases are up: the radiance rows as the library writes them, 8 words a ray
+ * (include/flexlight_hip_debug.h), unpacked into typed arrays */
+function traceRaysOn (context, rays, params) {
+  if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('traceRays: rays is a Float32Array of 8 floats per ray');
+  const rows = native().traceRays(context, rays, params);
+  const n = rays.length / 8;
+  const words = new Uint32Array(rows), f = new Float32Array(rows), i32 = new Int32Array(rows);
+  const out = { radiance: new Float32Array(4 * n), s: new Float32Array(n), entry: new Int32Array(n), transform: new Int32Array(n), shades: new Uint32Array(n) };
+  for (let k = 0; k < n; k++) {
+    out.radiance[4 * k] = f[8 * k]; out.radiance[4 * k + 1] = f[8 * k + 1]; out.radiance[4 * k + 2] = f[8 * k + 2]; out.radiance[4 * k + 3] = f[8 * k + 3];
+    out.s[k] = f[8 * k + 4]; out.entry[k] = i32[8 * k + 5]; out.transform[k] = i32[8 * k + 6] >> 1; out.shades[k] = words[8 * k + 7];
+  }
+  return out;
+}
+
 class PathTracerHIP {
   constructor (canvas, scene, camera, config, options) {
     this.type = 'pathtracer';
@@ -240,6 +255,34 @@ class PathTracerHIP {
     if (this._devices) throw new Error('castRays: one GPU only (a group of GPUs casts no rays)');
     this._uploadFrameState();
     return castRaysOn(this._context(), rays, what);
+  }
+
+  /* What the renderer SEES along rays of the application's own: another projection (panorama, fisheye, orthographic, a stereo pair), light probes, reflection
+   * rays of a hybrid renderer (flx_rays_trace, include/flexlight_hip_debug.h "ray queries").  rays: Float32Array, 8 floats per ray — origin x y z, noise x,
+   * direction x y z (not normalised), noise y.  The two noise coordinates stand where a frame has the pixel's position in [-1, 1): rays with equal noise
+   * coordinates draw equal random numbers, so give every ray its own.  options: { samples, maxReflections, minImportancy, ambient, randomSeed, textureWidth },
+   * each by default what the next frame would use — config.samplesPerRay, config.maxReflections, config.minImportancy, scene.ambientLight, the texture width of
+   * scene.standardTextureSizes — and seed 0.  Returns { radiance: Float32Array(4 n) (r g b and 1 for a hit; a miss is 0 0 0 0, not the ambient light),
+   * s: Float32Array(n) (the first hit lies at origin + s * direction), entry: Int32Array(n) (-1: none), transform: Int32Array(n), shades: Uint32Array(n) (bounce
+   * iterations shaded over all samples) }: per ray a frame's pixel without filter and temporal — the samples averaged, times the first surfaces' colour as the
+   * LAST sample left it.  It waits for the answer; frames in flight finish unchanged. */
+  traceRays (rays, options) {
+    if (this._devices) throw new Error('traceRays: one GPU only (a group of GPUs traces no rays)');
+    this._uploadFrameState();
+    return traceRaysOn(this._context(), rays, this.traceParams(options));
+  }
+
+  traceParams (options) {
+    const o = options || {};
+    const pick = (v, d) => (v === undefined ? d : v);
+    return {
+      samples: pick(o.samples, this.config.samplesPerRay),
+      maxReflections: pick(o.maxReflections, this.config.maxReflections),
+      minImportancy: pick(o.minImportancy, this.config.minImportancy),
+      ambient: Array.from(pick(o.ambient, this.scene.ambientLight)).slice(0, 3),
+      randomSeed: pick(o.randomSeed, 0),
+      textureWidth: pick(o.textureWidth, Math.floor(2048 / this.scene.standardTextureSizes[0]))
+    };
   }
 
   renderFrame (options) {

@@ -277,6 +277,39 @@ static bool read_params(napi_env env, napi_value o, flx_frame_params *p) {
   return true;
 }
 
+/* traceRays(handle, rays Float32Array(8 n), params { samples, maxReflections, minImportancy, ambient, randomSeed?, textureWidth }) -> ArrayBuffer(32 n):
+ * flx_rays_trace, the radiance rows as the library writes them (include/flexlight_hip_debug.h) */
+static napi_value TraceRays(napi_env env, napi_callback_info info) {
+  napi_value argv[3];
+  if (!get_args(env, info, 3, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  void *rays; size_t len;
+  if (!typed(env, argv[1], napi_float32_array, &rays, &len)) return nullptr;
+  if (len % 8 != 0 || len / 8 > 0xffffffffu) { napi_throw_range_error(env, nullptr, "traceRays: a ray needs 8 floats (origin, noise x, direction, noise y)"); return nullptr; }
+  flx_trace_params p;
+  memset(&p, 0, sizeof p);
+  double d = 0;
+  /* a JavaScript number -> int32_t: refused where the cast would not be defined (NaN, beyond the type's range); the library judges the values that fit */
+  auto int32 = [&](const char *key, int32_t *out) {
+    if (!num(env, argv[2], key, &d)) return false;
+    if (!(d >= -2147483648.0 && d <= 2147483647.0)) { napi_throw_range_error(env, nullptr, (std::string("traceRays: ") + key + " is not a number an int32 holds").c_str()); return false; }
+    *out = (int32_t)d;
+    return true;
+  };
+  if (!int32("samples", &p.samples) || !int32("maxReflections", &p.max_reflections)) return nullptr;
+  if (!num(env, argv[2], "minImportancy", &d)) return nullptr; p.min_importancy = (float)d;
+  if (!floats(env, argv[2], "ambient", p.ambient, 3)) return nullptr;
+  d = 0; if (!num(env, argv[2], "randomSeed", &d, false)) return nullptr; p.random_seed = (float)d;
+  if (!int32("textureWidth", &p.texture_width)) return nullptr;
+  void *rows = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, (len / 8) * 32, &rows, &buf));
+  flx_status rc = flx_rays_trace(ctx, &p, (const float *)rays, rows, (uint32_t)(len / 8));
+  if (rc != FLX_OK) return fail(env, ctx, "flx_rays_trace", rc);
+  return buf;
+}
+
 /* tileRowCount(params) -> rows this context renders */
 static napi_value TileRowCount(napi_env env, napi_callback_info info) {
   napi_value argv[1];
@@ -1066,7 +1099,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
