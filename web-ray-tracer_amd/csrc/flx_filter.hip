@@ -44,8 +44,9 @@ __device__ __forceinline__ f4 fetch(Tex t, int W, int H, int x, int y_gl) { retu
 __device__ __forceinline__ bool rawEq3(uint32_t a, uint32_t b) { return ((a ^ b) & 0x00ffffffu) == 0u; }
 __device__ __forceinline__ uint32_t rawW(uint32_t q) { return q >> 24; }
 
-/* The second and the final filter reach at most 9 texels from the centre (stencil radius 3 x a scale of at most 3, SURVEY §8a
- * F2 / F3): a workgroup's 16 x 16 texels and their halo of the five planes are staged in LDS once (34 x 34 x 5 words = 23 KB)
+/* The second and the final filter reach at most 8 texels from the centre (stencil radius 3 x a scale that stays below 3: 1 + 2 tanh
+ * and 0.7 + 2 tanh; tests/test_filter_literal_cpu.py tabulates the taps of all 256 x 256 byte pairs — FILTER_HALO
+ * keeps a texel to spare): a workgroup's 16 x 16 texels and their halo of the five planes are staged in LDS once (34 x 34 x 5 words = 23 KB)
  * and the ~37 x 5 data-dependent taps of every texel read from there.  Outside the image, and for a plane that is not bound,
  * the tile holds the 0 texelFetch yields there (fetchRaw). */
 constexpr int FILTER_HALO = 9;
