@@ -240,6 +240,42 @@ flx_status flx_scene_splice_device(flx_context *ctx, uint32_t first_entry, uint3
                                    const void *d_geometry /* n_new * 12 floats, on ctx's device */, const void *d_attributes /* n_new * 28 floats */, uint32_t n_new,
                                    const void *d_ids /* n_new_ids int32, relative to the block's first entry, or NULL */, uint32_t n_new_ids,
                                    void *producer_stream /* hipStream_t that wrote the arrays, or NULL: complete */);
+/* ---- textures ------------------------------------------------------------------------------------- */
+/* Beyond the drop-in boundary, like the scene paths above (flx_atlas_upload of a finished atlas is the drop-in call).  An atlas BUILT ON THE DEVICE from its source
+ * images, and ONE texture of it replaced in place.  The rule is the project's own (js/sceneFile.js: buildAtlas, which stays the yardstick): with tw = floor(2048 /
+ * cell_w), the atlas is cell_w * tw wide and cell_h * n high (the reference's too-tall canvas, modules/pathtracerWGL2.js:85-104: fetchTexVal divides by it); image i
+ * fills the cell at column i % tw, row floor(i / tw); destination texel (x, y) of a cell reads source texel (floor((2x + 1) * width / (2 * cell_w)), floor((2y + 1) *
+ * height / (2 * cell_h))) — integers throughout, = Math.floor((x + 0.5) * width / cell_w) for every size; every texel outside the n cells is transparent black.
+ * An image has tight rows.  FLX_IMAGE_RGBA8: 4 bytes a texel, copied.  FLX_IMAGE_RGBA32F: 4 floats a texel, each stored as the library's RGBA8 render targets store
+ * a channel: floor(clamp(x, 0, 1) * 255 + 0.5), NaN -> 0; the nearest texel is picked first, then quantised.  What the frame kernels read keeps its layout and bytes.
+ * flx_textures_upload replaces atlas `which` (0 albedo, 1 pbr, 2 translucency) from images in HOST memory, flx_textures_upload_device from images in memory of ctx's
+ * device (a torch tensor, a decoded video frame, a frame flx_render_device made): 4-byte aligned for RGBA8, 16 for RGBA32F.  n == 0 is "none", exactly
+ * flx_atlas_upload(ctx, which, NULL, 0, 0).  The context remembers cell_w, cell_h and n for later cell updates; flx_atlas_upload forgets them (a prebuilt atlas has
+ * no known cells).  Ordered like flx_atlas_upload and flx_scene_upload_device: the frame server's launch ends, a second lane's frames in flight are waited for, the
+ * kernel runs on the context's stream behind its own frames, and the call waits for that stream before it returns: the caller's pixels are free.
+ * flx_texture_update[_device] replaces cell `index` of the resident atlas from one image of any size and either format; no other byte of the atlas changes.  Ordered
+ * like flx_scene_update_device: the image is resampled into memory of the context's on a stream of its own (behind producer_stream), the host waits for that alone —
+ * the context's frames in flight go on, the caller's pixels are free on return — and the cell is copied in behind those frames.  A frame begun before the call shows
+ * the old texture, a frame begun after it the new one.
+ * producer_stream: as for flx_scene_update_device.
+ * Refusals, FLX_ERR_INVALID each with a message of its own, the atlas and what the context remembers of it exactly as they were, nothing enqueued on the context's
+ * stream; in this order: which not 0 .. 2; images NULL with n > 0; cell_w 0 or above 2048; cell_h 0; then the first offending image and within it the first of:
+ * pixels NULL, a dimension of 0, an unknown format, and — device variants — pixels not in memory of ctx's device, not aligned, or in an allocation that ends before
+ * the image does; last, an atlas of 2^31 texels in height or more.  The update, instead of the cell sizes: no atlas built by flx_textures_upload* is resident;
+ * index >= n.  A group keeps the host calls, as for scenes. */
+#define FLX_IMAGE_RGBA8   0u
+#define FLX_IMAGE_RGBA32F 1u
+typedef struct flx_image { const void *pixels; uint32_t width, height, format; } flx_image;      /* tight rows */
+flx_status flx_textures_upload(flx_context *ctx, int which, const flx_image *images, uint32_t n, uint32_t cell_w, uint32_t cell_h);      /* pixels in host memory */
+flx_status flx_textures_upload_device(flx_context *ctx, int which, const flx_image *images, uint32_t n, uint32_t cell_w, uint32_t cell_h,
+                                      void *producer_stream /* hipStream_t that wrote the pixels, or NULL: complete */);      /* pixels on ctx's device */
+flx_status flx_texture_update(flx_context *ctx, int which, uint32_t index, const flx_image *image);
+flx_status flx_texture_update_device(flx_context *ctx, int which, uint32_t index, const flx_image *image, void *producer_stream);
+flx_status flx_group_textures_upload(flx_group *group, int which, const flx_image *images, uint32_t n, uint32_t cell_w, uint32_t cell_h);
+flx_status flx_group_texture_update(flx_group *group, int which, uint32_t index, const flx_image *image);
+/* Atlas `which` as the device holds it, after everything enqueued so far: *width, *height (0, 0: none) and, where out is not NULL, its width * height * 4 bytes
+ * (FLX_ERR_INVALID where `bytes` is less).  out may be NULL to ask the size. */
+flx_status flx_debug_atlas_read(flx_context *ctx, int which, uint8_t *out, size_t bytes, uint32_t *width, uint32_t *height);
 /* ---- ray queries ---------------------------------------------------------------------------------- */
 /* Beyond the drop-in boundary, like the vertex updates above, and bound the same way (the N-API addon and the JavaScript renderers bind the host call: castRays).
  * Rays of the CALLER'S OWN cast at the resident scene: what does this ray hit, is this point lit from there, which object is under the cursor — what every frame asks

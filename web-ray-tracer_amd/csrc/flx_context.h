@@ -103,6 +103,13 @@ struct flx_context {
   DeviceBuffer<float> d_lights;
   DeviceBuffer<uchar4> d_atlas[3];
   uint32_t atlas_w[3] = { 0, 0, 0 }, atlas_h[3] = { 0, 0, 0 };
+  /* flx_textures_upload / flx_texture_update (flx_atlas.hip).  atlas_cells: what the resident atlas was built with (n 0: none, or a prebuilt one: no cell updates).
+   * d_texture_table: the build's table of sources, filled through the staging ring.  d_texture_src: the host variants' sources, staged; nothing in flight reads it
+   * when a call returns.  d_texture_cell: an update's resampled cell, read on the context's stream behind its frames: update_done guards it like the row stage. */
+  struct { uint32_t w = 0, h = 0, n = 0; } atlas_cells[3];
+  DeviceBuffer<flx::AtlasSource> d_texture_table;
+  DeviceBuffer<uint4> d_texture_src;
+  DeviceBuffer<uint32_t> d_texture_cell;
   uint32_t n_entries = 0, n_ids = 0, n_transforms = 0, n_lights = 0;
   uint32_t max_transform = 0;                   /* largest transform number an entry names */
   bool have_scene = false, have_transforms = false, have_lights = false;

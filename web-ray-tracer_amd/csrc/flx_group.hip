@@ -420,6 +420,10 @@ extern "C" flx_status flx_group_atlas_upload(flx_group *g, int which, const uint
 extern "C" flx_status flx_group_scene_update(flx_group *g, uint32_t first_entry, uint32_t n_entries, const float *geometry, const float *attributes) {
   FLX_GROUP_EACH(g, flx_scene_update(c, first_entry, n_entries, geometry, attributes));
 }
+extern "C" flx_status flx_group_textures_upload(flx_group *g, int which, const flx_image *images, uint32_t n, uint32_t cell_w, uint32_t cell_h) {
+  FLX_GROUP_EACH(g, flx_textures_upload(c, which, images, n, cell_w, cell_h));
+}
+extern "C" flx_status flx_group_texture_update(flx_group *g, int which, uint32_t index, const flx_image *image) { FLX_GROUP_EACH(g, flx_texture_update(c, which, index, image)); }
 extern "C" flx_status flx_group_scene_upload_view(flx_group *g, const flx_scene_view *scene) { FLX_GROUP_EACH(g, flx_scene_upload_view(c, scene)); }
 
 /* n_frames frames (a batch; 1 = one frame) of a camera path on all contexts of the group; the frames arrive on the host. */

@@ -179,6 +179,15 @@ void launch_splice_rows(const float4 *geometry, const float4 *attributes, const 
                         float4 *geometryOut, float4 *attributesOut, hipStream_t stream);
 void launch_splice_ids(const int32_t *ids, uint32_t n_ids, const int32_t *blockIds, uint32_t n_block, uint32_t below, uint32_t above, uint32_t first, int32_t delta,
                        int32_t *out, hipStream_t stream);
+/* flx_textures_upload / flx_texture_update (flx_atlas.hip): n source images nearest-resampled into cells of w x h texels of an RGBA8 image of `pitch` texels a row:
+ * image i fills cell first_cell + i, at column cell % tw, row cell / tw; texel (x, y) of a cell <- source texel (floor((2x + 1) sw / 2w), floor((2y + 1) sh / 2h)),
+ * copied (ATLAS_RGBA8) or quantised by pack_rgba8 (ATLAS_RGBA32F).  The sources: table[0 .. n) in device memory, or — table nullptr, n = 1 — *one, passed by value.
+ * It writes the texels of those cells and no others.  One launch: at most ATLAS_TABLE_IMAGES images (a slot of the staging ring holds their table). */
+enum { ATLAS_RGBA8 = 0, ATLAS_RGBA32F = 1 };
+struct AtlasSource { const void *pixels; uint32_t sw, sh, format, pad; };
+constexpr uint32_t ATLAS_TABLE_IMAGES = 2048;
+void launch_atlas_cells(uint32_t *dst, uint32_t pitch, uint32_t w, uint32_t h, uint32_t tw, uint32_t first_cell, uint32_t n, const AtlasSource *table,
+                        const AtlasSource *one, hipStream_t stream);
 /* ray queries (flx_query.hip): n caller's rays (2 float4 each) walked through the scene by one persistent launch, a hit row (2 float4) per ray; what: FLX_RAYS_*.
  * ctl: two device words, zeroed in front of the launch on the same stream: [0] the cursor the waves draw chunks of QUERY_CHUNK consecutive rays from, [1] <- waves
  * that drew at least one.  groups: workgroups wanted (0: one per compute unit, no more than the rays fill).  *ran: what was launched.  false: the kernel cannot have

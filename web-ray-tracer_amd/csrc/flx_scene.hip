@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "flx_context.h"
+#include "flx_texture_args.h"
 
 using namespace flx;
 
@@ -231,10 +232,10 @@ static void build_lockstep(const float *geometry, uint32_t n, std::vector<float>
   }
 }
 
-/* whether [p, p + bytes) is device memory of this context's device, 16-byte aligned */
-static bool rows_on_device(const flx_context *ctx, const void *p, size_t bytes) {
+/* whether [p, p + bytes) is device memory of this context's device, 16-byte aligned (or to `align`, a power of two) */
+static bool rows_on_device(const flx_context *ctx, const void *p, size_t bytes, uintptr_t align = 16) {
   hipPointerAttribute_t at;
-  if (((uintptr_t)p & 15u) || hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  if (((uintptr_t)p & (align - 1u)) || hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
   if (at.type != hipMemoryTypeDevice || at.device != ctx->device) return false;
   hipDeviceptr_t base = nullptr;
   size_t size = 0;
@@ -787,10 +788,141 @@ extern "C" flx_status flx_atlas_upload(flx_context *ctx, int which, const uint8_
   size_t bytes = rgba ? (size_t)width * height * 4 : 0;
   flx_status s;
   if ((s = shared_upload_begin(ctx))) return s;
+  ctx->atlas_cells[which] = {};              /* (a prebuilt atlas has no known cells: flx_texture_update is refused after it) */
   if ((s = upload(ctx, ctx->d_atlas[which], rgba, bytes))) return s;
   ctx->atlas_w[which] = bytes ? width : 0;
   ctx->atlas_h[which] = bytes ? height : 0;
   return shared_upload_end(ctx);
+}
+
+/* ---- atlases built on the device, one texture replaced in place (flx_atlas.hip) ---------------------------------------------------------------------------------
+ * The argument rules that need no device: flx_texture_args.h. */
+static_assert(FLX_IMAGE_RGBA8 == ATLAS_RGBA8 && FLX_IMAGE_RGBA32F == ATLAS_RGBA32F, "the kernel's formats are the header's");
+static const char *const TEXTURE_NOT_ON_DEVICE = "an image's pixels are not in memory of the context's device, not aligned (4 bytes for RGBA8, 16 for RGBA32F), or the allocation ends before the image";
+
+static bool image_on_device(const flx_context *ctx, const flx_image *image) {
+  const uint64_t bytes = flx_image_bytes(image);
+  return bytes != 0u && bytes <= SIZE_MAX && rows_on_device(ctx, image->pixels, (size_t)bytes, flx_image_texel_bytes(image->format));
+}
+
+/* host images staged behind each other in d_texture_src, each at a multiple of 16 bytes, by copies on `stream`; sources[i] <- where image i then is.  Nothing in
+ * flight reads the buffer: every call that fills it waits for the kernel that reads it before it returns. */
+static flx_status stage_host_images(flx_context *ctx, const flx_image *images, uint32_t n, std::vector<AtlasSource> &sources, hipStream_t stream) {
+  size_t total = 0;
+  for (uint32_t i = 0; i < n; i++) total += ((size_t)flx_image_bytes(images + i) + 15u) / 16u;
+  flx_status s;
+  if ((s = ctx->d_texture_src.ensure(ctx, total))) return s;
+  size_t at = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const size_t bytes = (size_t)flx_image_bytes(images + i);
+    FLX_HIP(ctx, hipMemcpyAsync(ctx->d_texture_src + at, images[i].pixels, bytes, hipMemcpyHostToDevice, stream));
+    sources[i] = AtlasSource{ ctx->d_texture_src + at, images[i].width, images[i].height, images[i].format, 0u };
+    at += (bytes + 15u) / 16u;
+  }
+  return FLX_OK;
+}
+
+static flx_status textures_upload(flx_context *ctx, int which, const flx_image *images, uint32_t n, uint32_t cell_w, uint32_t cell_h, void *producer_stream, bool device) {
+  if (!ctx) return FLX_ERR_INVALID;
+  if (flx_textures_refusal r = flx_textures_cells_check(which, images != nullptr, n, cell_w, cell_h)) return fail(ctx, FLX_ERR_INVALID, FLX_TEXTURES_UPLOAD_REFUSAL[r]);
+  if (n == 0) return flx_atlas_upload(ctx, which, nullptr, 0, 0);      /* "none" */
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  for (uint32_t i = 0; i < n; i++) {
+    if (flx_textures_refusal r = flx_image_check(images + i)) return fail(ctx, FLX_ERR_INVALID, FLX_TEXTURES_UPLOAD_REFUSAL[r]);
+    if (device ? !image_on_device(ctx, images + i) : flx_image_bytes(images + i) == 0u)
+      return fail(ctx, FLX_ERR_INVALID, device ? (std::string("flx_textures_upload_device: ") + TEXTURE_NOT_ON_DEVICE).c_str() : "flx_textures_upload: an image's bytes do not fit 64 bits");
+  }
+  if ((uint64_t)cell_h * n >= 0x80000000ull) return fail(ctx, FLX_ERR_INVALID, FLX_TEXTURES_UPLOAD_REFUSAL[FLX_TEXTURES_TALL]);
+  const uint32_t tw = flx_atlas_cells_per_row(cell_w), W = flx_atlas_width(cell_w), H = flx_atlas_height(cell_h, n);
+  std::vector<AtlasSource> sources(n);
+  flx_status s;
+  if ((s = ensure_side_stream(ctx))) return s;
+  if (device) {
+    for (uint32_t i = 0; i < n; i++) sources[i] = AtlasSource{ images[i].pixels, images[i].width, images[i].height, images[i].format, 0u };
+    if (producer_stream) FLX_HIP(ctx, hipEventRecord(ctx->update_produced, (hipStream_t)producer_stream));
+  }
+  /* from here the atlas changes: until the end the context has none */
+  if ((s = shared_upload_begin(ctx))) return s;
+  ctx->atlas_cells[which] = {}; ctx->atlas_w[which] = ctx->atlas_h[which] = 0;
+  if ((s = make_room(ctx, ctx->d_atlas[which], (size_t)W * H * 4))) return s;
+  if (device && producer_stream) FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->update_produced, 0));
+  if (!device && (s = stage_host_images(ctx, images, n, sources, ctx->stream))) return s;
+  /* transparent black outside the n cells (the buffer may come from a larger atlas): the rows from the first cell row that is not full */
+  uint32_t *const atlas = (uint32_t *)ctx->d_atlas[which].get();
+  const size_t full_rows = (size_t)(n / tw) * cell_h;
+  if (full_rows < H) FLX_HIP(ctx, hipMemsetAsync(atlas + full_rows * W, 0, ((size_t)H - full_rows) * W * 4, ctx->stream));
+  for (uint32_t first = 0; first < n; first += ATLAS_TABLE_IMAGES) {
+    const uint32_t count = std::min(n - first, ATLAS_TABLE_IMAGES);
+    const uint64_t sv = ctx->scene_version, tv = ctx->structure_version;
+    if ((s = upload(ctx, ctx->d_texture_table, sources.data() + first, (size_t)count * sizeof(AtlasSource)))) return s;      /* (the staging ring; in stream order) */
+    ctx->scene_version = sv; ctx->structure_version = tv;      /* (one upload, counted once) */
+    launch_atlas_cells(atlas, W, cell_w, cell_h, tw, first, count, ctx->d_texture_table, nullptr, ctx->stream);
+    FLX_HIP(ctx, hipGetLastError());
+  }
+  ctx->atlas_w[which] = W; ctx->atlas_h[which] = H;
+  ctx->atlas_cells[which].w = cell_w; ctx->atlas_cells[which].h = cell_h; ctx->atlas_cells[which].n = n;
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));          /* the caller's pixels are not retained (and: shared_upload_end) */
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_textures_upload(flx_context *ctx, int which, const flx_image *images, uint32_t n, uint32_t cell_w, uint32_t cell_h) {
+  return textures_upload(ctx, which, images, n, cell_w, cell_h, nullptr, false);
+}
+extern "C" flx_status flx_textures_upload_device(flx_context *ctx, int which, const flx_image *images, uint32_t n, uint32_t cell_w, uint32_t cell_h, void *producer_stream) {
+  return textures_upload(ctx, which, images, n, cell_w, cell_h, producer_stream, true);
+}
+
+/* One cell replaced, step for step as flx_scene_update_device and commit_rows: the image resampled on update_stream into the stage of one cell (the host waits for
+ * that stream alone: the frames in flight go on, the caller's pixels are free); then the frame server's launch ends, the second lane's frames are waited for, and the
+ * context's stream copies the stage into the cell behind its own frames in flight — the same kernel, the stage as an RGBA8 source of the cell's size. */
+static flx_status texture_update(flx_context *ctx, int which, uint32_t index, const flx_image *image, void *producer_stream, bool device) {
+  if (!ctx) return FLX_ERR_INVALID;
+  const uint32_t cells = which >= 0 && which <= 2 && ctx->d_atlas[which] ? ctx->atlas_cells[which].n : 0u;
+  if (flx_textures_refusal r = flx_texture_update_check(which, cells, index, image)) return fail(ctx, FLX_ERR_INVALID, FLX_TEXTURE_UPDATE_REFUSAL[r]);
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  if (device ? !image_on_device(ctx, image) : flx_image_bytes(image) == 0u)
+    return fail(ctx, FLX_ERR_INVALID, device ? (std::string("flx_texture_update_device: ") + TEXTURE_NOT_ON_DEVICE).c_str() : "flx_texture_update: the image's bytes do not fit 64 bits");
+  const uint32_t w = ctx->atlas_cells[which].w, h = ctx->atlas_cells[which].h, tw = flx_atlas_cells_per_row(w);
+  flx_status s;
+  if ((s = ensure_side_stream(ctx))) return s;
+  if (ctx->update_pending) { FLX_HIP(ctx, hipEventSynchronize(ctx->update_done)); ctx->update_pending = false; }      /* (the last update's copy reads the stage) */
+  if ((s = ctx->d_texture_cell.ensure(ctx, (size_t)w * h))) return s;
+  if ((s = check_on_side_stream(ctx, device ? producer_stream : nullptr))) return s;
+  std::vector<AtlasSource> source(1, AtlasSource{ image->pixels, image->width, image->height, image->format, 0u });
+  if (!device && (s = stage_host_images(ctx, image, 1, source, ctx->update_stream))) return s;
+  launch_atlas_cells(ctx->d_texture_cell, w, w, h, 1u, 0u, 1u, nullptr, &source[0], ctx->update_stream);
+  FLX_HIP(ctx, hipGetLastError());
+  if ((s = await_check(ctx))) return s;
+  if ((s = flx_server_stop(ctx)) || (s = shared_upload_begin(ctx))) return s;          /* (a running frame server reads the atlas) */
+  ctx->scene_version++; ctx->structure_version++;
+  FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->update_checked, 0));
+  const AtlasSource staged = { ctx->d_texture_cell.get(), w, h, ATLAS_RGBA8, 0u };
+  launch_atlas_cells((uint32_t *)ctx->d_atlas[which].get(), ctx->atlas_w[which], w, h, tw, index, 1u, nullptr, &staged, ctx->stream);
+  FLX_HIP(ctx, hipGetLastError());
+  FLX_HIP(ctx, hipEventRecord(ctx->update_done, ctx->stream));      /* the stage has been consumed: the next update of either kind waits for this before it overwrites it */
+  ctx->update_pending = true;
+  return shared_upload_end(ctx);
+}
+
+extern "C" flx_status flx_texture_update(flx_context *ctx, int which, uint32_t index, const flx_image *image) { return texture_update(ctx, which, index, image, nullptr, false); }
+extern "C" flx_status flx_texture_update_device(flx_context *ctx, int which, uint32_t index, const flx_image *image, void *producer_stream) {
+  return texture_update(ctx, which, index, image, producer_stream, true);
+}
+
+extern "C" flx_status flx_debug_atlas_read(flx_context *ctx, int which, uint8_t *out, size_t bytes, uint32_t *width, uint32_t *height) {
+  if (!ctx) return FLX_ERR_INVALID;
+  if (which < 0 || which > 2) return fail(ctx, FLX_ERR_INVALID, "flx_debug_atlas_read: which must be 0, 1 or 2");
+  const bool have = ctx->d_atlas[which] != nullptr;
+  const uint32_t W = have ? ctx->atlas_w[which] : 0u, H = have ? ctx->atlas_h[which] : 0u;
+  if (width) *width = W;
+  if (height) *height = H;
+  const size_t need = (size_t)W * H * 4;
+  if (!out || need == 0) return FLX_OK;
+  if (bytes < need) return fail(ctx, FLX_ERR_INVALID, "flx_debug_atlas_read: out is smaller than the atlas");
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  FLX_HIP(ctx, hipMemcpy(out, ctx->d_atlas[which].get(), need, hipMemcpyDeviceToHost));
+  return FLX_OK;
 }
 
 extern "C" flx_status flx_scene_upload_view(flx_context *ctx, const flx_scene_view *v) {

@@ -36,6 +36,8 @@ EXPORTS = [
     "flx_tree_build_device", "flx_tree_emit_device", "flx_scene_splice_device",
     "flx_rays_cast_device", "flx_rays_cast", "flx_debug_set_query_groups", "flx_debug_last_query",
     "flx_rays_trace_device", "flx_rays_trace", "flx_debug_set_trace_slab", "flx_debug_last_trace",
+    "flx_textures_upload", "flx_textures_upload_device", "flx_texture_update", "flx_texture_update_device", "flx_group_textures_upload", "flx_group_texture_update",
+    "flx_debug_atlas_read",
 ]
 
 
@@ -48,6 +50,7 @@ FRAME_FXAA = 0x10              # FLX_FRAME_FXAA: flags of flx_frame_begin's form
 FRAME_TAA = 0x20               # FLX_FRAME_TAA
 FRAME_RASTERIZER = 0x100       # FLX_FRAME_RASTERIZER
 MAX_BATCH_FRAMES = 32          # FLX_MAX_BATCH_FRAMES of include/flexlight_hip.h
+IMAGE_RGBA8, IMAGE_RGBA32F = 0, 1      # FLX_IMAGE_* of include/flexlight_hip_debug.h: an image's texels are 4 bytes, or 4 floats
 
 
 class FlexLightHipError(RuntimeError):
@@ -67,6 +70,11 @@ class TraceParams(C.Structure):
     def of_frame(cls, params):
         """the fields a frame's FrameParams shares with it"""
         return cls(params.samples, params.max_reflections, params.min_importancy, tuple(params.ambient), params.random_seed, params.texture_width)
+
+
+class Image(C.Structure):
+    """flx_image of include/flexlight_hip_debug.h: a source image of upload_textures / update_texture, tight rows"""
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32)]
 
 
 def _load():
@@ -97,6 +105,13 @@ def _load():
         "flx_rays_trace": (C.c_int, [vp, C.POINTER(TraceParams), fp, vp, u32]),
         "flx_debug_set_trace_slab": (C.c_int, [vp, u32]),
         "flx_debug_last_trace": (C.c_int, [vp, C.POINTER(u32)]),
+        "flx_textures_upload": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32]),
+        "flx_textures_upload_device": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32, vp]),
+        "flx_texture_update": (C.c_int, [vp, C.c_int, u32, C.POINTER(Image)]),
+        "flx_texture_update_device": (C.c_int, [vp, C.c_int, u32, C.POINTER(Image), vp]),
+        "flx_group_textures_upload": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32]),
+        "flx_group_texture_update": (C.c_int, [vp, C.c_int, u32, C.POINTER(Image)]),
+        "flx_debug_atlas_read": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(u32), C.POINTER(u32)]),
         "flx_transforms_upload": (C.c_int, [vp, fp, fp, u32]),
         "flx_lights_upload": (C.c_int, [vp, fp, u32]),
         "flx_atlas_upload": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint8), u32, u32]),
@@ -286,6 +301,53 @@ def _ray_rows(x, device, call="cast_rays_device"):
     return x.data_ptr(), x.shape[0]
 
 
+def _host_images(images, call):
+    """images of upload_textures / update_texture: numpy arrays [h, w, 4], uint8 or float32 -> (the Image array, the contiguous arrays it points into)"""
+    keep = []
+    for a in images:
+        a = np.asarray(a)
+        if a.dtype != np.uint8 and a.dtype != np.float32:
+            raise ValueError("%s: an image is a uint8 or float32 array [h, w, 4]" % call)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError("%s: an image is an array [h, w, 4]" % call)
+        keep.append(np.ascontiguousarray(a))
+    arr = (Image * max(1, len(keep)))()
+    for k, a in enumerate(keep):
+        arr[k] = Image(a.ctypes.data, a.shape[1], a.shape[0], IMAGE_RGBA8 if a.dtype == np.uint8 else IMAGE_RGBA32F)
+    return arr, keep
+
+
+def _device_images(tensors, device, call):
+    """images of upload_textures_device / update_texture_device: torch tensors [h, w, 4] (uint8 or float32, contiguous, on cuda:`device`) or
+    (address, w, h, format) -> the Image array"""
+    arr = (Image * max(1, len(tensors)))()
+    for k, x in enumerate(tensors):
+        if isinstance(x, tuple):
+            address, w, h, fmt = x
+            arr[k] = Image(int(address) or None, int(w), int(h), int(fmt))
+            continue
+        import torch                           # (here and not at the top: capi imports without torch)
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("%s: an image is a torch tensor or (address, width, height, format)" % call)
+        if x.dtype not in (torch.uint8, torch.float32) or x.dim() != 3 or x.shape[2] != 4 or not x.is_contiguous():
+            raise ValueError("%s: an image is a contiguous uint8 or float32 tensor [h, w, 4]" % call)
+        if x.device.type != "cuda" or x.device.index != device:
+            raise ValueError("%s: an image is on %s, the context on cuda:%d" % (call, x.device, device))
+        arr[k] = Image(x.data_ptr() or None, x.shape[1], x.shape[0], IMAGE_RGBA8 if x.dtype == torch.uint8 else IMAGE_RGBA32F)
+    return arr
+
+
+def _stream_handle(stream):
+    """stream of the *_device calls -> the raw hipStream_t or None; a torch stream whose handle is 0 (the legacy default stream, which the C calls cannot name) is
+    synchronised here instead"""
+    if stream is not None and not isinstance(stream, int):
+        handle = stream.cuda_stream
+        if handle == 0:
+            stream.synchronize()
+        stream = handle
+    return C.c_void_p(stream) if stream else None
+
+
 def unpack_radiance(rows):
     """radiance rows of trace_rays / trace_rays_device (uint8 [n, 32], a numpy array or a torch tensor: a tensor is copied to the host, which waits for the stream
     it is asked on — sync() first where the batch ran on another) -> dict of columns: rgb float32 [n, 3], alpha float32 [n] (1 a hit, 0 a miss), s float32 [n] (of the
@@ -447,6 +509,38 @@ class Context:
         geometry, out, ids = self.build_tree_device(triangles, attributes, stream)
         self.splice_scene_device(first, n_old, parent, geometry, out, ids)      # (the block is complete: flx_tree_emit_device waited)
         return geometry.shape[0]
+
+    # -- textures ------------------------------------------------------------------------------------
+    def upload_textures(self, which, images, cell):
+        """flx_textures_upload: atlas `which` (0 albedo, 1 pbr, 2 translucency) built on the device from images in host memory: numpy arrays [h, w, 4], uint8 or
+        float32 (quantised as an RGBA8 render target stores a channel); cell = (cell_w, cell_h): standardTextureSizes.  An empty list: no atlas."""
+        arr, keep = _host_images(images, "upload_textures")
+        self._check(LIB.flx_textures_upload(self._h, which, arr, len(keep), int(cell[0]), int(cell[1])), "flx_textures_upload")
+
+    def upload_textures_device(self, which, tensors, cell, stream=None):
+        """flx_textures_upload_device: upload_textures for images in device memory: torch tensors [h, w, 4] (uint8 or float32, contiguous, on the context's device) or
+        (address, width, height, format).  stream: as for update_scene_rows_device."""
+        arr = _device_images(tensors, self._device, "upload_textures_device")
+        self._check(LIB.flx_textures_upload_device(self._h, which, arr, len(tensors), int(cell[0]), int(cell[1]), _stream_handle(stream)), "flx_textures_upload_device")
+
+    def update_texture(self, which, index, image):
+        """flx_texture_update: cell `index` of the atlas upload_textures[_device] built, replaced from one image of any size (a numpy array [h, w, 4], uint8 or float32)"""
+        arr, keep = _host_images([image], "update_texture")
+        self._check(LIB.flx_texture_update(self._h, which, index, arr), "flx_texture_update")
+
+    def update_texture_device(self, which, index, tensor, stream=None):
+        """flx_texture_update_device: update_texture for an image in device memory (a torch tensor [h, w, 4] or (address, width, height, format))"""
+        arr = _device_images([tensor], self._device, "update_texture_device")
+        self._check(LIB.flx_texture_update_device(self._h, which, index, arr, _stream_handle(stream)), "flx_texture_update_device")
+
+    def atlas_read(self, which):
+        """flx_debug_atlas_read: atlas `which` as the device holds it, after everything enqueued so far -> uint8 [H, W, 4] ([0, 0, 4]: none)"""
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        self._check(LIB.flx_debug_atlas_read(self._h, which, None, 0, C.byref(w), C.byref(h)), "flx_debug_atlas_read")
+        out = np.zeros((h.value, w.value, 4), np.uint8)
+        if out.size:
+            self._check(LIB.flx_debug_atlas_read(self._h, which, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size, C.byref(w), C.byref(h)), "flx_debug_atlas_read")
+        return out
 
     def update_scene_rows(self, first, geometry, attributes=None):
         """flx_scene_update: rows [first, first + n) of the uploaded scene replaced (12 floats of geometry each, 28 of attributes or None:
@@ -1064,6 +1158,16 @@ class Group:
     def update_scene_rows(self, first, geometry, attributes=None):
         geometry, attributes, n = _rows(geometry, attributes)
         self._check(LIB.flx_group_scene_update(self._h, first, n, _fp(geometry), None if attributes is None else _fp(attributes)), "flx_group_scene_update")
+
+    def upload_textures(self, which, images, cell):
+        """flx_group_textures_upload: Context.upload_textures on every context of the group"""
+        arr, keep = _host_images(images, "upload_textures")
+        self._check(LIB.flx_group_textures_upload(self._h, which, arr, len(keep), int(cell[0]), int(cell[1])), "flx_group_textures_upload")
+
+    def update_texture(self, which, index, image):
+        """flx_group_texture_update: Context.update_texture on every context of the group"""
+        arr, keep = _host_images([image], "update_texture")
+        self._check(LIB.flx_group_texture_update(self._h, which, index, arr), "flx_group_texture_update")
 
     def update_primary_light_sources(self, lights):
         lights = np.ascontiguousarray(lights, np.float32).reshape(-1)

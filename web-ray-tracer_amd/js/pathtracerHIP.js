@@ -104,6 +104,7 @@ class PathTracerHIP {
       return {
         uploadScene: (a, b, c) => n.groupUploadScene(g, a, b, c), updateSceneRows: (f, a, b) => n.groupUpdateSceneRows(g, f, a, b), uploadTransforms: (a, b) => n.groupUploadTransforms(g, a, b),
         uploadLights: a => n.groupUploadLights(g, a), uploadAtlas: (w, px, x, y) => n.groupUploadAtlas(g, w, px, x, y),
+        uploadTextures: (w, list, x, y) => n.groupUploadTextures(g, w, list, x, y), updateTexture: (w, i, img) => n.groupUpdateTexture(g, w, i, img),
         render: (p, out, counters) => n.groupRender(g, [p], this._tileRows, out, counters),
         renderBatch: (ps, out, counters) => n.groupRender(g, ps, this._tileRows, out, counters),
         rows: p => p.height
@@ -113,6 +114,7 @@ class PathTracerHIP {
     return {
       uploadScene: (a, b, d) => n.uploadScene(c, a, b, d), updateSceneRows: (f, a, b) => n.updateSceneRows(c, f, a, b), uploadTransforms: (a, b) => n.uploadTransforms(c, a, b),
       uploadLights: a => n.uploadLights(c, a), uploadAtlas: (w, px, x, y) => n.uploadAtlas(c, w, px, x, y),
+      uploadTextures: (w, list, x, y) => n.uploadTextures(c, w, list, x, y), updateTexture: (w, i, img) => n.updateTexture(c, w, i, img),
       render: (p, out, counters) => n.render(c, p, out, counters), renderBatch: (ps, out, counters) => n.renderBatch(c, ps, out, counters),
       rows: p => n.tileRowCount(p)
     };
@@ -182,10 +184,15 @@ class PathTracerHIP {
     lists.forEach((list, which) => {
       const old = this._atlasLists[which];
       if (old && old.length === list.length && list.every((e, i) => e === old[i])) return;
+      const sizes = this.scene.standardTextureSizes;
       this._atlasLists[which] = list.slice();
       if (list.length === 0) { this._gpu().uploadAtlas(which, null, 0, 0); return; }
-      const atlas = sceneFile.buildAtlas(list, this.scene.standardTextureSizes);
-      this._gpu().uploadAtlas(which, atlas.data, atlas.width, atlas.height);
+      this._atlasLists[which].cells = [sizes[0], sizes[1]];      // what the resident atlas is built with (uploadTextures: the device resamples and composites, sceneFile.buildAtlas' bytes)
+      if (old && old.cells && old.length === list.length && old.cells[0] === sizes[0] && old.cells[1] === sizes[1]) {
+        list.forEach((e, i) => { if (e !== old[i]) this._gpu().updateTexture(which, i, sceneFile.nativeTexture(e)); });      // only the members that changed, each into its cell
+      } else {
+        this._gpu().uploadTextures(which, list.map(sceneFile.nativeTexture), sizes[0], sizes[1]);
+      }
     });
   }
 

@@ -90,10 +90,15 @@ class RasterizerHIP {
     lists.forEach((list, which) => {
       const old = this._atlasLists[which];
       if (old && old.length === list.length && list.every((e, i) => e === old[i])) return;
+      const sizes = this.scene.standardTextureSizes;
       this._atlasLists[which] = list.slice();
       if (list.length === 0) { n.uploadAtlas(c, which, null, 0, 0); return; }
-      const atlas = sceneFile.buildAtlas(list, this.scene.standardTextureSizes);
-      n.uploadAtlas(c, which, atlas.data, atlas.width, atlas.height);
+      this._atlasLists[which].cells = [sizes[0], sizes[1]];      // what the resident atlas is built with (uploadTextures: the device resamples and composites, sceneFile.buildAtlas' bytes)
+      if (old && old.cells && old.length === list.length && old.cells[0] === sizes[0] && old.cells[1] === sizes[1]) {
+        list.forEach((e, i) => { if (e !== old[i]) n.updateTexture(c, which, i, sceneFile.nativeTexture(e)); });      // only the members that changed, each into its cell
+      } else {
+        n.uploadTextures(c, which, list.map(sceneFile.nativeTexture), sizes[0], sizes[1]);
+      }
     });
   }
 

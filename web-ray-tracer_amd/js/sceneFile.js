@@ -44,6 +44,16 @@ function buildAtlas (images, sizes) {
   return { width: W, height: H, data };
 }
 
+// An image of a texture list as the native uploadTextures / updateTexture take it: the width * height * 4 bytes buildAtlas reads of img.data (anything that is no
+// byte array converted as buildAtlas' store into its Uint8Array converts it; missing bytes are 0).  The native atlas is then buildAtlas' byte for byte.
+function nativeTexture (img) {
+  const n = img.width * img.height * 4;
+  let data = img.data;
+  if (!(data instanceof Uint8Array || data instanceof Uint8ClampedArray)) data = Uint8Array.from(data);
+  if (data.length !== n) { const d = new Uint8Array(n); d.set(data.subarray(0, Math.min(n, data.length))); data = d; }
+  return { width: img.width, height: img.height, data };
+}
+
 // viewMatrix of modules/pathtracerWGL2.js:312-318 (row-major, uploaded with transpose = true).
 function buildViewMatrix (camera, width, height) {
   const invFov = 1 / camera.fov;
@@ -163,4 +173,4 @@ function changedRows (oldBuilt, newBuilt) {
   return { first, count: last - first + 1 };
 }
 
-module.exports = { buildLightArray, buildAtlas, buildViewMatrix, assemble, save, sceneFromFlxs, changedRows };
+module.exports = { buildLightArray, buildAtlas, nativeTexture, buildViewMatrix, assemble, save, sceneFromFlxs, changedRows };

@@ -256,6 +256,75 @@ static napi_value UploadAtlas(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+/* an image of uploadTextures / updateTexture: { width, height, data: Uint8Array | Uint8ClampedArray (RGBA8) | Float32Array (RGBA32F) }, width * height * 4 elements */
+static bool read_image(napi_env env, napi_value v, flx_image *out) {
+  napi_valuetype t;
+  napi_typeof(env, v, &t);
+  if (t != napi_object) { napi_throw_type_error(env, nullptr, "a texture is { width, height, data }"); return false; }
+  napi_value vw, vh, vd;
+  uint32_t w = 0, h = 0;
+  if (napi_get_named_property(env, v, "width", &vw) != napi_ok || napi_get_value_uint32(env, vw, &w) != napi_ok ||
+      napi_get_named_property(env, v, "height", &vh) != napi_ok || napi_get_value_uint32(env, vh, &h) != napi_ok ||
+      napi_get_named_property(env, v, "data", &vd) != napi_ok) { napi_throw_type_error(env, nullptr, "a texture is { width, height, data }"); return false; }
+  bool is = false;
+  napi_is_typedarray(env, vd, &is);
+  napi_typedarray_type type; size_t len = 0; void *data = nullptr;
+  if (!is || napi_get_typedarray_info(env, vd, &type, &len, &data, nullptr, nullptr) != napi_ok ||
+      (type != napi_uint8_array && type != napi_uint8_clamped_array && type != napi_float32_array)) {
+    napi_throw_type_error(env, nullptr, "a texture's data is a Uint8Array, a Uint8ClampedArray or a Float32Array"); return false;
+  }
+  if (len != (size_t)w * h * 4) { napi_throw_range_error(env, nullptr, "a texture's data needs width*height*4 elements"); return false; }
+  out->pixels = data; out->width = w; out->height = h; out->format = type == napi_float32_array ? FLX_IMAGE_RGBA32F : FLX_IMAGE_RGBA8;
+  return true;
+}
+/* the arguments of uploadTextures / groupUploadTextures after the handle: which, [image, ...], cellWidth, cellHeight */
+static bool textures_args(napi_env env, napi_value *argv, int32_t *which, std::vector<flx_image> &images, uint32_t *cw, uint32_t *ch) {
+  uint32_t n = 0;
+  bool isArray = false;
+  napi_is_array(env, argv[1], &isArray);
+  if (napi_get_value_int32(env, argv[0], which) != napi_ok || !isArray || napi_get_array_length(env, argv[1], &n) != napi_ok ||
+      napi_get_value_uint32(env, argv[2], cw) != napi_ok || napi_get_value_uint32(env, argv[3], ch) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "uploadTextures: which, an array of textures, cellWidth, cellHeight"); return false;
+  }
+  images.resize(n);
+  for (uint32_t i = 0; i < n; i++) {
+    napi_value e;
+    if (napi_get_element(env, argv[1], i, &e) != napi_ok || !read_image(env, e, &images[i])) return false;
+  }
+  return true;
+}
+/* ... of updateTexture / groupUpdateTexture: which, index, image */
+static bool texture_args(napi_env env, napi_value *argv, int32_t *which, uint32_t *index, flx_image *image) {
+  if (napi_get_value_int32(env, argv[0], which) != napi_ok || napi_get_value_uint32(env, argv[1], index) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "updateTexture: which, index, texture"); return false;
+  }
+  return read_image(env, argv[2], image);
+}
+/* uploadTextures(handle, which, [{ width, height, data }, ...], cellWidth, cellHeight): flx_textures_upload — the atlas is built on the device */
+static napi_value UploadTextures(napi_env env, napi_callback_info info) {
+  napi_value argv[5];
+  if (!get_args(env, info, 5, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  int32_t which; uint32_t cw, ch; std::vector<flx_image> images;
+  if (!textures_args(env, argv + 1, &which, images, &cw, &ch)) return nullptr;
+  flx_status rc = flx_textures_upload(ctx, which, images.data(), (uint32_t)images.size(), cw, ch);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_textures_upload", rc);
+  return nullptr;
+}
+/* updateTexture(handle, which, index, { width, height, data }): flx_texture_update — one cell of the resident atlas replaced */
+static napi_value UpdateTexture(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  int32_t which; uint32_t index; flx_image image;
+  if (!texture_args(env, argv + 1, &which, &index, &image)) return nullptr;
+  flx_status rc = flx_texture_update(ctx, which, index, &image);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_texture_update", rc);
+  return nullptr;
+}
+
 static bool read_params(napi_env env, napi_value o, flx_frame_params *p) {
   memset(p, 0, sizeof *p);
   double d = 0;
@@ -879,6 +948,28 @@ static napi_value GroupUploadAtlas(napi_env env, napi_callback_info info) {
   if (rc != FLX_OK) return gfail(env, grp, "flx_group_atlas_upload", rc);
   return nullptr;
 }
+static napi_value GroupUploadTextures(napi_env env, napi_callback_info info) {
+  napi_value argv[5];
+  if (!get_args(env, info, 5, argv)) return nullptr;
+  flx_group *grp = get_group(env, argv[0]);
+  if (!grp) return nullptr;
+  int32_t which; uint32_t cw, ch; std::vector<flx_image> images;
+  if (!textures_args(env, argv + 1, &which, images, &cw, &ch)) return nullptr;
+  flx_status rc = flx_group_textures_upload(grp, which, images.data(), (uint32_t)images.size(), cw, ch);
+  if (rc != FLX_OK) return gfail(env, grp, "flx_group_textures_upload", rc);
+  return nullptr;
+}
+static napi_value GroupUpdateTexture(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  flx_group *grp = get_group(env, argv[0]);
+  if (!grp) return nullptr;
+  int32_t which; uint32_t index; flx_image image;
+  if (!texture_args(env, argv + 1, &which, &index, &image)) return nullptr;
+  flx_status rc = flx_group_texture_update(grp, which, index, &image);
+  if (rc != FLX_OK) return gfail(env, grp, "flx_group_texture_update", rc);
+  return nullptr;
+}
 /* groupRender(handle, [params, ...], tileRows, out Float32Array(frames*height*width*4), wantCounters) -> { frameMs, counters? } */
 static napi_value GroupRender(napi_env env, napi_callback_info info) {
   napi_value argv[5];
@@ -1100,14 +1191,14 @@ static napi_value Version(napi_env env, napi_callback_info) {
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
     { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
-    { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas },
+    { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas }, { "uploadTextures", UploadTextures }, { "updateTexture", UpdateTexture },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
     { "meshScale", MeshScale }, { "meshSetMaterial", MeshSetMaterial }, { "meshFlatten", MeshFlatten }, { "meshBounding", MeshBounding }, { "packTransforms", PackTransforms },
     { "present", Present }, { "fxaa", Fxaa }, { "taa", Taa }, { "taaReset", TaaReset },
     { "frameBegin", FrameBegin }, { "frameEnd", FrameEnd }, { "frameEndAsync", FrameEndAsync }, { "groupFrameEndAsync", GroupFrameEndAsync }, { "framesInFlight", FramesInFlight },
     { "createGroup", CreateGroup }, { "destroyGroup", DestroyGroup }, { "groupInfo", GroupInfo }, { "groupUploadScene", GroupUploadScene },
-    { "groupUploadTransforms", GroupUploadTransforms }, { "groupUploadLights", GroupUploadLights }, { "groupUploadAtlas", GroupUploadAtlas },
+    { "groupUploadTransforms", GroupUploadTransforms }, { "groupUploadLights", GroupUploadLights }, { "groupUploadAtlas", GroupUploadAtlas }, { "groupUploadTextures", GroupUploadTextures }, { "groupUpdateTexture", GroupUpdateTexture },
     { "groupRender", GroupRender }, { "groupRenderRgba8", GroupRenderRgba8 }, { "groupFrameBegin", GroupFrameBegin }, { "groupFrameEnd", GroupFrameEnd }, { "groupFramesInFlight", GroupFramesInFlight },
     { "groupSetFrameLanes", GroupSetFrameLanes }, { "groupTemporalReset", GroupTemporalReset },
   };
