@@ -350,6 +350,54 @@ flx_status flx_debug_set_trace_slab(flx_context *ctx, uint32_t rays);
 /* The last traced batch (zeros if none): out[0] its slabs, [1] the rays of a full slab, [2] workgroups of the last slab's paths kernel, [3] whether its bounce walks
  * went in lockstep, [4] n, [5] samples, [6] workgroups of the last slab's first-hit launch, [7] the items a wave draws with one atomic.  It waits for nothing. */
 flx_status flx_debug_last_trace(flx_context *ctx, uint32_t out[8]);
+/* SURFACE ROWS: what the surface is where a ray first hits — the question between "where does it hit" (flx_rays_cast) and "what radiance comes back"
+ * (flx_rays_trace, flx_render).  The planes (AOVs) a denoiser of the caller's own, compositing or the shading of a hybrid renderer needs beside the noisy radiance:
+ * position, geometric normal, shading normal, texture coordinates, and albedo, RME and TPO with the atlases applied.  They are the first thing lightTrace computes
+ * at a hit (fragment:476-533) and have the oracle's bits: the same operations in the same order (csrc/flx_surface.hip: k_surface).
+ * `fields` names the planes.  A PLANE is n rows of 16 bytes, one row per ray (or per pixel, row k = pixel k of flx_render's frame, row 0 on top).  Only the planes
+ * asked for are written; they follow each other in bit order of `fields`: plane p starts at out + p * n * 16 bytes, and the output is popcount(fields) * n * 16
+ * bytes.  A row, by plane (lightTrace's names):
+ *   FLX_SURFACE_HIT              float s, u, v; int32 the entry index, -1 for none — flx_rays_cast's words 0..3
+ *   FLX_SURFACE_POSITION         origin + s * direction, formed as ray.origin is at fragment:479 (direction * s + origin); float 1.0 for a hit, 0.0 for a miss
+ *   FLX_SURFACE_GEOMETRY_NORMAL  normalize(cross(t0v - t1v, t0v - t2v)) of the transformed vertices, NOT flipped towards the ray; 0
+ *   FLX_SURFACE_NORMAL           the smooth normal FACING THE RAY (smoothNormal * -signDir, with lastHitPoint = the ray's origin); float signDir: -1 a front face
+ *                                was hit, +1 a back face, 0 at grazing incidence
+ *   FLX_SURFACE_UV               float bu, bv, the interpolated texture coordinates; int32 2 x the entry's transform number (flx_rays_cast's word 4); 0
+ *   FLX_SURFACE_ALBEDO           fetchTexVal(0, ..) r, g, b: the albedo atlas' texel, or the entry's own colour where it names no texture; 0
+ *   FLX_SURFACE_RME              fetchTexVal(1, ..): roughness, metallicity, emissiveness; 0
+ *   FLX_SURFACE_TPO              fetchTexVal(2, ..): translucency, particle density, optical density; 0
+ * A MISS ROW IS ALL ZEROS in every plane, with -1 in word 3 of the HIT plane.  (These are not flx_gbuffers' planes: those are packed for the reference's RGBA8
+ * denoise chain — normals in 4-bit codes, albedo multiplied over several bounces, no depth, no position.)
+ * flx_rays_surface_device: the rays are flx_rays_cast's ray rows (words 3 and 7 are ignored); the closest hit is found exactly as FLX_RAYS_CLOSEST finds it, into
+ * scratch the context owns (grown and never shrunk; the batch is cut into slabs of at most 2^21 rays so that it has a ceiling, flx_debug_set_trace_slab lowers it
+ * for tests), and k_surface follows on the same stream.  texture_width: the frame params' (floor(2048 / standardTextureSizes[0])).
+ * flx_frame_surface_device: the pixel's primary hit is found AS A FRAME FINDS IT (k_primary with the frame's own direction per pixel, not rayTracer: the two hit
+ * rules differ on a few pixels per million); the ray is the camera position and that direction.  Of the params only width, height, camera, view_matrix and
+ * texture_width are read; the tile policy must name the whole frame (0/0/0 or x/0/1).  A group has no such call, as it casts no rays.
+ * Ordering, producer_stream, the frame server and n == 0 are flx_rays_cast_device's, word for word: enqueued on the context's stream with no wait of the host, it
+ * sees the scene as of the call, frames in flight finish unchanged; n == 0: FLX_OK, nothing enqueued (the scene and the arguments are looked at first).  (Where
+ * the scratch must grow, the host waits for the stream first.)  flx_rays_surface and flx_frame_surface are the same for host arrays: staged through memory the
+ * context owns; they wait and copy the planes out.
+ * Refusals, each with a message of its own and nothing enqueued: FLX_ERR_NO_SCENE before a scene and transforms are up; FLX_ERR_INVALID for fields 0 or with a bit
+ * above FLX_SURFACE_TPO; texture_width < 1; NULL params; a width or height of 0 (or more than 2^32 - 1 pixels); a tile policy that is not the whole frame; an array
+ * that is NULL, that is not memory of the context's device or not 16-byte aligned (device variants), or that sits in an allocation too short; planes or an array's end
+ * that leave 64 bits; rays and output that overlap. */
+#define FLX_SURFACE_HIT             1u
+#define FLX_SURFACE_POSITION        2u
+#define FLX_SURFACE_GEOMETRY_NORMAL 4u
+#define FLX_SURFACE_NORMAL          8u
+#define FLX_SURFACE_UV              16u
+#define FLX_SURFACE_ALBEDO          32u
+#define FLX_SURFACE_RME             64u
+#define FLX_SURFACE_TPO             128u
+flx_status flx_rays_surface_device(flx_context *ctx, int32_t texture_width, const void *d_rays /* n * 8 floats, on ctx's device */, uint32_t n, uint32_t fields,
+                                   void *d_out /* popcount(fields) * n * 16 bytes */, void *producer_stream /* hipStream_t that wrote the rays, or NULL: they are complete */);
+flx_status flx_rays_surface(flx_context *ctx, int32_t texture_width, const float *rays /* n * 8 floats */, uint32_t n, uint32_t fields, void *out);      /* host arrays */
+flx_status flx_frame_surface_device(flx_context *ctx, const flx_frame_params *params, uint32_t fields, void *d_out /* planes of width * height rows, on ctx's device */);
+flx_status flx_frame_surface(flx_context *ctx, const flx_frame_params *params, uint32_t fields, void *out);      /* host array */
+/* The last surface call (zeros if none): out[0] its slabs, [1] the rays of a full slab (a frame: its pixels), [2] n, [3] fields, [4] 1 for a frame, [5] workgroups of
+ * the last slab's first-hit launch (a frame: 0); [6], [7] zero.  It waits for nothing. */
+flx_status flx_debug_last_surface(flx_context *ctx, uint32_t out[8]);
 /* The uploaded scene as the device holds it, after everything enqueued so far: which 0 the geometry rows (12 floats per entry), 1 the attribute rows (28),
  * 2 the threaded hot-first copy (12 per entry of walk_entries), 3 the forward-ordered copy (12 per entry of fwd_entries: flx_debug_last_walk_lds' out[5], out[6]),
  * 4 the id list (an int32 in every 4 bytes of out, n_ids of them).

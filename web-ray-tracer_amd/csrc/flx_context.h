@@ -272,6 +272,9 @@ struct flx_context {
   DeviceBuffer<uint32_t> d_trace_ctl;
   struct TraceLaunch { uint32_t slabs = 0, slab = 0, path_groups = 0, lock = 0, n = 0, samples = 0, query_groups = 0; } last_trace_rays;
   uint32_t trace_slab = 0;                       /* flx_debug_set_trace_slab: most rays of a slab (0: flx_trace_slab_rays' own ceiling) */
+  /* surface rows (flx_surface.hip): their hit scratch is the traced batches' above, their host variants' staging the queries'; what the last call ran
+   * (flx_debug_last_surface) */
+  struct SurfaceLaunch { uint32_t slabs = 0, slab = 0, n = 0, fields = 0, frame = 0, query_groups = 0; } last_surface;
   /* uploads: pinned staging ring */
   PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};

@@ -36,6 +36,7 @@ EXPORTS = [
     "flx_tree_build_device", "flx_tree_emit_device", "flx_scene_splice_device",
     "flx_rays_cast_device", "flx_rays_cast", "flx_debug_set_query_groups", "flx_debug_last_query",
     "flx_rays_trace_device", "flx_rays_trace", "flx_debug_set_trace_slab", "flx_debug_last_trace",
+    "flx_rays_surface_device", "flx_rays_surface", "flx_frame_surface_device", "flx_frame_surface", "flx_debug_last_surface",
     "flx_textures_upload", "flx_textures_upload_device", "flx_texture_update", "flx_texture_update_device", "flx_group_textures_upload", "flx_group_texture_update",
     "flx_debug_atlas_read",
 ]
@@ -45,6 +46,10 @@ EXPORTS = [
 SHARE_HANDLE_BYTES = 128      # FLX_SHARE_HANDLE_BYTES
 NO_PARENT = 0xffffffff         # FLX_NO_PARENT of include/flexlight_hip_debug.h
 RAYS_CLOSEST, RAYS_OCCLUDED, RAYS_COUNT = 1, 2, 4      # FLX_RAYS_* of include/flexlight_hip_debug.h: what cast_rays asks of every ray
+# FLX_SURFACE_* of include/flexlight_hip_debug.h: the planes surface_rays / frame_surface write, in the order they follow each other
+SURFACE_HIT, SURFACE_POSITION, SURFACE_GEOMETRY_NORMAL, SURFACE_NORMAL, SURFACE_UV, SURFACE_ALBEDO, SURFACE_RME, SURFACE_TPO = 1, 2, 4, 8, 16, 32, 64, 128
+SURFACE_ALL = 255
+SURFACE_NAMES = ("hit", "position", "geometry_normal", "normal", "uv", "albedo", "rme", "tpo")      # unpack_surface's keys, in bit order
 QUERY_CHUNK = 128              # consecutive rays a wave of the query kernel draws with one atomic (QUERY_CHUNK of csrc/flx_kernels.h; flx_debug_last_query reports it)
 FRAME_FXAA = 0x10              # FLX_FRAME_FXAA: flags of flx_frame_begin's format
 FRAME_TAA = 0x20               # FLX_FRAME_TAA
@@ -105,6 +110,11 @@ def _load():
         "flx_rays_trace": (C.c_int, [vp, C.POINTER(TraceParams), fp, vp, u32]),
         "flx_debug_set_trace_slab": (C.c_int, [vp, u32]),
         "flx_debug_last_trace": (C.c_int, [vp, C.POINTER(u32)]),
+        "flx_rays_surface_device": (C.c_int, [vp, C.c_int32, vp, u32, u32, vp, vp]),
+        "flx_rays_surface": (C.c_int, [vp, C.c_int32, fp, u32, u32, vp]),
+        "flx_frame_surface_device": (C.c_int, [vp, C.POINTER(FrameParams), u32, vp]),
+        "flx_frame_surface": (C.c_int, [vp, C.POINTER(FrameParams), u32, vp]),
+        "flx_debug_last_surface": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_textures_upload": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32]),
         "flx_textures_upload_device": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32, vp]),
         "flx_texture_update": (C.c_int, [vp, C.c_int, u32, C.POINTER(Image)]),
@@ -357,6 +367,32 @@ def unpack_radiance(rows):
     words = np.ascontiguousarray(rows, np.uint8).reshape(-1, 32).view(np.uint32)
     return {"rgb": words[:, 0:3].view(np.float32).copy(), "alpha": words[:, 3].view(np.float32).copy(), "s": words[:, 4].view(np.float32).copy(),
             "entry": words[:, 5].view(np.int32).copy(), "transform2": words[:, 6].view(np.int32).copy(), "shades": words[:, 7].copy()}
+
+
+def surface_planes(fields):
+    """planes a surface call writes for `fields`: its bits"""
+    return bin(int(fields) & 0xffffffff).count("1")
+
+
+def unpack_surface(planes, fields):
+    """planes of surface_rays / frame_surface and their _device forms ([popcount(fields), n, 4] float32, a numpy array or a torch tensor: a tensor is copied to the
+    host, which waits for the stream it is asked on — sync() first where the call ran on another) -> dict of the planes asked for, by SURFACE_NAMES: float32
+    [n, 4] each, with the int32 words viewed as int32 beside them: 'entry' int32 [n] (word 3 of 'hit', -1: none) and 'transform2' int32 [n] (word 2 of 'uv')"""
+    if not isinstance(planes, np.ndarray):
+        planes = planes.detach().cpu().numpy()
+    planes = np.ascontiguousarray(planes, np.float32)
+    if planes.ndim != 3 or planes.shape[2] != 4 or planes.shape[0] != surface_planes(fields) or int(fields) & ~SURFACE_ALL:
+        raise ValueError("unpack_surface: planes is [popcount(fields), n, 4] float32")
+    out, p = {}, 0
+    for k, name in enumerate(SURFACE_NAMES):
+        if int(fields) >> k & 1:
+            out[name] = planes[p].copy()
+            p += 1
+    if "hit" in out:
+        out["entry"] = out["hit"][:, 3].copy().view(np.int32)
+    if "uv" in out:
+        out["transform2"] = out["uv"][:, 2].copy().view(np.int32)
+    return out
 
 
 def noise_coordinates(n):
@@ -653,6 +689,59 @@ class Context:
         out = (C.c_uint32 * 8)()
         self._check(LIB.flx_debug_last_trace(self._h, out), "flx_debug_last_trace")
         return dict(zip(("slabs", "slab", "path_groups", "lockstep", "n", "samples", "query_groups", "chunk"), list(out)))
+
+    # -- surface rows -------------------------------------------------------------------------------
+    def _surface_out(self, out, n, fields, call):
+        """the planes of a *_device surface call: None (a new float32 tensor [popcount(fields), n, 4]), such a tensor to write into, or an address"""
+        planes = surface_planes(fields)
+        if out is None:
+            import torch
+            out = torch.empty((planes, n, 4), dtype=torch.float32, device="cuda:%d" % self._device)
+        if isinstance(out, int):
+            return out, out
+        if out.device.type != "cuda" or out.device.index != self._device or not out.is_contiguous() or out.numel() * out.element_size() < planes * n * 16:
+            raise ValueError("%s: out is a contiguous tensor of at least popcount(fields) x n x 16 bytes on the context's device" % call)
+        return out, out.data_ptr()
+
+    def surface_rays_device(self, rays, fields=SURFACE_ALL, texture_width=32, out=None, stream=None):
+        """flx_rays_surface_device: the surface at the first hit of rays of the caller's own, in device memory.  rays: a torch tensor [n, 8] (float32, contiguous, on
+        the context's device: cast_rays_device's rows) or (address, n); fields: SURFACE_* bits; texture_width: the frame params'; out: None (a new float32 tensor
+        [popcount(fields), n, 4]), such a tensor to write into, or an address (then the address comes back); stream: the torch.cuda.Stream (or raw hipStream_t) on
+        which the rays were written.  Returns the planes ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE: sync() before they are read on another stream
+        (unpack_surface reads them).  Both arrays stay alive until then."""
+        r, n = _ray_rows(rays, self._device, "surface_rays_device")
+        out, o = self._surface_out(out, n, fields, "surface_rays_device")
+        self._check(LIB.flx_rays_surface_device(self._h, int(texture_width), C.c_void_p(r), n, int(fields), C.c_void_p(o), _stream_handle(stream)), "flx_rays_surface_device")
+        return out
+
+    def surface_rays(self, rays, fields=SURFACE_ALL, texture_width=32):
+        """flx_rays_surface: rays [n, 8] float32 in host memory -> the planes [popcount(fields), n, 4] float32, complete (unpack_surface)"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros((surface_planes(fields), rays.shape[0], 4), np.float32)
+        self._check(LIB.flx_rays_surface(self._h, int(texture_width), _fp(rays), rays.shape[0], int(fields), out.ctypes.data_as(C.c_void_p)), "flx_rays_surface")
+        return out
+
+    def frame_surface_device(self, params, fields=SURFACE_ALL, out=None):
+        """flx_frame_surface_device: the surface at every pixel's primary hit, row k = pixel k of render()'s frame.  params: FrameParams (width, height, camera,
+        view_matrix and texture_width are read; the tile policy names the whole frame); out as for surface_rays_device.  Returns the planes
+        [popcount(fields), width * height, 4] enqueued on the context's stream and not yet complete."""
+        n = int(params.width) * int(params.height) if params is not None else 0
+        out, o = self._surface_out(out, n, fields, "frame_surface_device")
+        self._check(LIB.flx_frame_surface_device(self._h, C.byref(params) if params is not None else None, int(fields), C.c_void_p(o)), "flx_frame_surface_device")
+        return out
+
+    def frame_surface(self, params, fields=SURFACE_ALL):
+        """flx_frame_surface: -> the planes [popcount(fields), width * height, 4] float32 in host memory, complete (unpack_surface)"""
+        n = int(params.width) * int(params.height) if params is not None else 0
+        out = np.zeros((surface_planes(fields), n, 4), np.float32)
+        self._check(LIB.flx_frame_surface(self._h, C.byref(params) if params is not None else None, int(fields), out.ctypes.data_as(C.c_void_p)), "flx_frame_surface")
+        return out
+
+    def last_surface(self):
+        """flx_debug_last_surface -> dict (zeros when no surface call ran): slabs, slab (rays of a full one), n, fields, frame (1: a frame), query_groups"""
+        out = (C.c_uint32 * 8)()
+        self._check(LIB.flx_debug_last_surface(self._h, out), "flx_debug_last_surface")
+        return dict(zip(("slabs", "slab", "n", "fields", "frame", "query_groups"), list(out)))
 
     def scene_read(self, which, rows=None):
         """flx_debug_scene_read: the device's 'geometry' [rows, 12], 'attributes' [rows, 28], 'walk' (the threaded copy) or 'fwd' (the forward-ordered

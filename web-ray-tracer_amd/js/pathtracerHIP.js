@@ -58,6 +58,31 @@ function traceRaysOn (context, rays, params) {
   return out;
 }
 
+/* The planes of a surface call (flx_rays_surface, flx_frame_surface: include/flexlight_hip_debug.h "surface rows") as typed arrays over the buffer the library
+ * wrote: per plane asked for a Float32Array of 4 floats a row — hit, position, geometryNormal, normal, uv, albedo, rme, tpo, in that bit order of `fields` — and
+ * the two integer words as arrays of their own: entry (word 3 of hit, -1: none) and transform (word 2 of uv is 2 x the transform number). */
+const SURFACE = { HIT: 1, POSITION: 2, GEOMETRY_NORMAL: 4, NORMAL: 8, UV: 16, ALBEDO: 32, RME: 64, TPO: 128, ALL: 255 };
+const SURFACE_PLANES = ['hit', 'position', 'geometryNormal', 'normal', 'uv', 'albedo', 'rme', 'tpo'];
+function unpackSurface (buffer, n, fields) {
+  const out = { n, fields };
+  let p = 0;
+  SURFACE_PLANES.forEach((name, bit) => {
+    if (!(fields >> bit & 1)) return;
+    out[name] = new Float32Array(buffer, p * n * 16, 4 * n);
+    const i32 = new Int32Array(buffer, p * n * 16, 4 * n);
+    if (name === 'hit') { out.entry = new Int32Array(n); for (let k = 0; k < n; k++) out.entry[k] = i32[4 * k + 3]; }
+    if (name === 'uv') { out.transform = new Int32Array(n); for (let k = 0; k < n; k++) out.transform[k] = i32[4 * k + 2] >> 1; }
+    p++;
+  });
+  return out;
+}
+/* flx_rays_surface on a context whose scene, lights, transforms and atlases are up (both renderers' surfaceRays) */
+function surfaceRaysOn (context, rays, fields, textureWidth) {
+  if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('surfaceRays: rays is a Float32Array of 8 floats per ray');
+  const f = fields === undefined ? SURFACE.ALL : fields;
+  return unpackSurface(native().surfaceRays(context, rays, f, textureWidth), rays.length / 8, f);
+}
+
 class PathTracerHIP {
   constructor (canvas, scene, camera, config, options) {
     this.type = 'pathtracer';
@@ -279,6 +304,27 @@ class PathTracerHIP {
     return traceRaysOn(this._context(), rays, this.traceParams(options));
   }
 
+  /* What the SURFACE is where rays of the application's own first hit: the inputs of a denoiser, of compositing, of a hybrid renderer's shading
+   * (flx_rays_surface, include/flexlight_hip_debug.h "surface rows").  rays: castRays' rows (words 3 and 7 are ignored); fields: SURFACE bits (by default all).
+   * Returns typed arrays per plane asked for, 4 floats a ray — hit (s, u, v, -), position (x y z, 1 for a hit), geometryNormal, normal (facing the ray; w: -1
+   * front face, +1 back face), uv (u, v, -, 0), albedo, rme, tpo —, entry: Int32Array(n) with hit, transform: Int32Array(n) with uv.  A miss is all zeros,
+   * entry -1.  It waits for the answer; frames in flight finish unchanged. */
+  surfaceRays (rays, fields) {
+    if (this._devices) throw new Error('surfaceRays: one GPU only (a group of GPUs casts no rays)');
+    this._uploadFrameState();
+    return surfaceRaysOn(this._context(), rays, fields, Math.floor(2048 / this.scene.standardTextureSizes[0]));
+  }
+
+  /* The same planes for every pixel of the frame the next renderFrame() would trace without jitter (flx_frame_surface): row k of a plane is pixel k of that frame,
+   * the primary hit found as the frame finds it.  Also returns width and height. */
+  renderSurface (fields) {
+    if (this._devices) throw new Error('renderSurface: one GPU only (a group of GPUs casts no rays)');
+    this._uploadFrameState();
+    const p = this.frameParams();
+    const f = fields === undefined ? SURFACE.ALL : fields;
+    return Object.assign(unpackSurface(native().frameSurface(this._context(), p, f), p.width * p.height, f), { width: p.width, height: p.height });
+  }
+
   traceParams (options) {
     const o = options || {};
     const pick = (v, d) => (v === undefined ? d : v);
@@ -469,4 +515,4 @@ function taaVectors (n, random) {
   return vecs;
 }
 
-module.exports = { PathTracerHIP, taaVectors, native, castRaysOn };
+module.exports = { PathTracerHIP, taaVectors, native, castRaysOn, surfaceRaysOn, SURFACE };

@@ -11,7 +11,7 @@
  */
 const { Transform } = require('./scene.js');
 const sceneFile = require('./sceneFile.js');
-const { native, taaVectors, castRaysOn } = require('./pathtracerHIP.js');
+const { native, taaVectors, castRaysOn, surfaceRaysOn } = require('./pathtracerHIP.js');
 
 class RasterizerHIP {
   constructor (canvas, scene, camera, config, options) {
@@ -155,6 +155,12 @@ class RasterizerHIP {
   castRays (rays, what) {
     this._uploadFrameState();
     return castRaysOn(this._context(), rays, what);
+  }
+
+  /* PathTracerHIP.surfaceRays(): the surface under rays of the application's own — the shading inputs for the reflection rays of a hybrid renderer */
+  surfaceRays (rays, fields) {
+    this._uploadFrameState();
+    return surfaceRaysOn(this._context(), rays, fields, Math.floor(2048 / this.scene.standardTextureSizes[0]));
   }
 
   renderFrame (options) {

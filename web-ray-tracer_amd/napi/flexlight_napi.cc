@@ -379,6 +379,50 @@ static napi_value TraceRays(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+/* the planes a surface call may write: popcount(fields) for fields the library takes; anything else is left to the library to refuse, with room for one plane */
+static size_t surface_planes(uint32_t fields) {
+  size_t planes = 0;
+  if (fields <= 255u) for (uint32_t f = fields; f != 0u; f &= f - 1u) planes++;
+  return planes ? planes : 1;
+}
+/* surfaceRays(handle, rays Float32Array(8 n), fields, textureWidth) -> ArrayBuffer(popcount(fields) * n * 16): flx_rays_surface, the planes as the library writes them
+ * (include/flexlight_hip_debug.h, "surface rows") */
+static napi_value SurfaceRays(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  void *rays; size_t len; uint32_t fields; int32_t tw;
+  if (!typed(env, argv[1], napi_float32_array, &rays, &len)) return nullptr;
+  if (napi_get_value_uint32(env, argv[2], &fields) != napi_ok) { napi_throw_type_error(env, nullptr, "surfaceRays: fields is not a number"); return nullptr; }
+  if (napi_get_value_int32(env, argv[3], &tw) != napi_ok) { napi_throw_type_error(env, nullptr, "surfaceRays: textureWidth is not a number"); return nullptr; }
+  if (len % 8 != 0 || len / 8 > 0xffffffffu) { napi_throw_range_error(env, nullptr, "surfaceRays: a ray needs 8 floats (origin, one unused, direction, one unused)"); return nullptr; }
+  void *planes = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, surface_planes(fields) * (len / 8) * 16, &planes, &buf));
+  flx_status rc = flx_rays_surface(ctx, tw, (const float *)rays, (uint32_t)(len / 8), fields, planes);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_rays_surface", rc);
+  return buf;
+}
+/* frameSurface(handle, params, fields) -> ArrayBuffer(popcount(fields) * width * height * 16): flx_frame_surface */
+static napi_value FrameSurface(napi_env env, napi_callback_info info) {
+  napi_value argv[3];
+  if (!get_args(env, info, 3, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  flx_frame_params p;
+  uint32_t fields;
+  if (!read_params(env, argv[1], &p)) return nullptr;
+  if (napi_get_value_uint32(env, argv[2], &fields) != napi_ok) { napi_throw_type_error(env, nullptr, "frameSurface: fields is not a number"); return nullptr; }
+  if ((uint64_t)p.width * p.height > 0xffffffffull) { napi_throw_range_error(env, nullptr, "frameSurface: the frame has more than 2^32 - 1 pixels"); return nullptr; }
+  void *planes = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, surface_planes(fields) * (size_t)p.width * p.height * 16, &planes, &buf));
+  flx_status rc = flx_frame_surface(ctx, &p, fields, planes);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_frame_surface", rc);
+  return buf;
+}
+
 /* tileRowCount(params) -> rows this context renders */
 static napi_value TileRowCount(napi_env env, napi_callback_info info) {
   napi_value argv[1];
@@ -1190,7 +1234,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas }, { "uploadTextures", UploadTextures }, { "updateTexture", UpdateTexture },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
