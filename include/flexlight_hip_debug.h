@@ -307,7 +307,8 @@ flx_status flx_rays_cast_device(flx_context *ctx, const void *d_rays /* n * 8 fl
 flx_status flx_rays_cast(flx_context *ctx, const float *rays /* n * 8 floats */, void *hits /* n * 8 words */, uint32_t n, uint32_t what);      /* host arrays */
 /* workgroups the query launch takes (0, the default: its own choice — one per compute unit, fewer where the rays do not give every lane one).  For tests: one
  * workgroup makes every lane take ray after ray.  A traced batch (flx_rays_trace_device, below) takes the same number for BOTH of its persistent launches: the first-hit
- * launch (1024 lanes a workgroup) and the paths kernel (256 lanes a workgroup). */
+ * launch (1024 lanes a workgroup) and the paths kernel (256 lanes a workgroup).  So do flx_rays_planes[_device] and flx_rays_image[_device]: the first-hit launch and the
+ * planes kernel (256 lanes a workgroup). */
 flx_status flx_debug_set_query_groups(flx_context *ctx, uint32_t groups);
 /* The last query launch since the scene upload (zeros if none): out[0] its ldsCount (entries of the tree's top staged in LDS), [1] whether its rays were
  * pre-transformed (0: transformed on the fly), [2] workgroups launched (1024 lanes each), [3] waves that drew at least one chunk, [4] n, [5] what, [6] the rays of a
@@ -325,7 +326,9 @@ flx_status flx_debug_last_query(flx_context *ctx, uint32_t out[8]);
  * A RADIANCE ROW is 32 bytes, two 16-byte vector stores: words 0..2 float r, g, b; 3 float 1.0 for a hit, 0.0 for a miss (the frame's alpha); 4 float s of the
  * first hit; 5 int32 its entry, -1 for none; 6 int32 2 x its transform; 7 uint32 the bounce iterations shaded over all samples (the oracle's `shades` for this
  * ray).  A MISS ROW IS ALL ZEROS with -1 in word 5: as in a frame, where a pixel with no primary hit is (0, 0, 0, 0) — not the ambient light.
- * Filter and temporal are image-space and have no meaning here; a ray batch has no width, height or camera, hence the params of its own.
+ * A ray batch has no width, height or camera, hence the params of its own.  Temporal accumulation is image-space over a history and has no meaning for a batch.
+ * The FILTER's bookkeeping does carry over: the denoise chain reads nothing of a camera, and its five render targets are per ray (flx_rays_planes_device, below;
+ * flx_rays_image_device traces a ray IMAGE and runs the chain over it).  This call is the unfiltered radiance.
  * Ordering, producer_stream, the frame server, lights and transforms uploaded over a running launch, the staging of the host variant and n == 0 are
  * flx_rays_cast_device's and flx_rays_cast's, word for word: enqueued on the context's stream with no wait of the host, it sees the scene as of the call, frames in
  * flight finish unchanged; n == 0: FLX_OK, nothing enqueued (the scene and the params are looked at first).  The batch is cut into slabs of rays so that the
@@ -345,11 +348,49 @@ flx_status flx_rays_trace_device(flx_context *ctx, const flx_trace_params *param
                                  uint32_t n, void *producer_stream /* hipStream_t that wrote the rays, or NULL: they are complete */);
 flx_status flx_rays_trace(flx_context *ctx, const flx_trace_params *params, const float *rays /* n * 8 floats */, void *radiance /* n * 8 words */, uint32_t n);      /* host arrays */
 /* most rays of a slab of a traced batch (0, the default: the ceiling above).  For tests: a small value makes a batch span several slabs.  flx_debug_set_query_groups
- * sets the workgroups of a slab's first-hit launch AND of its paths kernel (256 lanes each there). */
+ * sets the workgroups of a slab's first-hit launch AND of its paths kernel (256 lanes each there).  Both apply to flx_rays_planes[_device] and
+ * flx_rays_image[_device] (below) as they do to a traced batch: the slab's ceiling, and the workgroups of the first-hit launch and of the planes kernel. */
 flx_status flx_debug_set_trace_slab(flx_context *ctx, uint32_t rays);
 /* The last traced batch (zeros if none): out[0] its slabs, [1] the rays of a full slab, [2] workgroups of the last slab's paths kernel, [3] whether its bounce walks
  * went in lockstep, [4] n, [5] samples, [6] workgroups of the last slab's first-hit launch, [7] the items a wave draws with one atomic.  It waits for nothing. */
 flx_status flx_debug_last_trace(flx_context *ctx, uint32_t out[8]);
+/* The denoise chain's FIVE FILTER PLANES for the caller's rays, and a ray IMAGE traced and denoised: what flx_render_planes_device and flx_render (use_filter = 1)
+ * are for the pixels behind the pinhole camera, for any rays — a panorama, a fisheye or orthographic view, a stereo pair, a probe's faces, a hybrid renderer's
+ * reflection buffer — at the 1 - 8 samples per ray the renderer is built for.  A ray row and flx_trace_params are flx_rays_trace's.
+ * Per ray: hit = rayTracer(origin, direction), exactly as FLX_RAYS_CLOSEST answers it.  A MISS WRITES ZEROS IN ALL FIVE PLANES, as fragment_main does for an
+ * uncovered pixel.  A hit is fragment_main with use_filter == 1 and is_temporal == 0 (fragment:601-646): the shader's globals (firstRayLength, glassFilter,
+ * originalRMEx, originalTPOx, renderId) are initialised once per ray and THE SAMPLES RUN IN ORDER ON THAT ONE STATE; with c = the samples' sum * (1.0f / samples):
+ *   plane 0 renderColor          fract(c), alpha 1
+ *   plane 1 renderColorIp        floor(c) / 256, alpha glassFilter
+ *   plane 2 renderOriginalColor  originalColor as the last sample left it, alpha min(originalRMEx, firstRayLength) + 1/255
+ *   plane 3 renderId             renderId, its w plus 1/255
+ *   plane 4 renderOriginalId     (0, 0, 0, originalTPOx + 1/255)
+ * — flx_render_planes_device's order, with the oracle's bits.  The ray's origin stands wherever lightTrace uses the camera, the row's two noise words stand in for
+ * the pixel's NDC, the direction is used as given: all as in flx_rays_trace.
+ * d_planes32: float4[5][n], the values before quantisation; d_planes8: uint32[5][n], each the RGBA8 texel a render target stores of that value (NaN and values
+ * <= 0 give 0, values >= 1 give 255, else (uint8)(x * 255 + 0.5f)): what flx_filter_planes_device reads.  Plane p starts at row p * n.  Either may be NULL, not both.
+ * flx_rays_image_device: the rays in image order, row 0 on top, n = width * height; the planes go to memory the context owns (grown, never shrunk), the chain follows
+ * exactly as flx_filter_planes_device launches it (the reference's frame-0 texture state; it reads width, height and hdr only) and writes float4[height][width].
+ * With a camera's rays the image is flx_render's with use_filter = 1, bit for bit wherever rayTracer and a frame's primary walk agree on the first hit.
+ * TEMPORAL ACCUMULATION OF RAY IMAGES IS OUT OF SCOPE: a group of rays has no history to be matched against.
+ * Ordering, producer_stream, the frame server, lights and transforms uploaded over a running launch, the staging of the host variants (they wait and copy out) and
+ * n == 0 (FLX_OK, nothing enqueued, the scene and the params looked at first) are flx_rays_trace_device's and flx_rays_trace's, word for word.  The batch is cut
+ * into slabs of at most 2^21 rays; the scratch is the traced batches' hit rows alone, 32 bytes a ray.  (Where scratch, planes or staging must grow, the host waits
+ * for the stream first.)
+ * Refusals, each with a message of its own and nothing enqueued: flx_rays_trace's for the scene and the params; FLX_ERR_INVALID where both plane pointers are NULL;
+ * where width or height is 0 (whatever the rays) or width * height is 2^32 or more; for an array that is NULL, not memory of the context's device, not 16-byte
+ * aligned or in an allocation too short; where an output overlaps the rays, or the two outputs each other.  A group has no such call, as it traces no rays. */
+flx_status flx_rays_planes_device(flx_context *ctx, const flx_trace_params *params, const void *d_rays /* n * 8 floats, on ctx's device */, uint32_t n,
+                                  void *d_planes8 /* uint32[5][n] RGBA8, or NULL */, void *d_planes32 /* float4[5][n] pre-quantisation, or NULL */,
+                                  void *producer_stream /* hipStream_t that wrote the rays, or NULL: they are complete */);
+flx_status flx_rays_planes(flx_context *ctx, const flx_trace_params *params, const float *rays /* n * 8 floats */, uint32_t n, void *planes8, void *planes32);      /* host arrays */
+flx_status flx_rays_image_device(flx_context *ctx, const flx_trace_params *params, int hdr, const void *d_rays /* width * height * 8 floats, on ctx's device */,
+                                 uint32_t width, uint32_t height, void *d_out_rgba /* float4[height][width] */, void *producer_stream);
+flx_status flx_rays_image(flx_context *ctx, const flx_trace_params *params, int hdr, const float *rays, uint32_t width, uint32_t height, float *out_rgba);      /* host arrays */
+/* The last planes or image call (zeros if none): out[0] its slabs, [1] the rays of a full slab, [2] workgroups of the last slab's planes kernel, [3] whether its
+ * bounce walks went in lockstep, [4] n, [5] samples, [6] workgroups of the last slab's first-hit launch, [7] the rays a wave draws with one atomic.  It waits for
+ * nothing. */
+flx_status flx_debug_last_ray_planes(flx_context *ctx, uint32_t out[8]);
 /* SURFACE ROWS: what the surface is where a ray first hits — the question between "where does it hit" (flx_rays_cast) and "what radiance comes back"
  * (flx_rays_trace, flx_render).  The planes (AOVs) a denoiser of the caller's own, compositing or the shading of a hybrid renderer needs beside the noisy radiance:
  * position, geometric normal, shading normal, texture coordinates, and albedo, RME and TPO with the atlases applied.  They are the first thing lightTrace computes

@@ -3,13 +3,15 @@
  * Trace rays of one's own through a BASELINE scene by the whole JavaScript path — FlexLight facade, scene graph, host flattening, N-API addon,
  * libflexlight_hip.so (flx_rays_trace) — and write what renderer.traceRays() returns.
  *   node tools/trace_rays.js <scene | file.flxs[.gz]> --rays rays.f32 --out rows.bin [--config-spp S --config-bounces B --samples S --bounces B --seed X
- *                            --running N --width W --height H --assets DIR]
+ *                            --running N --width W --height H --assets DIR --filter WxH --hdr 0|1]
  *   <scene>: a BASELINE scene built through the scene graph (scenes/index.js), or a .flxs file replayed (sceneFile.sceneFromFlxs: a box without the assets)
  *   --config-spp, --config-bounces: the renderer's config (by default the scene's BASELINE frame); --samples, --bounces, --seed: traceRays' options
  *   rays.f32: 8 float32 per ray (origin, noise x, direction, noise y); rows.bin: radiance float32[4 n], s float32[n], entry int32[n], transform int32[n],
  *   shades uint32[n].  Without --samples / --bounces / --seed the renderer's defaults apply (config, scene; seed 0); the params used are printed.
  *   --running N: render() runs meanwhile; traceRays is called after every one of its first N frames (the last call's answer is written) and the frames' sums
  *   are printed beside those of the same frames rendered alone.
+ *   --filter WxH: the rays are an image of W x H in image order (row 0 on top): renderer.traceImage() traces and DENOISES it (flx_rays_image); rows.bin is then the
+ *   image alone, float32[4 n].  --hdr: its tone map (by default config.hdr).
  */
 const fs = require('fs');
 const path = require('path');
@@ -49,6 +51,17 @@ const sum = a => { let s = 0; for (let i = 0; i < a.length; i++) if (a[i] === a[
   if (opt('--samples') !== undefined) options.samples = Number(opt('--samples'));
   if (opt('--bounces') !== undefined) options.maxReflections = Number(opt('--bounces'));
   if (opt('--seed') !== undefined) options.randomSeed = Number(opt('--seed'));
+  const filter = opt('--filter');
+  if (filter !== undefined) {
+    const size = /^(\d+)x(\d+)$/.exec(filter);
+    if (!size) throw new Error('--filter takes WxH');
+    if (opt('--hdr') !== undefined) options.hdr = Number(opt('--hdr')) !== 0;
+    const image = renderer.traceImage(rays, Number(size[1]), Number(size[2]), options);
+    fs.writeFileSync(opt('--out', 'rows.bin'), Buffer.from(image.radiance.buffer, image.radiance.byteOffset, image.radiance.byteLength));
+    console.log(JSON.stringify({ rays: rays.length / 8, width: image.width, height: image.height, params: renderer.traceParams(options), hdr: options.hdr === undefined ? !!engine.config.hdr : options.hdr, renderer: renderer.type }));
+    renderer.halt();
+    return;
+  }
   const info = { rays: rays.length / 8, params: renderer.traceParams(options), config: { samplesPerRay: engine.config.samplesPerRay, maxReflections: engine.config.maxReflections, minImportancy: engine.config.minImportancy }, ambient: Array.from(engine.scene.ambientLight), renderer: renderer.type };
   let rows;
   const running = Number(opt('--running', 0));

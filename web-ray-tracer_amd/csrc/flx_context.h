@@ -275,6 +275,10 @@ struct flx_context {
   /* surface rows (flx_surface.hip): their hit scratch is the traced batches' above, their host variants' staging the queries'; what the last call ran
    * (flx_debug_last_surface) */
   struct SurfaceLaunch { uint32_t slabs = 0, slab = 0, n = 0, fields = 0, frame = 0, query_groups = 0; } last_surface;
+  /* filter planes of ray batches (flx_rays_planes.hip): their hit scratch is the traced batches' too; the five RGBA8 planes of a ray image (and the host
+   * variant's byte planes), grown and never shrunk; what the last call ran (flx_debug_last_ray_planes) */
+  DeviceBuffer<uint32_t> d_ray_planes;
+  struct RayPlanesLaunch { uint32_t slabs = 0, slab = 0, groups = 0, lock = 0, n = 0, samples = 0, query_groups = 0; } last_ray_planes;
   /* uploads: pinned staging ring */
   PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};

@@ -1,0 +1,328 @@
+/* flx_rays_planes.hip — the denoise chain's five render targets for a caller's rays, and a ray IMAGE traced and denoised (include/flexlight_hip_debug.h, "ray
+ * queries": flx_rays_planes[_device], flx_rays_image[_device]).
+ *
+ * What a frame computes for a pixel with use_filter = 1 and is_temporal = 0 (fragment:601-646), computed for a ray of the caller's own: hit = rayTracer(origin,
+ * direction); the shader's globals (firstRayLength, glassFilter, originalRMEx, originalTPOx, renderId; fragment:83-89) initialised once; the samples'
+ * lightTrace(hit, direction, origin, cos(float(s)), max_reflections) run IN ORDER ON THAT ONE STATE and added, averaged; then the five targets as fragment_main's
+ * filter branch writes them.  The ray's origin stands where a frame has its camera, the row's two noise coordinates where a frame has the pixel's NDC.
+ *
+ * Because the globals carry from sample to sample, k_rays_paths (flx_rays_trace.hip), whose work items are (ray, sample) pairs, cannot make these planes.  Per slab:
+ *   1. first hits: k_ray_query as it stands (flx_query.hip, what = FLX_RAYS_CLOSEST) into the traced batches' hit rows;
+ *   2. k_rays_planes<LOCK>: persistent waves; a wave draws a block of 64 CONSECUTIVE rays with one atomic (the caller's coherence survives, as in k_rays_paths), and
+ *      A LANE OWNS ONE RAY FOR ALL OF ITS SAMPLES: PixelState stays in registers from the first sample to the stores.  The body is k_trace_pixels' (flx_kernels.hip)
+ *      with the hit row where that kernel has its primary walk: the surface at the first hit is shaded once (shadeSurface) and reused by every sample's first bounce
+ *      (bounceOn) — all samples share the first hit —, then the inner loop: the guard tested before every bounce, one bounce<false, LOCK>() a trip.  A ray stores
+ *      its row of every plane asked for: one 16-byte store per float plane, one 4-byte store per byte plane; plane p starts at row p * n, so the lanes of a block
+ *      write contiguous runs.  A miss stores zeros.  A wave finishes its 64 rays together and then draws the next block.
+ * Measured against the alternative, on the MI355X (profiles/rays_planes.txt): a form in which a lane went on to its next sample as soon as a path ended and free
+ * lanes drew new rays mid-wave once 24 (FLX_WF_BATCH) or 40 of them were free was 20 - 35 % slower than the same form finishing its rays together, and that one
+ * 3 - 9 % slower than this body; 5 and 6 waves per SIMD for the build without the lockstep copy (80 - 96 registers, more scratch) lost to 4 as well.
+ * bounce() is given a DeviceFrame of one view that holds the params' seed and ambient, as in flx_rays_trace.hip.  The batch is cut into slabs of at most 2^21 rays
+ * (flx_trace_slab_rays at one slot a ray); the scratch is hit rows only.  The host waits for nothing — but where the scratch must grow, for the work that may
+ * still use it.
+ *
+ * A ray image is those planes (RGBA8) into memory the context owns, then the chain exactly as flx_filter_planes_device launches it. */
+#include <cstring>
+#include <string>
+
+/* as flx_kernels.hip, whose k_trace_pixels this kernel restates: it shades inline between walks, where the table form of the sin / cos polynomial measures faster
+ * (the same floats; here 16.50 against 16.69 ms on the dragon's 1080p rays), and reads the shading's per-triangle table (flx_device.h: one definition per
+ * translation unit) */
+#define FLX_SINCOS_TABLE 1
+#define FLX_ANGLE_TABLE 1
+#include "flx_context.h"
+#include "flx_kernel_util.h"
+#include "flx_query_args.h"
+#include "flx_ray_planes_args.h"
+
+using namespace flx;
+
+namespace flx {
+
+constexpr uint32_t RAY_PLANES_BLOCK = 64u;             /* consecutive rays a wave draws with one atomic: a ray per lane */
+constexpr uint32_t RAY_PLANES_WAVES = 4;               /* waves per SIMD both builds are allocated for: 128 registers + 296 B of scratch a lane (profiles/rays_planes.txt) */
+
+struct RayPlanesArgs { DeviceScene sc; DeviceFrame fr; };
+static_assert(sizeof(RayPlanesArgs) + 64 <= 4096, "the planes kernel's arguments fit a 4 KB kernarg segment");
+
+/* m: rays of the slab (rays, hits and both outputs point at its first); stride: rows of a plane, the call's n */
+template <bool LOCK>
+__global__ __launch_bounds__(256, RAY_PLANES_WAVES) void k_rays_planes(RayPlanesArgs ra, const float4 *__restrict__ rays, const float4 *__restrict__ hits, uint32_t *__restrict__ planes8,
+                                                                      float4 *__restrict__ planes32, uint32_t *__restrict__ queue, uint32_t m, size_t stride) {
+  const DeviceScene &sc = ra.sc;
+  const DeviceFrame &fr = ra.fr;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t blocks = (m + RAY_PLANES_BLOCK - 1u) / RAY_PLANES_BLOCK;
+  /* fragment:475's guard before a sample's first bounce: importancyFactor and originalColor are (1, 1, 1) there for every sample (k_trace_pixels: firstBounce) */
+  const bool firstBounce = fr.max_reflections > 0 && length(F3(1.0f, 1.0f, 1.0f) * F3(1.0f, 1.0f, 1.0f)) >= fr.min_importancy * SQRT3;
+  WorkCounters cnt = {};
+  for (;;) {
+    uint32_t b = 0;
+    if (lane == 0) b = atomicAdd(queue, 1u);
+    b = __builtin_amdgcn_readfirstlane(b);
+    if (b >= blocks) break;
+    const uint32_t r = b * RAY_PLANES_BLOCK + lane;      /* b < blocks <= 2^15: no overflow */
+    if (r < m) {
+      float4 color = make_float4(0.f, 0.f, 0.f, 0.f), colorIp = color, origColor = color, rid = color, roid = color;      /* a miss: an uncovered pixel, fragment_main writes nothing */
+      const float4 h0 = hits[(size_t)r * 2u];
+      Hit hit0;
+      hit0.suv = F3(h0.x, h0.y, h0.z);
+      hit0.triangleId = __float_as_int(h0.w);
+      hit0.transformId = 0;
+      if (hit0.triangleId != -1) {
+        hit0.transformId = __float_as_int(hits[(size_t)r * 2u + 1u].x);
+        const float4 q0 = rays[(size_t)r * 2u], q1 = rays[(size_t)r * 2u + 1u];
+        const f3 origin = F3(q0.x, q0.y, q0.z);          /* lightTrace's `camera` */
+        const f3 dir0 = F3(q1.x, q1.y, q1.z);            /* as given: rayTracer does not normalise it, lightTrace steps along it by s */
+        Ray pr; pr.origin = origin; pr.dir = dir0;
+        PixelState ps;
+        ps.ndc_x = q0.w; ps.ndc_y = q1.w;
+        ps.seed = fr.view[0].random_seed;
+        ps.firstRayLength = 1.0f; ps.glassFilter = 0.0f; ps.originalRMEx = 0.0f; ps.originalTPOx = 0.0f;
+        ps.originalColor = F3(0.0f, 0.0f, 0.0f);
+        ps.renderId.x = ps.renderId.y = ps.renderId.z = ps.renderId.w = 0.0f;
+        ps.renderOriginalId = ps.renderId;
+        f3 finalColor = F3(0.0f, 0.0f, 0.0f);
+        /* every sample's first bounce lands on the first hit: what its shading knows before it draws a random number is computed once (k_trace_pixels) */
+        SurfaceCtx sf0;
+        WorkCounters sfCnt = {};
+        if (firstBounce) shadeSurface<false>(sc, fr, hit0, pr, origin, sf0, sfCnt);
+        for (int s = 0; s < fr.samples; s++) {
+          float cosSampleN = flx_cos((float)s);
+          PathState p;
+          p.dontFilter = true;
+          p.finalColor = F3(0.0f, 0.0f, 0.0f);
+          p.importancyFactor = F3(1.0f, 1.0f, 1.0f);
+          ps.originalColor = F3(1.0f, 1.0f, 1.0f);
+          p.ray.origin = origin; p.ray.dir = dir0;
+          p.lastHitPoint = origin;
+          p.hit = hit0;
+          bool alive = firstBounce;
+          if (firstBounce) alive = bounceOn<false, LOCK>(sc, fr, sf0, ps, p, origin, cosSampleN, 0, cnt);
+          for (int i = 1; alive && i < fr.max_reflections && length(p.importancyFactor * ps.originalColor) >= fr.min_importancy * SQRT3; i++) {
+            if (!bounce<false, LOCK>(sc, fr, ps, p, origin, cosSampleN, i, cnt)) break;
+          }
+          finalColor = finalColor + (p.finalColor + p.importancyFactor * frame_ambient(fr, 0));
+        }
+        /* fragment:614-646, the filter branch */
+        const float invSamples = 1.0f / (float)fr.samples;
+        finalColor = finalColor * invSamples;
+        color = make_float4(flx_fract(finalColor.x), flx_fract(finalColor.y), flx_fract(finalColor.z), 1.0f);
+        colorIp = make_float4(flx_floor(finalColor.x) * INV_256, flx_floor(finalColor.y) * INV_256, flx_floor(finalColor.z) * INV_256, ps.glassFilter);
+        origColor = make_float4(ps.originalColor.x, ps.originalColor.y, ps.originalColor.z, flx_min(ps.originalRMEx, ps.firstRayLength) + INV_255);
+        rid = make_float4(ps.renderId.x, ps.renderId.y, ps.renderId.z, ps.renderId.w + INV_255);
+        roid = make_float4(0.0f, 0.0f, 0.0f, ps.originalTPOx + INV_255);
+      }
+      if (planes32) {
+        float4 *o = planes32 + r;
+        o[0] = color; o[stride] = colorIp; o[2u * stride] = origColor; o[3u * stride] = rid; o[4u * stride] = roid;
+      }
+      if (planes8) {
+        uint32_t *o = planes8 + r;
+        o[0] = pack_rgba8(color.x, color.y, color.z, color.w);
+        o[stride] = pack_rgba8(colorIp.x, colorIp.y, colorIp.z, colorIp.w);
+        o[2u * stride] = pack_rgba8(origColor.x, origColor.y, origColor.z, origColor.w);
+        o[3u * stride] = pack_rgba8(rid.x, rid.y, rid.z, rid.w);
+        o[4u * stride] = pack_rgba8(roid.x, roid.y, roid.z, roid.w);
+      }
+    }
+  }
+}
+
+}  // namespace flx
+
+/* ---- the calls ------------------------------------------------------------------------------------------------------------------------------------- */
+
+static flx_status fail(flx_context *ctx, flx_status code, const char *msg) { return flx_fail(ctx, code, msg); }
+static flx_status fail(flx_context *ctx, flx_status code, const std::string &msg) { return flx_fail(ctx, code, msg.c_str()); }
+
+/* what every call refuses before it looks at an array: flx_rays_trace's rule for the scene and the params */
+static flx_status planes_refused(flx_context *ctx, const flx_trace_params *p, const char *call) {
+  if (!ctx->have_scene || !ctx->have_transforms) return fail(ctx, FLX_ERR_NO_SCENE, std::string(call) + ": no scene and transforms uploaded");
+  const char *what = "";
+  switch (flx_trace_args_check(p != nullptr, p ? p->samples : 0, p ? p->max_reflections : 0, p ? p->texture_width : 0, 0u, 0u, 0u)) {
+    case FLX_TRACE_ARGS_OK: return FLX_OK;
+    case FLX_TRACE_PARAMS_NULL: what = "params is NULL"; break;
+    case FLX_TRACE_SAMPLES: what = "samples is less than 1"; break;
+    case FLX_TRACE_REFLECTIONS: what = "max_reflections is negative"; break;
+    default: what = "texture_width is less than 1"; break;
+  }
+  return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": " + what);
+}
+
+/* a refusal of flx_ray_planes_args.h in words */
+static flx_status planes_refusal(flx_context *ctx, enum flx_ray_planes_refusal why, const char *call) {
+  const char *what = "";
+  switch (why) {
+    case FLX_RAY_PLANES_ARGS_OK: return FLX_OK;
+    case FLX_RAY_PLANES_NONE: what = "planes8 and planes32 are both NULL: no plane is asked for"; break;
+    case FLX_RAY_PLANES_SIZE: what = "width or height is 0"; break;
+    case FLX_RAY_PLANES_PIXELS: what = "width * height is 2^32 or more"; break;
+    case FLX_RAY_PLANES_NULL: what = "an array is NULL"; break;
+    case FLX_RAY_PLANES_WRAPS: what = "the rows leave the address space"; break;
+    case FLX_RAY_PLANES_OVERLAP_RAYS: what = "the rays and an output overlap"; break;
+    case FLX_RAY_PLANES_OVERLAP_OUT: what = "planes8 and planes32 overlap"; break;
+  }
+  return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": " + what);
+}
+
+/* the frame bounce() is given: one view, the params' seed and ambient (flx_rays_trace.hip: trace_frame), and use_filter, which makes bounce() keep renderId too (the
+ * rest of the filter's bookkeeping it does on every path) */
+static void planes_frame(const flx_trace_params *p, DeviceFrame &fr) {
+  memset(&fr, 0, sizeof fr);
+  fr.use_filter = 1;
+  fr.width = fr.height = fr.rows = fr.frame_rows = fr.frames = fr.tile_rows = fr.tile_count = 1u;
+  fr.samples = p->samples; fr.max_reflections = p->max_reflections;
+  fr.samples_shift = -1;
+  fr.min_importancy = p->min_importancy;
+  fr.texture_width = (float)p->texture_width;
+  memcpy(fr.view[0].ambient, p->ambient, sizeof fr.view[0].ambient);
+  fr.view[0].random_seed = p->random_seed;
+}
+
+/* The slabs' launches, the arguments accepted: the five planes of n > 0 rays into d_planes8 and / or d_planes32 */
+static flx_status planes_enqueue(flx_context *ctx, const flx_trace_params *params, const void *d_rays, uint32_t n, void *d_planes8, void *d_planes32, void *producer_stream,
+                                 const char *call) {
+  flx_status s;
+  RayPlanesArgs ra;
+  if ((s = flx_make_scene(ctx, ra.sc))) return s;           /* (refuses a scene that names a transform not uploaded) */
+  if ((s = flx_server_stop(ctx))) return s;                 /* as flx_render_device: the frame server's launch ends after the frames posted to it */
+  planes_frame(params, ra.fr);
+  const uint32_t slab = flx_trace_slab_rays(1u, ctx->trace_slab);
+  const uint32_t most = n < slab ? n : slab;                /* rays of the largest slab */
+  if (!ctx->d_trace_hits.fits((size_t)most * 2u) || !ctx->d_trace_ctl) {
+    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier batch may still use the scratch that is about to go) */
+    if ((s = ctx->d_trace_hits.ensure(ctx, (size_t)most * 2u)) || (s = ctx->d_trace_ctl.ensure(ctx, 4))) return s;
+  }
+  if (producer_stream) {
+    if (!ctx->query_produced) FLX_HIP(ctx, hipEventCreateWithFlags(&ctx->query_produced, hipEventDisableTiming));
+    FLX_HIP(ctx, hipEventRecord(ctx->query_produced, (hipStream_t)producer_stream));
+    FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->query_produced, 0));
+  }
+  if ((s = flx_angle_table(ctx, ra.sc))) return s;          /* the shading's per-triangle table, made again first where the scene or the transforms changed */
+  const bool lock = FLX_LOCKSTEP && ra.sc.lock_entries != 0u;
+  const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
+  flx_context::RayPlanesLaunch ran;
+  ran.n = n; ran.samples = (uint32_t)params->samples; ran.slab = slab; ran.lock = lock ? 1u : 0u;
+  for (uint64_t first = 0; first < n; first += slab) {
+    const uint32_t m = (uint32_t)(n - first < slab ? n - first : slab);
+    const float4 *rays = (const float4 *)d_rays + first * 2u;
+    uint32_t *out8 = d_planes8 ? (uint32_t *)d_planes8 + first : nullptr;
+    float4 *out32 = d_planes32 ? (float4 *)d_planes32 + first : nullptr;
+    /* the words of the slab's launches: [0] the query's chunk cursor, [1] its waves that drew; [2] the planes kernel's block cursor */
+    FLX_HIP(ctx, hipMemsetAsync(ctx->d_trace_ctl, 0, 4 * sizeof(uint32_t), ctx->stream));
+    QueryLaunch q;
+    if (!launch_ray_query(ra.sc, rays, ctx->d_trace_hits, m, FLX_RAYS_CLOSEST, ctx->d_trace_ctl, cus, ctx->query_groups, ctx->stream, &q))
+      return fail(ctx, FLX_ERR_DEVICE, std::string(call) + ": the query kernel cannot have its LDS on this device");
+    FLX_HIP(ctx, hipGetLastError());
+    /* persistent grid: enough workgroups to fill every CU at the kernel's occupancy, no more than the blocks of rays fill; flx_debug_set_query_groups sets it too */
+    const uint32_t full = (((m + RAY_PLANES_BLOCK - 1u) / RAY_PLANES_BLOCK) + 3u) / 4u;
+    const uint32_t groups = ctx->query_groups ? ctx->query_groups : (full < cus * 8u ? full : cus * 8u);
+    uint32_t *queue = ctx->d_trace_ctl.get() + 2;
+    if (lock) hipLaunchKernelGGL(k_rays_planes<true>, dim3(groups), dim3(256), 0, ctx->stream, ra, rays, (const float4 *)ctx->d_trace_hits.get(), out8, out32, queue, m, (size_t)n);
+    else hipLaunchKernelGGL(k_rays_planes<false>, dim3(groups), dim3(256), 0, ctx->stream, ra, rays, (const float4 *)ctx->d_trace_hits.get(), out8, out32, queue, m, (size_t)n);
+    FLX_HIP(ctx, hipGetLastError());
+    ran.slabs++; ran.groups = groups; ran.query_groups = q.groups;
+  }
+  ctx->last_ray_planes = ran;
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_rays_planes_device(flx_context *ctx, const flx_trace_params *params, const void *d_rays, uint32_t n, void *d_planes8, void *d_planes32,
+                                             void *producer_stream) {
+  static const char *const call = "flx_rays_planes_device";
+  if (!ctx) return FLX_ERR_INVALID;
+  flx_status s = planes_refused(ctx, params, call);
+  if (s || n == 0) return s;
+  const enum flx_ray_planes_refusal arrays = flx_ray_planes_arrays_check((uint64_t)(uintptr_t)d_rays, (uint64_t)(uintptr_t)d_planes8, (uint64_t)(uintptr_t)d_planes32, n);
+  const bool overlap = arrays == FLX_RAY_PLANES_OVERLAP_RAYS || arrays == FLX_RAY_PLANES_OVERLAP_OUT;      /* (said after the pointers are known to be the device's) */
+  if (arrays != FLX_RAY_PLANES_ARGS_OK && !overlap) return planes_refusal(ctx, arrays, call);
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  if (!flx_rows_on_device(ctx, d_rays, (size_t)n * FLX_RAY_PLANES_RAY_BYTES))
+    return fail(ctx, FLX_ERR_INVALID, "flx_rays_planes_device: the rays are not n rows in memory of the context's device, 16-byte aligned");
+  if (d_planes8 && !flx_rows_on_device(ctx, d_planes8, (size_t)n * FLX_RAY_PLANES * FLX_RAY_PLANES_ROW8))
+    return fail(ctx, FLX_ERR_INVALID, "flx_rays_planes_device: planes8 is not 5 n texels in memory of the context's device, 16-byte aligned");
+  if (d_planes32 && !flx_rows_on_device(ctx, d_planes32, (size_t)n * FLX_RAY_PLANES * FLX_RAY_PLANES_ROW32))
+    return fail(ctx, FLX_ERR_INVALID, "flx_rays_planes_device: planes32 is not 5 n rows in memory of the context's device, 16-byte aligned");
+  if (overlap) return planes_refusal(ctx, arrays, call);
+  return planes_enqueue(ctx, params, d_rays, n, d_planes8, d_planes32, producer_stream, call);
+}
+
+extern "C" flx_status flx_rays_planes(flx_context *ctx, const flx_trace_params *params, const float *rays, uint32_t n, void *planes8, void *planes32) {
+  static const char *const call = "flx_rays_planes";
+  if (!ctx) return FLX_ERR_INVALID;
+  flx_status s = planes_refused(ctx, params, call);
+  if (s || n == 0) return s;
+  if (!planes8 && !planes32) return planes_refusal(ctx, FLX_RAY_PLANES_NONE, call);
+  if (!rays) return planes_refusal(ctx, FLX_RAY_PLANES_NULL, call);
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t rows = (size_t)n * FLX_RAY_PLANES;
+  if (!ctx->d_query_rays.fits((size_t)n * 2u) || (planes32 && !ctx->d_query_hits.fits(rows)) || (planes8 && !ctx->d_ray_planes.fits(rows))) {
+    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier call may still read or write the staging that is about to go) */
+    if ((s = ctx->d_query_rays.ensure(ctx, (size_t)n * 2u))) return s;
+    if (planes32 && (s = ctx->d_query_hits.ensure(ctx, rows))) return s;
+    if (planes8 && (s = ctx->d_ray_planes.ensure(ctx, rows))) return s;
+  }
+  FLX_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, (size_t)n * FLX_RAY_PLANES_RAY_BYTES, hipMemcpyHostToDevice, ctx->stream));
+  if ((s = flx_rays_planes_device(ctx, params, ctx->d_query_rays, n, planes8 ? ctx->d_ray_planes.get() : nullptr, planes32 ? ctx->d_query_hits.get() : nullptr, nullptr))) return s;
+  if (planes8) FLX_HIP(ctx, hipMemcpyAsync(planes8, ctx->d_ray_planes, rows * FLX_RAY_PLANES_ROW8, hipMemcpyDeviceToHost, ctx->stream));
+  if (planes32) FLX_HIP(ctx, hipMemcpyAsync(planes32, ctx->d_query_hits, rows * FLX_RAY_PLANES_ROW32, hipMemcpyDeviceToHost, ctx->stream));
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_rays_image_device(flx_context *ctx, const flx_trace_params *params, int hdr, const void *d_rays, uint32_t width, uint32_t height, void *d_out_rgba,
+                                            void *producer_stream) {
+  static const char *const call = "flx_rays_image_device";
+  if (!ctx) return FLX_ERR_INVALID;
+  flx_status s = planes_refused(ctx, params, call);
+  if (s) return s;
+  uint32_t n = 0;
+  if ((s = planes_refusal(ctx, flx_ray_image_size_check(width, height, &n), call))) return s;
+  const enum flx_ray_planes_refusal arrays = flx_ray_image_arrays_check((uint64_t)(uintptr_t)d_rays, (uint64_t)(uintptr_t)d_out_rgba, n);
+  if (arrays != FLX_RAY_PLANES_ARGS_OK && arrays != FLX_RAY_PLANES_OVERLAP_RAYS) return planes_refusal(ctx, arrays, call);
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  if (!flx_rows_on_device(ctx, d_rays, (size_t)n * FLX_RAY_PLANES_RAY_BYTES))
+    return fail(ctx, FLX_ERR_INVALID, "flx_rays_image_device: the rays are not width * height rows in memory of the context's device, 16-byte aligned");
+  if (!flx_rows_on_device(ctx, d_out_rgba, (size_t)n * FLX_RAY_PLANES_ROW32))
+    return fail(ctx, FLX_ERR_INVALID, "flx_rays_image_device: the image is not width * height float4 in memory of the context's device, 16-byte aligned");
+  if (arrays == FLX_RAY_PLANES_OVERLAP_RAYS) return planes_refusal(ctx, arrays, call);
+  const size_t rows = (size_t)n * FLX_RAY_PLANES;
+  if (!ctx->d_ray_planes.fits(rows)) {
+    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier image's chain may still read the planes that are about to go) */
+    if ((s = ctx->d_ray_planes.ensure(ctx, rows))) return s;
+  }
+  if ((s = planes_enqueue(ctx, params, d_rays, n, ctx->d_ray_planes.get(), nullptr, producer_stream, call))) return s;
+  /* the chain reads width, height and hdr of a frame's params, nothing of a camera: frame-0 texture state, as flx_filter_planes_device starts it */
+  flx_frame_params image;
+  memset(&image, 0, sizeof image);
+  image.width = width; image.height = height; image.hdr = hdr;
+  return flx_filter_planes_enqueue(ctx, &image, ctx->d_ray_planes.get(), d_out_rgba, true);
+}
+
+extern "C" flx_status flx_rays_image(flx_context *ctx, const flx_trace_params *params, int hdr, const float *rays, uint32_t width, uint32_t height, float *out_rgba) {
+  static const char *const call = "flx_rays_image";
+  if (!ctx) return FLX_ERR_INVALID;
+  flx_status s = planes_refused(ctx, params, call);
+  if (s) return s;
+  uint32_t n = 0;
+  if ((s = planes_refusal(ctx, flx_ray_image_size_check(width, height, &n), call))) return s;
+  if (!rays || !out_rgba) return planes_refusal(ctx, FLX_RAY_PLANES_NULL, call);
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  if (!ctx->d_query_rays.fits((size_t)n * 2u) || !ctx->d_query_hits.fits(n)) {
+    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier call may still read or write the staging that is about to go) */
+    if ((s = ctx->d_query_rays.ensure(ctx, (size_t)n * 2u)) || (s = ctx->d_query_hits.ensure(ctx, n))) return s;
+  }
+  FLX_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, (size_t)n * FLX_RAY_PLANES_RAY_BYTES, hipMemcpyHostToDevice, ctx->stream));
+  if ((s = flx_rays_image_device(ctx, params, hdr, ctx->d_query_rays, width, height, ctx->d_query_hits, nullptr))) return s;
+  FLX_HIP(ctx, hipMemcpyAsync(out_rgba, ctx->d_query_hits, (size_t)n * FLX_RAY_PLANES_ROW32, hipMemcpyDeviceToHost, ctx->stream));
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_debug_last_ray_planes(flx_context *ctx, uint32_t out[8]) {
+  if (!ctx || !out) return FLX_ERR_INVALID;
+  const flx_context::RayPlanesLaunch &t = ctx->last_ray_planes;
+  out[0] = t.slabs; out[1] = t.slab; out[2] = t.groups; out[3] = t.lock; out[4] = t.n; out[5] = t.samples; out[6] = t.query_groups; out[7] = RAY_PLANES_BLOCK;
+  return FLX_OK;
+}

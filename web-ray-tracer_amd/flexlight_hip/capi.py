@@ -37,6 +37,7 @@ EXPORTS = [
     "flx_rays_cast_device", "flx_rays_cast", "flx_debug_set_query_groups", "flx_debug_last_query",
     "flx_rays_trace_device", "flx_rays_trace", "flx_debug_set_trace_slab", "flx_debug_last_trace",
     "flx_rays_surface_device", "flx_rays_surface", "flx_frame_surface_device", "flx_frame_surface", "flx_debug_last_surface",
+    "flx_rays_planes_device", "flx_rays_planes", "flx_rays_image_device", "flx_rays_image", "flx_debug_last_ray_planes",
     "flx_textures_upload", "flx_textures_upload_device", "flx_texture_update", "flx_texture_update_device", "flx_group_textures_upload", "flx_group_texture_update",
     "flx_debug_atlas_read",
 ]
@@ -50,6 +51,7 @@ RAYS_CLOSEST, RAYS_OCCLUDED, RAYS_COUNT = 1, 2, 4      # FLX_RAYS_* of include/f
 SURFACE_HIT, SURFACE_POSITION, SURFACE_GEOMETRY_NORMAL, SURFACE_NORMAL, SURFACE_UV, SURFACE_ALBEDO, SURFACE_RME, SURFACE_TPO = 1, 2, 4, 8, 16, 32, 64, 128
 SURFACE_ALL = 255
 SURFACE_NAMES = ("hit", "position", "geometry_normal", "normal", "uv", "albedo", "rme", "tpo")      # unpack_surface's keys, in bit order
+PLANE_NAMES = ("color", "color_ip", "original_color", "id", "original_id")      # the five filter planes of ray_planes, in flx_render_planes_device's order: unpack_planes' keys
 QUERY_CHUNK = 128              # consecutive rays a wave of the query kernel draws with one atomic (QUERY_CHUNK of csrc/flx_kernels.h; flx_debug_last_query reports it)
 FRAME_FXAA = 0x10              # FLX_FRAME_FXAA: flags of flx_frame_begin's format
 FRAME_TAA = 0x20               # FLX_FRAME_TAA
@@ -115,6 +117,11 @@ def _load():
         "flx_frame_surface_device": (C.c_int, [vp, C.POINTER(FrameParams), u32, vp]),
         "flx_frame_surface": (C.c_int, [vp, C.POINTER(FrameParams), u32, vp]),
         "flx_debug_last_surface": (C.c_int, [vp, C.POINTER(u32)]),
+        "flx_rays_planes_device": (C.c_int, [vp, C.POINTER(TraceParams), vp, u32, vp, vp, vp]),
+        "flx_rays_planes": (C.c_int, [vp, C.POINTER(TraceParams), fp, u32, vp, vp]),
+        "flx_rays_image_device": (C.c_int, [vp, C.POINTER(TraceParams), C.c_int, vp, u32, u32, vp, vp]),
+        "flx_rays_image": (C.c_int, [vp, C.POINTER(TraceParams), C.c_int, fp, u32, u32, fp]),
+        "flx_debug_last_ray_planes": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_textures_upload": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32]),
         "flx_textures_upload_device": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32, vp]),
         "flx_texture_update": (C.c_int, [vp, C.c_int, u32, C.POINTER(Image)]),
@@ -367,6 +374,20 @@ def unpack_radiance(rows):
     words = np.ascontiguousarray(rows, np.uint8).reshape(-1, 32).view(np.uint32)
     return {"rgb": words[:, 0:3].view(np.float32).copy(), "alpha": words[:, 3].view(np.float32).copy(), "s": words[:, 4].view(np.float32).copy(),
             "entry": words[:, 5].view(np.int32).copy(), "transform2": words[:, 6].view(np.int32).copy(), "shades": words[:, 7].copy()}
+
+
+def unpack_planes(planes):
+    """the five filter planes of ray_planes / ray_planes_device (uint32 [5, n] RGBA8 texels, or float32 [5, n, 4]; a numpy array or a torch tensor: a tensor is
+    copied to the host, which waits for the stream it is asked on — sync() first where the call ran on another) -> dict by PLANE_NAMES: uint8 [n, 4] (r, g, b, a
+    of every texel) for byte planes, float32 [n, 4] for float planes"""
+    if not isinstance(planes, np.ndarray):
+        planes = planes.detach().cpu().numpy()
+    if planes.dtype == np.float32 and planes.ndim == 3 and planes.shape[0] == 5 and planes.shape[2] == 4:
+        return {name: planes[k].copy() for k, name in enumerate(PLANE_NAMES)}
+    if planes.dtype.kind in "iu" and planes.dtype.itemsize == 4 and planes.ndim == 2 and planes.shape[0] == 5:
+        texels = np.ascontiguousarray(planes).view(np.uint8).reshape(5, -1, 4)
+        return {name: texels[k].copy() for k, name in enumerate(PLANE_NAMES)}
+    raise ValueError("unpack_planes: planes is uint32 [5, n] or float32 [5, n, 4]")
 
 
 def surface_planes(fields):
@@ -689,6 +710,84 @@ class Context:
         out = (C.c_uint32 * 8)()
         self._check(LIB.flx_debug_last_trace(self._h, out), "flx_debug_last_trace")
         return dict(zip(("slabs", "slab", "path_groups", "lockstep", "n", "samples", "query_groups", "chunk"), list(out)))
+
+    # -- filter planes of ray batches, ray images ------------------------------------------------------
+    def _device_out(self, out, bytes_needed, call, what):
+        """an output of a *_device call: a contiguous tensor on the context's device of at least so many bytes, or an address -> the address"""
+        if isinstance(out, int):
+            return out
+        if out.device.type != "cuda" or out.device.index != self._device or not out.is_contiguous() or out.numel() * out.element_size() < bytes_needed:
+            raise ValueError("%s: %s is a contiguous tensor of at least %d bytes on the context's device" % (call, what, bytes_needed))
+        return out.data_ptr()
+
+    def ray_planes_device(self, rays, params, planes8=None, planes32=None, stream=None):
+        """flx_rays_planes_device: the denoise chain's five filter planes (PLANE_NAMES) of rays of the caller's own, in device memory.  rays and params: as for
+        trace_rays_device; planes8: True (a new int32 tensor [5, n] of RGBA8 texels), such a tensor to write into, an address, or None: not asked for; planes32: True
+        (a new float32 tensor [5, n, 4], the values before quantisation), a tensor, an address, or None.  With neither given planes8 is made.  stream: as for
+        trace_rays_device.  Returns (planes8, planes32) ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE: sync() before they are read on another stream
+        (unpack_planes reads them).  All arrays stay alive until then."""
+        r, n = _ray_rows(rays, self._device, "ray_planes_device")
+        if params is not None and not isinstance(params, TraceParams):
+            raise TypeError("ray_planes_device: params is a TraceParams")      # (None goes to the library, which refuses it)
+        if planes8 is None and planes32 is None:
+            planes8 = True
+        if planes8 is True or planes32 is True:
+            import torch
+            if planes8 is True:
+                planes8 = torch.empty((5, n), dtype=torch.int32, device="cuda:%d" % self._device)
+            if planes32 is True:
+                planes32 = torch.empty((5, n, 4), dtype=torch.float32, device="cuda:%d" % self._device)
+        o8 = self._device_out(planes8, 5 * n * 4, "ray_planes_device", "planes8") if planes8 is not None else None
+        o32 = self._device_out(planes32, 5 * n * 16, "ray_planes_device", "planes32") if planes32 is not None else None
+        self._check(LIB.flx_rays_planes_device(self._h, C.byref(params) if params is not None else None, C.c_void_p(r), n, C.c_void_p(o8), C.c_void_p(o32),
+                                               _stream_handle(stream)), "flx_rays_planes_device")
+        return planes8, planes32
+
+    def ray_planes(self, rays, params, floats=False):
+        """flx_rays_planes: rays [n, 8] float32 in host memory -> the five filter planes, complete: uint32 [5, n] RGBA8 texels, or with floats=True the pair (uint32
+        [5, n], float32 [5, n, 4]) (unpack_planes)"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        n = rays.shape[0]
+        p8 = np.zeros((5, n), np.uint32)
+        p32 = np.zeros((5, n, 4), np.float32) if floats else None
+        self._check(LIB.flx_rays_planes(self._h, C.byref(params) if params is not None else None, _fp(rays), n, p8.ctypes.data_as(C.c_void_p),
+                                        p32.ctypes.data_as(C.c_void_p) if floats else None), "flx_rays_planes")
+        return (p8, p32) if floats else p8
+
+    def ray_image_device(self, rays, width, height, params, hdr=True, out=None, stream=None):
+        """flx_rays_image_device: a ray IMAGE traced and denoised, in device memory.  rays: width * height rows in image order, row 0 on top (as for
+        trace_rays_device); params: TraceParams; hdr: the chain's tone map (FrameParams.hdr); out: None (a new float32 tensor [height, width, 4]), such a tensor to
+        write into, or an address; stream: as for trace_rays_device.  Returns the image ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        r, n = _ray_rows(rays, self._device, "ray_image_device")
+        if params is not None and not isinstance(params, TraceParams):
+            raise TypeError("ray_image_device: params is a TraceParams")
+        width, height = int(width), int(height)
+        if n != width * height:
+            raise ValueError("ray_image_device: %d rays are no image of %d x %d" % (n, width, height))
+        if out is None:
+            import torch
+            out = torch.empty((height, width, 4), dtype=torch.float32, device="cuda:%d" % self._device)
+        o = self._device_out(out, n * 16, "ray_image_device", "out")
+        self._check(LIB.flx_rays_image_device(self._h, C.byref(params) if params is not None else None, int(bool(hdr)), C.c_void_p(r), width, height, C.c_void_p(o),
+                                              _stream_handle(stream)), "flx_rays_image_device")
+        return out
+
+    def ray_image(self, rays, width, height, params, hdr=True):
+        """flx_rays_image: rays [width * height, 8] float32 in host memory, image order -> the denoised image float32 [height, width, 4], complete"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        width, height = int(width), int(height)
+        if rays.shape[0] != width * height:
+            raise ValueError("ray_image: %d rays are no image of %d x %d" % (rays.shape[0], width, height))
+        out = np.zeros((height, width, 4), np.float32)
+        self._check(LIB.flx_rays_image(self._h, C.byref(params) if params is not None else None, int(bool(hdr)), _fp(rays), width, height, _fp(out)), "flx_rays_image")
+        return out
+
+    def last_ray_planes(self):
+        """flx_debug_last_ray_planes -> dict (zeros when no planes or image call ran): slabs, slab (rays of a full one), groups (of 256 lanes, last slab's planes
+        kernel), lockstep, n, samples, query_groups (of 1024 lanes, last slab), block (rays per draw)"""
+        out = (C.c_uint32 * 8)()
+        self._check(LIB.flx_debug_last_ray_planes(self._h, out), "flx_debug_last_ray_planes")
+        return dict(zip(("slabs", "slab", "groups", "lockstep", "n", "samples", "query_groups", "block"), list(out)))
 
     # -- surface rows -------------------------------------------------------------------------------
     def _surface_out(self, out, n, fields, call):

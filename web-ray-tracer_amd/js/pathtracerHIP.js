@@ -304,6 +304,24 @@ class PathTracerHIP {
     return traceRaysOn(this._context(), rays, this.traceParams(options));
   }
 
+  /* A ray IMAGE, traced and DENOISED: any projection the application makes rays for — a panorama, a fisheye or orthographic view, a stereo pair, a probe's faces, a
+   * reflection buffer — through the renderer's own filter (flx_rays_image, include/flexlight_hip_debug.h "ray queries").  rays: traceRays' rows, width * height of
+   * them in image order, row 0 on top.  options: traceRays' plus hdr (by default config.hdr), the chain's tone map.  Per ray the five filter planes are what a frame
+   * with config.filter writes for a pixel (the samples run in order on one state; a miss is zeros), and the chain over them is the frame's.  Returns { width,
+   * height, radiance: Float32Array(4 n) }.  Temporal accumulation does not apply: a set of rays has no history.  It waits for the answer; frames in flight finish
+   * unchanged. */
+  traceImage (rays, width, height, options) {
+    if (this._devices) throw new Error('traceImage: one GPU only (a group of GPUs traces no rays)');
+    if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('traceImage: rays is a Float32Array of 8 floats per ray');
+    if (!Number.isInteger(width) || !Number.isInteger(height) || width < 0 || height < 0 || rays.length / 8 !== width * height) {
+      throw new RangeError('traceImage: rays is width * height rays in image order');
+    }
+    this._uploadFrameState();
+    const hdr = options && options.hdr !== undefined ? !!options.hdr : !!this.config.hdr;
+    const image = native().rayImage(this._context(), rays, width, height, this.traceParams(options), hdr);
+    return { width, height, radiance: new Float32Array(image) };
+  }
+
   /* What the SURFACE is where rays of the application's own first hit: the inputs of a denoiser, of compositing, of a hybrid renderer's shading
    * (flx_rays_surface, include/flexlight_hip_debug.h "surface rows").  rays: castRays' rows (words 3 and 7 are ignored); fields: SURFACE bits (by default all).
    * Returns typed arrays per plane asked for, 4 floats a ray — hit (s, u, v, -), position (x y z, 1 for a hit), geometryNormal, normal (facing the ray; w: -1

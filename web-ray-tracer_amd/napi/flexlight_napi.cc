@@ -346,6 +346,24 @@ static bool read_params(napi_env env, napi_value o, flx_frame_params *p) {
   return true;
 }
 
+/* a traced call's params { samples, maxReflections, minImportancy, ambient, randomSeed?, textureWidth } -> flx_trace_params; `call`: the JavaScript name, for the
+ * messages.  A JavaScript number -> int32_t is refused where the cast would not be defined (NaN, beyond the type's range); the library judges the values that fit */
+static bool read_trace_params(napi_env env, napi_value o, const char *call, flx_trace_params *p) {
+  memset(p, 0, sizeof *p);
+  double d = 0;
+  auto int32 = [&](const char *key, int32_t *out) {
+    if (!num(env, o, key, &d)) return false;
+    if (!(d >= -2147483648.0 && d <= 2147483647.0)) { napi_throw_range_error(env, nullptr, (std::string(call) + ": " + key + " is not a number an int32 holds").c_str()); return false; }
+    *out = (int32_t)d;
+    return true;
+  };
+  if (!int32("samples", &p->samples) || !int32("maxReflections", &p->max_reflections)) return false;
+  if (!num(env, o, "minImportancy", &d)) return false; p->min_importancy = (float)d;
+  if (!floats(env, o, "ambient", p->ambient, 3)) return false;
+  d = 0; if (!num(env, o, "randomSeed", &d, false)) return false; p->random_seed = (float)d;
+  return int32("textureWidth", &p->texture_width);
+}
+
 /* traceRays(handle, rays Float32Array(8 n), params { samples, maxReflections, minImportancy, ambient, randomSeed?, textureWidth }) -> ArrayBuffer(32 n):
  * flx_rays_trace, the radiance rows as the library writes them (include/flexlight_hip_debug.h) */
 static napi_value TraceRays(napi_env env, napi_callback_info info) {
@@ -357,25 +375,38 @@ static napi_value TraceRays(napi_env env, napi_callback_info info) {
   if (!typed(env, argv[1], napi_float32_array, &rays, &len)) return nullptr;
   if (len % 8 != 0 || len / 8 > 0xffffffffu) { napi_throw_range_error(env, nullptr, "traceRays: a ray needs 8 floats (origin, noise x, direction, noise y)"); return nullptr; }
   flx_trace_params p;
-  memset(&p, 0, sizeof p);
-  double d = 0;
-  /* a JavaScript number -> int32_t: refused where the cast would not be defined (NaN, beyond the type's range); the library judges the values that fit */
-  auto int32 = [&](const char *key, int32_t *out) {
-    if (!num(env, argv[2], key, &d)) return false;
-    if (!(d >= -2147483648.0 && d <= 2147483647.0)) { napi_throw_range_error(env, nullptr, (std::string("traceRays: ") + key + " is not a number an int32 holds").c_str()); return false; }
-    *out = (int32_t)d;
-    return true;
-  };
-  if (!int32("samples", &p.samples) || !int32("maxReflections", &p.max_reflections)) return nullptr;
-  if (!num(env, argv[2], "minImportancy", &d)) return nullptr; p.min_importancy = (float)d;
-  if (!floats(env, argv[2], "ambient", p.ambient, 3)) return nullptr;
-  d = 0; if (!num(env, argv[2], "randomSeed", &d, false)) return nullptr; p.random_seed = (float)d;
-  if (!int32("textureWidth", &p.texture_width)) return nullptr;
+  if (!read_trace_params(env, argv[2], "traceRays", &p)) return nullptr;
   void *rows = nullptr;
   napi_value buf;
   NAPI_OK(env, napi_create_arraybuffer(env, (len / 8) * 32, &rows, &buf));
   flx_status rc = flx_rays_trace(ctx, &p, (const float *)rays, rows, (uint32_t)(len / 8));
   if (rc != FLX_OK) return fail(env, ctx, "flx_rays_trace", rc);
+  return buf;
+}
+
+/* rayImage(handle, rays Float32Array(8 width height), width, height, params (traceRays'), hdr) -> ArrayBuffer(16 width height): flx_rays_image, the rays in image
+ * order (row 0 on top) traced into the five filter planes and denoised by the chain; float4 per pixel (include/flexlight_hip_debug.h) */
+static napi_value RayImage(napi_env env, napi_callback_info info) {
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  void *rays; size_t len; uint32_t width, height;
+  if (!typed(env, argv[1], napi_float32_array, &rays, &len)) return nullptr;
+  if (napi_get_value_uint32(env, argv[2], &width) != napi_ok || napi_get_value_uint32(env, argv[3], &height) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "rayImage: width and height are numbers");
+    return nullptr;
+  }
+  if (len % 8 != 0 || (uint64_t)(len / 8) != (uint64_t)width * height) { napi_throw_range_error(env, nullptr, "rayImage: width * height rays of 8 floats (origin, noise x, direction, noise y)"); return nullptr; }
+  flx_trace_params p;
+  if (!read_trace_params(env, argv[4], "rayImage", &p)) return nullptr;
+  bool hdr = true;
+  if (napi_get_value_bool(env, argv[5], &hdr) != napi_ok) { napi_throw_type_error(env, nullptr, "rayImage: hdr is a boolean"); return nullptr; }
+  void *image = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, (len / 8) * 16, &image, &buf));
+  flx_status rc = flx_rays_image(ctx, &p, hdr ? 1 : 0, (const float *)rays, width, height, (float *)image);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_rays_image", rc);
   return buf;
 }
 
@@ -1234,7 +1265,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "rayImage", RayImage }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas }, { "uploadTextures", UploadTextures }, { "updateTexture", UpdateTexture },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
