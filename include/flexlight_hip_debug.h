@@ -326,7 +326,8 @@ flx_status flx_debug_last_query(flx_context *ctx, uint32_t out[8]);
  * A RADIANCE ROW is 32 bytes, two 16-byte vector stores: words 0..2 float r, g, b; 3 float 1.0 for a hit, 0.0 for a miss (the frame's alpha); 4 float s of the
  * first hit; 5 int32 its entry, -1 for none; 6 int32 2 x its transform; 7 uint32 the bounce iterations shaded over all samples (the oracle's `shades` for this
  * ray).  A MISS ROW IS ALL ZEROS with -1 in word 5: as in a frame, where a pixel with no primary hit is (0, 0, 0, 0) — not the ambient light.
- * A ray batch has no width, height or camera, hence the params of its own.  Temporal accumulation is image-space over a history and has no meaning for a batch.
+ * A ray batch has no width, height or camera, hence the params of its own.  Temporal accumulation is image-space over a history: a loose batch has none, a ray
+ * IMAGE traced again frame after frame has (flx_rays_image_temporal_device, below).
  * The FILTER's bookkeeping does carry over: the denoise chain reads nothing of a camera, and its five render targets are per ray (flx_rays_planes_device, below;
  * flx_rays_image_device traces a ray IMAGE and runs the chain over it).  This call is the unfiltered radiance.
  * Ordering, producer_stream, the frame server, lights and transforms uploaded over a running launch, the staging of the host variant and n == 0 are
@@ -372,7 +373,8 @@ flx_status flx_debug_last_trace(flx_context *ctx, uint32_t out[8]);
  * flx_rays_image_device: the rays in image order, row 0 on top, n = width * height; the planes go to memory the context owns (grown, never shrunk), the chain follows
  * exactly as flx_filter_planes_device launches it (the reference's frame-0 texture state; it reads width, height and hdr only) and writes float4[height][width].
  * With a camera's rays the image is flx_render's with use_filter = 1, bit for bit wherever rayTracer and a frame's primary walk agree on the first hit.
- * TEMPORAL ACCUMULATION OF RAY IMAGES IS OUT OF SCOPE: a group of rays has no history to be matched against.
+ * TEMPORAL ACCUMULATION OF RAY IMAGES IS OUT OF SCOPE OF THESE CALLS, which keep nothing from one image to the next (and a loose batch of rays has no history to be
+ * matched against).  A ray IMAGE traced again frame after frame has one: flx_rays_image_temporal[_device] (below) accumulates it over time.
  * Ordering, producer_stream, the frame server, lights and transforms uploaded over a running launch, the staging of the host variants (they wait and copy out) and
  * n == 0 (FLX_OK, nothing enqueued, the scene and the params looked at first) are flx_rays_trace_device's and flx_rays_trace's, word for word.  The batch is cut
  * into slabs of at most 2^21 rays; the scratch is the traced batches' hit rows alone, 32 bytes a ray.  (Where scratch, planes or staging must grow, the host waits
@@ -391,6 +393,49 @@ flx_status flx_rays_image(flx_context *ctx, const flx_trace_params *params, int 
  * bounce walks went in lockstep, [4] n, [5] samples, [6] workgroups of the last slab's first-hit launch, [7] the rays a wave draws with one atomic.  It waits for
  * nothing. */
 flx_status flx_debug_last_ray_planes(flx_context *ctx, uint32_t out[8]);
+/* RAY IMAGES OVER TIME: temporal accumulation (config.temporal of the reference, on by default there) for a ray image — the same width * height rays in the same
+ * order, traced again frame after frame — as flx_render with is_temporal = 1 accumulates the frames behind the pinhole camera.  The reference's temporal pass is
+ * strictly per pixel and reads nothing of a camera; the id it matches on, renderLocationId (fragment:640-642), is defined for any ray.
+ * The context keeps FLX_RAY_HISTORIES histories, named by `history`.  A history holds four rings of N RGBA8 planes of width * height texels: colour, colour integer
+ * part, location id, original id.  N = temporal_samples by flx_frame_params' rule (<= 0 -> 4, > 16 -> 16).
+ * One call: ray rows, flx_trace_params and the image order (row 0 on top) are flx_rays_image's.  The caller passes random_seed; the reference passes
+ * frame % temporalSamples.  The first hit is rayTracer(origin, direction) exactly as FLX_RAYS_CLOSEST answers it.  A HIT is fragment_main with is_temporal == 1 and
+ * use_filter as given, the ray's origin where a frame has its camera, the row's two noise words where a frame has the pixel's NDC: with use_filter == 1 the five
+ * targets flx_rays_planes writes; with use_filter == 0, c = the samples' average, renderColor = (fract(c * originalColor), 1) and renderColorIp =
+ * (floor(c * originalColor) / 256, 1); and in both modes a sixth target, over the hit entry's object-space vertices a, b, c:
+ *   rel = (a * (1 - u - v) + b * u) + c * v;  div = 2 * distance(rel, origin);  renderLocationId = (mod(rel, div) / div, 1/255)
+ * A MISS WRITES ZEROS in all six.  The call rotates the ring (the oldest slot becomes the head), stores the new frame's four texels at the head and runs the
+ * reference's temporal pass on the texel of the ray's own index in every slot: the slots whose location id equals the new frame's add their colour, those whose
+ * original id equals it add their glass filter (slots visited in groups of four, vec4(0) standing in for slots at or beyond N, which an all-zero id matches too,
+ * as in the shader).  Without the filter the averaged canvas colour is the output, tone-mapped where hdr == 1.  With it the pass' five RGBA8 targets feed the
+ * denoise chain exactly as flx_filter_planes_device starts it (frame-0 texture state; it reads width, height and hdr only).  With a camera's rays, seed f % N,
+ * the sequence is flx_render's temporal sequence after flx_temporal_reset, bit for bit wherever rayTracer and a frame's primary walk agree on the first hit.
+ * The whole job runs in the planes kernel, in the lane that owns the ray (csrc/flx_rays_planes.hip): no float G-buffer, no second pass over the image.
+ * A history is keyed by (width, height, N): a call with another key starts that history afresh — zero planes, head 0 —, as a resize does for frames;
+ * flx_rays_history_reset does the same on demand (history -1: all of them) and releases the rings' memory; it waits for the context's stream.  The rings are
+ * allocated on first use and freed with the context.  The frames' own history (flx_temporal_reset) and these never touch each other.  There is no reprojection
+ * under motion, as the reference has none: a ray whose location id changes starts over.
+ * Ordering, producer_stream, the frame server and the staging of the host variant are flx_rays_image_device's and flx_rays_image's, word for word; calls on one
+ * history are ordered by the context's stream.  (Where a history is (re)allocated the host waits for the stream first.)
+ * Refusals, each with a message of its own, nothing enqueued AND THE HISTORY EXACTLY WHAT IT WAS, neither rotated nor re-keyed: flx_rays_image's for the scene, the
+ * params, the size and the arrays; temporal NULL; history outside 0 .. FLX_RAY_HISTORIES - 1; use_filter or hdr not 0 or 1; flx_rays_history_reset with history
+ * below -1 or above 7.  A group has no such call, as it traces no rays. */
+#define FLX_RAY_HISTORIES 8
+typedef struct flx_ray_temporal {
+  int32_t history;           /* 0 .. FLX_RAY_HISTORIES - 1: which of the context's ray-image histories */
+  int32_t temporal_samples;  /* depth N, by flx_frame_params' rule: <= 0 -> 4, > 16 -> 16 */
+  int32_t use_filter;        /* 0: the temporal pass' canvas colour; 1: the denoise chain follows it */
+  int32_t hdr;
+} flx_ray_temporal;
+flx_status flx_rays_image_temporal_device(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal,
+                                          const void *d_rays /* width * height * 8 floats, on ctx's device */, uint32_t width, uint32_t height,
+                                          void *d_out_rgba /* float4[height][width] */, void *producer_stream);
+flx_status flx_rays_image_temporal(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal, const float *rays, uint32_t width, uint32_t height,
+                                   float *out_rgba);      /* host arrays */
+flx_status flx_rays_history_reset(flx_context *ctx, int history /* -1: all of them */);
+/* The last temporal ray image (zeros if none): out[0] its slabs, [1] the rays of a full slab, [2] N, [3] the history, [4] n, [5] samples, [6] the ring's head after
+ * the call, [7] 1 if the temporal pass ran inside the planes kernel.  It waits for nothing. */
+flx_status flx_debug_last_ray_temporal(flx_context *ctx, uint32_t out[8]);
 /* SURFACE ROWS: what the surface is where a ray first hits — the question between "where does it hit" (flx_rays_cast) and "what radiance comes back"
  * (flx_rays_trace, flx_render).  The planes (AOVs) a denoiser of the caller's own, compositing or the shading of a hybrid renderer needs beside the noisy radiance:
  * position, geometric normal, shading normal, texture coordinates, and albedo, RME and TPO with the atlases applied.  They are the first thing lightTrace computes

@@ -11,10 +11,12 @@ REPEATS rounds after WARMUP [min .. max]:
   flx_filter_planes_device         the chain alone, over the planes the ray call made
   flx_render_device, use_filter 1  the frame: its per-pixel trace kernel (primary walk inside) + chain
   flx_render_planes_device         the frame's trace alone
+  with --temporal N[,N..]: flx_rays_image_temporal_device at each depth N, with the chain and without (the ring keeps wrapping: every call has a full history)
 from which the split: planes kernel = planes call - first hits.  Once, outside the timed region, the image is held against the frame bit for bit (they differ where
 the frame's hit rule and rayTracer differ, and in what the chain spreads from there).  GPU box.
 
-usage: ray_image_time.py [--out FILE] [--repeats 20]      (its output is recorded in profiles/rays_planes.txt)"""
+usage: ray_image_time.py [--out FILE] [--repeats 20] [--temporal N[,N..]] [--only NAME]      (its output is recorded in profiles/rays_planes.txt and, with
+--temporal, in profiles/rays_temporal.txt; --only: one of the two frames, by its scene's name)"""
 import os
 import sys
 import time
@@ -29,6 +31,8 @@ from flexlight_hip.scene_io import Scene
 
 out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
 REPEATS = int(sys.argv[sys.argv.index("--repeats") + 1]) if "--repeats" in sys.argv else 20
+TEMPORAL = [int(x) for x in sys.argv[sys.argv.index("--temporal") + 1].split(",")] if "--temporal" in sys.argv else []
+ONLY = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
 WARMUP = 3
 W, H = 1920, 1080
 FRAMES = (("cornell_obj", 4, 3), ("dragon", 8, 4))
@@ -65,6 +69,8 @@ d_planes = torch.empty((5, n), dtype=torch.int32, device="cuda")
 d_frame_planes = torch.empty((5, n), dtype=torch.int32, device="cuda")
 d_hits = torch.empty((n, 32), dtype=torch.uint8, device="cuda")
 for name, spp, bounces in FRAMES:
+    if ONLY and name != ONLY:
+        continue
     sc = Scene.golden(name)
     p = sc.frame_params(width=W, height=H, samples=spp, max_reflections=bounces, use_filter=1)
     t = capi.TraceParams.of_frame(p)
@@ -92,6 +98,11 @@ for name, spp, bounces in FRAMES:
              ("flx_filter_planes_device", lambda: ctx.filter_planes_device(p, d_planes.data_ptr(), d_image.data_ptr())),
              ("flx_render_device, use_filter 1", lambda: ctx.render_device(p, d_frame.data_ptr())),
              ("flx_render_planes_device", lambda: ctx.render_planes_device(p, d_frame_planes.data_ptr()))]
+    for depth in TEMPORAL:                          # (a history per depth and mode: none is re-keyed inside the timed region)
+        for use_filter in (1, 0):
+            temporal = capi.RayTemporal(history=(len(calls) - 7) % capi.RAY_HISTORIES, temporal_samples=depth, use_filter=use_filter, hdr=p.hdr)
+            calls.append(("temporal N = %d, %s" % (depth, "chain" if use_filter else "no chain"),
+                          lambda temporal=temporal: ctx.rays_image_temporal(d_rays, W, H, t, temporal, device=True, out=d_image)))
     ms = {label: [] for label, _ in calls}
     for k in range(WARMUP + REPEATS):
         for label, call in calls:
@@ -111,6 +122,7 @@ for name, spp, bounces in FRAMES:
                   first, planes - first, med["flx_filter_planes_device"]),
               "  ray image / filtered frame: %.3f;  planes kernel / the frame's trace: %.3f;  planes call / the frame's trace: %.3f" % (
                   med["flx_rays_image_device"] / med["flx_render_device, use_filter 1"], (planes - first) / med["flx_render_planes_device"], planes / med["flx_render_planes_device"]),
+            ] + ["  %s - flx_rays_image_device: %+.3f ms" % (label, med[label] - med["flx_rays_image_device"]) for label, _ in calls if label.startswith("temporal")] + [
               "  verified once outside the timed region: the planes equal the frame's on %.4f %% of the pixels, the image the filtered frame bit for bit on %.4f %%" % (
                   100.0 * same_planes.mean(), 100.0 * same.mean())]
 if out_path:

@@ -3,7 +3,7 @@
  * Trace rays of one's own through a BASELINE scene by the whole JavaScript path — FlexLight facade, scene graph, host flattening, N-API addon,
  * libflexlight_hip.so (flx_rays_trace) — and write what renderer.traceRays() returns.
  *   node tools/trace_rays.js <scene | file.flxs[.gz]> --rays rays.f32 --out rows.bin [--config-spp S --config-bounces B --samples S --bounces B --seed X
- *                            --running N --width W --height H --assets DIR --filter WxH --hdr 0|1]
+ *                            --running N --width W --height H --assets DIR --filter WxH --hdr 0|1 --temporal N --frames F --history H --chain 0|1 --reset K]
  *   <scene>: a BASELINE scene built through the scene graph (scenes/index.js), or a .flxs file replayed (sceneFile.sceneFromFlxs: a box without the assets)
  *   --config-spp, --config-bounces: the renderer's config (by default the scene's BASELINE frame); --samples, --bounces, --seed: traceRays' options
  *   rays.f32: 8 float32 per ray (origin, noise x, direction, noise y); rows.bin: radiance float32[4 n], s float32[n], entry int32[n], transform int32[n],
@@ -12,6 +12,9 @@
  *   are printed beside those of the same frames rendered alone.
  *   --filter WxH: the rays are an image of W x H in image order (row 0 on top): renderer.traceImage() traces and DENOISES it (flx_rays_image); rows.bin is then the
  *   image alone, float32[4 n].  --hdr: its tone map (by default config.hdr).
+ *   --temporal N (with --filter WxH): the image is accumulated over time (flx_rays_image_temporal) at depth N: traceImage(..., { temporal: true }) is called
+ *   --frames F times (by default 1) on history --history H (0) and rows.bin holds the F images one after the other; --chain 0: without the denoise chain;
+ *   --reset K: renderer.resetRayHistory(H) before call K.  The seeds are the renderer's own (its counter % N) unless --seed is given.
  */
 const fs = require('fs');
 const path = require('path');
@@ -56,6 +59,23 @@ const sum = a => { let s = 0; for (let i = 0; i < a.length; i++) if (a[i] === a[
     const size = /^(\d+)x(\d+)$/.exec(filter);
     if (!size) throw new Error('--filter takes WxH');
     if (opt('--hdr') !== undefined) options.hdr = Number(opt('--hdr')) !== 0;
+    if (opt('--temporal') !== undefined) {
+      options.temporal = true;
+      options.temporalSamples = Number(opt('--temporal'));
+      options.history = Number(opt('--history', 0));
+      options.filter = Number(opt('--chain', 1)) !== 0;
+      const frames = Number(opt('--frames', 1)), reset = Number(opt('--reset', -1));
+      const images = [];
+      for (let f = 0; f < frames; f++) {
+        if (f === reset) renderer.resetRayHistory(options.history);
+        const image = renderer.traceImage(rays, Number(size[1]), Number(size[2]), options);
+        images.push(Buffer.from(image.radiance.buffer, image.radiance.byteOffset, image.radiance.byteLength));
+      }
+      fs.writeFileSync(opt('--out', 'rows.bin'), Buffer.concat(images));
+      console.log(JSON.stringify({ rays: rays.length / 8, width: Number(size[1]), height: Number(size[2]), frames, temporal: options.temporalSamples, history: options.history, chain: options.filter, params: renderer.traceParams(options), hdr: options.hdr === undefined ? !!engine.config.hdr : options.hdr, renderer: renderer.type }));
+      renderer.halt();
+      return;
+    }
     const image = renderer.traceImage(rays, Number(size[1]), Number(size[2]), options);
     fs.writeFileSync(opt('--out', 'rows.bin'), Buffer.from(image.radiance.buffer, image.radiance.byteOffset, image.radiance.byteLength));
     console.log(JSON.stringify({ rays: rays.length / 8, width: image.width, height: image.height, params: renderer.traceParams(options), hdr: options.hdr === undefined ? !!engine.config.hdr : options.hdr, renderer: renderer.type }));

@@ -13,6 +13,7 @@
 #include "flexlight_hip.h"
 #include "flexlight_hip_debug.h"
 #include "flx_kernels.h"
+#include "flx_ray_temporal_args.h"
 #include "flx_server.h"
 
 struct flx_share;                                 /* flx_share.hip: this context's part in the ranks' shared frames */
@@ -279,6 +280,11 @@ struct flx_context {
    * variant's byte planes), grown and never shrunk; what the last call ran (flx_debug_last_ray_planes) */
   DeviceBuffer<uint32_t> d_ray_planes;
   struct RayPlanesLaunch { uint32_t slabs = 0, slab = 0, groups = 0, lock = 0, n = 0, samples = 0, query_groups = 0; } last_ray_planes;
+  /* ray images over time (flx_rays_image_temporal[_device]): FLX_RAY_HISTORIES histories, each four rings (colour, colour ip, location id, original id: d_ring's)
+   * of at.n RGBA8 planes of at.width * at.height texels back to back in one allocation, slot s of ring j at texel (j * at.n + s) * width * height, the newest at slot
+   * at.head; allocated on first use, released by flx_rays_history_reset.  at.n == 0: no history.  The frames' ring above and these never touch each other.  What the last call ran (flx_debug_last_ray_temporal) */
+  struct RayHistory { DeviceBuffer<uint32_t> rings; flx_ray_history_state at = { 0u, 0u, 0, 0 }; } ray_history[FLX_RAY_TEMPORAL_HISTORIES];
+  struct RayTemporalLaunch { uint32_t slabs = 0, slab = 0, depth = 0, history = 0, n = 0, samples = 0, head = 0, fused = 0; } last_ray_temporal;
   /* uploads: pinned staging ring */
   PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};

@@ -15,12 +15,12 @@
 #include <type_traits>
 #include "flx_kernels.h"
 #include "flx_kernel_util.h"
+#include "flx_texel.h"      /* F4, unorm8, unpack, rawW, pack; temporal_texel */
 
 namespace flx {
 
 struct Tex { const uint32_t *p; };       /* RGBA8 plane, rows top-down; null = never written (reads 0) */
 
-__device__ __forceinline__ f4 F4(float x, float y, float z, float w) { f4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
 __device__ __forceinline__ f4 add4(f4 a, f4 b) { return F4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ f4 scale4(f4 a, float s) { return F4(a.x * s, a.y * s, a.z * s, a.w * s); }
 __device__ __forceinline__ bool eq3(f4 a, f4 b) { return a.x == b.x && a.y == b.y && a.z == b.z; }
@@ -33,16 +33,8 @@ __device__ __forceinline__ uint32_t fetchRaw(Tex t, int W, int H, int x, int y_g
   if (!t.p || x < 0 || y_gl < 0 || x >= W || y_gl >= H) return 0u;
   return t.p[(size_t)(H - 1 - y_gl) * W + x];
 }
-/* k / 255 correctly rounded without the division: RN(k * RN(1/255)) and one residual correction (exact for all 256 bytes) */
-__device__ __forceinline__ float unorm8(uint32_t k) {
-  const float r = 1.0f / 255.0f, kf = (float)k;
-  const float q = kf * r;
-  return __builtin_fmaf(__builtin_fmaf(-q, 255.0f, kf), r, q);
-}
-__device__ __forceinline__ f4 unpack(uint32_t q) { return F4(unorm8(q & 255u), unorm8((q >> 8) & 255u), unorm8((q >> 16) & 255u), unorm8(q >> 24)); }
 __device__ __forceinline__ f4 fetch(Tex t, int W, int H, int x, int y_gl) { return unpack(fetchRaw(t, W, H, x, y_gl)); }      /* texelFetch, zero outside */
 __device__ __forceinline__ bool rawEq3(uint32_t a, uint32_t b) { return ((a ^ b) & 0x00ffffffu) == 0u; }
-__device__ __forceinline__ uint32_t rawW(uint32_t q) { return q >> 24; }
 
 /* The second and the final filter reach at most 8 texels from the centre (stencil radius 3 x a scale that stays below 3: 1 + 2 tanh
  * and 0.7 + 2 tanh; tests/test_filter_literal_cpu.py tabulates the taps of all 256 x 256 byte pairs — FILTER_HALO
@@ -70,7 +62,6 @@ __device__ __forceinline__ uint32_t fetchTile(const uint32_t *lds, int H, TileOr
 }
 
 __device__ __forceinline__ uint32_t quant(float x) { return quant_unorm8(x); }                  /* flx_kernel_util.h */
-__device__ __forceinline__ uint32_t pack(f4 v) { return pack_rgba8(v.x, v.y, v.z, v.w); }
 
 __device__ const float STENCIL3_37[37][2] = {
                               {-3, -1}, {-3, 0}, {-3, 1},
@@ -152,50 +143,19 @@ __global__ __launch_bounds__(256) void k_temporal_frame(TemporalPass t) {
   const uint32_t qc = pack(F4(gc.x, gc.y, gc.z, gc.w)), qip = pack(F4(gip.x, gip.y, gip.z, gip.w));
   const uint32_t qid = pack(F4(gloc.x, gloc.y, gloc.z, gloc.w)), qoid = pack(F4(goid.x, goid.y, goid.z, goid.w));
   t.ring_c[0][i] = qc; t.ring_ip[0][i] = qip; t.ring_id[0][i] = qid; t.ring_oid[0][i] = qoid;
-  float counter = 1.0f, glassCounter = 1.0f;
-  const f4 cc = unpack(qc), ci = unpack(qip);
-  const float centerW = cc.w;
-  float color[3] = { cc.x + ci.x * 256.0f, cc.y + ci.y * 256.0f, cc.z + ci.z * 256.0f };
-  float glassFilter = ci.w;
-  for (int k = 1; k < t.n; k += 4) {
-    uint32_t cs[4], ips[4], ids[4], oids[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      if (k + j < t.n) { cs[j] = t.ring_c[k + j][i]; ips[j] = t.ring_ip[k + j][i]; ids[j] = t.ring_id[k + j][i]; oids[j] = t.ring_oid[k + j][i]; }
-      else cs[j] = ips[j] = ids[j] = oids[j] = 0u;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++) if (ids[j] == qid) {
-      const f4 c = unpack(cs[j]), p = unpack(ips[j]);
-      color[0] += c.x + p.x * 256.0f; color[1] += c.y + p.y * 256.0f; color[2] += c.z + p.z * 256.0f;
-      counter += 1.0f;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++) if (oids[j] == qoid) {
-      glassFilter += unorm8(rawW(ips[j]));
-      glassCounter += 1.0f;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 3; k++) color[k] /= counter;
-  glassFilter /= glassCounter;
+  f3 color; float glassFilter, centerW;
+  temporal_texel(qc, qip, qid, qoid, t.n, [&](int k, uint32_t &c, uint32_t &ip, uint32_t &id, uint32_t &oid) {
+    c = t.ring_c[k][i]; ip = t.ring_ip[k][i]; id = t.ring_id[k][i]; oid = t.ring_oid[k][i];
+  }, color, glassFilter, centerW);
   if (t.dColor) {
     const float4 go = t.original_color[i], gid = t.id[i];
-    t.dColor[i] = pack(F4(flx_mod(color[0], 1.0f), flx_mod(color[1], 1.0f), flx_mod(color[2], 1.0f), centerW));
-    t.dIp[i] = pack(F4(flx_floor(color[0]) / 256.0f, flx_floor(color[1]) / 256.0f, flx_floor(color[2]) / 256.0f, glassFilter));
+    t.dColor[i] = temporal_color_texel(color, centerW);
+    t.dIp[i] = temporal_ip_texel(color, glassFilter);
     t.dOColor[i] = pack(F4(go.x, go.y, go.z, go.w));
     t.dId[i] = pack(F4(gid.x, gid.y, gid.z, gid.w));
     t.dOId[i] = qoid;
   } else {
-    if (t.hdr == 1) {
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        color[k] = color[k] / (color[k] + 1.0f);
-        const float gamma = 0.8f;
-        color[k] = flx_pow(4.0f * color[k], 1.0f / gamma) / 4.0f * 1.3f;
-      }
-    }
-    t.out[i] = make_float4(color[0], color[1], color[2], centerW);
+    t.out[i] = temporal_canvas(color, centerW, t.hdr);
   }
 }
 

@@ -21,9 +21,13 @@
  * (flx_trace_slab_rays at one slot a ray); the scratch is hit rows only.  The host waits for nothing — but where the scratch must grow, for the work that may
  * still use it.
  *
- * A ray image is those planes (RGBA8) into memory the context owns, then the chain exactly as flx_filter_planes_device launches it. */
+ * A ray image is those planes (RGBA8) into memory the context owns, then the chain exactly as flx_filter_planes_device launches it.
+ *
+ * A ray image OVER TIME (flx_rays_image_temporal[_device], "ray images over time") is the same launches with the kernel's temporal instantiations, which run the
+ * reference's temporal pass over one of the context's ray-image histories in the lane that owns the ray, then the chain where use_filter == 1. */
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 /* as flx_kernels.hip, whose k_trace_pixels this kernel restates: it shades inline between walks, where the table form of the sin / cos polynomial measures faster
  * (the same floats; here 16.50 against 16.69 ms on the dragon's 1080p rays), and reads the shading's per-triangle table (flx_device.h: one definition per
@@ -34,6 +38,8 @@
 #include "flx_kernel_util.h"
 #include "flx_query_args.h"
 #include "flx_ray_planes_args.h"
+#include "flx_ray_temporal_args.h"
+#include "flx_texel.h"
 
 using namespace flx;
 
@@ -43,12 +49,26 @@ constexpr uint32_t RAY_PLANES_BLOCK = 64u;             /* consecutive rays a wav
 constexpr uint32_t RAY_PLANES_WAVES = 4;               /* waves per SIMD both builds are allocated for: 128 registers + 296 B of scratch a lane (profiles/rays_planes.txt) */
 
 struct RayPlanesArgs { DeviceScene sc; DeviceFrame fr; };
-static_assert(sizeof(RayPlanesArgs) + 64 <= 4096, "the planes kernel's arguments fit a 4 KB kernarg segment");
+/* What the temporal instantiations are given beside the planes': the history's four rings (colour, colour integer part, location id, original id) — back to back in
+ * one allocation, each `depth` planes of `stride` texels —, pointing AT THE SLAB'S FIRST RAY as the outputs do, so that rings[(j * depth + s) * stride + r] is ring j's
+ * texel of the ray's index in the image in slot s; packed: the slot that takes the new frame | depth << 8 | hdr << 16.  (One pointer and one word: with four
+ * pointers and three words held in scalar registers across the bounces the kernel needed 4 - 16 B more scratch a lane than the planes kernel;
+ * profiles/rays_temporal.txt.)  The planes kernel proper is given nothing. */
+struct RayTemporalArgs { uint32_t *rings; uint32_t packed; };
+enum RayPlanesMode { RAY_PLANES = 0, RAY_TEMPORAL_CANVAS = 1, RAY_TEMPORAL_FILTER = 2 };
+struct RayNoArgs {};
+template <int MODE> using RayModeArgs = typename std::conditional<MODE != RAY_PLANES, RayTemporalArgs, RayNoArgs>::type;
+static_assert(sizeof(RayPlanesArgs) + sizeof(RayTemporalArgs) + 64 <= 4096, "the planes kernel's arguments fit a 4 KB kernarg segment");
 
-/* m: rays of the slab (rays, hits and both outputs point at its first); stride: rows of a plane, the call's n */
-template <bool LOCK>
+/* m: rays of the slab (rays, hits and both outputs point at its first); stride: rows of a plane, the call's n.
+ * MODE RAY_TEMPORAL_CANVAS / RAY_TEMPORAL_FILTER (flx_rays_image_temporal_device): fragment_main with is_temporal == 1 and use_filter 0 / 1 (fr.use_filter says the same to bounce()), then the temporal pass of k_temporal_frame
+ * (flx_filter.hip) IN THE LANE THAT OWNS THE RAY: it packs its six rows, stores the four texels of the ring's head, reads its own index in the older slots and
+ * averages (temporal_texel, flx_texel.h: the pass works on unpack(pack(x)) of the new frame's values).  With the filter the five RGBA8 inputs of the chain go to
+ * planes8 as the planes kernel lays them out; without it the canvas colour goes to planes32[r], one float4 a ray.  No float G-buffer, no second pass. */
+template <bool LOCK, int MODE>
 __global__ __launch_bounds__(256, RAY_PLANES_WAVES) void k_rays_planes(RayPlanesArgs ra, const float4 *__restrict__ rays, const float4 *__restrict__ hits, uint32_t *__restrict__ planes8,
-                                                                      float4 *__restrict__ planes32, uint32_t *__restrict__ queue, uint32_t m, size_t stride) {
+                                                                      float4 *__restrict__ planes32, uint32_t *__restrict__ queue, uint32_t m, size_t stride, RayModeArgs<MODE> th) {
+  constexpr bool TEMPORAL = MODE != RAY_PLANES;
   const DeviceScene &sc = ra.sc;
   const DeviceFrame &fr = ra.fr;
   const uint32_t lane = threadIdx.x & 63u;
@@ -64,6 +84,7 @@ __global__ __launch_bounds__(256, RAY_PLANES_WAVES) void k_rays_planes(RayPlanes
     const uint32_t r = b * RAY_PLANES_BLOCK + lane;      /* b < blocks <= 2^15: no overflow */
     if (r < m) {
       float4 color = make_float4(0.f, 0.f, 0.f, 0.f), colorIp = color, origColor = color, rid = color, roid = color;      /* a miss: an uncovered pixel, fragment_main writes nothing */
+      uint32_t qc = 0u, qip = 0u, qo = 0u, qrid = 0u, qoid = 0u, qid = 0u;      /* the temporal instantiation's six rows as stored, renderLocationId the sixth */
       const float4 h0 = hits[(size_t)r * 2u];
       Hit hit0;
       hit0.suv = F3(h0.x, h0.y, h0.z);
@@ -107,11 +128,60 @@ __global__ __launch_bounds__(256, RAY_PLANES_WAVES) void k_rays_planes(RayPlanes
         /* fragment:614-646, the filter branch */
         const float invSamples = 1.0f / (float)fr.samples;
         finalColor = finalColor * invSamples;
+        float ipW = ps.glassFilter;
+        if constexpr (TEMPORAL) {
+          if (MODE == RAY_TEMPORAL_CANVAS) { finalColor = finalColor * ps.originalColor; ipW = 1.0f; }      /* fragment:632-636, is_temporal == 1 */
+        }
         color = make_float4(flx_fract(finalColor.x), flx_fract(finalColor.y), flx_fract(finalColor.z), 1.0f);
-        colorIp = make_float4(flx_floor(finalColor.x) * INV_256, flx_floor(finalColor.y) * INV_256, flx_floor(finalColor.z) * INV_256, ps.glassFilter);
+        colorIp = make_float4(flx_floor(finalColor.x) * INV_256, flx_floor(finalColor.y) * INV_256, flx_floor(finalColor.z) * INV_256, ipW);
         origColor = make_float4(ps.originalColor.x, ps.originalColor.y, ps.originalColor.z, flx_min(ps.originalRMEx, ps.firstRayLength) + INV_255);
         rid = make_float4(ps.renderId.x, ps.renderId.y, ps.renderId.z, ps.renderId.w + INV_255);
         roid = make_float4(0.0f, 0.0f, 0.0f, ps.originalTPOx + INV_255);
+        if constexpr (TEMPORAL) {
+          qc = pack_rgba8(color.x, color.y, color.z, color.w); qip = pack_rgba8(colorIp.x, colorIp.y, colorIp.z, colorIp.w);
+          qo = pack_rgba8(origColor.x, origColor.y, origColor.z, origColor.w); qrid = pack_rgba8(rid.x, rid.y, rid.z, rid.w); qoid = pack_rgba8(roid.x, roid.y, roid.z, roid.w);
+          /* fragment:640-642 as k_trace_pixels writes it: relativePosition in object space, the origin in world space */
+          /* the hit row is fetched again, through an index the compiler cannot see through: kept from the first fetch, u, v and the entry would hold three registers
+           * through the last sample's bounces, where the kernel has none to spare (the planes kernel lets them go after that sample's first bounce) */
+          uint32_t again = r;
+          asm volatile("" : "+v"(again));
+          const float4 h1 = hits[(size_t)again * 2u];
+          const int entry = __float_as_int(h1.w);
+          const float4 g0 = sc.geometry[3 * entry], g1 = sc.geometry[3 * entry + 1], g2 = sc.geometry[3 * entry + 2];
+          const float w0 = 1.0f - h1.y - h1.z;
+          const f3 rel = (F3(g0.x, g0.y, g0.z) * w0 + F3(g0.w, g1.x, g1.y) * h1.y) + F3(g1.z, g1.w, g2.x) * h1.z;
+          const float div = 2.0f * distance(rel, origin);
+          qid = pack_rgba8(flx_mod(rel.x, div) / div, flx_mod(rel.y, div) / div, flx_mod(rel.z, div) / div, INV_255);
+        }
+      }
+      if constexpr (TEMPORAL) {
+        const uint32_t th_head = th.packed & 255u, th_depth = (th.packed >> 8) & 255u;
+        const int th_hdr = (int)(th.packed >> 16);
+        const size_t ringT = (size_t)th_depth * stride;      /* texels of a ring */
+        uint32_t *const ring_0 = th.rings, *const ring_1 = ring_0 + ringT, *const ring_2 = ring_1 + ringT, *const ring_3 = ring_2 + ringT;
+        const size_t head = (size_t)th_head * stride + r;
+        ring_0[head] = qc; ring_1[head] = qip; ring_2[head] = qid; ring_3[head] = qoid;
+        if (MODE == RAY_TEMPORAL_FILTER) {     /* the three targets the pass hands on as they are */
+          uint32_t *o = planes8 + r;
+          o[2u * stride] = qo;
+          o[3u * stride] = qrid;
+          o[4u * stride] = qoid;
+        }
+        f3 avg; float glassFilter, centerW;
+        temporal_texel(qc, qip, qid, qoid, (int)th_depth, [&](int k, uint32_t &c, uint32_t &ip, uint32_t &id, uint32_t &oid) {
+          uint32_t slot = th_head + (uint32_t)k;             /* head, k < depth */
+          if (slot >= th_depth) slot -= th_depth;
+          const size_t at = (size_t)slot * stride + r;
+          c = ring_0[at]; ip = ring_1[at]; id = ring_2[at]; oid = ring_3[at];
+        }, avg, glassFilter, centerW);
+        if (MODE == RAY_TEMPORAL_FILTER) {
+          uint32_t *o = planes8 + r;
+          o[0] = temporal_color_texel(avg, centerW);
+          o[stride] = temporal_ip_texel(avg, glassFilter);
+        } else {
+          planes32[r] = temporal_canvas(avg, centerW, th_hdr);
+        }
+        continue;
       }
       if (planes32) {
         float4 *o = planes32 + r;
@@ -168,9 +238,10 @@ static flx_status planes_refusal(flx_context *ctx, enum flx_ray_planes_refusal w
 
 /* the frame bounce() is given: one view, the params' seed and ambient (flx_rays_trace.hip: trace_frame), and use_filter, which makes bounce() keep renderId too (the
  * rest of the filter's bookkeeping it does on every path) */
-static void planes_frame(const flx_trace_params *p, DeviceFrame &fr) {
+static void planes_frame(const flx_trace_params *p, DeviceFrame &fr, const flx_ray_temporal *temporal) {
   memset(&fr, 0, sizeof fr);
-  fr.use_filter = 1;
+  fr.use_filter = temporal ? temporal->use_filter : 1;
+  fr.is_temporal = temporal ? 1 : 0;
   fr.width = fr.height = fr.rows = fr.frame_rows = fr.frames = fr.tile_rows = fr.tile_count = 1u;
   fr.samples = p->samples; fr.max_reflections = p->max_reflections;
   fr.samples_shift = -1;
@@ -180,14 +251,36 @@ static void planes_frame(const flx_trace_params *p, DeviceFrame &fr) {
   fr.view[0].random_seed = p->random_seed;
 }
 
-/* The slabs' launches, the arguments accepted: the five planes of n > 0 rays into d_planes8 and / or d_planes32 */
+template <bool LOCK, int MODE>
+static void planes_launch(uint32_t groups, hipStream_t stream, const RayPlanesArgs &ra, const float4 *rays, const float4 *hits, uint32_t *out8, float4 *out32, uint32_t *queue, uint32_t m,
+                          size_t stride, const RayModeArgs<MODE> &th) {
+  hipLaunchKernelGGL((k_rays_planes<LOCK, MODE>), dim3(groups), dim3(256), 0, stream, ra, rays, hits, out8, out32, queue, m, stride, th);
+}
+
+/* A temporal image's history, keyed and rotated for an accepted call (everything that can refuse it is behind): a history of another size or depth starts afresh,
+ * zero planes and head 0, as a resize does for frames; then the oldest slot becomes the head.  width * height = the call's n. */
+static flx_status history_advance(flx_context *ctx, flx_context::RayHistory &h, uint32_t width, uint32_t height, int depth) {
+  if (!flx_ray_history_continues(&h.at, width, height, depth)) {
+    const size_t texels = (size_t)flx_ray_history_texels(width, height, depth);
+    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));          /* (an earlier image may still use the rings that are about to go) */
+    h.at.n = 0;                                               /* (re)allocation in progress: a failure below leaves no key to match */
+    flx_status s;
+    if ((s = h.rings.release(ctx)) || (s = h.rings.ensure(ctx, texels))) return s;
+    FLX_HIP(ctx, hipMemsetAsync(h.rings, 0, texels * sizeof(uint32_t), ctx->stream));
+  }
+  h.at = flx_ray_history_advance(h.at, width, height, depth);
+  return FLX_OK;
+}
+
+/* The slabs' launches, the arguments accepted: the five planes of n > 0 rays into d_planes8 and / or d_planes32.  With `temporal` (and the image's width): the
+ * temporal instantiation over that history, the chain's five inputs into d_planes8 (use_filter == 1) or the canvas colours into d_planes32, float4[n] */
 static flx_status planes_enqueue(flx_context *ctx, const flx_trace_params *params, const void *d_rays, uint32_t n, void *d_planes8, void *d_planes32, void *producer_stream,
-                                 const char *call) {
+                                 const char *call, const flx_ray_temporal *temporal = nullptr, uint32_t width = 0u) {
   flx_status s;
   RayPlanesArgs ra;
   if ((s = flx_make_scene(ctx, ra.sc))) return s;           /* (refuses a scene that names a transform not uploaded) */
   if ((s = flx_server_stop(ctx))) return s;                 /* as flx_render_device: the frame server's launch ends after the frames posted to it */
-  planes_frame(params, ra.fr);
+  planes_frame(params, ra.fr, temporal);
   const uint32_t slab = flx_trace_slab_rays(1u, ctx->trace_slab);
   const uint32_t most = n < slab ? n : slab;                /* rays of the largest slab */
   if (!ctx->d_trace_hits.fits((size_t)most * 2u) || !ctx->d_trace_ctl) {
@@ -204,6 +297,11 @@ static flx_status planes_enqueue(flx_context *ctx, const flx_trace_params *param
   const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
   flx_context::RayPlanesLaunch ran;
   ran.n = n; ran.samples = (uint32_t)params->samples; ran.slab = slab; ran.lock = lock ? 1u : 0u;
+  flx_context::RayHistory *history = nullptr;
+  if (temporal) {
+    history = &ctx->ray_history[temporal->history];
+    if ((s = history_advance(ctx, *history, width, n / width, flx_ray_temporal_depth(temporal->temporal_samples)))) return s;
+  }
   for (uint64_t first = 0; first < n; first += slab) {
     const uint32_t m = (uint32_t)(n - first < slab ? n - first : slab);
     const float4 *rays = (const float4 *)d_rays + first * 2u;
@@ -219,10 +317,30 @@ static flx_status planes_enqueue(flx_context *ctx, const flx_trace_params *param
     const uint32_t full = (((m + RAY_PLANES_BLOCK - 1u) / RAY_PLANES_BLOCK) + 3u) / 4u;
     const uint32_t groups = ctx->query_groups ? ctx->query_groups : (full < cus * 8u ? full : cus * 8u);
     uint32_t *queue = ctx->d_trace_ctl.get() + 2;
-    if (lock) hipLaunchKernelGGL(k_rays_planes<true>, dim3(groups), dim3(256), 0, ctx->stream, ra, rays, (const float4 *)ctx->d_trace_hits.get(), out8, out32, queue, m, (size_t)n);
-    else hipLaunchKernelGGL(k_rays_planes<false>, dim3(groups), dim3(256), 0, ctx->stream, ra, rays, (const float4 *)ctx->d_trace_hits.get(), out8, out32, queue, m, (size_t)n);
+    const float4 *hits = ctx->d_trace_hits.get();
+    if (history) {
+      RayTemporalArgs th;
+      th.rings = history->rings.get() + first;              /* the ray's index in the IMAGE: first + its index in the slab */
+      th.packed = (uint32_t)history->at.head | ((uint32_t)history->at.n << 8) | ((uint32_t)temporal->hdr << 16);
+      if (temporal->use_filter == 1) {
+        if (lock) planes_launch<true, RAY_TEMPORAL_FILTER>(groups, ctx->stream, ra, rays, hits, out8, out32, queue, m, (size_t)n, th);
+        else planes_launch<false, RAY_TEMPORAL_FILTER>(groups, ctx->stream, ra, rays, hits, out8, out32, queue, m, (size_t)n, th);
+      } else {
+        if (lock) planes_launch<true, RAY_TEMPORAL_CANVAS>(groups, ctx->stream, ra, rays, hits, out8, out32, queue, m, (size_t)n, th);
+        else planes_launch<false, RAY_TEMPORAL_CANVAS>(groups, ctx->stream, ra, rays, hits, out8, out32, queue, m, (size_t)n, th);
+      }
+    } else {
+      if (lock) planes_launch<true, RAY_PLANES>(groups, ctx->stream, ra, rays, hits, out8, out32, queue, m, (size_t)n, RayNoArgs());
+      else planes_launch<false, RAY_PLANES>(groups, ctx->stream, ra, rays, hits, out8, out32, queue, m, (size_t)n, RayNoArgs());
+    }
     FLX_HIP(ctx, hipGetLastError());
     ran.slabs++; ran.groups = groups; ran.query_groups = q.groups;
+  }
+  if (history) {
+    flx_context::RayTemporalLaunch &t = ctx->last_ray_temporal;
+    t.slabs = ran.slabs; t.slab = slab; t.depth = (uint32_t)history->at.n; t.history = (uint32_t)temporal->history; t.n = n; t.samples = ran.samples;
+    t.head = (uint32_t)history->at.head; t.fused = 1u;      /* the temporal pass ran inside the planes kernel */
+    return FLX_OK;
   }
   ctx->last_ray_planes = ran;
   return FLX_OK;
@@ -317,6 +435,100 @@ extern "C" flx_status flx_rays_image(flx_context *ctx, const flx_trace_params *p
   if ((s = flx_rays_image_device(ctx, params, hdr, ctx->d_query_rays, width, height, ctx->d_query_hits, nullptr))) return s;
   FLX_HIP(ctx, hipMemcpyAsync(out_rgba, ctx->d_query_hits, (size_t)n * FLX_RAY_PLANES_ROW32, hipMemcpyDeviceToHost, ctx->stream));
   FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return FLX_OK;
+}
+
+/* a refusal of flx_ray_temporal_args.h in words */
+static flx_status temporal_refusal(flx_context *ctx, enum flx_ray_temporal_refusal why, const char *call) {
+  const char *what = "";
+  switch (why) {
+    case FLX_RAY_TEMPORAL_ARGS_OK: return FLX_OK;
+    case FLX_RAY_TEMPORAL_NULL: what = "temporal is NULL"; break;
+    case FLX_RAY_TEMPORAL_HISTORY: what = "history is not one of 0 .. 7"; break;
+    case FLX_RAY_TEMPORAL_USE_FILTER: what = "use_filter is neither 0 nor 1"; break;
+    case FLX_RAY_TEMPORAL_HDR: what = "hdr is neither 0 nor 1"; break;
+    case FLX_RAY_TEMPORAL_RESET: what = "history is not one of -1 .. 7"; break;
+  }
+  return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": " + what);
+}
+static_assert(FLX_RAY_HISTORIES == FLX_RAY_TEMPORAL_HISTORIES, "the header's histories are the context's");
+
+extern "C" flx_status flx_rays_image_temporal_device(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal, const void *d_rays, uint32_t width,
+                                                     uint32_t height, void *d_out_rgba, void *producer_stream) {
+  static const char *const call = "flx_rays_image_temporal_device";
+  if (!ctx) return FLX_ERR_INVALID;
+  flx_status s = planes_refused(ctx, params, call);
+  if (s) return s;
+  uint32_t n = 0;
+  if ((s = planes_refusal(ctx, flx_ray_image_size_check(width, height, &n), call))) return s;
+  if ((s = temporal_refusal(ctx, flx_ray_temporal_check(temporal != nullptr, temporal ? temporal->history : 0, temporal ? temporal->use_filter : 0, temporal ? temporal->hdr : 0), call)))
+    return s;
+  const enum flx_ray_planes_refusal arrays = flx_ray_image_arrays_check((uint64_t)(uintptr_t)d_rays, (uint64_t)(uintptr_t)d_out_rgba, n);
+  if (arrays != FLX_RAY_PLANES_ARGS_OK && arrays != FLX_RAY_PLANES_OVERLAP_RAYS) return planes_refusal(ctx, arrays, call);
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  if (!flx_rows_on_device(ctx, d_rays, (size_t)n * FLX_RAY_PLANES_RAY_BYTES))
+    return fail(ctx, FLX_ERR_INVALID, "flx_rays_image_temporal_device: the rays are not width * height rows in memory of the context's device, 16-byte aligned");
+  if (!flx_rows_on_device(ctx, d_out_rgba, (size_t)n * FLX_RAY_PLANES_ROW32))
+    return fail(ctx, FLX_ERR_INVALID, "flx_rays_image_temporal_device: the image is not width * height float4 in memory of the context's device, 16-byte aligned");
+  if (arrays == FLX_RAY_PLANES_OVERLAP_RAYS) return planes_refusal(ctx, arrays, call);
+  if (temporal->use_filter != 1)      /* the canvas colour of the temporal pass, straight from the kernel */
+    return planes_enqueue(ctx, params, d_rays, n, nullptr, d_out_rgba, producer_stream, call, temporal, width);
+  const size_t rows = (size_t)n * FLX_RAY_PLANES;
+  if (!ctx->d_ray_planes.fits(rows)) {
+    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier image's chain may still read the planes that are about to go) */
+    if ((s = ctx->d_ray_planes.ensure(ctx, rows))) return s;
+  }
+  if ((s = planes_enqueue(ctx, params, d_rays, n, ctx->d_ray_planes.get(), nullptr, producer_stream, call, temporal, width))) return s;
+  /* dColor, dIp, dOColor, dId and dOId feed the chain as for a ray image: frame-0 texture state, of the params width, height and hdr alone */
+  flx_frame_params image;
+  memset(&image, 0, sizeof image);
+  image.width = width; image.height = height; image.hdr = temporal->hdr;
+  return flx_filter_planes_enqueue(ctx, &image, ctx->d_ray_planes.get(), d_out_rgba, true);
+}
+
+extern "C" flx_status flx_rays_image_temporal(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal, const float *rays, uint32_t width, uint32_t height,
+                                              float *out_rgba) {
+  static const char *const call = "flx_rays_image_temporal";
+  if (!ctx) return FLX_ERR_INVALID;
+  flx_status s = planes_refused(ctx, params, call);
+  if (s) return s;
+  uint32_t n = 0;
+  if ((s = planes_refusal(ctx, flx_ray_image_size_check(width, height, &n), call))) return s;
+  if ((s = temporal_refusal(ctx, flx_ray_temporal_check(temporal != nullptr, temporal ? temporal->history : 0, temporal ? temporal->use_filter : 0, temporal ? temporal->hdr : 0), call)))
+    return s;
+  if (!rays || !out_rgba) return planes_refusal(ctx, FLX_RAY_PLANES_NULL, call);
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  if (!ctx->d_query_rays.fits((size_t)n * 2u) || !ctx->d_query_hits.fits(n)) {
+    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier call may still read or write the staging that is about to go) */
+    if ((s = ctx->d_query_rays.ensure(ctx, (size_t)n * 2u)) || (s = ctx->d_query_hits.ensure(ctx, n))) return s;
+  }
+  FLX_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, (size_t)n * FLX_RAY_PLANES_RAY_BYTES, hipMemcpyHostToDevice, ctx->stream));
+  if ((s = flx_rays_image_temporal_device(ctx, params, temporal, ctx->d_query_rays, width, height, ctx->d_query_hits, nullptr))) return s;
+  FLX_HIP(ctx, hipMemcpyAsync(out_rgba, ctx->d_query_hits, (size_t)n * FLX_RAY_PLANES_ROW32, hipMemcpyDeviceToHost, ctx->stream));
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_rays_history_reset(flx_context *ctx, int history) {
+  static const char *const call = "flx_rays_history_reset";
+  if (!ctx) return FLX_ERR_INVALID;
+  flx_status s = temporal_refusal(ctx, flx_ray_history_reset_check(history), call);
+  if (s) return s;
+  FLX_HIP(ctx, hipSetDevice(ctx->device));
+  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));          /* (an image in flight may still use the rings) */
+  for (int h = 0; h < FLX_RAY_TEMPORAL_HISTORIES; h++) {
+    if (history != -1 && history != h) continue;
+    flx_context::RayHistory &one = ctx->ray_history[h];
+    one.at = flx_ray_history_state{ 0u, 0u, 0, 0 };
+    if ((s = one.rings.release(ctx))) return s;
+  }
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_debug_last_ray_temporal(flx_context *ctx, uint32_t out[8]) {
+  if (!ctx || !out) return FLX_ERR_INVALID;
+  const flx_context::RayTemporalLaunch &t = ctx->last_ray_temporal;
+  out[0] = t.slabs; out[1] = t.slab; out[2] = t.depth; out[3] = t.history; out[4] = t.n; out[5] = t.samples; out[6] = t.head; out[7] = t.fused;
   return FLX_OK;
 }
 

@@ -38,6 +38,7 @@ EXPORTS = [
     "flx_rays_trace_device", "flx_rays_trace", "flx_debug_set_trace_slab", "flx_debug_last_trace",
     "flx_rays_surface_device", "flx_rays_surface", "flx_frame_surface_device", "flx_frame_surface", "flx_debug_last_surface",
     "flx_rays_planes_device", "flx_rays_planes", "flx_rays_image_device", "flx_rays_image", "flx_debug_last_ray_planes",
+    "flx_rays_image_temporal_device", "flx_rays_image_temporal", "flx_rays_history_reset", "flx_debug_last_ray_temporal",
     "flx_textures_upload", "flx_textures_upload_device", "flx_texture_update", "flx_texture_update_device", "flx_group_textures_upload", "flx_group_texture_update",
     "flx_debug_atlas_read",
 ]
@@ -77,6 +78,17 @@ class TraceParams(C.Structure):
     def of_frame(cls, params):
         """the fields a frame's FrameParams shares with it"""
         return cls(params.samples, params.max_reflections, params.min_importancy, tuple(params.ambient), params.random_seed, params.texture_width)
+
+
+RAY_HISTORIES = 8              # FLX_RAY_HISTORIES of include/flexlight_hip_debug.h: the ray-image histories a context keeps
+
+
+class RayTemporal(C.Structure):
+    """flx_ray_temporal of include/flexlight_hip_debug.h: which history a temporal ray image accumulates into, how deep, and what follows the temporal pass"""
+    _fields_ = [("history", C.c_int32), ("temporal_samples", C.c_int32), ("use_filter", C.c_int32), ("hdr", C.c_int32)]
+
+    def __init__(self, history=0, temporal_samples=4, use_filter=1, hdr=1):
+        super().__init__(int(history), int(temporal_samples), int(use_filter), int(hdr))
 
 
 class Image(C.Structure):
@@ -122,6 +134,10 @@ def _load():
         "flx_rays_image_device": (C.c_int, [vp, C.POINTER(TraceParams), C.c_int, vp, u32, u32, vp, vp]),
         "flx_rays_image": (C.c_int, [vp, C.POINTER(TraceParams), C.c_int, fp, u32, u32, fp]),
         "flx_debug_last_ray_planes": (C.c_int, [vp, C.POINTER(u32)]),
+        "flx_rays_image_temporal_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(RayTemporal), vp, u32, u32, vp, vp]),
+        "flx_rays_image_temporal": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(RayTemporal), fp, u32, u32, fp]),
+        "flx_rays_history_reset": (C.c_int, [vp, C.c_int]),
+        "flx_debug_last_ray_temporal": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_textures_upload": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32]),
         "flx_textures_upload_device": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32, vp]),
         "flx_texture_update": (C.c_int, [vp, C.c_int, u32, C.POINTER(Image)]),
@@ -788,6 +804,49 @@ class Context:
         out = (C.c_uint32 * 8)()
         self._check(LIB.flx_debug_last_ray_planes(self._h, out), "flx_debug_last_ray_planes")
         return dict(zip(("slabs", "slab", "groups", "lockstep", "n", "samples", "query_groups", "block"), list(out)))
+
+    # -- ray images over time -------------------------------------------------------------------------
+    def rays_image_temporal(self, rays, width, height, trace_params, temporal, device=False, out=None, stream=None):
+        """flx_rays_image_temporal[_device]: a ray IMAGE accumulated over the history temporal.history (RayTemporal), then denoised where temporal.use_filter is 1.
+        trace_params: TraceParams; the caller passes random_seed (the reference: frame % temporal_samples).
+        device=False: rays [width * height, 8] float32 in host memory, image order -> the image float32 [height, width, 4], complete.
+        device=True: rays as for ray_image_device; out: None (a new float32 tensor [height, width, 4]), such a tensor to write into, or an address; stream: as for
+        trace_rays_device.  Returns the image ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        if trace_params is not None and not isinstance(trace_params, TraceParams):
+            raise TypeError("rays_image_temporal: trace_params is a TraceParams")      # (None goes to the library, which refuses it)
+        if temporal is not None and not isinstance(temporal, RayTemporal):
+            raise TypeError("rays_image_temporal: temporal is a RayTemporal")
+        width, height = int(width), int(height)
+        tp = C.byref(trace_params) if trace_params is not None else None
+        tt = C.byref(temporal) if temporal is not None else None
+        if device:
+            r, n = _ray_rows(rays, self._device, "rays_image_temporal")
+            if n != width * height:
+                raise ValueError("rays_image_temporal: %d rays are no image of %d x %d" % (n, width, height))
+            if out is None:
+                import torch
+                out = torch.empty((height, width, 4), dtype=torch.float32, device="cuda:%d" % self._device)
+            o = self._device_out(out, n * 16, "rays_image_temporal", "out")
+            self._check(LIB.flx_rays_image_temporal_device(self._h, tp, tt, C.c_void_p(r), width, height, C.c_void_p(o), _stream_handle(stream)),
+                        "flx_rays_image_temporal_device")
+            return out
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        if rays.shape[0] != width * height:
+            raise ValueError("rays_image_temporal: %d rays are no image of %d x %d" % (rays.shape[0], width, height))
+        img = np.zeros((height, width, 4), np.float32)
+        self._check(LIB.flx_rays_image_temporal(self._h, tp, tt, _fp(rays), width, height, _fp(img)), "flx_rays_image_temporal")
+        return img
+
+    def rays_history_reset(self, history=-1):
+        """flx_rays_history_reset: that ray-image history (-1: all of them) starts afresh with the next image, its memory released; waits for the context's stream"""
+        self._check(LIB.flx_rays_history_reset(self._h, int(history)), "flx_rays_history_reset")
+
+    def debug_last_ray_temporal(self):
+        """flx_debug_last_ray_temporal -> dict (zeros when no temporal ray image ran): slabs, slab (rays of a full one), depth (N), history, n, samples, head (the
+        ring's, after the call), fused (1: the temporal pass ran inside the planes kernel)"""
+        out = (C.c_uint32 * 8)()
+        self._check(LIB.flx_debug_last_ray_temporal(self._h, out), "flx_debug_last_ray_temporal")
+        return dict(zip(("slabs", "slab", "depth", "history", "n", "samples", "head", "fused"), list(out)))
 
     # -- surface rows -------------------------------------------------------------------------------
     def _surface_out(self, out, n, fields, call):

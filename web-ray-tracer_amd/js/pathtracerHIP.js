@@ -159,6 +159,7 @@ class PathTracerHIP {
     if (this._ctx) {
       try { native().destroyContext(this._ctx); } catch (e) { console.warn('Unable to release the GPU context', e.message); }
       this._ctx = null;
+      this._rayHistories = {};                            // the ray-image histories went with the context
     }
     if (this._group) {
       try { native().destroyGroup(this._group); } catch (e) { console.warn('Unable to release the GPU group', e.message); }
@@ -308,8 +309,12 @@ class PathTracerHIP {
    * reflection buffer — through the renderer's own filter (flx_rays_image, include/flexlight_hip_debug.h "ray queries").  rays: traceRays' rows, width * height of
    * them in image order, row 0 on top.  options: traceRays' plus hdr (by default config.hdr), the chain's tone map.  Per ray the five filter planes are what a frame
    * with config.filter writes for a pixel (the samples run in order on one state; a miss is zeros), and the chain over them is the frame's.  Returns { width,
-   * height, radiance: Float32Array(4 n) }.  Temporal accumulation does not apply: a set of rays has no history.  It waits for the answer; frames in flight finish
-   * unchanged. */
+   * height, radiance: Float32Array(4 n) }.  It waits for the answer; frames in flight finish unchanged.
+   * OVER TIME: with options.temporal the image is accumulated over one of the context's 8 ray-image histories (flx_rays_image_temporal), as a frame is with
+   * config.temporal: options { temporal: true, history = 0, temporalSamples = config.temporalSamples, filter = true, randomSeed }.  The same width * height rays in
+   * the same order are traced again call after call; a ray whose first hit moved starts over.  The renderer keeps a frame counter per history and passes
+   * counter % N as the seed (N: temporalSamples, 4 where it is <= 0, at most 16) unless randomSeed is given; the counter restarts with resetRayHistory(history) and
+   * with a change of size or N, as the history does.  Without the filter the temporal pass' colour is returned. */
   traceImage (rays, width, height, options) {
     if (this._devices) throw new Error('traceImage: one GPU only (a group of GPUs traces no rays)');
     if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('traceImage: rays is a Float32Array of 8 floats per ray');
@@ -318,8 +323,35 @@ class PathTracerHIP {
     }
     this._uploadFrameState();
     const hdr = options && options.hdr !== undefined ? !!options.hdr : !!this.config.hdr;
+    if (options && options.temporal) {
+      const history = options.history === undefined ? 0 : options.history;
+      if (!Number.isInteger(history) || history < 0 || history > 7) throw new RangeError('traceImage: history is one of 0 .. 7');
+      const temporalSamples = options.temporalSamples === undefined ? this.config.temporalSamples : options.temporalSamples;
+      const depth = temporalSamples <= 0 ? 4 : Math.min(16, temporalSamples);      // flx_frame_params' rule
+      if (!this._rayHistories) this._rayHistories = {};
+      let h = this._rayHistories[history];
+      if (!h || h.width !== width || h.height !== height || h.depth !== depth) h = this._rayHistories[history] = { width, height, depth, counter: 0 };
+      const params = this.traceParams(options);
+      if (options.randomSeed === undefined) params.randomSeed = h.counter % depth;
+      const filter = options.filter === undefined ? true : !!options.filter;
+      const image = native().rayImageTemporal(this._context(), rays, width, height, params, { history, temporalSamples, filter, hdr });
+      h.counter++;
+      return { width, height, radiance: new Float32Array(image) };
+    }
     const image = native().rayImage(this._context(), rays, width, height, this.traceParams(options), hdr);
     return { width, height, radiance: new Float32Array(image) };
+  }
+
+  /* A ray-image history of traceImage's (by default all of them) starts afresh with the next image: its frame counter and, where a context is up, the library's
+   * history (flx_rays_history_reset). */
+  resetRayHistory (history) {
+    const which = history === undefined ? -1 : history;
+    if (!Number.isInteger(which) || which < -1 || which > 7) throw new RangeError('resetRayHistory: history is one of 0 .. 7, or -1 for all');
+    if (this._rayHistories) {
+      if (which === -1) this._rayHistories = {};
+      else delete this._rayHistories[which];
+    }
+    if (this._ctx) native().rayHistoryReset(this._ctx, which);
   }
 
   /* What the SURFACE is where rays of the application's own first hit: the inputs of a denoiser, of compositing, of a hybrid renderer's shading

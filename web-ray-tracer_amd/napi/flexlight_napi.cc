@@ -410,6 +410,61 @@ static napi_value RayImage(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+/* rayImageTemporal(handle, rays Float32Array(8 width height), width, height, params (traceRays'), { history, temporalSamples, filter, hdr }) ->
+ * ArrayBuffer(16 width height): flx_rays_image_temporal, the ray image accumulated over that history of the context's, denoised where filter is true */
+static napi_value RayImageTemporal(napi_env env, napi_callback_info info) {
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  void *rays; size_t len; uint32_t width, height;
+  if (!typed(env, argv[1], napi_float32_array, &rays, &len)) return nullptr;
+  if (napi_get_value_uint32(env, argv[2], &width) != napi_ok || napi_get_value_uint32(env, argv[3], &height) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "rayImageTemporal: width and height are numbers");
+    return nullptr;
+  }
+  if (len % 8 != 0 || (uint64_t)(len / 8) != (uint64_t)width * height) { napi_throw_range_error(env, nullptr, "rayImageTemporal: width * height rays of 8 floats (origin, noise x, direction, noise y)"); return nullptr; }
+  flx_trace_params p;
+  if (!read_trace_params(env, argv[4], "rayImageTemporal", &p)) return nullptr;
+  flx_ray_temporal t;
+  memset(&t, 0, sizeof t);
+  double d = 0;
+  auto int32 = [&](const char *key, int32_t *out) {
+    if (!num(env, argv[5], key, &d)) return false;
+    if (!(d >= -2147483648.0 && d <= 2147483647.0)) { napi_throw_range_error(env, nullptr, (std::string("rayImageTemporal: ") + key + " is not a number an int32 holds").c_str()); return false; }
+    *out = (int32_t)d;
+    return true;
+  };
+  if (!int32("history", &t.history) || !int32("temporalSamples", &t.temporal_samples)) return nullptr;
+  napi_value v;
+  bool filter = true, hdr = true;
+  if (napi_get_named_property(env, argv[5], "filter", &v) != napi_ok || napi_get_value_bool(env, v, &filter) != napi_ok ||
+      napi_get_named_property(env, argv[5], "hdr", &v) != napi_ok || napi_get_value_bool(env, v, &hdr) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "rayImageTemporal: filter and hdr are booleans");
+    return nullptr;
+  }
+  t.use_filter = filter ? 1 : 0; t.hdr = hdr ? 1 : 0;
+  void *image = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, (len / 8) * 16, &image, &buf));
+  flx_status rc = flx_rays_image_temporal(ctx, &p, &t, (const float *)rays, width, height, (float *)image);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_rays_image_temporal", rc);
+  return buf;
+}
+
+/* rayHistoryReset(handle, history): flx_rays_history_reset, -1 for all of the context's ray-image histories */
+static napi_value RayHistoryReset(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  if (!get_args(env, info, 2, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  int32_t history = -1;
+  if (napi_get_value_int32(env, argv[1], &history) != napi_ok) { napi_throw_type_error(env, nullptr, "rayHistoryReset: history is a number"); return nullptr; }
+  flx_status rc = flx_rays_history_reset(ctx, history);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_rays_history_reset", rc);
+  return nullptr;
+}
+
 /* the planes a surface call may write: popcount(fields) for fields the library takes; anything else is left to the library to refuse, with room for one plane */
 static size_t surface_planes(uint32_t fields) {
   size_t planes = 0;
@@ -1265,7 +1320,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "rayImage", RayImage }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas }, { "uploadTextures", UploadTextures }, { "updateTexture", UpdateTexture },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
