@@ -340,5 +340,14 @@ flx_status flx_check_device_error(flx_context *ctx);      /* FLX_ERR_DEVICE (and
 flx_status flx_temporal_planes_enqueue(flx_context *ctx, const flx_frame_params *params, void *d_planes);
 /* flx_filter_planes_device; stamp_start = false leaves the frame's start event alone (the trace of the same frame recorded it) */
 flx_status flx_filter_planes_enqueue(flx_context *ctx, const flx_frame_params *params, const void *d_planes, void *d_out_rgba, bool stamp_start);
+/* flx_query.hip: the host path the ray-batch calls share — cast, trace, surface, planes, images; its templates are flx_rays_host.h's.  `call`: the entry point's
+ * name, which every message begins with. */
+flx_status flx_scene_refused(flx_context *ctx, const char *call);      /* FLX_ERR_NO_SCENE where no scene and transforms are uploaded */
+flx_status flx_trace_params_refused(flx_context *ctx, const flx_trace_params *p, const char *call);      /* that, then a flx_trace_params' refusals (flx_trace_args_check) in words */
+/* the frame bounce() is given for a caller's rays: one view, the params' seed and ambient; use_filter makes bounce() keep renderId too */
+void flx_trace_frame(const flx_trace_params *p, flx::DeviceFrame &fr, int use_filter, int is_temporal);
+flx_status flx_wait_for_producer(flx_context *ctx, void *producer_stream);      /* the context's stream waits for what the caller's stream holds now (NULL: nothing to wait for) */
+/* a slab's head: d_trace_ctl's four words zeroed, the closest hits of m rays into d_trace_hits; q <- the launch */
+flx_status flx_slab_first_hits(flx_context *ctx, const flx::DeviceScene &sc, const float4 *rays, uint32_t m, const char *call, flx::QueryLaunch &q);
 
 #endif

@@ -9,13 +9,18 @@
  * of pre-transformed rays] (the last two with pre-transformed rays only).  A wave draws chunks of QUERY_CHUNK consecutive ray indices from one device cursor, one
  * atomic per chunk, and hands them to its free lanes in order: the coherence the caller gave survives.  A lane whose walk ends writes its ray's hit row and takes
  * the next ray once QUERY_BATCH lanes of its wave are free.  No fold, no record, no live list; no wait on another wave or workgroup anywhere: the one shared word
- * is the cursor, zeroed in front of every launch, and every walk ends at the validated scene's terminator. */
+ * is the cursor, zeroed in front of every launch, and every walk ends at the validated scene's terminator.
+ *
+ * Behind the kernel: the host path that every ray-batch call shares (cast here; trace, surface, planes and images in flx_rays_trace.hip, flx_surface.hip and
+ * flx_rays_planes.hip) — declared in flx_context.h, its templates in flx_rays_host.h. */
 #include <cstring>
 #include <mutex>
+#include <string>
 
 #include "flx_context.h"
 #include "flx_kernel_util.h"
 #include "flx_query_args.h"
+#include "flx_rays_host.h"
 
 using namespace flx;
 
@@ -200,49 +205,101 @@ bool launch_ray_query(const DeviceScene &sc, const float4 *rays, float4 *hits, u
 
 }  // namespace flx
 
-/* ---- the calls ------------------------------------------------------------------------------------------------------------------------------------- */
+/* ---- the host path the ray-batch calls share (flx_context.h; flx_rays_host.h) -------------------------------------------------------------------- */
 
 static flx_status fail(flx_context *ctx, flx_status code, const char *msg) { return flx_fail(ctx, code, msg); }
+static flx_status fail(flx_context *ctx, flx_status code, const std::string &msg) { return flx_fail(ctx, code, msg.c_str()); }
+
+flx_status flx_scene_refused(flx_context *ctx, const char *call) {
+  if (!ctx->have_scene || !ctx->have_transforms) return fail(ctx, FLX_ERR_NO_SCENE, std::string(call) + ": no scene and transforms uploaded");
+  return FLX_OK;
+}
+
+flx_status flx_trace_params_refused(flx_context *ctx, const flx_trace_params *p, const char *call) {
+  flx_status s = flx_scene_refused(ctx, call);
+  if (s) return s;
+  const char *what = "";
+  switch (flx_trace_args_check(p != nullptr, p ? p->samples : 0, p ? p->max_reflections : 0, p ? p->texture_width : 0, 0u, 0u, 0u)) {
+    case FLX_TRACE_ARGS_OK: return FLX_OK;
+    case FLX_TRACE_PARAMS_NULL: what = "params is NULL"; break;
+    case FLX_TRACE_SAMPLES: what = "samples is less than 1"; break;
+    case FLX_TRACE_REFLECTIONS: what = "max_reflections is negative"; break;
+    default: what = "texture_width is less than 1"; break;
+  }
+  return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": " + what);
+}
+
+void flx_trace_frame(const flx_trace_params *p, DeviceFrame &fr, int use_filter, int is_temporal) {
+  memset(&fr, 0, sizeof fr);
+  fr.use_filter = use_filter;
+  fr.is_temporal = is_temporal;
+  fr.width = fr.height = fr.rows = fr.frame_rows = fr.frames = fr.tile_rows = fr.tile_count = 1u;
+  fr.samples = p->samples; fr.max_reflections = p->max_reflections;
+  fr.samples_shift = -1;
+  fr.min_importancy = p->min_importancy;
+  fr.texture_width = (float)p->texture_width;
+  memcpy(fr.view[0].ambient, p->ambient, sizeof fr.view[0].ambient);
+  fr.view[0].random_seed = p->random_seed;
+}
+
+flx_status flx_wait_for_producer(flx_context *ctx, void *producer_stream) {
+  if (!producer_stream) return FLX_OK;
+  if (!ctx->query_produced) FLX_HIP(ctx, hipEventCreateWithFlags(&ctx->query_produced, hipEventDisableTiming));
+  FLX_HIP(ctx, hipEventRecord(ctx->query_produced, (hipStream_t)producer_stream));
+  FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->query_produced, 0));
+  return FLX_OK;
+}
+
+/* one query launch, its control words zeroed in stream order in front of it: [0] the chunk cursor, [1] the waves that drew (d_trace_ctl: [2] the cursor of the kernel
+ * that follows in a slab) */
+static flx_status query_enqueue(flx_context *ctx, const DeviceScene &sc, const float4 *rays, float4 *hits, uint32_t n, uint32_t what, uint32_t *ctl, const char *call, QueryLaunch &q) {
+  FLX_HIP(ctx, hipMemsetAsync(ctl, 0, 4 * sizeof(uint32_t), ctx->stream));
+  if (!launch_ray_query(sc, rays, hits, n, what, ctl, (uint32_t)ctx->prop.multiProcessorCount, ctx->query_groups, ctx->stream, &q))
+    return fail(ctx, FLX_ERR_DEVICE, std::string(call) + ": the query kernel cannot have its LDS on this device");
+  FLX_HIP(ctx, hipGetLastError());
+  return FLX_OK;
+}
+
+flx_status flx_slab_first_hits(flx_context *ctx, const DeviceScene &sc, const float4 *rays, uint32_t m, const char *call, QueryLaunch &q) {
+  return query_enqueue(ctx, sc, rays, ctx->d_trace_hits, m, FLX_RAYS_CLOSEST, ctx->d_trace_ctl, call, q);
+}
+
+/* ---- the calls ------------------------------------------------------------------------------------------------------------------------------------- */
 
 /* what both calls refuse before they look at an array */
 static flx_status query_refused(flx_context *ctx, uint32_t what) {
-  if (!ctx->have_scene || !ctx->have_transforms) return fail(ctx, FLX_ERR_NO_SCENE, "flx_rays_cast: no scene and transforms uploaded");
+  flx_status s = flx_scene_refused(ctx, "flx_rays_cast");
+  if (s) return s;
   if ((what & ~7u) != 0u) return fail(ctx, FLX_ERR_INVALID, "flx_rays_cast: what has a bit beyond FLX_RAYS_CLOSEST | FLX_RAYS_OCCLUDED | FLX_RAYS_COUNT");
   if ((what & 3u) == 0u) return fail(ctx, FLX_ERR_INVALID, "flx_rays_cast: what asks for neither FLX_RAYS_CLOSEST nor FLX_RAYS_OCCLUDED");
   return FLX_OK;
 }
 
 extern "C" flx_status flx_rays_cast_device(flx_context *ctx, const void *d_rays, void *d_hits, uint32_t n, uint32_t what, void *producer_stream) {
+  static const char *const call = "flx_rays_cast_device";
   if (!ctx) return FLX_ERR_INVALID;
   flx_status s = query_refused(ctx, what);
   if (s || n == 0) return s;
-  switch (flx_query_args_check((uint64_t)(uintptr_t)d_rays, (uint64_t)(uintptr_t)d_hits, n, what)) {
+  const enum flx_query_refusal arrays = flx_query_args_check((uint64_t)(uintptr_t)d_rays, (uint64_t)(uintptr_t)d_hits, n, what);
+  switch (arrays) {
     case FLX_QUERY_ARGS_OK: case FLX_QUERY_OVERLAP: break;      /* (overlap: said after the pointers are known to be the device's) */
     case FLX_QUERY_NULL: return fail(ctx, FLX_ERR_INVALID, "flx_rays_cast_device: an array is NULL");
     default: return fail(ctx, FLX_ERR_INVALID, "flx_rays_cast_device: n rows of 32 bytes leave the address space");
   }
   FLX_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = (size_t)n * FLX_QUERY_ROW_BYTES;
+  const size_t bytes = (size_t)n * FLX_RAY_ROW_BYTES;
   if (!flx_rows_on_device(ctx, d_rays, bytes))
     return fail(ctx, FLX_ERR_INVALID, "flx_rays_cast_device: the rays are not n rows in memory of the context's device, 16-byte aligned");
   if (!flx_rows_on_device(ctx, d_hits, bytes))
     return fail(ctx, FLX_ERR_INVALID, "flx_rays_cast_device: the hits are not n rows in memory of the context's device, 16-byte aligned");
-  if (flx_query_args_check((uint64_t)(uintptr_t)d_rays, (uint64_t)(uintptr_t)d_hits, n, what) == FLX_QUERY_OVERLAP)
-    return fail(ctx, FLX_ERR_INVALID, "flx_rays_cast_device: the rays and the hits overlap");
+  if (arrays == FLX_QUERY_OVERLAP) return fail(ctx, FLX_ERR_INVALID, "flx_rays_cast_device: the rays and the hits overlap");
   DeviceScene sc;
   if ((s = flx_make_scene(ctx, sc))) return s;              /* (refuses a scene that names a transform not uploaded) */
   if ((s = flx_server_stop(ctx))) return s;                 /* as flx_render_device: the frame server's launch ends after the frames posted to it */
   if ((s = ctx->d_query_ctl.ensure(ctx, 4))) return s;
-  if (producer_stream) {
-    if (!ctx->query_produced) FLX_HIP(ctx, hipEventCreateWithFlags(&ctx->query_produced, hipEventDisableTiming));
-    FLX_HIP(ctx, hipEventRecord(ctx->query_produced, (hipStream_t)producer_stream));
-    FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->query_produced, 0));
-  }
-  FLX_HIP(ctx, hipMemsetAsync(ctx->d_query_ctl, 0, 4 * sizeof(uint32_t), ctx->stream));
+  if ((s = flx_wait_for_producer(ctx, producer_stream))) return s;
   QueryLaunch ran;
-  if (!launch_ray_query(sc, (const float4 *)d_rays, (float4 *)d_hits, n, what, ctx->d_query_ctl, (uint32_t)ctx->prop.multiProcessorCount, ctx->query_groups, ctx->stream, &ran))
-    return fail(ctx, FLX_ERR_DEVICE, "flx_rays_cast_device: the query kernel cannot have its LDS on this device");
-  FLX_HIP(ctx, hipGetLastError());
+  if ((s = query_enqueue(ctx, sc, (const float4 *)d_rays, (float4 *)d_hits, n, what, ctx->d_query_ctl, call, ran))) return s;
   ctx->last_query = ran;
   return FLX_OK;
 }
@@ -252,17 +309,8 @@ extern "C" flx_status flx_rays_cast(flx_context *ctx, const float *rays, void *h
   flx_status s = query_refused(ctx, what);
   if (s || n == 0) return s;
   if (!rays || !hits) return fail(ctx, FLX_ERR_INVALID, "flx_rays_cast: an array is NULL");
-  FLX_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = (size_t)n * FLX_QUERY_ROW_BYTES;
-  if (!ctx->d_query_rays.fits((size_t)n * 2u) || !ctx->d_query_hits.fits((size_t)n * 2u)) {
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier query may still read or write the staging that is about to go) */
-    if ((s = ctx->d_query_rays.ensure(ctx, (size_t)n * 2u)) || (s = ctx->d_query_hits.ensure(ctx, (size_t)n * 2u))) return s;
-  }
-  FLX_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, bytes, hipMemcpyHostToDevice, ctx->stream));
-  if ((s = flx_rays_cast_device(ctx, ctx->d_query_rays, ctx->d_query_hits, n, what, nullptr))) return s;
-  FLX_HIP(ctx, hipMemcpyAsync(hits, ctx->d_query_hits, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return FLX_OK;
+  return flx_rays_from_host(ctx, rays, n, [&]() { return flx_rays_cast_device(ctx, ctx->d_query_rays, ctx->d_query_hits, n, what, nullptr); },
+                            flx_down(&ctx->d_query_hits, (size_t)n * 2u, hits));
 }
 
 extern "C" flx_status flx_debug_set_query_groups(flx_context *ctx, uint32_t groups) {

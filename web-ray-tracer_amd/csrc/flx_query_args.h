@@ -5,7 +5,7 @@
 
 #include <stdint.h>
 
-#define FLX_QUERY_ROW_BYTES 32u      /* a ray row and a hit row alike: 8 words */
+#include "flx_range_args.h"      /* the range arithmetic, and FLX_RAY_ROW_BYTES: a ray row and a hit row alike */
 
 enum flx_query_refusal {
   FLX_QUERY_ARGS_OK = 0,
@@ -21,9 +21,9 @@ static inline enum flx_query_refusal flx_query_args_check(uint64_t rays, uint64_
   if ((what & ~7u) != 0u) return FLX_QUERY_WHAT_UNKNOWN;
   if ((what & 3u) == 0u) return FLX_QUERY_WHAT_NONE;
   if (rays == 0u || hits == 0u) return FLX_QUERY_NULL;
-  const uint64_t bytes = (uint64_t)n * FLX_QUERY_ROW_BYTES;
-  if (rays > UINT64_MAX - bytes || hits > UINT64_MAX - bytes) return FLX_QUERY_WRAPS;
-  if (rays < hits + bytes && hits < rays + bytes) return FLX_QUERY_OVERLAP;
+  const uint64_t bytes = (uint64_t)n * FLX_RAY_ROW_BYTES;
+  if (flx_range_wraps(rays, bytes) || flx_range_wraps(hits, bytes)) return FLX_QUERY_WRAPS;
+  if (flx_ranges_overlap(rays, bytes, hits, bytes)) return FLX_QUERY_OVERLAP;
   return FLX_QUERY_ARGS_OK;
 }
 
@@ -48,9 +48,9 @@ static inline enum flx_trace_refusal flx_trace_args_check(int have_params, int32
   if (texture_width < 1) return FLX_TRACE_TEXTURE_WIDTH;
   if (n == 0u) return FLX_TRACE_ARGS_OK;
   if (rays == 0u || radiance == 0u) return FLX_TRACE_NULL;
-  const uint64_t bytes = (uint64_t)n * FLX_QUERY_ROW_BYTES;
-  if (rays > UINT64_MAX - bytes || radiance > UINT64_MAX - bytes) return FLX_TRACE_WRAPS;
-  if (rays < radiance + bytes && radiance < rays + bytes) return FLX_TRACE_OVERLAP;
+  const uint64_t bytes = (uint64_t)n * FLX_RAY_ROW_BYTES;
+  if (flx_range_wraps(rays, bytes) || flx_range_wraps(radiance, bytes)) return FLX_TRACE_WRAPS;
+  if (flx_ranges_overlap(rays, bytes, radiance, bytes)) return FLX_TRACE_OVERLAP;
   return FLX_TRACE_ARGS_OK;
 }
 

@@ -17,9 +17,10 @@
  * Measured against the alternative, on the MI355X (profiles/rays_planes.txt): a form in which a lane went on to its next sample as soon as a path ended and free
  * lanes drew new rays mid-wave once 24 (FLX_WF_BATCH) or 40 of them were free was 20 - 35 % slower than the same form finishing its rays together, and that one
  * 3 - 9 % slower than this body; 5 and 6 waves per SIMD for the build without the lockstep copy (80 - 96 registers, more scratch) lost to 4 as well.
- * bounce() is given a DeviceFrame of one view that holds the params' seed and ambient, as in flx_rays_trace.hip.  The batch is cut into slabs of at most 2^21 rays
+ * bounce() is given a DeviceFrame of one view that holds the params' seed and ambient (flx_query.hip: flx_trace_frame).  The batch is cut into slabs of at most 2^21 rays
  * (flx_trace_slab_rays at one slot a ray); the scratch is hit rows only.  The host waits for nothing — but where the scratch must grow, for the work that may
- * still use it.
+ * still use it.  The params' refusal, the growth, the producer wait, the slab loop and its first hits and the host-memory calls are the ray-batch calls' shared path
+ * (flx_query.hip, flx_rays_host.h).
  *
  * A ray image is those planes (RGBA8) into memory the context owns, then the chain exactly as flx_filter_planes_device launches it.
  *
@@ -39,6 +40,7 @@
 #include "flx_query_args.h"
 #include "flx_ray_planes_args.h"
 #include "flx_ray_temporal_args.h"
+#include "flx_rays_host.h"
 #include "flx_texel.h"
 
 using namespace flx;
@@ -206,20 +208,6 @@ __global__ __launch_bounds__(256, RAY_PLANES_WAVES) void k_rays_planes(RayPlanes
 static flx_status fail(flx_context *ctx, flx_status code, const char *msg) { return flx_fail(ctx, code, msg); }
 static flx_status fail(flx_context *ctx, flx_status code, const std::string &msg) { return flx_fail(ctx, code, msg.c_str()); }
 
-/* what every call refuses before it looks at an array: flx_rays_trace's rule for the scene and the params */
-static flx_status planes_refused(flx_context *ctx, const flx_trace_params *p, const char *call) {
-  if (!ctx->have_scene || !ctx->have_transforms) return fail(ctx, FLX_ERR_NO_SCENE, std::string(call) + ": no scene and transforms uploaded");
-  const char *what = "";
-  switch (flx_trace_args_check(p != nullptr, p ? p->samples : 0, p ? p->max_reflections : 0, p ? p->texture_width : 0, 0u, 0u, 0u)) {
-    case FLX_TRACE_ARGS_OK: return FLX_OK;
-    case FLX_TRACE_PARAMS_NULL: what = "params is NULL"; break;
-    case FLX_TRACE_SAMPLES: what = "samples is less than 1"; break;
-    case FLX_TRACE_REFLECTIONS: what = "max_reflections is negative"; break;
-    default: what = "texture_width is less than 1"; break;
-  }
-  return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": " + what);
-}
-
 /* a refusal of flx_ray_planes_args.h in words */
 static flx_status planes_refusal(flx_context *ctx, enum flx_ray_planes_refusal why, const char *call) {
   const char *what = "";
@@ -234,21 +222,6 @@ static flx_status planes_refusal(flx_context *ctx, enum flx_ray_planes_refusal w
     case FLX_RAY_PLANES_OVERLAP_OUT: what = "planes8 and planes32 overlap"; break;
   }
   return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": " + what);
-}
-
-/* the frame bounce() is given: one view, the params' seed and ambient (flx_rays_trace.hip: trace_frame), and use_filter, which makes bounce() keep renderId too (the
- * rest of the filter's bookkeeping it does on every path) */
-static void planes_frame(const flx_trace_params *p, DeviceFrame &fr, const flx_ray_temporal *temporal) {
-  memset(&fr, 0, sizeof fr);
-  fr.use_filter = temporal ? temporal->use_filter : 1;
-  fr.is_temporal = temporal ? 1 : 0;
-  fr.width = fr.height = fr.rows = fr.frame_rows = fr.frames = fr.tile_rows = fr.tile_count = 1u;
-  fr.samples = p->samples; fr.max_reflections = p->max_reflections;
-  fr.samples_shift = -1;
-  fr.min_importancy = p->min_importancy;
-  fr.texture_width = (float)p->texture_width;
-  memcpy(fr.view[0].ambient, p->ambient, sizeof fr.view[0].ambient);
-  fr.view[0].random_seed = p->random_seed;
 }
 
 template <bool LOCK, int MODE>
@@ -280,42 +253,26 @@ static flx_status planes_enqueue(flx_context *ctx, const flx_trace_params *param
   RayPlanesArgs ra;
   if ((s = flx_make_scene(ctx, ra.sc))) return s;           /* (refuses a scene that names a transform not uploaded) */
   if ((s = flx_server_stop(ctx))) return s;                 /* as flx_render_device: the frame server's launch ends after the frames posted to it */
-  planes_frame(params, ra.fr, temporal);
-  const uint32_t slab = flx_trace_slab_rays(1u, ctx->trace_slab);
-  const uint32_t most = n < slab ? n : slab;                /* rays of the largest slab */
-  if (!ctx->d_trace_hits.fits((size_t)most * 2u) || !ctx->d_trace_ctl) {
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier batch may still use the scratch that is about to go) */
-    if ((s = ctx->d_trace_hits.ensure(ctx, (size_t)most * 2u)) || (s = ctx->d_trace_ctl.ensure(ctx, 4))) return s;
-  }
-  if (producer_stream) {
-    if (!ctx->query_produced) FLX_HIP(ctx, hipEventCreateWithFlags(&ctx->query_produced, hipEventDisableTiming));
-    FLX_HIP(ctx, hipEventRecord(ctx->query_produced, (hipStream_t)producer_stream));
-    FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->query_produced, 0));
-  }
+  flx_trace_frame(params, ra.fr, temporal ? temporal->use_filter : 1, temporal ? 1 : 0);
+  flx_ray_slabs cut(ctx, 1u, n);
+  if ((s = flx_grow(ctx, flx_need(&ctx->d_trace_hits, (size_t)cut.most * 2u), flx_need(&ctx->d_trace_ctl, 4)))) return s;
+  if ((s = flx_wait_for_producer(ctx, producer_stream))) return s;
   if ((s = flx_angle_table(ctx, ra.sc))) return s;          /* the shading's per-triangle table, made again first where the scene or the transforms changed */
   const bool lock = FLX_LOCKSTEP && ra.sc.lock_entries != 0u;
   const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
-  flx_context::RayPlanesLaunch ran;
-  ran.n = n; ran.samples = (uint32_t)params->samples; ran.slab = slab; ran.lock = lock ? 1u : 0u;
   flx_context::RayHistory *history = nullptr;
   if (temporal) {
     history = &ctx->ray_history[temporal->history];
     if ((s = history_advance(ctx, *history, width, n / width, flx_ray_temporal_depth(temporal->temporal_samples)))) return s;
   }
-  for (uint64_t first = 0; first < n; first += slab) {
-    const uint32_t m = (uint32_t)(n - first < slab ? n - first : slab);
-    const float4 *rays = (const float4 *)d_rays + first * 2u;
+  uint32_t groups = 0;
+  /* a slab's launch behind its first hits; of d_trace_ctl's words [2] is the planes kernel's block cursor */
+  s = flx_rays_slabs(ctx, ra.sc, d_rays, n, cut, call, [&](uint64_t first, uint32_t m, const float4 *rays) -> flx_status {
     uint32_t *out8 = d_planes8 ? (uint32_t *)d_planes8 + first : nullptr;
     float4 *out32 = d_planes32 ? (float4 *)d_planes32 + first : nullptr;
-    /* the words of the slab's launches: [0] the query's chunk cursor, [1] its waves that drew; [2] the planes kernel's block cursor */
-    FLX_HIP(ctx, hipMemsetAsync(ctx->d_trace_ctl, 0, 4 * sizeof(uint32_t), ctx->stream));
-    QueryLaunch q;
-    if (!launch_ray_query(ra.sc, rays, ctx->d_trace_hits, m, FLX_RAYS_CLOSEST, ctx->d_trace_ctl, cus, ctx->query_groups, ctx->stream, &q))
-      return fail(ctx, FLX_ERR_DEVICE, std::string(call) + ": the query kernel cannot have its LDS on this device");
-    FLX_HIP(ctx, hipGetLastError());
     /* persistent grid: enough workgroups to fill every CU at the kernel's occupancy, no more than the blocks of rays fill; flx_debug_set_query_groups sets it too */
     const uint32_t full = (((m + RAY_PLANES_BLOCK - 1u) / RAY_PLANES_BLOCK) + 3u) / 4u;
-    const uint32_t groups = ctx->query_groups ? ctx->query_groups : (full < cus * 8u ? full : cus * 8u);
+    groups = ctx->query_groups ? ctx->query_groups : (full < cus * 8u ? full : cus * 8u);
     uint32_t *queue = ctx->d_trace_ctl.get() + 2;
     const float4 *hits = ctx->d_trace_hits.get();
     if (history) {
@@ -334,14 +291,18 @@ static flx_status planes_enqueue(flx_context *ctx, const flx_trace_params *param
       else planes_launch<false, RAY_PLANES>(groups, ctx->stream, ra, rays, hits, out8, out32, queue, m, (size_t)n, RayNoArgs());
     }
     FLX_HIP(ctx, hipGetLastError());
-    ran.slabs++; ran.groups = groups; ran.query_groups = q.groups;
-  }
+    return FLX_OK;
+  });
+  if (s) return s;
   if (history) {
     flx_context::RayTemporalLaunch &t = ctx->last_ray_temporal;
-    t.slabs = ran.slabs; t.slab = slab; t.depth = (uint32_t)history->at.n; t.history = (uint32_t)temporal->history; t.n = n; t.samples = ran.samples;
+    t.slabs = cut.slabs; t.slab = cut.slab; t.depth = (uint32_t)history->at.n; t.history = (uint32_t)temporal->history; t.n = n; t.samples = (uint32_t)params->samples;
     t.head = (uint32_t)history->at.head; t.fused = 1u;      /* the temporal pass ran inside the planes kernel */
     return FLX_OK;
   }
+  flx_context::RayPlanesLaunch ran;
+  ran.n = n; ran.samples = (uint32_t)params->samples; ran.slab = cut.slab; ran.lock = lock ? 1u : 0u;
+  ran.slabs = cut.slabs; ran.groups = groups; ran.query_groups = cut.query.groups;
   ctx->last_ray_planes = ran;
   return FLX_OK;
 }
@@ -350,13 +311,13 @@ extern "C" flx_status flx_rays_planes_device(flx_context *ctx, const flx_trace_p
                                              void *producer_stream) {
   static const char *const call = "flx_rays_planes_device";
   if (!ctx) return FLX_ERR_INVALID;
-  flx_status s = planes_refused(ctx, params, call);
+  flx_status s = flx_trace_params_refused(ctx, params, call);
   if (s || n == 0) return s;
   const enum flx_ray_planes_refusal arrays = flx_ray_planes_arrays_check((uint64_t)(uintptr_t)d_rays, (uint64_t)(uintptr_t)d_planes8, (uint64_t)(uintptr_t)d_planes32, n);
   const bool overlap = arrays == FLX_RAY_PLANES_OVERLAP_RAYS || arrays == FLX_RAY_PLANES_OVERLAP_OUT;      /* (said after the pointers are known to be the device's) */
   if (arrays != FLX_RAY_PLANES_ARGS_OK && !overlap) return planes_refusal(ctx, arrays, call);
   FLX_HIP(ctx, hipSetDevice(ctx->device));
-  if (!flx_rows_on_device(ctx, d_rays, (size_t)n * FLX_RAY_PLANES_RAY_BYTES))
+  if (!flx_rows_on_device(ctx, d_rays, (size_t)n * FLX_RAY_ROW_BYTES))
     return fail(ctx, FLX_ERR_INVALID, "flx_rays_planes_device: the rays are not n rows in memory of the context's device, 16-byte aligned");
   if (d_planes8 && !flx_rows_on_device(ctx, d_planes8, (size_t)n * FLX_RAY_PLANES * FLX_RAY_PLANES_ROW8))
     return fail(ctx, FLX_ERR_INVALID, "flx_rays_planes_device: planes8 is not 5 n texels in memory of the context's device, 16-byte aligned");
@@ -369,73 +330,62 @@ extern "C" flx_status flx_rays_planes_device(flx_context *ctx, const flx_trace_p
 extern "C" flx_status flx_rays_planes(flx_context *ctx, const flx_trace_params *params, const float *rays, uint32_t n, void *planes8, void *planes32) {
   static const char *const call = "flx_rays_planes";
   if (!ctx) return FLX_ERR_INVALID;
-  flx_status s = planes_refused(ctx, params, call);
+  flx_status s = flx_trace_params_refused(ctx, params, call);
   if (s || n == 0) return s;
   if (!planes8 && !planes32) return planes_refusal(ctx, FLX_RAY_PLANES_NONE, call);
   if (!rays) return planes_refusal(ctx, FLX_RAY_PLANES_NULL, call);
-  FLX_HIP(ctx, hipSetDevice(ctx->device));
   const size_t rows = (size_t)n * FLX_RAY_PLANES;
-  if (!ctx->d_query_rays.fits((size_t)n * 2u) || (planes32 && !ctx->d_query_hits.fits(rows)) || (planes8 && !ctx->d_ray_planes.fits(rows))) {
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier call may still read or write the staging that is about to go) */
-    if ((s = ctx->d_query_rays.ensure(ctx, (size_t)n * 2u))) return s;
-    if (planes32 && (s = ctx->d_query_hits.ensure(ctx, rows))) return s;
-    if (planes8 && (s = ctx->d_ray_planes.ensure(ctx, rows))) return s;
-  }
-  FLX_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, (size_t)n * FLX_RAY_PLANES_RAY_BYTES, hipMemcpyHostToDevice, ctx->stream));
-  if ((s = flx_rays_planes_device(ctx, params, ctx->d_query_rays, n, planes8 ? ctx->d_ray_planes.get() : nullptr, planes32 ? ctx->d_query_hits.get() : nullptr, nullptr))) return s;
-  if (planes8) FLX_HIP(ctx, hipMemcpyAsync(planes8, ctx->d_ray_planes, rows * FLX_RAY_PLANES_ROW8, hipMemcpyDeviceToHost, ctx->stream));
-  if (planes32) FLX_HIP(ctx, hipMemcpyAsync(planes32, ctx->d_query_hits, rows * FLX_RAY_PLANES_ROW32, hipMemcpyDeviceToHost, ctx->stream));
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return FLX_OK;
+  return flx_rays_from_host(ctx, rays, n, [&]() {
+    return flx_rays_planes_device(ctx, params, ctx->d_query_rays, n, planes8 ? ctx->d_ray_planes.get() : nullptr, planes32 ? ctx->d_query_hits.get() : nullptr, nullptr);
+  }, flx_down(&ctx->d_ray_planes, rows, planes8), flx_down(&ctx->d_query_hits, rows, planes32));
 }
 
-extern "C" flx_status flx_rays_image_device(flx_context *ctx, const flx_trace_params *params, int hdr, const void *d_rays, uint32_t width, uint32_t height, void *d_out_rgba,
-                                            void *producer_stream) {
-  static const char *const call = "flx_rays_image_device";
-  if (!ctx) return FLX_ERR_INVALID;
-  flx_status s = planes_refused(ctx, params, call);
-  if (s) return s;
-  uint32_t n = 0;
-  if ((s = planes_refusal(ctx, flx_ray_image_size_check(width, height, &n), call))) return s;
+/* Both image calls behind their own refusals: the arrays of n = width * height rays, the planes, the chain.  temporal NULL: flx_rays_image_device, which has its hdr
+ * beside the params; else the image over that history, the hdr the history's. */
+static flx_status image_enqueue(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal, int hdr, const void *d_rays, uint32_t width, uint32_t height,
+                                uint32_t n, void *d_out_rgba, void *producer_stream, const char *call) {
   const enum flx_ray_planes_refusal arrays = flx_ray_image_arrays_check((uint64_t)(uintptr_t)d_rays, (uint64_t)(uintptr_t)d_out_rgba, n);
   if (arrays != FLX_RAY_PLANES_ARGS_OK && arrays != FLX_RAY_PLANES_OVERLAP_RAYS) return planes_refusal(ctx, arrays, call);
   FLX_HIP(ctx, hipSetDevice(ctx->device));
-  if (!flx_rows_on_device(ctx, d_rays, (size_t)n * FLX_RAY_PLANES_RAY_BYTES))
-    return fail(ctx, FLX_ERR_INVALID, "flx_rays_image_device: the rays are not width * height rows in memory of the context's device, 16-byte aligned");
+  if (!flx_rows_on_device(ctx, d_rays, (size_t)n * FLX_RAY_ROW_BYTES))
+    return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": the rays are not width * height rows in memory of the context's device, 16-byte aligned");
   if (!flx_rows_on_device(ctx, d_out_rgba, (size_t)n * FLX_RAY_PLANES_ROW32))
-    return fail(ctx, FLX_ERR_INVALID, "flx_rays_image_device: the image is not width * height float4 in memory of the context's device, 16-byte aligned");
+    return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": the image is not width * height float4 in memory of the context's device, 16-byte aligned");
   if (arrays == FLX_RAY_PLANES_OVERLAP_RAYS) return planes_refusal(ctx, arrays, call);
-  const size_t rows = (size_t)n * FLX_RAY_PLANES;
-  if (!ctx->d_ray_planes.fits(rows)) {
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier image's chain may still read the planes that are about to go) */
-    if ((s = ctx->d_ray_planes.ensure(ctx, rows))) return s;
-  }
-  if ((s = planes_enqueue(ctx, params, d_rays, n, ctx->d_ray_planes.get(), nullptr, producer_stream, call))) return s;
-  /* the chain reads width, height and hdr of a frame's params, nothing of a camera: frame-0 texture state, as flx_filter_planes_device starts it */
+  if (temporal && temporal->use_filter != 1)      /* the canvas colour of the temporal pass, straight from the kernel */
+    return planes_enqueue(ctx, params, d_rays, n, nullptr, d_out_rgba, producer_stream, call, temporal, width);
+  flx_status s;
+  if ((s = flx_grow(ctx, flx_need(&ctx->d_ray_planes, (size_t)n * FLX_RAY_PLANES)))) return s;      /* (an earlier image's chain may still read the planes that are about to go) */
+  if ((s = planes_enqueue(ctx, params, d_rays, n, ctx->d_ray_planes.get(), nullptr, producer_stream, call, temporal, width))) return s;
+  /* the chain reads width, height and hdr of a frame's params, nothing of a camera: frame-0 texture state, as flx_filter_planes_device starts it (with a history:
+   * dColor, dIp, dOColor, dId and dOId feed it as for a ray image) */
   flx_frame_params image;
   memset(&image, 0, sizeof image);
   image.width = width; image.height = height; image.hdr = hdr;
   return flx_filter_planes_enqueue(ctx, &image, ctx->d_ray_planes.get(), d_out_rgba, true);
 }
 
+extern "C" flx_status flx_rays_image_device(flx_context *ctx, const flx_trace_params *params, int hdr, const void *d_rays, uint32_t width, uint32_t height, void *d_out_rgba,
+                                            void *producer_stream) {
+  static const char *const call = "flx_rays_image_device";
+  if (!ctx) return FLX_ERR_INVALID;
+  flx_status s = flx_trace_params_refused(ctx, params, call);
+  if (s) return s;
+  uint32_t n = 0;
+  if ((s = planes_refusal(ctx, flx_ray_image_size_check(width, height, &n), call))) return s;
+  return image_enqueue(ctx, params, nullptr, hdr, d_rays, width, height, n, d_out_rgba, producer_stream, call);
+}
+
 extern "C" flx_status flx_rays_image(flx_context *ctx, const flx_trace_params *params, int hdr, const float *rays, uint32_t width, uint32_t height, float *out_rgba) {
   static const char *const call = "flx_rays_image";
   if (!ctx) return FLX_ERR_INVALID;
-  flx_status s = planes_refused(ctx, params, call);
+  flx_status s = flx_trace_params_refused(ctx, params, call);
   if (s) return s;
   uint32_t n = 0;
   if ((s = planes_refusal(ctx, flx_ray_image_size_check(width, height, &n), call))) return s;
   if (!rays || !out_rgba) return planes_refusal(ctx, FLX_RAY_PLANES_NULL, call);
-  FLX_HIP(ctx, hipSetDevice(ctx->device));
-  if (!ctx->d_query_rays.fits((size_t)n * 2u) || !ctx->d_query_hits.fits(n)) {
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier call may still read or write the staging that is about to go) */
-    if ((s = ctx->d_query_rays.ensure(ctx, (size_t)n * 2u)) || (s = ctx->d_query_hits.ensure(ctx, n))) return s;
-  }
-  FLX_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, (size_t)n * FLX_RAY_PLANES_RAY_BYTES, hipMemcpyHostToDevice, ctx->stream));
-  if ((s = flx_rays_image_device(ctx, params, hdr, ctx->d_query_rays, width, height, ctx->d_query_hits, nullptr))) return s;
-  FLX_HIP(ctx, hipMemcpyAsync(out_rgba, ctx->d_query_hits, (size_t)n * FLX_RAY_PLANES_ROW32, hipMemcpyDeviceToHost, ctx->stream));
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return FLX_OK;
+  return flx_rays_from_host(ctx, rays, n, [&]() { return flx_rays_image_device(ctx, params, hdr, ctx->d_query_rays, width, height, ctx->d_query_hits, nullptr); },
+                            flx_down(&ctx->d_query_hits, n, out_rgba));
 }
 
 /* a refusal of flx_ray_temporal_args.h in words */
@@ -457,56 +407,28 @@ extern "C" flx_status flx_rays_image_temporal_device(flx_context *ctx, const flx
                                                      uint32_t height, void *d_out_rgba, void *producer_stream) {
   static const char *const call = "flx_rays_image_temporal_device";
   if (!ctx) return FLX_ERR_INVALID;
-  flx_status s = planes_refused(ctx, params, call);
+  flx_status s = flx_trace_params_refused(ctx, params, call);
   if (s) return s;
   uint32_t n = 0;
   if ((s = planes_refusal(ctx, flx_ray_image_size_check(width, height, &n), call))) return s;
   if ((s = temporal_refusal(ctx, flx_ray_temporal_check(temporal != nullptr, temporal ? temporal->history : 0, temporal ? temporal->use_filter : 0, temporal ? temporal->hdr : 0), call)))
     return s;
-  const enum flx_ray_planes_refusal arrays = flx_ray_image_arrays_check((uint64_t)(uintptr_t)d_rays, (uint64_t)(uintptr_t)d_out_rgba, n);
-  if (arrays != FLX_RAY_PLANES_ARGS_OK && arrays != FLX_RAY_PLANES_OVERLAP_RAYS) return planes_refusal(ctx, arrays, call);
-  FLX_HIP(ctx, hipSetDevice(ctx->device));
-  if (!flx_rows_on_device(ctx, d_rays, (size_t)n * FLX_RAY_PLANES_RAY_BYTES))
-    return fail(ctx, FLX_ERR_INVALID, "flx_rays_image_temporal_device: the rays are not width * height rows in memory of the context's device, 16-byte aligned");
-  if (!flx_rows_on_device(ctx, d_out_rgba, (size_t)n * FLX_RAY_PLANES_ROW32))
-    return fail(ctx, FLX_ERR_INVALID, "flx_rays_image_temporal_device: the image is not width * height float4 in memory of the context's device, 16-byte aligned");
-  if (arrays == FLX_RAY_PLANES_OVERLAP_RAYS) return planes_refusal(ctx, arrays, call);
-  if (temporal->use_filter != 1)      /* the canvas colour of the temporal pass, straight from the kernel */
-    return planes_enqueue(ctx, params, d_rays, n, nullptr, d_out_rgba, producer_stream, call, temporal, width);
-  const size_t rows = (size_t)n * FLX_RAY_PLANES;
-  if (!ctx->d_ray_planes.fits(rows)) {
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier image's chain may still read the planes that are about to go) */
-    if ((s = ctx->d_ray_planes.ensure(ctx, rows))) return s;
-  }
-  if ((s = planes_enqueue(ctx, params, d_rays, n, ctx->d_ray_planes.get(), nullptr, producer_stream, call, temporal, width))) return s;
-  /* dColor, dIp, dOColor, dId and dOId feed the chain as for a ray image: frame-0 texture state, of the params width, height and hdr alone */
-  flx_frame_params image;
-  memset(&image, 0, sizeof image);
-  image.width = width; image.height = height; image.hdr = temporal->hdr;
-  return flx_filter_planes_enqueue(ctx, &image, ctx->d_ray_planes.get(), d_out_rgba, true);
+  return image_enqueue(ctx, params, temporal, temporal->hdr, d_rays, width, height, n, d_out_rgba, producer_stream, call);
 }
 
 extern "C" flx_status flx_rays_image_temporal(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal, const float *rays, uint32_t width, uint32_t height,
                                               float *out_rgba) {
   static const char *const call = "flx_rays_image_temporal";
   if (!ctx) return FLX_ERR_INVALID;
-  flx_status s = planes_refused(ctx, params, call);
+  flx_status s = flx_trace_params_refused(ctx, params, call);
   if (s) return s;
   uint32_t n = 0;
   if ((s = planes_refusal(ctx, flx_ray_image_size_check(width, height, &n), call))) return s;
   if ((s = temporal_refusal(ctx, flx_ray_temporal_check(temporal != nullptr, temporal ? temporal->history : 0, temporal ? temporal->use_filter : 0, temporal ? temporal->hdr : 0), call)))
     return s;
   if (!rays || !out_rgba) return planes_refusal(ctx, FLX_RAY_PLANES_NULL, call);
-  FLX_HIP(ctx, hipSetDevice(ctx->device));
-  if (!ctx->d_query_rays.fits((size_t)n * 2u) || !ctx->d_query_hits.fits(n)) {
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier call may still read or write the staging that is about to go) */
-    if ((s = ctx->d_query_rays.ensure(ctx, (size_t)n * 2u)) || (s = ctx->d_query_hits.ensure(ctx, n))) return s;
-  }
-  FLX_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, (size_t)n * FLX_RAY_PLANES_RAY_BYTES, hipMemcpyHostToDevice, ctx->stream));
-  if ((s = flx_rays_image_temporal_device(ctx, params, temporal, ctx->d_query_rays, width, height, ctx->d_query_hits, nullptr))) return s;
-  FLX_HIP(ctx, hipMemcpyAsync(out_rgba, ctx->d_query_hits, (size_t)n * FLX_RAY_PLANES_ROW32, hipMemcpyDeviceToHost, ctx->stream));
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return FLX_OK;
+  return flx_rays_from_host(ctx, rays, n, [&]() { return flx_rays_image_temporal_device(ctx, params, temporal, ctx->d_query_rays, width, height, ctx->d_query_hits, nullptr); },
+                            flx_down(&ctx->d_query_hits, n, out_rgba));
 }
 
 extern "C" flx_status flx_rays_history_reset(flx_context *ctx, int history) {

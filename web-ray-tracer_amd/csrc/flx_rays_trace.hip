@@ -18,13 +18,16 @@
  * that the scratch has a ceiling: flx_trace_slab_rays (flx_query_args.h) — at most 2^24 slots (256 MB) and 2^21 rays a slab, at least 64 rays.  A slab's three
  * launches follow each other on the context's stream, the cursors zeroed in stream order in front of them.  The paths kernel's cursor counts UNITS of 64 items
  * (a block of rays x a sample), of which a slab has fewer than 2^31 + 2^18 whatever n and the sample count: any n a uint32_t holds works at any sample count the
- * memory holds a slab of.  The host waits for nothing — but where the scratch must grow, for the work that may still use it. */
+ * memory holds a slab of.  The host waits for nothing — but where the scratch must grow, for the work that may still use it.
+ * The host side around the launches — the params' refusal and the frame bounce() is given, the growth, the producer wait, the slab loop and its first hits, the
+ * host-memory call — is the ray-batch calls' shared path (flx_query.hip, flx_rays_host.h). */
 #include <cstring>
 
 #define FLX_ANGLE_TABLE 1                  /* k_rays_paths reads the shading's per-triangle table (flx_device.h: one definition per translation unit), as k_paths does at the same four waves per SIMD */
 #include "flx_context.h"
 #include "flx_kernel_util.h"
 #include "flx_query_args.h"
+#include "flx_rays_host.h"
 
 using namespace flx;
 
@@ -157,33 +160,9 @@ __global__ __launch_bounds__(256) void k_rays_resolve(const float4 *__restrict__
 
 static flx_status fail(flx_context *ctx, flx_status code, const char *msg) { return flx_fail(ctx, code, msg); }
 
-/* what both calls refuse before they look at an array */
-static flx_status trace_refused(flx_context *ctx, const flx_trace_params *p) {
-  if (!ctx->have_scene || !ctx->have_transforms) return fail(ctx, FLX_ERR_NO_SCENE, "flx_rays_trace: no scene and transforms uploaded");
-  switch (flx_trace_args_check(p != nullptr, p ? p->samples : 0, p ? p->max_reflections : 0, p ? p->texture_width : 0, 0u, 0u, 0u)) {
-    case FLX_TRACE_ARGS_OK: return FLX_OK;
-    case FLX_TRACE_PARAMS_NULL: return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace: params is NULL");
-    case FLX_TRACE_SAMPLES: return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace: samples is less than 1");
-    case FLX_TRACE_REFLECTIONS: return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace: max_reflections is negative");
-    default: return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace: texture_width is less than 1");
-  }
-}
-
-/* the frame bounce() is given: one view, the params' seed and ambient; no filter, no temporal */
-static void trace_frame(const flx_trace_params *p, DeviceFrame &fr) {
-  memset(&fr, 0, sizeof fr);
-  fr.width = fr.height = fr.rows = fr.frame_rows = fr.frames = fr.tile_rows = fr.tile_count = 1u;
-  fr.samples = p->samples; fr.max_reflections = p->max_reflections;
-  fr.samples_shift = -1;
-  fr.min_importancy = p->min_importancy;
-  fr.texture_width = (float)p->texture_width;
-  memcpy(fr.view[0].ambient, p->ambient, sizeof fr.view[0].ambient);
-  fr.view[0].random_seed = p->random_seed;
-}
-
 extern "C" flx_status flx_rays_trace_device(flx_context *ctx, const flx_trace_params *params, const void *d_rays, void *d_radiance, uint32_t n, void *producer_stream) {
   if (!ctx) return FLX_ERR_INVALID;
-  flx_status s = trace_refused(ctx, params);
+  flx_status s = flx_trace_params_refused(ctx, params, "flx_rays_trace");      /* (both entry points say flx_rays_trace: here) */
   if (s || n == 0) return s;
   const enum flx_trace_refusal arrays = flx_trace_args_check(1, params->samples, params->max_reflections, params->texture_width, (uint64_t)(uintptr_t)d_rays,
                                                              (uint64_t)(uintptr_t)d_radiance, n);
@@ -193,7 +172,7 @@ extern "C" flx_status flx_rays_trace_device(flx_context *ctx, const flx_trace_pa
     default: return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_device: n rows of 32 bytes leave the address space");
   }
   FLX_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = (size_t)n * FLX_QUERY_ROW_BYTES;
+  const size_t bytes = (size_t)n * FLX_RAY_ROW_BYTES;
   if (!flx_rows_on_device(ctx, d_rays, bytes))
     return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_device: the rays are not n rows in memory of the context's device, 16-byte aligned");
   if (!flx_rows_on_device(ctx, d_radiance, bytes))
@@ -203,68 +182,47 @@ extern "C" flx_status flx_rays_trace_device(flx_context *ctx, const flx_trace_pa
   TraceArgs ta;
   if ((s = flx_make_scene(ctx, ta.sc))) return s;           /* (refuses a scene that names a transform not uploaded) */
   if ((s = flx_server_stop(ctx))) return s;                 /* as flx_render_device: the frame server's launch ends after the frames posted to it */
-  trace_frame(params, ta.fr);
+  flx_trace_frame(params, ta.fr, 0, 0);                     /* no filter, no temporal */
   const uint32_t S = (uint32_t)params->samples;
-  const uint32_t slab = flx_trace_slab_rays(S, ctx->trace_slab);
-  const uint32_t most = n < slab ? n : slab;                /* rays of the largest slab */
-  if (!ctx->d_trace_hits.fits((size_t)most * 2u) || !ctx->d_trace_slots.fits((size_t)most * S) || !ctx->d_trace_last.fits(most) || !ctx->d_trace_ctl) {
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier batch may still use the scratch that is about to go) */
-    if ((s = ctx->d_trace_hits.ensure(ctx, (size_t)most * 2u)) || (s = ctx->d_trace_slots.ensure(ctx, (size_t)most * S)) || (s = ctx->d_trace_last.ensure(ctx, most)) ||
-        (s = ctx->d_trace_ctl.ensure(ctx, 4)))
-      return s;
-  }
-  if (producer_stream) {
-    if (!ctx->query_produced) FLX_HIP(ctx, hipEventCreateWithFlags(&ctx->query_produced, hipEventDisableTiming));
-    FLX_HIP(ctx, hipEventRecord(ctx->query_produced, (hipStream_t)producer_stream));
-    FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->query_produced, 0));
-  }
+  flx_ray_slabs cut(ctx, S, n);
+  if ((s = flx_grow(ctx, flx_need(&ctx->d_trace_hits, (size_t)cut.most * 2u), flx_need(&ctx->d_trace_slots, (size_t)cut.most * S), flx_need(&ctx->d_trace_last, cut.most),
+                    flx_need(&ctx->d_trace_ctl, 4))))
+    return s;
+  if ((s = flx_wait_for_producer(ctx, producer_stream))) return s;
   if ((s = flx_angle_table(ctx, ta.sc))) return s;          /* the shading's per-triangle table, made again first where the scene or the transforms changed: FLX_ANGLE_TABLE above makes this file's bounce() read it */
   const bool lock = FLX_LOCKSTEP && ta.sc.lock_entries != 0u;
   const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
-  flx_context::TraceLaunch ran;
-  ran.n = n; ran.samples = S; ran.slab = slab; ran.lock = lock ? 1u : 0u;
-  for (uint64_t first = 0; first < n; first += slab) {
-    const uint32_t m = (uint32_t)(n - first < slab ? n - first : slab);
-    const float4 *rays = (const float4 *)d_rays + first * 2u;
+  uint32_t blocks = 0;
+  /* a slab's launches behind its first hits; of d_trace_ctl's words [2] is the paths kernel's unit cursor */
+  s = flx_rays_slabs(ctx, ta.sc, d_rays, n, cut, "flx_rays_trace_device", [&](uint64_t first, uint32_t m, const float4 *rays) -> flx_status {
     float4 *out = (float4 *)d_radiance + first * 2u;
-    /* the words of the slab's launches: [0] the query's chunk cursor, [1] its waves that drew; [2] the paths kernel's unit cursor */
-    FLX_HIP(ctx, hipMemsetAsync(ctx->d_trace_ctl, 0, 4 * sizeof(uint32_t), ctx->stream));
-    QueryLaunch q;
-    if (!launch_ray_query(ta.sc, rays, ctx->d_trace_hits, m, FLX_RAYS_CLOSEST, ctx->d_trace_ctl, cus, ctx->query_groups, ctx->stream, &q))
-      return fail(ctx, FLX_ERR_DEVICE, "flx_rays_trace_device: the query kernel cannot have its LDS on this device");
-    FLX_HIP(ctx, hipGetLastError());
     /* persistent grid: enough workgroups to fill every CU at the kernel's occupancy, no more than the items fill; flx_debug_set_query_groups sets it too */
     const uint32_t units = ((m + 63u) >> 6) * S;              /* (block of 64 rays, sample) pairs: below 2^31 + 2^18 by flx_trace_slab_rays' rule; four fill a workgroup */
     const uint32_t full = (units + 3u) / 4u;
-    const uint32_t blocks = ctx->query_groups ? ctx->query_groups : (full < cus * 8u ? full : cus * 8u);
+    blocks = ctx->query_groups ? ctx->query_groups : (full < cus * 8u ? full : cus * 8u);
     uint32_t *queue = ctx->d_trace_ctl.get() + 2;
     if (lock) hipLaunchKernelGGL(k_rays_paths<true>, dim3(blocks), dim3(256), 0, ctx->stream, ta, rays, ctx->d_trace_hits.get(), ctx->d_trace_slots.get(), ctx->d_trace_last.get(), queue, m, units);
     else hipLaunchKernelGGL(k_rays_paths<false>, dim3(blocks), dim3(256), 0, ctx->stream, ta, rays, ctx->d_trace_hits.get(), ctx->d_trace_slots.get(), ctx->d_trace_last.get(), queue, m, units);
     FLX_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_rays_resolve, dim3((m + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_trace_hits.get(), ctx->d_trace_slots.get(), ctx->d_trace_last.get(), out, m, params->samples);
     FLX_HIP(ctx, hipGetLastError());
-    ran.slabs++; ran.path_groups = blocks; ran.query_groups = q.groups;
-  }
+    return FLX_OK;
+  });
+  if (s) return s;
+  flx_context::TraceLaunch ran;
+  ran.n = n; ran.samples = S; ran.slab = cut.slab; ran.lock = lock ? 1u : 0u;
+  ran.slabs = cut.slabs; ran.path_groups = blocks; ran.query_groups = cut.query.groups;
   ctx->last_trace_rays = ran;
   return FLX_OK;
 }
 
 extern "C" flx_status flx_rays_trace(flx_context *ctx, const flx_trace_params *params, const float *rays, void *radiance, uint32_t n) {
   if (!ctx) return FLX_ERR_INVALID;
-  flx_status s = trace_refused(ctx, params);
+  flx_status s = flx_trace_params_refused(ctx, params, "flx_rays_trace");      /* (both entry points say flx_rays_trace: here) */
   if (s || n == 0) return s;
   if (!rays || !radiance) return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace: an array is NULL");
-  FLX_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = (size_t)n * FLX_QUERY_ROW_BYTES;
-  if (!ctx->d_query_rays.fits((size_t)n * 2u) || !ctx->d_query_hits.fits((size_t)n * 2u)) {
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier query may still read or write the staging that is about to go) */
-    if ((s = ctx->d_query_rays.ensure(ctx, (size_t)n * 2u)) || (s = ctx->d_query_hits.ensure(ctx, (size_t)n * 2u))) return s;
-  }
-  FLX_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, bytes, hipMemcpyHostToDevice, ctx->stream));
-  if ((s = flx_rays_trace_device(ctx, params, ctx->d_query_rays, ctx->d_query_hits, n, nullptr))) return s;
-  FLX_HIP(ctx, hipMemcpyAsync(radiance, ctx->d_query_hits, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return FLX_OK;
+  return flx_rays_from_host(ctx, rays, n, [&]() { return flx_rays_trace_device(ctx, params, ctx->d_query_rays, ctx->d_query_hits, n, nullptr); },
+                            flx_down(&ctx->d_query_hits, (size_t)n * 2u, radiance));
 }
 
 extern "C" flx_status flx_debug_set_trace_slab(flx_context *ctx, uint32_t rays) {

@@ -13,12 +13,14 @@
  *      and is not here.  Plane p of the output starts at out + p * n rows; every lane makes one 16-byte store per plane, a wave 1 KiB contiguous per plane.
  * The hit scratch is the traced batches' (flx_context.h: d_trace_hits, d_trace_ctl), grown and never shrunk; a ray batch is cut into slabs of at most 2^21 rays
  * (flx_trace_slab_rays at one slot a ray; flx_debug_set_trace_slab lowers it), a slab's two launches following each other on the context's stream.  The host waits
- * for nothing — but where the scratch must grow, for the work that may still use it. */
+ * for nothing — but where the scratch must grow, for the work that may still use it.  The growth, the producer wait, the slab loop and its first hits and the
+ * host-memory calls are the ray-batch calls' shared path (flx_query.hip, flx_rays_host.h). */
 #include <cstring>
 
 #include "flx_context.h"
 #include "flx_kernel_util.h"
 #include "flx_query_args.h"
+#include "flx_rays_host.h"
 #include "flx_surface_args.h"
 
 using namespace flx;
@@ -153,30 +155,19 @@ static flx_status surface_refusal(flx_context *ctx, enum flx_surface_refusal why
   return fail(ctx, FLX_ERR_INVALID, (std::string(call) + ": " + what).c_str());
 }
 
-static flx_status no_scene(flx_context *ctx, const char *call) {
-  return fail(ctx, FLX_ERR_NO_SCENE, (std::string(call) + ": no scene and transforms uploaded").c_str());
-}
-
-/* the hit scratch holds `rows` float4 and the launches' words are there: the host waits only where the scratch must grow */
-static flx_status surface_scratch(flx_context *ctx, size_t rows) {
-  if (ctx->d_trace_hits.fits(rows) && ctx->d_trace_ctl) return FLX_OK;
-  flx_status s;
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));          /* (an earlier batch may still use the scratch that is about to go) */
-  if ((s = ctx->d_trace_hits.ensure(ctx, rows)) || (s = ctx->d_trace_ctl.ensure(ctx, 4))) return s;
-  return FLX_OK;
-}
+/* the hit scratch holds `rows` float4 and the launches' words are there */
+static flx_status surface_scratch(flx_context *ctx, size_t rows) { return flx_grow(ctx, flx_need(&ctx->d_trace_hits, rows), flx_need(&ctx->d_trace_ctl, 4)); }
 
 extern "C" flx_status flx_rays_surface_device(flx_context *ctx, int32_t texture_width, const void *d_rays, uint32_t n, uint32_t fields, void *d_out, void *producer_stream) {
   static const char *const call = "flx_rays_surface_device";
   if (!ctx) return FLX_ERR_INVALID;
-  if (!ctx->have_scene || !ctx->have_transforms) return no_scene(ctx, call);
-  flx_status s = surface_refusal(ctx, flx_surface_fields_check(fields, texture_width), call);
-  if (s || n == 0) return s;
+  flx_status s = flx_scene_refused(ctx, call);
+  if (s || (s = surface_refusal(ctx, flx_surface_fields_check(fields, texture_width), call)) || n == 0) return s;
   uint64_t out_bytes = 0;
   const enum flx_surface_refusal arrays = flx_surface_arrays_check(1, (uint64_t)(uintptr_t)d_rays, (uint64_t)(uintptr_t)d_out, n, fields, &out_bytes);
   if (arrays != FLX_SURFACE_ARGS_OK && arrays != FLX_SURFACE_OVERLAP) return surface_refusal(ctx, arrays, call);      /* (overlap: said after the pointers are known to be the device's) */
   FLX_HIP(ctx, hipSetDevice(ctx->device));
-  if (!flx_rows_on_device(ctx, d_rays, (size_t)n * FLX_SURFACE_RAY_BYTES))
+  if (!flx_rows_on_device(ctx, d_rays, (size_t)n * FLX_RAY_ROW_BYTES))
     return fail(ctx, FLX_ERR_INVALID, "flx_rays_surface_device: the rays are not n rows in memory of the context's device, 16-byte aligned");
   if (!flx_rows_on_device(ctx, d_out, (size_t)out_bytes))
     return fail(ctx, FLX_ERR_INVALID, "flx_rays_surface_device: the planes are not popcount(fields) * n rows in memory of the context's device, 16-byte aligned");
@@ -186,30 +177,18 @@ extern "C" flx_status flx_rays_surface_device(flx_context *ctx, int32_t texture_
   if ((s = flx_make_scene(ctx, sa.sc))) return s;            /* (refuses a scene that names a transform not uploaded) */
   if ((s = flx_server_stop(ctx))) return s;                  /* as flx_render_device: the frame server's launch ends after the frames posted to it */
   sa.texture_width = (float)texture_width;
-  const uint32_t slab = flx_trace_slab_rays(1u, ctx->trace_slab);
-  const uint32_t most = n < slab ? n : slab;                 /* rays of the largest slab */
-  if ((s = surface_scratch(ctx, (size_t)most * 2u))) return s;
-  if (producer_stream) {
-    if (!ctx->query_produced) FLX_HIP(ctx, hipEventCreateWithFlags(&ctx->query_produced, hipEventDisableTiming));
-    FLX_HIP(ctx, hipEventRecord(ctx->query_produced, (hipStream_t)producer_stream));
-    FLX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->query_produced, 0));
-  }
-  const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
-  flx_context::SurfaceLaunch ran;
-  ran.n = n; ran.fields = fields; ran.slab = slab;
-  for (uint64_t first = 0; first < n; first += slab) {
-    const uint32_t m = (uint32_t)(n - first < slab ? n - first : slab);
-    const float4 *rays = (const float4 *)d_rays + first * 2u;
-    FLX_HIP(ctx, hipMemsetAsync(ctx->d_trace_ctl, 0, 4 * sizeof(uint32_t), ctx->stream));      /* [0] the query's chunk cursor, [1] its waves that drew */
-    QueryLaunch q;
-    if (!launch_ray_query(sa.sc, rays, ctx->d_trace_hits, m, FLX_RAYS_CLOSEST, ctx->d_trace_ctl, cus, ctx->query_groups, ctx->stream, &q))
-      return fail(ctx, FLX_ERR_DEVICE, "flx_rays_surface_device: the query kernel cannot have its LDS on this device");
-    FLX_HIP(ctx, hipGetLastError());
+  flx_ray_slabs cut(ctx, 1u, n);
+  if ((s = surface_scratch(ctx, (size_t)cut.most * 2u))) return s;
+  if ((s = flx_wait_for_producer(ctx, producer_stream))) return s;
+  s = flx_rays_slabs(ctx, sa.sc, d_rays, n, cut, call, [&](uint64_t first, uint32_t m, const float4 *rays) -> flx_status {
     hipLaunchKernelGGL(k_surface<false>, dim3((m + 255u) / 256u), dim3(256), 0, ctx->stream, sa, rays, (const float4 *)ctx->d_trace_hits.get(), (float4 *)d_out + first, m,
                        (size_t)n, fields);
     FLX_HIP(ctx, hipGetLastError());
-    ran.slabs++; ran.query_groups = q.groups;
-  }
+    return FLX_OK;
+  });
+  if (s) return s;
+  flx_context::SurfaceLaunch ran;
+  ran.n = n; ran.fields = fields; ran.slab = cut.slab; ran.slabs = cut.slabs; ran.query_groups = cut.query.groups;
   ctx->last_surface = ran;
   return FLX_OK;
 }
@@ -217,29 +196,19 @@ extern "C" flx_status flx_rays_surface_device(flx_context *ctx, int32_t texture_
 extern "C" flx_status flx_rays_surface(flx_context *ctx, int32_t texture_width, const float *rays, uint32_t n, uint32_t fields, void *out) {
   static const char *const call = "flx_rays_surface";
   if (!ctx) return FLX_ERR_INVALID;
-  if (!ctx->have_scene || !ctx->have_transforms) return no_scene(ctx, call);
-  flx_status s = surface_refusal(ctx, flx_surface_fields_check(fields, texture_width), call);
-  if (s || n == 0) return s;
+  flx_status s = flx_scene_refused(ctx, call);
+  if (s || (s = surface_refusal(ctx, flx_surface_fields_check(fields, texture_width), call)) || n == 0) return s;
   if (!rays || !out) return surface_refusal(ctx, FLX_SURFACE_NULL, call);
-  FLX_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t rows = (size_t)n * flx_surface_planes(fields);
-  if (!ctx->d_query_rays.fits((size_t)n * 2u) || !ctx->d_query_hits.fits(rows)) {
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier query may still read or write the staging that is about to go) */
-    if ((s = ctx->d_query_rays.ensure(ctx, (size_t)n * 2u)) || (s = ctx->d_query_hits.ensure(ctx, rows))) return s;
-  }
-  FLX_HIP(ctx, hipMemcpyAsync(ctx->d_query_rays, rays, (size_t)n * FLX_SURFACE_RAY_BYTES, hipMemcpyHostToDevice, ctx->stream));
-  if ((s = flx_rays_surface_device(ctx, texture_width, ctx->d_query_rays, n, fields, ctx->d_query_hits, nullptr))) return s;
-  FLX_HIP(ctx, hipMemcpyAsync(out, ctx->d_query_hits, rows * FLX_SURFACE_ROW_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return FLX_OK;
+  return flx_rays_from_host(ctx, rays, n, [&]() { return flx_rays_surface_device(ctx, texture_width, ctx->d_query_rays, n, fields, ctx->d_query_hits, nullptr); },
+                            flx_down(&ctx->d_query_hits, (size_t)n * flx_surface_planes(fields), out));
 }
 
 /* what both frame calls refuse before they look at the output */
 static flx_status frame_surface_refused(flx_context *ctx, const flx_frame_params *p, uint32_t fields, const char *call) {
-  if (!ctx->have_scene || !ctx->have_transforms) return no_scene(ctx, call);
-  if (!p) return surface_refusal(ctx, FLX_SURFACE_PARAMS_NULL, call);
-  flx_status s = surface_refusal(ctx, flx_surface_fields_check(fields, p->texture_width), call);
+  flx_status s = flx_scene_refused(ctx, call);
   if (s) return s;
+  if (!p) return surface_refusal(ctx, FLX_SURFACE_PARAMS_NULL, call);
+  if ((s = surface_refusal(ctx, flx_surface_fields_check(fields, p->texture_width), call))) return s;
   return surface_refusal(ctx, flx_surface_frame_check(1, p->width, p->height, p->tile_rows, p->tile_index, p->tile_count), call);
 }
 
@@ -289,16 +258,8 @@ extern "C" flx_status flx_frame_surface(flx_context *ctx, const flx_frame_params
   flx_status s = frame_surface_refused(ctx, params, fields, call);
   if (s) return s;
   if (!out) return surface_refusal(ctx, FLX_SURFACE_NULL, call);
-  FLX_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t rows = (size_t)params->width * params->height * flx_surface_planes(fields);
-  if (!ctx->d_query_hits.fits(rows)) {
-    FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));        /* (an earlier query may still write the staging that is about to go) */
-    if ((s = ctx->d_query_hits.ensure(ctx, rows))) return s;
-  }
-  if ((s = flx_frame_surface_device(ctx, params, fields, ctx->d_query_hits))) return s;
-  FLX_HIP(ctx, hipMemcpyAsync(out, ctx->d_query_hits, rows * FLX_SURFACE_ROW_BYTES, hipMemcpyDeviceToHost, ctx->stream));
-  FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return FLX_OK;
+  return flx_rays_from_host(ctx, nullptr, 0u, [&]() { return flx_frame_surface_device(ctx, params, fields, ctx->d_query_hits); },
+                            flx_down(&ctx->d_query_hits, (size_t)params->width * params->height * flx_surface_planes(fields), out));
 }
 
 extern "C" flx_status flx_debug_last_surface(flx_context *ctx, uint32_t out[8]) {

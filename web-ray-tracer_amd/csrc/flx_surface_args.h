@@ -1,12 +1,13 @@
 /* flx_surface_args.h — what flx_rays_surface_device and flx_frame_surface_device decide about their arguments before they ask the device anything (csrc/flx_surface.hip):
- * plain C++, no HIP, so that a stand-alone program can hold it under the sanitizers (tests/surface_args_main.cc), in the manner of flx_query_args.h. */
+ * plain C++, no HIP, so that a stand-alone program can hold it under the sanitizers (tests/surface_args_main.cc), in the manner of flx_query_args.h.  The range arithmetic is flx_range_args.h's. */
 #ifndef FLX_SURFACE_ARGS_H
 #define FLX_SURFACE_ARGS_H
 
 #include <stdint.h>
 
-#define FLX_SURFACE_ROW_BYTES 16u    /* a row of a plane: 4 words */
-#define FLX_SURFACE_RAY_BYTES 32u    /* a ray row: flx_rays_cast's (FLX_QUERY_ROW_BYTES) */
+#include "flx_range_args.h"
+
+#define FLX_SURFACE_ROW_BYTES 16u    /* a row of a plane: 4 words (a ray row: FLX_RAY_ROW_BYTES) */
 #define FLX_SURFACE_FIELDS_ALL 255u  /* FLX_SURFACE_HIT .. FLX_SURFACE_TPO */
 
 enum flx_surface_refusal {
@@ -57,10 +58,10 @@ static inline enum flx_surface_refusal flx_surface_frame_check(int have_params, 
 static inline enum flx_surface_refusal flx_surface_arrays_check(int have_rays, uint64_t rays, uint64_t out, uint32_t n, uint32_t fields, uint64_t *out_bytes) {
   if ((have_rays && rays == 0u) || out == 0u) return FLX_SURFACE_NULL;
   const uint64_t plane = (uint64_t)n * FLX_SURFACE_ROW_BYTES, planes = flx_surface_planes(fields);      /* n * 16 * 8 < 2^39: the product itself cannot leave 64 bits, address + bytes can */
-  const uint64_t bytes = plane * planes, ray_bytes = (uint64_t)n * FLX_SURFACE_RAY_BYTES;
+  const uint64_t bytes = plane * planes, ray_bytes = (uint64_t)n * FLX_RAY_ROW_BYTES;
   if (out_bytes) *out_bytes = bytes;
-  if (out > UINT64_MAX - bytes || (have_rays && rays > UINT64_MAX - ray_bytes)) return FLX_SURFACE_WRAPS;
-  if (have_rays && rays < out + bytes && out < rays + ray_bytes) return FLX_SURFACE_OVERLAP;
+  if (flx_range_wraps(out, bytes) || (have_rays && flx_range_wraps(rays, ray_bytes))) return FLX_SURFACE_WRAPS;
+  if (have_rays && flx_ranges_overlap(rays, ray_bytes, out, bytes)) return FLX_SURFACE_OVERLAP;
   return FLX_SURFACE_ARGS_OK;
 }
 
