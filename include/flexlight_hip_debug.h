@@ -436,6 +436,63 @@ flx_status flx_rays_history_reset(flx_context *ctx, int history /* -1: all of th
 /* The last temporal ray image (zeros if none): out[0] its slabs, [1] the rays of a full slab, [2] N, [3] the history, [4] n, [5] samples, [6] the ring's head after
  * the call, [7] 1 if the temporal pass ran inside the planes kernel.  It waits for nothing. */
 flx_status flx_debug_last_ray_temporal(flx_context *ctx, uint32_t out[8]);
+/* CAMERAS: the rays of a camera made ON THE DEVICE, so that a ray image needs no rays from the host — 32 bytes a pixel that would otherwise be built by the caller
+ * and cross the bus for every image.  Five projections; the arithmetic is include/flx_camera.h's, float32 with one rounding per operation, shared by the kernel
+ * (csrc/flx_camera.hip: k_camera_rays) and by a CPU reference, so rows are defined bit for bit.
+ * Pixel (px, row) of a width x height image, row 0 on top, py = height - 1 - row:
+ *   sx = ((float)px + (0.5f + jitter[0])) / (float)width * 2.0f - 1.0f, sy likewise from py, height and jitter[1];
+ *   THE ROW'S NOISE WORDS (3 and 7) ARE THE SAME EXPRESSIONS WITH ZERO JITTER: the pixel's NDC as a frame computes it, so a camera's rays draw a frame's random
+ *   numbers whatever the jitter.  world(l) = (right * l.x + up * l.y) + forward * l.z per component; every direction ends in normalize3, v / sqrt((x x + y y) + z z).
+ *   PINHOLE       d = normalize3(V^-1 (sx, sy, 1)), V = basis = flx_frame_params.view_matrix, inverted once on the host (flx_invert3x3); origin = position.  With
+ *                 zero jitter these are the bits of a frame's primary ray.
+ *   PANORAMA      equirectangular: lon = sx * (0.5f * extent[0]), lat = sy * (0.5f * extent[1]); l = (sin lon cos lat, sin lat, cos lon cos lat); d = normalize3(world(l))
+ *   FISHEYE       equidistant: q = sqrt(sx sx + sy sy), theta = q * (0.5f * extent[0]); l = (sin theta * sx / q, sin theta * sy / q, cos theta), (0, 0, 1) at q == 0;
+ *                 d = normalize3(world(l)).  NOT MASKED: the corners beyond the image circle continue the mapping (q up to sqrt 2); mask q > 1 yourself.
+ *   ORTHOGRAPHIC  origin = position + (right * (sx * (0.5f * extent[0])) + up * (sy * (0.5f * extent[1]))); d = normalize3(forward)
+ *   CUBE_FACE     l = F + R sx + U sy with the face's axes below, whose entries are 0 or +-1: l's components are exactly +-1, +-sx, +-sy, and the shared edge of two
+ *                 faces gets the same l from both.  d = normalize3(world(l)).
+ *                   face 0 (+x): F (1,0,0) R (0,0,-1) U (0,1,0)     1 (-x): F (-1,0,0) R (0,0,1) U (0,1,0)     2 (+y): F (0,1,0) R (1,0,0) U (0,0,-1)
+ *                   face 3 (-y): F (0,-1,0) R (1,0,0) U (0,0,1)     4 (+z): F (0,0,1) R (1,0,0) U (0,1,0)      5 (-z): F (0,0,-1) R (-1,0,0) U (0,1,0)
+ * flx_camera_rays_device writes ray rows (flx_rays_trace's: origin, noise x, direction, noise y) for n_cameras cameras of one image size in ONE launch — a stereo
+ * pair, a probe's six faces, a mixed batch: camera c's rows start at row c * w * h.  region = { x0, y0, w, h } of the image, or NULL for all of it: only the
+ * region's rays are written, in row order, and they are BIT FOR BIT the rows of the same pixels of the whole image (sx, sy and the noise words are always the full
+ * image's).  It needs a context for its device and stream and NO SCENE.  Ordering is flx_rays_cast_device's: enqueued on the context's stream with no wait of
+ * the host, behind a frame server's launch.  Trace, planes and surface rows of a camera's rays are two calls on the device: this one, then flx_rays_trace_device,
+ * flx_rays_planes_device or flx_rays_surface_device with producer_stream NULL.  flx_camera_rays is the same into host memory, staged through memory the context
+ * owns; it waits and copies out.
+ * flx_camera_image[_temporal]_device: ONE camera's rays into a buffer the context owns (grown, never shrunk), then exactly what flx_rays_image_device /
+ * flx_rays_image_temporal_device run on width * height rays: the image is theirs bit for bit, and ordering, the frame server, slabs, histories and refusals
+ * are theirs word for word.  The host variants stage the image only.
+ * Refusals, each FLX_ERR_INVALID with a message of its own and nothing enqueued: cameras NULL or n_cameras 0; width or height 0; n_cameras * width * height of
+ * 2^32 or more; a region that is empty or leaves the image; a projection that is none of the five; a face outside 0 .. 5; a field (position, basis, extent,
+ * jitter) that is not finite; a jitter outside [-0.5, 0.5]; an extent <= 0 where the projection reads it; an output that is NULL, not memory of the context's
+ * device, not 16-byte aligned or too short.  The image calls return FLX_ERR_NO_SCENE before a scene and transforms are up and refuse everything
+ * flx_rays_image[_temporal] refuses.  A group has no such call, as it traces no rays. */
+#define FLX_CAMERA_PINHOLE      0
+#define FLX_CAMERA_PANORAMA     1
+#define FLX_CAMERA_FISHEYE      2
+#define FLX_CAMERA_ORTHOGRAPHIC 3
+#define FLX_CAMERA_CUBE_FACE    4
+typedef struct flx_camera {
+  int32_t projection;   /* FLX_CAMERA_* */
+  int32_t face;         /* CUBE_FACE: 0 .. 5 = +x -x +y -y +z -z; 0 otherwise */
+  float position[3];
+  float basis[9];       /* PINHOLE: the frame params' view_matrix, used exactly as a frame uses it.  Others: rows right, up, forward in world space, used as given
+                           (neither normalised nor orthogonalised) */
+  float extent[2];      /* PANORAMA: the horizontal and vertical angle covered (rad; 2 pi, pi = the sphere).  FISHEYE: [0] the full field of view across the
+                           image's width (rad), [1] unused.  ORTHOGRAPHIC: width, height of the window in world units.  PINHOLE, CUBE_FACE: unused */
+  float jitter[2];      /* sub-pixel offset in pixels, each in [-0.5, 0.5] */
+} flx_camera;
+flx_status flx_camera_rays_device(flx_context *ctx, const flx_camera *cameras /* host */, uint32_t n_cameras, uint32_t width, uint32_t height,
+                                  const uint32_t region[4] /* x0, y0, w, h, or NULL */, void *d_rays /* n_cameras * w * h * 8 floats, on ctx's device */);
+flx_status flx_camera_rays(flx_context *ctx, const flx_camera *cameras, uint32_t n_cameras, uint32_t width, uint32_t height, const uint32_t region[4], float *rays);      /* host array out */
+flx_status flx_camera_image_device(flx_context *ctx, const flx_trace_params *params, int hdr, const flx_camera *camera, uint32_t width, uint32_t height,
+                                   void *d_out_rgba /* float4[height][width] */);
+flx_status flx_camera_image(flx_context *ctx, const flx_trace_params *params, int hdr, const flx_camera *camera, uint32_t width, uint32_t height, float *out_rgba);      /* host array out */
+flx_status flx_camera_image_temporal_device(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal, const flx_camera *camera, uint32_t width,
+                                            uint32_t height, void *d_out_rgba /* float4[height][width] */);
+flx_status flx_camera_image_temporal(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal, const flx_camera *camera, uint32_t width,
+                                     uint32_t height, float *out_rgba);      /* host array out */
 /* SURFACE ROWS: what the surface is where a ray first hits — the question between "where does it hit" (flx_rays_cast) and "what radiance comes back"
  * (flx_rays_trace, flx_render).  The planes (AOVs) a denoiser of the caller's own, compositing or the shading of a hybrid renderer needs beside the noisy radiance:
  * position, geometric normal, shading normal, texture coordinates, and albedo, RME and TPO with the atlases applied.  They are the first thing lightTrace computes

@@ -15,6 +15,10 @@
  *   --temporal N (with --filter WxH): the image is accumulated over time (flx_rays_image_temporal) at depth N: traceImage(..., { temporal: true }) is called
  *   --frames F times (by default 1) on history --history H (0) and rows.bin holds the F images one after the other; --chain 0: without the denoise chain;
  *   --reset K: renderer.resetRayHistory(H) before call K.  The seeds are the renderer's own (its counter % N) unless --seed is given.
+ *   --camera JSON (with --filter WxH, instead of --rays): a camera description ({} is the engine's own pinhole camera; { "projection": "panorama", ... }:
+ *   renderer.cameraOf): traceImage is given the description and the rays are made on the device (flx_camera_image[_temporal]).  --via-rays 1: the rays come back
+ *   through renderer.cameraRays() and go in again as a Float32Array, the path the description saves.  --rays-out FILE: cameraRays' rows, float32[8 n].  The camera
+ *   the library was given is printed as "camera".
  */
 const fs = require('fs');
 const path = require('path');
@@ -48,8 +52,16 @@ const sum = a => { let s = 0; for (let i = 0; i < a.length; i++) if (a[i] === a[
   const renderer = engine.renderer;
   if (replay) renderer.scene = replay;
   await renderer.updateScene();
-  const bytes = fs.readFileSync(opt('--rays'));
-  const rays = new Float32Array(bytes.buffer.slice(bytes.byteOffset, bytes.byteOffset + bytes.byteLength));
+  const filterSize = /^(\d+)x(\d+)$/.exec(opt('--filter', ''));
+  const description = opt('--camera') !== undefined ? JSON.parse(opt('--camera')) : null;
+  if (description && !filterSize) throw new Error('--camera takes --filter WxH');
+  const camera = description ? renderer.cameraOf(description, Number(filterSize[1]), Number(filterSize[2])) : null;
+  const viaRays = description && Number(opt('--via-rays', 0)) !== 0;
+  const madeRays = description && (viaRays || opt('--rays-out') !== undefined) ? renderer.cameraRays(description, Number(filterSize[1]), Number(filterSize[2])) : null;
+  if (madeRays && opt('--rays-out') !== undefined) fs.writeFileSync(opt('--rays-out'), Buffer.from(madeRays.buffer, madeRays.byteOffset, madeRays.byteLength));
+  const bytes = description ? null : fs.readFileSync(opt('--rays'));
+  const rays = description ? (viaRays ? madeRays : description) : new Float32Array(bytes.buffer.slice(bytes.byteOffset, bytes.byteOffset + bytes.byteLength));
+  const count = description ? Number(filterSize[1]) * Number(filterSize[2]) : rays.length / 8;
   const options = {};
   if (opt('--samples') !== undefined) options.samples = Number(opt('--samples'));
   if (opt('--bounces') !== undefined) options.maxReflections = Number(opt('--bounces'));
@@ -72,13 +84,13 @@ const sum = a => { let s = 0; for (let i = 0; i < a.length; i++) if (a[i] === a[
         images.push(Buffer.from(image.radiance.buffer, image.radiance.byteOffset, image.radiance.byteLength));
       }
       fs.writeFileSync(opt('--out', 'rows.bin'), Buffer.concat(images));
-      console.log(JSON.stringify({ rays: rays.length / 8, width: Number(size[1]), height: Number(size[2]), frames, temporal: options.temporalSamples, history: options.history, chain: options.filter, params: renderer.traceParams(options), hdr: options.hdr === undefined ? !!engine.config.hdr : options.hdr, renderer: renderer.type }));
+      console.log(JSON.stringify({ rays: count, camera, width: Number(size[1]), height: Number(size[2]), frames, temporal: options.temporalSamples, history: options.history, chain: options.filter, params: renderer.traceParams(options), hdr: options.hdr === undefined ? !!engine.config.hdr : options.hdr, renderer: renderer.type }));
       renderer.halt();
       return;
     }
     const image = renderer.traceImage(rays, Number(size[1]), Number(size[2]), options);
     fs.writeFileSync(opt('--out', 'rows.bin'), Buffer.from(image.radiance.buffer, image.radiance.byteOffset, image.radiance.byteLength));
-    console.log(JSON.stringify({ rays: rays.length / 8, width: image.width, height: image.height, params: renderer.traceParams(options), hdr: options.hdr === undefined ? !!engine.config.hdr : options.hdr, renderer: renderer.type }));
+    console.log(JSON.stringify({ rays: count, camera, width: image.width, height: image.height, params: renderer.traceParams(options), hdr: options.hdr === undefined ? !!engine.config.hdr : options.hdr, renderer: renderer.type }));
     renderer.halt();
     return;
   }

@@ -285,6 +285,8 @@ struct flx_context {
    * at.head; allocated on first use, released by flx_rays_history_reset.  at.n == 0: no history.  The frames' ring above and these never touch each other.  What the last call ran (flx_debug_last_ray_temporal) */
   struct RayHistory { DeviceBuffer<uint32_t> rings; flx_ray_history_state at = { 0u, 0u, 0, 0 }; } ray_history[FLX_RAY_TEMPORAL_HISTORIES];
   struct RayTemporalLaunch { uint32_t slabs = 0, slab = 0, depth = 0, history = 0, n = 0, samples = 0, head = 0, fused = 0; } last_ray_temporal;
+  /* cameras (flx_camera.hip): the rays flx_camera_image[_temporal]_device makes for the image calls that follow on the same stream, grown and never shrunk */
+  DeviceBuffer<float4> d_camera_rays;
   /* uploads: pinned staging ring */
   PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};

@@ -39,6 +39,7 @@ EXPORTS = [
     "flx_rays_surface_device", "flx_rays_surface", "flx_frame_surface_device", "flx_frame_surface", "flx_debug_last_surface",
     "flx_rays_planes_device", "flx_rays_planes", "flx_rays_image_device", "flx_rays_image", "flx_debug_last_ray_planes",
     "flx_rays_image_temporal_device", "flx_rays_image_temporal", "flx_rays_history_reset", "flx_debug_last_ray_temporal",
+    "flx_camera_rays_device", "flx_camera_rays", "flx_camera_image_device", "flx_camera_image", "flx_camera_image_temporal_device", "flx_camera_image_temporal",
     "flx_textures_upload", "flx_textures_upload_device", "flx_texture_update", "flx_texture_update_device", "flx_group_textures_upload", "flx_group_texture_update",
     "flx_debug_atlas_read",
 ]
@@ -91,6 +92,68 @@ class RayTemporal(C.Structure):
         super().__init__(int(history), int(temporal_samples), int(use_filter), int(hdr))
 
 
+CAMERA_PINHOLE, CAMERA_PANORAMA, CAMERA_FISHEYE, CAMERA_ORTHOGRAPHIC, CAMERA_CUBE_FACE = 0, 1, 2, 3, 4      # FLX_CAMERA_* of include/flexlight_hip_debug.h
+CAMERA_NAMES = ("pinhole", "panorama", "fisheye", "orthographic", "cube_face")
+IDENTITY_BASIS = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)      # right +x, up +y, forward +z
+
+
+class Camera(C.Structure):
+    """flx_camera of include/flexlight_hip_debug.h: a camera whose rays the device makes (camera_rays, camera_image).  basis: for the pinhole the frame params'
+    view_matrix; for the others the rows right, up, forward in world space, used as given.  jitter: a sub-pixel offset in pixels, each in [-0.5, 0.5]."""
+    _fields_ = [("projection", C.c_int32), ("face", C.c_int32), ("position", C.c_float * 3), ("basis", C.c_float * 9), ("extent", C.c_float * 2),
+                ("jitter", C.c_float * 2)]
+
+    def __init__(self, projection=CAMERA_PINHOLE, position=(0.0, 0.0, 0.0), basis=IDENTITY_BASIS, extent=(0.0, 0.0), jitter=(0.0, 0.0), face=0):
+        basis = np.asarray(basis, np.float32).reshape(9)
+        super().__init__(int(projection), int(face), (C.c_float * 3)(*[float(x) for x in position]), (C.c_float * 9)(*[float(x) for x in basis]),
+                         (C.c_float * 2)(*[float(x) for x in extent]), (C.c_float * 2)(*[float(x) for x in jitter]))
+
+    @classmethod
+    def pinhole(cls, frame_params, jitter=(0.0, 0.0)):
+        """the camera of a frame: its position and view matrix, used exactly as the frame uses them"""
+        return cls(CAMERA_PINHOLE, tuple(frame_params.camera), tuple(frame_params.view_matrix), jitter=jitter)
+
+    @classmethod
+    def panorama(cls, position, basis=IDENTITY_BASIS, horizontal=2.0 * np.pi, vertical=np.pi, jitter=(0.0, 0.0)):
+        """equirectangular: the angles covered in radians, by default the whole sphere"""
+        return cls(CAMERA_PANORAMA, position, basis, (horizontal, vertical), jitter)
+
+    @classmethod
+    def fisheye(cls, position, basis=IDENTITY_BASIS, fov=np.pi, jitter=(0.0, 0.0)):
+        """equidistant: fov the full field of view across the image's width in radians; not masked outside the image circle"""
+        return cls(CAMERA_FISHEYE, position, basis, (fov, 0.0), jitter)
+
+    @classmethod
+    def orthographic(cls, position, basis=IDENTITY_BASIS, width=1.0, height=1.0, jitter=(0.0, 0.0)):
+        """parallel rays along forward from a window of width x height world units around position"""
+        return cls(CAMERA_ORTHOGRAPHIC, position, basis, (width, height), jitter)
+
+    @classmethod
+    def cube_face(cls, position, face, basis=IDENTITY_BASIS, jitter=(0.0, 0.0)):
+        """one face of a cube map: face 0 .. 5 = +x -x +y -y +z -z in the basis' axes, 90 degrees each way"""
+        return cls(CAMERA_CUBE_FACE, position, basis, (0.0, 0.0), jitter, face)
+
+
+def _cameras(cameras, call):
+    """a Camera or a sequence of them -> (the flx_camera array or None, count)"""
+    if isinstance(cameras, Camera):
+        cameras = [cameras]
+    if cameras is None:
+        return None, 0
+    cameras = list(cameras)
+    if any(not isinstance(c, Camera) for c in cameras):
+        raise TypeError("%s: cameras is a Camera or a sequence of them" % call)
+    return (Camera * max(1, len(cameras)))(*cameras), len(cameras)
+
+
+def _region(region, width, height):
+    """region of camera_rays (x0, y0, w, h) or None -> (the uint32[4] or None, rows a camera)"""
+    if region is None:
+        return None, int(width) * int(height)
+    x0, y0, w, h = [int(v) for v in region]
+    return (C.c_uint32 * 4)(x0, y0, w, h), w * h
+
+
 class Image(C.Structure):
     """flx_image of include/flexlight_hip_debug.h: a source image of upload_textures / update_texture, tight rows"""
     _fields_ = [("pixels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32)]
@@ -137,6 +200,12 @@ def _load():
         "flx_rays_image_temporal_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(RayTemporal), vp, u32, u32, vp, vp]),
         "flx_rays_image_temporal": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(RayTemporal), fp, u32, u32, fp]),
         "flx_rays_history_reset": (C.c_int, [vp, C.c_int]),
+        "flx_camera_rays_device": (C.c_int, [vp, C.POINTER(Camera), u32, u32, u32, C.POINTER(u32), vp]),
+        "flx_camera_rays": (C.c_int, [vp, C.POINTER(Camera), u32, u32, u32, C.POINTER(u32), fp]),
+        "flx_camera_image_device": (C.c_int, [vp, C.POINTER(TraceParams), C.c_int, C.POINTER(Camera), u32, u32, vp]),
+        "flx_camera_image": (C.c_int, [vp, C.POINTER(TraceParams), C.c_int, C.POINTER(Camera), u32, u32, fp]),
+        "flx_camera_image_temporal_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(RayTemporal), C.POINTER(Camera), u32, u32, vp]),
+        "flx_camera_image_temporal": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(RayTemporal), C.POINTER(Camera), u32, u32, fp]),
         "flx_debug_last_ray_temporal": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_textures_upload": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32]),
         "flx_textures_upload_device": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32, vp]),
@@ -847,6 +916,84 @@ class Context:
         out = (C.c_uint32 * 8)()
         self._check(LIB.flx_debug_last_ray_temporal(self._h, out), "flx_debug_last_ray_temporal")
         return dict(zip(("slabs", "slab", "depth", "history", "n", "samples", "head", "fused"), list(out)))
+
+    # -- cameras: rays made on the device ---------------------------------------------------------------
+    def camera_rays_device(self, cameras, width, height, region=None, out=None):
+        """flx_camera_rays_device: the rays of a Camera (or of a sequence of them, all of one image size) made on the device.  region: (x0, y0, w, h) of the
+        image, or None for all of it; out: None (a new float32 tensor [cameras * w * h, 8], camera c's rows from row c * w * h, image order, row 0 on top), such a
+        tensor to write into, or an address.  Needs no scene.  Returns the ray rows ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE: the *_device ray calls
+        take them with stream=None; sync() before they are read on another stream."""
+        arr, n = _cameras(cameras, "camera_rays_device")
+        reg, rows = _region(region, width, height)
+        if out is None:
+            import torch
+            out = torch.empty((max(0, n * rows), 8), dtype=torch.float32, device="cuda:%d" % self._device)
+        o = self._device_out(out, n * rows * 32, "camera_rays_device", "out")
+        self._check(LIB.flx_camera_rays_device(self._h, arr, n, int(width), int(height), reg, C.c_void_p(o)), "flx_camera_rays_device")
+        return out
+
+    def camera_rays(self, cameras, width, height, region=None):
+        """flx_camera_rays: the same into host memory -> float32 [cameras * w * h, 8], complete"""
+        arr, n = _cameras(cameras, "camera_rays")
+        reg, rows = _region(region, width, height)
+        out = np.zeros((max(0, n * rows), 8), np.float32)
+        self._check(LIB.flx_camera_rays(self._h, arr, n, int(width), int(height), reg, _fp(out)), "flx_camera_rays")
+        return out
+
+    def camera_image_device(self, camera, width, height, params, hdr=True, out=None):
+        """flx_camera_image_device: a Camera's image traced and denoised with no rays from the host — ray_image_device on the rays the device makes for it.  out:
+        None (a new float32 tensor [height, width, 4]), such a tensor to write into, or an address.  Returns the image ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET
+        COMPLETE."""
+        if params is not None and not isinstance(params, TraceParams):
+            raise TypeError("camera_image_device: params is a TraceParams")
+        if camera is not None and not isinstance(camera, Camera):
+            raise TypeError("camera_image_device: camera is a Camera")
+        width, height = int(width), int(height)
+        if out is None:
+            import torch
+            out = torch.empty((height, width, 4), dtype=torch.float32, device="cuda:%d" % self._device)
+        o = self._device_out(out, width * height * 16, "camera_image_device", "out")
+        self._check(LIB.flx_camera_image_device(self._h, C.byref(params) if params is not None else None, int(bool(hdr)), C.byref(camera) if camera is not None else None,
+                                                width, height, C.c_void_p(o)), "flx_camera_image_device")
+        return out
+
+    def camera_image(self, camera, width, height, params, hdr=True):
+        """flx_camera_image: the same -> the denoised image float32 [height, width, 4] in host memory, complete"""
+        if camera is not None and not isinstance(camera, Camera):
+            raise TypeError("camera_image: camera is a Camera")
+        width, height = int(width), int(height)
+        out = np.zeros((height, width, 4), np.float32)
+        self._check(LIB.flx_camera_image(self._h, C.byref(params) if params is not None else None, int(bool(hdr)), C.byref(camera) if camera is not None else None, width,
+                                         height, _fp(out)), "flx_camera_image")
+        return out
+
+    def camera_image_temporal_device(self, camera, width, height, trace_params, temporal, out=None):
+        """flx_camera_image_temporal_device: a Camera's image accumulated over the history temporal.history (RayTemporal) — rays_image_temporal(device=True) on the
+        rays the device makes for it.  Returns the image ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        if trace_params is not None and not isinstance(trace_params, TraceParams):
+            raise TypeError("camera_image_temporal_device: trace_params is a TraceParams")
+        if temporal is not None and not isinstance(temporal, RayTemporal):
+            raise TypeError("camera_image_temporal_device: temporal is a RayTemporal")
+        if camera is not None and not isinstance(camera, Camera):
+            raise TypeError("camera_image_temporal_device: camera is a Camera")
+        width, height = int(width), int(height)
+        if out is None:
+            import torch
+            out = torch.empty((height, width, 4), dtype=torch.float32, device="cuda:%d" % self._device)
+        o = self._device_out(out, width * height * 16, "camera_image_temporal_device", "out")
+        self._check(LIB.flx_camera_image_temporal_device(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(temporal) if temporal is not None else None,
+                                                         C.byref(camera) if camera is not None else None, width, height, C.c_void_p(o)), "flx_camera_image_temporal_device")
+        return out
+
+    def camera_image_temporal(self, camera, width, height, trace_params, temporal):
+        """flx_camera_image_temporal: the same -> the image float32 [height, width, 4] in host memory, complete"""
+        if camera is not None and not isinstance(camera, Camera):
+            raise TypeError("camera_image_temporal: camera is a Camera")
+        width, height = int(width), int(height)
+        out = np.zeros((height, width, 4), np.float32)
+        self._check(LIB.flx_camera_image_temporal(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(temporal) if temporal is not None else None,
+                                                  C.byref(camera) if camera is not None else None, width, height, _fp(out)), "flx_camera_image_temporal")
+        return out
 
     # -- surface rows -------------------------------------------------------------------------------
     def _surface_out(self, out, n, fields, call):

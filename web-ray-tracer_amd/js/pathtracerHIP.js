@@ -61,6 +61,11 @@ function traceRaysOn (context, rays, params) {
 /* The planes of a surface call (flx_rays_surface, flx_frame_surface: include/flexlight_hip_debug.h "surface rows") as typed arrays over the buffer the library
  * wrote: per plane asked for a Float32Array of 4 floats a row — hit, position, geometryNormal, normal, uv, albedo, rme, tpo, in that bit order of `fields` — and
  * the two integer words as arrays of their own: entry (word 3 of hit, -1: none) and transform (word 2 of uv is 2 x the transform number). */
+/* the projections of a camera description, in the order of FLX_CAMERA_* (include/flexlight_hip_debug.h "cameras") */
+const CAMERA_PROJECTIONS = ['pinhole', 'panorama', 'fisheye', 'orthographic', 'cubeFace'];
+/* a camera description: a plain object (not the Float32Array of rays the same argument may be) */
+function isCameraDescription (x) { return x !== null && typeof x === 'object' && !ArrayBuffer.isView(x) && !Array.isArray(x); }
+
 const SURFACE = { HIT: 1, POSITION: 2, GEOMETRY_NORMAL: 4, NORMAL: 8, UV: 16, ALBEDO: 32, RME: 64, TPO: 128, ALL: 255 };
 const SURFACE_PLANES = ['hit', 'position', 'geometryNormal', 'normal', 'uv', 'albedo', 'rme', 'tpo'];
 function unpackSurface (buffer, n, fields) {
@@ -310,6 +315,9 @@ class PathTracerHIP {
    * them in image order, row 0 on top.  options: traceRays' plus hdr (by default config.hdr), the chain's tone map.  Per ray the five filter planes are what a frame
    * with config.filter writes for a pixel (the samples run in order on one state; a miss is zeros), and the chain over them is the frame's.  Returns { width,
    * height, radiance: Float32Array(4 n) }.  It waits for the answer; frames in flight finish unchanged.
+   * FROM A CAMERA: rays may be a camera description instead (cameraOf: { projection: 'panorama', position, basis, extent, jitter, face }; {} is the engine's own
+   * pinhole camera): the rays are made on the device (flx_camera_image) and NOTHING BUT THE IMAGE crosses the bus.  The image is, byte for byte, that of
+   * traceImage(cameraRays(description, width, height), width, height, options); options.temporal works the same way.
    * OVER TIME: with options.temporal the image is accumulated over one of the context's 8 ray-image histories (flx_rays_image_temporal), as a frame is with
    * config.temporal: options { temporal: true, history = 0, temporalSamples = config.temporalSamples, filter = true, randomSeed }.  The same width * height rays in
    * the same order are traced again call after call; a ray whose first hit moved starts over.  The renderer keeps a frame counter per history and passes
@@ -317,9 +325,12 @@ class PathTracerHIP {
    * with a change of size or N, as the history does.  Without the filter the temporal pass' colour is returned. */
   traceImage (rays, width, height, options) {
     if (this._devices) throw new Error('traceImage: one GPU only (a group of GPUs traces no rays)');
-    if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('traceImage: rays is a Float32Array of 8 floats per ray');
-    if (!Number.isInteger(width) || !Number.isInteger(height) || width < 0 || height < 0 || rays.length / 8 !== width * height) {
-      throw new RangeError('traceImage: rays is width * height rays in image order');
+    const camera = isCameraDescription(rays) ? this.cameraOf(rays, width, height, 'traceImage') : null;      // the rays are made on the device: none cross the bus
+    if (!camera) {
+      if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('traceImage: rays is a Float32Array of 8 floats per ray, or a camera description');
+      if (!Number.isInteger(width) || !Number.isInteger(height) || width < 0 || height < 0 || rays.length / 8 !== width * height) {
+        throw new RangeError('traceImage: rays is width * height rays in image order');
+      }
     }
     this._uploadFrameState();
     const hdr = options && options.hdr !== undefined ? !!options.hdr : !!this.config.hdr;
@@ -334,12 +345,55 @@ class PathTracerHIP {
       const params = this.traceParams(options);
       if (options.randomSeed === undefined) params.randomSeed = h.counter % depth;
       const filter = options.filter === undefined ? true : !!options.filter;
-      const image = native().rayImageTemporal(this._context(), rays, width, height, params, { history, temporalSamples, filter, hdr });
+      const over = { history, temporalSamples, filter, hdr };
+      const image = camera ? native().cameraImageTemporal(this._context(), camera, width, height, params, over) : native().rayImageTemporal(this._context(), rays, width, height, params, over);
       h.counter++;
       return { width, height, radiance: new Float32Array(image) };
     }
-    const image = native().rayImage(this._context(), rays, width, height, this.traceParams(options), hdr);
+    const image = camera ? native().cameraImage(this._context(), camera, width, height, this.traceParams(options), hdr) : native().rayImage(this._context(), rays, width, height, this.traceParams(options), hdr);
     return { width, height, radiance: new Float32Array(image) };
+  }
+
+  /* The rays of a camera, made on the device (flx_camera_rays, include/flexlight_hip_debug.h "cameras"): traceRays' rows, w * h of them in image order, row 0 on
+   * top, whose noise words are the pixels' positions as a frame has them.  camera: a description (cameraOf); region: [x0, y0, w, h] of the image, by default all
+   * of it — a region's rows are the whole image's rows of those pixels.  Needs no scene.  Returns a Float32Array of 8 floats per ray: what castRays, traceRays,
+   * surfaceRays and traceImage take.  (traceImage takes the description itself: then no rays come back to the host at all.) */
+  cameraRays (camera, width, height, region) {
+    if (this._devices) throw new Error('cameraRays: one GPU only (a group of GPUs traces no rays)');
+    if (!isCameraDescription(camera)) throw new TypeError('cameraRays: camera is a camera description');
+    if (region !== undefined && region !== null && !(Array.isArray(region) && region.length === 4)) throw new TypeError('cameraRays: region is [x0, y0, w, h]');
+    return new Float32Array(native().cameraRays(this._context(), this.cameraOf(camera, width, height, 'cameraRays'), width, height, region || null));
+  }
+
+  /* A camera description -> the library's flx_camera.  { projection, position, basis, extent, jitter, face }, all optional:
+   *   projection  'pinhole' (the default) | 'panorama' | 'fisheye' | 'orthographic' | 'cubeFace'
+   *   position    [x, y, z], by default the engine's camera's
+   *   basis       9 numbers.  The pinhole: a frame's view matrix, BY DEFAULT sceneFile.buildViewMatrix(this.camera, width, height) — {} is the engine's own camera, and
+   *               its image is the frame's.  The others: rows right, up, forward in world space, used as given; by default the identity.
+   *   extent      panorama: [horizontal, vertical] angle in radians (by default the sphere, [2 pi, pi]); fisheye: [field of view across the width] (by default pi);
+   *               orthographic: [width, height] of the window in world units (by default [1, 1])
+   *   jitter      [x, y] sub-pixel offset in pixels, each in [-0.5, 0.5]; by default none
+   *   face        cubeFace: 0 .. 5 = +x -x +y -y +z -z */
+  cameraOf (description, width, height, call) {
+    const d = description, who = call || 'cameraOf';
+    const projection = d.projection === undefined ? 'pinhole' : d.projection;
+    const code = CAMERA_PROJECTIONS.indexOf(projection);
+    if (code < 0) throw new RangeError(who + ': projection is one of ' + CAMERA_PROJECTIONS.join(', '));
+    const numbers = (v, n, name) => {
+      const a = Array.from(v);
+      if (a.length !== n || a.some(x => typeof x !== 'number')) throw new TypeError(who + ': ' + name + ' is ' + n + ' numbers');
+      return a;
+    };
+    const defaults = [[0, 0], [2 * Math.PI, Math.PI], [Math.PI, 0], [1, 1], [0, 0]][code];
+    const extent = d.extent === undefined ? defaults : Array.from(d.extent).concat(defaults.slice(Array.from(d.extent).length));
+    return {
+      projection: code,
+      face: d.face === undefined ? 0 : d.face,
+      position: d.position === undefined ? [this.camera.x, this.camera.y, this.camera.z] : numbers(d.position, 3, 'position'),
+      basis: d.basis !== undefined ? numbers(d.basis, 9, 'basis') : code === 0 ? Array.from(sceneFile.buildViewMatrix(this.camera, width, height)) : [1, 0, 0, 0, 1, 0, 0, 0, 1],
+      extent: numbers(extent, 2, 'extent'),
+      jitter: d.jitter === undefined ? [0, 0] : numbers(d.jitter, 2, 'jitter')
+    };
   }
 
   /* A ray-image history of traceImage's (by default all of them) starts afresh with the next image: its frame counter and, where a context is up, the library's

@@ -410,6 +410,28 @@ static napi_value RayImage(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+/* a temporal image's { history, temporalSamples, filter, hdr } -> flx_ray_temporal; `call`: the JavaScript name, for the messages */
+static bool read_ray_temporal(napi_env env, napi_value o, const char *call, flx_ray_temporal *t) {
+  memset(t, 0, sizeof *t);
+  double d = 0;
+  auto int32 = [&](const char *key, int32_t *out) {
+    if (!num(env, o, key, &d)) return false;
+    if (!(d >= -2147483648.0 && d <= 2147483647.0)) { napi_throw_range_error(env, nullptr, (std::string(call) + ": " + key + " is not a number an int32 holds").c_str()); return false; }
+    *out = (int32_t)d;
+    return true;
+  };
+  if (!int32("history", &t->history) || !int32("temporalSamples", &t->temporal_samples)) return false;
+  napi_value v;
+  bool filter = true, hdr = true;
+  if (napi_get_named_property(env, o, "filter", &v) != napi_ok || napi_get_value_bool(env, v, &filter) != napi_ok ||
+      napi_get_named_property(env, o, "hdr", &v) != napi_ok || napi_get_value_bool(env, v, &hdr) != napi_ok) {
+    napi_throw_type_error(env, nullptr, (std::string(call) + ": filter and hdr are booleans").c_str());
+    return false;
+  }
+  t->use_filter = filter ? 1 : 0; t->hdr = hdr ? 1 : 0;
+  return true;
+}
+
 /* rayImageTemporal(handle, rays Float32Array(8 width height), width, height, params (traceRays'), { history, temporalSamples, filter, hdr }) ->
  * ArrayBuffer(16 width height): flx_rays_image_temporal, the ray image accumulated over that history of the context's, denoised where filter is true */
 static napi_value RayImageTemporal(napi_env env, napi_callback_info info) {
@@ -427,28 +449,106 @@ static napi_value RayImageTemporal(napi_env env, napi_callback_info info) {
   flx_trace_params p;
   if (!read_trace_params(env, argv[4], "rayImageTemporal", &p)) return nullptr;
   flx_ray_temporal t;
-  memset(&t, 0, sizeof t);
-  double d = 0;
-  auto int32 = [&](const char *key, int32_t *out) {
-    if (!num(env, argv[5], key, &d)) return false;
-    if (!(d >= -2147483648.0 && d <= 2147483647.0)) { napi_throw_range_error(env, nullptr, (std::string("rayImageTemporal: ") + key + " is not a number an int32 holds").c_str()); return false; }
-    *out = (int32_t)d;
-    return true;
-  };
-  if (!int32("history", &t.history) || !int32("temporalSamples", &t.temporal_samples)) return nullptr;
-  napi_value v;
-  bool filter = true, hdr = true;
-  if (napi_get_named_property(env, argv[5], "filter", &v) != napi_ok || napi_get_value_bool(env, v, &filter) != napi_ok ||
-      napi_get_named_property(env, argv[5], "hdr", &v) != napi_ok || napi_get_value_bool(env, v, &hdr) != napi_ok) {
-    napi_throw_type_error(env, nullptr, "rayImageTemporal: filter and hdr are booleans");
-    return nullptr;
-  }
-  t.use_filter = filter ? 1 : 0; t.hdr = hdr ? 1 : 0;
+  if (!read_ray_temporal(env, argv[5], "rayImageTemporal", &t)) return nullptr;
   void *image = nullptr;
   napi_value buf;
   NAPI_OK(env, napi_create_arraybuffer(env, (len / 8) * 16, &image, &buf));
   flx_status rc = flx_rays_image_temporal(ctx, &p, &t, (const float *)rays, width, height, (float *)image);
   if (rc != FLX_OK) return fail(env, ctx, "flx_rays_image_temporal", rc);
+  return buf;
+}
+
+/* a camera { projection, face, position[3], basis[9], extent[2], jitter[2] } (pathtracerHIP.js: cameraOf makes it) -> flx_camera; the library judges the values */
+static bool read_camera(napi_env env, napi_value o, const char *call, flx_camera *c) {
+  memset(c, 0, sizeof *c);
+  napi_valuetype t;
+  if (napi_typeof(env, o, &t) != napi_ok || t != napi_object) { napi_throw_type_error(env, nullptr, (std::string(call) + ": camera is an object").c_str()); return false; }
+  double d = 0;
+  auto int32 = [&](const char *key, int32_t *out) {
+    if (!num(env, o, key, &d)) return false;
+    if (!(d >= -2147483648.0 && d <= 2147483647.0)) { napi_throw_range_error(env, nullptr, (std::string(call) + ": " + key + " is not a number an int32 holds").c_str()); return false; }
+    *out = (int32_t)d;
+    return true;
+  };
+  return int32("projection", &c->projection) && int32("face", &c->face) && floats(env, o, "position", c->position, 3) && floats(env, o, "basis", c->basis, 9) &&
+         floats(env, o, "extent", c->extent, 2) && floats(env, o, "jitter", c->jitter, 2);
+}
+
+static bool image_size(napi_env env, napi_value w, napi_value h, const char *call, uint32_t *width, uint32_t *height) {
+  if (napi_get_value_uint32(env, w, width) != napi_ok || napi_get_value_uint32(env, h, height) != napi_ok) {
+    napi_throw_type_error(env, nullptr, (std::string(call) + ": width and height are numbers").c_str());
+    return false;
+  }
+  return true;
+}
+
+/* cameraRays(handle, camera, width, height, region [x0, y0, w, h] | null) -> ArrayBuffer(32 w h): flx_camera_rays, the camera's ray rows made on the device */
+static napi_value CameraRays(napi_env env, napi_callback_info info) {
+  napi_value argv[5];
+  if (!get_args(env, info, 5, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  flx_camera c; uint32_t width, height, region[4] = { 0u, 0u, 0u, 0u };
+  if (!read_camera(env, argv[1], "cameraRays", &c) || !image_size(env, argv[2], argv[3], "cameraRays", &width, &height)) return nullptr;
+  napi_valuetype t;
+  napi_typeof(env, argv[4], &t);
+  const bool whole = t == napi_null || t == napi_undefined;
+  for (uint32_t k = 0; !whole && k < 4u; k++) {
+    napi_value e;
+    if (napi_get_element(env, argv[4], k, &e) != napi_ok || napi_get_value_uint32(env, e, &region[k]) != napi_ok) {
+      napi_throw_type_error(env, nullptr, "cameraRays: region is [x0, y0, w, h] or null");
+      return nullptr;
+    }
+  }
+  /* the rows the call writes where it accepts the arguments; one row's room for whatever it refuses */
+  const uint64_t w = whole ? width : region[2], h = whole ? height : region[3];
+  const uint64_t rows = (w == 0u || h == 0u || w > width || h > height || (uint64_t)width * height > 0xffffffffull) ? 1u : w * h;
+  void *rays = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, (size_t)rows * 32u, &rays, &buf));
+  flx_status rc = flx_camera_rays(ctx, &c, 1u, width, height, whole ? nullptr : region, (float *)rays);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_camera_rays", rc);
+  return buf;
+}
+
+/* the image's room where the library accepts the size; one pixel's for whatever it refuses */
+static size_t image_bytes(uint32_t width, uint32_t height) {
+  const uint64_t pixels = (uint64_t)width * height;
+  return (size_t)((pixels == 0u || pixels > 0xffffffffull) ? 1u : pixels) * 16u;
+}
+
+/* cameraImage(handle, camera, width, height, params (traceRays'), hdr) -> ArrayBuffer(16 width height): flx_camera_image — rayImage with the rays made on the device */
+static napi_value CameraImage(napi_env env, napi_callback_info info) {
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  flx_camera c; uint32_t width, height; flx_trace_params p;
+  if (!read_camera(env, argv[1], "cameraImage", &c) || !image_size(env, argv[2], argv[3], "cameraImage", &width, &height) || !read_trace_params(env, argv[4], "cameraImage", &p)) return nullptr;
+  bool hdr = true;
+  if (napi_get_value_bool(env, argv[5], &hdr) != napi_ok) { napi_throw_type_error(env, nullptr, "cameraImage: hdr is a boolean"); return nullptr; }
+  void *image = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, image_bytes(width, height), &image, &buf));
+  flx_status rc = flx_camera_image(ctx, &p, hdr ? 1 : 0, &c, width, height, (float *)image);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_camera_image", rc);
+  return buf;
+}
+
+/* cameraImageTemporal(handle, camera, width, height, params, { history, temporalSamples, filter, hdr }) -> ArrayBuffer(16 width height): flx_camera_image_temporal */
+static napi_value CameraImageTemporal(napi_env env, napi_callback_info info) {
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  flx_camera c; uint32_t width, height; flx_trace_params p; flx_ray_temporal t;
+  if (!read_camera(env, argv[1], "cameraImageTemporal", &c) || !image_size(env, argv[2], argv[3], "cameraImageTemporal", &width, &height) ||
+      !read_trace_params(env, argv[4], "cameraImageTemporal", &p) || !read_ray_temporal(env, argv[5], "cameraImageTemporal", &t)) return nullptr;
+  void *image = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, image_bytes(width, height), &image, &buf));
+  flx_status rc = flx_camera_image_temporal(ctx, &p, &t, &c, width, height, (float *)image);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_camera_image_temporal", rc);
   return buf;
 }
 
@@ -1320,7 +1420,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas }, { "uploadTextures", UploadTextures }, { "updateTexture", UpdateTexture },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
