@@ -355,6 +355,31 @@ flx_status flx_debug_set_trace_slab(flx_context *ctx, uint32_t rays);
 /* The last traced batch (zeros if none): out[0] its slabs, [1] the rays of a full slab, [2] workgroups of the last slab's paths kernel, [3] whether its bounce walks
  * went in lockstep, [4] n, [5] samples, [6] workgroups of the last slab's first-hit launch, [7] the items a wave draws with one atomic.  It waits for nothing. */
 flx_status flx_debug_last_trace(flx_context *ctx, uint32_t out[8]);
+/* A traced batch IN FIRST-HIT ORDER: flx_rays_trace_device for rays that arrive in no useful order — reflection rays, probe rays, rays a pipeline made for itself.
+ * The rows of a batch do not depend on each other, so the library may trace a slab's rays in any order: with FLX_TRACE_ORDER_HITS it sorts each slab by the Morton
+ * code of the first hit points (include/flx_ray_key.h: the key, exactly defined; csrc/flx_rays_order.hip: bounds, keys and a stable radix sort on the device) and
+ * the paths kernel takes its rays through that order, so that a wave's 64 lanes start in one corner of the scene.  THE RADIANCE ROWS ARE flx_rays_trace_device's,
+ * BIT FOR BIT, IN THE CALLER'S ORDER; what changes is the time (profiles/rays_order.txt) and 16 bytes of scratch a ray of a slab more (at most 2^21 rays: 33 MB).
+ * order == 0 is flx_rays_trace_device itself, with the same launches.  Ordering, producer_stream, the frame server, slabs, n == 0 and the host call's staging are
+ * flx_rays_trace_device's and flx_rays_trace's, word for word.  Refusals: an unknown bit of `order` is FLX_ERR_INVALID with its own message (for any n, after the
+ * scene and the params were looked at); every other refusal is flx_rays_trace's under this call's name. */
+#define FLX_TRACE_ORDER_HITS 1u   /* trace each slab's rays in the order of their first hit points' Morton codes */
+flx_status flx_rays_trace_ordered_device(flx_context *ctx, const flx_trace_params *params, const void *d_rays /* n * 8 floats, on ctx's device */,
+                                         void *d_radiance /* n * 8 words */, uint32_t n, uint32_t order, void *producer_stream /* as flx_rays_trace_device's */);
+flx_status flx_rays_trace_ordered(flx_context *ctx, const flx_trace_params *params, const float *rays /* n * 8 floats */, void *radiance /* n * 8 words */, uint32_t n,
+                                  uint32_t order);      /* host arrays */
+/* The sort alone, for tests: order[0 .. n) <- the positions 0 .. n - 1 in ascending order of keys[], equal keys in the order given (numpy.argsort(keys,
+ * kind="stable")).  Host arrays, staged through the context's memory; it waits.  n from 1 to 2^21, the most rays of a slab; FLX_ERR_INVALID otherwise, or for a
+ * NULL array.  Needs no scene. */
+flx_status flx_debug_sort_keys(flx_context *ctx, const uint32_t *keys, uint32_t n, uint32_t *order);
+/* Bounds and keys alone, for tests: n ray rows and their FLX_RAYS_CLOSEST hit rows (of which words 0 and 3 are read) -> keys[n] and bounds[6] (lo x y z, hi x y z;
+ * unused and no numbers where no ray is live), as include/flx_ray_key.h defines them.  Host arrays, staged; it waits.  n and refusals as flx_debug_sort_keys'. */
+flx_status flx_debug_hit_keys(flx_context *ctx, const float *rays /* n * 8 floats */, const void *hits /* n * 8 words */, uint32_t n, uint32_t *keys, float bounds[6]);
+/* The last traced batch (flx_rays_trace[_device] or the ordered calls; zeros but [1] if none), set only when the whole call succeeded: out[0] whether it was
+ * ordered, [1] T, the items a sort workgroup takes, [2] the sort workgroups of its last slab, [3] the sort passes run, [4] n, [5] the live rays of its last slab
+ * (rays with a first hit at a finite point), [6] and [7] reserved, zero.  [2], [3] and [5] are zero after an unordered batch.  After an ordered batch it waits for
+ * the context's stream. */
+flx_status flx_debug_last_ray_order(flx_context *ctx, uint32_t out[8]);
 /* The denoise chain's FIVE FILTER PLANES for the caller's rays, and a ray IMAGE traced and denoised: what flx_render_planes_device and flx_render (use_filter = 1)
  * are for the pixels behind the pinhole camera, for any rays — a panorama, a fisheye or orthographic view, a stereo pair, a probe's faces, a hybrid renderer's
  * reflection buffer — at the 1 - 8 samples per ray the renderer is built for.  A ray row and flx_trace_params are flx_rays_trace's.

@@ -8,7 +8,14 @@ GPU time between two events recorded on the context's stream around each call; t
 reported as median [min .. max].  Once, outside the timed region, the rows of (a) are held against flx_render_device's frame: words 0..3 are the frame's pixel, bit
 for bit, wherever the frame's hit rule and rayTracer agree (they differ on back faces, within 2^-16 of an edge, on ties and at the near plane).  GPU box.
 
-usage: rays_trace_time.py [--out profiles/rays_trace.txt] [--repeats 15]"""
+--ordered: the three sets through flx_rays_trace_ordered_device (FLX_TRACE_ORDER_HITS: each slab's rays traced in the order of their first hit points,
+csrc/flx_rays_order.hip) beside the unordered call, the six calls in turn, and nothing else; the ordered rows are held against the unordered rows once, outside the
+timed region, all eight words.  It writes profiles/rays_order.txt: every ordered call against its unordered twin and the ordered shuffled call against the unordered
+pixel-ordered one, each with the verdict whether the difference lies outside the two calls' own min .. max.  With a library that lacks the ordered call (FLX_LIB: an
+earlier build, the control) the three unordered calls are measured alone.
+--profile-once: one pass over the calls and no report, for a run under rocprofv3 --kernel-trace --stats.
+
+usage: rays_trace_time.py [--ordered] [--profile-once] [--out profiles/rays_trace.txt] [--repeats 15]"""
 import os
 import sys
 
@@ -20,7 +27,8 @@ sys.path.insert(0, os.path.join(ROOT, "web-ray-tracer_amd"))
 from flexlight_hip import capi
 from flexlight_hip.scene_io import Scene
 
-out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "rays_trace.txt")
+ORDERED = "--ordered" in sys.argv
+out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "rays_order.txt" if ORDERED else "rays_trace.txt")
 REPEATS = int(sys.argv[sys.argv.index("--repeats") + 1]) if "--repeats" in sys.argv else 15
 WARMUP = 3
 W, H, SPP, BOUNCES = 1920, 1080, 8, 4
@@ -108,7 +116,26 @@ def frame_call(pipeline):
 
 
 calls = [("flx_rays_trace_device, " + name, (lambda d: lambda: ctx.trace_rays_device(d, t, d_out))(d)) for name, d in d_sets]
-calls += [("flx_render_device, flx_set_pipeline(ctx, 2)", frame_call(2)), ("flx_render_device, default pipeline (%s)" % (default_pipeline,), frame_call(0))]
+have_ordered = hasattr(capi.LIB, "flx_rays_trace_ordered_device")
+if ORDERED and have_ordered:
+    d_twin = torch.empty_like(d_out)
+    for name, d in d_sets:                     # once, outside the timed region: the ordered rows are the unordered rows
+        ctx.trace_rays_device(d, t, d_out)
+        ctx.trace_rays_ordered_device(d, t, d_twin)
+        ctx.sync()
+        assert torch.equal(d_out, d_twin), name
+    order_info = ctx.last_ray_order()
+    del d_twin
+    calls = [c for name, d in d_sets for c in (("flx_rays_trace_device, " + name, (lambda d: lambda: ctx.trace_rays_device(d, t, d_out))(d)),
+                                                ("flx_rays_trace_ordered_device, " + name, (lambda d: lambda: ctx.trace_rays_ordered_device(d, t, d_out))(d)))]
+elif not ORDERED:
+    calls += [("flx_render_device, flx_set_pipeline(ctx, 2)", frame_call(2)), ("flx_render_device, default pipeline (%s)" % (default_pipeline,), frame_call(0))]
+if "--profile-once" in sys.argv:
+    for name, call in calls:
+        call()
+    ctx.sync()
+    ctx.close()
+    sys.exit(0)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 ms = {name: [] for name, _ in calls}
 for k in range(WARMUP + REPEATS):
@@ -127,6 +154,25 @@ lines = ["traced ray batches on the dragon scene (tests/golden/ref_dragon.flxs.g
 med = {name: float(np.median(v)) for name, v in ms.items()}
 for name, _ in calls:
     lines.append("  %-52s %8.3f ms [%8.3f .. %8.3f]" % (name, med[name], min(ms[name]), max(ms[name])))
+if ORDERED:
+    lines[1] = "GPU ms between two events around each call, the %d calls in turn, median of %d rounds after %d warm-up rounds [min .. max]" % (len(calls), REPEATS, WARMUP)
+    lines[2:2] = ["library: %s" % os.path.basename(os.path.dirname(os.path.abspath(capi.LIB_PATH)))] if os.environ.get("FLX_LIB") else []
+
+    def against(new, old):
+        apart = min(ms[new]) > max(ms[old]) or max(ms[new]) < min(ms[old])
+        return "  %-48s / %-44s %6.3f  (%+8.3f ms; %s the two calls' min .. max)" % (new, old, med[new] / med[old], med[new] - med[old], "OUTSIDE" if apart else "inside")
+
+    if have_ordered:
+        lines += ["", "ratios of the medians:"]
+        lines += [against("flx_rays_trace_ordered_device, " + name, "flx_rays_trace_device, " + name) for name, _ in d_sets]
+        lines += [against("flx_rays_trace_ordered_device, shuffled", "flx_rays_trace_device, pixel order"), against("flx_rays_trace_device, shuffled", "flx_rays_trace_device, pixel order")]
+        lines += ["", "the sort of the last batch: %d workgroups of T = %d items, %d passes, %d of %d rays live" % (order_info["groups"], order_info["T"], order_info["passes"], order_info["live"], order_info["n"]),
+                  "verified once outside the timed region: the ordered rows of every set equal the unordered rows, all eight words"]
+    with open(out_path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines), flush=True)
+    ctx.close()
+    sys.exit(0)
 p2 = med["flx_render_device, flx_set_pipeline(ctx, 2)"]
 spread = max(ms["flx_render_device, flx_set_pipeline(ctx, 2)"]) - min(ms["flx_render_device, flx_set_pipeline(ctx, 2)"])
 lines += ["", "ratio to the pipeline-2 frame (the run's spread of that frame: %.3f ms = %.1f %%):" % (spread, 100.0 * spread / p2)]

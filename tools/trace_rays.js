@@ -2,10 +2,11 @@
 /*
  * Trace rays of one's own through a BASELINE scene by the whole JavaScript path — FlexLight facade, scene graph, host flattening, N-API addon,
  * libflexlight_hip.so (flx_rays_trace) — and write what renderer.traceRays() returns.
- *   node tools/trace_rays.js <scene | file.flxs[.gz]> --rays rays.f32 --out rows.bin [--config-spp S --config-bounces B --samples S --bounces B --seed X
+ *   node tools/trace_rays.js <scene | file.flxs[.gz]> --rays rays.f32 --out rows.bin [--config-spp S --config-bounces B --samples S --bounces B --seed X --order hits
  *                            --running N --width W --height H --assets DIR --filter WxH --hdr 0|1 --temporal N --frames F --history H --chain 0|1 --reset K]
  *   <scene>: a BASELINE scene built through the scene graph (scenes/index.js), or a .flxs file replayed (sceneFile.sceneFromFlxs: a box without the assets)
  *   --config-spp, --config-bounces: the renderer's config (by default the scene's BASELINE frame); --samples, --bounces, --seed: traceRays' options
+ *   --order hits: traceRays' option order — the rays traced in the order of their first hit points (flx_rays_trace_ordered); the rows are the same
  *   rays.f32: 8 float32 per ray (origin, noise x, direction, noise y); rows.bin: radiance float32[4 n], s float32[n], entry int32[n], transform int32[n],
  *   shades uint32[n].  Without --samples / --bounces / --seed the renderer's defaults apply (config, scene; seed 0); the params used are printed.
  *   --running N: render() runs meanwhile; traceRays is called after every one of its first N frames (the last call's answer is written) and the frames' sums
@@ -66,6 +67,7 @@ const sum = a => { let s = 0; for (let i = 0; i < a.length; i++) if (a[i] === a[
   if (opt('--samples') !== undefined) options.samples = Number(opt('--samples'));
   if (opt('--bounces') !== undefined) options.maxReflections = Number(opt('--bounces'));
   if (opt('--seed') !== undefined) options.randomSeed = Number(opt('--seed'));
+  if (opt('--order') !== undefined) options.order = opt('--order');
   const filter = opt('--filter');
   if (filter !== undefined) {
     const size = /^(\d+)x(\d+)$/.exec(filter);
@@ -94,7 +96,7 @@ const sum = a => { let s = 0; for (let i = 0; i < a.length; i++) if (a[i] === a[
     renderer.halt();
     return;
   }
-  const info = { rays: rays.length / 8, params: renderer.traceParams(options), config: { samplesPerRay: engine.config.samplesPerRay, maxReflections: engine.config.maxReflections, minImportancy: engine.config.minImportancy }, ambient: Array.from(engine.scene.ambientLight), renderer: renderer.type };
+  const info = { rays: rays.length / 8, order: options.order === undefined ? null : options.order, params: renderer.traceParams(options), config: { samplesPerRay: engine.config.samplesPerRay, maxReflections: engine.config.maxReflections, minImportancy: engine.config.minImportancy }, ambient: Array.from(engine.scene.ambientLight), renderer: renderer.type };
   let rows;
   const running = Number(opt('--running', 0));
   if (running > 0) {

@@ -273,6 +273,12 @@ struct flx_context {
   DeviceBuffer<uint32_t> d_trace_ctl;
   struct TraceLaunch { uint32_t slabs = 0, slab = 0, path_groups = 0, lock = 0, n = 0, samples = 0, query_groups = 0; } last_trace_rays;
   uint32_t trace_slab = 0;                       /* flx_debug_set_trace_slab: most rays of a slab (0: flx_trace_slab_rays' own ceiling) */
+  /* traced batches in first-hit order (flx_rays_order.hip): the sort's scratch for a slab of rays, grown with the trace's scratch and never shrunk — two key and two
+   * position buffers (a pass reads one pair and writes the other; the order ends in d_order_pos[0]), the digit-major count table of one pass, and sixteen control words:
+   * [0..2] the least hit point per axis and [3..5] the greatest, as flx_ray_key_map's integers, [6] the slab's live rays, [7] unused, [8..15] the same for flx_debug_hit_keys —; what the last traced batch did
+   * (flx_debug_last_ray_order) */
+  DeviceBuffer<uint32_t> d_order_keys[2], d_order_pos[2], d_order_counts, d_order_ctl;
+  struct OrderLaunch { uint32_t ordered = 0, groups = 0, passes = 0, n = 0; } last_ray_order;
   /* surface rows (flx_surface.hip): their hit scratch is the traced batches' above, their host variants' staging the queries'; what the last call ran
    * (flx_debug_last_surface) */
   struct SurfaceLaunch { uint32_t slabs = 0, slab = 0, n = 0, fields = 0, frame = 0, query_groups = 0; } last_surface;
@@ -351,5 +357,11 @@ void flx_trace_frame(const flx_trace_params *p, flx::DeviceFrame &fr, int use_fi
 flx_status flx_wait_for_producer(flx_context *ctx, void *producer_stream);      /* the context's stream waits for what the caller's stream holds now (NULL: nothing to wait for) */
 /* a slab's head: d_trace_ctl's four words zeroed, the closest hits of m rays into d_trace_hits; q <- the launch */
 flx_status flx_slab_first_hits(flx_context *ctx, const flx::DeviceScene &sc, const float4 *rays, uint32_t m, const char *call, flx::QueryLaunch &q);
+/* flx_rays_order.hip: the words the sort's scratch must hold for a slab of at most `most` rays — keys and positions (each of the two), the count table —, and a slab's
+ * order: bounds, keys and the stable sort of m rays against their hit rows, enqueued on the context's stream; the order is d_order_pos[0]; *groups <- the sort's
+ * workgroups */
+size_t flx_order_room(uint32_t most);
+size_t flx_order_table_room(uint32_t most);
+flx_status flx_slab_order(flx_context *ctx, const float4 *rays, const float4 *hits, uint32_t m, uint32_t *groups);
 
 #endif

@@ -1,4 +1,5 @@
-/* flx_rays_trace.hip — radiance along a caller's rays (include/flexlight_hip_debug.h, "ray queries": flx_rays_trace, flx_rays_trace_device).
+/* flx_rays_trace.hip — radiance along a caller's rays (include/flexlight_hip_debug.h, "ray queries": flx_rays_trace, flx_rays_trace_device, and the same in
+ * first-hit order: flx_rays_trace_ordered, flx_rays_trace_ordered_device).
  *
  * What a frame computes for a pixel without filter and without temporal (fragment:601-632), computed for a ray of the caller's own: hit = rayTracer(origin,
  * direction); the samples' lightTrace(hit, direction, origin, cos(float(s)), max_reflections) added in sample order, averaged, times the originalColor the last
@@ -19,14 +20,20 @@
  * launches follow each other on the context's stream, the cursors zeroed in stream order in front of them.  The paths kernel's cursor counts UNITS of 64 items
  * (a block of rays x a sample), of which a slab has fewer than 2^31 + 2^18 whatever n and the sample count: any n a uint32_t holds works at any sample count the
  * memory holds a slab of.  The host waits for nothing — but where the scratch must grow, for the work that may still use it.
+ * IN FIRST-HIT ORDER (FLX_TRACE_ORDER_HITS) a slab has its bounds, keys and sort (flx_rays_order.hip) between 1 and 2, and k_rays_paths<LOCK, true> takes the item at
+ * position block * 64 + lane for ray order[position]: the 64 items a wave draws together are then 64 rays whose first hits are neighbours in the scene, whatever
+ * order the caller's rays came in.  Slots, lastOriginal and the resolve are indexed by the ray's own number, so the rows need no scatter and arrive in the caller's
+ * order, bit for bit the unordered call's: a row depends on nothing but its ray row and the scene.
  * The host side around the launches — the params' refusal and the frame bounce() is given, the growth, the producer wait, the slab loop and its first hits, the
  * host-memory call — is the ray-batch calls' shared path (flx_query.hip, flx_rays_host.h). */
 #include <cstring>
+#include <string>
 
 #define FLX_ANGLE_TABLE 1                  /* k_rays_paths reads the shading's per-triangle table (flx_device.h: one definition per translation unit), as k_paths does at the same four waves per SIMD */
 #include "flx_context.h"
 #include "flx_kernel_util.h"
 #include "flx_query_args.h"
+#include "flx_ray_order_args.h"
 #include "flx_rays_host.h"
 
 using namespace flx;
@@ -39,9 +46,13 @@ constexpr uint32_t TRACE_WAVES = 4;                    /* waves per SIMD the pat
 struct TraceArgs { DeviceScene sc; DeviceFrame fr; };
 static_assert(sizeof(TraceArgs) + 64 <= 4096, "the paths kernel's arguments fit a 4 KB kernarg segment");
 
-template <bool LOCK>
+/* ORDERED: the item at position block * 64 + (j & 63) names ray order[position] — a slab in first-hit order (flx_rays_order.hip): the 64 items a wave draws
+ * together start their paths in one corner of the scene whatever order the caller's rays came in.  Slots, lastOriginal and the resolve stay indexed by the ray's
+ * own number: the rows arrive in the caller's order with no scatter pass.  `order` is not read otherwise. */
+template <bool LOCK, bool ORDERED = false>
 __global__ __launch_bounds__(256, TRACE_WAVES) void k_rays_paths(TraceArgs ta, const float4 *__restrict__ rays, const float4 *__restrict__ hits, float4 *__restrict__ slots,
-                                                                 float4 *__restrict__ lastOriginal, uint32_t *__restrict__ queue, uint32_t n, uint32_t units) {
+                                                                 float4 *__restrict__ lastOriginal, uint32_t *__restrict__ queue, uint32_t n, uint32_t units,
+                                                                 const uint32_t *__restrict__ order) {
   const DeviceScene &sc = ta.sc;
   const DeviceFrame &fr = ta.fr;
   const uint32_t lane = threadIdx.x & 63u;
@@ -84,8 +95,10 @@ __global__ __launch_bounds__(256, TRACE_WAVES) void k_rays_paths(TraceArgs ta, c
       if (!alive && rank < take) {
         const uint32_t j = chunkNext + rank, unit = chunkUnit + (j >> 6);      /* unit = block * S + sample: < units, which the host keeps below 2^32 */
         const uint32_t block = unit / S, s = unit - block * S;
-        const uint32_t r = block * 64u + (j & 63u);                            /* block < 2^26: no overflow */
-        if (r < n) {
+        const uint32_t at = block * 64u + (j & 63u);                           /* block < 2^26: no overflow */
+        if (at < n) {
+          const uint32_t named = ORDERED ? order[at] : at;
+          const uint32_t r = named < n ? named : n - 1u;                       /* (an order is a permutation of 0 .. n - 1: the bound holds whatever the order says) */
           const float4 h = hits[(size_t)r * 2u];
           const int tri = __float_as_int(h.w);
           if (tri != -1) {
@@ -158,51 +171,68 @@ __global__ __launch_bounds__(256) void k_rays_resolve(const float4 *__restrict__
 
 /* ---- the calls ------------------------------------------------------------------------------------------------------------------------------------- */
 
-static flx_status fail(flx_context *ctx, flx_status code, const char *msg) { return flx_fail(ctx, code, msg); }
+static flx_status fail(flx_context *ctx, flx_status code, const std::string &msg) { return flx_fail(ctx, code, msg.c_str()); }
 
-extern "C" flx_status flx_rays_trace_device(flx_context *ctx, const flx_trace_params *params, const void *d_rays, void *d_radiance, uint32_t n, void *producer_stream) {
-  if (!ctx) return FLX_ERR_INVALID;
-  flx_status s = flx_trace_params_refused(ctx, params, "flx_rays_trace");      /* (both entry points say flx_rays_trace: here) */
-  if (s || n == 0) return s;
+/* One traced batch, behind both device calls: `call` is flx_rays_trace or flx_rays_trace_ordered, the name every message begins with (the device call's with
+ * _device behind it).  order: 0, or FLX_TRACE_ORDER_HITS — per slab bounds, keys and the sort (flx_rays_order.hip) between the first hits and the paths kernel,
+ * which then takes its rays through the order. */
+static flx_status trace_device(flx_context *ctx, const flx_trace_params *params, const void *d_rays, void *d_radiance, uint32_t n, uint32_t order, void *producer_stream,
+                               const char *call) {
+  const std::string device_call = std::string(call) + "_device";
   const enum flx_trace_refusal arrays = flx_trace_args_check(1, params->samples, params->max_reflections, params->texture_width, (uint64_t)(uintptr_t)d_rays,
                                                              (uint64_t)(uintptr_t)d_radiance, n);
   switch (arrays) {
     case FLX_TRACE_ARGS_OK: case FLX_TRACE_OVERLAP: break;      /* (overlap: said after the pointers are known to be the device's) */
-    case FLX_TRACE_NULL: return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_device: an array is NULL");
-    default: return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_device: n rows of 32 bytes leave the address space");
+    case FLX_TRACE_NULL: return fail(ctx, FLX_ERR_INVALID, device_call + ": an array is NULL");
+    default: return fail(ctx, FLX_ERR_INVALID, device_call + ": n rows of 32 bytes leave the address space");
   }
   FLX_HIP(ctx, hipSetDevice(ctx->device));
   const size_t bytes = (size_t)n * FLX_RAY_ROW_BYTES;
   if (!flx_rows_on_device(ctx, d_rays, bytes))
-    return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_device: the rays are not n rows in memory of the context's device, 16-byte aligned");
+    return fail(ctx, FLX_ERR_INVALID, device_call + ": the rays are not n rows in memory of the context's device, 16-byte aligned");
   if (!flx_rows_on_device(ctx, d_radiance, bytes))
-    return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_device: the radiance is not n rows in memory of the context's device, 16-byte aligned");
+    return fail(ctx, FLX_ERR_INVALID, device_call + ": the radiance is not n rows in memory of the context's device, 16-byte aligned");
   if (arrays == FLX_TRACE_OVERLAP)
-    return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_device: the rays and the radiance overlap");
+    return fail(ctx, FLX_ERR_INVALID, device_call + ": the rays and the radiance overlap");
+  flx_status s;
   TraceArgs ta;
   if ((s = flx_make_scene(ctx, ta.sc))) return s;           /* (refuses a scene that names a transform not uploaded) */
   if ((s = flx_server_stop(ctx))) return s;                 /* as flx_render_device: the frame server's launch ends after the frames posted to it */
   flx_trace_frame(params, ta.fr, 0, 0);                     /* no filter, no temporal */
   const uint32_t S = (uint32_t)params->samples;
+  const bool ordered = order != 0u;
   flx_ray_slabs cut(ctx, S, n);
+  /* the sort's scratch is asked for by an ordered batch alone, in the same growth and behind its one wait */
   if ((s = flx_grow(ctx, flx_need(&ctx->d_trace_hits, (size_t)cut.most * 2u), flx_need(&ctx->d_trace_slots, (size_t)cut.most * S), flx_need(&ctx->d_trace_last, cut.most),
-                    flx_need(&ctx->d_trace_ctl, 4))))
+                    flx_need(&ctx->d_trace_ctl, 4), flx_need(ordered ? &ctx->d_order_keys[0] : nullptr, flx_order_room(cut.most)),
+                    flx_need(ordered ? &ctx->d_order_keys[1] : nullptr, flx_order_room(cut.most)), flx_need(ordered ? &ctx->d_order_pos[0] : nullptr, flx_order_room(cut.most)),
+                    flx_need(ordered ? &ctx->d_order_pos[1] : nullptr, flx_order_room(cut.most)), flx_need(ordered ? &ctx->d_order_counts : nullptr, flx_order_table_room(cut.most)),
+                    flx_need(ordered ? &ctx->d_order_ctl : nullptr, 16))))
     return s;
   if ((s = flx_wait_for_producer(ctx, producer_stream))) return s;
   if ((s = flx_angle_table(ctx, ta.sc))) return s;          /* the shading's per-triangle table, made again first where the scene or the transforms changed: FLX_ANGLE_TABLE above makes this file's bounce() read it */
   const bool lock = FLX_LOCKSTEP && ta.sc.lock_entries != 0u;
   const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
-  uint32_t blocks = 0;
+  uint32_t blocks = 0, sort_groups = 0;
   /* a slab's launches behind its first hits; of d_trace_ctl's words [2] is the paths kernel's unit cursor */
-  s = flx_rays_slabs(ctx, ta.sc, d_rays, n, cut, "flx_rays_trace_device", [&](uint64_t first, uint32_t m, const float4 *rays) -> flx_status {
+  s = flx_rays_slabs(ctx, ta.sc, d_rays, n, cut, device_call.c_str(), [&](uint64_t first, uint32_t m, const float4 *rays) -> flx_status {
     float4 *out = (float4 *)d_radiance + first * 2u;
-    /* persistent grid: enough workgroups to fill every CU at the kernel's occupancy, no more than the items fill; flx_debug_set_query_groups sets it too */
+    flx_status so;
+    if (ordered && (so = flx_slab_order(ctx, rays, ctx->d_trace_hits.get(), m, &sort_groups))) return so;
+    const uint32_t *by = ctx->d_order_pos[0].get();          /* (the unordered kernels do not read it) */
+    /* persistent grid: enough workgroups to fill every CU at the kernel's occupancy, no more than the items fill; flx_debug_set_query_groups sets it too.  An
+     * ordered slab launches as many: its dead rays sit at the end of the order, where a unit of them costs a wave 64 loads of a hit row's entry */
     const uint32_t units = ((m + 63u) >> 6) * S;              /* (block of 64 rays, sample) pairs: below 2^31 + 2^18 by flx_trace_slab_rays' rule; four fill a workgroup */
     const uint32_t full = (units + 3u) / 4u;
     blocks = ctx->query_groups ? ctx->query_groups : (full < cus * 8u ? full : cus * 8u);
     uint32_t *queue = ctx->d_trace_ctl.get() + 2;
-    if (lock) hipLaunchKernelGGL(k_rays_paths<true>, dim3(blocks), dim3(256), 0, ctx->stream, ta, rays, ctx->d_trace_hits.get(), ctx->d_trace_slots.get(), ctx->d_trace_last.get(), queue, m, units);
-    else hipLaunchKernelGGL(k_rays_paths<false>, dim3(blocks), dim3(256), 0, ctx->stream, ta, rays, ctx->d_trace_hits.get(), ctx->d_trace_slots.get(), ctx->d_trace_last.get(), queue, m, units);
+    if (ordered) {
+      if (lock) hipLaunchKernelGGL((k_rays_paths<true, true>), dim3(blocks), dim3(256), 0, ctx->stream, ta, rays, ctx->d_trace_hits.get(), ctx->d_trace_slots.get(), ctx->d_trace_last.get(), queue, m, units, by);
+      else hipLaunchKernelGGL((k_rays_paths<false, true>), dim3(blocks), dim3(256), 0, ctx->stream, ta, rays, ctx->d_trace_hits.get(), ctx->d_trace_slots.get(), ctx->d_trace_last.get(), queue, m, units, by);
+    } else {
+      if (lock) hipLaunchKernelGGL((k_rays_paths<true, false>), dim3(blocks), dim3(256), 0, ctx->stream, ta, rays, ctx->d_trace_hits.get(), ctx->d_trace_slots.get(), ctx->d_trace_last.get(), queue, m, units, by);
+      else hipLaunchKernelGGL((k_rays_paths<false, false>), dim3(blocks), dim3(256), 0, ctx->stream, ta, rays, ctx->d_trace_hits.get(), ctx->d_trace_slots.get(), ctx->d_trace_last.get(), queue, m, units, by);
+    }
     FLX_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_rays_resolve, dim3((m + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->d_trace_hits.get(), ctx->d_trace_slots.get(), ctx->d_trace_last.get(), out, m, params->samples);
     FLX_HIP(ctx, hipGetLastError());
@@ -213,7 +243,17 @@ extern "C" flx_status flx_rays_trace_device(flx_context *ctx, const flx_trace_pa
   ran.n = n; ran.samples = S; ran.slab = cut.slab; ran.lock = lock ? 1u : 0u;
   ran.slabs = cut.slabs; ran.path_groups = blocks; ran.query_groups = cut.query.groups;
   ctx->last_trace_rays = ran;
+  flx_context::OrderLaunch sorted;
+  sorted.ordered = ordered ? 1u : 0u; sorted.groups = sort_groups; sorted.passes = ordered ? 4u : 0u; sorted.n = n;
+  ctx->last_ray_order = sorted;
   return FLX_OK;
+}
+
+extern "C" flx_status flx_rays_trace_device(flx_context *ctx, const flx_trace_params *params, const void *d_rays, void *d_radiance, uint32_t n, void *producer_stream) {
+  if (!ctx) return FLX_ERR_INVALID;
+  flx_status s = flx_trace_params_refused(ctx, params, "flx_rays_trace");      /* (both entry points say flx_rays_trace: here) */
+  if (s || n == 0) return s;
+  return trace_device(ctx, params, d_rays, d_radiance, n, 0u, producer_stream, "flx_rays_trace");
 }
 
 extern "C" flx_status flx_rays_trace(flx_context *ctx, const flx_trace_params *params, const float *rays, void *radiance, uint32_t n) {
@@ -222,6 +262,31 @@ extern "C" flx_status flx_rays_trace(flx_context *ctx, const flx_trace_params *p
   if (s || n == 0) return s;
   if (!rays || !radiance) return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace: an array is NULL");
   return flx_rays_from_host(ctx, rays, n, [&]() { return flx_rays_trace_device(ctx, params, ctx->d_query_rays, ctx->d_query_hits, n, nullptr); },
+                            flx_down(&ctx->d_query_hits, (size_t)n * 2u, radiance));
+}
+
+/* what both ordered calls refuse before they look at an array: the scene, the params, then a bit of `order` that is none of FLX_TRACE_ORDER_HITS */
+static flx_status ordered_refused(flx_context *ctx, const flx_trace_params *params, uint32_t order) {
+  flx_status s = flx_trace_params_refused(ctx, params, "flx_rays_trace_ordered");
+  if (s) return s;
+  if (!flx_order_bits_known(order)) return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_ordered: order has a bit beyond FLX_TRACE_ORDER_HITS");
+  return FLX_OK;
+}
+
+extern "C" flx_status flx_rays_trace_ordered_device(flx_context *ctx, const flx_trace_params *params, const void *d_rays, void *d_radiance, uint32_t n, uint32_t order,
+                                                    void *producer_stream) {
+  if (!ctx) return FLX_ERR_INVALID;
+  flx_status s = ordered_refused(ctx, params, order);
+  if (s || n == 0) return s;
+  return trace_device(ctx, params, d_rays, d_radiance, n, order, producer_stream, "flx_rays_trace_ordered");
+}
+
+extern "C" flx_status flx_rays_trace_ordered(flx_context *ctx, const flx_trace_params *params, const float *rays, void *radiance, uint32_t n, uint32_t order) {
+  if (!ctx) return FLX_ERR_INVALID;
+  flx_status s = ordered_refused(ctx, params, order);
+  if (s || n == 0) return s;
+  if (!rays || !radiance) return fail(ctx, FLX_ERR_INVALID, "flx_rays_trace_ordered: an array is NULL");
+  return flx_rays_from_host(ctx, rays, n, [&]() { return flx_rays_trace_ordered_device(ctx, params, ctx->d_query_rays, ctx->d_query_hits, n, order, nullptr); },
                             flx_down(&ctx->d_query_hits, (size_t)n * 2u, radiance));
 }
 

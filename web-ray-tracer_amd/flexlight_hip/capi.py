@@ -36,6 +36,7 @@ EXPORTS = [
     "flx_tree_build_device", "flx_tree_emit_device", "flx_scene_splice_device",
     "flx_rays_cast_device", "flx_rays_cast", "flx_debug_set_query_groups", "flx_debug_last_query",
     "flx_rays_trace_device", "flx_rays_trace", "flx_debug_set_trace_slab", "flx_debug_last_trace",
+    "flx_rays_trace_ordered_device", "flx_rays_trace_ordered", "flx_debug_sort_keys", "flx_debug_hit_keys", "flx_debug_last_ray_order",
     "flx_rays_surface_device", "flx_rays_surface", "flx_frame_surface_device", "flx_frame_surface", "flx_debug_last_surface",
     "flx_rays_planes_device", "flx_rays_planes", "flx_rays_image_device", "flx_rays_image", "flx_debug_last_ray_planes",
     "flx_rays_image_temporal_device", "flx_rays_image_temporal", "flx_rays_history_reset", "flx_debug_last_ray_temporal",
@@ -49,6 +50,7 @@ EXPORTS = [
 SHARE_HANDLE_BYTES = 128      # FLX_SHARE_HANDLE_BYTES
 NO_PARENT = 0xffffffff         # FLX_NO_PARENT of include/flexlight_hip_debug.h
 RAYS_CLOSEST, RAYS_OCCLUDED, RAYS_COUNT = 1, 2, 4      # FLX_RAYS_* of include/flexlight_hip_debug.h: what cast_rays asks of every ray
+TRACE_ORDER_HITS = 1           # FLX_TRACE_ORDER_HITS: trace_rays_ordered traces each slab's rays in the order of their first hit points
 # FLX_SURFACE_* of include/flexlight_hip_debug.h: the planes surface_rays / frame_surface write, in the order they follow each other
 SURFACE_HIT, SURFACE_POSITION, SURFACE_GEOMETRY_NORMAL, SURFACE_NORMAL, SURFACE_UV, SURFACE_ALBEDO, SURFACE_RME, SURFACE_TPO = 1, 2, 4, 8, 16, 32, 64, 128
 SURFACE_ALL = 255
@@ -187,6 +189,11 @@ def _load():
         "flx_rays_trace": (C.c_int, [vp, C.POINTER(TraceParams), fp, vp, u32]),
         "flx_debug_set_trace_slab": (C.c_int, [vp, u32]),
         "flx_debug_last_trace": (C.c_int, [vp, C.POINTER(u32)]),
+        "flx_rays_trace_ordered_device": (C.c_int, [vp, C.POINTER(TraceParams), vp, vp, u32, u32, vp]),
+        "flx_rays_trace_ordered": (C.c_int, [vp, C.POINTER(TraceParams), fp, vp, u32, u32]),
+        "flx_debug_sort_keys": (C.c_int, [vp, C.POINTER(u32), u32, C.POINTER(u32)]),
+        "flx_debug_hit_keys": (C.c_int, [vp, fp, vp, u32, C.POINTER(u32), fp]),
+        "flx_debug_last_ray_order": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_rays_surface_device": (C.c_int, [vp, C.c_int32, vp, u32, u32, vp, vp]),
         "flx_rays_surface": (C.c_int, [vp, C.c_int32, fp, u32, u32, vp]),
         "flx_frame_surface_device": (C.c_int, [vp, C.POINTER(FrameParams), u32, vp]),
@@ -758,9 +765,15 @@ class Context:
         [n, 32]), such a tensor to write into, or an address (then the address comes back); stream: the torch.cuda.Stream (or raw hipStream_t) on which the rays were
         written, as for cast_rays_device.  Returns the radiance rows ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE: sync() before they are read on another
         stream (unpack_radiance reads them).  Both arrays stay alive until then."""
-        r, n = _ray_rows(rays, self._device, "trace_rays_device")
+        r, n, o, out, stream = self._trace_device_args(rays, params, out, stream, "trace_rays_device")
+        self._check(LIB.flx_rays_trace_device(self._h, C.byref(params) if params is not None else None, C.c_void_p(r), C.c_void_p(o), n, C.c_void_p(stream) if stream else None), "flx_rays_trace_device")
+        return out
+
+    def _trace_device_args(self, rays, params, out, stream, call):
+        """what trace_rays_device and trace_rays_ordered_device are given -> (rays' address, n, out's address, out, the stream's handle)"""
+        r, n = _ray_rows(rays, self._device, call)
         if params is not None and not isinstance(params, TraceParams):
-            raise TypeError("trace_rays_device: params is a TraceParams")      # (None goes to the library, which refuses it)
+            raise TypeError("%s: params is a TraceParams" % call)      # (None goes to the library, which refuses it)
         if out is None:
             import torch
             out = torch.empty((n, 32), dtype=torch.uint8, device="cuda:%d" % self._device)
@@ -768,15 +781,14 @@ class Context:
             o = out
         else:
             if out.dtype.is_floating_point or out.device.type != "cuda" or out.device.index != self._device or not out.is_contiguous() or out.numel() * out.element_size() < n * 32:
-                raise ValueError("trace_rays_device: out is a contiguous integer tensor of at least n x 32 bytes on the context's device")
+                raise ValueError("%s: out is a contiguous integer tensor of at least n x 32 bytes on the context's device" % call)
             o = out.data_ptr()
         if stream is not None and not isinstance(stream, int):
             handle = stream.cuda_stream
             if handle == 0:
                 stream.synchronize()
             stream = handle
-        self._check(LIB.flx_rays_trace_device(self._h, C.byref(params) if params is not None else None, C.c_void_p(r), C.c_void_p(o), n, C.c_void_p(stream) if stream else None), "flx_rays_trace_device")
-        return out
+        return r, n, o, out, stream
 
     def trace_rays(self, rays, params):
         """flx_rays_trace: rays [n, 8] float32 in host memory (origin, noise x, direction, noise y) -> radiance rows uint8 [n, 32], complete (unpack_radiance)"""
@@ -784,6 +796,50 @@ class Context:
         out = np.zeros((rays.shape[0], 32), np.uint8)
         self._check(LIB.flx_rays_trace(self._h, C.byref(params) if params is not None else None, _fp(rays), out.ctypes.data_as(C.c_void_p), rays.shape[0]), "flx_rays_trace")
         return out
+
+    def trace_rays_ordered_device(self, rays, params, out=None, order=TRACE_ORDER_HITS, stream=None):
+        """flx_rays_trace_ordered_device: trace_rays_device with each slab's rays traced in the order of their first hit points (order = TRACE_ORDER_HITS; 0:
+        trace_rays_device itself).  The rows are trace_rays_device's, bit for bit and in the caller's order; for rays that come in no useful order it is the faster
+        call (profiles/rays_order.txt).  Everything else as trace_rays_device."""
+        r, n, o, out, stream = self._trace_device_args(rays, params, out, stream, "trace_rays_ordered_device")
+        self._check(LIB.flx_rays_trace_ordered_device(self._h, C.byref(params) if params is not None else None, C.c_void_p(r), C.c_void_p(o), n, int(order),
+                                                      C.c_void_p(stream) if stream else None), "flx_rays_trace_ordered_device")
+        return out
+
+    def trace_rays_ordered(self, rays, params, order=TRACE_ORDER_HITS):
+        """flx_rays_trace_ordered: trace_rays with each slab's rays traced in first-hit order -> radiance rows uint8 [n, 32], complete: trace_rays' rows"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros((rays.shape[0], 32), np.uint8)
+        self._check(LIB.flx_rays_trace_ordered(self._h, C.byref(params) if params is not None else None, _fp(rays), out.ctypes.data_as(C.c_void_p), rays.shape[0], int(order)),
+                    "flx_rays_trace_ordered")
+        return out
+
+    def sort_keys(self, keys):
+        """flx_debug_sort_keys: keys uint32 [n] in host memory, n from 1 to 2^21 -> the positions 0 .. n - 1 in ascending key order, equal keys in the order given
+        (numpy.argsort(keys, kind="stable")): the device's sort alone"""
+        keys = np.ascontiguousarray(keys, np.uint32).reshape(-1)
+        order = np.zeros(keys.shape[0], np.uint32)
+        self._check(LIB.flx_debug_sort_keys(self._h, keys.ctypes.data_as(C.POINTER(C.c_uint32)), keys.shape[0], order.ctypes.data_as(C.POINTER(C.c_uint32))), "flx_debug_sort_keys")
+        return order
+
+    def hit_keys(self, rays, hits):
+        """flx_debug_hit_keys: ray rows [n, 8] float32 and their closest-hit rows (cast_rays', [n, 32] uint8 or [n, 8] uint32) in host memory -> (keys uint32 [n],
+        bounds float32 [6]: lo x y z, hi x y z) as include/flx_ray_key.h defines them"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        hits = np.ascontiguousarray(hits).reshape(-1)
+        if hits.nbytes != rays.shape[0] * 32:
+            raise ValueError("hit_keys: a hit row of 32 bytes for every ray")
+        keys, bounds = np.zeros(rays.shape[0], np.uint32), np.zeros(6, np.float32)
+        self._check(LIB.flx_debug_hit_keys(self._h, _fp(rays), hits.ctypes.data_as(C.c_void_p), rays.shape[0], keys.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(bounds)),
+                    "flx_debug_hit_keys")
+        return keys, bounds
+
+    def last_ray_order(self):
+        """flx_debug_last_ray_order -> dict: ordered (whether the last traced batch was), T (items of a sort workgroup), groups (sort workgroups of its last slab),
+        passes, n, live (rays of its last slab with a first hit at a finite point)"""
+        out = (C.c_uint32 * 8)()
+        self._check(LIB.flx_debug_last_ray_order(self._h, out), "flx_debug_last_ray_order")
+        return dict(zip(("ordered", "T", "groups", "passes", "n", "live"), list(out)[:6]))
 
     def set_trace_slab(self, rays):
         """flx_debug_set_trace_slab: most rays of a slab of a traced batch (0: the library's ceiling)"""

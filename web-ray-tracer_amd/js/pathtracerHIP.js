@@ -45,9 +45,9 @@ function castRaysOn (context, rays, what) {
 
 /* flx_rays_trace on a context whose scene, lights, transforms and atlases are up: the radiance rows as the library writes them, 8 words a ray
  * (include/flexlight_hip_debug.h), unpacked into typed arrays */
-function traceRaysOn (context, rays, params) {
+function traceRaysOn (context, rays, params, order) {
   if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('traceRays: rays is a Float32Array of 8 floats per ray');
-  const rows = native().traceRays(context, rays, params);
+  const rows = order ? native().traceRaysOrdered(context, rays, params, order) : native().traceRays(context, rays, params);      // (order: FLX_TRACE_ORDER_* bits)
   const n = rays.length / 8;
   const words = new Uint32Array(rows), f = new Float32Array(rows), i32 = new Int32Array(rows);
   const out = { radiance: new Float32Array(4 * n), s: new Float32Array(n), entry: new Int32Array(n), transform: new Int32Array(n), shades: new Uint32Array(n) };
@@ -303,11 +303,16 @@ class PathTracerHIP {
    * scene.standardTextureSizes — and seed 0.  Returns { radiance: Float32Array(4 n) (r g b and 1 for a hit; a miss is 0 0 0 0, not the ambient light),
    * s: Float32Array(n) (the first hit lies at origin + s * direction), entry: Int32Array(n) (-1: none), transform: Int32Array(n), shades: Uint32Array(n) (bounce
    * iterations shaded over all samples) }: per ray a frame's pixel without filter and temporal — the samples averaged, times the first surfaces' colour as the
-   * LAST sample left it.  It waits for the answer; frames in flight finish unchanged. */
+   * LAST sample left it.  It waits for the answer; frames in flight finish unchanged.
+   * options.order: 'hits' traces the rays in the order of their first hit points (flx_rays_trace_ordered) — the same rows, bit for bit and in the order given,
+   * sooner where the rays come in no useful order: reflection rays, probe rays, shuffled rays.  Without it the rays are traced in the order given.  It is read
+   * here and is no part of traceParams()'s result; any other value is a TypeError. */
   traceRays (rays, options) {
     if (this._devices) throw new Error('traceRays: one GPU only (a group of GPUs traces no rays)');
+    const order = options ? options.order : undefined;
+    if (order !== undefined && order !== 'hits') throw new TypeError("traceRays: order is 'hits' or left out");
     this._uploadFrameState();
-    return traceRaysOn(this._context(), rays, this.traceParams(options));
+    return traceRaysOn(this._context(), rays, this.traceParams(options), order === 'hits' ? 1 : 0);
   }
 
   /* A ray IMAGE, traced and DENOISED: any projection the application makes rays for — a panorama, a fisheye or orthographic view, a stereo pair, a probe's faces, a

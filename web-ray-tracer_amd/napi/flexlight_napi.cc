@@ -384,6 +384,28 @@ static napi_value TraceRays(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+/* traceRaysOrdered(handle, rays Float32Array(8 n), params (traceRays'), order) -> ArrayBuffer(32 n): flx_rays_trace_ordered — traceRays' rows, each slab's rays
+ * traced in the order `order` asks for (1: FLX_TRACE_ORDER_HITS; the library refuses a bit it does not know) */
+static napi_value TraceRaysOrdered(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  void *rays; size_t len;
+  if (!typed(env, argv[1], napi_float32_array, &rays, &len)) return nullptr;
+  if (len % 8 != 0 || len / 8 > 0xffffffffu) { napi_throw_range_error(env, nullptr, "traceRaysOrdered: a ray needs 8 floats (origin, noise x, direction, noise y)"); return nullptr; }
+  flx_trace_params p;
+  if (!read_trace_params(env, argv[2], "traceRaysOrdered", &p)) return nullptr;
+  uint32_t order = 0;
+  if (napi_get_value_uint32(env, argv[3], &order) != napi_ok) { napi_throw_type_error(env, nullptr, "traceRaysOrdered: order is not a number"); return nullptr; }
+  void *rows = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, (len / 8) * 32, &rows, &buf));
+  flx_status rc = flx_rays_trace_ordered(ctx, &p, (const float *)rays, rows, (uint32_t)(len / 8), order);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_rays_trace_ordered", rc);
+  return buf;
+}
+
 /* rayImage(handle, rays Float32Array(8 width height), width, height, params (traceRays'), hdr) -> ArrayBuffer(16 width height): flx_rays_image, the rays in image
  * order (row 0 on top) traced into the five filter planes and denoised by the chain; float4 per pixel (include/flexlight_hip_debug.h) */
 static napi_value RayImage(napi_env env, napi_callback_info info) {
@@ -1420,7 +1442,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas }, { "uploadTextures", UploadTextures }, { "updateTexture", UpdateTexture },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
