@@ -518,6 +518,62 @@ flx_status flx_camera_image_temporal_device(flx_context *ctx, const flx_trace_pa
                                             uint32_t height, void *d_out_rgba /* float4[height][width] */);
 flx_status flx_camera_image_temporal(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal, const flx_camera *camera, uint32_t width,
                                      uint32_t height, float *out_rgba);      /* host array out */
+/* LIGHT PROBES: probe positions in, one spherical-harmonic (SH) row per probe out, and nothing but positions and SH rows crossing the bus.  A probe is a
+ * position and a face size w (1 .. 256); its R = 6 w w texels are six w x w cube faces, t = (face * w + row) * w + px, the faces in flx_camera's cube-face order,
+ * row 0 on top.  Every float is defined bit for bit in include/flx_probe.h, float32 with one rounding per operation, which the kernels (csrc/flx_probes.hip:
+ * k_probe_rays, k_probe_sh) and a CPU reference compile alike.
+ * THE RAY of texel t: origin and direction are flx_camera_ray's for a FLX_CAMERA_CUBE_FACE camera of that face with the identity basis, zero jitter, the probe's
+ * position and size w x w, bit for bit.  THE NOISE WORDS ARE NOT THE CAMERA'S (the six faces of a probe would share them, and equal noise words draw equal random
+ * numbers): with cols = ceil(sqrt(R)) and rows = ceil(R / cols) in integers, noise x is the camera's NDC expression of (t % cols, cols) and noise y that of
+ * (t / cols, rows), zero jitter.  Every ray of a probe draws its own random numbers and every probe draws the same ones as every other probe: a probe's row
+ * depends on its position, w and the params, and on nothing else in the call.
+ * THE WEIGHT of texel t, with sx, sy as the camera computes them: q = (1 + sx sx) + sy sy, d_omega = cell / (q sqrt(q)), cell = 4 / (w w).  THE WEIGHTS ARE NOT
+ * RENORMALISED: their sum is 4 pi (1 + e_w), e_w = 0.910, 0.0396, 0.0281, 0.0153, 0.00383, 0.00096, 0.00024 for w = 1, 2, 3, 4, 8, 16, 32; the row carries the sum.
+ * THE BASIS: real SH bands 0 - 2 of the direction (x, y, z): K0; K1 y, K1 z, K1 x; K2 x y, K2 y z, K3 (3 z z - 1), K2 x z, K4 (x x - y y).
+ * THE TERMS of texel t: its radiance row is flx_rays_trace's.  It is a hit where word 3 is not 0.0f; then L = words 0 .. 2 and s = word 4, the first-hit distance;
+ * otherwise L = params->sky (a miss row is all zeros, as in a frame: sky lets an open scene have an environment, sky = 0 keeps the frame's meaning).  Coefficient
+ * i, channel c gets L_c (b_i d_omega); four more sums get d_omega (all texels), d_omega (hits only), d_omega s and d_omega (s s) (hits only): the visibility
+ * moments a probe volume uses against leaking.
+ * THE ORDER OF THE 31 SUMS is part of the definition: 64 slots; slot j adds its texels j, j + 64, j + 128, .. in ascending order onto 0.0f; then for off = 1, 2, 4,
+ * 8, 16, 32 every slot becomes v[j] + v[j ^ off], after which all slots are equal.  A sum that meets a NaN is some NaN; its payload is not defined.
+ * THE SH ROW: 144 bytes, nine float4; coefficient i in words 4 i .. 4 i + 2; word 4 i + 3 holds for i = 0 .. 3 the four extra sums in the order above and 0.0f
+ * for i >= 4.
+ * flx_probe_irradiance (a plain host function, no context, no device): E_c = ((A0 (sh[c] b0)) + A1 ((sh[4 + c] b1 + sh[8 + c] b2) + sh[12 + c] b3)) + A2 (the five
+ * band-2 products summed in ascending i), A0 = pi, A1 = 2 pi / 3, A2 = pi / 4 as float32, b_i the basis at n (used as given), one rounding per operation.
+ * flx_probe_rays_device writes the n_probes * R ray rows of the probes at d_positions (rows of 4 floats, word 3 ignored), probe p's rows from row p * R; it needs
+ * NO SCENE, like flx_camera_rays_device.  POSITIONS ON THE DEVICE CANNOT BE LOOKED AT: a position that is not finite is traced as given.
+ * flx_probe_reduce_device reduces n_probes * R radiance rows to n_probes SH rows.  flx_probes_sh_device is the whole path: it cuts the probes into chunks of
+ * max(1, 2^21 / R) probes — the most rays of a trace slab; flx_debug_set_probe_chunk sets a smaller number, 0 the default — and runs per chunk, on the context's
+ * stream, k_probe_rays into a buffer the context owns, flx_rays_trace_ordered_device (params->order: 0 or FLX_TRACE_ORDER_HITS, the same rows either way) from
+ * there into a second one, and k_probe_sh into the chunk's rows of d_sh.  Both buffers are grown and never shrunk; together they end at 2^21 rays x 64 bytes.
+ * The result is bit for bit that of the three calls made one after the other, whatever the chunk.
+ * Ordering, producer_stream, the frame server and n_probes == 0 (FLX_OK, nothing enqueued, the scene and the params looked at first) are flx_rays_trace_device's,
+ * word for word: enqueued on the context's stream with no wait of the host, frames in flight finish unchanged.  (Where a buffer must grow, the host waits for the
+ * stream first.)  flx_probe_rays, flx_probe_reduce and flx_probes_sh are the same for host arrays, staged through memory the context owns; they wait and copy out.
+ * Refusals, each with a message of its own, nothing enqueued and the output untouched: for flx_probes_sh[_device] the scene's and the trace params', asked of
+ * flx_rays_trace_ordered_device in its words; then FLX_ERR_INVALID for params NULL; face_size 0 or above 256; a bit of order beyond FLX_TRACE_ORDER_HITS; a sky or
+ * reserved value that is not finite; n_probes * R of 2^32 or more (the ray and reduce calls, which handle that many rows in one piece); an array that is NULL, not
+ * memory of the context's device, not 16-byte aligned, in an allocation too short, or that overlaps the other.  A group has no such call, as it traces no rays. */
+typedef struct flx_probe_params {
+  uint32_t face_size;   /* w: 1 .. 256 texels along a cube face's edge */
+  uint32_t order;       /* 0 or FLX_TRACE_ORDER_HITS, handed to flx_rays_trace_ordered_device */
+  float sky[3];         /* L of a texel whose ray hits nothing */
+  float reserved;       /* 0; must be finite */
+} flx_probe_params;
+flx_status flx_probe_rays_device(flx_context *ctx, const void *d_positions /* n_probes * 4 floats, word 3 ignored */, uint32_t n_probes, uint32_t face_size,
+                                 void *d_rays /* n_probes * 6 w w * 8 floats */, void *producer_stream /* hipStream_t that wrote the positions, or NULL */);
+flx_status flx_probe_rays(flx_context *ctx, const float *positions, uint32_t n_probes, uint32_t face_size, float *rays);      /* host arrays */
+flx_status flx_probe_reduce_device(flx_context *ctx, const void *d_radiance /* n_probes * 6 w w rows of 32 bytes */, uint32_t n_probes, const flx_probe_params *params,
+                                   void *d_sh /* n_probes * 9 float4 */, void *producer_stream /* hipStream_t that wrote the radiance, or NULL */);
+flx_status flx_probe_reduce(flx_context *ctx, const void *radiance, uint32_t n_probes, const flx_probe_params *params, float *sh);      /* host arrays */
+flx_status flx_probes_sh_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const void *d_positions /* n_probes * 4 floats */,
+                                uint32_t n_probes, void *d_sh /* n_probes * 9 float4 */, void *producer_stream);
+flx_status flx_probes_sh(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const float *positions, uint32_t n_probes, float *sh);      /* host arrays */
+void flx_probe_irradiance(const float sh[36], const float n[3], float out[3]);
+flx_status flx_debug_set_probe_chunk(flx_context *ctx, uint32_t probes /* 0: the default */);
+/* The last flx_probes_sh[_device] (zeros if none): out[0] its chunks, [1] the probes of a full chunk, [2] the face size, [3] n_probes, [4] order, [5] the rays of a
+ * probe, [6] workgroups of the last chunk's k_probe_sh, [7] zero.  It waits for nothing. */
+flx_status flx_debug_last_probes(flx_context *ctx, uint32_t out[8]);
 /* SURFACE ROWS: what the surface is where a ray first hits — the question between "where does it hit" (flx_rays_cast) and "what radiance comes back"
  * (flx_rays_trace, flx_render).  The planes (AOVs) a denoiser of the caller's own, compositing or the shading of a hybrid renderer needs beside the noisy radiance:
  * position, geometric normal, shading normal, texture coordinates, and albedo, RME and TPO with the atlases applied.  They are the first thing lightTrace computes

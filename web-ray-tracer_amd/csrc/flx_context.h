@@ -293,6 +293,12 @@ struct flx_context {
   struct RayTemporalLaunch { uint32_t slabs = 0, slab = 0, depth = 0, history = 0, n = 0, samples = 0, head = 0, fused = 0; } last_ray_temporal;
   /* cameras (flx_camera.hip): the rays flx_camera_image[_temporal]_device makes for the image calls that follow on the same stream, grown and never shrunk */
   DeviceBuffer<float4> d_camera_rays;
+  /* light probes (flx_probes.hip): the rays and the radiance rows of one chunk of probes, which flx_probes_sh_device makes, traces and reduces on the same stream —
+   * at most 2^21 rays x 32 bytes each —, and the host variants' positions; all grown and never shrunk.  What the last flx_probes_sh[_device] ran
+   * (flx_debug_last_probes) */
+  DeviceBuffer<float4> d_probe_rays, d_probe_radiance, d_probe_positions;
+  struct ProbeLaunch { uint32_t chunks = 0, chunk = 0, face_size = 0, n = 0, order = 0, rays = 0, reduce_groups = 0; } last_probes;
+  uint32_t probe_chunk = 0;                      /* flx_debug_set_probe_chunk: most probes of a chunk (0: as many as a trace slab's 2^21 rays hold) */
   /* uploads: pinned staging ring */
   PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};

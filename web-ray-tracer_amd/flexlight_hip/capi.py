@@ -41,6 +41,8 @@ EXPORTS = [
     "flx_rays_planes_device", "flx_rays_planes", "flx_rays_image_device", "flx_rays_image", "flx_debug_last_ray_planes",
     "flx_rays_image_temporal_device", "flx_rays_image_temporal", "flx_rays_history_reset", "flx_debug_last_ray_temporal",
     "flx_camera_rays_device", "flx_camera_rays", "flx_camera_image_device", "flx_camera_image", "flx_camera_image_temporal_device", "flx_camera_image_temporal",
+    "flx_probe_rays_device", "flx_probe_rays", "flx_probe_reduce_device", "flx_probe_reduce", "flx_probes_sh_device", "flx_probes_sh", "flx_probe_irradiance",
+    "flx_debug_set_probe_chunk", "flx_debug_last_probes",
     "flx_textures_upload", "flx_textures_upload_device", "flx_texture_update", "flx_texture_update_device", "flx_group_textures_upload", "flx_group_texture_update",
     "flx_debug_atlas_read",
 ]
@@ -136,6 +138,30 @@ class Camera(C.Structure):
         return cls(CAMERA_CUBE_FACE, position, basis, (0.0, 0.0), jitter, face)
 
 
+class ProbeParams(C.Structure):
+    """flx_probe_params of include/flexlight_hip_debug.h: a probe's face size w (1 .. 256: 6 w w rays a probe), the order its rays are traced in (0 or
+    TRACE_ORDER_HITS: the same rows) and the radiance of a ray that hits nothing"""
+    _fields_ = [("face_size", C.c_uint32), ("order", C.c_uint32), ("sky", C.c_float * 3), ("reserved", C.c_float)]
+
+    def __init__(self, face_size=8, order=0, sky=(0.0, 0.0, 0.0), reserved=0.0):
+        super().__init__(int(face_size), int(order), (C.c_float * 3)(*[float(x) for x in sky]), float(reserved))
+
+
+def probe_ray_count(face_size):
+    """rays of a probe of that face size: 6 w w"""
+    return 6 * int(face_size) * int(face_size)
+
+
+def _probe_positions(positions):
+    """positions of a host probe call: [n, 3] or [n, 4] -> contiguous float32 [n, 4], word 3 zero where it was not given"""
+    positions = np.asarray(positions, np.float32)
+    if positions.ndim != 2 or positions.shape[1] not in (3, 4):
+        raise ValueError("probe positions are [n, 3] or [n, 4]")
+    out = np.zeros((positions.shape[0], 4), np.float32)
+    out[:, :positions.shape[1]] = positions
+    return out
+
+
 def _cameras(cameras, call):
     """a Camera or a sequence of them -> (the flx_camera array or None, count)"""
     if isinstance(cameras, Camera):
@@ -214,6 +240,15 @@ def _load():
         "flx_camera_image_temporal_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(RayTemporal), C.POINTER(Camera), u32, u32, vp]),
         "flx_camera_image_temporal": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(RayTemporal), C.POINTER(Camera), u32, u32, fp]),
         "flx_debug_last_ray_temporal": (C.c_int, [vp, C.POINTER(u32)]),
+        "flx_probe_rays_device": (C.c_int, [vp, vp, u32, u32, vp, vp]),
+        "flx_probe_rays": (C.c_int, [vp, fp, u32, u32, fp]),
+        "flx_probe_reduce_device": (C.c_int, [vp, vp, u32, C.POINTER(ProbeParams), vp, vp]),
+        "flx_probe_reduce": (C.c_int, [vp, vp, u32, C.POINTER(ProbeParams), fp]),
+        "flx_probes_sh_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), vp, u32, vp, vp]),
+        "flx_probes_sh": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), fp, u32, fp]),
+        "flx_probe_irradiance": (None, [fp, fp, fp]),
+        "flx_debug_set_probe_chunk": (C.c_int, [vp, u32]),
+        "flx_debug_last_probes": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_textures_upload": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32]),
         "flx_textures_upload_device": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32, vp]),
         "flx_texture_update": (C.c_int, [vp, C.c_int, u32, C.POINTER(Image)]),
@@ -506,6 +541,34 @@ def unpack_surface(planes, fields):
     if "uv" in out:
         out["transform2"] = out["uv"][:, 2].copy().view(np.int32)
     return out
+
+
+SH_NAMES = ("coefficients", "weight", "coverage", "mean_distance", "mean_distance2")      # unpack_sh's keys
+
+
+def unpack_sh(rows):
+    """SH rows of probes_sh / probe_reduce and their _device forms (float32 [n, 36], a numpy array or a torch tensor: a tensor is copied to the host, which waits
+    for the stream it is asked on — sync() first where the call ran on another) -> dict: coefficients float32 [n, 9, 3] (bands 0 - 2, rgb), weight float32 [n] (the
+    sum of d_omega over all texels), coverage [n] (over the texels that hit), mean_distance and mean_distance2 [n] (the sums of d_omega s and d_omega s s over the
+    hits: divide by coverage for the means)"""
+    if not isinstance(rows, np.ndarray):
+        rows = rows.detach().cpu().numpy()
+    rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 9, 4)
+    return {"coefficients": rows[:, :, 0:3].copy(), "weight": rows[:, 0, 3].copy(), "coverage": rows[:, 1, 3].copy(), "mean_distance": rows[:, 2, 3].copy(),
+            "mean_distance2": rows[:, 3, 3].copy()}
+
+
+def probe_irradiance(sh, normals):
+    """flx_probe_irradiance, the library's one definition (include/flx_probe.h): sh float32 [36] or [n, 36] (a row per normal, or one row for all), normals float32
+    [3] or [n, 3], used as given -> irradiance float32 [n, 3] ([3] where both were single).  A plain host function: no context, no device."""
+    sh2, n2 = np.ascontiguousarray(sh, np.float32).reshape(-1, 36), np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if sh2.shape[0] != n2.shape[0] and sh2.shape[0] != 1:
+        raise ValueError("probe_irradiance: one SH row, or one per normal")
+    out = np.zeros((n2.shape[0], 3), np.float32)
+    for k in range(n2.shape[0]):
+        row = sh2[k if sh2.shape[0] > 1 else 0]
+        LIB.flx_probe_irradiance(_fp(row), _fp(n2[k]), _fp(out[k]))
+    return out[0] if np.ndim(sh) == 1 and np.ndim(normals) == 1 else out
 
 
 def noise_coordinates(n):
@@ -1050,6 +1113,103 @@ class Context:
         self._check(LIB.flx_camera_image_temporal(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(temporal) if temporal is not None else None,
                                                   C.byref(camera) if camera is not None else None, width, height, _fp(out)), "flx_camera_image_temporal")
         return out
+
+    # -- light probes: SH rows of probe positions ---------------------------------------------------
+    def _probe_device_args(self, positions, out, out_rows_of, row_width, stream, call):
+        """positions of a *_device probe call (a contiguous float32 tensor [n, 4] on the context's device, or (address, n)), its output (None: a new float32 tensor
+        [out_rows_of(n), row_width]; such a tensor; an address) and stream -> (positions' address, n, out's address, out, the stream's handle)"""
+        if isinstance(positions, tuple):
+            p, n = int(positions[0]), int(positions[1])
+        else:
+            import torch
+            if not isinstance(positions, torch.Tensor):
+                raise TypeError("%s: positions is a torch tensor or (address, probes)" % call)
+            if positions.dtype != torch.float32 or positions.dim() != 2 or positions.shape[1] != 4 or not positions.is_contiguous():
+                raise ValueError("%s: positions is a contiguous float32 tensor [n, 4]" % call)
+            if positions.device.type != "cuda" or positions.device.index != self._device:
+                raise ValueError("%s: positions is on %s, the context on cuda:%d" % (call, positions.device, self._device))
+            p, n = positions.data_ptr(), positions.shape[0]
+        if out is None:
+            import torch
+            out = torch.empty((out_rows_of(n), row_width), dtype=torch.float32, device="cuda:%d" % self._device)
+        o = self._device_out(out, out_rows_of(n) * row_width * 4, call, "out")
+        return p, n, o, out, _stream_handle(stream)
+
+    def probe_rays_device(self, positions, face_size, out=None, stream=None):
+        """flx_probe_rays_device: the 6 w w ray rows of every probe made on the device.  positions: a torch tensor [n, 4] (float32, contiguous, on the context's
+        device; word 3 ignored) or (address, n); out: None (a new float32 tensor [n * 6 w w, 8], probe p's rows from row p * 6 w w), such a tensor, or an address;
+        stream: the stream on which the positions were written.  Needs no scene.  Returns the rows ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        rays = probe_ray_count(face_size)
+        p, n, o, out, stream = self._probe_device_args(positions, out, lambda n: n * rays, 8, stream, "probe_rays_device")
+        self._check(LIB.flx_probe_rays_device(self._h, C.c_void_p(p), n, int(face_size), C.c_void_p(o), stream), "flx_probe_rays_device")
+        return out
+
+    def probe_rays(self, positions, face_size):
+        """flx_probe_rays: positions [n, 3] or [n, 4] in host memory -> ray rows float32 [n * 6 w w, 8], complete"""
+        positions = _probe_positions(positions)
+        out = np.zeros((positions.shape[0] * probe_ray_count(face_size), 8), np.float32)
+        self._check(LIB.flx_probe_rays(self._h, _fp(positions), positions.shape[0], int(face_size), _fp(out)), "flx_probe_rays")
+        return out
+
+    def probe_reduce_device(self, radiance, n_probes, params, out=None, stream=None):
+        """flx_probe_reduce_device: n_probes * 6 w w radiance rows (trace_rays_device's: a contiguous tensor of that many x 32 bytes on the context's device, or an
+        address) reduced to SH rows.  params: ProbeParams; out: None (a new float32 tensor [n_probes, 36]), such a tensor, or an address.  Returns the SH rows
+        (unpack_sh) ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        if params is not None and not isinstance(params, ProbeParams):
+            raise TypeError("probe_reduce_device: params is a ProbeParams")
+        n = int(n_probes)
+        r = self._device_out(radiance, n * probe_ray_count(params.face_size if params is not None else 0) * 32, "probe_reduce_device", "radiance")
+        if out is None:
+            import torch
+            out = torch.empty((n, 36), dtype=torch.float32, device="cuda:%d" % self._device)
+        o = self._device_out(out, n * 144, "probe_reduce_device", "out")
+        self._check(LIB.flx_probe_reduce_device(self._h, C.c_void_p(r), n, C.byref(params) if params is not None else None, C.c_void_p(o), _stream_handle(stream)),
+                    "flx_probe_reduce_device")
+        return out
+
+    def probe_reduce(self, radiance, n_probes, params):
+        """flx_probe_reduce: radiance rows in host memory (n_probes * 6 w w x 32 bytes, any dtype) -> SH rows float32 [n_probes, 36], complete"""
+        if params is not None and not isinstance(params, ProbeParams):
+            raise TypeError("probe_reduce: params is a ProbeParams")
+        radiance = np.ascontiguousarray(radiance).reshape(-1)
+        n = int(n_probes)
+        if params is not None and radiance.nbytes != n * probe_ray_count(params.face_size) * 32:
+            raise ValueError("probe_reduce: a radiance row of 32 bytes for every ray of every probe")
+        out = np.zeros((n, 36), np.float32)
+        self._check(LIB.flx_probe_reduce(self._h, radiance.ctypes.data_as(C.c_void_p), n, C.byref(params) if params is not None else None, _fp(out)), "flx_probe_reduce")
+        return out
+
+    def probes_sh_device(self, positions, trace_params, params, out=None, stream=None):
+        """flx_probes_sh_device: probe positions in, one SH row per probe out, rays and radiance never leaving the device.  positions: as for probe_rays_device;
+        trace_params: TraceParams; params: ProbeParams; out: None (a new float32 tensor [n, 36]), such a tensor, or an address.  Returns the SH rows (unpack_sh)
+        ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        if trace_params is not None and not isinstance(trace_params, TraceParams):
+            raise TypeError("probes_sh_device: trace_params is a TraceParams")
+        if params is not None and not isinstance(params, ProbeParams):
+            raise TypeError("probes_sh_device: params is a ProbeParams")
+        p, n, o, out, stream = self._probe_device_args(positions, out, lambda n: n, 36, stream, "probes_sh_device")
+        self._check(LIB.flx_probes_sh_device(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None,
+                                             C.c_void_p(p), n, C.c_void_p(o), stream), "flx_probes_sh_device")
+        return out
+
+    def probes_sh(self, positions, trace_params, params):
+        """flx_probes_sh: positions [n, 3] or [n, 4] in host memory -> SH rows float32 [n, 36], complete (unpack_sh, probe_irradiance)"""
+        positions = _probe_positions(positions)
+        out = np.zeros((positions.shape[0], 36), np.float32)
+        self._check(LIB.flx_probes_sh(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None,
+                                      _fp(positions), positions.shape[0], _fp(out)), "flx_probes_sh")
+        return out
+
+    def set_probe_chunk(self, probes):
+        """flx_debug_set_probe_chunk: most probes of a chunk of probes_sh (0: as many as 2^21 rays hold)"""
+        self._check(LIB.flx_debug_set_probe_chunk(self._h, int(probes)), "flx_debug_set_probe_chunk")
+
+    def last_probes(self):
+        """flx_debug_last_probes -> dict (zeros when no probes_sh ran): chunks, chunk (probes of a full one), face_size, n, order, rays (of a probe), reduce_groups
+        (workgroups of the last chunk's reduction)"""
+        out = (C.c_uint32 * 8)()
+        self._check(LIB.flx_debug_last_probes(self._h, out), "flx_debug_last_probes")
+        return dict(zip(("chunks", "chunk", "face_size", "n", "order", "rays", "reduce_groups"), list(out)[:7]))
 
     # -- surface rows -------------------------------------------------------------------------------
     def _surface_out(self, out, n, fields, call):

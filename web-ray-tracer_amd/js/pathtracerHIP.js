@@ -315,6 +315,38 @@ class PathTracerHIP {
     return traceRaysOn(this._context(), rays, this.traceParams(options), order === 'hits' ? 1 : 0);
   }
 
+  /* LIGHT PROBES: probe positions in, one spherical-harmonic row per probe out, the rays and their radiance never leaving the device (flx_probes_sh,
+   * include/flexlight_hip_debug.h "light probes").  positions: Float32Array, 3 or 4 floats per probe (options.stride names which; by default 4 where the length is a
+   * multiple of 4 and not of 3, else 3).  options: traceRays' (order included) plus faceSize (1 .. 256, by default 8: 6 x 8 x 8 rays a probe) and sky ([r, g, b], the
+   * radiance of a ray that hits nothing, by default 0 0 0).  Returns a Float32Array of 36 floats per probe: coefficient i (real SH bands 0 - 2), channel c in word
+   * 4 i + c; words 3, 7, 11, 15 the sums of d_omega, of d_omega over the rays that hit, of d_omega s and of d_omega s s over them.  It waits for the answer. */
+  traceProbes (positions, options) {
+    if (this._devices) throw new Error('traceProbes: one GPU only (a group of GPUs traces no rays)');
+    if (!(positions instanceof Float32Array)) throw new TypeError('traceProbes: positions is a Float32Array of 3 or 4 floats per probe');
+    const o = options || {};
+    if (o.order !== undefined && o.order !== 'hits') throw new TypeError("traceProbes: order is 'hits' or left out");
+    const stride = o.stride !== undefined ? o.stride : (positions.length % 4 === 0 && positions.length % 3 !== 0 ? 4 : 3);
+    if ((stride !== 3 && stride !== 4) || positions.length % stride !== 0) throw new TypeError('traceProbes: positions is a Float32Array of 3 or 4 floats per probe');
+    let rows = positions;
+    if (stride === 3) {
+      rows = new Float32Array(positions.length / 3 * 4);
+      for (let k = 0; k < positions.length / 3; k++) { rows[4 * k] = positions[3 * k]; rows[4 * k + 1] = positions[3 * k + 1]; rows[4 * k + 2] = positions[3 * k + 2]; }
+    }
+    const sky = o.sky === undefined ? [0, 0, 0] : Array.from(o.sky);
+    if (sky.length !== 3) throw new TypeError('traceProbes: sky is [r, g, b]');
+    this._uploadFrameState();
+    const probe = { faceSize: o.faceSize === undefined ? 8 : o.faceSize, order: o.order === 'hits' ? 1 : 0, sky };
+    return new Float32Array(native().traceProbes(this._context(), rows, this.traceParams(options), probe));
+  }
+
+  /* The irradiance an SH row of traceProbes gives for a normal (flx_probe_irradiance, the definition Python shares): row Float32Array(36) — a probe's part of
+   * traceProbes' result, row.subarray(36 k, 36 k + 36) —, normal [x, y, z], used as given.  Returns Float32Array(3).  Needs no GPU call. */
+  probeIrradiance (row, normal) {
+    if (this._devices) throw new Error('probeIrradiance: one GPU only (a group of GPUs traces no rays)');
+    if (!(row instanceof Float32Array) || row.length !== 36) throw new TypeError('probeIrradiance: row is a Float32Array of 36 floats');
+    return native().probeIrradiance(row.byteOffset === 0 && row.buffer.byteLength === 144 ? row : Float32Array.from(row), Float32Array.from(normal));
+  }
+
   /* A ray IMAGE, traced and DENOISED: any projection the application makes rays for — a panorama, a fisheye or orthographic view, a stereo pair, a probe's faces, a
    * reflection buffer — through the renderer's own filter (flx_rays_image, include/flexlight_hip_debug.h "ray queries").  rays: traceRays' rows, width * height of
    * them in image order, row 0 on top.  options: traceRays' plus hdr (by default config.hdr), the chain's tone map.  Per ray the five filter planes are what a frame

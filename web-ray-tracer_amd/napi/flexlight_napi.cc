@@ -406,6 +406,50 @@ static napi_value TraceRaysOrdered(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+/* traceProbes(handle, positions Float32Array(4 n), params (traceRays'), { faceSize, order, sky[3] }) -> ArrayBuffer(144 n): flx_probes_sh, one SH row of 36 floats
+ * per probe position (include/flexlight_hip_debug.h "light probes"); the library judges the values */
+static napi_value TraceProbes(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  flx_context *ctx = get_ctx(env, argv[0]);
+  if (!ctx) return nullptr;
+  void *positions; size_t len;
+  if (!typed(env, argv[1], napi_float32_array, &positions, &len)) return nullptr;
+  if (len % 4 != 0 || len / 4 > 0xffffffffu) { napi_throw_range_error(env, nullptr, "traceProbes: a position needs 4 floats (x, y, z and a word that is ignored)"); return nullptr; }
+  flx_trace_params p;
+  if (!read_trace_params(env, argv[2], "traceProbes", &p)) return nullptr;
+  flx_probe_params q;
+  memset(&q, 0, sizeof q);
+  napi_value v;
+  if (napi_get_named_property(env, argv[3], "faceSize", &v) != napi_ok || napi_get_value_uint32(env, v, &q.face_size) != napi_ok ||
+      napi_get_named_property(env, argv[3], "order", &v) != napi_ok || napi_get_value_uint32(env, v, &q.order) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "traceProbes: faceSize and order are numbers");
+    return nullptr;
+  }
+  if (!floats(env, argv[3], "sky", q.sky, 3)) return nullptr;
+  void *rows = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, (len / 4) * 144, &rows, &buf));
+  flx_status rc = flx_probes_sh(ctx, &p, &q, (const float *)positions, (uint32_t)(len / 4), (float *)rows);
+  if (rc != FLX_OK) return fail(env, ctx, "flx_probes_sh", rc);
+  return buf;
+}
+
+/* probeIrradiance(row Float32Array(36), normal Float32Array(3)) -> Float32Array(3): flx_probe_irradiance, the library's one definition; no context */
+static napi_value ProbeIrradiance(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  if (!get_args(env, info, 2, argv)) return nullptr;
+  void *row, *normal; size_t row_len, normal_len;
+  if (!typed(env, argv[0], napi_float32_array, &row, &row_len) || !typed(env, argv[1], napi_float32_array, &normal, &normal_len)) return nullptr;
+  if (row_len != 36 || normal_len != 3) { napi_throw_range_error(env, nullptr, "probeIrradiance: an SH row of 36 floats and a normal of 3"); return nullptr; }
+  void *out = nullptr;
+  napi_value buf, array;
+  NAPI_OK(env, napi_create_arraybuffer(env, 12, &out, &buf));
+  flx_probe_irradiance((const float *)row, (const float *)normal, (float *)out);
+  NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, 3, buf, 0, &array));
+  return array;
+}
+
 /* rayImage(handle, rays Float32Array(8 width height), width, height, params (traceRays'), hdr) -> ArrayBuffer(16 width height): flx_rays_image, the rays in image
  * order (row 0 on top) traced into the five filter planes and denoised by the chain; float4 per pixel (include/flexlight_hip_debug.h) */
 static napi_value RayImage(napi_env env, napi_callback_info info) {
@@ -1442,7 +1486,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "traceProbes", TraceProbes }, { "probeIrradiance", ProbeIrradiance }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas }, { "uploadTextures", UploadTextures }, { "updateTexture", UpdateTexture },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
