@@ -574,6 +574,70 @@ flx_status flx_debug_set_probe_chunk(flx_context *ctx, uint32_t probes /* 0: the
 /* The last flx_probes_sh[_device] (zeros if none): out[0] its chunks, [1] the probes of a full chunk, [2] the face size, [3] n_probes, [4] order, [5] the rays of a
  * probe, [6] workgroups of the last chunk's k_probe_sh, [7] zero.  It waits for nothing. */
 flx_status flx_debug_last_probes(flx_context *ctx, uint32_t out[8]);
+/* PROBE VOLUMES: a regular grid of light probes, baked into SH rows on the device, and THE LOOKUP that joins them with surface rows: for every surface point the
+ * irradiance the grid gives it.  A hybrid renderer is three device calls with no host arithmetic in between: flx_volume_bake_device, flx_frame_surface_device (or
+ * the rasterizer), flx_volume_irradiance_device — or the last two in one, flx_frame_irradiance_device.  Every float is defined bit for bit in include/flx_volume.h,
+ * float32 with one rounding per operation, which the kernels (csrc/flx_volume.hip: k_volume_positions, k_volume_irradiance) and a CPU reference compile alike.
+ * THE GRID (flx_volume_grid): probe (ix, iy, iz) has index p = (iz ny + iy) nx + ix and, per axis, the position origin + (float)i spacing (the product, then the sum).
+ * THE LOOKUP takes a FLX_SURFACE_POSITION row (x, hit) and a FLX_SURFACE_NORMAL row (n, .); the normal is used as given, not normalised.
+ *   1. A miss — word 3 of the position equal to 0.0f — gives four 0.0f and reads no probe.
+ *   2. x' = n normal_bias + x per axis (the product, then the sum).
+ *   3. g = (x' - origin) / spacing; g = (g >= 0) ? g : 0 (a NaN becomes 0); g = (g <= (float)(count - 1)) ? g : (float)(count - 1).
+ *   4. i = min((uint32_t)g, count - 2) where count >= 2, else 0; f = g - (float)i.
+ *   5. Corner k = kx + 2 ky + 4 kz, k = 0 .. 7 ascending, is the probe at min(i_a + k_a, count_a - 1) per axis.  t = (tx ty) tz, t_a = k_a ? f_a : 1 - f_a.
+ *      d = probe - x', dist = sqrt((dx dx + dy dy) + dz dz), dir = d / dist (three quotients; zero where dist == 0), c = (((dirx nx + diry ny) + dirz nz) + 1) 0.5,
+ *      wb = c c + 0.2.  wv = 1 unless FLX_VOLUME_VISIBILITY is set and the row's sh[7] > 0; then mean = sh[11] / sh[7], mean2 = sh[15] / sh[7],
+ *      var = |mean2 - mean mean|, and where dist > mean: delta = dist - mean, den = var + delta delta, ch = den > 0 ? var / den : 0, wv = max((ch ch) ch, floor)
+ *      with max(a, b) = (a < b) ? b : a; otherwise wv = 1.  w_k = (t wb) wv, E_k = flx_probe_irradiance's of row k and n.
+ *   6. W and S_c start at 0.0f and add w_k and w_k E_k,c (the product first) in ascending k — also where t == 0: one path.
+ *   7. The row is (S_0 / W, S_1 / W, S_2 / W, W); four 0.0f where W <= 0.  A NaN W is neither > 0 nor <= 0 and takes the quotients: a NaN anywhere gives some NaN.
+ * WHERE THE ISSUE OF AN ORDER WAS OPEN it is fixed as written above: products before the sums that take them, sums of three left to right, x before y before z.
+ * THE MOMENTS ARE THOSE OF THE WHOLE SPHERE, not of a direction: the visibility weight is isotropic (include/flx_volume.h says what that costs); a directional
+ * visibility map is left out, and the flag turns the isotropic test off.
+ * flx_volume_positions_device writes the grid's nx ny nz positions as rows of 4 floats (word 3 is 0.0f), flx_probes_sh_device's input; it needs NO SCENE.
+ * flx_volume_bake_device writes them into a buffer the context owns and runs flx_probes_sh_device from there — there is no second probe path —: bit for bit the
+ * two calls one after the other.  flx_volume_irradiance_device is the lookup for n points: d_sh the grid's SH rows, d_positions and d_normals planes of n rows of 16
+ * bytes, d_out n rows of 16 bytes; it needs NO SCENE.  flx_rays_irradiance_device and flx_frame_irradiance_device take the two planes (FLX_SURFACE_POSITION |
+ * FLX_SURFACE_NORMAL) with flx_rays_surface_device / flx_frame_surface_device AS THEY STAND into a buffer the context owns (grown and never shrunk) and the lookup
+ * follows on the same stream: bit for bit the surface call followed by flx_volume_irradiance_device.  A ray batch goes in slabs of at most 2^21 rays
+ * (flx_debug_set_trace_slab lowers it for tests), so that the buffer ends at 2^21 x 32 bytes; a frame's holds width x height x 32 bytes.
+ * Ordering, producer_stream, the frame server and n == 0 (FLX_OK, nothing enqueued, the grid and the scene looked at first) are flx_rays_trace_device's, word for
+ * word: enqueued on the context's stream with no wait of the host, frames in flight finish unchanged.  (Where a buffer must grow, the host waits for the stream
+ * first.)  The calls without _device are the same for host arrays, staged through memory the context owns; they wait and copy out.  flx_volume_irradiance_of is a
+ * plain host function (no context, no device): the lookup of one point over SH rows in host memory.  A group has no such call.
+ * Refusals, each FLX_ERR_INVALID with a message of its own, nothing enqueued and the output untouched: a NULL grid (or NULL probe params: flx_probes_sh's words); a
+ * count of 0; nx ny nz of 2^31 or more; an origin or a spacing that is not finite; a spacing <= 0; a normal_bias that is negative or not finite; a floor outside
+ * [0, 1] or not finite; unknown flag bits; a reserved word that is not 0; an array that is NULL, not memory of the context's device, not 16-byte aligned, in an
+ * allocation too short for its rows, or that overlaps another of the call.  The scene's, the trace params', the probe params' and the surface calls' own refusals
+ * are passed through in their own words (those calls are asked first). */
+#define FLX_VOLUME_VISIBILITY 1u
+typedef struct flx_volume_grid {
+  float origin[3];      /* probe (0, 0, 0) */
+  float spacing[3];     /* > 0 per axis */
+  uint32_t count[3];    /* nx, ny, nz: at least 1 each, nx ny nz below 2^31 */
+  float normal_bias;    /* >= 0: how far along the normal the sample point is lifted off the surface */
+  float floor;          /* 0 .. 1: the least visibility weight */
+  uint32_t flags;       /* FLX_VOLUME_VISIBILITY or 0 */
+  uint32_t reserved;    /* 0 */
+} flx_volume_grid;
+flx_status flx_volume_positions_device(flx_context *ctx, const flx_volume_grid *grid, void *d_positions /* nx ny nz * 4 floats */, void *producer_stream /* hipStream_t that last used d_positions, or NULL */);
+flx_status flx_volume_positions(flx_context *ctx, const flx_volume_grid *grid, float *positions);      /* host array */
+flx_status flx_volume_bake_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid,
+                                  void *d_sh /* nx ny nz * 9 float4 */, void *producer_stream);
+flx_status flx_volume_bake(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, float *sh);      /* host array */
+flx_status flx_volume_irradiance_device(flx_context *ctx, const flx_volume_grid *grid, const void *d_sh /* nx ny nz * 9 float4 */, const void *d_positions /* n * 4 floats */,
+                                        const void *d_normals /* n * 4 floats */, uint32_t n, void *d_out /* n * 4 floats */, void *producer_stream /* hipStream_t that wrote the inputs, or NULL */);
+flx_status flx_volume_irradiance(flx_context *ctx, const flx_volume_grid *grid, const float *sh, const float *positions, const float *normals, uint32_t n, float *out);      /* host arrays */
+flx_status flx_rays_irradiance_device(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const void *d_sh, const void *d_rays /* n * 8 floats */, uint32_t n,
+                                      void *d_out /* n * 4 floats */, void *producer_stream);
+flx_status flx_rays_irradiance(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const float *sh, const float *rays, uint32_t n, float *out);      /* host arrays */
+flx_status flx_frame_irradiance_device(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const void *d_sh, void *d_out /* width * height * 4 floats */);
+flx_status flx_frame_irradiance(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const float *sh, float *out);      /* host arrays */
+void flx_volume_irradiance_of(const flx_volume_grid *grid, const float *sh_rows, const float position[4], const float normal[4], float out[4]);
+/* The last lookup — flx_volume_irradiance[_device], flx_rays_irradiance[_device] or flx_frame_irradiance[_device] — (zeros if none): out[0] its points, [1] its slabs,
+ * [2] the points of a full slab, [3] the grid's probes, [4] the grid's flags, [5] 1 for rays, 2 for a frame, 0 for planes of the caller's, [6] workgroups of the last
+ * slab's k_volume_irradiance, [7] zero.  (The kernel has one path: there is no count of waves by path to report.)  It waits for nothing. */
+flx_status flx_debug_last_volume(flx_context *ctx, uint32_t out[8]);
 /* SURFACE ROWS: what the surface is where a ray first hits — the question between "where does it hit" (flx_rays_cast) and "what radiance comes back"
  * (flx_rays_trace, flx_render).  The planes (AOVs) a denoiser of the caller's own, compositing or the shading of a hybrid renderer needs beside the noisy radiance:
  * position, geometric normal, shading normal, texture coordinates, and albedo, RME and TPO with the atlases applied.  They are the first thing lightTrace computes

@@ -299,6 +299,11 @@ struct flx_context {
   DeviceBuffer<float4> d_probe_rays, d_probe_radiance, d_probe_positions;
   struct ProbeLaunch { uint32_t chunks = 0, chunk = 0, face_size = 0, n = 0, order = 0, rays = 0, reduce_groups = 0; } last_probes;
   uint32_t probe_chunk = 0;                      /* flx_debug_set_probe_chunk: most probes of a chunk (0: as many as a trace slab's 2^21 rays hold) */
+  /* probe volumes (flx_volume.hip): the grid's positions flx_volume_bake_device makes for flx_probes_sh_device; the position plane and the normal plane of a slab
+   * of rays (at most 2^21 x 32 bytes) or of a frame, which flx_rays_irradiance_device and flx_frame_irradiance_device take for the lookup behind them; the host
+   * variants' SH rows; all grown and never shrunk.  What the last lookup ran (flx_debug_last_volume) */
+  DeviceBuffer<float4> d_volume_positions, d_volume_surface, d_volume_sh;
+  struct VolumeLaunch { uint32_t n = 0, slabs = 0, slab = 0, probes = 0, flags = 0, source = 0, groups = 0; } last_volume;
   /* uploads: pinned staging ring */
   PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};
@@ -363,6 +368,8 @@ void flx_trace_frame(const flx_trace_params *p, flx::DeviceFrame &fr, int use_fi
 flx_status flx_wait_for_producer(flx_context *ctx, void *producer_stream);      /* the context's stream waits for what the caller's stream holds now (NULL: nothing to wait for) */
 /* a slab's head: d_trace_ctl's four words zeroed, the closest hits of m rays into d_trace_hits; q <- the launch */
 flx_status flx_slab_first_hits(flx_context *ctx, const flx::DeviceScene &sc, const float4 *rays, uint32_t m, const char *call, flx::QueryLaunch &q);
+/* flx_surface.hip: what flx_frame_surface[_device] refuses before it looks at its output — the scene, the params, the fields, the frame's shape — in its words */
+flx_status flx_frame_surface_refused(flx_context *ctx, const flx_frame_params *p, uint32_t fields, const char *call);
 /* flx_rays_order.hip: the words the sort's scratch must hold for a slab of at most `most` rays — keys and positions (each of the two), the count table —, and a slab's
  * order: bounds, keys and the stable sort of m rays against their hit rows, enqueued on the context's stream; the order is d_order_pos[0]; *groups <- the sort's
  * workgroups */

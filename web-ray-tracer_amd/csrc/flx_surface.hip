@@ -203,8 +203,8 @@ extern "C" flx_status flx_rays_surface(flx_context *ctx, int32_t texture_width, 
                             flx_down(&ctx->d_query_hits, (size_t)n * flx_surface_planes(fields), out));
 }
 
-/* what both frame calls refuse before they look at the output */
-static flx_status frame_surface_refused(flx_context *ctx, const flx_frame_params *p, uint32_t fields, const char *call) {
+/* what both frame calls refuse before they look at the output (flx_context.h: flx_volume.hip asks the same for flx_frame_irradiance) */
+flx_status flx_frame_surface_refused(flx_context *ctx, const flx_frame_params *p, uint32_t fields, const char *call) {
   flx_status s = flx_scene_refused(ctx, call);
   if (s) return s;
   if (!p) return surface_refusal(ctx, FLX_SURFACE_PARAMS_NULL, call);
@@ -215,7 +215,7 @@ static flx_status frame_surface_refused(flx_context *ctx, const flx_frame_params
 extern "C" flx_status flx_frame_surface_device(flx_context *ctx, const flx_frame_params *params, uint32_t fields, void *d_out) {
   static const char *const call = "flx_frame_surface_device";
   if (!ctx) return FLX_ERR_INVALID;
-  flx_status s = frame_surface_refused(ctx, params, fields, call);
+  flx_status s = flx_frame_surface_refused(ctx, params, fields, call);
   if (s) return s;
   const uint32_t n = params->width * params->height;          /* (fits: flx_surface_frame_check) */
   uint64_t out_bytes = 0;
@@ -255,7 +255,7 @@ extern "C" flx_status flx_frame_surface_device(flx_context *ctx, const flx_frame
 extern "C" flx_status flx_frame_surface(flx_context *ctx, const flx_frame_params *params, uint32_t fields, void *out) {
   static const char *const call = "flx_frame_surface";
   if (!ctx) return FLX_ERR_INVALID;
-  flx_status s = frame_surface_refused(ctx, params, fields, call);
+  flx_status s = flx_frame_surface_refused(ctx, params, fields, call);
   if (s) return s;
   if (!out) return surface_refusal(ctx, FLX_SURFACE_NULL, call);
   return flx_rays_from_host(ctx, nullptr, 0u, [&]() { return flx_frame_surface_device(ctx, params, fields, ctx->d_query_hits); },

@@ -43,6 +43,9 @@ EXPORTS = [
     "flx_camera_rays_device", "flx_camera_rays", "flx_camera_image_device", "flx_camera_image", "flx_camera_image_temporal_device", "flx_camera_image_temporal",
     "flx_probe_rays_device", "flx_probe_rays", "flx_probe_reduce_device", "flx_probe_reduce", "flx_probes_sh_device", "flx_probes_sh", "flx_probe_irradiance",
     "flx_debug_set_probe_chunk", "flx_debug_last_probes",
+    "flx_volume_positions_device", "flx_volume_positions", "flx_volume_bake_device", "flx_volume_bake", "flx_volume_irradiance_device", "flx_volume_irradiance",
+    "flx_rays_irradiance_device", "flx_rays_irradiance", "flx_frame_irradiance_device", "flx_frame_irradiance", "flx_volume_irradiance_of",
+    "flx_debug_last_volume",
     "flx_textures_upload", "flx_textures_upload_device", "flx_texture_update", "flx_texture_update_device", "flx_group_textures_upload", "flx_group_texture_update",
     "flx_debug_atlas_read",
 ]
@@ -147,6 +150,61 @@ class ProbeParams(C.Structure):
         super().__init__(int(face_size), int(order), (C.c_float * 3)(*[float(x) for x in sky]), float(reserved))
 
 
+VOLUME_VISIBILITY = 1          # FLX_VOLUME_VISIBILITY of include/flexlight_hip_debug.h: the lookup weights a probe by its row's visibility moments
+
+
+class VolumeGrid(C.Structure):
+    """flx_volume_grid of include/flexlight_hip_debug.h: a regular grid of probes — probe (ix, iy, iz) at origin + i * spacing, index (iz ny + iy) nx + ix —, how far
+    along the normal a surface point is lifted before the lookup, the least visibility weight, and whether the visibility weight applies at all"""
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("count", C.c_uint32 * 3), ("normal_bias", C.c_float), ("floor", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0), count=(2, 2, 2), normal_bias=0.0, floor=0.05, flags=VOLUME_VISIBILITY, reserved=0):
+        super().__init__((C.c_float * 3)(*[float(x) for x in origin]), (C.c_float * 3)(*[float(x) for x in spacing]), (C.c_uint32 * 3)(*[int(x) for x in count]),
+                         float(normal_bias), float(floor), int(flags), int(reserved))
+
+    @property
+    def probes(self):
+        """nx ny nz"""
+        return int(self.count[0]) * int(self.count[1]) * int(self.count[2])
+
+
+def _grid(grid, call):
+    """grid of a volume call -> what ctypes hands the library: a reference, or None (which the library refuses)"""
+    if grid is not None and not isinstance(grid, VolumeGrid):
+        raise TypeError("%s: grid is a VolumeGrid" % call)
+    return C.byref(grid) if grid is not None else None
+
+
+def _surface_rows(rows, what, call):
+    """a plane of surface rows in host memory: [n, 4] (or, a position without its hit word or a normal, [n, 3]: word 3 becomes 1) -> contiguous float32 [n, 4]"""
+    rows = np.asarray(rows, np.float32)
+    if rows.ndim != 2 or rows.shape[1] not in (3, 4):
+        raise ValueError("%s: %s are [n, 3] or [n, 4]" % (call, what))
+    out = np.ones((rows.shape[0], 4), np.float32)
+    out[:, :rows.shape[1]] = rows
+    return out
+
+
+def volume_irradiance_of(grid, sh, position, normal):
+    """flx_volume_irradiance_of, the library's one definition of the lookup on the host (include/flx_volume.h): sh float32 [probes, 36], position [4] (x, y, z, hit)
+    or [n, 4], normal [3] or [4] or as many -> float32 [4] or [n, 4]: (E_r, E_g, E_b, W)"""
+    if not isinstance(grid, VolumeGrid):
+        raise TypeError("volume_irradiance_of: grid is a VolumeGrid")
+    sh = np.ascontiguousarray(sh, np.float32).reshape(-1, 36)
+    if sh.shape[0] != grid.probes:
+        raise ValueError("volume_irradiance_of: one SH row per probe of the grid")
+    one = np.ndim(position) == 1
+    positions = _surface_rows(np.atleast_2d(position), "positions", "volume_irradiance_of")
+    normals = _surface_rows(np.atleast_2d(normal), "normals", "volume_irradiance_of")
+    if len(normals) != len(positions):
+        raise ValueError("volume_irradiance_of: a normal per position")
+    out = np.zeros((len(positions), 4), np.float32)
+    for k in range(len(positions)):
+        LIB.flx_volume_irradiance_of(C.byref(grid), _fp(sh), _fp(positions[k]), _fp(normals[k]), _fp(out[k]))
+    return out[0] if one else out
+
+
 def probe_ray_count(face_size):
     """rays of a probe of that face size: 6 w w"""
     return 6 * int(face_size) * int(face_size)
@@ -249,6 +307,18 @@ def _load():
         "flx_probe_irradiance": (None, [fp, fp, fp]),
         "flx_debug_set_probe_chunk": (C.c_int, [vp, u32]),
         "flx_debug_last_probes": (C.c_int, [vp, C.POINTER(u32)]),
+        "flx_volume_positions_device": (C.c_int, [vp, C.POINTER(VolumeGrid), vp, vp]),
+        "flx_volume_positions": (C.c_int, [vp, C.POINTER(VolumeGrid), fp]),
+        "flx_volume_bake_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), C.POINTER(VolumeGrid), vp, vp]),
+        "flx_volume_bake": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), C.POINTER(VolumeGrid), fp]),
+        "flx_volume_irradiance_device": (C.c_int, [vp, C.POINTER(VolumeGrid), vp, vp, vp, u32, vp, vp]),
+        "flx_volume_irradiance": (C.c_int, [vp, C.POINTER(VolumeGrid), fp, fp, fp, u32, fp]),
+        "flx_rays_irradiance_device": (C.c_int, [vp, C.c_int32, C.POINTER(VolumeGrid), vp, vp, u32, vp, vp]),
+        "flx_rays_irradiance": (C.c_int, [vp, C.c_int32, C.POINTER(VolumeGrid), fp, fp, u32, fp]),
+        "flx_frame_irradiance_device": (C.c_int, [vp, C.POINTER(FrameParams), C.POINTER(VolumeGrid), vp, vp]),
+        "flx_frame_irradiance": (C.c_int, [vp, C.POINTER(FrameParams), C.POINTER(VolumeGrid), fp, fp]),
+        "flx_volume_irradiance_of": (None, [C.POINTER(VolumeGrid), fp, fp, fp, fp]),
+        "flx_debug_last_volume": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_textures_upload": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32]),
         "flx_textures_upload_device": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32, vp]),
         "flx_texture_update": (C.c_int, [vp, C.c_int, u32, C.POINTER(Image)]),
@@ -1210,6 +1280,145 @@ class Context:
         out = (C.c_uint32 * 8)()
         self._check(LIB.flx_debug_last_probes(self._h, out), "flx_debug_last_probes")
         return dict(zip(("chunks", "chunk", "face_size", "n", "order", "rays", "reduce_groups"), list(out)[:7]))
+
+    # -- probe volumes: a grid of probes baked, and the irradiance it gives surface points -------------------
+    def _new_rows(self, rows, width):
+        import torch
+        return torch.empty((rows, width), dtype=torch.float32, device="cuda:%d" % self._device)
+
+    def volume_positions_device(self, grid, out=None, stream=None):
+        """flx_volume_positions_device: the grid's probe positions made on the device, probes_sh_device's input.  out: None (a new float32 tensor [probes, 4]),
+        such a tensor, or an address; stream: the stream that last used out.  Needs no scene.  Returns the rows ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET
+        COMPLETE."""
+        g = _grid(grid, "volume_positions_device")
+        probes = grid.probes if grid is not None else 0
+        if out is None:
+            out = self._new_rows(probes, 4)
+        o = self._device_out(out, probes * 16, "volume_positions_device", "out")
+        self._check(LIB.flx_volume_positions_device(self._h, g, C.c_void_p(o), _stream_handle(stream)), "flx_volume_positions_device")
+        return out
+
+    def volume_positions(self, grid):
+        """flx_volume_positions: -> the positions float32 [probes, 4] in host memory, complete"""
+        g = _grid(grid, "volume_positions")
+        out = np.zeros((grid.probes if grid is not None else 0, 4), np.float32)
+        self._check(LIB.flx_volume_positions(self._h, g, _fp(out)), "flx_volume_positions")
+        return out
+
+    def volume_bake_device(self, grid, trace_params, params, out=None, stream=None):
+        """flx_volume_bake_device: the grid's positions made and probes_sh_device run on them, nothing crossing the bus.  trace_params: TraceParams; params:
+        ProbeParams; out: None (a new float32 tensor [probes, 36]), such a tensor, or an address.  Returns the SH rows ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET
+        COMPLETE: the lookups take them as they are."""
+        if trace_params is not None and not isinstance(trace_params, TraceParams):
+            raise TypeError("volume_bake_device: trace_params is a TraceParams")
+        if params is not None and not isinstance(params, ProbeParams):
+            raise TypeError("volume_bake_device: params is a ProbeParams")
+        g = _grid(grid, "volume_bake_device")
+        probes = grid.probes if grid is not None else 0
+        if out is None:
+            out = self._new_rows(probes, 36)
+        o = self._device_out(out, probes * 144, "volume_bake_device", "out")
+        self._check(LIB.flx_volume_bake_device(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None, g,
+                                               C.c_void_p(o), _stream_handle(stream)), "flx_volume_bake_device")
+        return out
+
+    def volume_bake(self, grid, trace_params, params):
+        """flx_volume_bake: -> the SH rows float32 [probes, 36] in host memory, complete"""
+        g = _grid(grid, "volume_bake")
+        out = np.zeros((grid.probes if grid is not None else 0, 36), np.float32)
+        self._check(LIB.flx_volume_bake(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None, g,
+                                        _fp(out)), "flx_volume_bake")
+        return out
+
+    def volume_irradiance_device(self, grid, sh, positions, normals, n=None, out=None, stream=None):
+        """flx_volume_irradiance_device: the lookup for n surface points.  sh: the grid's SH rows (a contiguous tensor of probes x 144 bytes on the context's device,
+        or an address); positions, normals: planes of surface rows (surface_rays_device's FLX_SURFACE_POSITION and FLX_SURFACE_NORMAL: contiguous tensors of n x 16
+        bytes, or addresses — then n is given); out: None (a new float32 tensor [n, 4]: E_r, E_g, E_b, W), such a tensor, or an address; stream: the stream that wrote
+        the inputs.  Needs no scene.  Returns the rows ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        g = _grid(grid, "volume_irradiance_device")
+        if n is None:
+            n = positions.shape[0]
+        n = int(n)
+        s = self._device_out(sh, (grid.probes if grid is not None else 0) * 144, "volume_irradiance_device", "sh")
+        p = self._device_out(positions, n * 16, "volume_irradiance_device", "positions")
+        q = self._device_out(normals, n * 16, "volume_irradiance_device", "normals")
+        if out is None:
+            out = self._new_rows(n, 4)
+        o = self._device_out(out, n * 16, "volume_irradiance_device", "out")
+        self._check(LIB.flx_volume_irradiance_device(self._h, g, C.c_void_p(s), C.c_void_p(p), C.c_void_p(q), n, C.c_void_p(o), _stream_handle(stream)),
+                    "flx_volume_irradiance_device")
+        return out
+
+    def volume_irradiance(self, grid, sh, positions, normals):
+        """flx_volume_irradiance: SH rows [probes, 36], positions [n, 4] (word 3: 0 a miss) or [n, 3] (all hits) and normals [n, 3] or [n, 4] in host memory -> the
+        irradiance rows float32 [n, 4], complete"""
+        g = _grid(grid, "volume_irradiance")
+        sh = np.ascontiguousarray(sh, np.float32).reshape(-1, 36)
+        if grid is not None and sh.shape[0] != grid.probes:
+            raise ValueError("volume_irradiance: one SH row per probe of the grid")
+        positions, normals = _surface_rows(positions, "positions", "volume_irradiance"), _surface_rows(normals, "normals", "volume_irradiance")
+        if len(positions) != len(normals):
+            raise ValueError("volume_irradiance: a normal per position")
+        out = np.zeros((len(positions), 4), np.float32)
+        self._check(LIB.flx_volume_irradiance(self._h, g, _fp(sh), _fp(positions), _fp(normals), len(positions), _fp(out)), "flx_volume_irradiance")
+        return out
+
+    def rays_irradiance_device(self, grid, sh, rays, texture_width=32, out=None, stream=None):
+        """flx_rays_irradiance_device: surface_rays_device's position and normal planes of the rays' first hits and the lookup behind them, in one call.  sh: as
+        for volume_irradiance_device; rays: as for surface_rays_device; out: None (a new float32 tensor [n, 4]), such a tensor, or an address.  Returns the rows
+        ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        g = _grid(grid, "rays_irradiance_device")
+        r, n = _ray_rows(rays, self._device, "rays_irradiance_device")
+        s = self._device_out(sh, (grid.probes if grid is not None else 0) * 144, "rays_irradiance_device", "sh")
+        if out is None:
+            out = self._new_rows(n, 4)
+        o = self._device_out(out, n * 16, "rays_irradiance_device", "out")
+        self._check(LIB.flx_rays_irradiance_device(self._h, int(texture_width), g, C.c_void_p(s), C.c_void_p(r), n, C.c_void_p(o), _stream_handle(stream)),
+                    "flx_rays_irradiance_device")
+        return out
+
+    def rays_irradiance(self, grid, sh, rays, texture_width=32):
+        """flx_rays_irradiance: SH rows [probes, 36] and rays [n, 8] in host memory -> the irradiance rows float32 [n, 4], complete"""
+        g = _grid(grid, "rays_irradiance")
+        sh = np.ascontiguousarray(sh, np.float32).reshape(-1, 36)
+        if grid is not None and sh.shape[0] != grid.probes:
+            raise ValueError("rays_irradiance: one SH row per probe of the grid")
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros((rays.shape[0], 4), np.float32)
+        self._check(LIB.flx_rays_irradiance(self._h, int(texture_width), g, _fp(sh), _fp(rays), rays.shape[0], _fp(out)), "flx_rays_irradiance")
+        return out
+
+    def frame_irradiance_device(self, params, grid, sh, out=None):
+        """flx_frame_irradiance_device: the irradiance image of a frame — frame_surface_device's position and normal planes and the lookup behind them.  params:
+        FrameParams (read as frame_surface_device reads them); sh: as for volume_irradiance_device; out: None (a new float32 tensor [height, width, 4]), such a
+        tensor, or an address.  Returns the image ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        g = _grid(grid, "frame_irradiance_device")
+        width, height = (int(params.width), int(params.height)) if params is not None else (0, 0)
+        s = self._device_out(sh, (grid.probes if grid is not None else 0) * 144, "frame_irradiance_device", "sh")
+        if out is None:
+            import torch
+            out = torch.empty((height, width, 4), dtype=torch.float32, device="cuda:%d" % self._device)
+        o = self._device_out(out, width * height * 16, "frame_irradiance_device", "out")
+        self._check(LIB.flx_frame_irradiance_device(self._h, C.byref(params) if params is not None else None, g, C.c_void_p(s), C.c_void_p(o)), "flx_frame_irradiance_device")
+        return out
+
+    def frame_irradiance(self, params, grid, sh):
+        """flx_frame_irradiance: SH rows [probes, 36] in host memory -> the irradiance image float32 [height, width, 4], complete"""
+        g = _grid(grid, "frame_irradiance")
+        sh = np.ascontiguousarray(sh, np.float32).reshape(-1, 36)
+        if grid is not None and sh.shape[0] != grid.probes:
+            raise ValueError("frame_irradiance: one SH row per probe of the grid")
+        width, height = (int(params.width), int(params.height)) if params is not None else (0, 0)
+        out = np.zeros((height, width, 4), np.float32)
+        self._check(LIB.flx_frame_irradiance(self._h, C.byref(params) if params is not None else None, g, _fp(sh), _fp(out)), "flx_frame_irradiance")
+        return out
+
+    def last_volume(self):
+        """flx_debug_last_volume -> dict (zeros when no lookup ran): n (points), slabs, slab (points of a full one), probes, flags, source (0 planes of the caller's,
+        1 rays, 2 a frame), groups (workgroups of the last slab's lookup).  Waits for nothing."""
+        out = (C.c_uint32 * 8)()
+        self._check(LIB.flx_debug_last_volume(self._h, out), "flx_debug_last_volume")
+        return dict(zip(("n", "slabs", "slab", "probes", "flags", "source", "groups"), list(out)[:7]))
 
     # -- surface rows -------------------------------------------------------------------------------
     def _surface_out(self, out, n, fields, call):

@@ -347,6 +347,47 @@ class PathTracerHIP {
     return native().probeIrradiance(row.byteOffset === 0 && row.buffer.byteLength === 144 ? row : Float32Array.from(row), Float32Array.from(normal));
   }
 
+  /* PROBE VOLUMES: a regular grid of light probes baked on the device, and the irradiance it gives surface points (include/flexlight_hip_debug.h "probe volumes").
+   * grid: { origin: [x, y, z], spacing: [x, y, z], count: [nx, ny, nz], normalBias = 0, floor = 0.05, visibility = true } — probe (ix, iy, iz) lies at
+   * origin + i * spacing and has index (iz ny + iy) nx + ix.  options: traceProbes' (faceSize, sky, order and traceRays').  Returns a handle { grid, probes,
+   * rows() } whose SH rows STAY ON THE DEVICE (flx_volume_bake_device): renderIrradiance and irradianceRays read them there; rows() fetches them as a Float32Array of
+   * 36 floats per probe, traceProbes' rows of the grid's positions bit for bit.  It waits for the bake. */
+  bakeVolume (grid, options) {
+    if (this._devices) throw new Error('bakeVolume: one GPU only (a group of GPUs traces no rays)');
+    const o = options || {};
+    if (o.order !== undefined && o.order !== 'hits') throw new TypeError("bakeVolume: order is 'hits' or left out");
+    const three = (v, what) => { const a = Array.from(v || []); if (a.length !== 3) throw new TypeError('bakeVolume: ' + what + ' is [x, y, z]'); return a; };
+    const g = { origin: three(grid.origin, 'origin'), spacing: three(grid.spacing, 'spacing'), count: three(grid.count, 'count'),
+      normalBias: grid.normalBias === undefined ? 0 : grid.normalBias, floor: grid.floor === undefined ? 0.05 : grid.floor, visibility: grid.visibility === undefined ? true : !!grid.visibility };
+    const sky = o.sky === undefined ? [0, 0, 0] : Array.from(o.sky);
+    if (sky.length !== 3) throw new TypeError('bakeVolume: sky is [r, g, b]');
+    this._uploadFrameState();
+    const context = this._context();
+    const probe = { faceSize: o.faceSize === undefined ? 8 : o.faceSize, order: o.order === 'hits' ? 1 : 0, sky };
+    const handle = native().bakeVolume(context, g, this.traceParams(options), probe);
+    return { grid: g, probes: g.count[0] * g.count[1] * g.count[2], _handle: handle, rows: () => new Float32Array(native().volumeRows(context, handle)) };
+  }
+
+  /* The irradiance IMAGE of the frame the next renderFrame() would trace without jitter (flx_frame_irradiance_device): per pixel the irradiance the volume gives
+   * the primary hit's position and ray-facing normal — r g b and the sum of the weights; a pixel that hits nothing is 0 0 0 0.  Nothing but the image crosses the
+   * bus.  volume: bakeVolume's handle.  Returns a Float32Array of 4 floats per pixel, row 0 on top, with width and height beside it. */
+  renderIrradiance (volume) {
+    if (this._devices) throw new Error('renderIrradiance: one GPU only (a group of GPUs casts no rays)');
+    if (!volume || !volume._handle) throw new TypeError('renderIrradiance: volume is what bakeVolume returned');
+    this._uploadFrameState();
+    const p = this.frameParams();
+    return Object.assign(new Float32Array(native().frameIrradiance(this._context(), p, volume._handle)), { width: p.width, height: p.height });
+  }
+
+  /* The same for rays of the application's own (flx_rays_irradiance_device): rays are castRays' rows; returns a Float32Array of 4 floats per ray. */
+  irradianceRays (rays, volume) {
+    if (this._devices) throw new Error('irradianceRays: one GPU only (a group of GPUs casts no rays)');
+    if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('irradianceRays: rays is a Float32Array of 8 floats per ray');
+    if (!volume || !volume._handle) throw new TypeError('irradianceRays: volume is what bakeVolume returned');
+    this._uploadFrameState();
+    return new Float32Array(native().raysIrradiance(this._context(), rays, Math.floor(2048 / this.scene.standardTextureSizes[0]), volume._handle));
+  }
+
   /* A ray IMAGE, traced and DENOISED: any projection the application makes rays for — a panorama, a fisheye or orthographic view, a stereo pair, a probe's faces, a
    * reflection buffer — through the renderer's own filter (flx_rays_image, include/flexlight_hip_debug.h "ray queries").  rays: traceRays' rows, width * height of
    * them in image order, row 0 on top.  options: traceRays' plus hdr (by default config.hdr), the chain's tone map.  Per ray the five filter planes are what a frame

@@ -9,6 +9,7 @@
  * (no node-gyp, no network): napi/Makefile.
  */
 #include <node_api.h>
+#include <hip/hip_runtime_api.h>      /* bakeVolume's SH rows stay in device memory between calls: hipMalloc, hipMemcpy, hipFree and nothing else */
 
 #include <cstdint>
 #include <cstring>
@@ -44,6 +45,7 @@ static bool get_args(napi_env env, napi_callback_info info, size_t want, napi_va
  * memory stops being that frame's: a JavaScript holder of an old frame then reads an empty array, never freed memory. */
 struct CtxBox {
   flx_context *ctx = nullptr;              /* first member: a handle also reads as flx_context ** */
+  int device = 0;                          /* the GPU it was created on (bakeVolume allocates there) */
   struct View { const void *ptr; napi_ref ref; };
   std::vector<View> views;
   bool busy = false;                       /* a frameEndAsync is waiting for the GPU on a worker thread: the context is that thread's until its promise settles */
@@ -137,6 +139,7 @@ static napi_value CreateContext(napi_env env, napi_callback_info info) {
   napi_value ext;
   CtxBox *box = new CtxBox();
   box->ctx = ctx;
+  box->device = device;
   NAPI_OK(env, napi_create_external(env, box, finalize_ctx, nullptr, &ext));
   return ext;
 }
@@ -448,6 +451,161 @@ static napi_value ProbeIrradiance(napi_env env, napi_callback_info info) {
   flx_probe_irradiance((const float *)row, (const float *)normal, (float *)out);
   NAPI_OK(env, napi_create_typedarray(env, napi_float32_array, 3, buf, 0, &array));
   return array;
+}
+
+/* PROBE VOLUMES (include/flexlight_hip_debug.h "probe volumes").  A volume handle owns the grid's SH rows IN DEVICE MEMORY — baked there by flx_volume_bake_device and
+ * read there by the lookups, so that a frame's irradiance costs no upload — and a second device buffer the lookups of host rays stage through, grown and never
+ * shrunk.  It keeps its context's handle alive and frees its memory when JavaScript lets go of it. */
+struct VolumeBox {
+  flx_volume_grid grid;
+  uint32_t probes = 0;
+  int device = 0;
+  void *d_sh = nullptr, *d_io = nullptr;
+  size_t io_bytes = 0;
+  napi_ref context = nullptr;
+};
+static void finalize_volume(napi_env env, void *data, void *) {
+  VolumeBox *v = static_cast<VolumeBox *>(data);
+  if (hipSetDevice(v->device) == hipSuccess) { (void)hipFree(v->d_sh); (void)hipFree(v->d_io); }
+  if (v->context) napi_delete_reference(env, v->context);
+  delete v;
+}
+static bool hip_ok(napi_env env, hipError_t e, const char *what) {
+  if (e == hipSuccess) return true;
+  napi_throw_error(env, nullptr, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
+  return false;
+}
+/* the volume's staging holds `bytes` */
+static bool volume_room(napi_env env, VolumeBox *v, size_t bytes) {
+  if (v->io_bytes >= bytes) return true;
+  if (!hip_ok(env, hipSetDevice(v->device), "hipSetDevice") || !hip_ok(env, hipFree(v->d_io), "hipFree")) return false;
+  v->d_io = nullptr; v->io_bytes = 0;
+  if (!hip_ok(env, hipMalloc(&v->d_io, bytes), "hipMalloc")) return false;
+  v->io_bytes = bytes;
+  return true;
+}
+static VolumeBox *get_volume(napi_env env, napi_value v, const CtxBox *box) {
+  void *p = nullptr;
+  if (napi_get_value_external(env, v, &p) != napi_ok || !p) { napi_throw_type_error(env, nullptr, "expected a volume handle"); return nullptr; }
+  VolumeBox *volume = static_cast<VolumeBox *>(p);
+  if (volume->device != box->device) { napi_throw_error(env, nullptr, "the volume was baked on another GPU"); return nullptr; }
+  return volume;
+}
+/* { origin[3], spacing[3], count[3], normalBias, floor, visibility } -> flx_volume_grid; the library judges the values */
+static bool read_grid(napi_env env, napi_value o, flx_volume_grid *g) {
+  memset(g, 0, sizeof *g);
+  float count[3];
+  double d = 0;
+  if (!floats(env, o, "origin", g->origin, 3) || !floats(env, o, "spacing", g->spacing, 3) || !floats(env, o, "count", count, 3)) return false;
+  for (int a = 0; a < 3; a++) {
+    if (!(count[a] >= 0.0f && count[a] <= 4294967040.0f) || count[a] != (float)(uint32_t)count[a]) { napi_throw_range_error(env, nullptr, "volume grid: count holds three whole numbers a uint32 holds"); return false; }
+    g->count[a] = (uint32_t)count[a];
+  }
+  if (!num(env, o, "normalBias", &d)) return false; g->normal_bias = (float)d;
+  if (!num(env, o, "floor", &d)) return false; g->floor = (float)d;
+  d = 1; if (!num(env, o, "visibility", &d, false)) return false; g->flags = d != 0.0 ? FLX_VOLUME_VISIBILITY : 0u;
+  return true;
+}
+
+/* bakeVolume(handle, grid, params (traceRays'), { faceSize, order, sky[3] }) -> volume handle: flx_volume_bake_device into device memory the handle owns */
+static napi_value BakeVolume(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  if (!box) return nullptr;
+  flx_volume_grid grid;
+  flx_trace_params p;
+  flx_probe_params q;
+  if (!read_grid(env, argv[1], &grid) || !read_trace_params(env, argv[2], "bakeVolume", &p)) return nullptr;
+  memset(&q, 0, sizeof q);
+  napi_value v;
+  if (napi_get_named_property(env, argv[3], "faceSize", &v) != napi_ok || napi_get_value_uint32(env, v, &q.face_size) != napi_ok ||
+      napi_get_named_property(env, argv[3], "order", &v) != napi_ok || napi_get_value_uint32(env, v, &q.order) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "bakeVolume: faceSize and order are numbers");
+    return nullptr;
+  }
+  if (!floats(env, argv[3], "sky", q.sky, 3)) return nullptr;
+  /* a grid the library refuses (a count of 0, 2^31 probes or more) gets no memory: the library says why */
+  const uint64_t xy = (uint64_t)grid.count[0] * grid.count[1];
+  const uint64_t probes = xy <= 0x7fffffffull ? xy * grid.count[2] : xy;
+  if (probes == 0 || probes > 0x7fffffffull) return fail(env, box->ctx, "flx_volume_bake_device", flx_volume_bake_device(box->ctx, &p, &q, &grid, nullptr, nullptr));
+  VolumeBox *volume = new VolumeBox();
+  volume->grid = grid; volume->probes = (uint32_t)probes; volume->device = box->device;
+  napi_value ext;
+  if (napi_create_external(env, volume, finalize_volume, nullptr, &ext) != napi_ok) { delete volume; napi_throw_error(env, nullptr, "N-API call failed: napi_create_external"); return nullptr; }
+  NAPI_OK(env, napi_create_reference(env, argv[0], 1, &volume->context));
+  if (!hip_ok(env, hipSetDevice(box->device), "hipSetDevice") || !hip_ok(env, hipMalloc(&volume->d_sh, (size_t)probes * 144), "hipMalloc")) return nullptr;
+  flx_status rc = flx_volume_bake_device(box->ctx, &p, &q, &grid, volume->d_sh, nullptr);
+  if (rc == FLX_OK) rc = flx_sync(box->ctx);
+  if (rc != FLX_OK) return fail(env, box->ctx, "flx_volume_bake_device", rc);
+  return ext;
+}
+
+/* volumeRows(handle, volume) -> ArrayBuffer(144 probes): the SH rows, fetched from the device */
+static napi_value VolumeRows(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  if (!get_args(env, info, 2, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  VolumeBox *volume = box ? get_volume(env, argv[1], box) : nullptr;
+  if (!volume) return nullptr;
+  void *rows = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, (size_t)volume->probes * 144, &rows, &buf));
+  flx_status rc = flx_sync(box->ctx);
+  if (rc != FLX_OK) return fail(env, box->ctx, "flx_sync", rc);
+  if (!hip_ok(env, hipSetDevice(box->device), "hipSetDevice") || !hip_ok(env, hipMemcpy(rows, volume->d_sh, (size_t)volume->probes * 144, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
+  return buf;
+}
+
+/* frameIrradiance(handle, params, volume) -> ArrayBuffer(16 width height): flx_frame_irradiance_device on the volume's rows, the image fetched */
+static napi_value FrameIrradiance(napi_env env, napi_callback_info info) {
+  napi_value argv[3];
+  if (!get_args(env, info, 3, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  if (!box) return nullptr;
+  flx_frame_params p;
+  if (!read_params(env, argv[1], &p)) return nullptr;
+  VolumeBox *volume = get_volume(env, argv[2], box);
+  if (!volume) return nullptr;
+  if ((uint64_t)p.width * p.height > 0xffffffffull) { napi_throw_range_error(env, nullptr, "frameIrradiance: the frame has more than 2^32 - 1 pixels"); return nullptr; }
+  const size_t bytes = (size_t)p.width * p.height * 16;
+  void *image = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, bytes, &image, &buf));
+  if (!volume_room(env, volume, bytes ? bytes : 16)) return nullptr;
+  flx_status rc = flx_frame_irradiance_device(box->ctx, &p, &volume->grid, volume->d_sh, volume->d_io);
+  if (rc == FLX_OK) rc = flx_sync(box->ctx);
+  if (rc != FLX_OK) return fail(env, box->ctx, "flx_frame_irradiance_device", rc);
+  if (!hip_ok(env, hipMemcpy(image, volume->d_io, bytes, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
+  return buf;
+}
+
+/* raysIrradiance(handle, rays Float32Array(8 n), textureWidth, volume) -> ArrayBuffer(16 n): flx_rays_irradiance_device on the volume's rows; the rays go up into
+ * the volume's staging, the rows come down from behind them */
+static napi_value RaysIrradiance(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  if (!box) return nullptr;
+  void *rays; size_t len; int32_t tw;
+  if (!typed(env, argv[1], napi_float32_array, &rays, &len)) return nullptr;
+  if (napi_get_value_int32(env, argv[2], &tw) != napi_ok) { napi_throw_type_error(env, nullptr, "raysIrradiance: textureWidth is not a number"); return nullptr; }
+  if (len % 8 != 0 || len / 8 > 0xffffffffu) { napi_throw_range_error(env, nullptr, "raysIrradiance: a ray needs 8 floats (origin, one unused, direction, one unused)"); return nullptr; }
+  VolumeBox *volume = get_volume(env, argv[3], box);
+  if (!volume) return nullptr;
+  const size_t n = len / 8;
+  void *rows = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, n * 16, &rows, &buf));
+  if (n == 0) return buf;
+  if (!volume_room(env, volume, n * 48)) return nullptr;
+  char *d_rays = static_cast<char *>(volume->d_io), *d_rows = d_rays + n * 32;
+  if (!hip_ok(env, hipMemcpy(d_rays, rays, n * 32, hipMemcpyHostToDevice), "hipMemcpy")) return nullptr;
+  flx_status rc = flx_rays_irradiance_device(box->ctx, tw, &volume->grid, volume->d_sh, d_rays, (uint32_t)n, d_rows, nullptr);
+  if (rc == FLX_OK) rc = flx_sync(box->ctx);
+  if (rc != FLX_OK) return fail(env, box->ctx, "flx_rays_irradiance_device", rc);
+  if (!hip_ok(env, hipMemcpy(rows, d_rows, n * 16, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
+  return buf;
 }
 
 /* rayImage(handle, rays Float32Array(8 width height), width, height, params (traceRays'), hdr) -> ArrayBuffer(16 width height): flx_rays_image, the rays in image
@@ -1486,7 +1644,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "traceProbes", TraceProbes }, { "probeIrradiance", ProbeIrradiance }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "traceProbes", TraceProbes }, { "probeIrradiance", ProbeIrradiance }, { "bakeVolume", BakeVolume }, { "volumeRows", VolumeRows }, { "frameIrradiance", FrameIrradiance }, { "raysIrradiance", RaysIrradiance }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas }, { "uploadTextures", UploadTextures }, { "updateTexture", UpdateTexture },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
