@@ -1,5 +1,5 @@
-"""Helpers of the light-probe tests (test_probes_cpu.py, test_probes_gpu.py, test_probes_js_gpu.py): the CPU reference built once per session, synthetic
-radiance rows, and a float64 restatement of include/flx_probe.h's quadrature."""
+"""Helpers of the light-probe tests (test_probes_cpu.py, test_probes_gpu.py, test_probe_seams_gpu.py, test_probes_js_gpu.py): the CPU reference built once per
+session, synthetic radiance rows, poisoned device outputs, and a float64 restatement of include/flx_probe.h's quadrature."""
 import os
 import sys
 
@@ -11,6 +11,7 @@ import flx_probe_ref  # noqa: E402
 POSITION = (0.0, -1.5, 2.25)            # a zero and a negative component
 K = (0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396)
 A = (np.pi, 2.0 * np.pi / 3.0, np.pi / 4.0)
+SPARE = 8               # rows behind the last one of a poisoned output that must keep their poison
 EPSILON = {1: 0.910, 2: 0.0396, 3: 0.0281, 4: 0.0153, 8: 0.00383, 16: 0.00096, 32: 0.00024}      # sum d_omega = 4 pi (1 + e_w), as the header prints it
 
 _ref = []
@@ -21,6 +22,20 @@ def reference(tmp_path_factory):
     if not _ref:
         _ref.append(flx_probe_ref.build(str(tmp_path_factory.mktemp("probe_ref"))))
     return _ref[0]
+
+
+def poisoned(rows, row_bytes):
+    """a device output of that many rows and SPARE rows behind them, every byte 0xA5"""
+    import torch
+    return torch.full(((rows + SPARE) * row_bytes,), 0xA5, dtype=torch.uint8, device="cuda")
+
+
+def finished(ctx, out, rows, row_words):
+    """a poisoned output after the call -> its uint32 [rows, row_words]: nothing past the last row was written"""
+    ctx.sync()
+    words = out.cpu().numpy().view(np.uint32)
+    assert (words[rows * row_words:] == 0xA5A5A5A5).all()
+    return words[:rows * row_words].reshape(rows, row_words)
 
 
 def positions_of(n, seed=3):

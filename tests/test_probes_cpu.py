@@ -18,6 +18,7 @@ CALLS = ("flx_probe_rays_device", "flx_probe_rays", "flx_probe_reduce_device", "
          "flx_debug_set_probe_chunk", "flx_debug_last_probes")
 ARGS_CASES = 838        # the cases tests/probe_args_main.cc runs
 SIZES = (1, 2, 3, 4, 8, 16, 32)      # the header's table
+LARGE = (48, 64, 128, 256)           # beyond the table, up to the largest face the library accepts: 36 .. 6 144 terms a slot, 96 times the terms of a 32 face at 256
 # The float32 sums against the float64 restatement of the SAME quadrature, relative to the sum's scale.  Each bound is the worst deviation observed over the
 # test's cases (beside it, and in profiles/probes.txt) with a margin of 4x: the order of the additions makes the error depend on the input.
 WEIGHT_SUM_BOUND = 4 * 1.36e-7          # observed 1.36e-07
@@ -69,83 +70,103 @@ def relative(got, want, scale):
     return float(np.abs(np.asarray(got, np.float64) - want).max() / scale)
 
 
+def epsilon_of(w, dw):
+    """e_w of the float64 weights: the header's table where it has the size; beyond it e_w w w, which tends to a constant (0.245037 at 48, 0.245035 at 256), is
+    held within 0.244 .. 0.246 and the float64 value itself is used"""
+    epsilon = float(dw.sum() / (4.0 * np.pi) - 1.0)
+    if w in EPSILON:
+        return EPSILON[w]
+    assert 0.244 <= epsilon * w * w <= 0.246, (w, epsilon)
+    return epsilon
+
+
+def report(what, worst):
+    """worst: {face size: deviation}; printed size by size (profiles/probes.txt has the rows) -> the worst of all"""
+    print("%s: worst relative deviation %.3g (%s)" % (what, max(worst.values()), ", ".join("%d: %.3g" % kv for kv in sorted(worst.items()))))
+    return max(worst.values())
+
+
 def test_the_weight_sum_is_the_tables(ref):
-    worst = 0.0
-    for w in SIZES:
+    worst = {}
+    for w in SIZES + LARGE:
         weights = ref.weights(w)
         _, dw, _ = quadrature64(w)
         assert np.abs(weights - dw).max() <= 2.0 ** -22 * dw.max()                       # each weight: five roundings
         epsilon = dw.sum() / (4.0 * np.pi) - 1.0
-        digits = 3 if w == 1 else (4 if w < 8 else 5)
-        assert round(epsilon, digits) == EPSILON[w], (w, epsilon)
+        if w in SIZES:
+            digits = 3 if w == 1 else (4 if w < 8 else 5)
+            assert round(epsilon, digits) == EPSILON[w], (w, epsilon)
+        else:
+            assert 0.244 <= epsilon * w * w <= 0.246, (w, epsilon)                       # the table ends at 32; e_w w w tends to a constant
         rows = hit_rows(np.ones((6 * w * w, 3)))
         total = ref.reduce(rows, 1, w)[0, 3]
-        worst = max(worst, relative(total, dw.sum(), dw.sum()))
-    print("weight sum: worst relative deviation %.3g" % worst)
-    assert worst <= WEIGHT_SUM_BOUND, worst
+        worst[w] = relative(total, dw.sum(), dw.sum())
+    assert report("weight sum", worst) <= WEIGHT_SUM_BOUND, worst
 
 
 def test_constant_radiance_gives_band_zero_alone(ref):
     colour = np.array([0.5, 1.0, 2.0])
-    worst = 0.0
-    for w in SIZES:
+    worst = {}
+    for w in SIZES + LARGE:
         _, dw, _ = quadrature64(w)
         sh = ref.reduce(hit_rows(np.tile(colour, (6 * w * w, 1)), distance=3.0), 1, w).reshape(9, 4)
         want = sh64(w, np.tile(colour, (6 * w * w, 1)))
         scale = dw.sum() * colour.max()
-        worst = max(worst, relative(sh[:, 0:3], want, scale))
+        worst[w] = relative(sh[:, 0:3], want, scale)
         assert np.abs(want[0] - K[0] * dw.sum() * colour).max() <= 1e-12 * scale          # coefficient 0 = K0 sum d_omega L
         assert np.abs(want[1:]).max() <= 1e-12 * scale                                    # the cube's symmetry: the other eight vanish in the quadrature itself
         # the four extra sums: every texel hits at distance 3
-        worst = max(worst, relative(sh[2, 3], 3.0 * dw.sum(), 3.0 * dw.sum()), relative(sh[3, 3], 9.0 * dw.sum(), 9.0 * dw.sum()))
+        worst[w] = max(worst[w], relative(sh[2, 3], 3.0 * dw.sum(), 3.0 * dw.sum()), relative(sh[3, 3], 9.0 * dw.sum(), 9.0 * dw.sum()))
         assert sh[0, 3] == sh[1, 3] and (sh[4:, 3] == 0.0).all()
-    print("constant radiance: worst relative deviation %.3g" % worst)
-    assert worst <= CONSTANT_BOUND, worst
+    assert report("constant radiance", worst) <= CONSTANT_BOUND, worst
 
 
 def test_linear_radiance_recovers_band_one(ref):
     """L_c(d) = 1 + a_c . d: coefficients 1 .. 3 are K1 a_c (y, z, x) times the quadrature's second moments, which the float64 restatement has"""
     a = np.array([[0.3, -0.2, 0.5], [-0.7, 0.1, 0.25], [0.0, 0.9, -0.4]])      # a_c, one row a channel
-    worst = 0.0
-    for w in SIZES:
+    worst = {}
+    for w in SIZES + LARGE:
         d, dw, _ = quadrature64(w)
         radiance = 1.0 + d @ a.T
         sh = ref.reduce(hit_rows(radiance), 1, w).reshape(9, 4)
         want = sh64(w, radiance)
         scale = dw.sum() * np.abs(radiance).max()
-        worst = max(worst, relative(sh[:, 0:3], want, scale))
+        worst[w] = relative(sh[:, 0:3], want, scale)
         if w >= 8:      # the quadrature's second moments are 4 pi / 3 within its own error e_w: band 1 is a, in SH order y, z, x
             band1 = want[1:4] / (K[1] * 4.0 * np.pi / 3.0)
-            assert np.abs(band1 - a.T[[1, 2, 0]]).max() <= 4.0 * EPSILON[w]
-    print("linear radiance: worst relative deviation %.3g" % worst)
-    assert worst <= LINEAR_BOUND, worst
+            assert np.abs(band1 - a.T[[1, 2, 0]]).max() <= 4.0 * epsilon_of(w, dw)
+    assert report("linear radiance", worst) <= LINEAR_BOUND, worst
 
 
 def test_irradiance_under_a_uniform_sky(ref):
     """every texel misses and the sky is 1: E = pi (1 + e_w) for any normal"""
     from flexlight_hip import capi
     normals = np.array([[0, 0, 1], [0, 1, 0], [-1, 0, 0], [0.6, 0.0, -0.8], [0.48, -0.6, 0.64]], np.float32)
-    worst = 0.0
-    for w in SIZES:
+    worst = {}
+    for w in SIZES + LARGE:
         _, dw, _ = quadrature64(w)
+        epsilon = epsilon_of(w, dw)
+        worst[w] = 0.0
         sh = ref.reduce(synthetic_radiance(1, w, seed=1, all_miss=True), 1, w, sky=(1.0, 1.0, 1.0))
         assert sh[0, 7] == 0.0 and sh[0, 11] == 0.0 and sh[0, 15] == 0.0 and sh[0, 3] > 0.0      # no coverage, no distances
         coefficients = sh64(w, np.ones((6 * w * w, 3)))
         for n in normals:
             got = ref.irradiance(sh, n)
             want = irradiance64(coefficients, n)
-            worst = max(worst, relative(got, want, np.pi * (1.0 + EPSILON[w])))
+            worst[w] = max(worst[w], relative(got, want, np.pi * (1.0 + epsilon)))
             assert np.abs(want - np.pi * dw.sum() / (4.0 * np.pi)).max() <= 1e-12
             assert np.array_equal(capi.probe_irradiance(sh[0], n).view(np.uint32), got.view(np.uint32))      # the library's export is the same definition
-        assert round(float(want[0]) / np.pi - 1.0, 3 if w == 1 else (4 if w < 8 else 5)) == EPSILON[w]
-    print("irradiance: worst relative deviation %.3g" % worst)
-    assert worst <= IRRADIANCE_BOUND, worst
+        if w in SIZES:
+            assert round(float(want[0]) / np.pi - 1.0, 3 if w == 1 else (4 if w < 8 else 5)) == EPSILON[w]
+        else:
+            assert 0.244 <= (float(want[0]) / np.pi - 1.0) * w * w <= 0.246
+    assert report("irradiance", worst) <= IRRADIANCE_BOUND, worst
 
 
 def test_the_reduction_adds_in_the_slots_order(ref):
     """the 64 slots and the xor tree, restated in numpy float32 for one sum (d_omega over the hits), equal the reference's word bit for bit: sizes whose slots own no,
-    one or two, exactly six and many texels"""
-    for w in (1, 2, 3, 4, 8, 11):
+    one or two, exactly six, many, and exactly twenty-four texels"""
+    for w in (1, 2, 3, 4, 8, 11, 16):
         rows = synthetic_radiance(1, w, seed=w)
         weights = ref.weights(w)
         term = np.where(rows[:, 3] != 0, weights, np.float32(0.0)).astype(np.float32)

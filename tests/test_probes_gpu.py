@@ -6,12 +6,11 @@ import pytest
 import torch
 
 from flexlight_hip import capi
-from probe_util import assert_same_words, cornell_probes, positions_of, reference, synthetic_radiance
+from probe_util import assert_same_words, cornell_probes, finished, poisoned, positions_of, reference, synthetic_radiance
 from rays_trace_util import trace_params
 
 pytestmark = pytest.mark.gpu
 
-SPARE = 8               # rows behind the last one that must keep their poison
 SIZES = (1, 2, 3, 4, 5, 8, 11)       # w w below 256 (the face is the lane's own), 8: 64; R below 64 for 1 .. 3 (slots without a texel), 4: one or two texels a slot, 8: exactly six, 11: w w = 121 across workgroups
 COUNTS = (1, 3, 4, 5, 9)             # 1, 3, 5: the last workgroup of the reduction has waves without a probe
 WIDE = (16, 32)                      # w w = 256 and 1024: a workgroup of k_probe_rays lies within one face, which one or four workgroups cover
@@ -20,18 +19,6 @@ WIDE = (16, 32)                      # w w = 256 and 1024: a workgroup of k_prob
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
     return reference(tmp_path_factory)
-
-
-def poisoned(rows, row_bytes):
-    return torch.full(((rows + SPARE) * row_bytes,), 0xA5, dtype=torch.uint8, device="cuda")
-
-
-def finished(ctx, out, rows, row_words):
-    """a poisoned output after the call -> its uint32 [rows, row_words]: nothing past the last row was written"""
-    ctx.sync()
-    words = out.cpu().numpy().view(np.uint32)
-    assert (words[rows * row_words:] == 0xA5A5A5A5).all()
-    return words[:rows * row_words].reshape(rows, row_words)
 
 
 def device_rays(ctx, positions, w):
