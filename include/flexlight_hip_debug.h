@@ -592,8 +592,8 @@ flx_status flx_debug_last_probes(flx_context *ctx, uint32_t out[8]);
  *   6. W and S_c start at 0.0f and add w_k and w_k E_k,c (the product first) in ascending k — also where t == 0: one path.
  *   7. The row is (S_0 / W, S_1 / W, S_2 / W, W); four 0.0f where W <= 0.  A NaN W is neither > 0 nor <= 0 and takes the quotients: a NaN anywhere gives some NaN.
  * WHERE THE ISSUE OF AN ORDER WAS OPEN it is fixed as written above: products before the sums that take them, sums of three left to right, x before y before z.
- * THE MOMENTS ARE THOSE OF THE WHOLE SPHERE, not of a direction: the visibility weight is isotropic (include/flx_volume.h says what that costs); a directional
- * visibility map is left out, and the flag turns the isotropic test off.
+ * THE MOMENTS ARE THOSE OF THE WHOLE SPHERE, not of a direction: the visibility weight is isotropic (include/flx_volume.h says what that costs); the directional
+ * visibility map is include/flx_volume_map.h's and has calls of its own ("directional visibility" below), and the flag turns the test off.
  * flx_volume_positions_device writes the grid's nx ny nz positions as rows of 4 floats (word 3 is 0.0f), flx_probes_sh_device's input; it needs NO SCENE.
  * flx_volume_bake_device writes them into a buffer the context owns and runs flx_probes_sh_device from there — there is no second probe path —: bit for bit the
  * two calls one after the other.  flx_volume_irradiance_device is the lookup for n points: d_sh the grid's SH rows, d_positions and d_normals planes of n rows of 16
@@ -638,6 +638,69 @@ void flx_volume_irradiance_of(const flx_volume_grid *grid, const float *sh_rows,
  * [2] the points of a full slab, [3] the grid's probes, [4] the grid's flags, [5] 1 for rays, 2 for a frame, 0 for planes of the caller's, [6] workgroups of the last
  * slab's k_volume_irradiance, [7] zero.  (The kernel has one path: there is no count of waves by path to report.)  It waits for nothing. */
 flx_status flx_debug_last_volume(flx_context *ctx, uint32_t out[8]);
+/* DIRECTIONAL VISIBILITY: an octahedral map of filtered distance moments per probe, reduced on the device from the radiance rows the SH row is reduced from, baked
+ * with the volume, and read by the lookup in place of the SH row's whole-sphere moments — the cure for light leaking through walls and for open rooms dimmed for
+ * nothing.  All of it is calls of its own beside the ones above, which do what they did.  Every float is defined bit for bit in include/flx_volume_map.h, which the
+ * kernels (csrc/flx_volume_map.hip: k_probe_map; csrc/flx_volume.hip: k_volume_irradiance_map) and a CPU reference compile alike.
+ * THE MAP (flx_volume_map): m x m bins, bin b = by m + bx, each a row of 4 floats; probe p's rows start at row p m m of the maps array.  The centre of bin (bx, by)
+ * in the octahedral square is u = ndc(bx, m), v = ndc(by, m), ndc(i, m) = (((float)i + 0.5) / (float)m) 2 - 1 (flx_camera_ndc).
+ * DECODE (u, v) to a direction: z = (1 - |u|) - |v|; where z < 0: x = (1 - |v|) sgn(u), y = (1 - |u|) sgn(v), sgn(a) = (a >= 0) ? 1 : -1, the products exact;
+ *   otherwise x = u, y = v; l = sqrt((x x + y y) + z z); three quotients by l.
+ * ENCODE a direction to a bin: l1 = (|x| + |y|) + |z|; where not l1 > 0 the bin is 0; px = x / l1, py = y / l1; where z < 0 the decode's two expressions on (px, py);
+ *   per axis g = ((p + 1) 0.5) (float)m, g = (g >= 0) ? g : 0 (a NaN becomes 0), the index min((uint32_t)g, m - 1).  No index leaves the map.
+ * THE TERMS of cube texel t for a bin of direction b: direction d and d_omega of the texel are the probe reduction's; c = (dx bx + dy by) + dz bz, c = (c > 0) ? c : 0,
+ *   c squared `sharpness` times, g = d_omega c.  The texel is a hit where word 3 of its radiance row is not 0.0f; s is word 4.  The bin's row is (sum of g over hits,
+ *   of g s over hits, of g (s s) over hits, of g over all texels); a miss adds 0.0f to the first three.
+ * THE ORDER OF THE FOUR SUMS is the probe reduction's, word for word: 64 slots; slot j adds its texels j, j + 64, .. in ascending order onto 0.0f; then for off = 1,
+ *   2, 4, 8, 16, 32 every slot becomes v[j] + v[j ^ off].  A sum that meets a NaN is some NaN.
+ * THE DIRECTIONAL WEIGHT: with dir of step 5 of the lookup above (from the sample point to the probe), q = the row of the bin of (-dir0, -dir1, -dir2) — the nearest
+ *   bin —; wv = 1 unless FLX_VOLUME_VISIBILITY is set and q[0] > 0; then mean = q[1] / q[0], mean2 = q[2] / q[0], and from there step 5's text unchanged.  A bin that
+ *   nothing hit leaves the probe fully visible in that direction.  Everything else of the lookup is as above.
+ * WHERE THE ISSUE OF AN ORDER WAS OPEN it is fixed as written here: x before y before z, sums of three left to right, the fold's operands 1 - |v| and 1 - |u| each
+ *   one difference, s s before its product with g, by before bx only in b = by m + bx.
+ * LEFT OUT: bilinear taps between bins, map borders, hysteresis, probe relocation, maps for groups of GPUs.
+ * flx_probe_map_device reduces n_probes * 6 w w radiance rows to n_probes * m m map rows; it needs NO SCENE.  flx_probes_sh_map_device is flx_probes_sh_device's
+ * chunk loop — the same function — with k_probe_map enqueued beside k_probe_sh on each chunk's radiance: bit for bit the separate calls' rows, whatever the chunk.
+ * flx_volume_bake_map_device is flx_volume_bake_device with maps.  flx_volume_irradiance_map_device, flx_rays_irradiance_map_device and
+ * flx_frame_irradiance_map_device are their siblings plus (map, d_maps), one implementation behind both.  flx_volume_irradiance_map_of is the lookup of one point on
+ * the host.  Ordering, producer_stream, the frame server and n == 0 are the siblings'.  The calls without _device are the same for host arrays.
+ * Refusals, each FLX_ERR_INVALID with a message of its own, nothing enqueued and the outputs untouched, asked after the siblings' own, which pass through in their
+ * words: map NULL; size 0 or above 16; sharpness above 8; a reserved word that is not 0; n_probes * m * m of 2^31 rows or more (a maps array ends below 2^35 bytes);
+ * a maps array that is NULL, not memory of the context's device, not 16-byte aligned, in an allocation too short, or that overlaps another array of the call. */
+typedef struct flx_volume_map {
+  uint32_t size;        /* m: 1 .. 16 bins along the octahedral square's edge */
+  uint32_t sharpness;   /* k: 0 .. 8, the filter's exponent is 2^k */
+  uint32_t reserved[2]; /* 0 */
+} flx_volume_map;
+flx_status flx_probe_map_device(flx_context *ctx, const void *d_radiance /* n_probes * 6 w w rows of 32 bytes */, uint32_t n_probes, uint32_t face_size, const flx_volume_map *map,
+                                void *d_maps /* n_probes * m m float4 */, void *producer_stream /* hipStream_t that wrote the radiance, or NULL */);
+flx_status flx_probe_map(flx_context *ctx, const void *radiance, uint32_t n_probes, uint32_t face_size, const flx_volume_map *map, float *maps);      /* host arrays */
+flx_status flx_probes_sh_map_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_map *map, const void *d_positions,
+                                    uint32_t n_probes, void *d_sh /* n_probes * 9 float4 */, void *d_maps /* n_probes * m m float4 */, void *producer_stream);
+flx_status flx_probes_sh_map(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_map *map, const float *positions, uint32_t n_probes,
+                             float *sh, float *maps);      /* host arrays */
+flx_status flx_volume_bake_map_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map,
+                                      void *d_sh, void *d_maps, void *producer_stream);
+flx_status flx_volume_bake_map(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map, float *sh,
+                               float *maps);      /* host arrays */
+flx_status flx_volume_irradiance_map_device(flx_context *ctx, const flx_volume_grid *grid, const void *d_sh, const void *d_positions, const void *d_normals, uint32_t n, void *d_out,
+                                            const flx_volume_map *map, const void *d_maps /* nx ny nz * m m float4 */, void *producer_stream);
+flx_status flx_volume_irradiance_map(flx_context *ctx, const flx_volume_grid *grid, const float *sh, const float *positions, const float *normals, uint32_t n, float *out,
+                                     const flx_volume_map *map, const float *maps);      /* host arrays */
+flx_status flx_rays_irradiance_map_device(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const void *d_sh, const void *d_rays, uint32_t n, void *d_out,
+                                          const flx_volume_map *map, const void *d_maps, void *producer_stream);
+flx_status flx_rays_irradiance_map(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const float *sh, const float *rays, uint32_t n, float *out,
+                                   const flx_volume_map *map, const float *maps);      /* host arrays */
+flx_status flx_frame_irradiance_map_device(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const void *d_sh, void *d_out, const flx_volume_map *map,
+                                           const void *d_maps);
+flx_status flx_frame_irradiance_map(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const float *sh, float *out, const flx_volume_map *map,
+                                    const float *maps);      /* host arrays */
+void flx_volume_irradiance_map_of(const flx_volume_grid *grid, const flx_volume_map *map, const float *sh_rows, const float *map_rows, const float position[4], const float normal[4],
+                                  float out[4]);
+/* The last map reduction — flx_probe_map[_device], or the last chunk's of flx_probes_sh_map[_device] / flx_volume_bake_map[_device] — (zeros if none): out[0] its
+ * probes (of the whole call), [1] m, [2] k, [3] launches of k_probe_map (of the last chunk), [4] workgroups of its last launch, [5] the face size, [6], [7] zero.  It
+ * waits for nothing. */
+flx_status flx_debug_last_volume_map(flx_context *ctx, uint32_t out[8]);
 /* SURFACE ROWS: what the surface is where a ray first hits — the question between "where does it hit" (flx_rays_cast) and "what radiance comes back"
  * (flx_rays_trace, flx_render).  The planes (AOVs) a denoiser of the caller's own, compositing or the shading of a hybrid renderer needs beside the noisy radiance:
  * position, geometric normal, shading normal, texture coordinates, and albedo, RME and TPO with the atlases applied.  They are the first thing lightTrace computes

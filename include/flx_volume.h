@@ -12,8 +12,9 @@
  * THE MOMENTS ARE THOSE OF THE WHOLE SPHERE, NOT OF A DIRECTION.  A row's words 7, 11 and 15 are sums over every texel that hit: their quotients are the mean and
  * the mean square of the distance to whatever the probe sees, all around.  The visibility weight is Chebyshev's bound on "a surface as far as this point lies in
  * front of the probe" under that one distribution, so it is ISOTROPIC: it dims a probe for points further away than its surroundings on average, whatever lies
- * between the two.  It keeps light from leaking through walls where probes sit close to them and it darkens open rooms seen from a corner; a directional
- * (octahedral) visibility map per probe is left out.  FLX_VOLUME_VISIBILITY is a flag so that a caller can turn the isotropic test off.
+ * between the two.  It keeps light from leaking through walls where probes sit close to them and it darkens open rooms seen from a corner; the directional
+ * (octahedral) visibility map per probe that cures both is flx_volume_map.h's, read by calls of its own beside these.  FLX_VOLUME_VISIBILITY is a flag so that a
+ * caller can turn the test off, isotropic or directional.
  */
 #ifndef FLX_VOLUME_H
 #define FLX_VOLUME_H
@@ -87,7 +88,8 @@ FLX_HD uint32_t flx_volume_corner(const flx_volume_grid *g, const flx_volume_cel
  *   wv = 1 unless the grid's FLX_VOLUME_VISIBILITY is set and sh[7] > 0.  Then mean = sh[11] / sh[7], mean2 = sh[15] / sh[7], var = |mean2 - mean mean| (the
  *        product first); where dist > mean: delta = dist - mean, den = var + delta delta, ch = den > 0 ? var / den : 0, wv = flx_max((ch ch) ch, floor) — a NaN
  *        cube stays a NaN —; otherwise wv = 1. */
-FLX_HD float flx_volume_weight(const flx_volume_grid *g, const flx_volume_cell *c, uint32_t k, const float n[3], const float sh[36]) {
+/* the first part of the weight, which a directional map (flx_volume_map.h) shares: -> t wb; *dist_out and dir_out: dist and dir as defined above */
+FLX_HD float flx_volume_weight_base(const flx_volume_grid *g, const flx_volume_cell *c, uint32_t k, const float n[3], float *dist_out, float dir_out[3]) {
   float t[3], d[3];
   for (int a = 0; a < 3; a++) {
     t[a] = ((k >> a) & 1u) ? c->f[a] : 1.0f - c->f[a];
@@ -106,21 +108,35 @@ FLX_HD float flx_volume_weight(const flx_volume_grid *g, const flx_volume_cell *
   const float half = (cosine + 1.0f) * 0.5f;
   const float half2 = half * half;
   const float wb = half2 + FLX_VOLUME_BACK_FLOOR;
+  *dist_out = dist;
+  dir_out[0] = dir0; dir_out[1] = dir1; dir_out[2] = dir2;
+  return tri * wb;
+}
+
+/* the second part: wv of the moments' quotients mean and mean2 for a point dist away — Chebyshev's bound, cubed, kept above floor; 1 where dist > mean does not hold */
+FLX_HD float flx_volume_visibility(float mean, float mean2, float dist, float floor) {
+  const float mm = mean * mean;
+  const float var = flx_abs(mean2 - mm);
+  float wv = 1.0f;
+  if (dist > mean) {
+    const float delta = dist - mean;
+    const float dd = delta * delta;
+    const float den = var + dd;
+    const float ch = den > 0.0f ? var / den : 0.0f;
+    const float ch2 = ch * ch;
+    wv = flx_max(ch2 * ch, floor);
+  }
+  return wv;
+}
+
+FLX_HD float flx_volume_weight(const flx_volume_grid *g, const flx_volume_cell *c, uint32_t k, const float n[3], const float sh[36]) {
+  float dist, dir[3];
+  const float tb = flx_volume_weight_base(g, c, k, n, &dist, dir);
   float wv = 1.0f;
   if ((g->flags & FLX_VOLUME_VISIBILITY) != 0u && sh[7] > 0.0f) {
     const float mean = sh[11] / sh[7], mean2 = sh[15] / sh[7];
-    const float mm = mean * mean;
-    const float var = flx_abs(mean2 - mm);
-    if (dist > mean) {
-      const float delta = dist - mean;
-      const float dd = delta * delta;
-      const float den = var + dd;
-      const float ch = den > 0.0f ? var / den : 0.0f;
-      const float ch2 = ch * ch;
-      wv = flx_max(ch2 * ch, g->floor);
-    }
+    wv = flx_volume_visibility(mean, mean2, dist, g->floor);
   }
-  const float tb = tri * wb;
   return tb * wv;
 }
 

@@ -5,8 +5,9 @@
  * renderer.irradianceRays() return.
  *   node tools/render_irradiance.js <scene> --origin x,y,z --spacing x,y,z --count nx,ny,nz --rows rows.bin --out image.bin [--rays rays.f32 --rays-out rays.bin
  *                              --bias B --floor F --visibility 0|1 --face W --order hits --sky r,g,b --samples S --bounces B --seed X --config-spp S
- *                              --config-bounces B --width W --height H]
+ *                              --config-bounces B --width W --height H --map size,sharpness --maps maps.bin]
  *   rows.bin: 36 float32 per probe; image.bin: 4 float32 per pixel of the W x H frame, row 0 on top; rays.bin: 4 float32 per ray of rays.f32 (8 float32 per ray).
+ *   --map: the volume is baked with directional visibility (bakeVolume's options.map) and the lookups use it; maps.bin: 4 float32 per bin of every probe.
  *   The last line printed is JSON: the grid, the trace params, the frame params and the transform arrays the renderer used, so that a caller can repeat the calls.
  */
 const fs = require('fs');
@@ -44,7 +45,9 @@ const write = (file, a) => fs.writeFileSync(file, Buffer.from(a.buffer, a.byteOf
   if (opt('--seed') !== undefined) options.randomSeed = Number(opt('--seed'));
   if (opt('--order') !== undefined) options.order = opt('--order');
   if (opt('--sky') !== undefined) options.sky = opt('--sky').split(',').map(Number);
+  if (opt('--map') !== undefined) { const m = opt('--map').split(',').map(Number); options.map = { size: m[0], sharpness: m[1] }; }
   const volume = renderer.bakeVolume(grid, options);
+  if (volume.maps) write(opt('--maps', 'maps.bin'), volume.maps());
   const image = renderer.renderIrradiance(volume);
   write(opt('--rows', 'rows.bin'), volume.rows());
   write(opt('--out', 'image.bin'), image);
@@ -58,6 +61,6 @@ const write = (file, a) => fs.writeFileSync(file, Buffer.from(a.buffer, a.byteOf
   const tr = Transform.buildWGL2Arrays();
   console.log(JSON.stringify({ probes: volume.probes, grid: volume.grid, width: image.width, height: image.height, rays, faceSize: options.faceSize,
     order: options.order === undefined ? null : options.order, trace: renderer.traceParams(options), params: renderer.frameParams(), rotation: Array.from(tr[0]), shift: Array.from(tr[1]),
-    renderer: renderer.type }));
+    renderer: renderer.type, map: volume.map === undefined ? null : volume.map }));
   renderer.halt();
 })().catch(e => { console.error(e); process.exit(1); });

@@ -304,6 +304,10 @@ struct flx_context {
    * variants' SH rows; all grown and never shrunk.  What the last lookup ran (flx_debug_last_volume) */
   DeviceBuffer<float4> d_volume_positions, d_volume_surface, d_volume_sh;
   struct VolumeLaunch { uint32_t n = 0, slabs = 0, slab = 0, probes = 0, flags = 0, source = 0, groups = 0; } last_volume;
+  /* directional visibility (flx_volume_map.hip): the host variants' map rows, going up or coming down; grown and never shrunk.  What the last map reduction ran
+   * (flx_debug_last_volume_map) */
+  DeviceBuffer<float4> d_volume_maps;
+  struct VolumeMapLaunch { uint32_t probes = 0, size = 0, sharpness = 0, launches = 0, groups = 0, face_size = 0; } last_volume_map;
   /* uploads: pinned staging ring */
   PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};

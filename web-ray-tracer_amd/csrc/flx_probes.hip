@@ -13,13 +13,15 @@
  *
  * flx_probes_sh_device cuts the probes into chunks of at most 2^21 rays and runs, per chunk and on the context's stream, k_probe_rays into ctx->d_probe_rays,
  * flx_rays_trace_ordered_device from there into ctx->d_probe_radiance — there is no second trace implementation — and k_probe_sh into the chunk's rows of the
- * output.  The host-memory calls are the ray-batch calls' shared path (flx_rays_host.h). */
+ * output.  flx_probes_sh_map_device is the same loop — the same function — with k_probe_map (flx_volume_map.hip) enqueued beside k_probe_sh on each chunk's radiance.
+ * The host-memory calls are the ray-batch calls' shared path (flx_rays_host.h). */
 #include <string>
 
 #include "flx_context.h"
 #include "flx_probe.h"
 #include "flx_probe_args.h"
 #include "flx_rays_host.h"
+#include "flx_volume_map_host.h"
 
 namespace flx {
 
@@ -198,15 +200,21 @@ static flx_status probes_refused(flx_context *ctx, const flx_trace_params *trace
   return s ? s : probe_refusal(ctx, params_check(params), call);
 }
 
-extern "C" flx_status flx_probes_sh_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const void *d_positions, uint32_t n_probes, void *d_sh,
-                                           void *producer_stream) {
-  static const char *const call = "flx_probes_sh_device";
+/* flx_probes_sh_device and flx_probes_sh_map_device: ONE LOOP.  has_map: k_probe_map is enqueued beside k_probe_sh on each chunk's radiance (flx_volume_map.hip),
+ * into the chunk's rows of d_maps; the map's refusals are asked after the siblings' own. */
+static flx_status probes_sh_run(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, bool has_map, const flx_volume_map *map, const void *d_positions,
+                                uint32_t n_probes, void *d_sh, void *d_maps, void *producer_stream, const char *call) {
   if (!ctx) return FLX_ERR_INVALID;
+  uint32_t map_rows = 0;
   flx_status s = probes_refused(ctx, trace, params, call);
-  if (s || n_probes == 0u) return s;
+  if (s || (has_map && (s = flx_volume_map_refused(ctx, map, n_probes, &map_rows, call))) || n_probes == 0u) return s;
   if ((s = arrays_refused(ctx, d_positions, (uint64_t)n_probes * FLX_PROBE_POSITION_BYTES, "the positions are not n_probes rows of 16 bytes", d_sh,
                           (uint64_t)n_probes * FLX_PROBE_SH_BYTES, "the SH rows are not n_probes rows of 144 bytes", call)))
     return s;
+  if (has_map) {
+    const flx_map_other others[2] = { { d_positions, (uint64_t)n_probes * FLX_PROBE_POSITION_BYTES }, { d_sh, (uint64_t)n_probes * FLX_PROBE_SH_BYTES } };
+    if ((s = flx_volume_maps_refused(ctx, d_maps, map_rows, others, 2, call))) return s;
+  }
   const flx_probe_grid g = flx_probe_grid_of(params->face_size);
   const uint32_t chunk = flx_probe_chunk(params->face_size, ctx->probe_chunk);
   const uint32_t most = n_probes < chunk ? n_probes : chunk;
@@ -220,6 +228,7 @@ extern "C" flx_status flx_probes_sh_device(flx_context *ctx, const flx_trace_par
     if ((s = rays_enqueue(ctx, (const float4 *)d_positions + first, m, g, ctx->d_probe_rays.get()))) return s;
     if ((s = flx_rays_trace_ordered_device(ctx, trace, ctx->d_probe_rays.get(), ctx->d_probe_radiance.get(), m * g.rays, params->order, nullptr))) return s;
     if ((s = reduce_enqueue(ctx, ctx->d_probe_radiance.get(), m, g, params->sky, (float4 *)d_sh + (size_t)first * 9u))) return s;
+    if (has_map && (s = flx_probe_map_enqueue(ctx, ctx->d_probe_radiance.get(), m, g, *map, (float4 *)d_maps + (size_t)first * (map->size * map->size), n_probes))) return s;
     groups = flx_probe_reduce_groups(m);
     chunks++;
     if (n_probes - first <= chunk) break;                   /* (first + chunk could wrap) */
@@ -228,6 +237,31 @@ extern "C" flx_status flx_probes_sh_device(flx_context *ctx, const flx_trace_par
   ran.chunks = chunks; ran.chunk = chunk; ran.face_size = params->face_size; ran.n = n_probes; ran.order = params->order; ran.rays = g.rays; ran.reduce_groups = groups;
   ctx->last_probes = ran;
   return FLX_OK;
+}
+
+extern "C" flx_status flx_probes_sh_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const void *d_positions, uint32_t n_probes, void *d_sh,
+                                           void *producer_stream) {
+  return probes_sh_run(ctx, trace, params, false, nullptr, d_positions, n_probes, d_sh, nullptr, producer_stream, "flx_probes_sh_device");
+}
+
+extern "C" flx_status flx_probes_sh_map_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_map *map, const void *d_positions,
+                                               uint32_t n_probes, void *d_sh, void *d_maps, void *producer_stream) {
+  return probes_sh_run(ctx, trace, params, true, map, d_positions, n_probes, d_sh, d_maps, producer_stream, "flx_probes_sh_map_device");
+}
+
+extern "C" flx_status flx_probes_sh_map(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_map *map, const float *positions,
+                                        uint32_t n_probes, float *sh, float *maps) {
+  static const char *const call = "flx_probes_sh_map";
+  if (!ctx) return FLX_ERR_INVALID;
+  uint32_t map_rows = 0;
+  flx_status s = probes_refused(ctx, trace, params, call);
+  if (s || (s = flx_volume_map_refused(ctx, map, n_probes, &map_rows, call)) || n_probes == 0u) return s;
+  if (!positions || !sh) return probe_refusal(ctx, FLX_PROBE_NULL, call);
+  if (!maps) return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": the maps array is NULL");
+  return flx_rays_from_host(ctx, nullptr, 0u, [&]() {
+    flx_status up = positions_up(ctx, positions, n_probes);
+    return up ? up : flx_probes_sh_map_device(ctx, trace, params, map, ctx->d_probe_positions.get(), n_probes, ctx->d_query_hits.get(), ctx->d_volume_maps.get(), nullptr);
+  }, flx_down(&ctx->d_query_hits, (size_t)n_probes * 9u, sh), flx_down(&ctx->d_volume_maps, (size_t)map_rows, maps));
 }
 
 extern "C" flx_status flx_probes_sh(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const float *positions, uint32_t n_probes, float *sh) {

@@ -13,6 +13,10 @@
  *   agreed, read the eight rows through wave-uniform addresses as scalar loads was built and measured on the dragon at 1080p: 0.088 ms against this gather's 0.094,
  *   the two runs' ranges overlapping (profiles/volume.txt).  It was deleted as the issue of its keeping was set: faster only if outside the spread.
  * No LDS, no atomics, no scratch (make resources).
+ *   k_volume_irradiance_map is the same body instantiated with a map (include/flx_volume_map.h, "directional visibility"): per corner the encode of the direction
+ *   from the probe to the point and one 16-byte gather of that bin's row, whose moments stand in for the SH row's words 7, 11 and 15.  The instantiation without a
+ *   map is the code it was.  Every lookup call and its _map sibling are one implementation (irradiance_run, rays_run, frame_run), which the plain calls enter with no
+ *   maps; the map's own refusals (flx_volume_map_host.h) are asked after the siblings'.
  *
  * flx_volume_bake_device is k_volume_positions into ctx->d_volume_positions and flx_probes_sh_device from there: there is no second probe path.
  * flx_rays_irradiance_device and flx_frame_irradiance_device are flx_rays_surface_device / flx_frame_surface_device, as they stand, into ctx->d_volume_surface
@@ -23,8 +27,9 @@
 #include "flx_context.h"
 #include "flx_query_args.h"
 #include "flx_rays_host.h"
-#include "flx_volume.h"
 #include "flx_volume_args.h"
+#include "flx_volume_map.h"
+#include "flx_volume_map_host.h"
 
 namespace flx {
 
@@ -49,9 +54,11 @@ __device__ __forceinline__ void load_sh(const float4 *__restrict__ sh, uint32_t 
   }
 }
 
-/* sh: the grid's rows; positions, normals, out: n rows each */
-__global__ __launch_bounds__(VOLUME_THREADS) void k_volume_irradiance(const float4 *__restrict__ sh, const float4 *__restrict__ positions, const float4 *__restrict__ normals,
-                                                                      float4 *__restrict__ out, flx_volume_grid g, uint32_t n) {
+/* sh: the grid's rows; positions, normals, out: n rows each.  MAP: the directional weight (include/flx_volume_map.h) — per corner the encode and one 16-byte gather
+ * of the bin's row from maps (m m rows a probe), in place of the row's words 7, 11 and 15; without it the body is what it was, and maps and map are not read. */
+template <bool MAP>
+__device__ __forceinline__ void volume_irradiance(const float4 *__restrict__ sh, const float4 *__restrict__ maps, const float4 *__restrict__ positions,
+                                                  const float4 *__restrict__ normals, float4 *__restrict__ out, const flx_volume_grid &g, const flx_volume_map &map, uint32_t n) {
   const uint32_t r = blockIdx.x * VOLUME_THREADS + threadIdx.x;      /* (n / 256 + 1 workgroups: no wrap) */
   if (r >= n) return;
   const float4 x = positions[r];
@@ -65,12 +72,33 @@ __global__ __launch_bounds__(VOLUME_THREADS) void k_volume_irradiance(const floa
 #pragma unroll 1
   for (uint32_t k = 0; k < 8u; k++) {
     float row[FLX_PROBE_SH_WORDS];
-    load_sh(sh, flx_volume_corner(&g, &c, k), row);
-    flx_volume_add(sums, flx_volume_weight(&g, &c, k, normal, row), row, normal);
+    const uint32_t p = flx_volume_corner(&g, &c, k);
+    load_sh(sh, p, row);
+    if constexpr (MAP) {
+      float dist, dir[3];
+      const float tb = flx_volume_weight_base(&g, &c, k, normal, &dist, dir);
+      const float4 bin = maps[(size_t)p * flx_volume_map_bins(&map) + flx_volume_map_corner_bin(&map, dir)];      /* (below 2^31 rows: the calls' check) */
+      const float q[4] = { bin.x, bin.y, bin.z, bin.w };
+      flx_volume_add(sums, flx_volume_map_weight(&g, tb, dist, q), row, normal);
+    } else {
+      flx_volume_add(sums, flx_volume_weight(&g, &c, k, normal, row), row, normal);
+    }
   }
   float e[4];
   flx_volume_row(sums, e);
   out[r] = make_float4(e[0], e[1], e[2], e[3]);
+}
+
+__global__ __launch_bounds__(VOLUME_THREADS) void k_volume_irradiance(const float4 *__restrict__ sh, const float4 *__restrict__ positions, const float4 *__restrict__ normals,
+                                                                      float4 *__restrict__ out, flx_volume_grid g, uint32_t n) {
+  const flx_volume_map none = { 0u, 0u, { 0u, 0u } };
+  volume_irradiance<false>(sh, nullptr, positions, normals, out, g, none, n);
+}
+
+__global__ __launch_bounds__(VOLUME_THREADS) void k_volume_irradiance_map(const float4 *__restrict__ sh, const float4 *__restrict__ maps, const float4 *__restrict__ positions,
+                                                                          const float4 *__restrict__ normals, float4 *__restrict__ out, flx_volume_grid g, flx_volume_map map,
+                                                                          uint32_t n) {
+  volume_irradiance<true>(sh, maps, positions, normals, out, g, map, n);
 }
 
 }  // namespace flx
@@ -105,6 +133,14 @@ static flx_status volume_refusal(flx_context *ctx, enum flx_volume_refusal why, 
 /* an array of a device call: what it is, for the message */
 struct VolumeArray { const void *p; uint64_t bytes; const char *what; };
 
+/* the maps of a call: none (the plain calls), or the map and its rows on the device (the _map calls; either may be NULL, which is refused) */
+struct VolumeMaps { const flx_volume_map *map = nullptr; const void *d_maps = nullptr; bool has = false; };
+static VolumeMaps with_maps(const flx_volume_map *map, const void *d_maps) {
+  VolumeMaps maps;
+  maps.map = map; maps.d_maps = d_maps; maps.has = true;
+  return maps;
+}
+
 /* The k arrays of a device call: there, inside 64 bits, memory of the context's device, and apart — in that order. */
 static flx_status arrays_refused(flx_context *ctx, const VolumeArray *arrays, int k, const char *call) {
   uint64_t address[FLX_VOLUME_MAX_ARRAYS], bytes[FLX_VOLUME_MAX_ARRAYS];
@@ -118,14 +154,32 @@ static flx_status arrays_refused(flx_context *ctx, const VolumeArray *arrays, in
   return volume_refusal(ctx, why, call);
 }
 
+/* what a map call asks after its sibling's own refusals: the map and its rows for the grid's probes ... */
+static flx_status maps_params_refused(flx_context *ctx, const VolumeMaps &maps, uint32_t probes, uint32_t *rows, const char *call) {
+  return maps.has ? flx_volume_map_refused(ctx, maps.map, probes, rows, call) : FLX_OK;
+}
+
+/* ... and, behind the sibling's arrays, the maps array against them */
+static flx_status maps_array_refused(flx_context *ctx, const VolumeMaps &maps, uint32_t rows, const VolumeArray *arrays, int k, const char *call) {
+  if (!maps.has) return FLX_OK;
+  flx_map_other others[FLX_VOLUME_MAX_ARRAYS];
+  for (int i = 0; i < k; i++) others[i] = { arrays[i].p, arrays[i].bytes };
+  return flx_volume_maps_refused(ctx, maps.d_maps, rows, others, k, call);
+}
+
 static flx_status positions_enqueue(flx_context *ctx, const flx_volume_grid &g, uint32_t probes, float4 *d_positions) {
   hipLaunchKernelGGL(k_volume_positions, dim3(flx_volume_groups(probes)), dim3(VOLUME_THREADS), 0, ctx->stream, d_positions, g, probes);
   FLX_HIP(ctx, hipGetLastError());
   return FLX_OK;
 }
 
-static flx_status lookup_enqueue(flx_context *ctx, const flx_volume_grid &g, const float4 *d_sh, const float4 *d_positions, const float4 *d_normals, uint32_t n, float4 *d_out) {
-  hipLaunchKernelGGL(k_volume_irradiance, dim3(flx_volume_groups(n)), dim3(VOLUME_THREADS), 0, ctx->stream, d_sh, d_positions, d_normals, d_out, g, n);
+static flx_status lookup_enqueue(flx_context *ctx, const flx_volume_grid &g, const float4 *d_sh, const float4 *d_positions, const float4 *d_normals, uint32_t n, float4 *d_out,
+                                 const VolumeMaps &maps) {
+  if (maps.has)
+    hipLaunchKernelGGL(k_volume_irradiance_map, dim3(flx_volume_groups(n)), dim3(VOLUME_THREADS), 0, ctx->stream, d_sh, (const float4 *)maps.d_maps, d_positions, d_normals, d_out, g,
+                       *maps.map, n);
+  else
+    hipLaunchKernelGGL(k_volume_irradiance, dim3(flx_volume_groups(n)), dim3(VOLUME_THREADS), 0, ctx->stream, d_sh, d_positions, d_normals, d_out, g, n);
   FLX_HIP(ctx, hipGetLastError());
   return FLX_OK;
 }
@@ -166,20 +220,44 @@ static flx_status bake_refused(flx_context *ctx, const flx_trace_params *trace, 
   return s ? s : volume_refusal(ctx, flx_volume_grid_check(grid, probes), call);
 }
 
-extern "C" flx_status flx_volume_bake_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, void *d_sh,
-                                             void *producer_stream) {
-  static const char *const call = "flx_volume_bake_device";
+/* flx_volume_bake_device and flx_volume_bake_map_device: one implementation; d_maps: where the maps go (maps.has) */
+static flx_status bake_run(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, void *d_sh, const VolumeMaps &maps,
+                           void *d_maps, void *producer_stream, const char *call) {
   if (!ctx) return FLX_ERR_INVALID;
-  uint32_t probes = 0;
+  uint32_t probes = 0, rows = 0;
   flx_status s = bake_refused(ctx, trace, params, grid, &probes, call);
-  if (s) return s;
+  if (s || (s = maps_params_refused(ctx, maps, probes, &rows, call))) return s;
   const VolumeArray arrays[1] = { { d_sh, flx_volume_sh_bytes(probes), "the SH rows are not nx * ny * nz rows of 144 bytes" } };
-  if ((s = arrays_refused(ctx, arrays, 1, call))) return s;
+  if ((s = arrays_refused(ctx, arrays, 1, call)) || (s = maps_array_refused(ctx, maps, rows, arrays, 1, call))) return s;
   if ((s = flx_server_stop(ctx))) return s;
   if ((s = flx_grow(ctx, flx_need(&ctx->d_volume_positions, (size_t)probes)))) return s;
   if ((s = flx_wait_for_producer(ctx, producer_stream))) return s;
   if ((s = positions_enqueue(ctx, *grid, probes, ctx->d_volume_positions.get()))) return s;
-  return flx_probes_sh_device(ctx, trace, params, ctx->d_volume_positions.get(), probes, d_sh, nullptr);
+  return maps.has ? flx_probes_sh_map_device(ctx, trace, params, maps.map, ctx->d_volume_positions.get(), probes, d_sh, d_maps, nullptr)
+                  : flx_probes_sh_device(ctx, trace, params, ctx->d_volume_positions.get(), probes, d_sh, nullptr);
+}
+
+extern "C" flx_status flx_volume_bake_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, void *d_sh,
+                                             void *producer_stream) {
+  return bake_run(ctx, trace, params, grid, d_sh, VolumeMaps(), nullptr, producer_stream, "flx_volume_bake_device");
+}
+
+extern "C" flx_status flx_volume_bake_map_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map,
+                                                 void *d_sh, void *d_maps, void *producer_stream) {
+  return bake_run(ctx, trace, params, grid, d_sh, with_maps(map, d_maps), d_maps, producer_stream, "flx_volume_bake_map_device");
+}
+
+extern "C" flx_status flx_volume_bake_map(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map,
+                                          float *sh, float *maps) {
+  static const char *const call = "flx_volume_bake_map";
+  if (!ctx) return FLX_ERR_INVALID;
+  uint32_t probes = 0, rows = 0;
+  flx_status s = bake_refused(ctx, trace, params, grid, &probes, call);
+  if (s || (s = flx_volume_map_refused(ctx, map, probes, &rows, call))) return s;
+  if (!sh) return volume_refusal(ctx, FLX_VOLUME_NULL, call);
+  if (!maps) return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": the maps array is NULL");
+  return flx_rays_from_host(ctx, nullptr, 0u, [&]() { return flx_volume_bake_map_device(ctx, trace, params, grid, map, ctx->d_query_hits.get(), ctx->d_volume_maps.get(), nullptr); },
+                            flx_down(&ctx->d_query_hits, (size_t)probes * 9u, sh), flx_down(&ctx->d_volume_maps, (size_t)rows, maps));
 }
 
 extern "C" flx_status flx_volume_bake(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, float *sh) {
@@ -193,22 +271,32 @@ extern "C" flx_status flx_volume_bake(flx_context *ctx, const flx_trace_params *
                             flx_down(&ctx->d_query_hits, (size_t)probes * 9u, sh));
 }
 
-extern "C" flx_status flx_volume_irradiance_device(flx_context *ctx, const flx_volume_grid *grid, const void *d_sh, const void *d_positions, const void *d_normals, uint32_t n,
-                                                   void *d_out, void *producer_stream) {
-  static const char *const call = "flx_volume_irradiance_device";
+/* THE LOOKUPS: each _device call and its _map sibling are one implementation, `maps` telling them apart. */
+static flx_status irradiance_run(flx_context *ctx, const flx_volume_grid *grid, const void *d_sh, const void *d_positions, const void *d_normals, uint32_t n, void *d_out,
+                                 const VolumeMaps &maps, void *producer_stream, const char *call) {
   if (!ctx) return FLX_ERR_INVALID;
-  uint32_t probes = 0;
+  uint32_t probes = 0, rows = 0;
   flx_status s = volume_refusal(ctx, flx_volume_grid_check(grid, &probes), call);
-  if (s || n == 0u) return s;
+  if (s || (s = maps_params_refused(ctx, maps, probes, &rows, call)) || n == 0u) return s;
   const VolumeArray arrays[4] = { { d_sh, flx_volume_sh_bytes(probes), "the SH rows are not nx * ny * nz rows of 144 bytes" },
                                   { d_positions, flx_volume_plane_bytes(n), "the positions are not n rows of 16 bytes" },
                                   { d_normals, flx_volume_plane_bytes(n), "the normals are not n rows of 16 bytes" },
                                   { d_out, flx_volume_plane_bytes(n), "the irradiance rows are not n rows of 16 bytes" } };
-  if ((s = arrays_refused(ctx, arrays, 4, call))) return s;
+  if ((s = arrays_refused(ctx, arrays, 4, call)) || (s = maps_array_refused(ctx, maps, rows, arrays, 4, call))) return s;
   if ((s = flx_server_stop(ctx)) || (s = flx_wait_for_producer(ctx, producer_stream))) return s;
-  if ((s = lookup_enqueue(ctx, *grid, (const float4 *)d_sh, (const float4 *)d_positions, (const float4 *)d_normals, n, (float4 *)d_out))) return s;
+  if ((s = lookup_enqueue(ctx, *grid, (const float4 *)d_sh, (const float4 *)d_positions, (const float4 *)d_normals, n, (float4 *)d_out, maps))) return s;
   lookup_ran(ctx, *grid, probes, n, 1u, n, 0u, flx_volume_groups(n));
   return FLX_OK;
+}
+
+extern "C" flx_status flx_volume_irradiance_device(flx_context *ctx, const flx_volume_grid *grid, const void *d_sh, const void *d_positions, const void *d_normals, uint32_t n,
+                                                   void *d_out, void *producer_stream) {
+  return irradiance_run(ctx, grid, d_sh, d_positions, d_normals, n, d_out, VolumeMaps(), producer_stream, "flx_volume_irradiance_device");
+}
+
+extern "C" flx_status flx_volume_irradiance_map_device(flx_context *ctx, const flx_volume_grid *grid, const void *d_sh, const void *d_positions, const void *d_normals, uint32_t n,
+                                                       void *d_out, const flx_volume_map *map, const void *d_maps, void *producer_stream) {
+  return irradiance_run(ctx, grid, d_sh, d_positions, d_normals, n, d_out, with_maps(map, d_maps), producer_stream, "flx_volume_irradiance_map_device");
 }
 
 /* the SH rows of a host variant into ctx->d_volume_sh, on the context's stream */
@@ -219,37 +307,67 @@ static flx_status sh_up(flx_context *ctx, const float *sh, uint32_t probes) {
   return FLX_OK;
 }
 
-extern "C" flx_status flx_volume_irradiance(flx_context *ctx, const flx_volume_grid *grid, const float *sh, const float *positions, const float *normals, uint32_t n, float *out) {
-  static const char *const call = "flx_volume_irradiance";
+/* the map rows of a host variant into ctx->d_volume_maps, on the context's stream; -> the call's maps on the device (none where the call has none) */
+static flx_status maps_up(flx_context *ctx, const flx_volume_map *map, const float *maps, uint32_t rows, VolumeMaps *up) {
+  *up = VolumeMaps();
+  if (!map) return FLX_OK;
+  flx_status s = flx_grow(ctx, flx_need(&ctx->d_volume_maps, (size_t)rows));
+  if (s) return s;
+  FLX_HIP(ctx, hipMemcpyAsync(ctx->d_volume_maps.get(), maps, (size_t)flx_volume_map_bytes(rows), hipMemcpyHostToDevice, ctx->stream));
+  *up = with_maps(map, ctx->d_volume_maps.get());
+  return FLX_OK;
+}
+
+/* what a host map call refuses behind its sibling's grid: the map, its rows, a NULL maps array (has_map: the call is a _map call) */
+static flx_status host_maps_refused(flx_context *ctx, bool has_map, const flx_volume_map *map, const float *maps, uint32_t probes, uint32_t *rows, const char *call) {
+  if (!has_map) return FLX_OK;
+  const flx_status s = flx_volume_map_refused(ctx, map, probes, rows, call);
+  if (s) return s;
+  return maps ? FLX_OK : fail(ctx, FLX_ERR_INVALID, std::string(call) + ": the maps array is NULL");
+}
+
+static flx_status irradiance_host(flx_context *ctx, const flx_volume_grid *grid, const float *sh, const float *positions, const float *normals, uint32_t n, float *out, bool has_map,
+                                  const flx_volume_map *map, const float *maps, const char *call) {
   if (!ctx) return FLX_ERR_INVALID;
-  uint32_t probes = 0;
+  uint32_t probes = 0, rows = 0;
   flx_status s = volume_refusal(ctx, flx_volume_grid_check(grid, &probes), call);
-  if (s || n == 0u) return s;
+  if (s || (has_map && (s = flx_volume_map_refused(ctx, map, probes, &rows, call))) || n == 0u) return s;
   if (!sh || !positions || !normals || !out) return volume_refusal(ctx, FLX_VOLUME_NULL, call);
+  if ((s = host_maps_refused(ctx, has_map, map, maps, probes, &rows, call))) return s;
   /* the two planes go up where a ray batch's rays go, one behind the other: n rows of 32 bytes are 2 n rows of 16 */
   return flx_rays_from_host(ctx, nullptr, 0u, [&]() -> flx_status {
+    VolumeMaps dm;
     flx_status up = sh_up(ctx, sh, probes);
-    if (up || (up = flx_grow(ctx, flx_need(&ctx->d_query_rays, (size_t)n * 2u)))) return up;
+    if (up || (up = maps_up(ctx, has_map ? map : nullptr, maps, rows, &dm)) || (up = flx_grow(ctx, flx_need(&ctx->d_query_rays, (size_t)n * 2u)))) return up;
     float4 *planes = ctx->d_query_rays.get();
     FLX_HIP(ctx, hipMemcpyAsync(planes, positions, (size_t)flx_volume_plane_bytes(n), hipMemcpyHostToDevice, ctx->stream));
     FLX_HIP(ctx, hipMemcpyAsync(planes + n, normals, (size_t)flx_volume_plane_bytes(n), hipMemcpyHostToDevice, ctx->stream));
-    return flx_volume_irradiance_device(ctx, grid, ctx->d_volume_sh.get(), planes, planes + n, n, ctx->d_query_hits.get(), nullptr);
+    return irradiance_run(ctx, grid, ctx->d_volume_sh.get(), planes, planes + n, n, ctx->d_query_hits.get(), dm, nullptr,
+                          has_map ? "flx_volume_irradiance_map_device" : "flx_volume_irradiance_device");
   }, flx_down(&ctx->d_query_hits, (size_t)n, out));
 }
 
-extern "C" flx_status flx_rays_irradiance_device(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const void *d_sh, const void *d_rays, uint32_t n, void *d_out,
-                                                 void *producer_stream) {
-  static const char *const call = "flx_rays_irradiance_device";
+extern "C" flx_status flx_volume_irradiance(flx_context *ctx, const flx_volume_grid *grid, const float *sh, const float *positions, const float *normals, uint32_t n, float *out) {
+  return irradiance_host(ctx, grid, sh, positions, normals, n, out, false, nullptr, nullptr, "flx_volume_irradiance");
+}
+
+extern "C" flx_status flx_volume_irradiance_map(flx_context *ctx, const flx_volume_grid *grid, const float *sh, const float *positions, const float *normals, uint32_t n, float *out,
+                                                const flx_volume_map *map, const float *maps) {
+  return irradiance_host(ctx, grid, sh, positions, normals, n, out, true, map, maps, "flx_volume_irradiance_map");
+}
+
+static flx_status rays_run(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const void *d_sh, const void *d_rays, uint32_t n, void *d_out, const VolumeMaps &maps,
+                           void *producer_stream, const char *call) {
   static const uint32_t fields = FLX_SURFACE_POSITION | FLX_SURFACE_NORMAL;
   if (!ctx) return FLX_ERR_INVALID;
   /* the scene and texture_width in the surface call's words (n = 0: it looks at them and at nothing else), then the grid */
-  uint32_t probes = 0;
+  uint32_t probes = 0, rows = 0;
   flx_status s = flx_rays_surface_device(ctx, texture_width, nullptr, 0u, fields, nullptr, nullptr);
-  if (s || (s = volume_refusal(ctx, flx_volume_grid_check(grid, &probes), call)) || n == 0u) return s;
+  if (s || (s = volume_refusal(ctx, flx_volume_grid_check(grid, &probes), call)) || (s = maps_params_refused(ctx, maps, probes, &rows, call)) || n == 0u) return s;
   const VolumeArray arrays[3] = { { d_sh, flx_volume_sh_bytes(probes), "the SH rows are not nx * ny * nz rows of 144 bytes" },
                                   { d_rays, (uint64_t)n * FLX_RAY_ROW_BYTES, "the rays are not n rows of 32 bytes" },
                                   { d_out, flx_volume_plane_bytes(n), "the irradiance rows are not n rows of 16 bytes" } };
-  if ((s = arrays_refused(ctx, arrays, 3, call))) return s;
+  if ((s = arrays_refused(ctx, arrays, 3, call)) || (s = maps_array_refused(ctx, maps, rows, arrays, 3, call))) return s;
   if ((s = flx_server_stop(ctx))) return s;
   const uint32_t slab = flx_trace_slab_rays(1u, ctx->trace_slab), most = n < slab ? n : slab;
   if ((s = flx_grow(ctx, flx_need(&ctx->d_volume_surface, (size_t)most * 2u)))) return s;
@@ -259,7 +377,7 @@ extern "C" flx_status flx_rays_irradiance_device(flx_context *ctx, int32_t textu
     const uint32_t m = (uint32_t)(n - first < slab ? n - first : slab);
     float4 *planes = ctx->d_volume_surface.get();
     if ((s = flx_rays_surface_device(ctx, texture_width, (const float4 *)d_rays + first * 2u, m, fields, planes, nullptr))) return s;
-    if ((s = lookup_enqueue(ctx, *grid, (const float4 *)d_sh, planes, planes + m, m, (float4 *)d_out + first))) return s;
+    if ((s = lookup_enqueue(ctx, *grid, (const float4 *)d_sh, planes, planes + m, m, (float4 *)d_out + first, maps))) return s;
     groups = flx_volume_groups(m);
     slabs++;
   }
@@ -267,17 +385,40 @@ extern "C" flx_status flx_rays_irradiance_device(flx_context *ctx, int32_t textu
   return FLX_OK;
 }
 
-extern "C" flx_status flx_rays_irradiance(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const float *sh, const float *rays, uint32_t n, float *out) {
-  static const char *const call = "flx_rays_irradiance";
+extern "C" flx_status flx_rays_irradiance_device(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const void *d_sh, const void *d_rays, uint32_t n, void *d_out,
+                                                 void *producer_stream) {
+  return rays_run(ctx, texture_width, grid, d_sh, d_rays, n, d_out, VolumeMaps(), producer_stream, "flx_rays_irradiance_device");
+}
+
+extern "C" flx_status flx_rays_irradiance_map_device(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const void *d_sh, const void *d_rays, uint32_t n, void *d_out,
+                                                     const flx_volume_map *map, const void *d_maps, void *producer_stream) {
+  return rays_run(ctx, texture_width, grid, d_sh, d_rays, n, d_out, with_maps(map, d_maps), producer_stream, "flx_rays_irradiance_map_device");
+}
+
+static flx_status rays_host(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const float *sh, const float *rays, uint32_t n, float *out, bool has_map,
+                            const flx_volume_map *map, const float *maps, const char *call) {
   if (!ctx) return FLX_ERR_INVALID;
-  uint32_t probes = 0;
+  uint32_t probes = 0, rows = 0;
   flx_status s = flx_rays_surface_device(ctx, texture_width, nullptr, 0u, FLX_SURFACE_POSITION | FLX_SURFACE_NORMAL, nullptr, nullptr);
-  if (s || (s = volume_refusal(ctx, flx_volume_grid_check(grid, &probes), call)) || n == 0u) return s;
+  if (s || (s = volume_refusal(ctx, flx_volume_grid_check(grid, &probes), call)) || (has_map && (s = flx_volume_map_refused(ctx, map, probes, &rows, call))) || n == 0u) return s;
   if (!sh || !rays || !out) return volume_refusal(ctx, FLX_VOLUME_NULL, call);
+  if ((s = host_maps_refused(ctx, has_map, map, maps, probes, &rows, call))) return s;
   return flx_rays_from_host(ctx, rays, n, [&]() -> flx_status {
+    VolumeMaps dm;
     flx_status up = sh_up(ctx, sh, probes);
-    return up ? up : flx_rays_irradiance_device(ctx, texture_width, grid, ctx->d_volume_sh.get(), ctx->d_query_rays.get(), n, ctx->d_query_hits.get(), nullptr);
+    if (up || (up = maps_up(ctx, has_map ? map : nullptr, maps, rows, &dm))) return up;
+    return rays_run(ctx, texture_width, grid, ctx->d_volume_sh.get(), ctx->d_query_rays.get(), n, ctx->d_query_hits.get(), dm, nullptr,
+                    has_map ? "flx_rays_irradiance_map_device" : "flx_rays_irradiance_device");
   }, flx_down(&ctx->d_query_hits, (size_t)n, out));
+}
+
+extern "C" flx_status flx_rays_irradiance(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const float *sh, const float *rays, uint32_t n, float *out) {
+  return rays_host(ctx, texture_width, grid, sh, rays, n, out, false, nullptr, nullptr, "flx_rays_irradiance");
+}
+
+extern "C" flx_status flx_rays_irradiance_map(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const float *sh, const float *rays, uint32_t n, float *out,
+                                              const flx_volume_map *map, const float *maps) {
+  return rays_host(ctx, texture_width, grid, sh, rays, n, out, true, map, maps, "flx_rays_irradiance_map");
 }
 
 /* what both frame calls refuse before they look at an array: the scene and the frame params in the surface call's words, then the grid */
@@ -286,40 +427,65 @@ static flx_status frame_refused(flx_context *ctx, const flx_frame_params *params
   return s ? s : volume_refusal(ctx, flx_volume_grid_check(grid, probes), call);
 }
 
-extern "C" flx_status flx_frame_irradiance_device(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const void *d_sh, void *d_out) {
-  static const char *const call = "flx_frame_irradiance_device";
+static flx_status frame_run(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const void *d_sh, void *d_out, const VolumeMaps &maps, const char *call) {
   if (!ctx) return FLX_ERR_INVALID;
-  uint32_t probes = 0;
+  uint32_t probes = 0, rows = 0;
   flx_status s = frame_refused(ctx, params, grid, &probes, call);
-  if (s) return s;
+  if (s || (s = maps_params_refused(ctx, maps, probes, &rows, call))) return s;
   const uint32_t n = params->width * params->height;          /* (fits: the surface call's check) */
   const VolumeArray arrays[2] = { { d_sh, flx_volume_sh_bytes(probes), "the SH rows are not nx * ny * nz rows of 144 bytes" },
                                   { d_out, flx_volume_plane_bytes(n), "the irradiance rows are not width * height rows of 16 bytes" } };
-  if ((s = arrays_refused(ctx, arrays, 2, call))) return s;
+  if ((s = arrays_refused(ctx, arrays, 2, call)) || (s = maps_array_refused(ctx, maps, rows, arrays, 2, call))) return s;
   if ((s = flx_server_stop(ctx))) return s;
   if ((s = flx_grow(ctx, flx_need(&ctx->d_volume_surface, (size_t)n * 2u)))) return s;
   float4 *planes = ctx->d_volume_surface.get();
   if ((s = flx_frame_surface_device(ctx, params, FLX_SURFACE_POSITION | FLX_SURFACE_NORMAL, planes))) return s;
-  if ((s = lookup_enqueue(ctx, *grid, (const float4 *)d_sh, planes, planes + n, n, (float4 *)d_out))) return s;
+  if ((s = lookup_enqueue(ctx, *grid, (const float4 *)d_sh, planes, planes + n, n, (float4 *)d_out, maps))) return s;
   lookup_ran(ctx, *grid, probes, n, 1u, n, 2u, flx_volume_groups(n));
   return FLX_OK;
 }
 
-extern "C" flx_status flx_frame_irradiance(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const float *sh, float *out) {
-  static const char *const call = "flx_frame_irradiance";
+extern "C" flx_status flx_frame_irradiance_device(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const void *d_sh, void *d_out) {
+  return frame_run(ctx, params, grid, d_sh, d_out, VolumeMaps(), "flx_frame_irradiance_device");
+}
+
+extern "C" flx_status flx_frame_irradiance_map_device(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const void *d_sh, void *d_out,
+                                                      const flx_volume_map *map, const void *d_maps) {
+  return frame_run(ctx, params, grid, d_sh, d_out, with_maps(map, d_maps), "flx_frame_irradiance_map_device");
+}
+
+static flx_status frame_host(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const float *sh, float *out, bool has_map, const flx_volume_map *map,
+                             const float *maps, const char *call) {
   if (!ctx) return FLX_ERR_INVALID;
-  uint32_t probes = 0;
+  uint32_t probes = 0, rows = 0;
   flx_status s = frame_refused(ctx, params, grid, &probes, call);
   if (s) return s;
   if (!sh || !out) return volume_refusal(ctx, FLX_VOLUME_NULL, call);
+  if ((s = host_maps_refused(ctx, has_map, map, maps, probes, &rows, call))) return s;
   return flx_rays_from_host(ctx, nullptr, 0u, [&]() -> flx_status {
+    VolumeMaps dm;
     flx_status up = sh_up(ctx, sh, probes);
-    return up ? up : flx_frame_irradiance_device(ctx, params, grid, ctx->d_volume_sh.get(), ctx->d_query_hits.get());
+    if (up || (up = maps_up(ctx, has_map ? map : nullptr, maps, rows, &dm))) return up;
+    return frame_run(ctx, params, grid, ctx->d_volume_sh.get(), ctx->d_query_hits.get(), dm, has_map ? "flx_frame_irradiance_map_device" : "flx_frame_irradiance_device");
   }, flx_down(&ctx->d_query_hits, (size_t)params->width * params->height, out));
+}
+
+extern "C" flx_status flx_frame_irradiance(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const float *sh, float *out) {
+  return frame_host(ctx, params, grid, sh, out, false, nullptr, nullptr, "flx_frame_irradiance");
+}
+
+extern "C" flx_status flx_frame_irradiance_map(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const float *sh, float *out, const flx_volume_map *map,
+                                               const float *maps) {
+  return frame_host(ctx, params, grid, sh, out, true, map, maps, "flx_frame_irradiance_map");
 }
 
 extern "C" void flx_volume_irradiance_of(const flx_volume_grid *grid, const float *sh_rows, const float position[4], const float normal[4], float out[4]) {
   flx_volume_lookup(grid, sh_rows, position, normal, out);
+}
+
+extern "C" void flx_volume_irradiance_map_of(const flx_volume_grid *grid, const flx_volume_map *map, const float *sh_rows, const float *map_rows, const float position[4],
+                                             const float normal[4], float out[4]) {
+  flx_volume_map_lookup(grid, map, sh_rows, map_rows, position, normal, out);
 }
 
 extern "C" flx_status flx_debug_last_volume(flx_context *ctx, uint32_t out[8]) {

@@ -46,6 +46,9 @@ EXPORTS = [
     "flx_volume_positions_device", "flx_volume_positions", "flx_volume_bake_device", "flx_volume_bake", "flx_volume_irradiance_device", "flx_volume_irradiance",
     "flx_rays_irradiance_device", "flx_rays_irradiance", "flx_frame_irradiance_device", "flx_frame_irradiance", "flx_volume_irradiance_of",
     "flx_debug_last_volume",
+    "flx_probe_map_device", "flx_probe_map", "flx_probes_sh_map_device", "flx_probes_sh_map", "flx_volume_bake_map_device", "flx_volume_bake_map",
+    "flx_volume_irradiance_map_device", "flx_volume_irradiance_map", "flx_rays_irradiance_map_device", "flx_rays_irradiance_map", "flx_frame_irradiance_map_device",
+    "flx_frame_irradiance_map", "flx_volume_irradiance_map_of", "flx_debug_last_volume_map",
     "flx_textures_upload", "flx_textures_upload_device", "flx_texture_update", "flx_texture_update_device", "flx_group_textures_upload", "flx_group_texture_update",
     "flx_debug_atlas_read",
 ]
@@ -205,6 +208,51 @@ def volume_irradiance_of(grid, sh, position, normal):
     return out[0] if one else out
 
 
+class VolumeMap(C.Structure):
+    """flx_volume_map of include/flexlight_hip_debug.h: the octahedral moment map every probe of a volume carries — size x size bins of 4 floats — and the exponent
+    2^sharpness of the cosine filter its bins are reduced with"""
+    _fields_ = [("size", C.c_uint32), ("sharpness", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    def __init__(self, size=8, sharpness=5, reserved=(0, 0)):
+        super().__init__(int(size), int(sharpness), (C.c_uint32 * 2)(*[int(x) for x in reserved]))
+
+    @property
+    def bins(self):
+        """size x size"""
+        return int(self.size) * int(self.size)
+
+
+def _map(vmap, call):
+    """map of a directional-visibility call -> what ctypes hands the library: a reference, or None (which the library refuses)"""
+    if vmap is not None and not isinstance(vmap, VolumeMap):
+        raise TypeError("%s: map is a VolumeMap" % call)
+    return C.byref(vmap) if vmap is not None else None
+
+
+def _map_rows(vmap, probes):
+    return int(probes) * vmap.bins if vmap is not None else 0
+
+
+def volume_irradiance_map_of(grid, vmap, sh, maps, position, normal):
+    """flx_volume_irradiance_map_of, the library's one definition of the lookup with maps on the host (include/flx_volume_map.h): sh float32 [probes, 36], maps
+    float32 [probes * bins, 4], position [4] or [n, 4], normal [3] or [4] or as many -> float32 [4] or [n, 4]: (E_r, E_g, E_b, W)"""
+    if not isinstance(grid, VolumeGrid) or not isinstance(vmap, VolumeMap):
+        raise TypeError("volume_irradiance_map_of: grid is a VolumeGrid, map a VolumeMap")
+    sh = np.ascontiguousarray(sh, np.float32).reshape(-1, 36)
+    maps = np.ascontiguousarray(maps, np.float32).reshape(-1, 4)
+    if sh.shape[0] != grid.probes or maps.shape[0] != grid.probes * vmap.bins:
+        raise ValueError("volume_irradiance_map_of: one SH row and size x size map rows per probe of the grid")
+    one = np.ndim(position) == 1
+    positions = _surface_rows(np.atleast_2d(position), "positions", "volume_irradiance_map_of")
+    normals = _surface_rows(np.atleast_2d(normal), "normals", "volume_irradiance_map_of")
+    if len(normals) != len(positions):
+        raise ValueError("volume_irradiance_map_of: a normal per position")
+    out = np.zeros((len(positions), 4), np.float32)
+    for k in range(len(positions)):
+        LIB.flx_volume_irradiance_map_of(C.byref(grid), C.byref(vmap), _fp(sh), _fp(maps), _fp(positions[k]), _fp(normals[k]), _fp(out[k]))
+    return out[0] if one else out
+
+
 def probe_ray_count(face_size):
     """rays of a probe of that face size: 6 w w"""
     return 6 * int(face_size) * int(face_size)
@@ -319,6 +367,20 @@ def _load():
         "flx_frame_irradiance": (C.c_int, [vp, C.POINTER(FrameParams), C.POINTER(VolumeGrid), fp, fp]),
         "flx_volume_irradiance_of": (None, [C.POINTER(VolumeGrid), fp, fp, fp, fp]),
         "flx_debug_last_volume": (C.c_int, [vp, C.POINTER(u32)]),
+        "flx_probe_map_device": (C.c_int, [vp, vp, u32, u32, C.POINTER(VolumeMap), vp, vp]),
+        "flx_probe_map": (C.c_int, [vp, vp, u32, u32, C.POINTER(VolumeMap), fp]),
+        "flx_probes_sh_map_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), C.POINTER(VolumeMap), vp, u32, vp, vp, vp]),
+        "flx_probes_sh_map": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), C.POINTER(VolumeMap), fp, u32, fp, fp]),
+        "flx_volume_bake_map_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), C.POINTER(VolumeGrid), C.POINTER(VolumeMap), vp, vp, vp]),
+        "flx_volume_bake_map": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), C.POINTER(VolumeGrid), C.POINTER(VolumeMap), fp, fp]),
+        "flx_volume_irradiance_map_device": (C.c_int, [vp, C.POINTER(VolumeGrid), vp, vp, vp, u32, vp, C.POINTER(VolumeMap), vp, vp]),
+        "flx_volume_irradiance_map": (C.c_int, [vp, C.POINTER(VolumeGrid), fp, fp, fp, u32, fp, C.POINTER(VolumeMap), fp]),
+        "flx_rays_irradiance_map_device": (C.c_int, [vp, C.c_int32, C.POINTER(VolumeGrid), vp, vp, u32, vp, C.POINTER(VolumeMap), vp, vp]),
+        "flx_rays_irradiance_map": (C.c_int, [vp, C.c_int32, C.POINTER(VolumeGrid), fp, fp, u32, fp, C.POINTER(VolumeMap), fp]),
+        "flx_frame_irradiance_map_device": (C.c_int, [vp, C.POINTER(FrameParams), C.POINTER(VolumeGrid), vp, vp, C.POINTER(VolumeMap), vp]),
+        "flx_frame_irradiance_map": (C.c_int, [vp, C.POINTER(FrameParams), C.POINTER(VolumeGrid), fp, fp, C.POINTER(VolumeMap), fp]),
+        "flx_volume_irradiance_map_of": (None, [C.POINTER(VolumeGrid), C.POINTER(VolumeMap), fp, fp, fp, fp, fp]),
+        "flx_debug_last_volume_map": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_textures_upload": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32]),
         "flx_textures_upload_device": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32, vp]),
         "flx_texture_update": (C.c_int, [vp, C.c_int, u32, C.POINTER(Image)]),
@@ -1419,6 +1481,176 @@ class Context:
         out = (C.c_uint32 * 8)()
         self._check(LIB.flx_debug_last_volume(self._h, out), "flx_debug_last_volume")
         return dict(zip(("n", "slabs", "slab", "probes", "flags", "source", "groups"), list(out)[:7]))
+
+    # -- directional visibility: an octahedral moment map per probe, beside the calls above ---------------------
+    def _maps_out(self, maps, vmap, probes, call):
+        """the maps of a *_device call that writes them: None (a new float32 tensor [probes * bins, 4]), such a tensor, or an address -> (what comes back, address)"""
+        rows = _map_rows(vmap, probes)
+        if maps is None:
+            maps = self._new_rows(rows, 4)
+        return maps, self._device_out(maps, rows * 16, call, "maps")
+
+    def probe_map_device(self, radiance, n_probes, face_size, vmap, out=None, stream=None):
+        """flx_probe_map_device: n_probes * 6 w w radiance rows (as for probe_reduce_device) reduced to the probes' octahedral moment maps.  vmap: VolumeMap; out: None
+        (a new float32 tensor [n_probes * bins, 4], probe p's rows from row p * bins), such a tensor, or an address.  Needs no scene.  Returns the rows ENQUEUED ON
+        THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        m, n = _map(vmap, "probe_map_device"), int(n_probes)
+        r = self._device_out(radiance, n * probe_ray_count(face_size) * 32, "probe_map_device", "radiance")
+        out, o = self._maps_out(out, vmap, n, "probe_map_device")
+        self._check(LIB.flx_probe_map_device(self._h, C.c_void_p(r), n, int(face_size), m, C.c_void_p(o), _stream_handle(stream)), "flx_probe_map_device")
+        return out
+
+    def probe_map(self, radiance, n_probes, face_size, vmap):
+        """flx_probe_map: radiance rows in host memory (n_probes * 6 w w x 32 bytes, any dtype) -> map rows float32 [n_probes * bins, 4], complete"""
+        m, n = _map(vmap, "probe_map"), int(n_probes)
+        radiance = np.ascontiguousarray(radiance).reshape(-1)
+        if radiance.nbytes != n * probe_ray_count(face_size) * 32:
+            raise ValueError("probe_map: a radiance row of 32 bytes for every ray of every probe")
+        out = np.zeros((_map_rows(vmap, n), 4), np.float32)
+        self._check(LIB.flx_probe_map(self._h, radiance.ctypes.data_as(C.c_void_p), n, int(face_size), m, _fp(out)), "flx_probe_map")
+        return out
+
+    def probes_sh_map_device(self, positions, trace_params, params, vmap, out=None, maps=None, stream=None):
+        """flx_probes_sh_map_device: probes_sh_device with the probes' maps reduced from the same radiance, chunk by chunk.  out, maps: None (new tensors [n, 36] and
+        [n * bins, 4]), such tensors, or addresses.  Returns (SH rows, map rows) ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        if trace_params is not None and not isinstance(trace_params, TraceParams):
+            raise TypeError("probes_sh_map_device: trace_params is a TraceParams")
+        if params is not None and not isinstance(params, ProbeParams):
+            raise TypeError("probes_sh_map_device: params is a ProbeParams")
+        m = _map(vmap, "probes_sh_map_device")
+        p, n, o, out, stream = self._probe_device_args(positions, out, lambda n: n, 36, stream, "probes_sh_map_device")
+        maps, q = self._maps_out(maps, vmap, n, "probes_sh_map_device")
+        self._check(LIB.flx_probes_sh_map_device(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None, m,
+                                                 C.c_void_p(p), n, C.c_void_p(o), C.c_void_p(q), stream), "flx_probes_sh_map_device")
+        return out, maps
+
+    def probes_sh_map(self, positions, trace_params, params, vmap):
+        """flx_probes_sh_map: positions [n, 3] or [n, 4] in host memory -> (SH rows float32 [n, 36], map rows float32 [n * bins, 4]), complete"""
+        m = _map(vmap, "probes_sh_map")
+        positions = _probe_positions(positions)
+        n = positions.shape[0]
+        out, maps = np.zeros((n, 36), np.float32), np.zeros((_map_rows(vmap, n), 4), np.float32)
+        self._check(LIB.flx_probes_sh_map(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None, m,
+                                          _fp(positions), n, _fp(out), _fp(maps)), "flx_probes_sh_map")
+        return out, maps
+
+    def volume_bake_map_device(self, grid, trace_params, params, vmap, out=None, maps=None, stream=None):
+        """flx_volume_bake_map_device: volume_bake_device with the grid's maps baked beside its SH rows.  Returns (SH rows [probes, 36], map rows [probes * bins, 4])
+        ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE: the _map lookups take them as they are."""
+        if trace_params is not None and not isinstance(trace_params, TraceParams):
+            raise TypeError("volume_bake_map_device: trace_params is a TraceParams")
+        if params is not None and not isinstance(params, ProbeParams):
+            raise TypeError("volume_bake_map_device: params is a ProbeParams")
+        g, m = _grid(grid, "volume_bake_map_device"), _map(vmap, "volume_bake_map_device")
+        probes = grid.probes if grid is not None else 0
+        if out is None:
+            out = self._new_rows(probes, 36)
+        o = self._device_out(out, probes * 144, "volume_bake_map_device", "out")
+        maps, q = self._maps_out(maps, vmap, probes, "volume_bake_map_device")
+        self._check(LIB.flx_volume_bake_map_device(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None, g, m,
+                                                   C.c_void_p(o), C.c_void_p(q), _stream_handle(stream)), "flx_volume_bake_map_device")
+        return out, maps
+
+    def volume_bake_map(self, grid, trace_params, params, vmap):
+        """flx_volume_bake_map: -> (SH rows float32 [probes, 36], map rows float32 [probes * bins, 4]) in host memory, complete"""
+        g, m = _grid(grid, "volume_bake_map"), _map(vmap, "volume_bake_map")
+        probes = grid.probes if grid is not None else 0
+        out, maps = np.zeros((probes, 36), np.float32), np.zeros((_map_rows(vmap, probes), 4), np.float32)
+        self._check(LIB.flx_volume_bake_map(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None, g, m,
+                                            _fp(out), _fp(maps)), "flx_volume_bake_map")
+        return out, maps
+
+    def _maps_in(self, maps, vmap, grid, call):
+        return self._device_out(maps, _map_rows(vmap, grid.probes if grid is not None else 0) * 16, call, "maps")
+
+    def volume_irradiance_map_device(self, grid, sh, positions, normals, vmap, maps, n=None, out=None, stream=None):
+        """flx_volume_irradiance_map_device: volume_irradiance_device with the directional weight.  vmap: VolumeMap; maps: the grid's map rows (a contiguous tensor of
+        probes x bins x 16 bytes on the context's device, or an address).  Returns the rows ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        g, m = _grid(grid, "volume_irradiance_map_device"), _map(vmap, "volume_irradiance_map_device")
+        if n is None:
+            n = positions.shape[0]
+        n = int(n)
+        s = self._device_out(sh, (grid.probes if grid is not None else 0) * 144, "volume_irradiance_map_device", "sh")
+        p = self._device_out(positions, n * 16, "volume_irradiance_map_device", "positions")
+        q = self._device_out(normals, n * 16, "volume_irradiance_map_device", "normals")
+        d = self._maps_in(maps, vmap, grid, "volume_irradiance_map_device")
+        if out is None:
+            out = self._new_rows(n, 4)
+        o = self._device_out(out, n * 16, "volume_irradiance_map_device", "out")
+        self._check(LIB.flx_volume_irradiance_map_device(self._h, g, C.c_void_p(s), C.c_void_p(p), C.c_void_p(q), n, C.c_void_p(o), m, C.c_void_p(d), _stream_handle(stream)),
+                    "flx_volume_irradiance_map_device")
+        return out
+
+    @staticmethod
+    def _host_maps(grid, vmap, sh, maps, call):
+        sh = np.ascontiguousarray(sh, np.float32).reshape(-1, 36)
+        maps = np.ascontiguousarray(maps, np.float32).reshape(-1, 4)
+        if grid is not None and (sh.shape[0] != grid.probes or (vmap is not None and maps.shape[0] != grid.probes * vmap.bins)):
+            raise ValueError("%s: one SH row and size x size map rows per probe of the grid" % call)
+        return sh, maps
+
+    def volume_irradiance_map(self, grid, sh, positions, normals, vmap, maps):
+        """flx_volume_irradiance_map: volume_irradiance with map rows [probes * bins, 4] in host memory -> the irradiance rows float32 [n, 4], complete"""
+        g, m = _grid(grid, "volume_irradiance_map"), _map(vmap, "volume_irradiance_map")
+        sh, maps = self._host_maps(grid, vmap, sh, maps, "volume_irradiance_map")
+        positions, normals = _surface_rows(positions, "positions", "volume_irradiance_map"), _surface_rows(normals, "normals", "volume_irradiance_map")
+        if len(positions) != len(normals):
+            raise ValueError("volume_irradiance_map: a normal per position")
+        out = np.zeros((len(positions), 4), np.float32)
+        self._check(LIB.flx_volume_irradiance_map(self._h, g, _fp(sh), _fp(positions), _fp(normals), len(positions), _fp(out), m, _fp(maps)), "flx_volume_irradiance_map")
+        return out
+
+    def rays_irradiance_map_device(self, grid, sh, rays, vmap, maps, texture_width=32, out=None, stream=None):
+        """flx_rays_irradiance_map_device: rays_irradiance_device with the directional weight.  Returns the rows ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        g, m = _grid(grid, "rays_irradiance_map_device"), _map(vmap, "rays_irradiance_map_device")
+        r, n = _ray_rows(rays, self._device, "rays_irradiance_map_device")
+        s = self._device_out(sh, (grid.probes if grid is not None else 0) * 144, "rays_irradiance_map_device", "sh")
+        d = self._maps_in(maps, vmap, grid, "rays_irradiance_map_device")
+        if out is None:
+            out = self._new_rows(n, 4)
+        o = self._device_out(out, n * 16, "rays_irradiance_map_device", "out")
+        self._check(LIB.flx_rays_irradiance_map_device(self._h, int(texture_width), g, C.c_void_p(s), C.c_void_p(r), n, C.c_void_p(o), m, C.c_void_p(d), _stream_handle(stream)),
+                    "flx_rays_irradiance_map_device")
+        return out
+
+    def rays_irradiance_map(self, grid, sh, rays, vmap, maps, texture_width=32):
+        """flx_rays_irradiance_map: SH rows, rays [n, 8] and map rows in host memory -> the irradiance rows float32 [n, 4], complete"""
+        g, m = _grid(grid, "rays_irradiance_map"), _map(vmap, "rays_irradiance_map")
+        sh, maps = self._host_maps(grid, vmap, sh, maps, "rays_irradiance_map")
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros((rays.shape[0], 4), np.float32)
+        self._check(LIB.flx_rays_irradiance_map(self._h, int(texture_width), g, _fp(sh), _fp(rays), rays.shape[0], _fp(out), m, _fp(maps)), "flx_rays_irradiance_map")
+        return out
+
+    def frame_irradiance_map_device(self, params, grid, sh, vmap, maps, out=None):
+        """flx_frame_irradiance_map_device: frame_irradiance_device with the directional weight.  Returns the image ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        g, m = _grid(grid, "frame_irradiance_map_device"), _map(vmap, "frame_irradiance_map_device")
+        width, height = (int(params.width), int(params.height)) if params is not None else (0, 0)
+        s = self._device_out(sh, (grid.probes if grid is not None else 0) * 144, "frame_irradiance_map_device", "sh")
+        d = self._maps_in(maps, vmap, grid, "frame_irradiance_map_device")
+        if out is None:
+            import torch
+            out = torch.empty((height, width, 4), dtype=torch.float32, device="cuda:%d" % self._device)
+        o = self._device_out(out, width * height * 16, "frame_irradiance_map_device", "out")
+        self._check(LIB.flx_frame_irradiance_map_device(self._h, C.byref(params) if params is not None else None, g, C.c_void_p(s), C.c_void_p(o), m, C.c_void_p(d)),
+                    "flx_frame_irradiance_map_device")
+        return out
+
+    def frame_irradiance_map(self, params, grid, sh, vmap, maps):
+        """flx_frame_irradiance_map: SH rows and map rows in host memory -> the irradiance image float32 [height, width, 4], complete"""
+        g, m = _grid(grid, "frame_irradiance_map"), _map(vmap, "frame_irradiance_map")
+        sh, maps = self._host_maps(grid, vmap, sh, maps, "frame_irradiance_map")
+        width, height = (int(params.width), int(params.height)) if params is not None else (0, 0)
+        out = np.zeros((height, width, 4), np.float32)
+        self._check(LIB.flx_frame_irradiance_map(self._h, C.byref(params) if params is not None else None, g, _fp(sh), _fp(out), m, _fp(maps)), "flx_frame_irradiance_map")
+        return out
+
+    def last_volume_map(self):
+        """flx_debug_last_volume_map -> dict (zeros when no map reduction ran): probes (of the whole call), size, sharpness, launches and groups (workgroups of the last
+        launch) of the last chunk's k_probe_map, face_size.  Waits for nothing."""
+        out = (C.c_uint32 * 8)()
+        self._check(LIB.flx_debug_last_volume_map(self._h, out), "flx_debug_last_volume_map")
+        return dict(zip(("probes", "size", "sharpness", "launches", "groups", "face_size"), list(out)[:6]))
 
     # -- surface rows -------------------------------------------------------------------------------
     def _surface_out(self, out, n, fields, call):

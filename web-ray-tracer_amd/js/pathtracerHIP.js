@@ -351,7 +351,11 @@ class PathTracerHIP {
    * grid: { origin: [x, y, z], spacing: [x, y, z], count: [nx, ny, nz], normalBias = 0, floor = 0.05, visibility = true } — probe (ix, iy, iz) lies at
    * origin + i * spacing and has index (iz ny + iy) nx + ix.  options: traceProbes' (faceSize, sky, order and traceRays').  Returns a handle { grid, probes,
    * rows() } whose SH rows STAY ON THE DEVICE (flx_volume_bake_device): renderIrradiance and irradianceRays read them there; rows() fetches them as a Float32Array of
-   * 36 floats per probe, traceProbes' rows of the grid's positions bit for bit.  It waits for the bake. */
+   * 36 floats per probe, traceProbes' rows of the grid's positions bit for bit.  It waits for the bake.
+   * options.map = { size: 1 .. 16, sharpness: 0 .. 8 = 5 }: DIRECTIONAL VISIBILITY ("directional visibility", flx_volume_bake_map_device) — every probe also gets an
+   * octahedral map of size x size bins of distance moments, baked from the same rays and kept on the device beside the SH rows; renderIrradiance and
+   * irradianceRays then weigh a probe by what it sees TOWARDS the point, not all around: walls stop leaking and open rooms are not dimmed.  The handle has map and
+   * maps() (4 floats per bin) then.  Without options.map every call does what it did. */
   bakeVolume (grid, options) {
     if (this._devices) throw new Error('bakeVolume: one GPU only (a group of GPUs traces no rays)');
     const o = options || {};
@@ -364,11 +368,18 @@ class PathTracerHIP {
     this._uploadFrameState();
     const context = this._context();
     const probe = { faceSize: o.faceSize === undefined ? 8 : o.faceSize, order: o.order === 'hits' ? 1 : 0, sky };
+    if (o.map !== undefined) {
+      if (o.map === null || typeof o.map !== 'object' || typeof o.map.size !== 'number') throw new TypeError('bakeVolume: map is { size, sharpness }');
+      probe.map = { size: o.map.size, sharpness: o.map.sharpness === undefined ? 5 : o.map.sharpness };
+    }
     const handle = native().bakeVolume(context, g, this.traceParams(options), probe);
-    return { grid: g, probes: g.count[0] * g.count[1] * g.count[2], _handle: handle, rows: () => new Float32Array(native().volumeRows(context, handle)) };
+    const volume = { grid: g, probes: g.count[0] * g.count[1] * g.count[2], _handle: handle, rows: () => new Float32Array(native().volumeRows(context, handle)) };
+    if (probe.map) Object.assign(volume, { map: probe.map, maps: () => new Float32Array(native().volumeMaps(context, handle)) });
+    return volume;
   }
 
-  /* The irradiance IMAGE of the frame the next renderFrame() would trace without jitter (flx_frame_irradiance_device): per pixel the irradiance the volume gives
+  /* The irradiance IMAGE of the frame the next renderFrame() would trace without jitter (flx_frame_irradiance_device; flx_frame_irradiance_map_device where the
+   * volume was baked with a map): per pixel the irradiance the volume gives
    * the primary hit's position and ray-facing normal — r g b and the sum of the weights; a pixel that hits nothing is 0 0 0 0.  Nothing but the image crosses the
    * bus.  volume: bakeVolume's handle.  Returns a Float32Array of 4 floats per pixel, row 0 on top, with width and height beside it. */
   renderIrradiance (volume) {
@@ -379,7 +390,7 @@ class PathTracerHIP {
     return Object.assign(new Float32Array(native().frameIrradiance(this._context(), p, volume._handle)), { width: p.width, height: p.height });
   }
 
-  /* The same for rays of the application's own (flx_rays_irradiance_device): rays are castRays' rows; returns a Float32Array of 4 floats per ray. */
+  /* The same for rays of the application's own (flx_rays_irradiance_device; flx_rays_irradiance_map_device where the volume was baked with a map): rays are castRays' rows; returns a Float32Array of 4 floats per ray. */
   irradianceRays (rays, volume) {
     if (this._devices) throw new Error('irradianceRays: one GPU only (a group of GPUs casts no rays)');
     if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('irradianceRays: rays is a Float32Array of 8 floats per ray');

@@ -463,10 +463,14 @@ struct VolumeBox {
   void *d_sh = nullptr, *d_io = nullptr;
   size_t io_bytes = 0;
   napi_ref context = nullptr;
+  /* directional visibility ("directional visibility"): baked with { map: { size, sharpness } }, the handle also owns the probes' octahedral maps in device memory
+   * and the lookups read them (the _map calls); without, d_maps stays NULL and every call is the plain one */
+  flx_volume_map map = { 0u, 0u, { 0u, 0u } };
+  void *d_maps = nullptr;
 };
 static void finalize_volume(napi_env env, void *data, void *) {
   VolumeBox *v = static_cast<VolumeBox *>(data);
-  if (hipSetDevice(v->device) == hipSuccess) { (void)hipFree(v->d_sh); (void)hipFree(v->d_io); }
+  if (hipSetDevice(v->device) == hipSuccess) { (void)hipFree(v->d_sh); (void)hipFree(v->d_io); (void)hipFree(v->d_maps); }
   if (v->context) napi_delete_reference(env, v->context);
   delete v;
 }
@@ -507,7 +511,8 @@ static bool read_grid(napi_env env, napi_value o, flx_volume_grid *g) {
   return true;
 }
 
-/* bakeVolume(handle, grid, params (traceRays'), { faceSize, order, sky[3] }) -> volume handle: flx_volume_bake_device into device memory the handle owns */
+/* bakeVolume(handle, grid, params (traceRays'), { faceSize, order, sky[3], map: { size, sharpness } or undefined }) -> volume handle: flx_volume_bake_device — with a
+ * map flx_volume_bake_map_device — into device memory the handle owns */
 static napi_value BakeVolume(napi_env env, napi_callback_info info) {
   napi_value argv[4];
   if (!get_args(env, info, 4, argv)) return nullptr;
@@ -525,19 +530,38 @@ static napi_value BakeVolume(napi_env env, napi_callback_info info) {
     return nullptr;
   }
   if (!floats(env, argv[3], "sky", q.sky, 3)) return nullptr;
+  flx_volume_map map = { 0u, 0u, { 0u, 0u } };
+  napi_valuetype map_type = napi_undefined;
+  if (napi_get_named_property(env, argv[3], "map", &v) != napi_ok || napi_typeof(env, v, &map_type) != napi_ok) { napi_throw_type_error(env, nullptr, "bakeVolume: map is { size, sharpness }"); return nullptr; }
+  const bool has_map = map_type != napi_undefined;
+  if (has_map) {
+    napi_value field;
+    if (map_type != napi_object || napi_get_named_property(env, v, "size", &field) != napi_ok || napi_get_value_uint32(env, field, &map.size) != napi_ok ||
+        napi_get_named_property(env, v, "sharpness", &field) != napi_ok || napi_get_value_uint32(env, field, &map.sharpness) != napi_ok) {
+      napi_throw_type_error(env, nullptr, "bakeVolume: map is { size, sharpness }, two numbers");
+      return nullptr;
+    }
+  }
   /* a grid the library refuses (a count of 0, 2^31 probes or more) gets no memory: the library says why */
   const uint64_t xy = (uint64_t)grid.count[0] * grid.count[1];
   const uint64_t probes = xy <= 0x7fffffffull ? xy * grid.count[2] : xy;
   if (probes == 0 || probes > 0x7fffffffull) return fail(env, box->ctx, "flx_volume_bake_device", flx_volume_bake_device(box->ctx, &p, &q, &grid, nullptr, nullptr));
+  /* ... and so does a map it refuses (a size outside 1 .. 16, 2^31 rows or more) */
+  const uint64_t map_rows = has_map && map.size >= 1u && map.size <= 16u ? probes * (map.size * map.size) : 0u;
+  if (has_map && (map_rows == 0 || map_rows > 0x7fffffffull))
+    return fail(env, box->ctx, "flx_volume_bake_map_device", flx_volume_bake_map_device(box->ctx, &p, &q, &grid, &map, nullptr, nullptr, nullptr));
   VolumeBox *volume = new VolumeBox();
   volume->grid = grid; volume->probes = (uint32_t)probes; volume->device = box->device;
   napi_value ext;
   if (napi_create_external(env, volume, finalize_volume, nullptr, &ext) != napi_ok) { delete volume; napi_throw_error(env, nullptr, "N-API call failed: napi_create_external"); return nullptr; }
   NAPI_OK(env, napi_create_reference(env, argv[0], 1, &volume->context));
   if (!hip_ok(env, hipSetDevice(box->device), "hipSetDevice") || !hip_ok(env, hipMalloc(&volume->d_sh, (size_t)probes * 144), "hipMalloc")) return nullptr;
-  flx_status rc = flx_volume_bake_device(box->ctx, &p, &q, &grid, volume->d_sh, nullptr);
+  if (has_map && !hip_ok(env, hipMalloc(&volume->d_maps, (size_t)map_rows * 16), "hipMalloc")) return nullptr;
+  volume->map = map;
+  flx_status rc = has_map ? flx_volume_bake_map_device(box->ctx, &p, &q, &grid, &map, volume->d_sh, volume->d_maps, nullptr)
+                          : flx_volume_bake_device(box->ctx, &p, &q, &grid, volume->d_sh, nullptr);
   if (rc == FLX_OK) rc = flx_sync(box->ctx);
-  if (rc != FLX_OK) return fail(env, box->ctx, "flx_volume_bake_device", rc);
+  if (rc != FLX_OK) return fail(env, box->ctx, has_map ? "flx_volume_bake_map_device" : "flx_volume_bake_device", rc);
   return ext;
 }
 
@@ -557,6 +581,24 @@ static napi_value VolumeRows(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+/* volumeMaps(handle, volume) -> ArrayBuffer(16 size size probes): the map rows of a volume baked with a map, fetched from the device */
+static napi_value VolumeMaps(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  if (!get_args(env, info, 2, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  VolumeBox *volume = box ? get_volume(env, argv[1], box) : nullptr;
+  if (!volume) return nullptr;
+  if (!volume->d_maps) { napi_throw_error(env, nullptr, "volumeMaps: the volume was baked without a map"); return nullptr; }
+  const size_t bytes = (size_t)volume->probes * volume->map.size * volume->map.size * 16;
+  void *rows = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, bytes, &rows, &buf));
+  flx_status rc = flx_sync(box->ctx);
+  if (rc != FLX_OK) return fail(env, box->ctx, "flx_sync", rc);
+  if (!hip_ok(env, hipSetDevice(box->device), "hipSetDevice") || !hip_ok(env, hipMemcpy(rows, volume->d_maps, bytes, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
+  return buf;
+}
+
 /* frameIrradiance(handle, params, volume) -> ArrayBuffer(16 width height): flx_frame_irradiance_device on the volume's rows, the image fetched */
 static napi_value FrameIrradiance(napi_env env, napi_callback_info info) {
   napi_value argv[3];
@@ -573,9 +615,10 @@ static napi_value FrameIrradiance(napi_env env, napi_callback_info info) {
   napi_value buf;
   NAPI_OK(env, napi_create_arraybuffer(env, bytes, &image, &buf));
   if (!volume_room(env, volume, bytes ? bytes : 16)) return nullptr;
-  flx_status rc = flx_frame_irradiance_device(box->ctx, &p, &volume->grid, volume->d_sh, volume->d_io);
+  flx_status rc = volume->d_maps ? flx_frame_irradiance_map_device(box->ctx, &p, &volume->grid, volume->d_sh, volume->d_io, &volume->map, volume->d_maps)
+                                 : flx_frame_irradiance_device(box->ctx, &p, &volume->grid, volume->d_sh, volume->d_io);
   if (rc == FLX_OK) rc = flx_sync(box->ctx);
-  if (rc != FLX_OK) return fail(env, box->ctx, "flx_frame_irradiance_device", rc);
+  if (rc != FLX_OK) return fail(env, box->ctx, volume->d_maps ? "flx_frame_irradiance_map_device" : "flx_frame_irradiance_device", rc);
   if (!hip_ok(env, hipMemcpy(image, volume->d_io, bytes, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
   return buf;
 }
@@ -601,9 +644,10 @@ static napi_value RaysIrradiance(napi_env env, napi_callback_info info) {
   if (!volume_room(env, volume, n * 48)) return nullptr;
   char *d_rays = static_cast<char *>(volume->d_io), *d_rows = d_rays + n * 32;
   if (!hip_ok(env, hipMemcpy(d_rays, rays, n * 32, hipMemcpyHostToDevice), "hipMemcpy")) return nullptr;
-  flx_status rc = flx_rays_irradiance_device(box->ctx, tw, &volume->grid, volume->d_sh, d_rays, (uint32_t)n, d_rows, nullptr);
+  flx_status rc = volume->d_maps ? flx_rays_irradiance_map_device(box->ctx, tw, &volume->grid, volume->d_sh, d_rays, (uint32_t)n, d_rows, &volume->map, volume->d_maps, nullptr)
+                                 : flx_rays_irradiance_device(box->ctx, tw, &volume->grid, volume->d_sh, d_rays, (uint32_t)n, d_rows, nullptr);
   if (rc == FLX_OK) rc = flx_sync(box->ctx);
-  if (rc != FLX_OK) return fail(env, box->ctx, "flx_rays_irradiance_device", rc);
+  if (rc != FLX_OK) return fail(env, box->ctx, volume->d_maps ? "flx_rays_irradiance_map_device" : "flx_rays_irradiance_device", rc);
   if (!hip_ok(env, hipMemcpy(rows, d_rows, n * 16, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
   return buf;
 }
@@ -1644,7 +1688,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "traceProbes", TraceProbes }, { "probeIrradiance", ProbeIrradiance }, { "bakeVolume", BakeVolume }, { "volumeRows", VolumeRows }, { "frameIrradiance", FrameIrradiance }, { "raysIrradiance", RaysIrradiance }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "traceProbes", TraceProbes }, { "probeIrradiance", ProbeIrradiance }, { "bakeVolume", BakeVolume }, { "volumeRows", VolumeRows }, { "volumeMaps", VolumeMaps }, { "frameIrradiance", FrameIrradiance }, { "raysIrradiance", RaysIrradiance }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas }, { "uploadTextures", UploadTextures }, { "updateTexture", UpdateTexture },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
