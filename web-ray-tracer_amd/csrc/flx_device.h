@@ -1028,33 +1028,32 @@ FLX_DEV void walkLoadRay(const float2 *raysGeneric, int t, WalkState &w) {
 }
 /* (walkG = sc.walk: the kernels whose arguments stay in the kernarg segment hand it over in registers — pinnedWalkCopy() — so that the stepping loop does
  * not read it again, with a wait that also covers the LDS reads in flight, every time a lane's entry lies outside the tree top) */
-template <bool COUNT>
-FLX_DEV bool walkFetchG(const float4 *walkG, const float4 *lds, uint32_t ldsCount, const float2 *rays, WalkState &w, WalkEntry &cur,
-                        WorkCounters &cnt) {
-#if FLX_WF_LINK_KIND
-  /* What the entry a link names IS, the link says itself (build_threaded: kind 0 terminator, 1 box, 2 triangle, 3 = WALK_END, the loop bound of fragment:184): a walk ends
-   * on kinds 0 and 3 without waiting for — or, the terminator's fetch being a counted visit and nothing else, issuing — a load; kinds 1 and 2 are fetched, and nothing the
-   * trip decides next (another object space? box or triangle? still walking?) reads the loaded words, so the wait for them moves down to the test that uses them. */
+/* The fetch in two halves, so that a trip can have an entry's loads in flight while it still tests the entry before (FLX_WF_TRI_EARLY_FETCH, flx_frame_common.h).
+ * Issue: the three loads of the entry `link` names into `e`, from its home (the LDS top or the global copy).  Nothing of the walk changes. */
+FLX_DEV void walkFetchIssue(const float4 *walkG, const float4 *lds, uint32_t ldsCount, uint32_t link, WalkEntry &e) {
   /* (No branch around the loads: a link of kind 0 or 3 has index 0 — the shared terminator, the first entry of the LDS top — and its lanes load that, a broadcast, once per
    * walk; a branch would be one more mask region in every trip.) */
-  const uint32_t link0 = (uint32_t)w.i;
-  const bool stop = ((link0 + (1u << LINK_KIND_SHIFT)) & (2u << LINK_KIND_SHIFT)) == 0u;      /* kind + 1 has bit 1 set for the kinds 1 and 2 only */
-#else
-  /* the loop bound of fragment:184: no fetch, so no visit is counted.  Uncounted kernels skip the test (four instructions a trip): WALK_END's index bits name the shared
-   * terminator, whose fetch ends the walk all the same */
-  if (COUNT) { if (((uint32_t)w.i == WALK_END)) return true; }
-#endif
-  const uint32_t i = linkIndex((uint32_t)w.i);
+  const uint32_t i = linkIndex(link);
 #if FLX_WF_FLAT_FETCH
   {   /* one instruction stream for both homes of an entry: a generic pointer into LDS or into the global copy (flat_load) */
     const float4 *src = (i < ldsCount) ? lds + 3u * i : walkG + 3 * (size_t)i;
-    cur.e0 = src[0]; cur.e1 = src[1]; cur.e2 = src[2];
+    e.e0 = src[0]; e.e1 = src[1]; e.e2 = src[2];
   }
 #else
-  if (i < ldsCount) { const lds_cf4 *L = (const lds_cf4 *)lds + __umul24(i, 3u); cur.e0 = ldsLoad4(L); cur.e1 = ldsLoad4(L + 1); cur.e2 = ldsLoad4(L + 2); }      /* (i < ldsCount <= 3 328) */
-  else { cur.e0 = walkG[3 * (size_t)i]; cur.e1 = walkG[3 * (size_t)i + 1]; cur.e2 = walkG[3 * (size_t)i + 2]; }
+  if (i < ldsCount) { const lds_cf4 *L = (const lds_cf4 *)lds + __umul24(i, 3u); e.e0 = ldsLoad4(L); e.e1 = ldsLoad4(L + 1); e.e2 = ldsLoad4(L + 2); }      /* (i < ldsCount <= 3 328) */
+  else { e.e0 = walkG[3 * (size_t)i]; e.e1 = walkG[3 * (size_t)i + 1]; e.e2 = walkG[3 * (size_t)i + 2]; }
 #endif
+}
+/* Arrival: the walk stands at the entry w.i names, whose loads were issued into `e`: the visit is counted, the ray changes its object space where the link says so, and
+ * the return value says whether the walk ends here.  Only the change of object space reads `e`. */
+template <bool COUNT>
+FLX_DEV bool walkFetchArrive(const float2 *rays, WalkState &w, const WalkEntry &e, WorkCounters &cnt) {
 #if FLX_WF_LINK_KIND
+  /* What the entry a link names IS, the link says itself (build_threaded: kind 0 terminator, 1 box, 2 triangle, 3 = WALK_END, the loop bound of fragment:184): a walk ends
+   * on kinds 0 and 3 without waiting for a load (the terminator's fetch is a counted visit and nothing else); kinds 1 and 2 are fetched, and nothing the
+   * trip decides next (another object space? box or triangle? still walking?) reads the loaded words, so the wait for them moves down to the test that uses them. */
+  const uint32_t link0 = (uint32_t)w.i;
+  const bool stop = ((link0 + (1u << LINK_KIND_SHIFT)) & (2u << LINK_KIND_SHIFT)) == 0u;      /* kind + 1 has bit 1 set for the kinds 1 and 2 only */
   if (COUNT) { if (linkKind(link0) != 3u) { if (w.mode == 0) cnt.shadow_visits++; else cnt.closest_visits++; } }      /* (the loop bound is no visit; the terminator's fetch is one, fragment:208) */
 #else
   if (COUNT) { if (w.mode == 0) cnt.shadow_visits++; else cnt.closest_visits++; }
@@ -1063,12 +1062,12 @@ FLX_DEV bool walkFetchG(const float4 *walkG, const float4 *lds, uint32_t ldsCoun
   /* the link says whether the entry it names stands in another object space than the entry it came from (LINK_XFORM, build_threaded) — which is the space the walk's ray
    * is in: no comparison with the space cached, and the verdict does not wait for the entry */
   if (FLX_UNLIKELY(((uint32_t)w.i & LINK_XFORM) != 0u)) {
-    const int tI = (__float_as_int(cur.e2.z) >> 2) << 1;
+    const int tI = (__float_as_int(e.e2.z) >> 2) << 1;
     w.cachedTI = tI;
     walkLoadRay(rays, tI >> 1, w);
   }
 #else
-  const int tI = (__float_as_int(cur.e2.z) >> 2) << 1;
+  const int tI = (__float_as_int(e.e2.z) >> 2) << 1;
   if (FLX_UNLIKELY(tI != w.cachedTI)) {
     w.cachedTI = tI;
     walkLoadRay(rays, tI >> 1, w);
@@ -1077,8 +1076,20 @@ FLX_DEV bool walkFetchG(const float4 *walkG, const float4 *lds, uint32_t ldsCoun
 #if FLX_WF_LINK_KIND
   return stop;
 #else
-  return (__float_as_int(cur.e2.z) & 3) == 0;
+  return (__float_as_int(e.e2.z) & 3) == 0;
 #endif
+}
+/* the fetch of the entry w.i names: the two halves in sequence */
+template <bool COUNT>
+FLX_DEV bool walkFetchG(const float4 *walkG, const float4 *lds, uint32_t ldsCount, const float2 *rays, WalkState &w, WalkEntry &cur,
+                        WorkCounters &cnt) {
+#if !FLX_WF_LINK_KIND
+  /* the loop bound of fragment:184: no fetch, so no visit is counted.  Uncounted kernels skip the test (four instructions a trip): WALK_END's index bits name the shared
+   * terminator, whose fetch ends the walk all the same */
+  if (COUNT) { if (((uint32_t)w.i == WALK_END)) return true; }
+#endif
+  walkFetchIssue(walkG, lds, ldsCount, (uint32_t)w.i, cur);
+  return walkFetchArrive<COUNT>(rays, w, cur, cnt);
 }
 template <bool COUNT>
 FLX_DEV bool walkFetchP(const DeviceScene &sc, const float4 *lds, uint32_t ldsCount, const float2 *rays, WalkState &w, WalkEntry &cur,

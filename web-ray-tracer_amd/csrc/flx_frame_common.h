@@ -360,6 +360,48 @@ FLX_DEV void walkLaneSwitch(WalkLane &L) {                  /* the shadow walk i
 /* One entry for a walking lane: the test its entry asks for, then the entry its link names.  (A macro, not a function: as an inlined function the same statements cost
  * the frame kernel's stepping loop six more instructions per trip — two register copies and four mask operations — and the dragon frame 2.4 %: 6.40 -> 6.56 ms.)
  * THICK_: the box test's form for a scene without a flat box (rayCuboidInterval<true>, DeviceScene::walk_thick_boxes), a compile-time choice of the kernel launched. */
+/* FLX_WF_TRI_EARLY_FETCH: the successor's loads leave before the triangle test they used to follow.  A triangle's successor is cur.e2.y whatever its test says
+ * (walkTriT: only a shadow hit ends the walk instead), and a box lane's successor needs the box test and nothing else.  So the trip runs the box body, issues the loads
+ * of EVERY walking lane's successor — one load site, as before —, and then the triangle body, some 70 vector instructions, with all those loads in flight.  The loads
+ * go into a second entry, nxt: the triangle test still reads cur.  What the walk does on arrival stays after both bodies (walkFetchArrive): the visit's count, the change
+ * of object space — it replaces the ray the triangle test of the OLD entry reads —, the end of the walk.  A lane whose shadow walk ended on its triangle does none of
+ * it: the entry it loaded is never visited (every link names a valid entry, so the load itself is harmless).
+ * Two things the compiler needs to be told:
+ *   - the triangle body's condition is read from a copy of the link the compiler cannot see through (an empty asm), or it joins the triangle lanes' two parts — the choice
+ *     of the link before the loads, the test after them — into one branch ahead of the loads;
+ *   - nxt starts each trip as registers "as they happen to stand" (an empty asm that writes them), not as a defined value that a parked lane would have to keep, so that
+ *     `cur = nxt` is a renaming of registers and not twelve moves under the mask.  A parked lane's entry is dead: walkLaneSetup fetches anew before the lane walks again.
+ * (The order "triangle lanes issue at the top, box lanes after the box body" was built too and is worse with this compiler: profiles/trip_early_fetch.txt.)
+ * 0: the trip of before, to the instruction. */
+#ifndef FLX_WF_TRI_EARLY_FETCH
+#define FLX_WF_TRI_EARLY_FETCH 1
+#endif
+#if FLX_WF_TRI_EARLY_FETCH && !(FLX_WF_LINK_KIND && FLX_WF_LINK_ISBOX)
+#error "FLX_WF_TRI_EARLY_FETCH needs FLX_WF_LINK_KIND and FLX_WF_LINK_ISBOX: neither the arrival nor the trip's control may wait for the loaded entry"
+#endif
+FLX_DEV float4 walkAnyFloat4() {
+  float x, y, z, w;
+  asm volatile("" : "=v"(x)); asm volatile("" : "=v"(y)); asm volatile("" : "=v"(z)); asm volatile("" : "=v"(w));
+  return make_float4(x, y, z, w);
+}
+#if FLX_WF_TRI_EARLY_FETCH
+#define FLX_WALK_LANE_STEP(COUNT_, THICK_, walkG_, ldsEntries_, ldsCount_, myRays_, L_, cnt_)                                      \
+  do {                                                                                                                           \
+    WalkEntry nxt_;                                                                                                              \
+    nxt_.e0 = walkAnyFloat4(); nxt_.e1 = walkAnyFloat4(); nxt_.e2 = walkAnyFloat4();                                             \
+    if ((L_).st == P_WALKING) {                                                                                                  \
+      bool ended_ = false;                                                                                                       \
+      uint32_t here_ = (uint32_t)(L_).w.i;                      /* the link that led to cur: box or triangle */                  \
+      if (walkIsBoxL((L_).w)) walkBoxP<THICK_>((L_).w, (L_).cur); else (L_).w.i = __float_as_int((L_).cur.e2.y);                 \
+      walkFetchIssue(walkG_, ldsEntries_, ldsCount_, (uint32_t)(L_).w.i, nxt_);                                                  \
+      asm("" : "+v"(here_));                                                                                                     \
+      if (linkKind(here_) != 1u) ended_ = walkTriT((L_).w, (L_).cur);                                                            \
+      if (!ended_) ended_ = walkFetchArrive<COUNT_>(myRays_, (L_).w, nxt_, cnt_);                                                \
+      if (ended_) (L_).st = ((L_).w.mode == 0) ? P_SWITCH : P_DONE;                                                              \
+    }                                                                                                                            \
+    (L_).cur = nxt_;                                                                                                             \
+  } while (0)
+#else
 #define FLX_WALK_LANE_STEP(COUNT_, THICK_, walkG_, ldsEntries_, ldsCount_, myRays_, L_, cnt_)                                      \
   do {                                                                                                                           \
     if ((L_).st == P_WALKING) {                                                                                                  \
@@ -369,6 +411,7 @@ FLX_DEV void walkLaneSwitch(WalkLane &L) {                  /* the shadow walk i
       if (ended_) (L_).st = ((L_).w.mode == 0) ? P_SWITCH : P_DONE;                                                              \
     }                                                                                                                            \
   } while (0)
+#endif
 
 constexpr uint32_t FQ_SIZE = WF_FRAME_RING;   /* ids per ring (the rings live in HBM-backed memory private to the workgroup, their counts in LDS) */
 #ifndef FLX_FQ_LIMIT
