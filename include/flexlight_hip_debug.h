@@ -658,7 +658,7 @@ flx_status flx_debug_last_volume(flx_context *ctx, uint32_t out[8]);
  *   nothing hit leaves the probe fully visible in that direction.  Everything else of the lookup is as above.
  * WHERE THE ISSUE OF AN ORDER WAS OPEN it is fixed as written here: x before y before z, sums of three left to right, the fold's operands 1 - |v| and 1 - |u| each
  *   one difference, s s before its product with g, by before bx only in b = by m + bx.
- * LEFT OUT: bilinear taps between bins, map borders, hysteresis, probe relocation, maps for groups of GPUs.
+ * LEFT OUT: bilinear taps between bins, map borders, probe relocation, maps for groups of GPUs.  (Hysteresis between bakes: "volume updates" below.)
  * flx_probe_map_device reduces n_probes * 6 w w radiance rows to n_probes * m m map rows; it needs NO SCENE.  flx_probes_sh_map_device is flx_probes_sh_device's
  * chunk loop — the same function — with k_probe_map enqueued beside k_probe_sh on each chunk's radiance: bit for bit the separate calls' rows, whatever the chunk.
  * flx_volume_bake_map_device is flx_volume_bake_device with maps.  flx_volume_irradiance_map_device, flx_rays_irradiance_map_device and
@@ -701,6 +701,66 @@ void flx_volume_irradiance_map_of(const flx_volume_grid *grid, const flx_volume_
  * probes (of the whole call), [1] m, [2] k, [3] launches of k_probe_map (of the last chunk), [4] workgroups of its last launch, [5] the face size, [6], [7] zero.  It
  * waits for nothing. */
 flx_status flx_debug_last_volume_map(flx_context *ctx, uint32_t out[8]);
+/* VOLUME UPDATES: a probe volume that lives over many frames.  Each frame a LIST of its probes is retraced (the caller varies trace->random_seed from update to
+ * update; with equal seeds an update is deterministic) and the new rows are blended into the resident ones with a hysteresis, a poisoned new row is rejected, and
+ * nothing but the call crosses the bus.  All of it is calls of its own beside the ones above, which do what they did.  Every sum of an SH row and of a map row is
+ * linear in the radiance rows, so blending the sums is blending the moments and the lookups read the rows as they always did.  Every float is defined bit for bit in
+ * include/flx_volume_update.h, which the kernels (csrc/flx_volume_update.hip: k_volume_positions_list, k_volume_blend) and a CPU reference compile alike.
+ * THE LIST: entry j of n_list names the probe d_indices[j] where a list is given, otherwise update->first + j update->stride, computed in 64 bits (a rotating
+ *   subset is first = frame % stride, with no list made anywhere).
+ * THE STATE of an entry, one uint32 per entry of d_state, the rules tried in this order ("finite": the exponent bits are not all ones):
+ *   3 SKIPPED  the index is nx ny nz or more.  Nothing of the volume is read or written; no index leaves the grid.
+ *   2 KEPT     any of the 36 words of the NEW SH row is not finite.  The probe's SH row and all its map rows keep their bits.
+ *   1 TAKEN    h == 0, or the OLD row's word 3 (the sum of d_omega over all texels) is not > 0 — never baked, zero-initialised, a NaN —, or any old word is not
+ *              finite.  The new row's bits are copied.
+ *   0 BLENDED  otherwise.  With g = 1 - h computed once, every word is old + ((new - old) g): the difference, the product, the sum.  A word whose new bits equal
+ *              its old ones keeps them (so does a row, for every h; -0.0f too).  Overflow of a finite difference is left as IEEE gives it.
+ * THE MAP ROWS of a probe follow the probe's state, with two exceptions per row: where the probe blends or takes, a map row with a NEW word that is not finite
+ *   keeps its old bits; where the probe blends, a map row with an OLD word that is not finite takes the new bits.
+ * THE POSITION of entry j is flx_volume.h's of its probe; a skipped entry gets the position of probe nx ny nz - 1, and the blend ignores its rows.
+ * flx_volume_positions_list_device writes the n_list position rows (flx_probes_sh_device's input); it needs NO SCENE.  flx_volume_blend_device blends n_list new
+ * SH rows (entry-major: n_list x 9 float4) and, with a map, n_list m m new map rows into the grid's resident rows d_sh (and d_maps), and writes the states where
+ * d_state is given; it needs NO SCENE.  flx_volume_update_device is the whole path on the context's stream: k_volume_positions_list into a buffer the context
+ * owns, flx_probes_sh_device (flx_probes_sh_map_device with a map) AS IT STANDS from there into two more — there is no second probe path, so its chunks and slabs
+ * apply —, and k_volume_blend: bit for bit the three calls one after the other.  The buffers are grown behind one wait and never shrunk.
+ * A LIST IN DEVICE MEMORY CANNOT BE LOOKED AT: entries out of range are SKIPPED, and a probe named twice gets one of the possible results, TORN ROWS INCLUDED (two
+ * waves write the same rows in no order).  The calls without _device are the same for host arrays, staged through memory the context owns; they wait and copy out,
+ * and they REFUSE A DUPLICATE among the entries inside the grid, since they can look.  flx_volume_blend_row_of is a plain host function (no context, no device): one
+ * SH row with its bins map rows, updated in place; -> the state.
+ * Ordering, producer_stream, the frame server and n_list == 0 (FLX_OK, nothing enqueued, the rules below that need no array looked at first) are
+ * flx_probes_sh_device's, word for word: enqueued on the context's stream with no wait of the host, frames in flight finish unchanged.
+ * Refusals, each with a message of its own, nothing enqueued and the outputs untouched.  The siblings' come first in their own words: the scene's, the trace
+ * params', the probe params' (flx_volume_update only), the grid's, the map's where one is given.  Then FLX_ERR_INVALID for update NULL; a hysteresis that is not
+ * finite or outside [0, 1]; a reserved word that is not 0; n_list above nx ny nz; an arithmetic list (no d_indices) with stride 0 and n_list > 1, or whose last
+ * entry first + (n_list - 1) stride is nx ny nz or more — the host can see these —; maps without a map, or a map without maps; an array that is NULL, misaligned
+ * (16 bytes; 4 for indices and states), leaving the address space, not memory of the context's device, in an allocation too short, or overlapping another array
+ * of the call. */
+struct flx_volume_update {
+  float hysteresis;     /* h: finite, 0 .. 1; 0 takes the new rows, 1 keeps the old ones */
+  uint32_t first;       /* the arithmetic list (no d_indices): entry j names probe first + j stride */
+  uint32_t stride;
+  uint32_t reserved;    /* 0 */
+};
+#define FLX_VOLUME_UPDATE_STATES 4u      /* 0 blended, 1 taken, 2 kept, 3 skipped */
+flx_status flx_volume_positions_list_device(flx_context *ctx, const flx_volume_grid *grid, const struct flx_volume_update *update, const void *d_indices /* n_list uint32, or NULL */,
+                                            uint32_t n_list, void *d_positions /* n_list * 4 floats */, void *producer_stream /* hipStream_t that wrote the indices, or NULL */);
+flx_status flx_volume_positions_list(flx_context *ctx, const flx_volume_grid *grid, const struct flx_volume_update *update, const uint32_t *indices, uint32_t n_list,
+                                     float *positions);      /* host arrays */
+flx_status flx_volume_blend_device(flx_context *ctx, const flx_volume_grid *grid, const flx_volume_map *map /* or NULL */, const struct flx_volume_update *update,
+                                   const void *d_indices /* n_list uint32, or NULL */, uint32_t n_list, const void *d_new_sh /* n_list * 9 float4 */,
+                                   const void *d_new_maps /* n_list * m m float4; NULL without a map */, void *d_sh /* nx ny nz * 9 float4 */,
+                                   void *d_maps /* nx ny nz * m m float4; NULL without a map */, void *d_state /* n_list uint32, or NULL */, void *producer_stream);
+flx_status flx_volume_blend(flx_context *ctx, const flx_volume_grid *grid, const flx_volume_map *map, const struct flx_volume_update *update, const uint32_t *indices,
+                            uint32_t n_list, const float *new_sh, const float *new_maps, float *sh, float *maps, uint32_t *state);      /* host arrays; sh and maps in and out */
+flx_status flx_volume_update_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map /* or NULL */,
+                                    const struct flx_volume_update *update, const void *d_indices, uint32_t n_list, void *d_sh, void *d_maps, void *d_state, void *producer_stream);
+flx_status flx_volume_update(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map,
+                             const struct flx_volume_update *update, const uint32_t *indices, uint32_t n_list, float *sh, float *maps, uint32_t *state);      /* host arrays; sh and maps in and out */
+uint32_t flx_volume_blend_row_of(const struct flx_volume_update *update, uint32_t bins, const float new_sh[36], const float *new_maps, float sh[36], float *maps);
+/* The last flx_volume_blend[_device] or flx_volume_update[_device] (zeros if none): out[0] its entries, [1] workgroups of k_volume_blend, [2] m (0 without a map),
+ * [3] 1 where a list was given, 0 for the arithmetic one, [4] the chunks of the bake behind it (0 for a blend alone), [5] 1 for an update, 0 for a blend; [6], [7]
+ * zero.  It waits for nothing. */
+flx_status flx_debug_last_volume_update(flx_context *ctx, uint32_t out[8]);
 /* SURFACE ROWS: what the surface is where a ray first hits — the question between "where does it hit" (flx_rays_cast) and "what radiance comes back"
  * (flx_rays_trace, flx_render).  The planes (AOVs) a denoiser of the caller's own, compositing or the shading of a hybrid renderer needs beside the noisy radiance:
  * position, geometric normal, shading normal, texture coordinates, and albedo, RME and TPO with the atlases applied.  They are the first thing lightTrace computes

@@ -308,6 +308,12 @@ struct flx_context {
    * (flx_debug_last_volume_map) */
   DeviceBuffer<float4> d_volume_maps;
   struct VolumeMapLaunch { uint32_t probes = 0, size = 0, sharpness = 0, launches = 0, groups = 0, face_size = 0; } last_volume_map;
+  /* volume updates (flx_volume_update.hip): the listed probes' positions, their new SH rows and their new map rows, which flx_volume_update_device makes, bakes and
+   * blends on the same stream (the host blend's new rows go up into the latter two); the host variants' list and states; all grown behind flx_grow's one wait and
+   * never shrunk.  What the last blend or update ran (flx_debug_last_volume_update) */
+  DeviceBuffer<float4> d_update_positions, d_update_sh, d_update_maps;
+  DeviceBuffer<uint32_t> d_update_indices, d_update_state;
+  struct VolumeUpdateLaunch { uint32_t entries = 0, groups = 0, size = 0, listed = 0, chunks = 0, fused = 0; } last_volume_update;
   /* uploads: pinned staging ring */
   PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};
@@ -356,6 +362,8 @@ int flx_server_continues(flx_context *ctx, const flx_frame_params *params);     
 flx_status flx_server_prepare(flx_context *ctx, const flx_frame_params *params); /* the launch ends; everything a launch for frames like this needs is allocated */
 flx_status flx_server_stop(flx_context *ctx);      /* the frame server's launch ends (after the frames posted to it), the frames in flight are resolved into their output slots */
 bool flx_rows_on_device(const flx_context *ctx, const void *p, size_t bytes);      /* flx_scene.hip: [p, p + bytes) is memory of the context's device, 16-byte aligned, inside one allocation */
+bool flx_words_on_device(const flx_context *ctx, const void *p, size_t bytes);     /* flx_scene.hip: the same for an array of 4-byte words: 4-byte aligned */
+flx_status flx_volume_grid_refused(flx_context *ctx, const flx_volume_grid *grid, uint32_t *probes, const char *call);      /* flx_volume.hip: a grid's refusals in words; *probes <- nx ny nz of an accepted one */
 flx_status flx_dyn_flush(flx_context *ctx);        /* flx_scene.hip: the device's transforms and lights follow the host's copies, where a launch went on over their uploads */
 flx_status flx_check_device_error(flx_context *ctx);      /* FLX_ERR_DEVICE (and the word cleared) if a frame kernel's watchdog has tripped since the last check */
 /* a temporal filter frame's strips (params->tile_*; use_filter = 1, is_temporal = 1): traced, the temporal pass over this context's history,

@@ -243,6 +243,7 @@ static bool rows_on_device(const flx_context *ctx, const void *p, size_t bytes, 
   return (uintptr_t)p - (uintptr_t)base + bytes <= size;
 }
 bool flx_rows_on_device(const flx_context *ctx, const void *p, size_t bytes) { return rows_on_device(ctx, p, bytes); }      /* (flx_query.hip asks the same of its rays and hits) */
+bool flx_words_on_device(const flx_context *ctx, const void *p, size_t bytes) { return rows_on_device(ctx, p, bytes, 4); }      /* (flx_volume_update.hip: a list's indices and states) */
 
 /* What an upload learns about its entry array.  flx_scene_upload fills it from its scan and the two builders, flx_scene_upload_device from the record of
  * k_derive_check (flx_derive.hip); the two derivations stay apart, each is the other's oracle (tests/test_scene_upload_device_gpu.py). */

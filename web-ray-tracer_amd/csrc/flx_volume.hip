@@ -130,6 +130,9 @@ static flx_status volume_refusal(flx_context *ctx, enum flx_volume_refusal why, 
   return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": " + what);
 }
 
+/* the same for the files whose calls take a grid beside their own arguments (flx_volume_update.hip) */
+flx_status flx_volume_grid_refused(flx_context *ctx, const flx_volume_grid *grid, uint32_t *probes, const char *call) { return volume_refusal(ctx, flx_volume_grid_check(grid, probes), call); }
+
 /* an array of a device call: what it is, for the message */
 struct VolumeArray { const void *p; uint64_t bytes; const char *what; };
 

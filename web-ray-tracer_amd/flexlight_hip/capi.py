@@ -49,6 +49,8 @@ EXPORTS = [
     "flx_probe_map_device", "flx_probe_map", "flx_probes_sh_map_device", "flx_probes_sh_map", "flx_volume_bake_map_device", "flx_volume_bake_map",
     "flx_volume_irradiance_map_device", "flx_volume_irradiance_map", "flx_rays_irradiance_map_device", "flx_rays_irradiance_map", "flx_frame_irradiance_map_device",
     "flx_frame_irradiance_map", "flx_volume_irradiance_map_of", "flx_debug_last_volume_map",
+    "flx_volume_positions_list_device", "flx_volume_positions_list", "flx_volume_blend_device", "flx_volume_blend", "flx_volume_update_device", "flx_volume_update",
+    "flx_volume_blend_row_of", "flx_debug_last_volume_update",
     "flx_textures_upload", "flx_textures_upload_device", "flx_texture_update", "flx_texture_update_device", "flx_group_textures_upload", "flx_group_texture_update",
     "flx_debug_atlas_read",
 ]
@@ -253,6 +255,55 @@ def volume_irradiance_map_of(grid, vmap, sh, maps, position, normal):
     return out[0] if one else out
 
 
+UPDATE_STATES = ("blended", "taken", "kept", "skipped")      # the states of a volume update's entries, 0 .. 3 (include/flx_volume_update.h)
+
+
+class VolumeUpdate(C.Structure):
+    """struct flx_volume_update of include/flexlight_hip_debug.h: the hysteresis h of an update (0 takes the new rows, 1 keeps the old ones) and the arithmetic list
+    — entry j names probe first + j * stride — that stands in where no list of indices is given"""
+    _fields_ = [("hysteresis", C.c_float), ("first", C.c_uint32), ("stride", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, hysteresis=0.97, first=0, stride=1, reserved=0):
+        super().__init__(float(hysteresis), int(first), int(stride), int(reserved))
+
+
+def _update(update, call):
+    """update of a volume-update call -> what ctypes hands the library: a reference, or None (which the library refuses)"""
+    if update is not None and not isinstance(update, VolumeUpdate):
+        raise TypeError("%s: update is a VolumeUpdate" % call)
+    return C.byref(update) if update is not None else None
+
+
+def _host_list(indices, n_list, call):
+    """the list of a host volume-update call: None with n_list given (the arithmetic list), or indices -> (contiguous uint32 [n] or None, what ctypes takes, n)"""
+    if indices is None:
+        if n_list is None:
+            raise ValueError("%s: n_list is given where no indices are" % call)
+        return None, None, int(n_list)
+    indices = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+    if n_list is not None and int(n_list) != indices.shape[0]:
+        raise ValueError("%s: n_list is the number of indices" % call)
+    return indices, indices.ctypes.data_as(C.POINTER(C.c_uint32)), indices.shape[0]
+
+
+def volume_blend_row_of(update, new_sh, sh, new_maps=None, maps=None):
+    """flx_volume_blend_row_of, the library's one definition of a probe's blend on the host (include/flx_volume_update.h): new_sh and sh float32 [36], new_maps and
+    maps float32 [bins, 4] or None -> (state, the blended SH row float32 [36], the blended map rows float32 [bins, 4] or None); the arguments are left alone"""
+    if not isinstance(update, VolumeUpdate):
+        raise TypeError("volume_blend_row_of: update is a VolumeUpdate")
+    new_sh, sh = np.ascontiguousarray(new_sh, np.float32).reshape(36), np.array(sh, np.float32).reshape(36)
+    if (new_maps is None) != (maps is None):
+        raise ValueError("volume_blend_row_of: new map rows and resident map rows go together")
+    bins = 0
+    if maps is not None:
+        new_maps, maps = np.ascontiguousarray(new_maps, np.float32).reshape(-1, 4), np.array(maps, np.float32).reshape(-1, 4)
+        if new_maps.shape != maps.shape:
+            raise ValueError("volume_blend_row_of: as many new map rows as resident ones")
+        bins = maps.shape[0]
+    state = LIB.flx_volume_blend_row_of(C.byref(update), bins, _fp(new_sh), _fp(new_maps) if bins else None, _fp(sh), _fp(maps) if bins else None)
+    return int(state), sh, maps
+
+
 def probe_ray_count(face_size):
     """rays of a probe of that face size: 6 w w"""
     return 6 * int(face_size) * int(face_size)
@@ -381,6 +432,16 @@ def _load():
         "flx_frame_irradiance_map": (C.c_int, [vp, C.POINTER(FrameParams), C.POINTER(VolumeGrid), fp, fp, C.POINTER(VolumeMap), fp]),
         "flx_volume_irradiance_map_of": (None, [C.POINTER(VolumeGrid), C.POINTER(VolumeMap), fp, fp, fp, fp, fp]),
         "flx_debug_last_volume_map": (C.c_int, [vp, C.POINTER(u32)]),
+        "flx_volume_positions_list_device": (C.c_int, [vp, C.POINTER(VolumeGrid), C.POINTER(VolumeUpdate), vp, u32, vp, vp]),
+        "flx_volume_positions_list": (C.c_int, [vp, C.POINTER(VolumeGrid), C.POINTER(VolumeUpdate), C.POINTER(u32), u32, fp]),
+        "flx_volume_blend_device": (C.c_int, [vp, C.POINTER(VolumeGrid), C.POINTER(VolumeMap), C.POINTER(VolumeUpdate), vp, u32, vp, vp, vp, vp, vp, vp]),
+        "flx_volume_blend": (C.c_int, [vp, C.POINTER(VolumeGrid), C.POINTER(VolumeMap), C.POINTER(VolumeUpdate), C.POINTER(u32), u32, fp, fp, fp, fp, C.POINTER(u32)]),
+        "flx_volume_update_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), C.POINTER(VolumeGrid), C.POINTER(VolumeMap), C.POINTER(VolumeUpdate), vp, u32, vp,
+                                               vp, vp, vp]),
+        "flx_volume_update": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), C.POINTER(VolumeGrid), C.POINTER(VolumeMap), C.POINTER(VolumeUpdate), C.POINTER(u32), u32,
+                                        fp, fp, C.POINTER(u32)]),
+        "flx_volume_blend_row_of": (u32, [C.POINTER(VolumeUpdate), u32, fp, fp, fp, fp]),
+        "flx_debug_last_volume_update": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_textures_upload": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32]),
         "flx_textures_upload_device": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32, vp]),
         "flx_texture_update": (C.c_int, [vp, C.c_int, u32, C.POINTER(Image)]),
@@ -1651,6 +1712,133 @@ class Context:
         out = (C.c_uint32 * 8)()
         self._check(LIB.flx_debug_last_volume_map(self._h, out), "flx_debug_last_volume_map")
         return dict(zip(("probes", "size", "sharpness", "launches", "groups", "face_size"), list(out)[:6]))
+
+    # -- volume updates: listed probes re-baked and blended into the resident rows with a hysteresis ----------------
+    def _list_in(self, indices, n_list, call):
+        """the list of a *_device volume-update call: None with n_list given (the arithmetic list), a contiguous uint32 / int32 tensor on the context's device, or
+        an address with n_list given -> (address or 0, n)"""
+        if indices is None or isinstance(indices, int):
+            if n_list is None:
+                raise ValueError("%s: n_list is given where indices is None or an address" % call)
+            return int(indices or 0), int(n_list)
+        n = int(indices.numel()) if n_list is None else int(n_list)
+        if indices.element_size() != 4:
+            raise ValueError("%s: indices are 4-byte words" % call)
+        return self._device_out(indices, n * 4, call, "indices"), n
+
+    def _new_words(self, n):
+        import torch
+        return torch.empty((n,), dtype=torch.int32, device="cuda:%d" % self._device)
+
+    def _state_out(self, state, n, call):
+        """the states of a *_device call: True (a new int32 tensor [n]), such a tensor, an address, or None: not asked for -> (what comes back, address or 0)"""
+        if state is None:
+            return None, 0
+        if state is True:
+            state = self._new_words(n)
+        return state, self._device_out(state, n * 4, call, "state")
+
+    def volume_positions_list_device(self, grid, update, indices=None, n_list=None, out=None, stream=None):
+        """flx_volume_positions_list_device: the positions of the listed probes made on the device, probes_sh_device's input.  indices: see _list_in; out: None (a
+        new float32 tensor [n_list, 4]), such a tensor, or an address.  Needs no scene.  Returns the rows ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        g, u = _grid(grid, "volume_positions_list_device"), _update(update, "volume_positions_list_device")
+        i, n = self._list_in(indices, n_list, "volume_positions_list_device")
+        if out is None:
+            out = self._new_rows(n, 4)
+        o = self._device_out(out, n * 16, "volume_positions_list_device", "out")
+        self._check(LIB.flx_volume_positions_list_device(self._h, g, u, C.c_void_p(i), n, C.c_void_p(o), _stream_handle(stream)), "flx_volume_positions_list_device")
+        return out
+
+    def volume_positions_list(self, grid, update, indices=None, n_list=None):
+        """flx_volume_positions_list: -> the listed probes' positions float32 [n_list, 4] in host memory, complete"""
+        g, u = _grid(grid, "volume_positions_list"), _update(update, "volume_positions_list")
+        indices, i, n = _host_list(indices, n_list, "volume_positions_list")
+        out = np.zeros((n, 4), np.float32)
+        self._check(LIB.flx_volume_positions_list(self._h, g, u, i, n, _fp(out)), "flx_volume_positions_list")
+        return out
+
+    def volume_blend_device(self, grid, vmap, update, new_sh, sh, new_maps=None, maps=None, indices=None, n_list=None, state=None, stream=None):
+        """flx_volume_blend_device: n_list new SH rows (entry-major, a contiguous tensor of n_list x 144 bytes or an address) and, with a map, n_list x bins new map
+        rows blended IN PLACE into the grid's resident rows sh (and maps).  vmap: a VolumeMap or None; state: see _state_out.  Needs no scene.  Returns the states
+        (or None) ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE, like the rows."""
+        call = "volume_blend_device"
+        g, m, u = _grid(grid, call), _map(vmap, call), _update(update, call)
+        i, n = self._list_in(indices, n_list, call)
+        probes = grid.probes if grid is not None else 0
+        a = self._device_out(new_sh, n * 144, call, "new_sh")
+        s = self._device_out(sh, probes * 144, call, "sh")
+        b = self._device_out(new_maps, _map_rows(vmap, n) * 16, call, "new_maps") if new_maps is not None else 0
+        d = self._device_out(maps, _map_rows(vmap, probes) * 16, call, "maps") if maps is not None else 0
+        state, t = self._state_out(state, n, call)
+        self._check(LIB.flx_volume_blend_device(self._h, g, m, u, C.c_void_p(i), n, C.c_void_p(a), C.c_void_p(b), C.c_void_p(s), C.c_void_p(d), C.c_void_p(t), _stream_handle(stream)),
+                    "flx_volume_blend_device")
+        return state
+
+    @staticmethod
+    def _host_resident(grid, vmap, sh, maps, call):
+        sh = np.array(sh, np.float32).reshape(-1, 36)
+        if maps is not None:
+            maps = np.array(maps, np.float32).reshape(-1, 4)
+        if grid is not None and (sh.shape[0] != grid.probes or (vmap is not None and maps is not None and maps.shape[0] != grid.probes * vmap.bins)):
+            raise ValueError("%s: one SH row and size x size map rows per probe of the grid" % call)
+        return sh, maps
+
+    def volume_blend(self, grid, vmap, update, new_sh, sh, new_maps=None, maps=None, indices=None, n_list=None):
+        """flx_volume_blend: the same for host arrays -> (the blended SH rows float32 [probes, 36], the blended map rows float32 [probes * bins, 4] or None, the
+        states uint32 [n_list]), complete; the arguments are left alone.  A list that names a probe of the grid twice is refused."""
+        call = "volume_blend"
+        g, m, u = _grid(grid, call), _map(vmap, call), _update(update, call)
+        indices, i, n = _host_list(indices, n_list, call)
+        sh, maps = self._host_resident(grid, vmap, sh, maps, call)
+        new_sh = np.ascontiguousarray(new_sh, np.float32).reshape(-1, 36)
+        if new_sh.shape[0] != n:
+            raise ValueError("volume_blend: a new SH row per entry of the list")
+        if new_maps is not None:
+            new_maps = np.ascontiguousarray(new_maps, np.float32).reshape(-1, 4)
+            if vmap is not None and new_maps.shape[0] != n * vmap.bins:
+                raise ValueError("volume_blend: size x size new map rows per entry of the list")
+        state = np.zeros(n, np.uint32)
+        self._check(LIB.flx_volume_blend(self._h, g, m, u, i, n, _fp(new_sh), _fp(new_maps) if new_maps is not None else None, _fp(sh), _fp(maps) if maps is not None else None,
+                                         state.ctypes.data_as(C.POINTER(C.c_uint32))), "flx_volume_blend")
+        return sh, maps, state
+
+    def volume_update_device(self, grid, trace_params, params, vmap, update, sh, maps=None, indices=None, n_list=None, state=None, stream=None):
+        """flx_volume_update_device: the listed probes' positions made, probes_sh_device (probes_sh_map_device with a map) run on them and the new rows blended IN
+        PLACE into the resident rows sh (and maps), nothing crossing the bus.  The caller varies trace_params.random_seed from update to update.  Returns the states
+        (or None) ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE, like the rows: the lookups take them as they are."""
+        call = "volume_update_device"
+        if trace_params is not None and not isinstance(trace_params, TraceParams):
+            raise TypeError("volume_update_device: trace_params is a TraceParams")
+        if params is not None and not isinstance(params, ProbeParams):
+            raise TypeError("volume_update_device: params is a ProbeParams")
+        g, m, u = _grid(grid, call), _map(vmap, call), _update(update, call)
+        i, n = self._list_in(indices, n_list, call)
+        probes = grid.probes if grid is not None else 0
+        s = self._device_out(sh, probes * 144, call, "sh")
+        d = self._device_out(maps, _map_rows(vmap, probes) * 16, call, "maps") if maps is not None else 0
+        state, t = self._state_out(state, n, call)
+        self._check(LIB.flx_volume_update_device(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None, g, m, u,
+                                                 C.c_void_p(i), n, C.c_void_p(s), C.c_void_p(d), C.c_void_p(t), _stream_handle(stream)), "flx_volume_update_device")
+        return state
+
+    def volume_update(self, grid, trace_params, params, vmap, update, sh, maps=None, indices=None, n_list=None):
+        """flx_volume_update: the same for host arrays -> (the updated SH rows, the updated map rows or None, the states uint32 [n_list]), complete; the arguments
+        are left alone"""
+        call = "volume_update"
+        g, m, u = _grid(grid, call), _map(vmap, call), _update(update, call)
+        indices, i, n = _host_list(indices, n_list, call)
+        sh, maps = self._host_resident(grid, vmap, sh, maps, call)
+        state = np.zeros(n, np.uint32)
+        self._check(LIB.flx_volume_update(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None, g, m, u, i, n,
+                                          _fp(sh), _fp(maps) if maps is not None else None, state.ctypes.data_as(C.POINTER(C.c_uint32))), "flx_volume_update")
+        return sh, maps, state
+
+    def last_volume_update(self):
+        """flx_debug_last_volume_update -> dict (zeros when no blend or update ran): entries, groups (workgroups of k_volume_blend), size (m; 0 without a map), listed
+        (1 where a list was given), chunks (of the bake behind an update; 0 for a blend alone), fused (1 for an update).  Waits for nothing."""
+        out = (C.c_uint32 * 8)()
+        self._check(LIB.flx_debug_last_volume_update(self._h, out), "flx_debug_last_volume_update")
+        return dict(zip(("entries", "groups", "size", "listed", "chunks", "fused"), list(out)[:6]))
 
     # -- surface rows -------------------------------------------------------------------------------
     def _surface_out(self, out, n, fields, call):

@@ -378,6 +378,26 @@ class PathTracerHIP {
     return volume;
   }
 
+  /* VOLUME UPDATES (include/flexlight_hip_debug.h "volume updates", flx_volume_update_device): a baked volume kept alive over many frames.  The probes named by
+   * options.probes — a Uint32Array of indices, or { first, stride, count } for probe first + j * stride (a rotating subset is first = frame % stride) — are traced
+   * again with the face size, sky and order the volume was baked with and with options' traceRays' fields (vary randomSeed from update to update), and the new rows
+   * are blended into the handle's resident rows, and its maps if it has them, IN PLACE on the device: old + (new - old) (1 - options.hysteresis).  A new row that
+   * holds a NaN or an infinity is rejected; a probe that was never baked takes the new row.  Returns { states: Uint32Array }, per entry 0 blended, 1 taken, 2 kept,
+   * 3 skipped (an index outside the grid).  It waits for the update.  A list that names a probe twice gives that probe one of the possible results. */
+  updateVolume (volume, options) {
+    if (this._devices) throw new Error('updateVolume: one GPU only (a group of GPUs traces no rays)');
+    if (!volume || !volume._handle) throw new TypeError('updateVolume: volume is what bakeVolume returned');
+    const o = options || {};
+    if (typeof o.hysteresis !== 'number') throw new TypeError('updateVolume: hysteresis is a number');
+    const list = { hysteresis: o.hysteresis };
+    if (o.probes instanceof Uint32Array) list.indices = o.probes.byteOffset === 0 && o.probes.buffer.byteLength === o.probes.byteLength ? o.probes : Uint32Array.from(o.probes);
+    else if (o.probes !== null && typeof o.probes === 'object' && ['first', 'stride', 'count'].every(k => Number.isInteger(o.probes[k]) && o.probes[k] >= 0 && o.probes[k] <= 0xffffffff)) {
+      Object.assign(list, { first: o.probes.first, stride: o.probes.stride, count: o.probes.count });
+    } else throw new TypeError('updateVolume: probes is a Uint32Array of indices or { first, stride, count }');
+    this._uploadFrameState();
+    return { states: new Uint32Array(native().updateVolume(this._context(), volume._handle, this.traceParams(options), list)) };
+  }
+
   /* The irradiance IMAGE of the frame the next renderFrame() would trace without jitter (flx_frame_irradiance_device; flx_frame_irradiance_map_device where the
    * volume was baked with a map): per pixel the irradiance the volume gives
    * the primary hit's position and ray-facing normal — r g b and the sum of the weights; a pixel that hits nothing is 0 0 0 0.  Nothing but the image crosses the

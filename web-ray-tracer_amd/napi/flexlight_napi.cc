@@ -467,6 +467,8 @@ struct VolumeBox {
    * and the lookups read them (the _map calls); without, d_maps stays NULL and every call is the plain one */
   flx_volume_map map = { 0u, 0u, { 0u, 0u } };
   void *d_maps = nullptr;
+  /* volume updates ("volume updates"): updateVolume re-bakes listed probes with the face size, order and sky the volume was baked with */
+  flx_probe_params probe = { 0u, 0u, { 0.0f, 0.0f, 0.0f }, 0.0f };
 };
 static void finalize_volume(napi_env env, void *data, void *) {
   VolumeBox *v = static_cast<VolumeBox *>(data);
@@ -558,6 +560,7 @@ static napi_value BakeVolume(napi_env env, napi_callback_info info) {
   if (!hip_ok(env, hipSetDevice(box->device), "hipSetDevice") || !hip_ok(env, hipMalloc(&volume->d_sh, (size_t)probes * 144), "hipMalloc")) return nullptr;
   if (has_map && !hip_ok(env, hipMalloc(&volume->d_maps, (size_t)map_rows * 16), "hipMalloc")) return nullptr;
   volume->map = map;
+  volume->probe = q;
   flx_status rc = has_map ? flx_volume_bake_map_device(box->ctx, &p, &q, &grid, &map, volume->d_sh, volume->d_maps, nullptr)
                           : flx_volume_bake_device(box->ctx, &p, &q, &grid, volume->d_sh, nullptr);
   if (rc == FLX_OK) rc = flx_sync(box->ctx);
@@ -596,6 +599,60 @@ static napi_value VolumeMaps(napi_env env, napi_callback_info info) {
   flx_status rc = flx_sync(box->ctx);
   if (rc != FLX_OK) return fail(env, box->ctx, "flx_sync", rc);
   if (!hip_ok(env, hipSetDevice(box->device), "hipSetDevice") || !hip_ok(env, hipMemcpy(rows, volume->d_maps, bytes, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
+  return buf;
+}
+
+/* updateVolume(handle, volume, params (traceRays'), { hysteresis, indices: Uint32Array or undefined, first, stride, count }) -> ArrayBuffer(4 n): flx_volume_update_device
+ * on the volume's resident rows (and maps, where it has them), in place; the list goes up into the volume's staging and the states come down from behind it.  The
+ * library judges the values. */
+static napi_value UpdateVolume(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  if (!box) return nullptr;
+  VolumeBox *volume = get_volume(env, argv[1], box);
+  if (!volume) return nullptr;
+  flx_trace_params p;
+  if (!read_trace_params(env, argv[2], "updateVolume", &p)) return nullptr;
+  struct flx_volume_update u = { 0.0f, 0u, 0u, 0u };
+  double h = 0;
+  if (!num(env, argv[3], "hysteresis", &h)) return nullptr;
+  u.hysteresis = (float)h;
+  napi_value v;
+  napi_valuetype list_type = napi_undefined;
+  if (napi_get_named_property(env, argv[3], "indices", &v) != napi_ok || napi_typeof(env, v, &list_type) != napi_ok) { napi_throw_type_error(env, nullptr, "updateVolume: indices is a Uint32Array"); return nullptr; }
+  void *indices = nullptr;
+  size_t n = 0;
+  if (list_type != napi_undefined) {
+    if (!typed(env, v, napi_uint32_array, &indices, &n)) return nullptr;
+  } else {
+    napi_value field;
+    uint32_t count = 0;
+    if (napi_get_named_property(env, argv[3], "first", &field) != napi_ok || napi_get_value_uint32(env, field, &u.first) != napi_ok ||
+        napi_get_named_property(env, argv[3], "stride", &field) != napi_ok || napi_get_value_uint32(env, field, &u.stride) != napi_ok ||
+        napi_get_named_property(env, argv[3], "count", &field) != napi_ok || napi_get_value_uint32(env, field, &count) != napi_ok) {
+      napi_throw_type_error(env, nullptr, "updateVolume: probes is a Uint32Array or { first, stride, count }, three numbers");
+      return nullptr;
+    }
+    n = count;
+  }
+  if (n > 0xffffffffu) { napi_throw_range_error(env, nullptr, "updateVolume: more indices than a uint32 counts"); return nullptr; }
+  /* a list the library refuses for its length gets no memory: the library says why */
+  const bool fits = n <= volume->probes;
+  void *states = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, fits ? n * 4 : 0, &states, &buf));
+  char *d_list = nullptr, *d_state = nullptr;
+  if (fits && n > 0) {
+    if (!volume_room(env, volume, n * 8)) return nullptr;
+    d_list = static_cast<char *>(volume->d_io); d_state = d_list + n * 4;
+    if (indices && !hip_ok(env, hipMemcpy(d_list, indices, n * 4, hipMemcpyHostToDevice), "hipMemcpy")) return nullptr;
+  }
+  flx_status rc = flx_volume_update_device(box->ctx, &p, &volume->probe, &volume->grid, volume->d_maps ? &volume->map : nullptr, &u, indices && fits ? d_list : nullptr, (uint32_t)n,
+                                           volume->d_sh, volume->d_maps, d_state, nullptr);
+  if (rc == FLX_OK) rc = flx_sync(box->ctx);
+  if (rc != FLX_OK) return fail(env, box->ctx, "flx_volume_update_device", rc);
+  if (n > 0 && !hip_ok(env, hipMemcpy(states, d_state, n * 4, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
   return buf;
 }
 
@@ -1688,7 +1745,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "traceProbes", TraceProbes }, { "probeIrradiance", ProbeIrradiance }, { "bakeVolume", BakeVolume }, { "volumeRows", VolumeRows }, { "volumeMaps", VolumeMaps }, { "frameIrradiance", FrameIrradiance }, { "raysIrradiance", RaysIrradiance }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "traceProbes", TraceProbes }, { "probeIrradiance", ProbeIrradiance }, { "bakeVolume", BakeVolume }, { "volumeRows", VolumeRows }, { "volumeMaps", VolumeMaps }, { "updateVolume", UpdateVolume }, { "frameIrradiance", FrameIrradiance }, { "raysIrradiance", RaysIrradiance }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas }, { "uploadTextures", UploadTextures }, { "updateTexture", UpdateTexture },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
