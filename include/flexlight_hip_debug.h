@@ -658,7 +658,8 @@ flx_status flx_debug_last_volume(flx_context *ctx, uint32_t out[8]);
  *   nothing hit leaves the probe fully visible in that direction.  Everything else of the lookup is as above.
  * WHERE THE ISSUE OF AN ORDER WAS OPEN it is fixed as written here: x before y before z, sums of three left to right, the fold's operands 1 - |v| and 1 - |u| each
  *   one difference, s s before its product with g, by before bx only in b = by m + bx.
- * LEFT OUT: bilinear taps between bins, map borders, probe relocation, maps for groups of GPUs.  (Hysteresis between bakes: "volume updates" below.)
+ * LEFT OUT: bilinear taps between bins, map borders, maps for groups of GPUs.  (Hysteresis between bakes: "volume updates" below; probe relocation: "probe
+ * relocation" below them.)
  * flx_probe_map_device reduces n_probes * 6 w w radiance rows to n_probes * m m map rows; it needs NO SCENE.  flx_probes_sh_map_device is flx_probes_sh_device's
  * chunk loop — the same function — with k_probe_map enqueued beside k_probe_sh on each chunk's radiance: bit for bit the separate calls' rows, whatever the chunk.
  * flx_volume_bake_map_device is flx_volume_bake_device with maps.  flx_volume_irradiance_map_device, flx_rays_irradiance_map_device and
@@ -761,6 +762,99 @@ uint32_t flx_volume_blend_row_of(const struct flx_volume_update *update, uint32_
  * [3] 1 where a list was given, 0 for the arithmetic one, [4] the chunks of the bake behind it (0 for a blend alone), [5] 1 for an update, 0 for a blend; [6], [7]
  * zero.  It waits for nothing. */
 flx_status flx_debug_last_volume_update(flx_context *ctx, uint32_t out[8]);
+/* PROBE RELOCATION: flx_volume_position puts every probe exactly on the lattice, and a lattice point inside geometry or within a hair of a wall gives a probe
+ * that bakes black and is blended into eight cells all the same.  Every probe gets AN OFFSET ROW — one float4: words 0 .. 2 the offset from its lattice point in
+ * world units, word 3 a uint32 STATE —, made on the device from the first hits of the probe's own cube-face rays, and positions, bakes, updates and lookups that
+ * honour the rows.  A zero-initialised array means "no offsets, every probe active".  All of it is calls of its own beside the ones above, which do what they did.
+ * Every word is defined bit for bit in include/flx_volume_relocate.h, which the kernels (csrc/flx_volume_relocate.hip: k_probe_relocate,
+ * k_volume_positions_offset; csrc/flx_volume.hip: the relocated lookups) and a CPU reference compile alike.
+ * THE REDUCTION of a probe's R = 6 w w texels: row t of a FLX_SURFACE_HIT plane and of a FLX_SURFACE_NORMAL plane.  A texel is a HIT where the HIT row's word 3
+ *   (int32) is not -1; a hit is BACK where the NORMAL row's word 3 is > 0, FRONT where it is < 0, NEITHER where it is 0 or a NaN.  H counts the hits, B the backs;
+ *   the closest back, the closest front (least s = the HIT row's word 0) and the farthest front (greatest s) are pairs (s, t), TIES TO THE LOWEST t.  A hit whose s
+ *   is a NaN or negative counts but takes part in no extreme (-0.0f takes part as 0.0f).  Counts are integers and extremes exact selections: there is no order of
+ *   sums to fix.  A texel's direction is recomputed from t (include/flx_probe.h); no ray row is read.
+ * THE MOVE, o the old offset as given, the rules tried in this order; inside = (float)B > back_share (float)R (the product first):
+ *   1 inside, and a closest back exists: o' = o + dir_cb (s_cb + min_front 0.5) — min_front 0.5 first, then the sum, then per axis the product and the sum.
+ *   2 otherwise, a closest front exists and s_cf < min_front: where (dir_cf . dir_ff) <= 0.5, o' = o + dir_ff min(s_ff, min_front); otherwise (a NaN too) o' = o.
+ *   3 otherwise: len = sqrt((ox ox + oy oy) + oz oz); margin = min(s_cf - min_front, len), len where no front exists; where len > 0: o' = o - (o / len) margin (three
+ *     quotients, three products, three differences); otherwise o' = o.
+ *   o' is ACCEPTED where its three words are finite and |o'_a| <= limit spacing_a per axis (the product first); otherwise the row keeps o's bits.  Under
+ *   FLX_VOLUME_RELOCATE_FREEZE the row always keeps o's bits and only the state is written.
+ * THE STATE: bit 0 INACTIVE — inside, or no front hit with s <= reach —; bits 1 - 2 the rule that fired, 1 .. 3; bit 3 REJECTED — a move was computed and not
+ *   accepted.  IT DESCRIBES THE POSITION THE RAYS WERE CAST FROM: iterate the call a few times and end with one frozen call.
+ * WHERE THE ISSUE OF AN ORDER WAS OPEN it is fixed as written here: x before y before z, dot products and the squared length (x x + y y) + z z with the products
+ *   first, min(a, b) = (b < a) ? b : a.
+ * THE POSITION of probe p with offsets is flx_volume.h's plus the offset, one sum per axis, word 3 0.0f; of a list's entry (update and d_indices as for "volume
+ *   updates"; an entry outside the grid gets probe nx ny nz - 1) the same.  update NULL: the whole grid, n = nx ny nz.
+ * THE LOOKUP WITH OFFSETS is the lookup above — the directional one where a map is given — with two changes: step 5 takes d = (probe + offset) - x', one sum, one
+ *   difference per axis; and an INACTIVE corner adds nothing and NONE OF ITS ROWS ARE READ (a NaN row in a dead probe does not poison its neighbours).  The
+ *   trilinear weights stay the lattice cell's; all eight corners inactive give four 0.0f.
+ * flx_probe_relocate_device is the reduction alone over two planes of the caller's, n_probes R rows each, probe first_probe + i's rows from row i R; it updates
+ * offset rows first_probe .. first_probe + n_probes - 1 of d_offsets (nx ny nz rows) in place; NO SCENE.  flx_volume_positions_offset_device: NO SCENE.
+ * flx_volume_relocate_device is the whole path on the context's stream: the probes in chunks of max(1, 2^21 / R) (flx_debug_set_probe_chunk lowers it), per chunk
+ * k_volume_positions_offset, k_probe_rays, flx_rays_surface_device AS IT STANDS with FLX_SURFACE_HIT | FLX_SURFACE_NORMAL into a buffer the context owns (grown
+ * behind one wait, never shrunk), k_probe_relocate: bit for bit the calls one after the other, whatever the chunk.  The relocated lookups are the _map siblings'
+ * signatures plus d_offsets; map and d_maps may both be NULL for the whole-sphere moments.  flx_volume_irradiance_relocated_of is one point on the host,
+ * flx_volume_relocate_row_of one probe's planes to its offset row on the host.  flx_volume_bake_relocated_device is flx_volume_positions_offset_device into a buffer
+ * the context owns and flx_probes_sh_device (flx_probes_sh_map_device with a map) from there; flx_volume_update_relocated_device the same with a list, then
+ * flx_volume_blend_device: bit for bit those calls.
+ * Ordering, producer_stream, the frame server and n == 0 are flx_probes_sh_device's, word for word.  The calls without _device are the same for host arrays.
+ * Refusals, each with a message of its own, nothing enqueued and the outputs untouched.  The siblings' come first in their own words.  Then FLX_ERR_INVALID for
+ * relocate NULL; back_share outside [0, 1] or not finite; min_front negative or not finite; reach not > 0 or not finite; limit outside [0, 0.5] or not finite;
+ * unknown flag bits; a reserved word that is not 0; face_size 0 or above 256; first_probe + n_probes beyond the grid (in 64 bits); n_probes R of 2^32 or more; an
+ * array that is NULL, misaligned, leaving the address space, not memory of the context's device, in an allocation too short, or overlapping another of the call. */
+#define FLX_VOLUME_RELOCATE_FREEZE 1u
+struct flx_volume_relocate {
+  float back_share;     /* 0 .. 1; typical 0.25 */
+  float min_front;      /* >= 0, finite: the distance to keep from front faces */
+  float reach;          /* > 0, finite: a probe whose nearest front face is farther than this lights nothing */
+  float limit;          /* 0 .. 0.5: the share of the spacing an offset may reach per axis; typical 0.45 */
+  uint32_t flags;       /* FLX_VOLUME_RELOCATE_FREEZE or 0 */
+  uint32_t reserved;    /* 0 */
+};
+flx_status flx_probe_relocate_device(flx_context *ctx, const flx_volume_grid *grid, const struct flx_volume_relocate *relocate, const void *d_hit /* n_probes * 6 w w float4 */,
+                                     const void *d_normal /* the same */, uint32_t n_probes, uint32_t face_size, uint32_t first_probe, void *d_offsets /* nx ny nz float4, in and out */,
+                                     void *producer_stream);
+flx_status flx_probe_relocate(flx_context *ctx, const flx_volume_grid *grid, const struct flx_volume_relocate *relocate, const void *hit, const void *normal, uint32_t n_probes,
+                              uint32_t face_size, uint32_t first_probe, float *offsets);      /* host arrays; offsets in and out */
+flx_status flx_volume_positions_offset_device(flx_context *ctx, const flx_volume_grid *grid, const void *d_offsets /* nx ny nz float4 */, const struct flx_volume_update *update /* or NULL */,
+                                              const void *d_indices /* n uint32, or NULL */, uint32_t n, void *d_positions /* n * 4 floats */, void *producer_stream);
+flx_status flx_volume_positions_offset(flx_context *ctx, const flx_volume_grid *grid, const float *offsets, const struct flx_volume_update *update, const uint32_t *indices, uint32_t n,
+                                       float *positions);      /* host arrays */
+flx_status flx_volume_relocate_device(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const struct flx_volume_relocate *relocate, uint32_t face_size,
+                                      void *d_offsets /* nx ny nz float4, in and out */, void *producer_stream);
+flx_status flx_volume_relocate(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const struct flx_volume_relocate *relocate, uint32_t face_size,
+                               float *offsets);      /* host array; in and out */
+flx_status flx_volume_irradiance_relocated_device(flx_context *ctx, const flx_volume_grid *grid, const void *d_sh, const void *d_positions, const void *d_normals, uint32_t n,
+                                                  void *d_out, const flx_volume_map *map /* or NULL */, const void *d_maps /* or NULL */, const void *d_offsets, void *producer_stream);
+flx_status flx_volume_irradiance_relocated(flx_context *ctx, const flx_volume_grid *grid, const float *sh, const float *positions, const float *normals, uint32_t n, float *out,
+                                           const flx_volume_map *map, const float *maps, const float *offsets);      /* host arrays */
+flx_status flx_rays_irradiance_relocated_device(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const void *d_sh, const void *d_rays, uint32_t n, void *d_out,
+                                                const flx_volume_map *map, const void *d_maps, const void *d_offsets, void *producer_stream);
+flx_status flx_rays_irradiance_relocated(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const float *sh, const float *rays, uint32_t n, float *out,
+                                         const flx_volume_map *map, const float *maps, const float *offsets);      /* host arrays */
+flx_status flx_frame_irradiance_relocated_device(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const void *d_sh, void *d_out, const flx_volume_map *map,
+                                                 const void *d_maps, const void *d_offsets);
+flx_status flx_frame_irradiance_relocated(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const float *sh, float *out, const flx_volume_map *map,
+                                          const float *maps, const float *offsets);      /* host arrays */
+flx_status flx_volume_bake_relocated_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map /* or NULL */,
+                                            const void *d_offsets, void *d_sh, void *d_maps /* NULL without a map */, void *producer_stream);
+flx_status flx_volume_bake_relocated(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map,
+                                     const float *offsets, float *sh, float *maps);      /* host arrays */
+flx_status flx_volume_update_relocated_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map /* or NULL */,
+                                              const struct flx_volume_update *update, const void *d_indices, uint32_t n_list, const void *d_offsets, void *d_sh, void *d_maps, void *d_state,
+                                              void *producer_stream);
+flx_status flx_volume_update_relocated(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map,
+                                       const struct flx_volume_update *update, const uint32_t *indices, uint32_t n_list, const float *offsets, float *sh, float *maps,
+                                       uint32_t *state);      /* host arrays; sh and maps in and out */
+void flx_volume_irradiance_relocated_of(const flx_volume_grid *grid, const flx_volume_map *map /* or NULL */, const float *sh_rows, const float *map_rows /* or NULL */,
+                                        const float *offset_rows, const float position[4], const float normal[4], float out[4]);
+void flx_volume_relocate_row_of(const flx_volume_grid *grid, const struct flx_volume_relocate *relocate, uint32_t face_size, const float *hit /* 6 w w * 4 floats */,
+                                const float *normal /* the same */, float offset[4] /* in and out */);
+/* The last flx_probe_relocate[_device] or flx_volume_relocate[_device] (zeros if none): out[0] its probes, [1] the face size, [2] its chunks (0 for the reduction
+ * alone), [3] the probes of a full chunk, [4] workgroups of the last k_probe_relocate, [5] the relocation's flags, [6] first_probe, [7] 1 for the whole path.  It
+ * waits for nothing. */
+flx_status flx_debug_last_volume_relocate(flx_context *ctx, uint32_t out[8]);
 /* SURFACE ROWS: what the surface is where a ray first hits — the question between "where does it hit" (flx_rays_cast) and "what radiance comes back"
  * (flx_rays_trace, flx_render).  The planes (AOVs) a denoiser of the caller's own, compositing or the shading of a hybrid renderer needs beside the noisy radiance:
  * position, geometric normal, shading normal, texture coordinates, and albedo, RME and TPO with the atlases applied.  They are the first thing lightTrace computes

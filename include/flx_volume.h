@@ -140,6 +140,43 @@ FLX_HD float flx_volume_weight(const flx_volume_grid *g, const flx_volume_cell *
   return tb * wv;
 }
 
+/* THE SAME TWO PARTS FOR A PROBE THAT DOES NOT STAND ON THE LATTICE (flx_volume_relocate.h: the lattice point plus an offset).  flx_volume_weight_base_at is
+ * flx_volume_weight_base's text with the probe's position given as `at`, and flx_volume_weight_of is flx_volume_weight's second half; with at_a = flx_volume_axis of
+ * the corner they give the functions above bit for bit (tests/test_volume_relocate_cpu.py holds them to it).  They stand beside the originals, which do not call
+ * them, so that the plain lookups' compiled code stays what it was: a change to either pair is a change to both. */
+FLX_HD float flx_volume_weight_base_at(const flx_volume_cell *c, uint32_t k, const float n[3], const float at[3], float *dist_out, float dir_out[3]) {
+  float t[3], d[3];
+  for (int a = 0; a < 3; a++) {
+    t[a] = ((k >> a) & 1u) ? c->f[a] : 1.0f - c->f[a];
+    d[a] = at[a] - c->x[a];
+  }
+  const float txy = t[0] * t[1];
+  const float tri = txy * t[2];
+  const float xx = d[0] * d[0], yy = d[1] * d[1], zz = d[2] * d[2];
+  const float xxyy = xx + yy;
+  const float dist = flx_sqrt(xxyy + zz);
+  const int apart = dist != 0.0f;
+  const float dir0 = apart ? d[0] / dist : 0.0f, dir1 = apart ? d[1] / dist : 0.0f, dir2 = apart ? d[2] / dist : 0.0f;
+  const float p0 = dir0 * n[0], p1 = dir1 * n[1], p2 = dir2 * n[2];
+  const float p01 = p0 + p1;
+  const float cosine = p01 + p2;
+  const float half = (cosine + 1.0f) * 0.5f;
+  const float half2 = half * half;
+  const float wb = half2 + FLX_VOLUME_BACK_FLOOR;
+  *dist_out = dist;
+  dir_out[0] = dir0; dir_out[1] = dir1; dir_out[2] = dir2;
+  return tri * wb;
+}
+
+FLX_HD float flx_volume_weight_of(const flx_volume_grid *g, float tb, float dist, const float sh[36]) {
+  float wv = 1.0f;
+  if ((g->flags & FLX_VOLUME_VISIBILITY) != 0u && sh[7] > 0.0f) {
+    const float mean = sh[11] / sh[7], mean2 = sh[15] / sh[7];
+    wv = flx_volume_visibility(mean, mean2, dist, g->floor);
+  }
+  return tb * wv;
+}
+
 /* THE ORDER OF THE SUMS: W and S_c start at 0.0f; corner k = 0 .. 7 in ascending order adds w_k to W and w_k E_k,c (the product first) to S_c, E_k =
  * flx_probe_irradiance_of(row_k, n) — also where the corner's trilinear weight is 0: there is one path.  sums: W, S_0, S_1, S_2. */
 FLX_HD void flx_volume_add(float sums[4], float w, const float sh[36], const float n[3]) {

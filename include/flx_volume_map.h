@@ -13,7 +13,7 @@
  * flx_volume_map_terms below.  Plain C99, also valid C++ / HIP.  A numerical definition, not a renderer.
  *
  * LEFT OUT: bilinear taps between bins (the lookup reads the nearest bin only, so the weight steps where a direction crosses a bin's edge); borders around a map;
- * probe relocation; maps for groups of GPUs.  (Hysteresis between bakes is flx_volume_update.h's.)  Sizes 1 .. 3 are accepted because they are where the kernels can go wrong, not because
+ * maps for groups of GPUs.  (Hysteresis between bakes is flx_volume_update.h's, probe relocation flx_volume_relocate.h's.)  Sizes 1 .. 3 are accepted because they are where the kernels can go wrong, not because
  * they are useful.
  */
 #ifndef FLX_VOLUME_MAP_H

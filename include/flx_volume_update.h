@@ -17,7 +17,8 @@
  * OVERFLOW IS LEFT AS IEEE GIVES IT: the difference of two finite words of opposite sign may be an infinity, its product with g = 0 a NaN, and the sum is then
  * what the operations give.  The next update finds the word not finite and takes the new row.
  *
- * LEFT OUT: probe relocation, a hysteresis per probe that adapts to how much the probe's surroundings changed, updates for groups of GPUs.
+ * LEFT OUT: a hysteresis per probe that adapts to how much the probe's surroundings changed, updates for groups of GPUs.  (Probe relocation is flx_volume_relocate.h's:
+ * flx_volume_update_relocated traces the listed probes from their offset positions and blends as this file says.)
  *
  * (struct flx_volume_update has no typedef: the call that runs the whole path bears the same name, and a function and a structure tag may share one in C and
  * in C++ alike.)

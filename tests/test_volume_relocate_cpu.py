@@ -1,0 +1,345 @@
+"""Probe relocation without a GPU (include/flexlight_hip_debug.h, "probe relocation"; include/flx_volume_relocate.h): the CPU reference the GPU tests compare against
+is itself held against a float64 restatement written by hand over synthetic planes and against the properties a relocation must have in an analytic room; ties go to
+the lowest texel, empties and poison are what the header says; the lookup with zero offsets is the plain lookup bit for bit and a dead probe's NaN rows change no
+bit; the calls are declared, exported and bound; the structure has the C compiler's layout; and the argument rules that need no device
+(csrc/flx_volume_relocate_args.h) hold in a stand-alone program under the address and undefined-behaviour sanitizers."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from volume_map_util import reference as map_reference
+from volume_relocate_util import (FACES, FLAVOURS, FREEZE, INACTIVE, REJECTED, assert_same_rows, assert_same_words, grid_of, map_of, planes_of, reference, relocate64,
+                                  relocate_of, room_iterate, rule_of, states_of, synthetic_case, synthetic_maps, synthetic_sh)
+from volume_update_util import update_of
+from volume_util import COUNTS, POINT_SETS, point_set
+from volume_util import reference as volume_reference
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CALLS = ("flx_probe_relocate_device", "flx_probe_relocate", "flx_volume_positions_offset_device", "flx_volume_positions_offset", "flx_volume_relocate_device", "flx_volume_relocate",
+         "flx_volume_irradiance_relocated_device", "flx_volume_irradiance_relocated", "flx_rays_irradiance_relocated_device", "flx_rays_irradiance_relocated",
+         "flx_frame_irradiance_relocated_device", "flx_frame_irradiance_relocated", "flx_volume_bake_relocated_device", "flx_volume_bake_relocated",
+         "flx_volume_update_relocated_device", "flx_volume_update_relocated", "flx_volume_irradiance_relocated_of", "flx_volume_relocate_row_of", "flx_debug_last_volume_relocate")
+ARGS_CASES = 155         # the cases tests/volume_relocate_args_main.cc runs
+# An offset word in float32 with one rounding per operation against the float64 restatement over the same inputs, relative to the larger of 1 (the spacing's scale)
+# and the largest word of the offset: a handful of roundings of 2^-24 each of intermediates below 1, plus the texel direction's own float32 rounding (the
+# restatement's directions are float64).  The bound is the worst deviation measured on this test's own cases with a margin of 4x, as test_volume_map_cpu.py and
+# test_volume_update_cpu.py set theirs.
+OFFSET_BOUND = 4 * 1.79e-8           # observed 1.79e-08
+THRESHOLD = 1.0e-5                   # a case whose float64 restatement finds a comparison's two sides closer than this, relatively, may be left out
+
+
+@pytest.fixture(scope="module")
+def ref(tmp_path_factory):
+    return reference(tmp_path_factory)
+
+
+def test_the_relocate_structure_matches_the_c_compiler(tmp_path):
+    from flexlight_hip import capi
+    src = tmp_path / "layout.c"
+    src.write_text(r"""
+#include <stdio.h>
+#include <stddef.h>
+#include "flexlight_hip_debug.h"
+int main(void) {
+  printf("%zu %zu %zu %zu %zu %zu %zu %u\n", sizeof(struct flx_volume_relocate), offsetof(struct flx_volume_relocate, back_share), offsetof(struct flx_volume_relocate, min_front),
+         offsetof(struct flx_volume_relocate, reach), offsetof(struct flx_volume_relocate, limit), offsetof(struct flx_volume_relocate, flags),
+         offsetof(struct flx_volume_relocate, reserved), FLX_VOLUME_RELOCATE_FREEZE);
+  return 0;
+}
+""")
+    exe = tmp_path / "layout"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = list(map(int, subprocess.check_output([str(exe)]).decode().split()))
+    r = capi.VolumeRelocate
+    assert got == [C.sizeof(r), r.back_share.offset, r.min_front.offset, r.reach.offset, r.limit.offset, r.flags.offset, r.reserved.offset, capi.RELOCATE_FREEZE] == [24, 0, 4, 8, 12, 16, 20, 1]
+    q = capi.VolumeRelocate(0.5, 0.125, 8.0, 0.25, 1)
+    assert (q.back_share, q.min_front, q.reach, q.limit, q.flags, q.reserved) == (0.5, 0.125, 8.0, 0.25, 1, 0)
+    assert (capi.RELOCATE_INACTIVE, capi.RELOCATE_REJECTED) == (INACTIVE, REJECTED)
+
+
+def test_the_reference_against_float64_by_hand(ref):
+    grid = grid_of((3, 2, 4))
+    worst, cases, left_out, rules, flags = 0.0, 0, 0, set(), set()
+    for w in FACES:
+        for seed in range(4):
+            relocate = relocate_of(flags=FREEZE if seed == 3 else 0)
+            n = len(FLAVOURS)
+            hit, normal, old, flavours = synthetic_case(n, w, seed, relocate)
+            offsets = np.zeros((grid.probes, 4), np.float32)
+            offsets[:n] = old
+            got = ref.relocate(grid, relocate, w, hit, normal, offsets)
+            rays = 6 * w * w
+            for i in range(n):
+                want, state, margin = relocate64(grid, relocate, w, hit[i * rays:(i + 1) * rays], normal[i * rays:(i + 1) * rays], old[i])
+                cases += 1
+                if margin < THRESHOLD:
+                    left_out += 1
+                    continue
+                got_state = int(states_of(got[i:i + 1])[0])
+                assert got_state == state, (w, seed, flavours[i], got_state, state)
+                rules.add(int(rule_of(state)))
+                flags.add(state & (INACTIVE | REJECTED))
+                if np.isnan(old[i, :3]).any() or (state & REJECTED) or seed == 3:
+                    assert_same_words(got[i:i + 1, :3], old[i:i + 1, :3], "kept bits, %s" % flavours[i])
+                else:
+                    scale = max(1.0, float(np.abs(want).max()))
+                    worst = max(worst, float(np.abs(got[i, :3].astype(np.float64) - want).max()) / scale)
+            assert_same_words(got[n:], offsets[n:], "probes beyond the run")
+    print("relocate against float64: worst deviation %.3g over %d cases, %d left out" % (worst, cases, left_out))
+    assert cases >= 300 and left_out <= cases // 100, (cases, left_out)          # the left-out cases are at most 1 % of the cases
+    assert rules == {1, 2, 3} and flags == {0, INACTIVE, REJECTED, INACTIVE | REJECTED}
+    assert worst <= OFFSET_BOUND, worst
+
+
+def test_the_slots_reduce_to_what_the_plain_loop_does(ref):
+    """the kernel's order — 64 slots, six joins — and the plain loop give the same counts and keys: the tie rule is the whole definition"""
+    for w in FACES:
+        hit, normal, _, _ = synthetic_case(len(FLAVOURS), w, 1, relocate_of())
+        rays = 6 * w * w
+        for i in range(len(FLAVOURS)):
+            h, nn = hit[i * rays:(i + 1) * rays], normal[i * rays:(i + 1) * rays]
+            assert ref.sums(w, h, nn) == ref.sums(w, h, nn, slots=True), (w, i)
+
+
+def key(s, t, far=False):
+    bits = int(np.array([s], np.float32).view(np.uint32)[0])
+    return ((~bits & 0xffffffff if far else bits) << 32) | t
+
+
+def test_ties_empties_and_poison(ref):
+    none = 0xffffffffffffffff
+    w, rays = 4, 96
+    # equal s at two texels gives the lower t: across lanes (3 and 70 are lanes 3 and 6), within a lane (5 and 69 are lane 5's), and for the farthest too
+    s, side, hit = np.full(rays, 1.0), -np.ones(rays), np.ones(rays, bool)
+    s[[70, 3]] = 0.5
+    s[[69, 5]] = 2.0
+    side[[80, 16]] = 1.0
+    s[[80, 16]] = 0.25
+    for slots in (False, True):
+        assert ref.sums(w, *planes_of(s, side, hit), slots=slots) == (96, 2, key(0.25, 16), key(0.5, 3), key(2.0, 5, far=True))
+    # no hits
+    assert ref.sums(w, *planes_of(s, side, np.zeros(rays, bool))) == (0, 0, none, none, none)
+    # all back; all grazing (0.0, -0.0 and a NaN)
+    assert ref.sums(w, *planes_of(s, np.ones(rays), hit)) == (96, 96, key(0.25, 16), none, none)
+    grazing = np.array([0.0, -0.0, np.nan] * 32)
+    assert ref.sums(w, *planes_of(s, grazing, hit)) == (96, 0, none, none, none)
+    # s a NaN, negative or an infinity: counted, in no extreme but for +infinity, which is the greatest; -0.0 takes part as 0.0
+    s2, side2 = np.full(rays, np.nan), -np.ones(rays)
+    side2[:10] = 1.0
+    assert ref.sums(w, *planes_of(s2, side2, hit)) == (96, 10, none, none, none)
+    s2[:] = -1.0
+    s2[50] = -np.inf
+    assert ref.sums(w, *planes_of(s2, side2, hit)) == (96, 10, none, none, none)
+    s2[[40, 60]] = np.inf
+    s2[30] = -0.0
+    s2[5] = 3.0
+    assert ref.sums(w, *planes_of(s2, side2, hit)) == (96, 10, key(3.0, 5), key(0.0, 30), key(np.inf, 40, far=True))
+    # ... and through the move: an infinite closest back is a move that is not finite, rejected; the bits stay
+    grid = grid_of((2, 2, 2))
+    offsets = np.zeros((8, 4), np.float32)
+    offsets[2, :3] = (0.125, -0.0, 0.25)
+    s3 = np.full(rays, np.inf)
+    got = ref.relocate(grid, relocate_of(), w, *planes_of(s3, np.ones(rays), hit), offsets, first_probe=2)
+    assert states_of(got)[2] == INACTIVE | (1 << 1) | REJECTED
+    assert_same_words(got[:, :3], offsets[:, :3], "an infinite move")
+    assert (states_of(got)[[0, 1, 3, 4, 5, 6, 7]] == 0).all()
+    # an old offset that is a NaN is used as given: the result is not accepted and the bits are kept, payload and sign too
+    for word in range(3):
+        offsets = np.zeros((8, 4), np.float32)
+        offsets.view(np.uint32)[0, word] = 0xffc12345
+        for s4, side4 in ((np.full(rays, 1.0), -np.ones(rays)), (np.full(rays, 0.1), np.ones(rays)), (np.full(rays, 0.1), -np.ones(rays))):
+            got = ref.relocate(grid, relocate_of(), w, *planes_of(s4, side4, hit), offsets)
+            assert states_of(got)[0] & REJECTED
+            assert_same_words(got[:1, :3], offsets[:1, :3], "a NaN offset")
+
+
+NOTHING = (np.array([9.0, 9.0, 9.0]), np.array([9.5, 9.5, 9.5]))                  # a solid box outside the room: an empty room
+SOLID_SMALL = (np.array([-1.1, 0.4, -0.55]), np.array([-0.9, 0.6, -0.3]))          # around probe 0, narrower than 2 limit spacing on every axis
+SOLID_WIDE = (np.array([-1.9, -0.5, -1.5]), np.array([0.5, 1.9, 0.9]))             # around probe 0, wider than 2 limit spacing on every axis: no accepted offset leaves it
+
+
+def room_grid():
+    """3 x 2 x 4 probes inside the room: x -1, -0.25, 0.5; y 0.5, 1.75; z -0.5, 0, 0.5, 1.  Probe 0 stands at (-1, 0.5, -0.5)."""
+    grid = grid_of((3, 2, 4))
+    grid.origin[2] = -0.5
+    return grid
+
+
+def test_a_probe_inside_a_box_leaves_it_or_ends_inactive_and_rejected(ref):
+    grid, relocate, w = room_grid(), relocate_of(back_share=0.25, min_front=0.05), 8
+    limit = 0.45 * np.array([0.75, 1.25, 0.5])
+    assert (2 * limit > SOLID_SMALL[1] - SOLID_SMALL[0]).all() and (2 * limit < SOLID_WIDE[1] - SOLID_WIDE[0]).all()
+    rows, shares = room_iterate(ref, grid, relocate, w, SOLID_SMALL, 0, np.zeros(4, np.float32), 8)
+    assert shares[0] == 1.0 and states_of(rows[:1])[0] == INACTIVE | (1 << 1)
+    assert shares[-1] <= 0.25 and not states_of(rows[-1:])[0] & INACTIVE, (shares, rows)
+    assert (np.abs(rows[:, :3]) <= limit).all() and np.abs(rows[-1, :3]).max() > 0
+    rows, shares = room_iterate(ref, grid, relocate, w, SOLID_WIDE, 0, np.zeros(4, np.float32), 8)
+    assert states_of(rows[-1:])[0] & (INACTIVE | REJECTED) == INACTIVE | REJECTED and shares[-1] > 0.25
+    assert (rows[:, :3] == 0).all()
+
+
+def test_a_probe_near_a_wall_moves_away_from_it(ref):
+    grid, w = room_grid(), 8
+    grid.origin[2] = 1.9                     # probe 3 = (0, 1, 0) stands at (-1, 1.75, 1.9): 0.25 from the wall y = 2, 0.1 from the wall z = 2
+    relocate = relocate_of(min_front=0.3, reach=10.0)
+    rows, _ = room_iterate(ref, grid, relocate, w, NOTHING, 3, np.zeros(4, np.float32), 1)
+    assert states_of(rows[:1])[0] == 2 << 1                  # rule 2, accepted, active
+    lattice = np.array([-1.0, 1.75, 1.9])
+    after = lattice + rows[0, :3].astype(np.float64)
+    clearance = lambda p: float(np.minimum(p - (-2.0), 2.0 - p).min())          # noqa: E731
+    assert clearance(after) > clearance(lattice) and np.abs(rows[0, :3]).max() > 0
+
+
+def test_a_displaced_probe_in_open_space_returns_to_the_lattice(ref):
+    grid, w = room_grid(), 4
+    relocate = relocate_of(min_front=0.25, reach=10.0)
+    start = np.array([0.3, -0.5, 0.2, 0.0], np.float32)      # probe 1 stands at (-0.25, 0.5, -0.5), every wall more than a unit away
+    rows, _ = room_iterate(ref, grid, relocate, w, NOTHING, 1, start, 6)
+    lengths = [float(np.sqrt((r[:3].astype(np.float64) ** 2).sum())) for r in np.concatenate([start[None], rows])]
+    print("|o| pass by pass:", lengths)
+    assert all(b <= a for a, b in zip(lengths, lengths[1:])), lengths
+    assert lengths[-1] == 0.0 and (rule_of(states_of(rows)) == 3).all() and not (states_of(rows) & (INACTIVE | REJECTED)).any()
+    # ... step by step where a wall is nearer than the way back: the margin is what the closest front leaves over min_front
+    relocate = relocate_of(min_front=1.4, reach=10.0)         # the nearest wall, y = 2, is 1.5 from the lattice point
+    rows, _ = room_iterate(ref, grid, relocate, w, NOTHING, 1, start, 6)
+    lengths = [float(np.sqrt((r[:3].astype(np.float64) ** 2).sum())) for r in np.concatenate([start[None], rows])]
+    print("|o| pass by pass, a wall near:", lengths)
+    assert all(b <= a for a, b in zip(lengths, lengths[1:])) and lengths[1] < lengths[0] and lengths[-1] == 0.0, lengths
+
+
+def test_a_probe_that_sees_nothing_within_reach_is_inactive(ref):
+    grid, w = room_grid(), 4
+    rows, _ = room_iterate(ref, grid, relocate_of(reach=0.5), w, NOTHING, 1, np.zeros(4, np.float32), 1)
+    assert (states_of(rows) & INACTIVE).all()
+    rows, _ = room_iterate(ref, grid, relocate_of(reach=10.0), w, NOTHING, 1, np.zeros(4, np.float32), 1)
+    assert not (states_of(rows) & INACTIVE).any()
+    # no hit at all: inactive, rule 3
+    h, nn = planes_of(np.ones(96), -np.ones(96), np.zeros(96, bool))
+    got = ref.relocate(grid, relocate_of(), w, h, nn, np.zeros((24, 4), np.float32), first_probe=7)
+    assert states_of(got)[7] == INACTIVE | (3 << 1)
+
+
+def test_an_accepted_offset_never_exceeds_the_limit_and_freeze_changes_no_offset_bit(ref):
+    grid = grid_of((3, 2, 4))
+    spacing = np.array(list(grid.spacing), np.float32)
+    for limit in (0.0, 0.1, 0.45, 0.5):
+        for w in (2, 5):
+            for seed in range(3):
+                relocate = relocate_of(limit=limit)
+                n = len(FLAVOURS)
+                hit, normal, old, _ = synthetic_case(n, w, seed, relocate)
+                offsets = np.zeros((24, 4), np.float32)
+                offsets[:n] = old
+                got = ref.relocate(grid, relocate, w, hit, normal, offsets)
+                accepted = (states_of(got[:n]) & REJECTED) == 0
+                most = (np.float32(limit) * spacing).astype(np.float32)
+                assert (np.abs(got[:n][accepted][:, :3]) <= most).all()
+                assert_same_words(got[:n][~accepted][:, :3], old[~accepted][:, :3], "rejected rows keep their bits")
+                frozen = ref.relocate(grid, relocate_of(limit=limit, flags=FREEZE), w, hit, normal, offsets)
+                assert_same_words(frozen[:, :3], offsets[:, :3], "freeze")
+                assert (states_of(frozen[:n]) == states_of(got[:n])).all()
+
+
+def test_positions_with_offsets(ref, tmp_path_factory):
+    plain = volume_reference(tmp_path_factory)
+    rng = np.random.default_rng(2)
+    for count in ((1, 1, 1), (2, 2, 2), (3, 2, 4)):
+        grid = grid_of(count)
+        offsets = rng.uniform(-0.3, 0.3, size=(grid.probes, 4)).astype(np.float32)
+        offsets.view(np.uint32)[:, 3] = rng.integers(0, 16, size=grid.probes)
+        lattice = plain.positions(grid)
+        assert_same_words(ref.positions(grid, np.zeros_like(offsets)), lattice, "zero offsets")
+        want = lattice.copy()
+        want[:, :3] = lattice[:, :3] + offsets[:, :3]
+        assert_same_words(ref.positions(grid, offsets), want, "the whole grid")
+        indices = np.array([grid.probes - 1, 0, grid.probes, 0xffffffff], np.uint32)
+        assert_same_words(ref.positions(grid, offsets, update_of(0.5), indices), want[[grid.probes - 1, 0, grid.probes - 1, grid.probes - 1]], "a list")
+        got = ref.positions(grid, offsets, update_of(0.5, 1, 3), n=3)
+        assert_same_words(got, want[[min(1 + 3 * j, grid.probes - 1) for j in range(3)]], "first + j stride, skipped entries")
+
+
+def test_zero_offsets_are_the_plain_lookup_bit_for_bit(ref, tmp_path_factory):
+    from flexlight_hip import capi
+    mref = map_reference(tmp_path_factory)
+    vmap = map_of(2, 1)
+    for k, count in enumerate(COUNTS):
+        for bias, visibility in ((0.0, True), (0.125, True), (0.0, False)):
+            grid = grid_of(count, bias, visibility)
+            sh, maps = synthetic_sh(grid.probes, k), synthetic_maps(grid.probes, 2, k)
+            zero = np.zeros((grid.probes, 4), np.float32)
+            for kind in POINT_SETS:
+                positions, normals = point_set(grid, kind, 70, 5 * k + 1)
+                assert_same_rows(ref.lookup(grid, sh, zero, positions, normals), capi.volume_irradiance_of(grid, sh, positions, normals), "%s %s" % (count, kind))
+                assert_same_rows(ref.lookup(grid, sh, zero, positions, normals, vmap, maps), mref.irradiance(grid, vmap, sh, maps, positions, normals), "%s %s, map" % (count, kind))
+                assert_same_rows(capi.volume_irradiance_relocated_of(grid, None, sh, None, zero, positions, normals), ref.lookup(grid, sh, zero, positions, normals), "the export")
+
+
+def test_an_inactive_probe_adds_nothing_and_its_rows_are_not_read(ref):
+    rng = np.random.default_rng(8)
+    vmap = map_of(2, 1)
+    for k, count in enumerate(COUNTS):
+        grid = grid_of(count, 0.0625)
+        sh, maps = synthetic_sh(grid.probes, k), synthetic_maps(grid.probes, 2, k)
+        maps[np.isnan(maps)] = 1.0
+        offsets = rng.uniform(-0.2, 0.2, size=(grid.probes, 4)).astype(np.float32)
+        dead = rng.random(grid.probes) < 0.4
+        offsets.view(np.uint32)[:, 3] = np.where(dead, INACTIVE | (1 << 1) | REJECTED, 3 << 1)
+        sh_nan, sh_zero, maps_nan, maps_zero = sh.copy(), sh.copy(), maps.copy(), maps.copy()
+        sh_nan[dead], sh_zero[dead] = np.nan, 0.0
+        maps_nan[np.repeat(dead, 4)], maps_zero[np.repeat(dead, 4)] = np.nan, 0.0
+        for kind in POINT_SETS:
+            positions, normals = point_set(grid, kind, 70, 3 * k + 2)
+            a, b = ref.lookup(grid, sh_nan, offsets, positions, normals), ref.lookup(grid, sh_zero, offsets, positions, normals)
+            assert_same_words(a, b, "%s %s" % (count, kind))
+            assert not np.isnan(a[positions[:, 3] == positions[:, 3]]).any()
+            a, b = ref.lookup(grid, sh_nan, offsets, positions, normals, vmap, maps_nan), ref.lookup(grid, sh_zero, offsets, positions, normals, vmap, maps_zero)
+            assert_same_words(a, b, "%s %s, map" % (count, kind))
+        # an offset moves the weights: a live volume with offsets differs from the same without
+        if grid.probes > 1 and not dead.all():
+            positions, normals = point_set(grid, "one_cell", 70, 1)
+            assert (ref.lookup(grid, sh, offsets, positions, normals) != ref.lookup(grid, sh, np.zeros_like(offsets), positions, normals)).any()
+        # all eight corners inactive: four zeros
+        offsets.view(np.uint32)[:, 3] = INACTIVE
+        positions, normals = point_set(grid, "outside", 70, 4)
+        assert (ref.lookup(grid, sh_nan, offsets, positions, normals).view(np.uint32) == 0).all()
+        assert (ref.lookup(grid, sh_nan, offsets, positions, normals, vmap, maps_nan).view(np.uint32) == 0).all()
+
+
+def test_the_calls_are_declared_exported_and_bound(ref):
+    from flexlight_hip import capi
+    header = open(os.path.join(ROOT, "include", "flexlight_hip_debug.h")).read()
+    public = open(os.path.join(ROOT, "include", "flexlight_hip.h")).read()
+    for name in CALLS:
+        assert name in capi.EXPORTS and hasattr(capi.LIB, name) and name + "(" in header and name not in public, name
+    for method in ("probe_relocate", "probe_relocate_device", "volume_positions_offset", "volume_positions_offset_device", "volume_relocate", "volume_relocate_device",
+                   "volume_irradiance_relocated", "volume_irradiance_relocated_device", "rays_irradiance_relocated", "rays_irradiance_relocated_device",
+                   "frame_irradiance_relocated", "frame_irradiance_relocated_device", "volume_bake_relocated", "volume_bake_relocated_device", "volume_update_relocated",
+                   "volume_update_relocated_device", "last_volume_relocate"):
+        assert callable(getattr(capi.Context, method))
+    # the library's host export is the reference's definition
+    grid, relocate, w = grid_of((3, 2, 4)), relocate_of(), 3
+    hit, normal, old, _ = synthetic_case(len(FLAVOURS), w, 2, relocate)
+    offsets = np.zeros((24, 4), np.float32)
+    offsets[:len(FLAVOURS)] = old
+    want = ref.relocate(grid, relocate, w, hit, normal, offsets)
+    for p in range(len(FLAVOURS)):
+        row = capi.volume_relocate_row_of(grid, relocate, w, hit[p * 54:(p + 1) * 54], normal[p * 54:(p + 1) * 54], offsets[p])
+        assert_same_words(row.reshape(1, 4), want[p:p + 1], "probe %d" % p)
+    assert (capi.relocate_states(want) == states_of(want)).all() and (capi.relocate_rule(states_of(want)) == rule_of(states_of(want))).all()
+
+
+def test_argument_rules_in_a_stand_alone_program_under_the_sanitizers(tmp_path):
+    """every refusal of flx_volume_relocate_args.h and their order, the range on either side of the grid's end and where a 32-bit sum would wrap, the rows on either
+    side of 2^32, every pairing of arrays: the header with a main of its own, built with -fsanitize=address,undefined, run directly"""
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "a host C++ compiler is part of the image (the oracle is built with gcc)"
+    exe = tmp_path / "volume_relocate_args"
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "web-ray-tracer_amd", "csrc"),
+                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "volume_relocate_args_main.cc"), "-o", str(exe)])
+    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=60)
+    assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout
+    assert int(out.stdout.split()[1]) == ARGS_CASES

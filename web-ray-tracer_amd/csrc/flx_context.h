@@ -314,6 +314,11 @@ struct flx_context {
   DeviceBuffer<float4> d_update_positions, d_update_sh, d_update_maps;
   DeviceBuffer<uint32_t> d_update_indices, d_update_state;
   struct VolumeUpdateLaunch { uint32_t entries = 0, groups = 0, size = 0, listed = 0, chunks = 0, fused = 0; } last_volume_update;
+  /* probe relocation (flx_volume_relocate.hip): the positions of one chunk of probes and the HIT plane and the NORMAL plane of their rays (at most 2^21 x 32
+   * bytes), which flx_volume_relocate_device makes, casts and reduces on the same stream — the rays themselves are d_probe_rays above —; the host variants' offset
+   * rows; all grown behind flx_grow's one wait and never shrunk.  What the last reduction or relocation ran (flx_debug_last_volume_relocate) */
+  DeviceBuffer<float4> d_relocate_positions, d_relocate_planes, d_relocate_offsets;
+  struct VolumeRelocateLaunch { uint32_t probes = 0, face_size = 0, chunks = 0, chunk = 0, groups = 0, flags = 0, first = 0, fused = 0; } last_volume_relocate;
   /* uploads: pinned staging ring */
   PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};
@@ -364,7 +369,13 @@ flx_status flx_server_stop(flx_context *ctx);      /* the frame server's launch 
 bool flx_rows_on_device(const flx_context *ctx, const void *p, size_t bytes);      /* flx_scene.hip: [p, p + bytes) is memory of the context's device, 16-byte aligned, inside one allocation */
 bool flx_words_on_device(const flx_context *ctx, const void *p, size_t bytes);     /* flx_scene.hip: the same for an array of 4-byte words: 4-byte aligned */
 flx_status flx_volume_grid_refused(flx_context *ctx, const flx_volume_grid *grid, uint32_t *probes, const char *call);      /* flx_volume.hip: a grid's refusals in words; *probes <- nx ny nz of an accepted one */
-flx_status flx_dyn_flush(flx_context *ctx);        /* flx_scene.hip: the device's transforms and lights follow the host's copies, where a launch went on over their uploads */
+/* flx_volume_update.hip: everything flx_volume_update_device refuses, under the caller's name (n_list == 0: FLX_OK before the arrays); the update and the list alone */
+flx_status flx_volume_update_args_refused(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map,
+                                          const struct flx_volume_update *update, const void *d_indices, uint32_t n_list, void *d_sh, void *d_maps, void *d_state, uint32_t *probes,
+                                          uint32_t *new_rows, const char *call);
+flx_status flx_volume_update_list_refused(flx_context *ctx, const struct flx_volume_update *update, bool has_list, uint32_t n_list, uint32_t probes, const char *call);
+flx_status flx_volume_offsets_refused(flx_context *ctx, const void *d_offsets, uint32_t probes, const void *const *others, const uint64_t *other_bytes, int k, const char *call);      /* flx_volume_relocate.hip: the offset rows of a relocated lookup against the call's other arrays */
+flx_status flx_dyn_flush(flx_context *ctx);       /* flx_scene.hip: the device's transforms and lights follow the host's copies, where a launch went on over their uploads */
 flx_status flx_check_device_error(flx_context *ctx);      /* FLX_ERR_DEVICE (and the word cleared) if a frame kernel's watchdog has tripped since the last check */
 /* a temporal filter frame's strips (params->tile_*; use_filter = 1, is_temporal = 1): traced, the temporal pass over this context's history,
  * the five render targets the chain reads stored to d_planes = uint32[5][rows][width] (flx_render_planes_device's layout); enqueued on its stream */

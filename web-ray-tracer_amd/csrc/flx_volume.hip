@@ -30,6 +30,7 @@
 #include "flx_volume_args.h"
 #include "flx_volume_map.h"
 #include "flx_volume_map_host.h"
+#include "flx_volume_relocate.h"
 
 namespace flx {
 
@@ -56,9 +57,12 @@ __device__ __forceinline__ void load_sh(const float4 *__restrict__ sh, uint32_t 
 
 /* sh: the grid's rows; positions, normals, out: n rows each.  MAP: the directional weight (include/flx_volume_map.h) — per corner the encode and one 16-byte gather
  * of the bin's row from maps (m m rows a probe), in place of the row's words 7, 11 and 15; without it the body is what it was, and maps and map are not read. */
-template <bool MAP>
+/* OFFSETS: the lookup with offsets (include/flx_volume_relocate.h) — per corner one 16-byte load of the probe's offset row BEFORE any SH or map row is read; an
+ * inactive corner is left there, and the others' probes stand at the lattice point plus the offset.  Without it the body is what it was, and offsets is not read. */
+template <bool MAP, bool OFFSETS = false>
 __device__ __forceinline__ void volume_irradiance(const float4 *__restrict__ sh, const float4 *__restrict__ maps, const float4 *__restrict__ positions,
-                                                  const float4 *__restrict__ normals, float4 *__restrict__ out, const flx_volume_grid &g, const flx_volume_map &map, uint32_t n) {
+                                                  const float4 *__restrict__ normals, float4 *__restrict__ out, const flx_volume_grid &g, const flx_volume_map &map, uint32_t n,
+                                                  const float4 *__restrict__ offsets = nullptr) {
   const uint32_t r = blockIdx.x * VOLUME_THREADS + threadIdx.x;      /* (n / 256 + 1 workgroups: no wrap) */
   if (r >= n) return;
   const float4 x = positions[r];
@@ -73,6 +77,22 @@ __device__ __forceinline__ void volume_irradiance(const float4 *__restrict__ sh,
   for (uint32_t k = 0; k < 8u; k++) {
     float row[FLX_PROBE_SH_WORDS];
     const uint32_t p = flx_volume_corner(&g, &c, k);
+    if constexpr (OFFSETS) {
+      const float4 o = offsets[p];
+      const float offset[4] = { o.x, o.y, o.z, o.w };
+      if (flx_volume_relocate_inactive(offset)) continue;
+      load_sh(sh, p, row);
+      float dist, dir[3];
+      const float tb = flx_volume_relocate_corner(&g, &c, k, normal, offset, &dist, dir);
+      if constexpr (MAP) {
+        const float4 bin = maps[(size_t)p * flx_volume_map_bins(&map) + flx_volume_map_corner_bin(&map, dir)];
+        const float q[4] = { bin.x, bin.y, bin.z, bin.w };
+        flx_volume_add(sums, flx_volume_map_weight(&g, tb, dist, q), row, normal);
+      } else {
+        flx_volume_add(sums, flx_volume_weight_of(&g, tb, dist, row), row, normal);
+      }
+      continue;
+    }
     load_sh(sh, p, row);
     if constexpr (MAP) {
       float dist, dir[3];
@@ -99,6 +119,18 @@ __global__ __launch_bounds__(VOLUME_THREADS) void k_volume_irradiance_map(const 
                                                                           const float4 *__restrict__ normals, float4 *__restrict__ out, flx_volume_grid g, flx_volume_map map,
                                                                           uint32_t n) {
   volume_irradiance<true>(sh, maps, positions, normals, out, g, map, n);
+}
+
+__global__ __launch_bounds__(VOLUME_THREADS) void k_volume_irradiance_relocated(const float4 *__restrict__ sh, const float4 *__restrict__ offsets, const float4 *__restrict__ positions,
+                                                                                const float4 *__restrict__ normals, float4 *__restrict__ out, flx_volume_grid g, uint32_t n) {
+  const flx_volume_map none = { 0u, 0u, { 0u, 0u } };
+  volume_irradiance<false, true>(sh, nullptr, positions, normals, out, g, none, n, offsets);
+}
+
+__global__ __launch_bounds__(VOLUME_THREADS) void k_volume_irradiance_map_relocated(const float4 *__restrict__ sh, const float4 *__restrict__ maps, const float4 *__restrict__ offsets,
+                                                                                    const float4 *__restrict__ positions, const float4 *__restrict__ normals, float4 *__restrict__ out,
+                                                                                    flx_volume_grid g, flx_volume_map map, uint32_t n) {
+  volume_irradiance<true, true>(sh, maps, positions, normals, out, g, map, n, offsets);
 }
 
 }  // namespace flx
@@ -137,10 +169,16 @@ flx_status flx_volume_grid_refused(flx_context *ctx, const flx_volume_grid *grid
 struct VolumeArray { const void *p; uint64_t bytes; const char *what; };
 
 /* the maps of a call: none (the plain calls), or the map and its rows on the device (the _map calls; either may be NULL, which is refused) */
-struct VolumeMaps { const flx_volume_map *map = nullptr; const void *d_maps = nullptr; bool has = false; };
+struct VolumeMaps { const flx_volume_map *map = nullptr; const void *d_maps = nullptr; bool has = false; const void *d_offsets = nullptr; bool relocated = false; };
 static VolumeMaps with_maps(const flx_volume_map *map, const void *d_maps) {
   VolumeMaps maps;
   maps.map = map; maps.d_maps = d_maps; maps.has = true;
+  return maps;
+}
+/* the same for a relocated call: the map and its rows where either is given (both NULL: the whole-sphere moments), and the offset rows */
+static VolumeMaps with_offsets(const flx_volume_map *map, const void *d_maps, const void *d_offsets) {
+  VolumeMaps maps = (map || d_maps) ? with_maps(map, d_maps) : VolumeMaps();
+  maps.d_offsets = d_offsets; maps.relocated = true;
   return maps;
 }
 
@@ -170,6 +208,16 @@ static flx_status maps_array_refused(flx_context *ctx, const VolumeMaps &maps, u
   return flx_volume_maps_refused(ctx, maps.d_maps, rows, others, k, call);
 }
 
+/* ... and, behind both, a relocated call's offset rows against them and the maps */
+static flx_status offsets_array_refused(flx_context *ctx, const VolumeMaps &maps, uint32_t probes, uint32_t rows, const VolumeArray *arrays, int k, const char *call) {
+  if (!maps.relocated) return FLX_OK;
+  const void *others[FLX_VOLUME_MAX_ARRAYS + 1];
+  uint64_t bytes[FLX_VOLUME_MAX_ARRAYS + 1];
+  for (int i = 0; i < k; i++) { others[i] = arrays[i].p; bytes[i] = arrays[i].bytes; }
+  if (maps.has) { others[k] = maps.d_maps; bytes[k] = flx_volume_map_bytes(rows); k++; }
+  return flx_volume_offsets_refused(ctx, maps.d_offsets, probes, others, bytes, k, call);
+}
+
 static flx_status positions_enqueue(flx_context *ctx, const flx_volume_grid &g, uint32_t probes, float4 *d_positions) {
   hipLaunchKernelGGL(k_volume_positions, dim3(flx_volume_groups(probes)), dim3(VOLUME_THREADS), 0, ctx->stream, d_positions, g, probes);
   FLX_HIP(ctx, hipGetLastError());
@@ -178,7 +226,13 @@ static flx_status positions_enqueue(flx_context *ctx, const flx_volume_grid &g, 
 
 static flx_status lookup_enqueue(flx_context *ctx, const flx_volume_grid &g, const float4 *d_sh, const float4 *d_positions, const float4 *d_normals, uint32_t n, float4 *d_out,
                                  const VolumeMaps &maps) {
-  if (maps.has)
+  if (maps.relocated && maps.has)
+    hipLaunchKernelGGL(k_volume_irradiance_map_relocated, dim3(flx_volume_groups(n)), dim3(VOLUME_THREADS), 0, ctx->stream, d_sh, (const float4 *)maps.d_maps,
+                       (const float4 *)maps.d_offsets, d_positions, d_normals, d_out, g, *maps.map, n);
+  else if (maps.relocated)
+    hipLaunchKernelGGL(k_volume_irradiance_relocated, dim3(flx_volume_groups(n)), dim3(VOLUME_THREADS), 0, ctx->stream, d_sh, (const float4 *)maps.d_offsets, d_positions, d_normals,
+                       d_out, g, n);
+  else if (maps.has)
     hipLaunchKernelGGL(k_volume_irradiance_map, dim3(flx_volume_groups(n)), dim3(VOLUME_THREADS), 0, ctx->stream, d_sh, (const float4 *)maps.d_maps, d_positions, d_normals, d_out, g,
                        *maps.map, n);
   else
@@ -285,7 +339,7 @@ static flx_status irradiance_run(flx_context *ctx, const flx_volume_grid *grid, 
                                   { d_positions, flx_volume_plane_bytes(n), "the positions are not n rows of 16 bytes" },
                                   { d_normals, flx_volume_plane_bytes(n), "the normals are not n rows of 16 bytes" },
                                   { d_out, flx_volume_plane_bytes(n), "the irradiance rows are not n rows of 16 bytes" } };
-  if ((s = arrays_refused(ctx, arrays, 4, call)) || (s = maps_array_refused(ctx, maps, rows, arrays, 4, call))) return s;
+  if ((s = arrays_refused(ctx, arrays, 4, call)) || (s = maps_array_refused(ctx, maps, rows, arrays, 4, call)) || (s = offsets_array_refused(ctx, maps, probes, rows, arrays, 4, call))) return s;
   if ((s = flx_server_stop(ctx)) || (s = flx_wait_for_producer(ctx, producer_stream))) return s;
   if ((s = lookup_enqueue(ctx, *grid, (const float4 *)d_sh, (const float4 *)d_positions, (const float4 *)d_normals, n, (float4 *)d_out, maps))) return s;
   lookup_ran(ctx, *grid, probes, n, 1u, n, 0u, flx_volume_groups(n));
@@ -321,6 +375,16 @@ static flx_status maps_up(flx_context *ctx, const flx_volume_map *map, const flo
   return FLX_OK;
 }
 
+/* the offset rows of a relocated host variant into ctx->d_relocate_offsets, on the context's stream; *up becomes the relocated call's (offsets NULL: *up is left) */
+static flx_status offsets_up(flx_context *ctx, const float *offsets, uint32_t probes, VolumeMaps *up) {
+  if (!offsets) return FLX_OK;
+  flx_status s = flx_grow(ctx, flx_need(&ctx->d_relocate_offsets, (size_t)probes));
+  if (s) return s;
+  FLX_HIP(ctx, hipMemcpyAsync(ctx->d_relocate_offsets.get(), offsets, (size_t)probes * 16u, hipMemcpyHostToDevice, ctx->stream));
+  up->d_offsets = ctx->d_relocate_offsets.get(); up->relocated = true;
+  return FLX_OK;
+}
+
 /* what a host map call refuses behind its sibling's grid: the map, its rows, a NULL maps array (has_map: the call is a _map call) */
 static flx_status host_maps_refused(flx_context *ctx, bool has_map, const flx_volume_map *map, const float *maps, uint32_t probes, uint32_t *rows, const char *call) {
   if (!has_map) return FLX_OK;
@@ -329,24 +393,27 @@ static flx_status host_maps_refused(flx_context *ctx, bool has_map, const flx_vo
   return maps ? FLX_OK : fail(ctx, FLX_ERR_INVALID, std::string(call) + ": the maps array is NULL");
 }
 
+/* (relocated: the call takes offset rows, which must be there; the device call's name follows) */
 static flx_status irradiance_host(flx_context *ctx, const flx_volume_grid *grid, const float *sh, const float *positions, const float *normals, uint32_t n, float *out, bool has_map,
-                                  const flx_volume_map *map, const float *maps, const char *call) {
+                                  const flx_volume_map *map, const float *maps, const char *call, bool relocated = false, const float *offsets = nullptr) {
   if (!ctx) return FLX_ERR_INVALID;
   uint32_t probes = 0, rows = 0;
   flx_status s = volume_refusal(ctx, flx_volume_grid_check(grid, &probes), call);
   if (s || (has_map && (s = flx_volume_map_refused(ctx, map, probes, &rows, call))) || n == 0u) return s;
-  if (!sh || !positions || !normals || !out) return volume_refusal(ctx, FLX_VOLUME_NULL, call);
+  if (!sh || !positions || !normals || !out || (relocated && !offsets)) return volume_refusal(ctx, FLX_VOLUME_NULL, call);
   if ((s = host_maps_refused(ctx, has_map, map, maps, probes, &rows, call))) return s;
   /* the two planes go up where a ray batch's rays go, one behind the other: n rows of 32 bytes are 2 n rows of 16 */
   return flx_rays_from_host(ctx, nullptr, 0u, [&]() -> flx_status {
     VolumeMaps dm;
     flx_status up = sh_up(ctx, sh, probes);
-    if (up || (up = maps_up(ctx, has_map ? map : nullptr, maps, rows, &dm)) || (up = flx_grow(ctx, flx_need(&ctx->d_query_rays, (size_t)n * 2u)))) return up;
+    if (up || (up = maps_up(ctx, has_map ? map : nullptr, maps, rows, &dm)) || (up = offsets_up(ctx, offsets, probes, &dm)) ||
+        (up = flx_grow(ctx, flx_need(&ctx->d_query_rays, (size_t)n * 2u))))
+      return up;
     float4 *planes = ctx->d_query_rays.get();
     FLX_HIP(ctx, hipMemcpyAsync(planes, positions, (size_t)flx_volume_plane_bytes(n), hipMemcpyHostToDevice, ctx->stream));
     FLX_HIP(ctx, hipMemcpyAsync(planes + n, normals, (size_t)flx_volume_plane_bytes(n), hipMemcpyHostToDevice, ctx->stream));
     return irradiance_run(ctx, grid, ctx->d_volume_sh.get(), planes, planes + n, n, ctx->d_query_hits.get(), dm, nullptr,
-                          has_map ? "flx_volume_irradiance_map_device" : "flx_volume_irradiance_device");
+                          relocated ? "flx_volume_irradiance_relocated_device" : has_map ? "flx_volume_irradiance_map_device" : "flx_volume_irradiance_device");
   }, flx_down(&ctx->d_query_hits, (size_t)n, out));
 }
 
@@ -370,7 +437,7 @@ static flx_status rays_run(flx_context *ctx, int32_t texture_width, const flx_vo
   const VolumeArray arrays[3] = { { d_sh, flx_volume_sh_bytes(probes), "the SH rows are not nx * ny * nz rows of 144 bytes" },
                                   { d_rays, (uint64_t)n * FLX_RAY_ROW_BYTES, "the rays are not n rows of 32 bytes" },
                                   { d_out, flx_volume_plane_bytes(n), "the irradiance rows are not n rows of 16 bytes" } };
-  if ((s = arrays_refused(ctx, arrays, 3, call)) || (s = maps_array_refused(ctx, maps, rows, arrays, 3, call))) return s;
+  if ((s = arrays_refused(ctx, arrays, 3, call)) || (s = maps_array_refused(ctx, maps, rows, arrays, 3, call)) || (s = offsets_array_refused(ctx, maps, probes, rows, arrays, 3, call))) return s;
   if ((s = flx_server_stop(ctx))) return s;
   const uint32_t slab = flx_trace_slab_rays(1u, ctx->trace_slab), most = n < slab ? n : slab;
   if ((s = flx_grow(ctx, flx_need(&ctx->d_volume_surface, (size_t)most * 2u)))) return s;
@@ -399,19 +466,19 @@ extern "C" flx_status flx_rays_irradiance_map_device(flx_context *ctx, int32_t t
 }
 
 static flx_status rays_host(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const float *sh, const float *rays, uint32_t n, float *out, bool has_map,
-                            const flx_volume_map *map, const float *maps, const char *call) {
+                            const flx_volume_map *map, const float *maps, const char *call, bool relocated = false, const float *offsets = nullptr) {
   if (!ctx) return FLX_ERR_INVALID;
   uint32_t probes = 0, rows = 0;
   flx_status s = flx_rays_surface_device(ctx, texture_width, nullptr, 0u, FLX_SURFACE_POSITION | FLX_SURFACE_NORMAL, nullptr, nullptr);
   if (s || (s = volume_refusal(ctx, flx_volume_grid_check(grid, &probes), call)) || (has_map && (s = flx_volume_map_refused(ctx, map, probes, &rows, call))) || n == 0u) return s;
-  if (!sh || !rays || !out) return volume_refusal(ctx, FLX_VOLUME_NULL, call);
+  if (!sh || !rays || !out || (relocated && !offsets)) return volume_refusal(ctx, FLX_VOLUME_NULL, call);
   if ((s = host_maps_refused(ctx, has_map, map, maps, probes, &rows, call))) return s;
   return flx_rays_from_host(ctx, rays, n, [&]() -> flx_status {
     VolumeMaps dm;
     flx_status up = sh_up(ctx, sh, probes);
-    if (up || (up = maps_up(ctx, has_map ? map : nullptr, maps, rows, &dm))) return up;
+    if (up || (up = maps_up(ctx, has_map ? map : nullptr, maps, rows, &dm)) || (up = offsets_up(ctx, offsets, probes, &dm))) return up;
     return rays_run(ctx, texture_width, grid, ctx->d_volume_sh.get(), ctx->d_query_rays.get(), n, ctx->d_query_hits.get(), dm, nullptr,
-                    has_map ? "flx_rays_irradiance_map_device" : "flx_rays_irradiance_device");
+                    relocated ? "flx_rays_irradiance_relocated_device" : has_map ? "flx_rays_irradiance_map_device" : "flx_rays_irradiance_device");
   }, flx_down(&ctx->d_query_hits, (size_t)n, out));
 }
 
@@ -438,7 +505,7 @@ static flx_status frame_run(flx_context *ctx, const flx_frame_params *params, co
   const uint32_t n = params->width * params->height;          /* (fits: the surface call's check) */
   const VolumeArray arrays[2] = { { d_sh, flx_volume_sh_bytes(probes), "the SH rows are not nx * ny * nz rows of 144 bytes" },
                                   { d_out, flx_volume_plane_bytes(n), "the irradiance rows are not width * height rows of 16 bytes" } };
-  if ((s = arrays_refused(ctx, arrays, 2, call)) || (s = maps_array_refused(ctx, maps, rows, arrays, 2, call))) return s;
+  if ((s = arrays_refused(ctx, arrays, 2, call)) || (s = maps_array_refused(ctx, maps, rows, arrays, 2, call)) || (s = offsets_array_refused(ctx, maps, probes, rows, arrays, 2, call))) return s;
   if ((s = flx_server_stop(ctx))) return s;
   if ((s = flx_grow(ctx, flx_need(&ctx->d_volume_surface, (size_t)n * 2u)))) return s;
   float4 *planes = ctx->d_volume_surface.get();
@@ -458,18 +525,19 @@ extern "C" flx_status flx_frame_irradiance_map_device(flx_context *ctx, const fl
 }
 
 static flx_status frame_host(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const float *sh, float *out, bool has_map, const flx_volume_map *map,
-                             const float *maps, const char *call) {
+                             const float *maps, const char *call, bool relocated = false, const float *offsets = nullptr) {
   if (!ctx) return FLX_ERR_INVALID;
   uint32_t probes = 0, rows = 0;
   flx_status s = frame_refused(ctx, params, grid, &probes, call);
   if (s) return s;
-  if (!sh || !out) return volume_refusal(ctx, FLX_VOLUME_NULL, call);
+  if (!sh || !out || (relocated && !offsets)) return volume_refusal(ctx, FLX_VOLUME_NULL, call);
   if ((s = host_maps_refused(ctx, has_map, map, maps, probes, &rows, call))) return s;
   return flx_rays_from_host(ctx, nullptr, 0u, [&]() -> flx_status {
     VolumeMaps dm;
     flx_status up = sh_up(ctx, sh, probes);
-    if (up || (up = maps_up(ctx, has_map ? map : nullptr, maps, rows, &dm))) return up;
-    return frame_run(ctx, params, grid, ctx->d_volume_sh.get(), ctx->d_query_hits.get(), dm, has_map ? "flx_frame_irradiance_map_device" : "flx_frame_irradiance_device");
+    if (up || (up = maps_up(ctx, has_map ? map : nullptr, maps, rows, &dm)) || (up = offsets_up(ctx, offsets, probes, &dm))) return up;
+    return frame_run(ctx, params, grid, ctx->d_volume_sh.get(), ctx->d_query_hits.get(), dm,
+                     relocated ? "flx_frame_irradiance_relocated_device" : has_map ? "flx_frame_irradiance_map_device" : "flx_frame_irradiance_device");
   }, flx_down(&ctx->d_query_hits, (size_t)params->width * params->height, out));
 }
 
@@ -480,6 +548,42 @@ extern "C" flx_status flx_frame_irradiance(flx_context *ctx, const flx_frame_par
 extern "C" flx_status flx_frame_irradiance_map(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const float *sh, float *out, const flx_volume_map *map,
                                                const float *maps) {
   return frame_host(ctx, params, grid, sh, out, true, map, maps, "flx_frame_irradiance_map");
+}
+
+/* THE RELOCATED LOOKUPS: the same implementations once more, entered with offset rows (and with a map where either of map and maps is given). */
+extern "C" flx_status flx_volume_irradiance_relocated_device(flx_context *ctx, const flx_volume_grid *grid, const void *d_sh, const void *d_positions, const void *d_normals, uint32_t n,
+                                                             void *d_out, const flx_volume_map *map, const void *d_maps, const void *d_offsets, void *producer_stream) {
+  return irradiance_run(ctx, grid, d_sh, d_positions, d_normals, n, d_out, with_offsets(map, d_maps, d_offsets), producer_stream, "flx_volume_irradiance_relocated_device");
+}
+
+extern "C" flx_status flx_volume_irradiance_relocated(flx_context *ctx, const flx_volume_grid *grid, const float *sh, const float *positions, const float *normals, uint32_t n, float *out,
+                                                      const flx_volume_map *map, const float *maps, const float *offsets) {
+  return irradiance_host(ctx, grid, sh, positions, normals, n, out, map || maps, map, maps, "flx_volume_irradiance_relocated", true, offsets);
+}
+
+extern "C" flx_status flx_rays_irradiance_relocated_device(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const void *d_sh, const void *d_rays, uint32_t n,
+                                                           void *d_out, const flx_volume_map *map, const void *d_maps, const void *d_offsets, void *producer_stream) {
+  return rays_run(ctx, texture_width, grid, d_sh, d_rays, n, d_out, with_offsets(map, d_maps, d_offsets), producer_stream, "flx_rays_irradiance_relocated_device");
+}
+
+extern "C" flx_status flx_rays_irradiance_relocated(flx_context *ctx, int32_t texture_width, const flx_volume_grid *grid, const float *sh, const float *rays, uint32_t n, float *out,
+                                                    const flx_volume_map *map, const float *maps, const float *offsets) {
+  return rays_host(ctx, texture_width, grid, sh, rays, n, out, map || maps, map, maps, "flx_rays_irradiance_relocated", true, offsets);
+}
+
+extern "C" flx_status flx_frame_irradiance_relocated_device(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const void *d_sh, void *d_out,
+                                                            const flx_volume_map *map, const void *d_maps, const void *d_offsets) {
+  return frame_run(ctx, params, grid, d_sh, d_out, with_offsets(map, d_maps, d_offsets), "flx_frame_irradiance_relocated_device");
+}
+
+extern "C" flx_status flx_frame_irradiance_relocated(flx_context *ctx, const flx_frame_params *params, const flx_volume_grid *grid, const float *sh, float *out, const flx_volume_map *map,
+                                                     const float *maps, const float *offsets) {
+  return frame_host(ctx, params, grid, sh, out, map || maps, map, maps, "flx_frame_irradiance_relocated", true, offsets);
+}
+
+extern "C" void flx_volume_irradiance_relocated_of(const flx_volume_grid *grid, const flx_volume_map *map, const float *sh_rows, const float *map_rows, const float *offset_rows,
+                                                   const float position[4], const float normal[4], float out[4]) {
+  flx_volume_relocate_lookup(grid, map, sh_rows, map_rows, offset_rows, position, normal, out);
 }
 
 extern "C" void flx_volume_irradiance_of(const flx_volume_grid *grid, const float *sh_rows, const float position[4], const float normal[4], float out[4]) {

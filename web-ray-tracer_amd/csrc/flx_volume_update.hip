@@ -278,21 +278,44 @@ static flx_status bake_refused(flx_context *ctx, const flx_trace_params *trace, 
   return flx_probes_sh_device(ctx, trace, params, nullptr, 0u, nullptr, nullptr);
 }
 
+/* everything flx_volume_update_device refuses, in its order (n_list == 0: FLX_OK before the arrays are looked at) */
+static flx_status update_args_refused(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map,
+                                      const struct flx_volume_update *update, const void *d_indices, uint32_t n_list, void *d_sh, void *d_maps, void *d_state, UpdateShape *shape,
+                                      const char *call) {
+  flx_status s = bake_refused(ctx, trace, params);
+  if (s || (s = shape_refused(ctx, grid, map, update, d_indices != nullptr, n_list, shape, call))) return s;
+  if ((s = update_refusal(ctx, flx_volume_update_pairing(map != nullptr, d_maps != nullptr, d_maps != nullptr), call)) || n_list == 0u) return s;
+  const bool no_map = map == nullptr;
+  const UpdateArray arrays[4] = { { d_indices, flx_volume_update_word_bytes(n_list), 4u, true, INDICES_WHAT },
+                                  { d_sh, flx_volume_update_sh_bytes(shape->probes), 16u, false, SH_WHAT },
+                                  { d_maps, flx_volume_map_bytes(shape->rows), 16u, no_map, MAPS_WHAT },
+                                  { d_state, flx_volume_update_word_bytes(n_list), 4u, true, STATE_WHAT } };
+  return arrays_refused(ctx, arrays, 4, call);
+}
+
+/* the same for flx_volume_update_relocated_device (flx_volume_relocate.hip), under its own name; *probes and *new_rows (n_list m m; 0 without a map) of an accepted call */
+flx_status flx_volume_update_args_refused(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map,
+                                          const struct flx_volume_update *update, const void *d_indices, uint32_t n_list, void *d_sh, void *d_maps, void *d_state, uint32_t *probes,
+                                          uint32_t *new_rows, const char *call) {
+  UpdateShape shape;
+  const flx_status s = update_args_refused(ctx, trace, params, grid, map, update, d_indices, n_list, d_sh, d_maps, d_state, &shape, call);
+  *probes = shape.probes; *new_rows = shape.new_rows;
+  return s;
+}
+
+/* the update and the list alone, in this file's words (flx_volume_positions_offset_device takes a list) */
+flx_status flx_volume_update_list_refused(flx_context *ctx, const struct flx_volume_update *update, bool has_list, uint32_t n_list, uint32_t probes, const char *call) {
+  return update_refusal(ctx, flx_volume_update_check(update, has_list ? 1 : 0, n_list, probes), call);
+}
+
 extern "C" flx_status flx_volume_update_device(flx_context *ctx, const flx_trace_params *trace, const flx_probe_params *params, const flx_volume_grid *grid, const flx_volume_map *map,
                                                const struct flx_volume_update *update, const void *d_indices, uint32_t n_list, void *d_sh, void *d_maps, void *d_state,
                                                void *producer_stream) {
   static const char *const call = "flx_volume_update_device";
   if (!ctx) return FLX_ERR_INVALID;
   UpdateShape shape;
-  flx_status s = bake_refused(ctx, trace, params);
-  if (s || (s = shape_refused(ctx, grid, map, update, d_indices != nullptr, n_list, &shape, call))) return s;
-  if ((s = update_refusal(ctx, flx_volume_update_pairing(map != nullptr, d_maps != nullptr, d_maps != nullptr), call)) || n_list == 0u) return s;
-  const bool no_map = map == nullptr;
-  const UpdateArray arrays[4] = { { d_indices, flx_volume_update_word_bytes(n_list), 4u, true, INDICES_WHAT },
-                                  { d_sh, flx_volume_update_sh_bytes(shape.probes), 16u, false, SH_WHAT },
-                                  { d_maps, flx_volume_map_bytes(shape.rows), 16u, no_map, MAPS_WHAT },
-                                  { d_state, flx_volume_update_word_bytes(n_list), 4u, true, STATE_WHAT } };
-  if ((s = arrays_refused(ctx, arrays, 4, call))) return s;
+  flx_status s = update_args_refused(ctx, trace, params, grid, map, update, d_indices, n_list, d_sh, d_maps, d_state, &shape, call);
+  if (s || n_list == 0u) return s;
   if ((s = flx_server_stop(ctx))) return s;
   /* (an earlier update's blend may still read the buffers that are about to go: flx_grow waits first) */
   if ((s = flx_grow(ctx, flx_need(&ctx->d_update_positions, (size_t)n_list), flx_need(&ctx->d_update_sh, (size_t)n_list * 9u),

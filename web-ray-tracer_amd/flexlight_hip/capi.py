@@ -51,6 +51,10 @@ EXPORTS = [
     "flx_frame_irradiance_map", "flx_volume_irradiance_map_of", "flx_debug_last_volume_map",
     "flx_volume_positions_list_device", "flx_volume_positions_list", "flx_volume_blend_device", "flx_volume_blend", "flx_volume_update_device", "flx_volume_update",
     "flx_volume_blend_row_of", "flx_debug_last_volume_update",
+    "flx_probe_relocate_device", "flx_probe_relocate", "flx_volume_positions_offset_device", "flx_volume_positions_offset", "flx_volume_relocate_device", "flx_volume_relocate",
+    "flx_volume_irradiance_relocated_device", "flx_volume_irradiance_relocated", "flx_rays_irradiance_relocated_device", "flx_rays_irradiance_relocated",
+    "flx_frame_irradiance_relocated_device", "flx_frame_irradiance_relocated", "flx_volume_bake_relocated_device", "flx_volume_bake_relocated",
+    "flx_volume_update_relocated_device", "flx_volume_update_relocated", "flx_volume_irradiance_relocated_of", "flx_volume_relocate_row_of", "flx_debug_last_volume_relocate",
     "flx_textures_upload", "flx_textures_upload_device", "flx_texture_update", "flx_texture_update_device", "flx_group_textures_upload", "flx_group_texture_update",
     "flx_debug_atlas_read",
 ]
@@ -304,6 +308,77 @@ def volume_blend_row_of(update, new_sh, sh, new_maps=None, maps=None):
     return int(state), sh, maps
 
 
+RELOCATE_FREEZE = 1          # VolumeRelocate.flags: move nothing, write the states alone
+RELOCATE_INACTIVE = 1        # state bit 0 of an offset row (include/flx_volume_relocate.h)
+RELOCATE_REJECTED = 8        # state bit 3: a move was computed and not accepted
+
+
+class VolumeRelocate(C.Structure):
+    """struct flx_volume_relocate of include/flexlight_hip_debug.h: the share of back-face hits above which a probe counts as inside geometry, the distance to keep
+    from front faces, the distance within which a probe must see a front face to light anything, the share of the spacing an offset may reach per axis, and
+    RELOCATE_FREEZE"""
+    _fields_ = [("back_share", C.c_float), ("min_front", C.c_float), ("reach", C.c_float), ("limit", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, back_share=0.25, min_front=0.1, reach=1e30, limit=0.45, flags=0, reserved=0):
+        super().__init__(float(back_share), float(min_front), float(reach), float(limit), int(flags), int(reserved))
+
+
+def _relocate(relocate, call):
+    """relocate of a probe-relocation call -> what ctypes hands the library: a reference, or None (which the library refuses)"""
+    if relocate is not None and not isinstance(relocate, VolumeRelocate):
+        raise TypeError("%s: relocate is a VolumeRelocate" % call)
+    return C.byref(relocate) if relocate is not None else None
+
+
+def relocate_states(offsets):
+    """offset rows float32 [probes, 4] -> their state words uint32 [probes]"""
+    return np.ascontiguousarray(offsets, np.float32).reshape(-1, 4)[:, 3].copy().view(np.uint32)
+
+
+def relocate_rule(states):
+    """state words -> the rule that fired, 1 .. 3 (0: never relocated)"""
+    return (np.asarray(states, np.uint32) >> 1) & 3
+
+
+def volume_relocate_row_of(grid, relocate, face_size, hit, normal, offset):
+    """flx_volume_relocate_row_of, the library's one definition of a probe's relocation on the host (include/flx_volume_relocate.h): hit and normal float32
+    [6 w w, 4] (the HIT plane's int32 word 3 as bits), offset float32 [4] -> the new offset row float32 [4]; the arguments are left alone"""
+    if not isinstance(grid, VolumeGrid) or not isinstance(relocate, VolumeRelocate):
+        raise TypeError("volume_relocate_row_of: grid is a VolumeGrid, relocate a VolumeRelocate")
+    rays = probe_ray_count(face_size)
+    hit, normal = np.ascontiguousarray(hit).reshape(-1), np.ascontiguousarray(normal).reshape(-1)
+    if not 1 <= int(face_size) <= 256 or hit.nbytes != rays * 16 or normal.nbytes != rays * 16:
+        raise ValueError("volume_relocate_row_of: 6 w w rows of 16 bytes in each plane")
+    out = np.array(offset, np.float32).reshape(4)
+    LIB.flx_volume_relocate_row_of(C.byref(grid), C.byref(relocate), int(face_size), hit.ctypes.data_as(C.POINTER(C.c_float)), normal.ctypes.data_as(C.POINTER(C.c_float)), _fp(out))
+    return out
+
+
+def volume_irradiance_relocated_of(grid, vmap, sh, maps, offsets, position, normal):
+    """flx_volume_irradiance_relocated_of, the library's one definition of the lookup with offsets on the host: vmap and maps may both be None (the whole-sphere
+    moments); offsets float32 [probes, 4]; otherwise as volume_irradiance_map_of"""
+    if not isinstance(grid, VolumeGrid) or (vmap is not None and not isinstance(vmap, VolumeMap)):
+        raise TypeError("volume_irradiance_relocated_of: grid is a VolumeGrid, map a VolumeMap or None")
+    if (vmap is None) != (maps is None):
+        raise ValueError("volume_irradiance_relocated_of: a map and its rows go together")
+    sh = np.ascontiguousarray(sh, np.float32).reshape(-1, 36)
+    offsets = np.ascontiguousarray(offsets, np.float32).reshape(-1, 4)
+    if maps is not None:
+        maps = np.ascontiguousarray(maps, np.float32).reshape(-1, 4)
+    if sh.shape[0] != grid.probes or offsets.shape[0] != grid.probes or (maps is not None and maps.shape[0] != grid.probes * vmap.bins):
+        raise ValueError("volume_irradiance_relocated_of: one SH row, one offset row and size x size map rows per probe of the grid")
+    one = np.ndim(position) == 1
+    positions = _surface_rows(np.atleast_2d(position), "positions", "volume_irradiance_relocated_of")
+    normals = _surface_rows(np.atleast_2d(normal), "normals", "volume_irradiance_relocated_of")
+    if len(normals) != len(positions):
+        raise ValueError("volume_irradiance_relocated_of: a normal per position")
+    out = np.zeros((len(positions), 4), np.float32)
+    for k in range(len(positions)):
+        LIB.flx_volume_irradiance_relocated_of(C.byref(grid), C.byref(vmap) if vmap is not None else None, _fp(sh), _fp(maps) if maps is not None else None, _fp(offsets),
+                                               _fp(positions[k]), _fp(normals[k]), _fp(out[k]))
+    return out[0] if one else out
+
+
 def probe_ray_count(face_size):
     """rays of a probe of that face size: 6 w w"""
     return 6 * int(face_size) * int(face_size)
@@ -442,6 +517,27 @@ def _load():
                                         fp, fp, C.POINTER(u32)]),
         "flx_volume_blend_row_of": (u32, [C.POINTER(VolumeUpdate), u32, fp, fp, fp, fp]),
         "flx_debug_last_volume_update": (C.c_int, [vp, C.POINTER(u32)]),
+        "flx_probe_relocate_device": (C.c_int, [vp, C.POINTER(VolumeGrid), C.POINTER(VolumeRelocate), vp, vp, u32, u32, u32, vp, vp]),
+        "flx_probe_relocate": (C.c_int, [vp, C.POINTER(VolumeGrid), C.POINTER(VolumeRelocate), vp, vp, u32, u32, u32, fp]),
+        "flx_volume_positions_offset_device": (C.c_int, [vp, C.POINTER(VolumeGrid), vp, C.POINTER(VolumeUpdate), vp, u32, vp, vp]),
+        "flx_volume_positions_offset": (C.c_int, [vp, C.POINTER(VolumeGrid), fp, C.POINTER(VolumeUpdate), C.POINTER(u32), u32, fp]),
+        "flx_volume_relocate_device": (C.c_int, [vp, C.c_int32, C.POINTER(VolumeGrid), C.POINTER(VolumeRelocate), u32, vp, vp]),
+        "flx_volume_relocate": (C.c_int, [vp, C.c_int32, C.POINTER(VolumeGrid), C.POINTER(VolumeRelocate), u32, fp]),
+        "flx_volume_irradiance_relocated_device": (C.c_int, [vp, C.POINTER(VolumeGrid), vp, vp, vp, u32, vp, C.POINTER(VolumeMap), vp, vp, vp]),
+        "flx_volume_irradiance_relocated": (C.c_int, [vp, C.POINTER(VolumeGrid), fp, fp, fp, u32, fp, C.POINTER(VolumeMap), fp, fp]),
+        "flx_rays_irradiance_relocated_device": (C.c_int, [vp, C.c_int32, C.POINTER(VolumeGrid), vp, vp, u32, vp, C.POINTER(VolumeMap), vp, vp, vp]),
+        "flx_rays_irradiance_relocated": (C.c_int, [vp, C.c_int32, C.POINTER(VolumeGrid), fp, fp, u32, fp, C.POINTER(VolumeMap), fp, fp]),
+        "flx_frame_irradiance_relocated_device": (C.c_int, [vp, C.POINTER(FrameParams), C.POINTER(VolumeGrid), vp, vp, C.POINTER(VolumeMap), vp, vp]),
+        "flx_frame_irradiance_relocated": (C.c_int, [vp, C.POINTER(FrameParams), C.POINTER(VolumeGrid), fp, fp, C.POINTER(VolumeMap), fp, fp]),
+        "flx_volume_bake_relocated_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), C.POINTER(VolumeGrid), C.POINTER(VolumeMap), vp, vp, vp, vp]),
+        "flx_volume_bake_relocated": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), C.POINTER(VolumeGrid), C.POINTER(VolumeMap), fp, fp, fp]),
+        "flx_volume_update_relocated_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), C.POINTER(VolumeGrid), C.POINTER(VolumeMap), C.POINTER(VolumeUpdate), vp, u32,
+                                                         vp, vp, vp, vp, vp]),
+        "flx_volume_update_relocated": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(ProbeParams), C.POINTER(VolumeGrid), C.POINTER(VolumeMap), C.POINTER(VolumeUpdate), C.POINTER(u32),
+                                                  u32, fp, fp, fp, C.POINTER(u32)]),
+        "flx_volume_irradiance_relocated_of": (None, [C.POINTER(VolumeGrid), C.POINTER(VolumeMap), fp, fp, fp, fp, fp, fp]),
+        "flx_volume_relocate_row_of": (None, [C.POINTER(VolumeGrid), C.POINTER(VolumeRelocate), u32, fp, fp, fp]),
+        "flx_debug_last_volume_relocate": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_textures_upload": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32]),
         "flx_textures_upload_device": (C.c_int, [vp, C.c_int, C.POINTER(Image), u32, u32, u32, vp]),
         "flx_texture_update": (C.c_int, [vp, C.c_int, u32, C.POINTER(Image)]),
@@ -1839,6 +1935,261 @@ class Context:
         out = (C.c_uint32 * 8)()
         self._check(LIB.flx_debug_last_volume_update(self._h, out), "flx_debug_last_volume_update")
         return dict(zip(("entries", "groups", "size", "listed", "chunks", "fused"), list(out)[:6]))
+
+    # -- probe relocation: an offset row per probe, made from the probes' own first hits, and everything that honours it ----------------
+    def _offsets_in(self, offsets, grid, call):
+        """the offset rows of a *_device call: a contiguous tensor of probes x 16 bytes on the context's device, or an address -> the address"""
+        return self._device_out(offsets, (grid.probes if grid is not None else 0) * 16, call, "offsets")
+
+    @staticmethod
+    def _host_offsets(offsets, grid, call, copy=False):
+        offsets = (np.array if copy else np.ascontiguousarray)(offsets, np.float32).reshape(-1, 4)
+        if grid is not None and offsets.shape[0] != grid.probes:
+            raise ValueError("%s: one offset row per probe of the grid" % call)
+        return offsets
+
+    def probe_relocate_device(self, grid, relocate, hit, normal, n_probes, face_size, offsets, first_probe=0, stream=None):
+        """flx_probe_relocate_device: the reduction alone — n_probes x 6 w w rows of a HIT plane and of a NORMAL plane (contiguous tensors on the context's device, or
+        addresses) to the offset rows first_probe .. of offsets (probes x 16 bytes), updated IN PLACE.  Needs no scene.  ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET
+        COMPLETE."""
+        call = "probe_relocate_device"
+        g, r, n = _grid(grid, call), _relocate(relocate, call), int(n_probes)
+        rows = n * probe_ray_count(face_size)
+        h = self._device_out(hit, rows * 16, call, "hit")
+        q = self._device_out(normal, rows * 16, call, "normal")
+        o = self._offsets_in(offsets, grid, call)
+        self._check(LIB.flx_probe_relocate_device(self._h, g, r, C.c_void_p(h), C.c_void_p(q), n, int(face_size), int(first_probe), C.c_void_p(o), _stream_handle(stream)),
+                    "flx_probe_relocate_device")
+        return offsets
+
+    def probe_relocate(self, grid, relocate, hit, normal, n_probes, face_size, offsets, first_probe=0):
+        """flx_probe_relocate: the same for host arrays (the planes of any dtype, 16 bytes a row) -> the updated offset rows float32 [probes, 4], complete; the
+        arguments are left alone"""
+        call = "probe_relocate"
+        g, r, n = _grid(grid, call), _relocate(relocate, call), int(n_probes)
+        hit, normal = np.ascontiguousarray(hit).reshape(-1), np.ascontiguousarray(normal).reshape(-1)
+        rows = n * probe_ray_count(face_size) if 1 <= int(face_size) <= 256 else 0
+        if rows and (hit.nbytes != rows * 16 or normal.nbytes != rows * 16):
+            raise ValueError("probe_relocate: a row of 16 bytes in each plane for every ray of every probe")
+        offsets = self._host_offsets(offsets, grid, call, copy=True)
+        self._check(LIB.flx_probe_relocate(self._h, g, r, hit.ctypes.data_as(C.c_void_p), normal.ctypes.data_as(C.c_void_p), n, int(face_size), int(first_probe), _fp(offsets)),
+                    "flx_probe_relocate")
+        return offsets
+
+    def volume_positions_offset_device(self, grid, offsets, update=None, indices=None, n=None, out=None, stream=None):
+        """flx_volume_positions_offset_device: the positions of the grid's probes (update None: n = probes) or of a list's entries (update, indices: as for
+        volume_positions_list_device) with their offsets added, probes_sh_device's input.  Needs no scene.  Returns the rows ENQUEUED ON THE CONTEXT'S STREAM AND NOT
+        YET COMPLETE."""
+        call = "volume_positions_offset_device"
+        g, u = _grid(grid, call), _update(update, call)
+        if update is None and indices is None and n is None:
+            n = grid.probes if grid is not None else 0
+        i, n = self._list_in(indices, n, call)
+        d = self._offsets_in(offsets, grid, call)
+        if out is None:
+            out = self._new_rows(n, 4)
+        o = self._device_out(out, n * 16, call, "out")
+        self._check(LIB.flx_volume_positions_offset_device(self._h, g, C.c_void_p(d), u, C.c_void_p(i), n, C.c_void_p(o), _stream_handle(stream)), "flx_volume_positions_offset_device")
+        return out
+
+    def volume_positions_offset(self, grid, offsets, update=None, indices=None, n=None):
+        """flx_volume_positions_offset: -> the position rows float32 [n, 4] in host memory, complete"""
+        call = "volume_positions_offset"
+        g, u = _grid(grid, call), _update(update, call)
+        if update is None and indices is None and n is None:
+            n = grid.probes if grid is not None else 0
+        indices, i, n = _host_list(indices, n, call)
+        offsets = self._host_offsets(offsets, grid, call)
+        out = np.zeros((n, 4), np.float32)
+        self._check(LIB.flx_volume_positions_offset(self._h, g, _fp(offsets), u, i, n, _fp(out)), "flx_volume_positions_offset")
+        return out
+
+    def volume_relocate_device(self, grid, relocate, face_size, offsets, texture_width=32, stream=None):
+        """flx_volume_relocate_device: one pass of the whole path — every probe's rays cast from its offset position at the resident scene, their first hits reduced
+        to the probe's new offset row and state, IN PLACE in offsets.  Iterate it a few times and end with one pass under RELOCATE_FREEZE.  ENQUEUED ON THE
+        CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        call = "volume_relocate_device"
+        g, r = _grid(grid, call), _relocate(relocate, call)
+        o = self._offsets_in(offsets, grid, call)
+        self._check(LIB.flx_volume_relocate_device(self._h, int(texture_width), g, r, int(face_size), C.c_void_p(o), _stream_handle(stream)), "flx_volume_relocate_device")
+        return offsets
+
+    def volume_relocate(self, grid, relocate, face_size, offsets=None, texture_width=32):
+        """flx_volume_relocate: the same for a host array (None: zeros) -> the updated offset rows float32 [probes, 4], complete; the argument is left alone"""
+        call = "volume_relocate"
+        g, r = _grid(grid, call), _relocate(relocate, call)
+        offsets = np.zeros(((grid.probes if grid is not None else 0), 4), np.float32) if offsets is None else self._host_offsets(offsets, grid, call, copy=True)
+        self._check(LIB.flx_volume_relocate(self._h, int(texture_width), g, r, int(face_size), _fp(offsets)), "flx_volume_relocate")
+        return offsets
+
+    def volume_irradiance_relocated_device(self, grid, sh, positions, normals, offsets, vmap=None, maps=None, n=None, out=None, stream=None):
+        """flx_volume_irradiance_relocated_device: volume_irradiance_device (volume_irradiance_map_device where vmap and maps are given) with the probes at their offset
+        positions and inactive probes left out.  Returns the rows ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        call = "volume_irradiance_relocated_device"
+        g, m = _grid(grid, call), _map(vmap, call)
+        if n is None:
+            n = positions.shape[0]
+        n = int(n)
+        s = self._device_out(sh, (grid.probes if grid is not None else 0) * 144, call, "sh")
+        p = self._device_out(positions, n * 16, call, "positions")
+        q = self._device_out(normals, n * 16, call, "normals")
+        d = self._maps_in(maps, vmap, grid, call) if maps is not None else 0
+        f = self._offsets_in(offsets, grid, call)
+        if out is None:
+            out = self._new_rows(n, 4)
+        o = self._device_out(out, n * 16, call, "out")
+        self._check(LIB.flx_volume_irradiance_relocated_device(self._h, g, C.c_void_p(s), C.c_void_p(p), C.c_void_p(q), n, C.c_void_p(o), m, C.c_void_p(d), C.c_void_p(f),
+                                                               _stream_handle(stream)), "flx_volume_irradiance_relocated_device")
+        return out
+
+    def _host_relocated(self, grid, vmap, sh, maps, offsets, call):
+        if maps is not None:
+            sh, maps = self._host_maps(grid, vmap, sh, maps, call)
+        else:
+            sh = np.ascontiguousarray(sh, np.float32).reshape(-1, 36)
+        return sh, maps, self._host_offsets(offsets, grid, call)
+
+    def volume_irradiance_relocated(self, grid, sh, positions, normals, offsets, vmap=None, maps=None):
+        """flx_volume_irradiance_relocated: the same for host arrays -> the irradiance rows float32 [n, 4], complete"""
+        call = "volume_irradiance_relocated"
+        g, m = _grid(grid, call), _map(vmap, call)
+        sh, maps, offsets = self._host_relocated(grid, vmap, sh, maps, offsets, call)
+        positions, normals = _surface_rows(positions, "positions", call), _surface_rows(normals, "normals", call)
+        if len(positions) != len(normals):
+            raise ValueError("volume_irradiance_relocated: a normal per position")
+        out = np.zeros((len(positions), 4), np.float32)
+        self._check(LIB.flx_volume_irradiance_relocated(self._h, g, _fp(sh), _fp(positions), _fp(normals), len(positions), _fp(out), m, _fp(maps) if maps is not None else None,
+                                                        _fp(offsets)), "flx_volume_irradiance_relocated")
+        return out
+
+    def rays_irradiance_relocated_device(self, grid, sh, rays, offsets, vmap=None, maps=None, texture_width=32, out=None, stream=None):
+        """flx_rays_irradiance_relocated_device: rays_irradiance_device (rays_irradiance_map_device with vmap and maps) with offsets.  Returns the rows ENQUEUED ON THE
+        CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        call = "rays_irradiance_relocated_device"
+        g, m = _grid(grid, call), _map(vmap, call)
+        r, n = _ray_rows(rays, self._device, call)
+        s = self._device_out(sh, (grid.probes if grid is not None else 0) * 144, call, "sh")
+        d = self._maps_in(maps, vmap, grid, call) if maps is not None else 0
+        f = self._offsets_in(offsets, grid, call)
+        if out is None:
+            out = self._new_rows(n, 4)
+        o = self._device_out(out, n * 16, call, "out")
+        self._check(LIB.flx_rays_irradiance_relocated_device(self._h, int(texture_width), g, C.c_void_p(s), C.c_void_p(r), n, C.c_void_p(o), m, C.c_void_p(d), C.c_void_p(f),
+                                                             _stream_handle(stream)), "flx_rays_irradiance_relocated_device")
+        return out
+
+    def rays_irradiance_relocated(self, grid, sh, rays, offsets, vmap=None, maps=None, texture_width=32):
+        """flx_rays_irradiance_relocated: the same for host arrays -> the irradiance rows float32 [n, 4], complete"""
+        call = "rays_irradiance_relocated"
+        g, m = _grid(grid, call), _map(vmap, call)
+        sh, maps, offsets = self._host_relocated(grid, vmap, sh, maps, offsets, call)
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros((rays.shape[0], 4), np.float32)
+        self._check(LIB.flx_rays_irradiance_relocated(self._h, int(texture_width), g, _fp(sh), _fp(rays), rays.shape[0], _fp(out), m, _fp(maps) if maps is not None else None,
+                                                      _fp(offsets)), "flx_rays_irradiance_relocated")
+        return out
+
+    def frame_irradiance_relocated_device(self, params, grid, sh, offsets, vmap=None, maps=None, out=None):
+        """flx_frame_irradiance_relocated_device: frame_irradiance_device (frame_irradiance_map_device with vmap and maps) with offsets.  Returns the image ENQUEUED ON
+        THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        call = "frame_irradiance_relocated_device"
+        g, m = _grid(grid, call), _map(vmap, call)
+        width, height = (int(params.width), int(params.height)) if params is not None else (0, 0)
+        s = self._device_out(sh, (grid.probes if grid is not None else 0) * 144, call, "sh")
+        d = self._maps_in(maps, vmap, grid, call) if maps is not None else 0
+        f = self._offsets_in(offsets, grid, call)
+        if out is None:
+            import torch
+            out = torch.empty((height, width, 4), dtype=torch.float32, device="cuda:%d" % self._device)
+        o = self._device_out(out, width * height * 16, call, "out")
+        self._check(LIB.flx_frame_irradiance_relocated_device(self._h, C.byref(params) if params is not None else None, g, C.c_void_p(s), C.c_void_p(o), m, C.c_void_p(d),
+                                                              C.c_void_p(f)), "flx_frame_irradiance_relocated_device")
+        return out
+
+    def frame_irradiance_relocated(self, params, grid, sh, offsets, vmap=None, maps=None):
+        """flx_frame_irradiance_relocated: the same for host arrays -> the irradiance image float32 [height, width, 4], complete"""
+        call = "frame_irradiance_relocated"
+        g, m = _grid(grid, call), _map(vmap, call)
+        sh, maps, offsets = self._host_relocated(grid, vmap, sh, maps, offsets, call)
+        width, height = (int(params.width), int(params.height)) if params is not None else (0, 0)
+        out = np.zeros((height, width, 4), np.float32)
+        self._check(LIB.flx_frame_irradiance_relocated(self._h, C.byref(params) if params is not None else None, g, _fp(sh), _fp(out), m, _fp(maps) if maps is not None else None,
+                                                       _fp(offsets)), "flx_frame_irradiance_relocated")
+        return out
+
+    def volume_bake_relocated_device(self, grid, trace_params, params, offsets, vmap=None, out=None, maps=None, stream=None):
+        """flx_volume_bake_relocated_device: volume_positions_offset_device into a buffer the context owns and probes_sh_device (probes_sh_map_device with vmap) from
+        there.  Returns (SH rows [probes, 36], map rows [probes * bins, 4] or None) ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        call = "volume_bake_relocated_device"
+        if trace_params is not None and not isinstance(trace_params, TraceParams):
+            raise TypeError("volume_bake_relocated_device: trace_params is a TraceParams")
+        if params is not None and not isinstance(params, ProbeParams):
+            raise TypeError("volume_bake_relocated_device: params is a ProbeParams")
+        g, m = _grid(grid, call), _map(vmap, call)
+        probes = grid.probes if grid is not None else 0
+        f = self._offsets_in(offsets, grid, call)
+        if out is None:
+            out = self._new_rows(probes, 36)
+        o = self._device_out(out, probes * 144, call, "out")
+        q = 0
+        if vmap is not None or maps is not None:
+            maps, q = self._maps_out(maps, vmap, probes, call)
+        self._check(LIB.flx_volume_bake_relocated_device(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None, g, m,
+                                                         C.c_void_p(f), C.c_void_p(o), C.c_void_p(q), _stream_handle(stream)), "flx_volume_bake_relocated_device")
+        return out, maps
+
+    def volume_bake_relocated(self, grid, trace_params, params, offsets, vmap=None):
+        """flx_volume_bake_relocated: -> (SH rows float32 [probes, 36], map rows float32 [probes * bins, 4] or None) in host memory, complete"""
+        call = "volume_bake_relocated"
+        g, m = _grid(grid, call), _map(vmap, call)
+        probes = grid.probes if grid is not None else 0
+        offsets = self._host_offsets(offsets, grid, call)
+        out = np.zeros((probes, 36), np.float32)
+        maps = np.zeros((_map_rows(vmap, probes), 4), np.float32) if vmap is not None else None
+        self._check(LIB.flx_volume_bake_relocated(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None, g, m,
+                                                  _fp(offsets), _fp(out), _fp(maps) if maps is not None else None), "flx_volume_bake_relocated")
+        return out, maps
+
+    def volume_update_relocated_device(self, grid, trace_params, params, vmap, update, offsets, sh, maps=None, indices=None, n_list=None, state=None, stream=None):
+        """flx_volume_update_relocated_device: volume_update_device with the listed probes traced from their offset positions.  Returns the states (or None) ENQUEUED
+        ON THE CONTEXT'S STREAM AND NOT YET COMPLETE, like the rows."""
+        call = "volume_update_relocated_device"
+        if trace_params is not None and not isinstance(trace_params, TraceParams):
+            raise TypeError("volume_update_relocated_device: trace_params is a TraceParams")
+        if params is not None and not isinstance(params, ProbeParams):
+            raise TypeError("volume_update_relocated_device: params is a ProbeParams")
+        g, m, u = _grid(grid, call), _map(vmap, call), _update(update, call)
+        i, n = self._list_in(indices, n_list, call)
+        probes = grid.probes if grid is not None else 0
+        f = self._offsets_in(offsets, grid, call)
+        s = self._device_out(sh, probes * 144, call, "sh")
+        d = self._device_out(maps, _map_rows(vmap, probes) * 16, call, "maps") if maps is not None else 0
+        state, t = self._state_out(state, n, call)
+        self._check(LIB.flx_volume_update_relocated_device(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None, g, m, u,
+                                                           C.c_void_p(i), n, C.c_void_p(f), C.c_void_p(s), C.c_void_p(d), C.c_void_p(t), _stream_handle(stream)),
+                    "flx_volume_update_relocated_device")
+        return state
+
+    def volume_update_relocated(self, grid, trace_params, params, vmap, update, offsets, sh, maps=None, indices=None, n_list=None):
+        """flx_volume_update_relocated: the same for host arrays -> (the updated SH rows, the updated map rows or None, the states uint32 [n_list]), complete; the
+        arguments are left alone"""
+        call = "volume_update_relocated"
+        g, m, u = _grid(grid, call), _map(vmap, call), _update(update, call)
+        indices, i, n = _host_list(indices, n_list, call)
+        sh, maps = self._host_resident(grid, vmap, sh, maps, call)
+        offsets = self._host_offsets(offsets, grid, call)
+        state = np.zeros(n, np.uint32)
+        self._check(LIB.flx_volume_update_relocated(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(params) if params is not None else None, g, m, u, i, n,
+                                                    _fp(offsets), _fp(sh), _fp(maps) if maps is not None else None, state.ctypes.data_as(C.POINTER(C.c_uint32))),
+                    "flx_volume_update_relocated")
+        return sh, maps, state
+
+    def last_volume_relocate(self):
+        """flx_debug_last_volume_relocate -> dict (zeros when none ran): probes, face_size, chunks (0 for the reduction alone), chunk (the probes of a full chunk),
+        groups (workgroups of the last k_probe_relocate), flags, first (first_probe), fused (1 for the whole path).  Waits for nothing."""
+        out = (C.c_uint32 * 8)()
+        self._check(LIB.flx_debug_last_volume_relocate(self._h, out), "flx_debug_last_volume_relocate")
+        return dict(zip(("probes", "face_size", "chunks", "chunk", "groups", "flags", "first", "fused"), list(out)))
 
     # -- surface rows -------------------------------------------------------------------------------
     def _surface_out(self, out, n, fields, call):

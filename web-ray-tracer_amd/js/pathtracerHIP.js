@@ -355,7 +355,9 @@ class PathTracerHIP {
    * options.map = { size: 1 .. 16, sharpness: 0 .. 8 = 5 }: DIRECTIONAL VISIBILITY ("directional visibility", flx_volume_bake_map_device) — every probe also gets an
    * octahedral map of size x size bins of distance moments, baked from the same rays and kept on the device beside the SH rows; renderIrradiance and
    * irradianceRays then weigh a probe by what it sees TOWARDS the point, not all around: walls stop leaking and open rooms are not dimmed.  The handle has map and
-   * maps() (4 floats per bin) then.  Without options.map every call does what it did. */
+   * maps() (4 floats per bin) then.  Without options.map every call does what it did.
+   * options.relocate = relocateVolume's options: PROBE RELOCATION first, from zero offsets, and the bake from the moved positions (flx_volume_bake_relocated_device);
+   * the handle has offsets() and states() then, and every later call on it goes through the relocated calls. */
   bakeVolume (grid, options) {
     if (this._devices) throw new Error('bakeVolume: one GPU only (a group of GPUs traces no rays)');
     const o = options || {};
@@ -372,10 +374,51 @@ class PathTracerHIP {
       if (o.map === null || typeof o.map !== 'object' || typeof o.map.size !== 'number') throw new TypeError('bakeVolume: map is { size, sharpness }');
       probe.map = { size: o.map.size, sharpness: o.map.sharpness === undefined ? 5 : o.map.sharpness };
     }
+    if (o.relocate !== undefined) probe.relocate = this._relocateOptions(o.relocate, 'bakeVolume');
     const handle = native().bakeVolume(context, g, this.traceParams(options), probe);
     const volume = { grid: g, probes: g.count[0] * g.count[1] * g.count[2], _handle: handle, rows: () => new Float32Array(native().volumeRows(context, handle)) };
     if (probe.map) Object.assign(volume, { map: probe.map, maps: () => new Float32Array(native().volumeMaps(context, handle)) });
+    if (probe.relocate) this._withOffsets(volume, context);
     return volume;
+  }
+
+  /* relocateVolume's options with their defaults -> what the addon reads; `call`: the method's name, for the messages */
+  _relocateOptions (options, call) {
+    const o = options || {};
+    if (o === null || typeof o !== 'object') throw new TypeError(call + ': relocate is { backShare, minFront, reach, limit, iterations, faceSize }');
+    for (const k of ['minFront', 'reach']) if (typeof o[k] !== 'number') throw new TypeError(call + ': ' + k + ' is a number (world units)');
+    const r = { backShare: o.backShare === undefined ? 0.25 : o.backShare, minFront: o.minFront, reach: o.reach, limit: o.limit === undefined ? 0.45 : o.limit,
+      iterations: o.iterations === undefined ? 4 : o.iterations, faceSize: o.faceSize === undefined ? 8 : o.faceSize };
+    if (!Number.isInteger(r.iterations) || r.iterations < 0 || r.iterations > 64) throw new RangeError(call + ': iterations is a whole number, 0 .. 64');
+    if (!Number.isInteger(r.faceSize) || r.faceSize < 0 || r.faceSize > 0xffffffff) throw new RangeError(call + ': faceSize is a whole number');
+    return r;
+  }
+
+  /* a handle that has offsets: offsets() fetches them (4 floats per probe: x, y, z and the state's bits), states() the state words */
+  _withOffsets (volume, context) {
+    const handle = volume._handle;
+    volume.offsets = () => new Float32Array(native().volumeOffsets(context, handle));
+    volume.states = () => Uint32Array.from(new Uint32Array(native().volumeOffsets(context, handle)).filter((_, i) => i % 4 === 3));
+    return volume;
+  }
+
+  /* PROBE RELOCATION (include/flexlight_hip_debug.h "probe relocation", flx_volume_relocate_device): probes that lie inside geometry or within a hair of a wall are
+   * moved — out of geometry, away from a near wall, back towards the lattice where there is room — and probes that are inside something or see no front face
+   * within reach are switched off.  options: { backShare = 0.25, minFront, reach, limit = 0.45, iterations = 4, faceSize = 8 }; minFront and reach are world units.
+   * The handle keeps an offsets array on the device, zero-filled at the first call; `iterations` passes run and then one frozen pass, which moves nothing and
+   * classifies every probe where it stands.  Returns { offsets: Float32Array (4 floats per probe: x, y, z and the state's bits), states: Uint32Array (bit 0
+   * inactive, bits 1 - 2 the rule that fired, bit 3 rejected) }.  From then on updateVolume, renderIrradiance and irradianceRays on this handle take the relocated
+   * calls: a probe stands at its lattice point plus its offset, and an inactive probe gets no weight.  The handle's rows and maps are NOT re-baked: call
+   * updateVolume with hysteresis 0 over the probes that moved, or bake with bakeVolume(grid, { relocate }) in the first place.  It waits for the passes. */
+  relocateVolume (volume, options) {
+    if (this._devices) throw new Error('relocateVolume: one GPU only (a group of GPUs casts no rays)');
+    if (!volume || !volume._handle) throw new TypeError('relocateVolume: volume is what bakeVolume returned');
+    const r = this._relocateOptions(options, 'relocateVolume');
+    this._uploadFrameState();
+    const context = this._context();
+    const buffer = native().relocateVolume(context, volume._handle, Math.floor(2048 / this.scene.standardTextureSizes[0]), r);
+    if (!volume.offsets) this._withOffsets(volume, context);
+    return { offsets: new Float32Array(buffer), states: Uint32Array.from(new Uint32Array(buffer).filter((_, i) => i % 4 === 3)) };
   }
 
   /* VOLUME UPDATES (include/flexlight_hip_debug.h "volume updates", flx_volume_update_device): a baked volume kept alive over many frames.  The probes named by
@@ -383,7 +426,8 @@ class PathTracerHIP {
    * again with the face size, sky and order the volume was baked with and with options' traceRays' fields (vary randomSeed from update to update), and the new rows
    * are blended into the handle's resident rows, and its maps if it has them, IN PLACE on the device: old + (new - old) (1 - options.hysteresis).  A new row that
    * holds a NaN or an infinity is rejected; a probe that was never baked takes the new row.  Returns { states: Uint32Array }, per entry 0 blended, 1 taken, 2 kept,
-   * 3 skipped (an index outside the grid).  It waits for the update.  A list that names a probe twice gives that probe one of the possible results. */
+   * 3 skipped (an index outside the grid).  It waits for the update.  A list that names a probe twice gives that probe one of the possible results.
+   * A handle that has offsets (relocateVolume) traces the listed probes from their offset positions (flx_volume_update_relocated_device). */
   updateVolume (volume, options) {
     if (this._devices) throw new Error('updateVolume: one GPU only (a group of GPUs traces no rays)');
     if (!volume || !volume._handle) throw new TypeError('updateVolume: volume is what bakeVolume returned');
@@ -401,7 +445,8 @@ class PathTracerHIP {
   /* The irradiance IMAGE of the frame the next renderFrame() would trace without jitter (flx_frame_irradiance_device; flx_frame_irradiance_map_device where the
    * volume was baked with a map): per pixel the irradiance the volume gives
    * the primary hit's position and ray-facing normal — r g b and the sum of the weights; a pixel that hits nothing is 0 0 0 0.  Nothing but the image crosses the
-   * bus.  volume: bakeVolume's handle.  Returns a Float32Array of 4 floats per pixel, row 0 on top, with width and height beside it. */
+   * bus.  volume: bakeVolume's handle; one that has offsets (relocateVolume) goes through flx_frame_irradiance_relocated_device, as irradianceRays goes through
+   * flx_rays_irradiance_relocated_device.  Returns a Float32Array of 4 floats per pixel, row 0 on top, with width and height beside it. */
   renderIrradiance (volume) {
     if (this._devices) throw new Error('renderIrradiance: one GPU only (a group of GPUs casts no rays)');
     if (!volume || !volume._handle) throw new TypeError('renderIrradiance: volume is what bakeVolume returned');

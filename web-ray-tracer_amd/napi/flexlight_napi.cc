@@ -469,10 +469,13 @@ struct VolumeBox {
   void *d_maps = nullptr;
   /* volume updates ("volume updates"): updateVolume re-bakes listed probes with the face size, order and sky the volume was baked with */
   flx_probe_params probe = { 0u, 0u, { 0.0f, 0.0f, 0.0f }, 0.0f };
+  /* probe relocation ("probe relocation"): one offset row per probe in device memory, zero-filled at the first relocateVolume; a handle that has them goes through
+   * the relocated calls, one without goes where it went */
+  void *d_offsets = nullptr;
 };
 static void finalize_volume(napi_env env, void *data, void *) {
   VolumeBox *v = static_cast<VolumeBox *>(data);
-  if (hipSetDevice(v->device) == hipSuccess) { (void)hipFree(v->d_sh); (void)hipFree(v->d_io); (void)hipFree(v->d_maps); }
+  if (hipSetDevice(v->device) == hipSuccess) { (void)hipFree(v->d_sh); (void)hipFree(v->d_io); (void)hipFree(v->d_maps); (void)hipFree(v->d_offsets); }
   if (v->context) napi_delete_reference(env, v->context);
   delete v;
 }
@@ -513,8 +516,43 @@ static bool read_grid(napi_env env, napi_value o, flx_volume_grid *g) {
   return true;
 }
 
-/* bakeVolume(handle, grid, params (traceRays'), { faceSize, order, sky[3], map: { size, sharpness } or undefined }) -> volume handle: flx_volume_bake_device — with a
- * map flx_volume_bake_map_device — into device memory the handle owns */
+/* { backShare, minFront, reach, limit, iterations, faceSize } -> the relocation, its passes and its face size; the library judges the values */
+struct RelocateOptions { struct flx_volume_relocate r; uint32_t iterations, face_size; };
+static bool read_relocate(napi_env env, napi_value o, RelocateOptions *out) {
+  double d = 0;
+  memset(out, 0, sizeof *out);
+  if (!num(env, o, "backShare", &d)) return false; out->r.back_share = (float)d;
+  if (!num(env, o, "minFront", &d)) return false; out->r.min_front = (float)d;
+  if (!num(env, o, "reach", &d)) return false; out->r.reach = (float)d;
+  if (!num(env, o, "limit", &d)) return false; out->r.limit = (float)d;
+  napi_value v;
+  if (napi_get_named_property(env, o, "iterations", &v) != napi_ok || napi_get_value_uint32(env, v, &out->iterations) != napi_ok ||
+      napi_get_named_property(env, o, "faceSize", &v) != napi_ok || napi_get_value_uint32(env, v, &out->face_size) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "relocateVolume: iterations and faceSize are numbers");
+    return false;
+  }
+  return true;
+}
+/* the volume has offset rows: zero-filled where it had none */
+static bool volume_offsets(napi_env env, VolumeBox *v) {
+  if (v->d_offsets) return true;
+  if (!hip_ok(env, hipSetDevice(v->device), "hipSetDevice") || !hip_ok(env, hipMalloc(&v->d_offsets, (size_t)v->probes * 16), "hipMalloc")) return false;
+  return hip_ok(env, hipMemset(v->d_offsets, 0, (size_t)v->probes * 16), "hipMemset");
+}
+/* `iterations` passes of flx_volume_relocate_device on the volume's offsets and one frozen pass, which moves nothing and classifies every probe where it stands */
+static flx_status relocate_passes(flx_context *ctx, VolumeBox *v, int32_t texture_width, const RelocateOptions &o) {
+  struct flx_volume_relocate r = o.r;
+  for (uint32_t k = 0; k <= o.iterations; k++) {
+    r.flags = k == o.iterations ? FLX_VOLUME_RELOCATE_FREEZE : 0u;
+    const flx_status rc = flx_volume_relocate_device(ctx, texture_width, &v->grid, &r, o.face_size, v->d_offsets, nullptr);
+    if (rc != FLX_OK) return rc;
+  }
+  return FLX_OK;
+}
+
+/* bakeVolume(handle, grid, params (traceRays'), { faceSize, order, sky[3], map: { size, sharpness } or undefined, relocate: relocateVolume's options or undefined })
+ * -> volume handle: flx_volume_bake_device — with a map flx_volume_bake_map_device — into device memory the handle owns; with relocate the probes are relocated first
+ * (from zero offsets) and the bake is flx_volume_bake_relocated_device's, from the moved positions */
 static napi_value BakeVolume(napi_env env, napi_callback_info info) {
   napi_value argv[4];
   if (!get_args(env, info, 4, argv)) return nullptr;
@@ -544,6 +582,16 @@ static napi_value BakeVolume(napi_env env, napi_callback_info info) {
       return nullptr;
     }
   }
+  RelocateOptions relocate;
+  napi_valuetype relocate_type = napi_undefined;
+  if (napi_get_named_property(env, argv[3], "relocate", &v) != napi_ok || napi_typeof(env, v, &relocate_type) != napi_ok) { napi_throw_type_error(env, nullptr, "bakeVolume: relocate is an object"); return nullptr; }
+  const bool relocated = relocate_type != napi_undefined;
+  if (relocated && (relocate_type != napi_object || !read_relocate(env, v, &relocate))) {
+    bool pending = false;
+    napi_is_exception_pending(env, &pending);
+    if (!pending) napi_throw_type_error(env, nullptr, "bakeVolume: relocate is { backShare, minFront, reach, limit, iterations, faceSize }");
+    return nullptr;
+  }
   /* a grid the library refuses (a count of 0, 2^31 probes or more) gets no memory: the library says why */
   const uint64_t xy = (uint64_t)grid.count[0] * grid.count[1];
   const uint64_t probes = xy <= 0x7fffffffull ? xy * grid.count[2] : xy;
@@ -561,6 +609,15 @@ static napi_value BakeVolume(napi_env env, napi_callback_info info) {
   if (has_map && !hip_ok(env, hipMalloc(&volume->d_maps, (size_t)map_rows * 16), "hipMalloc")) return nullptr;
   volume->map = map;
   volume->probe = q;
+  if (relocated) {
+    if (!volume_offsets(env, volume)) return nullptr;
+    flx_status rc = relocate_passes(box->ctx, volume, p.texture_width, relocate);
+    if (rc != FLX_OK) return fail(env, box->ctx, "flx_volume_relocate_device", rc);
+    rc = flx_volume_bake_relocated_device(box->ctx, &p, &q, &grid, has_map ? &map : nullptr, volume->d_offsets, volume->d_sh, volume->d_maps, nullptr);
+    if (rc == FLX_OK) rc = flx_sync(box->ctx);
+    if (rc != FLX_OK) return fail(env, box->ctx, "flx_volume_bake_relocated_device", rc);
+    return ext;
+  }
   flx_status rc = has_map ? flx_volume_bake_map_device(box->ctx, &p, &q, &grid, &map, volume->d_sh, volume->d_maps, nullptr)
                           : flx_volume_bake_device(box->ctx, &p, &q, &grid, volume->d_sh, nullptr);
   if (rc == FLX_OK) rc = flx_sync(box->ctx);
@@ -599,6 +656,51 @@ static napi_value VolumeMaps(napi_env env, napi_callback_info info) {
   flx_status rc = flx_sync(box->ctx);
   if (rc != FLX_OK) return fail(env, box->ctx, "flx_sync", rc);
   if (!hip_ok(env, hipSetDevice(box->device), "hipSetDevice") || !hip_ok(env, hipMemcpy(rows, volume->d_maps, bytes, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
+  return buf;
+}
+
+/* volumeOffsets(handle, volume) -> ArrayBuffer(16 probes): the offset rows of a volume that has them, fetched from the device */
+static napi_value VolumeOffsets(napi_env env, napi_callback_info info) {
+  napi_value argv[2];
+  if (!get_args(env, info, 2, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  VolumeBox *volume = box ? get_volume(env, argv[1], box) : nullptr;
+  if (!volume) return nullptr;
+  if (!volume->d_offsets) { napi_throw_error(env, nullptr, "volumeOffsets: the volume was never relocated"); return nullptr; }
+  void *rows = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, (size_t)volume->probes * 16, &rows, &buf));
+  flx_status rc = flx_sync(box->ctx);
+  if (rc != FLX_OK) return fail(env, box->ctx, "flx_sync", rc);
+  if (!hip_ok(env, hipSetDevice(box->device), "hipSetDevice") || !hip_ok(env, hipMemcpy(rows, volume->d_offsets, (size_t)volume->probes * 16, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
+  return buf;
+}
+
+/* relocateVolume(handle, volume, textureWidth, { backShare, minFront, reach, limit, iterations, faceSize }) -> ArrayBuffer(16 probes): the volume's offset rows —
+ * zero-filled at the first call — after `iterations` passes of flx_volume_relocate_device and one frozen pass.  The volume's SH rows and maps are left as they are:
+ * the caller bakes or updates again.  The library judges the values. */
+static napi_value RelocateVolume(napi_env env, napi_callback_info info) {
+  napi_value argv[4];
+  if (!get_args(env, info, 4, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  VolumeBox *volume = box ? get_volume(env, argv[1], box) : nullptr;
+  if (!volume) return nullptr;
+  int32_t tw;
+  if (napi_get_value_int32(env, argv[2], &tw) != napi_ok) { napi_throw_type_error(env, nullptr, "relocateVolume: textureWidth is not a number"); return nullptr; }
+  RelocateOptions o;
+  if (!read_relocate(env, argv[3], &o)) return nullptr;
+  const bool fresh = volume->d_offsets == nullptr;
+  if (!volume_offsets(env, volume)) return nullptr;
+  flx_status rc = relocate_passes(box->ctx, volume, tw, o);
+  if (rc == FLX_OK) rc = flx_sync(box->ctx);
+  if (rc != FLX_OK) {
+    if (fresh) { (void)hipFree(volume->d_offsets); volume->d_offsets = nullptr; }      /* a refused first call leaves the handle without offsets: it goes where it went */
+    return fail(env, box->ctx, "flx_volume_relocate_device", rc);
+  }
+  void *rows = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, (size_t)volume->probes * 16, &rows, &buf));
+  if (!hip_ok(env, hipMemcpy(rows, volume->d_offsets, (size_t)volume->probes * 16, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
   return buf;
 }
 
@@ -648,10 +750,14 @@ static napi_value UpdateVolume(napi_env env, napi_callback_info info) {
     d_list = static_cast<char *>(volume->d_io); d_state = d_list + n * 4;
     if (indices && !hip_ok(env, hipMemcpy(d_list, indices, n * 4, hipMemcpyHostToDevice), "hipMemcpy")) return nullptr;
   }
-  flx_status rc = flx_volume_update_device(box->ctx, &p, &volume->probe, &volume->grid, volume->d_maps ? &volume->map : nullptr, &u, indices && fits ? d_list : nullptr, (uint32_t)n,
-                                           volume->d_sh, volume->d_maps, d_state, nullptr);
+  /* (a handle with offsets: the listed probes are traced from their offset positions) */
+  flx_status rc = volume->d_offsets
+                      ? flx_volume_update_relocated_device(box->ctx, &p, &volume->probe, &volume->grid, volume->d_maps ? &volume->map : nullptr, &u, indices && fits ? d_list : nullptr,
+                                                           (uint32_t)n, volume->d_offsets, volume->d_sh, volume->d_maps, d_state, nullptr)
+                      : flx_volume_update_device(box->ctx, &p, &volume->probe, &volume->grid, volume->d_maps ? &volume->map : nullptr, &u, indices && fits ? d_list : nullptr, (uint32_t)n,
+                                                 volume->d_sh, volume->d_maps, d_state, nullptr);
   if (rc == FLX_OK) rc = flx_sync(box->ctx);
-  if (rc != FLX_OK) return fail(env, box->ctx, "flx_volume_update_device", rc);
+  if (rc != FLX_OK) return fail(env, box->ctx, volume->d_offsets ? "flx_volume_update_relocated_device" : "flx_volume_update_device", rc);
   if (n > 0 && !hip_ok(env, hipMemcpy(states, d_state, n * 4, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
   return buf;
 }
@@ -672,10 +778,13 @@ static napi_value FrameIrradiance(napi_env env, napi_callback_info info) {
   napi_value buf;
   NAPI_OK(env, napi_create_arraybuffer(env, bytes, &image, &buf));
   if (!volume_room(env, volume, bytes ? bytes : 16)) return nullptr;
-  flx_status rc = volume->d_maps ? flx_frame_irradiance_map_device(box->ctx, &p, &volume->grid, volume->d_sh, volume->d_io, &volume->map, volume->d_maps)
-                                 : flx_frame_irradiance_device(box->ctx, &p, &volume->grid, volume->d_sh, volume->d_io);
+  flx_status rc = volume->d_offsets ? flx_frame_irradiance_relocated_device(box->ctx, &p, &volume->grid, volume->d_sh, volume->d_io, volume->d_maps ? &volume->map : nullptr, volume->d_maps,
+                                                                            volume->d_offsets)
+                  : volume->d_maps  ? flx_frame_irradiance_map_device(box->ctx, &p, &volume->grid, volume->d_sh, volume->d_io, &volume->map, volume->d_maps)
+                                    : flx_frame_irradiance_device(box->ctx, &p, &volume->grid, volume->d_sh, volume->d_io);
   if (rc == FLX_OK) rc = flx_sync(box->ctx);
-  if (rc != FLX_OK) return fail(env, box->ctx, volume->d_maps ? "flx_frame_irradiance_map_device" : "flx_frame_irradiance_device", rc);
+  if (rc != FLX_OK)
+    return fail(env, box->ctx, volume->d_offsets ? "flx_frame_irradiance_relocated_device" : volume->d_maps ? "flx_frame_irradiance_map_device" : "flx_frame_irradiance_device", rc);
   if (!hip_ok(env, hipMemcpy(image, volume->d_io, bytes, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
   return buf;
 }
@@ -701,10 +810,13 @@ static napi_value RaysIrradiance(napi_env env, napi_callback_info info) {
   if (!volume_room(env, volume, n * 48)) return nullptr;
   char *d_rays = static_cast<char *>(volume->d_io), *d_rows = d_rays + n * 32;
   if (!hip_ok(env, hipMemcpy(d_rays, rays, n * 32, hipMemcpyHostToDevice), "hipMemcpy")) return nullptr;
-  flx_status rc = volume->d_maps ? flx_rays_irradiance_map_device(box->ctx, tw, &volume->grid, volume->d_sh, d_rays, (uint32_t)n, d_rows, &volume->map, volume->d_maps, nullptr)
-                                 : flx_rays_irradiance_device(box->ctx, tw, &volume->grid, volume->d_sh, d_rays, (uint32_t)n, d_rows, nullptr);
+  flx_status rc = volume->d_offsets ? flx_rays_irradiance_relocated_device(box->ctx, tw, &volume->grid, volume->d_sh, d_rays, (uint32_t)n, d_rows, volume->d_maps ? &volume->map : nullptr,
+                                                                           volume->d_maps, volume->d_offsets, nullptr)
+                  : volume->d_maps  ? flx_rays_irradiance_map_device(box->ctx, tw, &volume->grid, volume->d_sh, d_rays, (uint32_t)n, d_rows, &volume->map, volume->d_maps, nullptr)
+                                    : flx_rays_irradiance_device(box->ctx, tw, &volume->grid, volume->d_sh, d_rays, (uint32_t)n, d_rows, nullptr);
   if (rc == FLX_OK) rc = flx_sync(box->ctx);
-  if (rc != FLX_OK) return fail(env, box->ctx, volume->d_maps ? "flx_rays_irradiance_map_device" : "flx_rays_irradiance_device", rc);
+  if (rc != FLX_OK)
+    return fail(env, box->ctx, volume->d_offsets ? "flx_rays_irradiance_relocated_device" : volume->d_maps ? "flx_rays_irradiance_map_device" : "flx_rays_irradiance_device", rc);
   if (!hip_ok(env, hipMemcpy(rows, d_rows, n * 16, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
   return buf;
 }
@@ -1745,7 +1857,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "traceProbes", TraceProbes }, { "probeIrradiance", ProbeIrradiance }, { "bakeVolume", BakeVolume }, { "volumeRows", VolumeRows }, { "volumeMaps", VolumeMaps }, { "updateVolume", UpdateVolume }, { "frameIrradiance", FrameIrradiance }, { "raysIrradiance", RaysIrradiance }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "traceProbes", TraceProbes }, { "probeIrradiance", ProbeIrradiance }, { "bakeVolume", BakeVolume }, { "volumeRows", VolumeRows }, { "volumeMaps", VolumeMaps }, { "updateVolume", UpdateVolume }, { "relocateVolume", RelocateVolume }, { "volumeOffsets", VolumeOffsets }, { "frameIrradiance", FrameIrradiance }, { "raysIrradiance", RaysIrradiance }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas }, { "uploadTextures", UploadTextures }, { "updateTexture", UpdateTexture },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
