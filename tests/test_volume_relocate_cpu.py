@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 
 from volume_map_util import reference as map_reference
-from volume_relocate_util import (FACES, FLAVOURS, FREEZE, INACTIVE, REJECTED, assert_same_rows, assert_same_words, grid_of, map_of, planes_of, reference, relocate64,
-                                  relocate_of, room_iterate, rule_of, states_of, synthetic_case, synthetic_maps, synthetic_sh)
+from volume_relocate_util import (FACES, FLAVOURS, FREEZE, INACTIVE, LARGE, REJECTED, assert_same_rows, assert_same_words, grid_of, map_of, placed_distances, placed_probe,
+                                  placed_winners, planes_of, reference, relocate64, relocate_of, room_iterate, rule_of, states_of, synthetic_case, synthetic_maps, synthetic_sh)
 from volume_update_util import update_of
 from volume_util import COUNTS, POINT_SETS, point_set
 from volume_util import reference as volume_reference
@@ -28,7 +28,7 @@ ARGS_CASES = 155         # the cases tests/volume_relocate_args_main.cc runs
 # and the largest word of the offset: a handful of roundings of 2^-24 each of intermediates below 1, plus the texel direction's own float32 rounding (the
 # restatement's directions are float64).  The bound is the worst deviation measured on this test's own cases with a margin of 4x, as test_volume_map_cpu.py and
 # test_volume_update_cpu.py set theirs.
-OFFSET_BOUND = 4 * 1.79e-8           # observed 1.79e-08
+OFFSET_BOUND = 4 * 1.79e-8           # observed 1.79e-08 at w = 1 .. 16; 1.89e-08 at w = 20 .. 256 over the same flavours and the placed winners, inside the bound
 THRESHOLD = 1.0e-5                   # a case whose float64 restatement finds a comparison's two sides closer than this, relatively, may be left out
 
 
@@ -108,6 +108,74 @@ def test_the_slots_reduce_to_what_the_plain_loop_does(ref):
 def key(s, t, far=False):
     bits = int(np.array([s], np.float32).view(np.uint32)[0])
     return ((~bits & 0xffffffff if far else bits) << 32) | t
+
+
+def test_the_reference_at_large_faces_and_placed_winners(ref):
+    """What test_volume_relocate_seams_gpu.py leans on, made a checked fact: at face sizes 20 .. 256 the reference agrees with the float64 restatement — states
+    equal, kept bits exact, offsets within OFFSET_BOUND — (a) on synthetic_case's flavours, whose winners are all low texels, and (b) on placed_probe's cases, whose
+    three keys are won at the first trip's ends, in the last trip, at R - 1, on either side of 2^16, 2^17 and 2^18 and at 393 215, alone or as the lowest of a tie
+    with texels of other lanes and of the same lane's later trips.  For (b) the keys themselves are held against key(): the placed texel and the placed distance's
+    bits, from the plain loop and from the slots."""
+    grid = grid_of((3, 2, 4))
+    tally = {"worst": 0.0, "cases": 0, "left_out": 0, "rules": set(), "flags": set()}
+
+    def held(w, relocate, hit, normal, old, got, what):
+        """one probe of the reference against relocate64"""
+        want, state, margin = relocate64(grid, relocate, w, hit, normal, old)
+        tally["cases"] += 1
+        if margin < THRESHOLD:
+            tally["left_out"] += 1
+            return
+        got_state = int(states_of(got.reshape(1, 4))[0])
+        assert got_state == state, (what, got_state, state)
+        tally["rules"].add(int(rule_of(state)))
+        tally["flags"].add(state & (INACTIVE | REJECTED))
+        if np.isnan(old[:3]).any() or (state & REJECTED) or (int(relocate.flags) & FREEZE):
+            assert_same_words(got[None, :3], old[None, :3], "kept bits, %s" % what)
+        else:
+            scale = max(1.0, float(np.abs(want).max()))
+            tally["worst"] = max(tally["worst"], float(np.abs(got[:3].astype(np.float64) - want).max()) / scale)
+
+    relocate = relocate_of()
+    for w in (20, 48, 128, 256):                                             # (a)
+        n, rays = len(FLAVOURS), 6 * w * w
+        hit, normal, old, flavours = synthetic_case(n, w, 0, relocate)
+        offsets = np.zeros((grid.probes, 4), np.float32)
+        offsets[:n] = old
+        got = ref.relocate(grid, relocate, w, hit, normal, offsets)
+        for i in range(n):
+            held(w, relocate, hit[i * rays:(i + 1) * rays], normal[i * rays:(i + 1) * rays], old[i], got[i], "w %d, %s" % (w, flavours[i]))
+        assert_same_words(got[n:], offsets[n:], "probes beyond the run")
+    placed_cases, moved = 0, 0
+    for w, _ in LARGE:                                                       # (b)
+        rays, highest = 6 * w * w, 0
+        rng = np.random.default_rng(w)
+        for i, winners in enumerate(placed_winners(w)):
+            what = "w %d, rule %d, %s at %d" % (w, winners["rule"], winners["key"], winners["texel"])
+            r = relocate_of(flags=FREEZE if i % 5 == 4 else 0)
+            s, side, is_hit, old = placed_probe(w, rng, r, winners)
+            hit, normal = planes_of(s, side, is_hit)
+            placed = placed_distances(r, winners["rule"])
+            keys = (key(placed["cb"], winners["cb"]), key(placed["cf"], winners["cf"]), key(placed["ff"], winners["ff"], far=True))
+            for slots in (False, True):
+                sums = ref.sums(w, hit, normal, slots=slots)
+                assert sums[2:] == keys and sums[0] == int(is_hit.sum()) and sums[1] == int((is_hit & (side > 0)).sum()), (what, slots)
+            first = i % grid.probes
+            offsets = np.zeros((grid.probes, 4), np.float32)
+            offsets[first] = old
+            got = ref.relocate(grid, r, w, hit, normal, offsets, first_probe=first)
+            held(w, r, hit, normal, old, got[first], what)
+            assert rule_of(states_of(got[first:first + 1]))[0] == winners["rule"], what
+            moved += int((got[first, :3] != old[:3]).any())
+            highest = max([highest] + [k & 0xffffffff for k in sums[2:]])
+            placed_cases += 1
+        # what the GPU tests assert of their own planes holds for the reference alone
+        assert highest >= rays - 64 and (w < 128 or highest >= 65536) and (w < 256 or highest >= 262144), (w, highest)
+    print("relocate against float64 at large faces: worst deviation %.3g over %d cases (%d placed, %d of them moved), %d left out"
+          % (tally["worst"], tally["cases"], placed_cases, moved, tally["left_out"]))
+    assert placed_cases >= 150 and moved >= placed_cases // 2 and tally["left_out"] <= tally["cases"] // 100, (placed_cases, moved, tally)
+    assert tally["rules"] == {1, 2, 3} and tally["flags"] == {0, INACTIVE, REJECTED, INACTIVE | REJECTED}
+    assert tally["worst"] <= OFFSET_BOUND, tally["worst"]
 
 
 def test_ties_empties_and_poison(ref):
