@@ -30,7 +30,13 @@ namespace flx {
 #define FLX_WF_DRAWS_PER_WAVE 16
 #endif
 #ifndef FLX_FRAME_SHADERS_FRONT
-#define FLX_FRAME_SHADERS_FRONT 3           /* shade waves of a frame-kernel workgroup when they also make the fresh paths (WavefrontBuffers::front) */
+#define FLX_FRAME_SHADERS_FRONT 4           /* shade waves of a frame-kernel workgroup when they also make the fresh paths (WavefrontBuffers::front), and of the frame server's.  Three until the walk
+                                             * waves' trip and fold got shorter: then the walk waves ran their trips half empty, waiting for paths (32 of 64 lanes a trip on the dragon; 40 with four).
+                                             * dragon 1080p 3 -> 5.33, 4 -> 5.17, and with FLX_WF_FOLD_EARLY 3 -> 5.35, 4 -> 5.07, 5 -> 5.31 ms (profiles/fold_early_loads.txt) */
+#endif
+#ifndef FLX_WF_MAX_TRANSFORMS
+#define FLX_WF_MAX_TRANSFORMS 4             /* object spaces of a scene the frame kernel and the frame server take.  With five, the rays of thirteen walk waves left no LDS for the tree's top; those of
+                                             * twelve leave 120 entries, a frame nobody has measured: such scenes stay with the rounds, as before */
 #endif
 #ifndef FLX_FRAME_PROLOGUE_WAVES
 #define FLX_FRAME_PROLOGUE_WAVES 2          /* walk waves that make a first tile before their loop (FRONT) */
@@ -260,6 +266,72 @@ FLX_DEV const float4 *pix_part(const DeviceFrame &fr, const WavefrontBuffers &wb
  * caller hands it to the shade waves); one that ends has its radiance stored (ended_: the caller takes it off its count).  The lane is free afterwards.
  * A macro for the reason FLX_WALK_LANE_STEP is one: as an inlined function taking the lane by reference the same statements schedule differently in the frame kernel's
  * fold (loads hoisted over a mask change, eight more instructions) and the dragon frame measures 0.65 % slower (6.39 -> 6.44 ms, same lease, three runs each). */
+/* FLX_WF_FOLD_EARLY: the fold without the memory round trips its result does not need (profiles/fold_early_loads.txt).
+ *   - A compact bounce-0 path that goes on gets the first words of its full record from the lane, not from rec0 / pix0 a second time: they are what walkLaneFetchRecord
+ *     loaded when the path came in, and walkLaneInstall put every one into a field that is live until the fold anyway (a later P_SWITCH's set-up reads them).
+ *     L.flags carries the arrival stamp above bit 8 in the stamped kernels: the record gets the flags alone.
+ *   - The loads the fold starts with have ONE site for either form of record (the addresses are chosen, not the loads), and the constants that stand for a compact
+ *     record's q5 and q6 are put in after them.  In the fold of before each form had its loads in its own branch, and the compact branch first wrote those constants
+ *     into registers the other lanes' loads were in flight to: a wave that held both forms — most do — waited for one round trip before it issued the next.
+ * The fold is in two halves, FLX_WALK_LANE_FOLD_FETCH and FLX_WALK_LANE_FOLD_WITH.  Issuing the first BEFORE the block's pops was built and measured, and is not done: the
+ * block gets no shorter (a pop waits for its ring slot, a vector load that returns after these) and the frame no faster.
+ * 0: the fold of before, to the instruction. */
+#ifndef FLX_WF_FOLD_EARLY
+#define FLX_WF_FOLD_EARLY 1
+#endif
+#if FLX_WF_FOLD_EARLY
+struct WalkFold { float4 q4, q5, q6, q7; bool compact; };      /* what the fold loads first; compact: from a compact bounce-0 record */
+#define FLX_WALK_LANE_FOLD_FETCH(fr_, wb_, compactRecs_, L_, F_)                                                                 \
+  do {                                                                                                                           \
+    const float4 *a4_ = (wb_).rec + (size_t)(L_).pathId * 8 + 4, *a7_ = a4_ + 3;                                                 \
+    (F_).compact = (compactRecs_) && (L_).pathBounce == 0;                                                                       \
+    if ((F_).compact) { a4_ = (wb_).rec0 + (size_t)(L_).pathId * 3 + 2; a7_ = pix_part(fr_, wb_, (L_).pathId) + 2; }             \
+    /* one load site for either form of record, and no constant written here: a write to a register that another lane's load is in flight to would wait for that load */ \
+    (F_).q4 = *a4_; (F_).q7 = *a7_;                                                                                              \
+    if (!(F_).compact) { (F_).q5 = a4_[1]; (F_).q6 = a4_[2]; }      /* (a compact path's are constants: the fold puts them in) */ \
+  } while (0)
+#define FLX_WALK_LANE_FOLD_WITH(LV_, fr_, wb_, compactRecs_, L_, F_, lv_, toShade_, ended_, costed_, stamp_)                     \
+  do {                                                                                                                           \
+    float4 *rec_ = (wb_).rec + (size_t)(L_).pathId * 8;                                                                          \
+    const bool compact_ = (F_).compact;                                                                                          \
+    const float4 q4_ = (F_).q4, q7_ = (F_).q7;                                                                                   \
+    float4 q5_ = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q6_ = make_float4(1.0f, 1.0f, 1.0f, 0.0f);                                 \
+    if (!compact_) { q5_ = (F_).q5; q6_ = (F_).q6; }                                                                             \
+    const bool shadowed_ = ((L_).flags & RF_SHADOWED_NO_WALK) || (((L_).flags & RF_NEED_SHADOW) && (L_).w.shadowed);            \
+    const f3 localColor_ = shadowed_ ? F3((L_).base, (L_).base, (L_).base) : F3(q4_.x, q4_.y, q4_.z);                            \
+    const f3 importancy_ = F3(q6_.x, q6_.y, q6_.z), originalColor_ = F3(q7_.x, q7_.y, q7_.z);                                    \
+    const f3 finalColor_ = F3(q5_.x, q5_.y, q5_.z) + localColor_ * importancy_;                                                  \
+    /* what the path has cost so far (time in the walk lanes, 10 ns ticks; q5.w, then the w of its radiance slot: the adaptive tile order's measure) */ \
+    const float cost_ = (costed_) ? q5_.w + (float)(((stamp_) - ((uint32_t)(L_).flags >> 8)) & 0xffffffu) : 1.0f;     /* (costed_: a compile-time constant) */ \
+    bool cont_ = (L_).w.tri != -1;                                                                                               \
+    if (cont_) cont_ = ((L_).pathBounce + 1) < (fr_).max_reflections && length(importancy_ * originalColor_) >= (fr_).min_importancy * SQRT3;      \
+    if (cont_) {                                                                                                                 \
+      if (compact_) {                                   /* the path goes on: now it gets its full record (what shade0 would have written) */      \
+        /* ... from the lane: the words its install loaded */                                                                    \
+        rec_[0] = make_float4((L_).nextRay.origin.x, (L_).nextRay.origin.y, (L_).nextRay.origin.z, __int_as_float((L_).flags & 0xff));             \
+        rec_[1] = make_float4((L_).nextRay.dir.x, (L_).nextRay.dir.y, (L_).nextRay.dir.z, (L_).shadowLen);                                         \
+        rec_[3] = make_float4((L_).shadowRay.dir.x, (L_).shadowRay.dir.y, (L_).shadowRay.dir.z, __int_as_float(0));                                \
+        rec_[6] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);                                                                           \
+        rec_[7] = make_float4(q7_.x, q7_.y, q7_.z, 0.0f);                                                                        \
+      }                                                                                                                          \
+      rec_[5] = make_float4(finalColor_.x, finalColor_.y, finalColor_.z, (costed_) ? cost_ : 0.0f);                                                 \
+      rec_[2] = make_float4((L_).w.suv.x, (L_).w.suv.y, (L_).w.suv.z, __int_as_float((L_).w.tri));                               \
+      toShade_ = true;                                                                                                           \
+    } else {                                                                                                                     \
+      finalize_path<LV_>(fr_, wb_, (L_).pathId, finalColor_, importancy_, originalColor_, lv_, cost_);                           \
+      ended_ = true;                                                                                                             \
+    }                                                                                                                            \
+    (L_).st = P_EMPTY;                                                                                                           \
+  } while (0)
+/* both halves in one place */
+#define FLX_WALK_LANE_FOLD(LV_, fr_, wb_, compactRecs_, L_, lv_, toShade_, ended_, costed_, stamp_)                              \
+  do {                                                                                                                           \
+    WalkFold fold_;                                                                                                              \
+    FLX_WALK_LANE_FOLD_FETCH(fr_, wb_, compactRecs_, L_, fold_);                                                                 \
+    FLX_WALK_LANE_FOLD_WITH(LV_, fr_, wb_, compactRecs_, L_, fold_, lv_, toShade_, ended_, costed_, stamp_);                     \
+  } while (0)
+#else
+/* the fold in one piece, as it was */
 #define FLX_WALK_LANE_FOLD(LV_, fr_, wb_, compactRecs_, L_, lv_, toShade_, ended_, costed_, stamp_)                              \
   do {                                                                                                                           \
     float4 *rec_ = (wb_).rec + (size_t)(L_).pathId * 8;                                                                          \
@@ -277,12 +349,11 @@ FLX_DEV const float4 *pix_part(const DeviceFrame &fr, const WavefrontBuffers &wb
     const f3 localColor_ = shadowed_ ? F3((L_).base, (L_).base, (L_).base) : F3(q4_.x, q4_.y, q4_.z);                            \
     const f3 importancy_ = F3(q6_.x, q6_.y, q6_.z), originalColor_ = F3(q7_.x, q7_.y, q7_.z);                                    \
     const f3 finalColor_ = F3(q5_.x, q5_.y, q5_.z) + localColor_ * importancy_;                                                  \
-    /* what the path has cost so far (time in the walk lanes, 10 ns ticks; q5.w, then the w of its radiance slot: the adaptive tile order's measure) */ \
-    const float cost_ = (costed_) ? q5_.w + (float)(((stamp_) - ((uint32_t)(L_).flags >> 8)) & 0xffffffu) : 1.0f;     /* (costed_: a compile-time constant) */ \
+    const float cost_ = (costed_) ? q5_.w + (float)(((stamp_) - ((uint32_t)(L_).flags >> 8)) & 0xffffffu) : 1.0f;               \
     bool cont_ = (L_).w.tri != -1;                                                                                               \
     if (cont_) cont_ = ((L_).pathBounce + 1) < (fr_).max_reflections && length(importancy_ * originalColor_) >= (fr_).min_importancy * SQRT3;      \
     if (cont_) {                                                                                                                 \
-      if (compact_) {                                   /* the path goes on: now it gets its full record (what shade0 would have written) */      \
+      if (compact_) {                                                                                                            \
         const float4 a_ = (wb_).rec0[(size_t)(L_).pathId * 3], bq_ = (wb_).rec0[(size_t)(L_).pathId * 3 + 1], p0_ = pp_[0];      \
         rec_[0] = make_float4(p0_.x, p0_.y, p0_.z, a_.w);                                                                        \
         rec_[1] = make_float4(a_.x, a_.y, a_.z, bq_.w);                                                                          \
@@ -290,7 +361,7 @@ FLX_DEV const float4 *pix_part(const DeviceFrame &fr, const WavefrontBuffers &wb
         rec_[6] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);                                                                           \
         rec_[7] = make_float4(q7_.x, q7_.y, q7_.z, 0.0f);                                                                        \
       }                                                                                                                          \
-      rec_[5] = make_float4(finalColor_.x, finalColor_.y, finalColor_.z, (costed_) ? cost_ : 0.0f);                                                 \
+      rec_[5] = make_float4(finalColor_.x, finalColor_.y, finalColor_.z, (costed_) ? cost_ : 0.0f);                              \
       rec_[2] = make_float4((L_).w.suv.x, (L_).w.suv.y, (L_).w.suv.z, __int_as_float((L_).w.tri));                               \
       toShade_ = true;                                                                                                           \
     } else {                                                                                                                     \
@@ -299,6 +370,7 @@ FLX_DEV const float4 *pix_part(const DeviceFrame &fr, const WavefrontBuffers &wb
     }                                                                                                                            \
     (L_).st = P_EMPTY;                                                                                                           \
   } while (0)
+#endif
 
 /* Take path `id` into a free lane: its record (the compact bounce-0 form where `compactFresh`).  true: the item is dead (a pixel without a path), the lane stays free.
  * In two halves — the loads, and what they mean for the lane — so that a kernel can have the loads in flight while it does something else (k_wf_frame folds the lane's old path). */

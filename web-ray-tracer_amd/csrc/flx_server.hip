@@ -420,7 +420,7 @@ __global__ __launch_bounds__(FLX_WF_WALK_THREADS, FLX_WF_WAVES_PER_EU) void k_wf
       newRec.q0 = newRec.q1 = newRec.q2 = newRec.q3 = make_float4(0.f, 0.f, 0.f, 0.f);
       const uint32_t P = fq_load(&ctl[SC_SLOTP]);
       {
-        const bool want = L.st == P_EMPTY || L.st == P_DONE;      /* (a lane at P_DONE is free once it is folded, whatever becomes of its path) */
+        const bool want = L.st == P_EMPTY || L.st == P_DONE;     /* (a lane at P_DONE is free once it is folded, whatever becomes of its path) */
         for (;;) {
           const unsigned long long idle = flx_ballot(want && newId == WF_INVALID);
           if (idle == 0ull) break;
@@ -520,7 +520,7 @@ bool server_kernel_fits(const DeviceScene &sc, uint32_t &ldsCount, uint32_t &lds
   if (shadeWaves == 0u) shadeWaves = (uint32_t)FLX_SERVER_SHADERS;
   const uint32_t walkThreads = FLX_WF_WALK_THREADS - 64u * shadeWaves;
   const uint32_t fixed = walkThreads * T * 40u + xfSlots * T * 64u + (SC_WORDS + SC_VIEW_WORDS) * 4u;
-  if (fixed + 4096u > (uint32_t)FLX_WF_LDS_TOTAL) return false;
+  if (fixed + 4096u > (uint32_t)FLX_WF_LDS_TOTAL || T > (uint32_t)FLX_WF_MAX_TRANSFORMS) return false;
   ldsCount = ((uint32_t)FLX_WF_LDS_TOTAL - fixed) / 48u;
   if (ldsCount > sc.walk_hot) ldsCount = sc.walk_hot;
   ldsBytes = ldsCount * 48u + fixed;

@@ -789,7 +789,7 @@ __global__ __launch_bounds__(FLX_WF_WALK_THREADS, FLX_WF_WAVES_PER_EU) void k_wf
 #define FLX_FRAME_SHADERS 2                 /* shade waves of a frame-kernel workgroup (dragon 1080p: 1 -> 7.27, 2 -> 6.87, 3 -> 7.16 ms per frame) */
 #endif
 #ifndef FLX_FRAME_SHADERS_FRONT
-#define FLX_FRAME_SHADERS_FRONT 3           /* ... when they also make the fresh paths (WavefrontBuffers::front) */
+#define FLX_FRAME_SHADERS_FRONT 4           /* ... when they also make the fresh paths (WavefrontBuffers::front): flx_frame_common.h */
 #endif
 #ifndef FLX_FRAME_PROLOGUE_WAVES
 #define FLX_FRAME_PROLOGUE_WAVES 2          /* walk waves that make a first tile before their loop (FRONT) */
@@ -1216,6 +1216,7 @@ static bool frame_kernel_fits(const DeviceScene &sc, bool withFront, uint32_t &l
   const uint32_t walkThreads = FLX_WF_WALK_THREADS - 64u * (withFront ? (uint32_t)FLX_FRAME_SHADERS_FRONT : (uint32_t)FLX_FRAME_SHADERS);      /* (the shade waves keep no rays) */
   const uint32_t fixed = walkThreads * T * 40u + T * 64u + FC_WORDS * 4u;
   if (!FLX_WF_PRETRANSFORM || fixed + 4096u > (uint32_t)FLX_WF_LDS_TOTAL) return false;
+  if (T > (uint32_t)FLX_WF_MAX_TRANSFORMS) return false;
   ldsCount = ((uint32_t)FLX_WF_LDS_TOTAL - fixed) / 48u;
   if (ldsCount > sc.walk_hot) ldsCount = sc.walk_hot;
   ldsBytes = ldsCount * 48u + fixed;
