@@ -163,7 +163,7 @@ static void fill_scene(flx_context *ctx, DeviceScene &sc) {
   sc.walk_thick_boxes = ctx->box_test < 0 ? ctx->walk_thick_boxes : (uint32_t)ctx->box_test;      /* (either form gives every scene's booleans: flx_device.h, rayCuboidInterval) */
   sc.fwd = ctx->d_fwd; sc.fwd_entries = ctx->fwd_entries; sc.fwd_root = ctx->fwd_root;
   sc.lock = ctx->d_fwd; sc.lock_entries = (ctx->lock_ok && ctx->lock_use) ? ctx->fwd_entries : 0u; sc.lock_root = ctx->fwd_root;
-  sc.angle_tan = nullptr;                  /* (the per-pixel kernel's table: flx_run_frame makes it where that kernel is launched) */
+  sc.angle_tan = nullptr;                  /* (the shading's per-triangle table: made, by angle_table(), in front of the launches whose kernels read it) */
 }
 /* ... for a caller that renders no frame (the ray queries); flx_make_frame's refusals that concern the scene */
 flx_status flx_make_scene(flx_context *ctx, DeviceScene &sc) {
@@ -328,6 +328,19 @@ static flx_status angle_table(flx_context *ctx, DeviceScene &scT) {
 }
 flx_status flx_angle_table(flx_context *ctx, DeviceScene &sc) { return angle_table(ctx, sc); }      /* (flx_rays_trace.hip, which defines FLX_ANGLE_TABLE 1: k_rays_paths' shading loads the table, as k_paths' does) */
 
+/* wb.cosSample: the context's table of the samples' cosines, made first (on its stream) where it is not there yet */
+static flx_status cos_table(flx_context *ctx, WavefrontBuffers &wb) {
+  if (!ctx->cos_sample_made || !ctx->d_cos_sample) {
+    flx_status es = ctx->d_cos_sample.ensure(ctx, WF_COS_SAMPLES);
+    if (es) return es;
+    launch_cos_sample(ctx->d_cos_sample, WF_COS_SAMPLES, ctx->stream);
+    FLX_HIP(ctx, hipGetLastError());
+    ctx->cos_sample_made = true;
+  }
+  wb.cosSample = ctx->d_cos_sample; wb.cosSampleCount = WF_COS_SAMPLES;
+  return FLX_OK;
+}
+
 flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFrame &fr, float4 *d_out, const GBufferPtrs &gb) {
   { flx_status ss = flx_server_stop(ctx); if (ss) return ss; }      /* (the frame server renders into the same workspace) */
   unsigned long long *cnt = ctx->counters_enabled ? ctx->d_counters : nullptr;
@@ -437,6 +450,13 @@ flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFr
       FLX_HIP(ctx, hipMemsetAsync(ctx->d_tile_time, 0, (size_t)tiles * sizeof(float), ctx->stream));
     }
     const size_t listSlice = std::min(ctx->d_live[0].capacity(), ctx->d_live[1].capacity()) / (size_t)groups;
+    /* what the frame kernel's shading reads where a shade computed it: the samples' cosines, and — whole frames, the front inside and unstamped — the per-triangle
+     * table (FLX_FRAME_ANGLE_TABLE, flx_kernels.h), made again first where the geometry, the attributes or the transforms changed.  Both on this context's stream: in front
+     * of the launch, and of the fork below */
+    WavefrontBuffers wbTables;
+    { flx_status es = cos_table(ctx, wbTables); if (es) return es; }
+    DeviceScene scW = sc;
+    if (FLX_FRAME_ANGLE_TABLE && front && (!(adaptive && front) || FLX_THIN_ANGLE_TABLE)) { flx_status es = angle_table(ctx, scW); if (es) return es; }
     if (groups > 1) {
       FLX_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
       for (int g = 1; g < groups; g++) FLX_HIP(ctx, hipStreamWaitEvent(ctx->aux_stream[g - 1], ctx->ev_fork, 0));
@@ -458,13 +478,14 @@ flx_status flx_run_frame(flx_context *ctx, const DeviceScene &sc, const DeviceFr
       wb.counts = ctx->d_wfcounts + (size_t)g * 2 * (WF_MAX_BOUNCES + 2); wb.walkQueue = wb.counts + (WF_MAX_BOUNCES + 2);
       wb.item_base = t0 * perTile; wb.item_count = (t1 - t0) * perTile;
       wb.hits = ctx->d_hits; wb.sampleRadiance = ctx->d_samples; wb.lastOriginal = ctx->d_last; wb.counters = cnt;
+      wb.cosSample = wbTables.cosSample; wb.cosSampleCount = wbTables.cosSampleCount;
       hipStream_t st = g == 0 ? ctx->stream : ctx->aux_stream[g - 1];
       /* Two lanes gathering over a communicator (flx_frame_begin_gathered): the persistent walk workgroups of one lane's frame hold every
        * CU until they end, and the other lane's RCCL kernel — a handful of workgroups that carry the finished frame's strips — would wait
        * behind them for a whole frame.  Such a context leaves a few CUs to the exchange. */
       const uint32_t cusWalk = (ctx->comm && (ctx->twin || ctx->is_twin) && cus > 4u * FLX_COMM_RESERVED_CUS) ? cus - FLX_COMM_RESERVED_CUS : cus;
       WalkLdsLaunch lds;
-      const int ran = launch_wavefront(sc, fr, wb, cusWalk, cnt != nullptr, organisationNow, g == 0 ? ctx->ev_k0 : nullptr, g == 0 ? ctx->ev_k1 : nullptr, st, &lds);
+      const int ran = launch_wavefront(scW, fr, wb, cusWalk, cnt != nullptr, organisationNow, g == 0 ? ctx->ev_k0 : nullptr, g == 0 ? ctx->ev_k1 : nullptr, st, &lds);
       FLX_HIP(ctx, hipGetLastError());
       if (ran == -2) return fail(ctx, FLX_ERR_DEVICE, "the walk kernels need 156 KB of dynamic LDS and hipFuncSetAttribute refused it on this device");
       if (ran < 0) return fail(ctx, FLX_ERR_DEVICE, "internal: the frame kernel was to trace the primary rays but does not take this frame");
@@ -1215,6 +1236,11 @@ static flx_status server_post(flx_context *ctx, const flx_frame_params *params, 
     if ((s = server_allocate(ctx, frOne, depth))) return s;
     const size_t P1 = (size_t)frOne.rows * frOne.width;
     ctx->sv_out_pixels = P1;
+    WavefrontBuffers wb = {};
+    if ((s = cos_table(ctx, wb))) return s;                    /* (on the context's stream: in front of the wait below) */
+    DeviceScene scL = sc;
+    const bool ver = ctx->sv_want_ver && server_versions_fit(ctx);
+    if (FLX_SERVER_ANGLE_TABLE && !ver && (s = angle_table(ctx, scL))) return s;      /* a static scene: the server's shading reads the per-triangle table (any upload ends the launch) */
     FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));         /* whatever used the workspace before, and the allocations above */
     ctx->sv_counter += 16u;                                  /* sequence numbers: consecutive within a launch, never reused across launches, never 0 */
     if (ctx->sv_counter < 16u) ctx->sv_counter = 16u;
@@ -1223,7 +1249,6 @@ static flx_status server_post(flx_context *ctx, const flx_frame_params *params, 
     FLX_HIP(ctx, hipMemsetAsync(ctx->d_sv_slots, 0, SV_MAX_DEPTH * sizeof(ServerSlot), ctx->sv_stream));
     FLX_HIP(ctx, hipMemsetAsync(ctx->d_sv_relay, 0, sizeof(ServerMail), ctx->sv_stream));
     FLX_HIP(ctx, hipMemsetAsync(ctx->d_sv_stats, 0, SV_STAT_TOTAL * sizeof(unsigned long long), ctx->sv_stream));
-    WavefrontBuffers wb = {};
     wb.rec = ctx->d_rec; wb.rec0 = ctx->d_rec0; wb.pix0 = ctx->d_pix0;
     wb.frameRings = ctx->d_sv_rings; wb.front = 1u;
     wb.error = ctx->d_dev_error; wb.watchdog = 0u; wb.inject = 0u;
@@ -1254,8 +1279,6 @@ static flx_status server_post(flx_context *ctx, const flx_frame_params *params, 
     uint32_t cusWalk = cus > 4u * FLX_SERVER_RESERVED_CUS ? cus - FLX_SERVER_RESERVED_CUS : cus;
     if (ctx->sv_groups && ctx->sv_groups < cusWalk) cusWalk = ctx->sv_groups;
     /* a scene that moves: the launch reads the lights and transforms of every frame from versions of its own, filled from what is posted with the frame */
-    const bool ver = ctx->sv_want_ver && server_versions_fit(ctx);
-    DeviceScene scL = sc;
     if (ver) {
       const size_t versions = (size_t)cusWalk * depth;
       sa.blobWords = server_blob_words(ctx->n_transforms, ctx->n_lights);

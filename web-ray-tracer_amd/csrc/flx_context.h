@@ -155,6 +155,9 @@ struct flx_context {
   uint32_t geometry_version = 0;                 /* counts uploads of the geometry / attribute arrays (the second lane copies the primary's: mirror_scene) */
   uint32_t transforms_version = 0;               /* counts uploads of this context's transforms */
   int angle_table = 1;                           /* flx_debug: 0 = the shading computes the values itself */
+  /* WavefrontBuffers::cosSample: cos((float)s) of the first WF_COS_SAMPLES sample numbers, made once on this context's stream in front of the first launch that reads it */
+  DeviceBuffer<float> d_cos_sample;
+  bool cos_sample_made = false;
   /* frame workspace */
   DeviceBuffer<float4> d_out;
   DeviceBuffer<float4> d_gb[6];

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "flx_math.h"
+#include "flx_reservoir_first.h"
 
 #define FLX_DEV __device__ __forceinline__
 
@@ -406,6 +407,14 @@ struct ShadeOut {
 };
 
 /* fragment:400-453: everything of reservoirSample before the shadow ray is walked. */
+/* FLX_SHADE_FIRST_LIGHT (FIRST): in a scene of ONE light the draw in front of the loop is not made.  Its .y decides one comparison, and that comparison is an f32 range
+ * check of the sine's argument and of the weight (include/flx_reservoir_first.h: the derivation; a weight of +inf takes the sine as before); a light of strength <= 0
+ * reads nothing of it.  With more lights the draw feeds the next one and nothing changes.  The persistent kernels' shading takes it (shade0_tile, shade_path); the
+ * per-pixel kernels instantiate FIRST = false, the code of before to the instruction.  0: that code everywhere. */
+#ifndef FLX_SHADE_FIRST_LIGHT
+#define FLX_SHADE_FIRST_LIGHT 1
+#endif
+template <bool FIRST = false>
 FLX_DEV void reservoirPick(const DeviceScene &sc, const DeviceFrame &fr, PixelState &ps, const Material &material, const Ray &ray,
                            f4 randomVec, f3 N, f3 smoothNormal, float geometryOffset, bool dontFilter, int i, ShadeOut &so) {
   f3 localColor = F3(0.0f, 0.0f, 0.0f);
@@ -414,9 +423,13 @@ FLX_DEV void reservoirPick(const DeviceScene &sc, const DeviceFrame &fr, PixelSt
   int reservoirNum = 0;
   float reservoirWeight = 0.0f;
   f3 reservoirLightDir = F3(0.0f, 0.0f, 0.0f);
-  f4 n0 = noise(ps.seed, randomVec.z, randomVec.w, BIAS);
-  float lastRandomX = n0.x, lastRandomY = n0.y;
   const int size = (int)sc.n_lights;
+  const bool oneLight = FIRST && size <= 1;            /* (uniform: a scalar test.  No light at all: the loop does not run and nobody reads the draw) */
+  float lastRandomX = 0.0f, lastRandomY = 0.0f;
+  if (!oneLight) {
+    f4 n0 = noise(ps.seed, randomVec.z, randomVec.w, BIAS);
+    lastRandomX = n0.x; lastRandomY = n0.y;
+  }
   for (int j = 0; j < size; j++) {
     const float *lt = sc.lights + 6 * j + ps.lightBase;
     float strength = lt[3], variation = lt[4];
@@ -428,7 +441,9 @@ FLX_DEV void reservoirPick(const DeviceScene &sc, const DeviceFrame &fr, PixelSt
     localColor = localColor + colorForLight;
     float weight = length(colorForLight);
     totalWeight += weight;
-    if (flx_abs(lastRandomY) * totalWeight <= weight) {
+    const bool taken = oneLight ? flx_first_light_taken(flx_noise_y_arg(ps.seed, randomVec.z, randomVec.w, BIAS), weight) != 0
+                                : flx_abs(lastRandomY) * totalWeight <= weight;
+    if (taken) {
       reservoirNum = j;
       reservoirWeight = weight;
       reservoirLightDir = dir;
@@ -467,9 +482,13 @@ struct SurfaceCtx {
   Material material;
 };
 
-/* Who reads the per-triangle table (DeviceScene::angle_tan) is decided per source file: the per-pixel kernel gains 4.5 % from it; the persistent kernels — whose paths' chains
- * walk -> shade -> walk set the pace of a thin share — lose to the extra dependent load (a rank's eighth through the frame server with two frames in flight 1.235 -> 1.351 ms,
- * k_paths + 1 %: profiles/r04_angle_table.txt) and keep computing the terms.  (As FLX_SINCOS_TABLE: one definition per translation unit.) */
+/* Who reads the per-triangle table (DeviceScene::angle_tan) is decided per kernel instantiation: TABLE of shadeSurface, handed down through bounceShade, shade0_tile and
+ * shade_path.  Its default is the translation unit's FLX_ANGLE_TABLE (the per-pixel kernels' files define it 1: k_trace_pixels gains 4.5 %, k_paths 5 % at four waves per
+ * SIMD).  Of the persistent kernels the frame kernel with the front of the frame inside, unstamped — whole frames, where the shade waves are the producer the walk waves
+ * wait for — reads it (FLX_FRAME_ANGLE_TABLE, flx_kernels.h; profiles/shade_needless.txt), and so does the frame server with a static scene (FLX_SERVER_ANGLE_TABLE): in
+ * round 4, when its paths' chains walk -> shade -> walk set the pace, it lost to the extra dependent load (a rank's eighth with two frames in flight 1.235 -> 1.351 ms:
+ * profiles/r04_angle_table.txt); with today's shorter trips the same share gains 8 %.  The stamped frame kernels (thin frames) were not measured and compute the terms; so
+ * does the server with a scene that moves, whose frames each have transforms of their own that one table cannot follow. */
 #ifndef FLX_ANGLE_TABLE
 #define FLX_ANGLE_TABLE 0
 #endif
@@ -491,7 +510,7 @@ FLX_DEV f3 triangleAngleTanOf(const DeviceScene &sc, int tri) {
                           mul(rTI, F3(a0.x, a0.y, a0.z)), mul(rTI, F3(a0.w, a1.x, a1.y)), mul(rTI, F3(a1.z, a1.w, a2.x)));
 }
 
-template <bool COUNT>
+template <bool COUNT, bool TABLE = (FLX_ANGLE_TABLE != 0)>
 FLX_DEV void shadeSurface(const DeviceScene &sc, const DeviceFrame &fr, const Hit &hit, const Ray &ray, f3 lastHitPoint, SurfaceCtx &sf,
                           WorkCounters &cnt) {
   if (COUNT) cnt.shades++;
@@ -514,7 +533,7 @@ FLX_DEV void shadeSurface(const DeviceScene &sc, const DeviceFrame &fr, const Hi
                                  (n0.y * uvw.x + n1.y * uvw.y) + n2.y * uvw.z,
                                  (n0.z * uvw.x + n1.z * uvw.y) + n2.z * uvw.z));
   f3 angleTan;
-  if (FLX_ANGLE_TABLE && sc.angle_tan) { const float4 t = sc.angle_tan[hit.triangleId]; angleTan = F3(t.x, t.y, t.z); }      /* the same floats, computed at the upload (k_angle_tan) */
+  if (TABLE && sc.angle_tan) { const float4 t = sc.angle_tan[hit.triangleId]; angleTan = F3(t.x, t.y, t.z); }      /* the same floats, computed at the upload (k_angle_tan) */
   else angleTan = triangleAngleTan(t0v, t1v, t2v, n0, n1, n2);
   sf.geometryOffset = dot(diffs * angleTan, uvw);
   /* uv0 = a2.yz, uv1 = (a2.w, a3.x), uv2 = a3.yz */
@@ -534,6 +553,7 @@ FLX_DEV void shadeSurface(const DeviceScene &sc, const DeviceFrame &fr, const Hi
 
 /* The rest of the bounce (fragment:535-589): the random vector of this (pixel, sample, bounce), Fresnel choice, filter
  * bookkeeping, light pick, next direction. */
+template <bool FIRST = false>
 FLX_DEV void shadeSample(const DeviceScene &sc, const DeviceFrame &fr, const SurfaceCtx &sf, PixelState &ps, PathState &p, f3 camera, float cosSampleN,
                          int i, ShadeOut &so) {
   const float fi = (float)i;
@@ -573,7 +593,7 @@ FLX_DEV void shadeSample(const DeviceScene &sc, const DeviceFrame &fr, const Sur
   }
 
   if (i == 1) ps.firstRayLength = flx_min(length(p.ray.origin - p.lastHitPoint) / length(p.lastHitPoint - camera), ps.firstRayLength);
-  reservoirPick(sc, fr, ps, material, p.ray, randomVec, roughNormal * (-sf.signDir), smoothNormal * (-sf.signDir), sf.geometryOffset, p.dontFilter, i, so);
+  reservoirPick<FIRST>(sc, fr, ps, material, p.ray, randomVec, roughNormal * (-sf.signDir), smoothNormal * (-sf.signDir), sf.geometryOffset, p.dontFilter, i, so);
   if (isSolid) {
     p.ray.dir = normalize(mix(reflect(p.ray.dir, smoothNormal), randomSpheareVec, sf.roughnessBRDF));
   } else {
@@ -582,12 +602,12 @@ FLX_DEV void shadeSample(const DeviceScene &sc, const DeviceFrame &fr, const Sur
   }
 }
 
-template <bool COUNT>
+template <bool COUNT, bool TABLE = (FLX_ANGLE_TABLE != 0), bool FIRST = false>
 FLX_DEV void bounceShade(const DeviceScene &sc, const DeviceFrame &fr, PixelState &ps, PathState &p, f3 camera, float cosSampleN, int i,
                          ShadeOut &so, WorkCounters &cnt) {
   SurfaceCtx sf;
-  shadeSurface<COUNT>(sc, fr, p.hit, p.ray, p.lastHitPoint, sf, cnt);
-  shadeSample(sc, fr, sf, ps, p, camera, cosSampleN, i, so);
+  shadeSurface<COUNT, TABLE>(sc, fr, p.hit, p.ray, p.lastHitPoint, sf, cnt);
+  shadeSample<FIRST>(sc, fr, sf, ps, p, camera, cosSampleN, i, so);
 }
 
 #ifndef FLX_BOX_FALLBACK_COUNT

@@ -30,9 +30,11 @@ namespace flx {
 #define FLX_WF_DRAWS_PER_WAVE 16
 #endif
 #ifndef FLX_FRAME_SHADERS_FRONT
-#define FLX_FRAME_SHADERS_FRONT 4           /* shade waves of a frame-kernel workgroup when they also make the fresh paths (WavefrontBuffers::front), and of the frame server's.  Three until the walk
-                                             * waves' trip and fold got shorter: then the walk waves ran their trips half empty, waiting for paths (32 of 64 lanes a trip on the dragon; 40 with four).
-                                             * dragon 1080p 3 -> 5.33, 4 -> 5.17, and with FLX_WF_FOLD_EARLY 3 -> 5.35, 4 -> 5.07, 5 -> 5.31 ms (profiles/fold_early_loads.txt) */
+#define FLX_FRAME_SHADERS_FRONT 3           /* shade waves of a frame-kernel workgroup when they also make the fresh paths (WavefrontBuffers::front).  Three until the walk waves' trip and
+                                             * fold got shorter: then the walk waves ran their trips half empty, waiting for paths, and a fourth shade wave paid (dragon 1080p, with
+                                             * FLX_WF_FOLD_EARLY: 3 -> 5.35, 4 -> 5.07, 5 -> 5.31 ms: profiles/fold_early_loads.txt).  Three again since a shade costs fewer instructions (the
+                                             * cosine table, the one-light rule, the per-triangle table): 3 -> 4.91, 4 -> 4.99, 5 -> 5.26 ms; without those three 3 -> 5.31 (profiles/shade_needless.txt).
+                                             * The frame server keeps four (FLX_SERVER_SHADERS, flx_server.hip) */
 #endif
 #ifndef FLX_WF_MAX_TRANSFORMS
 #define FLX_WF_MAX_TRANSFORMS 4             /* object spaces of a scene the frame kernel and the frame server take.  With five, the rays of thirteen walk waves left no LDS for the tree's top; those of
@@ -61,10 +63,33 @@ FLX_DEV FrameArgsP kernel_frame_args() { return (FrameArgsP)__builtin_amdgcn_ker
 /* (the lane's pixel of screen tile `tile`; h = its primary hit: suv + triangle id as bits, -1 for none; returns whether the pixel's paths run) */
 /* VER (the frame server with a scene that moves, flx_server.hip): DeviceScene::rotation / shift / lights hold one version of those arrays per (workgroup, frame
  * slot) — version blockIdx.x x frames + the frame's slot — and a path reads its frame's. */
+/* What a shade's result does not need (profiles/shade_needless.txt).  The persistent frame kernels and the frame server instantiate their shading with SHORT, and the
+ * frame kernel of whole frames with TABLE; the shade kernels of the rounds (k_wf_shade0, k_wf_front, k_wf_shade) keep the defaults, the code of before.
+ *   FLX_SHADE_COS_TABLE (SHORT)    cos((float)s) of the sample number from WavefrontBuffers::cosSample.  In shade0_tile s is the loop's counter, the same in every lane:
+ *                                  a scalar load (the table is read through the constant address space: nothing in the launch writes it); in shade_path a vector load by
+ *                                  the lane's s.  A sample number beyond the table's count computes.
+ *   FLX_SHADE_FIRST_LIGHT (SHORT)  flx_device.h, reservoirPick: one light, no draw in front of the loop.
+ *   FLX_FRAME_ANGLE_TABLE (TABLE)  flx_kernels.h: shadeSurface reads DeviceScene::angle_tan.
+ * Each at 0: the instructions of before. */
+#ifndef FLX_SHADE_COS_TABLE
+#define FLX_SHADE_COS_TABLE 1
+#endif
+typedef const __attribute__((address_space(4))) float *ConstFloatP;
+template <bool SHORT>
+FLX_DEV float sample_cos_uniform(const WavefrontBuffers &wb, uint32_t s) {      /* s: the same in every lane */
+  if (SHORT && FLX_SHADE_COS_TABLE && s < wb.cosSampleCount) return ((ConstFloatP)(uintptr_t)wb.cosSample)[s];
+  return flx_cos((float)s);
+}
+template <bool SHORT>
+FLX_DEV float sample_cos(const WavefrontBuffers &wb, uint32_t s) {
+  if (SHORT && FLX_SHADE_COS_TABLE && s < wb.cosSampleCount) return wb.cosSample[s];
+  return flx_cos((float)s);
+}
+
 template <bool VER>
 FLX_DEV uint32_t scene_version_of(const DeviceFrame &fr, uint32_t frameIdx) { return VER ? blockIdx.x * fr.frames + frameIdx : 0u; }
 
-template <bool COUNT, bool LV = false, bool VER = false>
+template <bool COUNT, bool LV = false, bool VER = false, bool TABLE = (FLX_ANGLE_TABLE != 0), bool SHORT = false>
 FLX_DEV bool shade0_tile(FrameArgsP ab, uint32_t tile, uint32_t lane, float4 h, WorkCounters &cnt, const FrameView *lv = nullptr) {
   uint32_t S, frameIdx, lightBase = 0;
   int tri;
@@ -95,7 +120,7 @@ FLX_DEV bool shade0_tile(FrameArgsP ab, uint32_t tile, uint32_t lane, float4 h, 
     pr.origin = camera;
     pr.dir = primary_dir_v(fr, view_at<LV>(fr, lv, frameIdx), px, py_gl, ndcX, ndcY, viewDepthPerS);
     const WorkCounters before = cnt;
-    shadeSurface<COUNT>(sc, fr, hit, pr, camera, sf, cnt);
+    shadeSurface<COUNT, TABLE>(sc, fr, hit, pr, camera, sf, cnt);
     if (COUNT) {                                            /* the per-path kernel counts these once per path */
       cnt.shades = before.shades + (cnt.shades - before.shades) * S;
       cnt.atlas_texels = before.atlas_texels + (cnt.atlas_texels - before.atlas_texels) * S;
@@ -125,9 +150,9 @@ FLX_DEV bool shade0_tile(FrameArgsP ab, uint32_t tile, uint32_t lane, float4 h, 
     p.lastHitPoint = camera;
     p.dontFilter = true;
     p.importancyFactor = F3(1.0f, 1.0f, 1.0f);
-    const float cosSampleN = flx_cos((float)s);
+    const float cosSampleN = sample_cos_uniform<SHORT>(wb, s);
     ShadeOut so;
-    shadeSample(sc, fr, sf, ps, p, camera, cosSampleN, 0, so);
+    shadeSample<SHORT && FLX_SHADE_FIRST_LIGHT>(sc, fr, sf, ps, p, camera, cosSampleN, 0, so);
     const int flags = (p.dontFilter ? RF_DONT_FILTER : 0) | (so.needShadow ? RF_NEED_SHADOW : 0) | (so.shadowedNoWalk ? RF_SHADOWED_NO_WALK : 0) |
                       (nextBounceRuns(fr, 0, p.importancyFactor, ps.originalColor) ? 0 : RF_NO_CLOSEST);
     if (compact) {
@@ -192,7 +217,7 @@ FLX_DEV float4 primary_tile(FrameArgsP ab, uint32_t tile, uint32_t lane, WorkCou
 }
 
 /* One path's shading for its next bounce (fragment:476-589): the record the last walk left -> the record the next walk reads. */
-template <bool COUNT, bool LV = false, bool VER = false>
+template <bool COUNT, bool LV = false, bool VER = false, bool TABLE = (FLX_ANGLE_TABLE != 0), bool SHORT = false>
 FLX_DEV void shade_path(FrameArgsP ab, uint32_t pathId, WorkCounters &cnt, const FrameView *lv = nullptr) {
   FLX_ARGS_OF(ab);
   float4 *rec = wb.rec + (size_t)pathId * 8;
@@ -221,9 +246,9 @@ FLX_DEV void shade_path(FrameArgsP ab, uint32_t pathId, WorkCounters &cnt, const
   float viewDepthPerS;
   (void)primary_dir_v(fr, view_at<LV>(fr, lv, frameIdx), px, py_gl, ps.ndc_x, ps.ndc_y, viewDepthPerS);
   ps.seed = view_at<LV>(fr, lv, frameIdx).random_seed;
-  const float cosSampleN = flx_cos((float)s);
+  const float cosSampleN = sample_cos<SHORT>(wb, s);
   ShadeOut so;
-  bounceShade<COUNT>(sc, fr, ps, p, camera, cosSampleN, pb, so, cnt);
+  bounceShade<COUNT, TABLE, SHORT && FLX_SHADE_FIRST_LIGHT>(sc, fr, ps, p, camera, cosSampleN, pb, so, cnt);
   const int flags = (p.dontFilter ? RF_DONT_FILTER : 0) | (so.needShadow ? RF_NEED_SHADOW : 0) | (so.shadowedNoWalk ? RF_SHADOWED_NO_WALK : 0) |
                     (nextBounceRuns(fr, pb, p.importancyFactor, ps.originalColor) ? 0 : RF_NO_CLOSEST);
   rec[0] = make_float4(p.ray.origin.x, p.ray.origin.y, p.ray.origin.z, __int_as_float(flags));

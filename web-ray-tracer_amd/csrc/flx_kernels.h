@@ -8,6 +8,19 @@
 #define FLX_PATHS_ANGLE_TABLE 1        /* k_paths reads the shading's per-triangle table too (DeviceScene::angle_tan): at the seven waves per SIMD it ran at first the table's dependent load cost it 1 %,
                                         * at four it gains 5 % — theater 9.29 -> 8.80 ms (profiles/r04_paths_occupancy.txt) */
 #endif
+#ifndef FLX_FRAME_ANGLE_TABLE
+#define FLX_FRAME_ANGLE_TABLE 1        /* the frame kernel with the front of the frame inside, unstamped (whole frames: k_wf_frame<., true>), reads the table at bounce 0 and at every later
+                                        * shade: its shade waves are the producer its walk waves wait for, and the three acos and three tan in double are a third of a later
+                                        * shade's instructions (profiles/shade_needless.txt).  flx_run_frame makes the table in front of such a launch */
+#endif
+#ifndef FLX_SERVER_ANGLE_TABLE
+#define FLX_SERVER_ANGLE_TABLE 1       /* the frame server with a static scene reads it too (flx_frame_begin makes it in front of the launch; any upload ends the launch).  Round 4 lost 9 % on a
+                                        * rank's eighth with two frames in flight (profiles/r04_angle_table.txt); with today's trips it gains 8 % there, 1.06 -> 0.975 ms, and nothing
+                                        * else moves (profiles/shade_needless.txt).  A scene that moves has transforms per frame slot, which one table cannot follow: it computes */
+#endif
+#ifndef FLX_THIN_ANGLE_TABLE
+#define FLX_THIN_ANGLE_TABLE 0         /* 1, a measuring build: also the stamped frame kernel with the front inside (thin frames: a rank's quarter) reads it.  Not measured: it computes */
+#endif
 #define FLX_FAST_BOX_BOUND 5.764607523034235e17f      /* 2^59: rayCuboidR's precondition, flx_device.h */
 namespace flx {
 
@@ -64,6 +77,11 @@ struct WavefrontBuffers {
   uint32_t tileCostPrimary;     /* tileCost (below) has a second half for the primary rays' visits per tile */
   const uint32_t *tileOrder;    /* frame kernel with its front inside: the screen tile the q-th draw from the frame's tile queue makes (a permutation of the frame's tiles), or nullptr: tile q */
   unsigned long long *tileCost; /* counted frames: entries visited by the paths of every screen tile (flx_debug_tile_cost), or nullptr */
+  /* cos((float)s) for the sample numbers s < cosSampleCount (k_cos_sample: flx_cos itself, once per context), or nullptr / 0: the shading of the persistent frame kernels
+   * reads the value where a shade computed it — 83 vector instructions, 29 of them double precision, for a number that depends on the sample alone.  Samples beyond the
+   * count are computed as before.  (At the end: every other member keeps its place in the kernels' arguments.) */
+  const float *cosSample = nullptr;
+  uint32_t cosSampleCount = 0;
 };
 /* the arguments of the shade kernels and the frame kernels, read from the kernarg segment where they are used (flx_frame_common.h) */
 struct FrameArgs { DeviceScene sc; DeviceFrame fr; WavefrontBuffers wb; };
@@ -97,6 +115,8 @@ void launch_taa(const uint32_t *const planes[9], uint32_t *out8, int W, int H, h
 /* float4 plane -> RGBA8 plane (a render-target store) */
 void launch_quantize(const float4 *src, uint32_t *dst, size_t n, hipStream_t stream);
 void launch_angle_tan(const DeviceScene &sc, float4 *out, hipStream_t stream);      /* DeviceScene::angle_tan for the scene as it stands */
+constexpr uint32_t WF_COS_SAMPLES = 64;      /* sample numbers a context's cosine table holds (WavefrontBuffers::cosSample) */
+void launch_cos_sample(float *out, uint32_t n, hipStream_t stream);                 /* out[s] <- flx_cos((float)s), s < n */
 /* the chain over planes whose slot 0 (R[0], Ip[0], O[0], Id[0], OId) holds the frame */
 void launch_filter_chain(const FilterPlanes &pl, float4 *out, int W, int H, int hdr, hipStream_t stream);
 /* temporal accumulation (pathtracerWGL2.js:571-662), one pass after the trace of a temporal frame over its `pixels` in storage order (a whole frame, or a

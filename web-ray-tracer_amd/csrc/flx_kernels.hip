@@ -653,6 +653,15 @@ void launch_angle_tan(const DeviceScene &sc, float4 *out, hipStream_t stream) {
   hipLaunchKernelGGL(k_angle_tan, dim3((sc.n_entries + 255u) / 256u), dim3(256), 0, stream, s, out);
 }
 
+/* WavefrontBuffers::cosSample: cos((float)s) for the sample numbers s < n, by the routine every shade would call (flx_math.h: flx_cos) — the same floats, once per context */
+__global__ __launch_bounds__(64) void k_cos_sample(float *__restrict__ out, uint32_t n) {
+  const uint32_t s = blockIdx.x * 64u + threadIdx.x;
+  if (s < n) out[s] = flx_cos((float)s);
+}
+void launch_cos_sample(float *out, uint32_t n, hipStream_t stream) {
+  if (n) hipLaunchKernelGGL(k_cos_sample, dim3((n + 63u) / 64u), dim3(64), 0, stream, out, n);
+}
+
 uint64_t path_item_count64(const DeviceFrame &fr) {
   return (uint64_t)((fr.width + 7u) >> 3) * ((fr.rows + 7u) >> 3) * (uint64_t)fr.samples * 64u;
 }

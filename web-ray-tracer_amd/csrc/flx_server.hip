@@ -34,7 +34,9 @@ namespace flx {
 #define FLX_SERVER_RELAY_GROUPS 16           /* workgroups whose shade waves read the host's mailbox and pass it on in device memory */
 #endif
 #ifndef FLX_SERVER_SHADERS
-#define FLX_SERVER_SHADERS FLX_FRAME_SHADERS_FRONT      /* shade waves of a server workgroup (they also make the fresh paths) */
+#define FLX_SERVER_SHADERS 4                            /* shade waves of a server workgroup (they also make the fresh paths).  The frame kernel went back to three when its shades got
+                                                        * cheaper (FLX_FRAME_SHADERS_FRONT); the server with three loses 11 %: a whole frame 5.16 -> 5.76 ms, a rank's eighth with three in
+                                                        * flight 0.78 -> 0.86 (profiles/shade_needless.txt) */
 #endif
 #ifndef FLX_SERVER_SHADERS_DEPTH2_MAX_TILES
 #define FLX_SERVER_SHADERS_DEPTH2_MAX_TILES 24         /* ... of at most this many screen tiles per workgroup and frame */
@@ -237,7 +239,7 @@ __global__ __launch_bounds__(FLX_WF_WALK_THREADS, FLX_WF_WAVES_PER_EU) void k_wf
       else __hip_atomic_fetch_or(sa.error, WF_ERR_LIST, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     const float4 h = primary_tile<false, true, VER>(ab, tile, lane, cnt, lv);
-    const bool runs = shade0_tile<false, true, VER>(ab, tile, lane, h, cnt, lv);
+    const bool runs = shade0_tile<false, true, VER, FLX_SERVER_ANGLE_TABLE && !VER, true>(ab, tile, lane, h, cnt, lv);
     if (flx_ballot(runs) == 0ull) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");            /* (what the tile's dead pixels stored, before the count) */
       if (lane == 0) atomicSub(&ctl[SC_ALIVE + slot], perTile);
@@ -370,7 +372,7 @@ __global__ __launch_bounds__(FLX_WF_WALK_THREADS, FLX_WF_WAVES_PER_EU) void k_wf
           const long long tb0 = wall_clock64();
           const bool mine = lane < got && id != WF_INVALID;
           statAdd(SVS_BATCHES, 1ull); statAdd(SVS_BATCH_LANES, got);
-          if (mine) shade_path<false, true, VER>(ab, id, cnt, lv);
+          if (mine) shade_path<false, true, VER, FLX_SERVER_ANGLE_TABLE && !VER, true>(ab, id, cnt, lv);
           const uint32_t slotMine = slotOf(id);
           for (uint32_t sl = 0; sl < depth; sl++) fq_push(ring(RK_WALK, sl), rctl(RK_WALK, sl), mine && slotMine == sl, id, lane);
           tBatch += wall_clock64() - tb0;

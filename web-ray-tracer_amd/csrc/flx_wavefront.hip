@@ -789,7 +789,7 @@ __global__ __launch_bounds__(FLX_WF_WALK_THREADS, FLX_WF_WAVES_PER_EU) void k_wf
 #define FLX_FRAME_SHADERS 2                 /* shade waves of a frame-kernel workgroup (dragon 1080p: 1 -> 7.27, 2 -> 6.87, 3 -> 7.16 ms per frame) */
 #endif
 #ifndef FLX_FRAME_SHADERS_FRONT
-#define FLX_FRAME_SHADERS_FRONT 4           /* ... when they also make the fresh paths (WavefrontBuffers::front): flx_frame_common.h */
+#define FLX_FRAME_SHADERS_FRONT 3           /* ... when they also make the fresh paths (WavefrontBuffers::front): flx_frame_common.h */
 #endif
 #ifndef FLX_FRAME_PROLOGUE_WAVES
 #define FLX_FRAME_PROLOGUE_WAVES 2          /* walk waves that make a first tile before their loop (FRONT) */
@@ -825,6 +825,7 @@ __device__ __forceinline__ void wf_frame_body(uint32_t total_items, uint32_t lds
    * tile at a time (what k_primary and k_wf_shade0 do in front of the launch otherwise) — and hand them to the walk waves as (tile, sample) units of 64
    * through a third ring; the frame's queue then counts screen tiles. */
   constexpr bool front = FRONT;                /* (a kernel of its own: the front's code costs the other one registers) */
+  constexpr bool ANGLE_TABLE = FLX_FRAME_ANGLE_TABLE && FRONT && (!STAMP || FLX_THIN_ANGLE_TABLE);      /* whole frames: the shading reads DeviceScene::angle_tan (flx_kernels.h) */
   const uint32_t perTile = samples * 64u;
   float2 *raysBase = (float2 *)(ctl + FC_WORDS);
   {
@@ -866,7 +867,7 @@ __device__ __forceinline__ void wf_frame_body(uint32_t total_items, uint32_t lds
     if (wb.tileOrder) tile = __builtin_amdgcn_readfirstlane(wb.tileOrder[tile]);      /* (set only for a launch that owns the whole frame: item_base 0) */
     tile += wb.item_base / perTile;
     const float4 h = primary_tile<COUNT>(argBase, tile, lane, cnt);
-    const bool runs = shade0_tile<COUNT>(argBase, tile, lane, h, cnt);
+    const bool runs = shade0_tile<COUNT, false, false, ANGLE_TABLE, true>(argBase, tile, lane, h, cnt);
     if (flx_ballot(runs) == 0ull) {
       if (lane == 0) atomicSub(&ctl[FC_ALIVE], perTile);
     } else {
@@ -926,7 +927,7 @@ __device__ __forceinline__ void wf_frame_body(uint32_t total_items, uint32_t lds
       const bool mine = lane < got && id != WF_INVALID;
       if (flx_ballot(lane < got && id == WF_INVALID) != 0ull && lane == 0 && wb.error) __hip_atomic_fetch_or(wb.error, WF_ERR_RING_SLOT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      /* (a slot that never filled: fq_pop gave up on it) */
       if (inject & WF_INJECT_NO_SHADING) continue;            /* fault injection: the batch is dropped */
-      if (mine) shade_path<COUNT>(argBase, id, cnt);
+      if (mine) shade_path<COUNT, false, false, ANGLE_TABLE, true>(argBase, id, cnt);
       fq_push(walkRing, ctl + FC_WQ, mine, id, lane);
     }
     { FLX_FRAME_ARGS(); flush_counters<COUNT>(cnt, wb.counters); }
