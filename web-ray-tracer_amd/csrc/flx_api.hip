@@ -1108,6 +1108,14 @@ static bool chain_wanted(flx_context *ctx, const flx_frame_params *p, const Devi
 #define FLX_SERVER_TILE_LIST_FACTOR 4       /* a workgroup's list of tiles to resolve: this many times its even share .. */
 #define FLX_SERVER_TILE_LIST_MIN 64         /* .. this many at the least; a workgroup whose list is full leaves the rest of the frame's tiles to the others */
 #endif
+/* A frame of the server comes down to the host in a copy of at least this size.  The runtime hands a short device-to-host copy (below 16 KB by default:
+ * GPU_FORCE_BLIT_COPY_SIZE) to a KERNEL instead of a DMA engine; beside a launch that fills every CU that kernel finds no room, waits for the launch's idle exit —
+ * two seconds — and the launch starts again at the next frame (a frame of 8 x 8 pixels, or the canvas' bytes of 64 x 48; tests/test_server_moving_gpu.py).  The
+ * launch's images and the host slots have room for it (server_allocate, frame_begin_on). */
+#ifndef FLX_SERVER_COPY_MIN_BYTES
+#define FLX_SERVER_COPY_MIN_BYTES (64u * 1024u)
+#endif
+static size_t server_copy_bytes(size_t bytes) { return bytes && bytes < (size_t)FLX_SERVER_COPY_MIN_BYTES ? (size_t)FLX_SERVER_COPY_MIN_BYTES : bytes; }
 static flx_status server_take(flx_context *ctx, int k);
 flx_status flx_server_stop(flx_context *ctx) {
   if (!ctx->sv_running && !(ctx->sv_pending[0].valid || ctx->sv_pending[1].valid || ctx->sv_pending[2].valid)) return flx_dyn_flush(ctx);
@@ -1156,9 +1164,10 @@ static flx_status server_allocate(flx_context *ctx, const DeviceFrame &frOne, ui
   int chains = 1;
   if ((s = ensure_workspace(ctx, fr, 3, false, chains))) return s;
   const size_t P1 = (size_t)frOne.rows * frOne.width;
-  if (!ctx->sv_target_slots && ctx->d_sv_out.capacity() < SV_MAX_DEPTH * P1) {      /* (with a frame target the launch resolves into the caller's images) */
+  const size_t outPixels = SV_MAX_DEPTH * P1 + FLX_SERVER_COPY_MIN_BYTES / sizeof(float4);      /* (room behind the last slot for a short frame's padded copy: server_take) */
+  if (!ctx->sv_target_slots && ctx->d_sv_out.capacity() < outPixels) {      /* (with a frame target the launch resolves into the caller's images) */
     FLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if ((s = ctx->d_sv_out.ensure(ctx, SV_MAX_DEPTH * P1))) return s;
+    if ((s = ctx->d_sv_out.ensure(ctx, outPixels))) return s;
   }
   /* a workgroup's list of the screen tiles it made of a frame: a few times its even share (its tiles come to it as it asks for them) */
   const size_t tilesPerSlot0 = itemsPerSlot / ((size_t)fr.samples * 64u);
@@ -1346,7 +1355,7 @@ static flx_status server_take(flx_context *ctx, int k) {
   FLX_HIP(ctx, hipEventRecord(ctx->ev_slot_start[k], ctx->copy_stream));
   FLX_HIP(ctx, hipEventRecord(ctx->ev_slot_traced[k], ctx->copy_stream));
   if (pf.format != FLX_FRAME_DEVICE) {
-    if (ctx->slot_bytes[k]) FLX_HIP(ctx, hipMemcpyAsync(ctx->h_slot[k], src, ctx->slot_bytes[k], hipMemcpyDeviceToHost, ctx->copy_stream));
+    if (ctx->slot_bytes[k]) FLX_HIP(ctx, hipMemcpyAsync(ctx->h_slot[k], src, server_copy_bytes(ctx->slot_bytes[k]), hipMemcpyDeviceToHost, ctx->copy_stream));      /* (padded: FLX_SERVER_COPY_MIN_BYTES) */
     FLX_HIP(ctx, hipEventRecord(ctx->ev_slot_done[k], ctx->copy_stream));
   }
   return FLX_OK;
@@ -1379,11 +1388,12 @@ static flx_status frame_begin_on(flx_context *ctx, const flx_frame_params *param
   /* (hipMalloc / hipFree / hipHostMalloc wait for the device: with the frame server's launch running they would wait for its end — which waits for this
    * frame.  A slot that has to grow ends the launch first; the next frame starts another.) */
   const bool served = chained == 2 && !gathered && pixels;      /* (a frame of the server is handed out from the launch's own images, or the caller's: it needs no device slot) */
-  if (ctx->sv_running && ((!served && !ctx->d_slot[k].fits(pixels)) || (format != FLX_FRAME_DEVICE && !ctx->h_slot[k].fits(bytes))))
+  const size_t hostBytes = served ? server_copy_bytes(bytes) : bytes;      /* (a short frame of the server comes down in a padded copy) */
+  if (ctx->sv_running && ((!served && !ctx->d_slot[k].fits(pixels)) || (format != FLX_FRAME_DEVICE && !ctx->h_slot[k].fits(hostBytes))))
     if ((s = flx_server_stop(ctx))) return s;
   if (!served && (s = ctx->d_slot[k].ensure(ctx, pixels))) return s;
   if (format == FLX_FRAME_RGBA8 && !served && pixels && (s = ctx->d_slot8[k].ensure(ctx, pixels))) return s;      /* (a frame of the server is quantised where it is resolved) */
-  if (format != FLX_FRAME_DEVICE && !ctx->h_slot[k].fits(bytes) && (s = ctx->h_slot[k].ensure(ctx, bytes ? bytes : 16, hipHostMallocDefault))) return s;
+  if (format != FLX_FRAME_DEVICE && !ctx->h_slot[k].fits(hostBytes) && (s = ctx->h_slot[k].ensure(ctx, hostBytes ? hostBytes : 16, hipHostMallocDefault))) return s;
   if (served) {
     /* the frame server: the frame is posted to the running launch; flx_frame_end takes it (server_take) */
     uint32_t seq = 0, sslot = 0;

@@ -200,9 +200,17 @@ __global__ __launch_bounds__(FLX_WF_WALK_THREADS, FLX_WF_WAVES_PER_EU) void k_wf
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    /* "The view is here" is said under the rotation's lock, and only while the slot still has the frame this wave copied.  Several waves copy the same post side by side;
+     * the first one through says so, and a workgroup that holds nothing of the frame (a frame of one screen tile: all but one) rotates the slot a few microseconds
+     * later.  A wave that was still copying then, and looked at the slot's number just before the rotation changed it, used to set the word just after the rotation had
+     * cleared it: the slot's NEXT frame — not posted yet — passed for present with this frame's view and arrays, its workgroup went through the slot a second time and
+     * counted itself twice in groupsDone (a frame that never completes, or completes a workgroup early), or made tiles of the next frame with this frame's arrays. */
     if (fq_load(&ctl[SC_SEQ + slot]) != want) return false;                /* (the slot went on to its next frame while this wave was copying: that frame's view is not this one) */
-    if (lane == 0) __hip_atomic_store(&ctl[SC_SAVAIL + slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      /* (the slot's frame cannot change while its view is not here: a rotation needs it) */
-    return true;
+    if (lane == 0 && atomicCAS(&ctl[SC_ROTLOCK], 0u, 1u) == 0u) {           /* (busy: a sibling says it, or the next poll does) */
+      if (fq_load(&ctl[SC_SEQ + slot]) == want) __hip_atomic_store(&ctl[SC_SAVAIL + slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_store(&ctl[SC_ROTLOCK], 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    return true;                                                            /* (whoever goes on from here looks at the word itself: makeTile, the walk waves' refill, tryRotate) */
   };
 
   /* The front of a frame for one 8 x 8 screen tile of `slot` (k_wf_frame's makeTile), r = the age of its frame here: 0 not now, 1 a tile made, 2 no more tiles.
