@@ -930,6 +930,47 @@ flx_status flx_get_diag(flx_context *ctx, uint64_t out[32]);   /* out[8..12]: bo
  * for k = 0 .. 11 out[3k], out[3k+1], out[3k+2] = sum / count / max over the walk workgroups of the shader cycles since the workgroup's start
  * at which its walks in flight first numbered <= 2^k; out[36..38] the same for the moment the workgroup found the walk queue dry. */
 flx_status flx_get_tail_diag(flx_context *ctx, uint64_t out[40]);
+/* ---- ray batches with a volume (beside "ray queries" and "probe volumes" above, whose types it takes) --------------------------------------------- */
+/* A TRACED BATCH WHOSE PATHS END IN A PROBE VOLUME: flx_rays_trace_ordered_device with the ambient term looked up.  A path of flx_rays_trace ends in finalColor +
+ * importancyFactor * ambient, the params' constant standing for all the light the path did not trace.  Here it ends in finalColor + importancyFactor * A, per
+ * component, the product first (include/flx_gather.h: the definition, which the kernels and the tests' CPU reference compile alike):
+ *   THE LAST POINT of a path is the surface point of the last bounce iteration it shaded: x that iteration's ray origin, n its smooth normal facing the arriving ray
+ *     — a FLX_SURFACE_POSITION and a FLX_SURFACE_NORMAL row's floats for the ray that arrived there.  A path that shaded nothing (max_reflections == 0, or the loop
+ *     guard failing before bounce 0) has none.
+ *   THE LOOKUP E = (e0, e1, e2, W) of the position row (x, 1.0f) and n: flx_volume_irradiance_of's with neither offsets nor map, flx_volume_irradiance_map_of's with
+ *     a map, flx_volume_irradiance_relocated_of's with offsets (with or without a map).
+ *   THE VALUE A_c = (W > 0.0f) ? e_c * gain : params->ambient[c]; a NaN W and a path without a last point take the constant.  Irradiance over pi is the radiance a
+ *     Lambertian surface sends on, which is what `ambient` stands for: a gain of (float)(1 / pi) is the usual one.
+ * Everything else of a radiance row — the loop guard, the bounces, the walks, the noise, the sum over samples in sample order, the scale, originalColor, the eight
+ * words, the miss row — is flx_rays_trace's.  Two bounces and a volume stand in for many bounces at the cost of two bounces and one lookup.
+ * Three launches a slab behind its first hits (csrc/flx_rays_gather.hip): k_rays_paths_gather writes a PATH RECORD of 64 bytes per (ray, sample), k_gather_ambient
+ * looks the records up one lane each and writes the 16-byte slots k_rays_resolve reads.  Ray rows, radiance rows, `order`, producer_stream, the frame server, n == 0,
+ * slabs and the host call's staging are flx_rays_trace_ordered_device's and flx_rays_trace_ordered's, word for word; a slab's scratch holds five 16-byte slots a
+ * (ray, sample) where theirs holds one, under the same 256 MB.  flx_debug_set_trace_slab and flx_debug_set_query_groups apply as they do there.  A group has no
+ * such call; frames, filter planes and ray images do not take a volume.
+ * Refusals, each with nothing enqueued and the output untouched, in this order: the scene's and the trace params' own and an unknown bit of `order` (for any n); for
+ * n > 0 the rays' and the radiance's, all in flx_rays_trace_ordered's words under this call's name; a NULL volume; the grid's and the map's (a map only where one is
+ * given) and the volume's arrays' — NULL, not memory of the context's device, not 16-byte aligned, too short, overlapping each other — in the volume calls' words;
+ * then, FLX_ERR_INVALID with a message of its own each: a gain that is negative or not finite; a reserved word that is not 0; `map` and `maps` not both given or both
+ * NULL; an array of the volume that overlaps the rays or the radiance. */
+typedef struct flx_gather_volume {
+  const flx_volume_grid *grid;
+  const void *sh;            /* nx ny nz * 9 float4 */
+  const flx_volume_map *map; /* or NULL */
+  const void *maps;          /* nx ny nz * m m float4; NULL without a map */
+  const void *offsets;       /* nx ny nz float4 ("probe relocation"), or NULL: probes on the lattice */
+  float gain;                /* finite, >= 0 */
+  uint32_t reserved;         /* 0 */
+} flx_gather_volume;
+flx_status flx_rays_trace_gather_device(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume /* host struct, arrays on ctx's device */,
+                                        const void *d_rays /* n * 8 floats */, void *d_radiance /* n * 8 words */, uint32_t n, uint32_t order /* 0 or FLX_TRACE_ORDER_HITS */,
+                                        void *producer_stream /* as flx_rays_trace_device's */);
+flx_status flx_rays_trace_gather(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume /* host arrays */, const float *rays, void *radiance, uint32_t n,
+                                 uint32_t order);
+/* The last batch traced with a volume (zeros but [7] if none), set only when the whole call succeeded: out[0] its rays, [1] its slabs, [2] the rays of a full slab,
+ * [3] workgroups of the last slab's paths kernel, [4] workgroups of its lookup kernel, [5] bit 0 a map, bit 1 offsets, [6] whether it was ordered, [7] the bytes of
+ * one path record.  It waits for nothing. */
+flx_status flx_debug_last_gather(flx_context *ctx, uint32_t out[8]);
 
 #ifdef __cplusplus
 }

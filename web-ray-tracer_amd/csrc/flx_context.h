@@ -322,6 +322,10 @@ struct flx_context {
    * rows; all grown behind flx_grow's one wait and never shrunk.  What the last reduction or relocation ran (flx_debug_last_volume_relocate) */
   DeviceBuffer<float4> d_relocate_positions, d_relocate_planes, d_relocate_offsets;
   struct VolumeRelocateLaunch { uint32_t probes = 0, face_size = 0, chunks = 0, chunk = 0, groups = 0, flags = 0, first = 0, fused = 0; } last_volume_relocate;
+  /* ray batches with a volume (flx_rays_gather.hip): the path records of a slab, four float4 a (ray, sample) as planes, grown with the traced batches' scratch above
+   * — which a slab of these uses too — behind flx_grow's one wait and never shrunk.  What the last batch ran (flx_debug_last_gather) */
+  DeviceBuffer<float4> d_gather_records;
+  struct GatherLaunch { uint32_t n = 0, slabs = 0, slab = 0, path_groups = 0, lookup_groups = 0, flags = 0, order = 0; } last_gather;
   /* uploads: pinned staging ring */
   PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};

@@ -37,6 +37,7 @@ EXPORTS = [
     "flx_rays_cast_device", "flx_rays_cast", "flx_debug_set_query_groups", "flx_debug_last_query",
     "flx_rays_trace_device", "flx_rays_trace", "flx_debug_set_trace_slab", "flx_debug_last_trace",
     "flx_rays_trace_ordered_device", "flx_rays_trace_ordered", "flx_debug_sort_keys", "flx_debug_hit_keys", "flx_debug_last_ray_order",
+    "flx_rays_trace_gather_device", "flx_rays_trace_gather", "flx_debug_last_gather",
     "flx_rays_surface_device", "flx_rays_surface", "flx_frame_surface_device", "flx_frame_surface", "flx_debug_last_surface",
     "flx_rays_planes_device", "flx_rays_planes", "flx_rays_image_device", "flx_rays_image", "flx_debug_last_ray_planes",
     "flx_rays_image_temporal_device", "flx_rays_image_temporal", "flx_rays_history_reset", "flx_debug_last_ray_temporal",
@@ -237,6 +238,16 @@ def _map(vmap, call):
 
 def _map_rows(vmap, probes):
     return int(probes) * vmap.bins if vmap is not None else 0
+
+
+class GatherVolume(C.Structure):
+    """flx_gather_volume (flexlight_hip_debug.h, "ray batches with a volume"): the volume a traced batch's paths end in — pointers to the grid and the map, the
+    addresses of the SH rows, the map rows and the offset rows (0: none), the gain and a reserved word.  Context.trace_rays_gather[_device] make it."""
+    _fields_ = [("grid", C.POINTER(VolumeGrid)), ("sh", C.c_void_p), ("map", C.POINTER(VolumeMap)), ("maps", C.c_void_p), ("offsets", C.c_void_p), ("gain", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
+GATHER_GAIN = float(np.float32(1.0 / np.pi))      # irradiance over pi: the radiance a Lambertian surface sends on, which `ambient` stands for
 
 
 def volume_irradiance_map_of(grid, vmap, sh, maps, position, normal):
@@ -449,6 +460,9 @@ def _load():
         "flx_debug_last_trace": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_rays_trace_ordered_device": (C.c_int, [vp, C.POINTER(TraceParams), vp, vp, u32, u32, vp]),
         "flx_rays_trace_ordered": (C.c_int, [vp, C.POINTER(TraceParams), fp, vp, u32, u32]),
+        "flx_rays_trace_gather_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), vp, vp, u32, u32, vp]),
+        "flx_rays_trace_gather": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), fp, vp, u32, u32]),
+        "flx_debug_last_gather": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_debug_sort_keys": (C.c_int, [vp, C.POINTER(u32), u32, C.POINTER(u32)]),
         "flx_debug_hit_keys": (C.c_int, [vp, fp, vp, u32, C.POINTER(u32), fp]),
         "flx_debug_last_ray_order": (C.c_int, [vp, C.POINTER(u32)]),
@@ -1165,6 +1179,64 @@ class Context:
         self._check(LIB.flx_rays_trace_ordered(self._h, C.byref(params) if params is not None else None, _fp(rays), out.ctypes.data_as(C.c_void_p), rays.shape[0], int(order)),
                     "flx_rays_trace_ordered")
         return out
+
+    @staticmethod
+    def _gather_volume(grid, sh, vmap, maps, offsets, gain, reserved, call):
+        """-> a GatherVolume over addresses (sh, maps, offsets: integers, 0 for none); the grid and the map are kept alive by the caller's references"""
+        if grid is not None and not isinstance(grid, VolumeGrid):
+            raise TypeError("%s: grid is a VolumeGrid" % call)
+        if vmap is not None and not isinstance(vmap, VolumeMap):
+            raise TypeError("%s: map is a VolumeMap" % call)
+        v = GatherVolume()
+        if grid is not None:
+            v.grid = C.pointer(grid)
+        if vmap is not None:
+            v.map = C.pointer(vmap)
+        v.sh, v.maps, v.offsets = sh or None, maps or None, offsets or None
+        v.gain, v.reserved = gain, int(reserved)
+        return v
+
+    def trace_rays_gather_device(self, rays, params, grid, sh, vmap=None, maps=None, offsets=None, gain=GATHER_GAIN, out=None, order=0, stream=None, reserved=0, volume=True):
+        """flx_rays_trace_gather_device: trace_rays_ordered_device whose paths end in the volume's irradiance at their last point times gain in place of the params'
+        ambient (include/flx_gather.h).  grid: VolumeGrid; sh, maps, offsets: contiguous tensors on the context's device (or addresses) of probes x 144, probes x bins
+        x 16 and probes x 16 bytes, maps with vmap, offsets or not; volume=False hands the library no volume, which it refuses.  Returns the rows ENQUEUED ON THE
+        CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        call = "trace_rays_gather_device"
+        r, n, o, out, stream = self._trace_device_args(rays, params, out, stream, call)
+        probes = grid.probes if grid is not None else 0
+        s = self._device_out(sh, probes * 144, call, "sh") if sh is not None else 0
+        d = self._device_out(maps, _map_rows(vmap, probes) * 16, call, "maps") if maps is not None else 0
+        f = self._device_out(offsets, probes * 16, call, "offsets") if offsets is not None else 0
+        v = self._gather_volume(grid, s, vmap, d, f, gain, reserved, call)
+        self._check(LIB.flx_rays_trace_gather_device(self._h, C.byref(params) if params is not None else None, C.byref(v) if volume else None, C.c_void_p(r), C.c_void_p(o), n,
+                                                     int(order), C.c_void_p(stream) if stream else None), "flx_rays_trace_gather_device")
+        return out
+
+    def trace_rays_gather(self, rays, params, grid, sh, vmap=None, maps=None, offsets=None, gain=GATHER_GAIN, order=0, reserved=0):
+        """flx_rays_trace_gather: the same for host arrays — rays [n, 8], sh [probes, 36], maps [probes * bins, 4], offsets [probes, 4], all float32 -> radiance rows
+        uint8 [n, 32], complete"""
+        call = "trace_rays_gather"
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        sh = np.ascontiguousarray(sh, np.float32).reshape(-1, 36) if sh is not None else None
+        maps = np.ascontiguousarray(maps, np.float32).reshape(-1, 4) if maps is not None else None
+        offsets = np.ascontiguousarray(offsets, np.float32).reshape(-1, 4) if offsets is not None else None
+        probes = grid.probes if grid is not None else 0
+        if (sh is not None and sh.shape[0] != probes) or (maps is not None and vmap is not None and maps.shape[0] != probes * vmap.bins) or (
+                offsets is not None and offsets.shape[0] != probes):
+            raise ValueError("%s: one SH row, size x size map rows and one offset row per probe of the grid" % call)
+        v = self._gather_volume(grid, sh.ctypes.data if sh is not None else 0, vmap, maps.ctypes.data if maps is not None else 0,
+                                offsets.ctypes.data if offsets is not None else 0, gain, reserved, call)
+        out = np.zeros((rays.shape[0], 32), np.uint8)
+        self._check(LIB.flx_rays_trace_gather(self._h, C.byref(params) if params is not None else None, C.byref(v), _fp(rays), out.ctypes.data_as(C.c_void_p), rays.shape[0],
+                                              int(order)), "flx_rays_trace_gather")
+        return out
+
+    def last_gather(self):
+        """flx_debug_last_gather -> dict (zeros but record_bytes when no batch was traced with a volume): n, slabs, slab (rays of a full one), path_groups and
+        lookup_groups (of 256 lanes, last slab), flags (bit 0 a map, bit 1 offsets), ordered, record_bytes"""
+        out = (C.c_uint32 * 8)()
+        self._check(LIB.flx_debug_last_gather(self._h, out), "flx_debug_last_gather")
+        return dict(zip(("n", "slabs", "slab", "path_groups", "lookup_groups", "flags", "ordered", "record_bytes"), list(out)))
 
     def sort_keys(self, keys):
         """flx_debug_sort_keys: keys uint32 [n] in host memory, n from 1 to 2^21 -> the positions 0 .. n - 1 in ascending key order, equal keys in the order given

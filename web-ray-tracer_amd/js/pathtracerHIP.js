@@ -45,9 +45,10 @@ function castRaysOn (context, rays, what) {
 
 /* flx_rays_trace on a context whose scene, lights, transforms and atlases are up: the radiance rows as the library writes them, 8 words a ray
  * (include/flexlight_hip_debug.h), unpacked into typed arrays */
-function traceRaysOn (context, rays, params, order) {
+function traceRaysOn (context, rays, params, order, volume, gain) {
   if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('traceRays: rays is a Float32Array of 8 floats per ray');
-  const rows = order ? native().traceRaysOrdered(context, rays, params, order) : native().traceRays(context, rays, params);      // (order: FLX_TRACE_ORDER_* bits)
+  const rows = volume ? native().traceRaysGather(context, rays, params, order, volume, gain)      // (volume: bakeVolume's native handle)
+    : order ? native().traceRaysOrdered(context, rays, params, order) : native().traceRays(context, rays, params);      // (order: FLX_TRACE_ORDER_* bits)
   const n = rays.length / 8;
   const words = new Uint32Array(rows), f = new Float32Array(rows), i32 = new Int32Array(rows);
   const out = { radiance: new Float32Array(4 * n), s: new Float32Array(n), entry: new Int32Array(n), transform: new Int32Array(n), shades: new Uint32Array(n) };
@@ -306,13 +307,22 @@ class PathTracerHIP {
    * LAST sample left it.  It waits for the answer; frames in flight finish unchanged.
    * options.order: 'hits' traces the rays in the order of their first hit points (flx_rays_trace_ordered) — the same rows, bit for bit and in the order given,
    * sooner where the rays come in no useful order: reflection rays, probe rays, shuffled rays.  Without it the rays are traced in the order given.  It is read
-   * here and is no part of traceParams()'s result; any other value is a TypeError. */
+   * here and is no part of traceParams()'s result; any other value is a TypeError.
+   * options.volume: bakeVolume's handle.  Every path then ends in the volume's irradiance at its last surface point times options.gain — by default
+   * Math.fround(1 / Math.PI): irradiance over pi is the radiance a Lambertian surface sends on — where it ends in scene.ambientLight without (flx_rays_trace_gather,
+   * "ray batches with a volume"): two bounces and a volume stand in for many bounces.  The handle's SH rows, its maps and its offsets stay on the device and are
+   * honoured as renderIrradiance honours them; where the volume has nothing to say (no probe in reach, a path that shaded nothing) the ambient light stays.  A
+   * volume that is no handle and a gain that is no number are TypeErrors.  Without options.volume the call is what it was. */
   traceRays (rays, options) {
     if (this._devices) throw new Error('traceRays: one GPU only (a group of GPUs traces no rays)');
     const order = options ? options.order : undefined;
     if (order !== undefined && order !== 'hits') throw new TypeError("traceRays: order is 'hits' or left out");
+    const volume = options ? options.volume : undefined;
+    if (volume !== undefined && (!volume || !volume._handle)) throw new TypeError('traceRays: volume is what bakeVolume returned');
+    const gain = options && options.gain !== undefined ? options.gain : Math.fround(1 / Math.PI);
+    if (volume !== undefined && typeof gain !== 'number') throw new TypeError('traceRays: gain is a number');
     this._uploadFrameState();
-    return traceRaysOn(this._context(), rays, this.traceParams(options), order === 'hits' ? 1 : 0);
+    return traceRaysOn(this._context(), rays, this.traceParams(options), order === 'hits' ? 1 : 0, volume ? volume._handle : undefined, gain);
   }
 
   /* LIGHT PROBES: probe positions in, one spherical-harmonic row per probe out, the rays and their radiance never leaving the device (flx_probes_sh,

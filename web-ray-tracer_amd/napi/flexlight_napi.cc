@@ -821,6 +821,45 @@ static napi_value RaysIrradiance(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+/* traceRaysGather(handle, rays Float32Array(8 n), params (traceRays'), order, volume, gain) -> ArrayBuffer(32 n): flx_rays_trace_gather_device on the volume's rows —
+ * its SH rows, its maps and its offsets where it has them, all resident —: traceRays' rows whose paths end in the volume's irradiance at their last point times gain
+ * (include/flexlight_hip_debug.h "ray batches with a volume").  The rays go up into the volume's staging, the rows come down from behind them. */
+static napi_value TraceRaysGather(napi_env env, napi_callback_info info) {
+  napi_value argv[6];
+  if (!get_args(env, info, 6, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  if (!box) return nullptr;
+  void *rays; size_t len;
+  if (!typed(env, argv[1], napi_float32_array, &rays, &len)) return nullptr;
+  if (len % 8 != 0 || len / 8 > 0xffffffffu) { napi_throw_range_error(env, nullptr, "traceRays: a ray needs 8 floats (origin, noise x, direction, noise y)"); return nullptr; }
+  flx_trace_params p;
+  if (!read_trace_params(env, argv[2], "traceRays", &p)) return nullptr;
+  uint32_t order = 0;
+  if (napi_get_value_uint32(env, argv[3], &order) != napi_ok) { napi_throw_type_error(env, nullptr, "traceRays: order is not a number"); return nullptr; }
+  VolumeBox *volume = get_volume(env, argv[4], box);
+  if (!volume) return nullptr;
+  double gain = 0;
+  if (napi_get_value_double(env, argv[5], &gain) != napi_ok) { napi_throw_type_error(env, nullptr, "traceRays: gain is not a number"); return nullptr; }
+  const size_t n = len / 8;
+  void *rows = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, n * 32, &rows, &buf));
+  if (!volume_room(env, volume, n ? n * 64 : 64)) return nullptr;
+  char *d_rays = static_cast<char *>(volume->d_io), *d_rows = d_rays + n * 32;
+  if (n > 0 && !hip_ok(env, hipMemcpy(d_rays, rays, n * 32, hipMemcpyHostToDevice), "hipMemcpy")) return nullptr;
+  flx_gather_volume v;
+  memset(&v, 0, sizeof v);
+  v.grid = &volume->grid; v.sh = volume->d_sh;
+  v.map = volume->d_maps ? &volume->map : nullptr; v.maps = volume->d_maps;
+  v.offsets = volume->d_offsets;
+  v.gain = (float)gain;
+  flx_status rc = flx_rays_trace_gather_device(box->ctx, &p, &v, d_rays, d_rows, (uint32_t)n, order, nullptr);
+  if (rc == FLX_OK) rc = flx_sync(box->ctx);
+  if (rc != FLX_OK) return fail(env, box->ctx, "flx_rays_trace_gather_device", rc);
+  if (n > 0 && !hip_ok(env, hipMemcpy(rows, d_rows, n * 32, hipMemcpyDeviceToHost), "hipMemcpy")) return nullptr;
+  return buf;
+}
+
 /* rayImage(handle, rays Float32Array(8 width height), width, height, params (traceRays'), hdr) -> ArrayBuffer(16 width height): flx_rays_image, the rays in image
  * order (row 0 on top) traced into the five filter planes and denoised by the chain; float4 per pixel (include/flexlight_hip_debug.h) */
 static napi_value RayImage(napi_env env, napi_callback_info info) {
@@ -1857,7 +1896,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "traceProbes", TraceProbes }, { "probeIrradiance", ProbeIrradiance }, { "bakeVolume", BakeVolume }, { "volumeRows", VolumeRows }, { "volumeMaps", VolumeMaps }, { "updateVolume", UpdateVolume }, { "relocateVolume", RelocateVolume }, { "volumeOffsets", VolumeOffsets }, { "frameIrradiance", FrameIrradiance }, { "raysIrradiance", RaysIrradiance }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "traceRaysGather", TraceRaysGather }, { "traceProbes", TraceProbes }, { "probeIrradiance", ProbeIrradiance }, { "bakeVolume", BakeVolume }, { "volumeRows", VolumeRows }, { "volumeMaps", VolumeMaps }, { "updateVolume", UpdateVolume }, { "relocateVolume", RelocateVolume }, { "volumeOffsets", VolumeOffsets }, { "frameIrradiance", FrameIrradiance }, { "raysIrradiance", RaysIrradiance }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas }, { "uploadTextures", UploadTextures }, { "updateTexture", UpdateTexture },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
