@@ -947,7 +947,7 @@ flx_status flx_get_tail_diag(flx_context *ctx, uint64_t out[40]);
  * looks the records up one lane each and writes the 16-byte slots k_rays_resolve reads.  Ray rows, radiance rows, `order`, producer_stream, the frame server, n == 0,
  * slabs and the host call's staging are flx_rays_trace_ordered_device's and flx_rays_trace_ordered's, word for word; a slab's scratch holds five 16-byte slots a
  * (ray, sample) where theirs holds one, under the same 256 MB.  flx_debug_set_trace_slab and flx_debug_set_query_groups apply as they do there.  A group has no
- * such call; frames, filter planes and ray images do not take a volume.
+ * such call; frames do not take a volume; filter planes and ray images take one through the calls of "ray images with a volume" below.
  * Refusals, each with nothing enqueued and the output untouched, in this order: the scene's and the trace params' own and an unknown bit of `order` (for any n); for
  * n > 0 the rays' and the radiance's, all in flx_rays_trace_ordered's words under this call's name; a NULL volume; the grid's and the map's (a map only where one is
  * given) and the volume's arrays' — NULL, not memory of the context's device, not 16-byte aligned, too short, overlapping each other — in the volume calls' words;
@@ -971,6 +971,51 @@ flx_status flx_rays_trace_gather(flx_context *ctx, const flx_trace_params *param
  * [3] workgroups of the last slab's paths kernel, [4] workgroups of its lookup kernel, [5] bit 0 a map, bit 1 offsets, [6] whether it was ordered, [7] the bytes of
  * one path record.  It waits for nothing. */
 flx_status flx_debug_last_gather(flx_context *ctx, uint32_t out[8]);
+/* ---- ray images with a volume (beside "ray queries", "ray images over time", "cameras" and "ray batches with a volume" above, whose types it takes) ---------- */
+/* THE FILTER PLANES, THE RAY IMAGES AND THE RAY IMAGES OVER TIME WHOSE SAMPLES END IN A PROBE VOLUME: the displayable output — the five planes, the denoise chain,
+ * the temporal histories — lit by a volume.  THE RULE: a gathered plane row is flx_rays_planes' row ("ray queries") with one change: sample s of a ray contributes
+ * flx_gather_path_value(finalColor_s, importancyFactor_s, A_s) where flx_rays_planes adds finalColor_s + importancyFactor_s * ambient.  A_s is computed exactly as
+ * include/flx_gather.h defines it: flx_gather_lookup at the sample's last point (x, n), in whichever of the three forms the volume takes, then flx_gather_ambient with
+ * the caller's gain; the params' ambient where W is not > 0 and where the sample shaded nothing (max_reflections == 0, min_importancy > 1).  The last point of a
+ * sample is a gathered batch's: x the ray origin of the last bounce iteration the sample shaded, n that iteration's smooth normal facing the arriving ray.
+ * Everything else is unchanged: the globals carried from sample to sample, the sample order, the scale, fract / floor, planes 2 to 4, the miss row of zeros, the
+ * RGBA8 packing, the temporal pass in the lane that owns the ray, finalColor * originalColor in the temporal canvas mode.  include/flx_gather.h has no new function.
+ * The lookup runs INLINE in the planes kernel (csrc/flx_rays_planes_gather.hip: k_rays_planes_gather), at the end of every sample's bounce loop, where the wave is
+ * together again: no records, no second kernel; the scratch is the hit rows only and a slab is one slot a ray, 2^21 rays, so that a 1080p image is one slab.
+ * Each call has its sibling's signature with the volume after the params.  The _device calls take a host struct whose arrays are memory of the context's device.
+ * THE HOST CALLS TAKE HOST RAYS AND HOST OUTPUTS BUT A VOLUME WHOSE ARRAYS ARE ON THE DEVICE, as a volume handle's are (flx_volume_bake_device's rows): a volume is
+ * resident, the rays of an image are not.  The camera calls make the rays on the device as flx_camera_image[_temporal]_device do and hand them on.
+ * The temporal calls use the same FLX_RAY_HISTORIES histories as flx_rays_image_temporal: A HISTORY DOES NOT KNOW WHETHER A VOLUME LIT IT — images with and without
+ * a volume, or with different volumes, blend in one history if the caller names the same one; flx_rays_history_reset is the caller's business.
+ * Ordering, producer_stream, the frame server, n == 0, slabs, flx_debug_set_trace_slab and flx_debug_set_query_groups are the siblings', word for word.
+ * Refusals, each with nothing enqueued, the outputs untouched and the history exactly what it was, in this order: 1. the sibling's own for the scene, the params, the
+ * size, the temporal, the camera and the arrays, under the new call's name; 2. flx_rays_trace_gather's for the volume: a NULL volume, the grid's, the map's, the
+ * arrays', a gain that is negative or not finite, a reserved word that is not 0, `map` and `maps` not both given or both NULL; 3. an array of the volume that
+ * overlaps the rays, a plane output or the image.  A group has no such call; frames do not take a volume. */
+flx_status flx_rays_planes_gather_device(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume /* host struct, arrays on ctx's device */,
+                                         const void *d_rays, uint32_t n, void *d_planes8, void *d_planes32, void *producer_stream);
+flx_status flx_rays_planes_gather(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume /* arrays on ctx's device */, const float *rays, uint32_t n,
+                                  void *planes8, void *planes32);
+flx_status flx_rays_image_gather_device(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, int hdr, const void *d_rays, uint32_t width,
+                                        uint32_t height, void *d_out_rgba, void *producer_stream);
+flx_status flx_rays_image_gather(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume /* arrays on ctx's device */, int hdr, const float *rays,
+                                 uint32_t width, uint32_t height, float *out_rgba);
+flx_status flx_rays_image_temporal_gather_device(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, const flx_ray_temporal *temporal,
+                                                 const void *d_rays, uint32_t width, uint32_t height, void *d_out_rgba, void *producer_stream);
+flx_status flx_rays_image_temporal_gather(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume /* arrays on ctx's device */,
+                                          const flx_ray_temporal *temporal, const float *rays, uint32_t width, uint32_t height, float *out_rgba);
+flx_status flx_camera_image_gather_device(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, int hdr, const flx_camera *camera, uint32_t width,
+                                          uint32_t height, void *d_out_rgba);
+flx_status flx_camera_image_gather(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume /* arrays on ctx's device */, int hdr,
+                                   const flx_camera *camera, uint32_t width, uint32_t height, float *out_rgba);
+flx_status flx_camera_image_temporal_gather_device(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, const flx_ray_temporal *temporal,
+                                                   const flx_camera *camera, uint32_t width, uint32_t height, void *d_out_rgba);
+flx_status flx_camera_image_temporal_gather(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume /* arrays on ctx's device */,
+                                            const flx_ray_temporal *temporal, const flx_camera *camera, uint32_t width, uint32_t height, float *out_rgba);
+/* The last planes, image or temporal call with a volume (zeros if none), set only when the whole call succeeded: out[0] its rays, [1] its slabs, [2] the rays of a
+ * full slab, [3] workgroups of the last planes launch, [4] bit 0 a map, bit 1 offsets, [5] the mode (0 planes, 1 the temporal canvas, 2 the temporal filter),
+ * [6] samples, [7] whether the lockstep walk ran.  It waits for nothing. */
+flx_status flx_debug_last_planes_gather(flx_context *ctx, uint32_t out[8]);
 
 #ifdef __cplusplus
 }

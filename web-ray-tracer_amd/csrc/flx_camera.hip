@@ -21,6 +21,7 @@
 #include "flx_ray_planes_args.h"
 #include "flx_ray_temporal_args.h"
 #include "flx_rays_host.h"
+#include "flx_rays_planes_gather.h"
 
 namespace flx {
 
@@ -127,44 +128,57 @@ extern "C" flx_status flx_camera_rays(flx_context *ctx, const flx_camera *camera
  * camera.  A refusal that is flx_rays_image[_temporal]_device's own is asked of that call, which looks at those before it looks at an array: its words.
  * *n <- width * height. */
 static flx_status image_refused(flx_context *ctx, const flx_trace_params *params, bool over_time, const flx_ray_temporal *temporal, int hdr, const flx_camera *camera, uint32_t width,
-                                uint32_t height, uint32_t *n, const char *call) {
+                                uint32_t height, uint32_t *n, const char *call, bool gather = false, const flx_gather_volume *volume = nullptr) {
   flx_status s = flx_trace_params_refused(ctx, params, call);
   if (s) return s;
   const bool theirs = flx_ray_image_size_check(width, height, n) != FLX_RAY_PLANES_ARGS_OK ||
                       (over_time && flx_ray_temporal_check(temporal != nullptr, temporal ? temporal->history : 0, temporal ? temporal->use_filter : 0, temporal ? temporal->hdr : 0) !=
                                         FLX_RAY_TEMPORAL_ARGS_OK);
+  if (theirs && gather)      /* "ray images with a volume": the same of the calls that take one */
+    return over_time ? flx_rays_image_temporal_gather_device(ctx, params, volume, temporal, nullptr, width, height, nullptr, nullptr)
+                     : flx_rays_image_gather_device(ctx, params, volume, hdr, nullptr, width, height, nullptr, nullptr);
   if (theirs)
     return over_time ? flx_rays_image_temporal_device(ctx, params, temporal, nullptr, width, height, nullptr, nullptr) : flx_rays_image_device(ctx, params, hdr, nullptr, width, height, nullptr, nullptr);
   flx_camera_span span;
   return cameras_refused(ctx, camera, 1u, width, height, nullptr, &span, call);
 }
 
-/* Both image calls: the camera's rays into the context's buffer, then the ray-image call on them.  temporal NULL: flx_rays_image_device with hdr. */
+/* Both image calls: the camera's rays into the context's buffer, then the ray-image call on them.  temporal NULL: flx_rays_image_device with hdr.  With `gather` the
+ * calls that take a volume: its refusals behind the image's, before the rays are made, then flx_rays_image[_temporal]_gather_device. */
 static flx_status image_device(flx_context *ctx, const flx_trace_params *params, bool over_time, const flx_ray_temporal *temporal, int hdr, const flx_camera *camera, uint32_t width,
-                               uint32_t height, void *d_out_rgba, const char *call) {
+                               uint32_t height, void *d_out_rgba, const char *call, bool gather = false, const flx_gather_volume *volume = nullptr) {
   uint32_t n = 0;
-  flx_status s = image_refused(ctx, params, over_time, temporal, hdr, camera, width, height, &n, call);
+  flx_status s = image_refused(ctx, params, over_time, temporal, hdr, camera, width, height, &n, call, gather, volume);
   if (s) return s;
   /* the image, looked at before the rays are made: a refusal enqueues nothing */
   if (!d_out_rgba) return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": the image is NULL");
   FLX_HIP(ctx, hipSetDevice(ctx->device));
   if (flx_range_wraps((uint64_t)(uintptr_t)d_out_rgba, (uint64_t)n * FLX_RAY_PLANES_ROW32) || !flx_rows_on_device(ctx, d_out_rgba, (size_t)n * FLX_RAY_PLANES_ROW32))
     return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": the image is not width * height float4 in memory of the context's device, 16-byte aligned");
+  if (gather) {
+    flx_planes_gather_array mine[FLX_PLANES_GATHER_CALL_ARRAYS];
+    const int kc = flx_planes_gather_image_arrays(0u, (uint64_t)(uintptr_t)d_out_rgba, n, mine);
+    if ((s = flx_planes_gather_volume_refused(ctx, volume, mine, kc, call, nullptr))) return s;
+  }
   if ((s = flx_grow(ctx, flx_need(&ctx->d_camera_rays, (size_t)n * 2u)))) return s;      /* (an earlier image may still read the rays that are about to go) */
   const flx_camera_span whole = { 0u, 0u, width, height, n };
   if ((s = camera_enqueue(ctx, camera, 1u, width, height, whole, ctx->d_camera_rays.get()))) return s;
+  if (gather)
+    return over_time ? flx_rays_image_temporal_gather_device(ctx, params, volume, temporal, ctx->d_camera_rays.get(), width, height, d_out_rgba, nullptr)
+                     : flx_rays_image_gather_device(ctx, params, volume, hdr, ctx->d_camera_rays.get(), width, height, d_out_rgba, nullptr);
   return over_time ? flx_rays_image_temporal_device(ctx, params, temporal, ctx->d_camera_rays.get(), width, height, d_out_rgba, nullptr)
                    : flx_rays_image_device(ctx, params, hdr, ctx->d_camera_rays.get(), width, height, d_out_rgba, nullptr);
 }
 
 /* their host-memory twins: the image staged as flx_rays_image stages it */
 static flx_status image_host(flx_context *ctx, const flx_trace_params *params, bool over_time, const flx_ray_temporal *temporal, int hdr, const flx_camera *camera, uint32_t width,
-                             uint32_t height, float *out_rgba, const char *call) {
+                             uint32_t height, float *out_rgba, const char *call, bool gather = false, const flx_gather_volume *volume = nullptr) {
   uint32_t n = 0;
-  flx_status s = image_refused(ctx, params, over_time, temporal, hdr, camera, width, height, &n, call);
+  flx_status s = image_refused(ctx, params, over_time, temporal, hdr, camera, width, height, &n, call, gather, volume);
   if (s) return s;
   if (!out_rgba) return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": the image is NULL");
-  return flx_rays_from_host(ctx, nullptr, 0u, [&]() { return image_device(ctx, params, over_time, temporal, hdr, camera, width, height, ctx->d_query_hits, call); },
+  if (gather && (s = flx_planes_gather_volume_refused(ctx, volume, nullptr, 0, call, nullptr))) return s;      /* (before anything is staged) */
+  return flx_rays_from_host(ctx, nullptr, 0u, [&]() { return image_device(ctx, params, over_time, temporal, hdr, camera, width, height, ctx->d_query_hits, call, gather, volume); },
                             flx_down(&ctx->d_query_hits, n, out_rgba));
 }
 
@@ -188,4 +202,30 @@ extern "C" flx_status flx_camera_image_temporal(flx_context *ctx, const flx_trac
                                                 uint32_t height, float *out_rgba) {
   if (!ctx) return FLX_ERR_INVALID;
   return image_host(ctx, params, true, temporal, 0, camera, width, height, out_rgba, "flx_camera_image_temporal");
+}
+
+/* ---- "ray images with a volume": the four calls above with a flx_gather_volume behind the params ------------------------------------------------------ */
+
+extern "C" flx_status flx_camera_image_gather_device(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, int hdr, const flx_camera *camera,
+                                                     uint32_t width, uint32_t height, void *d_out_rgba) {
+  if (!ctx) return FLX_ERR_INVALID;
+  return image_device(ctx, params, false, nullptr, hdr, camera, width, height, d_out_rgba, "flx_camera_image_gather_device", true, volume);
+}
+
+extern "C" flx_status flx_camera_image_gather(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, int hdr, const flx_camera *camera, uint32_t width,
+                                              uint32_t height, float *out_rgba) {
+  if (!ctx) return FLX_ERR_INVALID;
+  return image_host(ctx, params, false, nullptr, hdr, camera, width, height, out_rgba, "flx_camera_image_gather", true, volume);
+}
+
+extern "C" flx_status flx_camera_image_temporal_gather_device(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, const flx_ray_temporal *temporal,
+                                                              const flx_camera *camera, uint32_t width, uint32_t height, void *d_out_rgba) {
+  if (!ctx) return FLX_ERR_INVALID;
+  return image_device(ctx, params, true, temporal, 0, camera, width, height, d_out_rgba, "flx_camera_image_temporal_gather_device", true, volume);
+}
+
+extern "C" flx_status flx_camera_image_temporal_gather(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, const flx_ray_temporal *temporal,
+                                                       const flx_camera *camera, uint32_t width, uint32_t height, float *out_rgba) {
+  if (!ctx) return FLX_ERR_INVALID;
+  return image_host(ctx, params, true, temporal, 0, camera, width, height, out_rgba, "flx_camera_image_temporal_gather", true, volume);
 }

@@ -326,6 +326,9 @@ struct flx_context {
    * — which a slab of these uses too — behind flx_grow's one wait and never shrunk.  What the last batch ran (flx_debug_last_gather) */
   DeviceBuffer<float4> d_gather_records;
   struct GatherLaunch { uint32_t n = 0, slabs = 0, slab = 0, path_groups = 0, lookup_groups = 0, flags = 0, order = 0; } last_gather;
+  /* ray images with a volume (flx_rays_planes_gather.hip): no buffer of their own — the scratch is the planes calls' hit rows.  What the last launch ran, and the
+   * last call that succeeded as a whole (flx_debug_last_planes_gather) */
+  struct PlanesGatherLaunch { uint32_t n = 0, slabs = 0, slab = 0, groups = 0, flags = 0, mode = 0, samples = 0, lock = 0; } planes_gather_launch, last_planes_gather;
   /* uploads: pinned staging ring */
   PinnedBuffer<uint8_t> stage;
   hipEvent_t stage_done[8] = {};

@@ -41,6 +41,7 @@
 #include "flx_ray_planes_args.h"
 #include "flx_ray_temporal_args.h"
 #include "flx_rays_host.h"
+#include "flx_rays_planes_gather.h"
 #include "flx_texel.h"
 
 using namespace flx;
@@ -246,9 +247,10 @@ static flx_status history_advance(flx_context *ctx, flx_context::RayHistory &h, 
 }
 
 /* The slabs' launches, the arguments accepted: the five planes of n > 0 rays into d_planes8 and / or d_planes32.  With `temporal` (and the image's width): the
- * temporal instantiation over that history, the chain's five inputs into d_planes8 (use_filter == 1) or the canvas colours into d_planes32, float4[n] */
+ * temporal instantiation over that history, the chain's five inputs into d_planes8 (use_filter == 1) or the canvas colours into d_planes32, float4[n].  With `volume`
+ * ("ray images with a volume"), accepted: the same launches of k_rays_planes_gather (flx_rays_planes_gather.hip) */
 static flx_status planes_enqueue(flx_context *ctx, const flx_trace_params *params, const void *d_rays, uint32_t n, void *d_planes8, void *d_planes32, void *producer_stream,
-                                 const char *call, const flx_ray_temporal *temporal = nullptr, uint32_t width = 0u) {
+                                 const char *call, const flx_ray_temporal *temporal = nullptr, uint32_t width = 0u, const flx_planes_volume *volume = nullptr) {
   flx_status s;
   RayPlanesArgs ra;
   if ((s = flx_make_scene(ctx, ra.sc))) return s;           /* (refuses a scene that names a transform not uploaded) */
@@ -275,6 +277,12 @@ static flx_status planes_enqueue(flx_context *ctx, const flx_trace_params *param
     groups = ctx->query_groups ? ctx->query_groups : (full < cus * 8u ? full : cus * 8u);
     uint32_t *queue = ctx->d_trace_ctl.get() + 2;
     const float4 *hits = ctx->d_trace_hits.get();
+    if (volume) {
+      const int mode = !history ? RAY_PLANES : temporal->use_filter == 1 ? RAY_TEMPORAL_FILTER : RAY_TEMPORAL_CANVAS;
+      uint32_t *rings = history ? history->rings.get() + first : nullptr;      /* as th below */
+      const uint32_t packed = history ? (uint32_t)history->at.head | ((uint32_t)history->at.n << 8) | ((uint32_t)temporal->hdr << 16) : 0u;
+      return flx_planes_gather_launch(ctx, lock, mode, groups, ra.sc, ra.fr, rays, hits, out8, out32, queue, m, (size_t)n, rings, packed, *volume);
+    }
     if (history) {
       RayTemporalArgs th;
       th.rings = history->rings.get() + first;              /* the ray's index in the IMAGE: first + its index in the slab */
@@ -294,6 +302,7 @@ static flx_status planes_enqueue(flx_context *ctx, const flx_trace_params *param
     return FLX_OK;
   });
   if (s) return s;
+  if (volume) flx_planes_gather_ran(ctx, n, cut.slabs, cut.slab);
   if (history) {
     flx_context::RayTemporalLaunch &t = ctx->last_ray_temporal;
     t.slabs = cut.slabs; t.slab = cut.slab; t.depth = (uint32_t)history->at.n; t.history = (uint32_t)temporal->history; t.n = n; t.samples = (uint32_t)params->samples;
@@ -307,9 +316,9 @@ static flx_status planes_enqueue(flx_context *ctx, const flx_trace_params *param
   return FLX_OK;
 }
 
-extern "C" flx_status flx_rays_planes_device(flx_context *ctx, const flx_trace_params *params, const void *d_rays, uint32_t n, void *d_planes8, void *d_planes32,
-                                             void *producer_stream) {
-  static const char *const call = "flx_rays_planes_device";
+/* flx_rays_planes_device, and with `gather` flx_rays_planes_gather_device: the volume's refusals behind the arrays', its overlap with them last */
+static flx_status planes_device(flx_context *ctx, const flx_trace_params *params, bool gather, const flx_gather_volume *volume, const void *d_rays, uint32_t n, void *d_planes8,
+                                void *d_planes32, void *producer_stream, const char *call) {
   if (!ctx) return FLX_ERR_INVALID;
   flx_status s = flx_trace_params_refused(ctx, params, call);
   if (s || n == 0) return s;
@@ -318,32 +327,60 @@ extern "C" flx_status flx_rays_planes_device(flx_context *ctx, const flx_trace_p
   if (arrays != FLX_RAY_PLANES_ARGS_OK && !overlap) return planes_refusal(ctx, arrays, call);
   FLX_HIP(ctx, hipSetDevice(ctx->device));
   if (!flx_rows_on_device(ctx, d_rays, (size_t)n * FLX_RAY_ROW_BYTES))
-    return fail(ctx, FLX_ERR_INVALID, "flx_rays_planes_device: the rays are not n rows in memory of the context's device, 16-byte aligned");
+    return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": the rays are not n rows in memory of the context's device, 16-byte aligned");
   if (d_planes8 && !flx_rows_on_device(ctx, d_planes8, (size_t)n * FLX_RAY_PLANES * FLX_RAY_PLANES_ROW8))
-    return fail(ctx, FLX_ERR_INVALID, "flx_rays_planes_device: planes8 is not 5 n texels in memory of the context's device, 16-byte aligned");
+    return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": planes8 is not 5 n texels in memory of the context's device, 16-byte aligned");
   if (d_planes32 && !flx_rows_on_device(ctx, d_planes32, (size_t)n * FLX_RAY_PLANES * FLX_RAY_PLANES_ROW32))
-    return fail(ctx, FLX_ERR_INVALID, "flx_rays_planes_device: planes32 is not 5 n rows in memory of the context's device, 16-byte aligned");
+    return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": planes32 is not 5 n rows in memory of the context's device, 16-byte aligned");
   if (overlap) return planes_refusal(ctx, arrays, call);
-  return planes_enqueue(ctx, params, d_rays, n, d_planes8, d_planes32, producer_stream, call);
+  if (!gather) return planes_enqueue(ctx, params, d_rays, n, d_planes8, d_planes32, producer_stream, call);
+  flx_planes_gather_array mine[FLX_PLANES_GATHER_CALL_ARRAYS];
+  const int kc = flx_planes_gather_planes_arrays((uint64_t)(uintptr_t)d_rays, (uint64_t)(uintptr_t)d_planes8, (uint64_t)(uintptr_t)d_planes32, n, mine);
+  flx_planes_volume pv;
+  if ((s = flx_planes_gather_volume_refused(ctx, volume, mine, kc, call, &pv))) return s;
+  return planes_enqueue(ctx, params, d_rays, n, d_planes8, d_planes32, producer_stream, call, nullptr, 0u, &pv);
 }
 
-extern "C" flx_status flx_rays_planes(flx_context *ctx, const flx_trace_params *params, const float *rays, uint32_t n, void *planes8, void *planes32) {
-  static const char *const call = "flx_rays_planes";
+extern "C" flx_status flx_rays_planes_device(flx_context *ctx, const flx_trace_params *params, const void *d_rays, uint32_t n, void *d_planes8, void *d_planes32,
+                                             void *producer_stream) {
+  return planes_device(ctx, params, false, nullptr, d_rays, n, d_planes8, d_planes32, producer_stream, "flx_rays_planes_device");
+}
+
+extern "C" flx_status flx_rays_planes_gather_device(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, const void *d_rays, uint32_t n,
+                                                    void *d_planes8, void *d_planes32, void *producer_stream) {
+  return planes_device(ctx, params, true, volume, d_rays, n, d_planes8, d_planes32, producer_stream, "flx_rays_planes_gather_device");
+}
+
+/* flx_rays_planes, and with `gather` flx_rays_planes_gather: host rays and planes, the volume's arrays on the device */
+static flx_status planes_host(flx_context *ctx, const flx_trace_params *params, bool gather, const flx_gather_volume *volume, const float *rays, uint32_t n, void *planes8,
+                              void *planes32, const char *call) {
   if (!ctx) return FLX_ERR_INVALID;
   flx_status s = flx_trace_params_refused(ctx, params, call);
   if (s || n == 0) return s;
   if (!planes8 && !planes32) return planes_refusal(ctx, FLX_RAY_PLANES_NONE, call);
   if (!rays) return planes_refusal(ctx, FLX_RAY_PLANES_NULL, call);
   const size_t rows = (size_t)n * FLX_RAY_PLANES;
+  if (gather && (s = flx_planes_gather_volume_refused(ctx, volume, nullptr, 0, call, nullptr))) return s;      /* (before anything is staged) */
   return flx_rays_from_host(ctx, rays, n, [&]() {
-    return flx_rays_planes_device(ctx, params, ctx->d_query_rays, n, planes8 ? ctx->d_ray_planes.get() : nullptr, planes32 ? ctx->d_query_hits.get() : nullptr, nullptr);
+    void *d8 = planes8 ? ctx->d_ray_planes.get() : nullptr, *d32 = planes32 ? ctx->d_query_hits.get() : nullptr;
+    return gather ? planes_device(ctx, params, true, volume, ctx->d_query_rays, n, d8, d32, nullptr, call)
+                  : flx_rays_planes_device(ctx, params, ctx->d_query_rays, n, d8, d32, nullptr);
   }, flx_down(&ctx->d_ray_planes, rows, planes8), flx_down(&ctx->d_query_hits, rows, planes32));
+}
+
+extern "C" flx_status flx_rays_planes(flx_context *ctx, const flx_trace_params *params, const float *rays, uint32_t n, void *planes8, void *planes32) {
+  return planes_host(ctx, params, false, nullptr, rays, n, planes8, planes32, "flx_rays_planes");
+}
+
+extern "C" flx_status flx_rays_planes_gather(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, const float *rays, uint32_t n, void *planes8,
+                                             void *planes32) {
+  return planes_host(ctx, params, true, volume, rays, n, planes8, planes32, "flx_rays_planes_gather");
 }
 
 /* Both image calls behind their own refusals: the arrays of n = width * height rays, the planes, the chain.  temporal NULL: flx_rays_image_device, which has its hdr
  * beside the params; else the image over that history, the hdr the history's. */
 static flx_status image_enqueue(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal, int hdr, const void *d_rays, uint32_t width, uint32_t height,
-                                uint32_t n, void *d_out_rgba, void *producer_stream, const char *call) {
+                                uint32_t n, void *d_out_rgba, void *producer_stream, const char *call, bool gather = false, const flx_gather_volume *gather_volume = nullptr) {
   const enum flx_ray_planes_refusal arrays = flx_ray_image_arrays_check((uint64_t)(uintptr_t)d_rays, (uint64_t)(uintptr_t)d_out_rgba, n);
   if (arrays != FLX_RAY_PLANES_ARGS_OK && arrays != FLX_RAY_PLANES_OVERLAP_RAYS) return planes_refusal(ctx, arrays, call);
   FLX_HIP(ctx, hipSetDevice(ctx->device));
@@ -352,11 +389,19 @@ static flx_status image_enqueue(flx_context *ctx, const flx_trace_params *params
   if (!flx_rows_on_device(ctx, d_out_rgba, (size_t)n * FLX_RAY_PLANES_ROW32))
     return fail(ctx, FLX_ERR_INVALID, std::string(call) + ": the image is not width * height float4 in memory of the context's device, 16-byte aligned");
   if (arrays == FLX_RAY_PLANES_OVERLAP_RAYS) return planes_refusal(ctx, arrays, call);
-  if (temporal && temporal->use_filter != 1)      /* the canvas colour of the temporal pass, straight from the kernel */
-    return planes_enqueue(ctx, params, d_rays, n, nullptr, d_out_rgba, producer_stream, call, temporal, width);
   flx_status s;
+  flx_planes_volume pv;
+  const flx_planes_volume *volume = nullptr;      /* "ray images with a volume": the volume's refusals behind the arrays', its overlap with them last */
+  if (gather) {
+    flx_planes_gather_array mine[FLX_PLANES_GATHER_CALL_ARRAYS];
+    const int kc = flx_planes_gather_image_arrays((uint64_t)(uintptr_t)d_rays, (uint64_t)(uintptr_t)d_out_rgba, n, mine);
+    if ((s = flx_planes_gather_volume_refused(ctx, gather_volume, mine, kc, call, &pv))) return s;
+    volume = &pv;
+  }
+  if (temporal && temporal->use_filter != 1)      /* the canvas colour of the temporal pass, straight from the kernel */
+    return planes_enqueue(ctx, params, d_rays, n, nullptr, d_out_rgba, producer_stream, call, temporal, width, volume);
   if ((s = flx_grow(ctx, flx_need(&ctx->d_ray_planes, (size_t)n * FLX_RAY_PLANES)))) return s;      /* (an earlier image's chain may still read the planes that are about to go) */
-  if ((s = planes_enqueue(ctx, params, d_rays, n, ctx->d_ray_planes.get(), nullptr, producer_stream, call, temporal, width))) return s;
+  if ((s = planes_enqueue(ctx, params, d_rays, n, ctx->d_ray_planes.get(), nullptr, producer_stream, call, temporal, width, volume))) return s;
   /* the chain reads width, height and hdr of a frame's params, nothing of a camera: frame-0 texture state, as flx_filter_planes_device starts it (with a history:
    * dColor, dIp, dOColor, dId and dOId feed it as for a ray image) */
   flx_frame_params image;
@@ -365,27 +410,46 @@ static flx_status image_enqueue(flx_context *ctx, const flx_trace_params *params
   return flx_filter_planes_enqueue(ctx, &image, ctx->d_ray_planes.get(), d_out_rgba, true);
 }
 
-extern "C" flx_status flx_rays_image_device(flx_context *ctx, const flx_trace_params *params, int hdr, const void *d_rays, uint32_t width, uint32_t height, void *d_out_rgba,
-                                            void *producer_stream) {
-  static const char *const call = "flx_rays_image_device";
+static flx_status image_device(flx_context *ctx, const flx_trace_params *params, bool gather, const flx_gather_volume *volume, int hdr, const void *d_rays, uint32_t width,
+                               uint32_t height, void *d_out_rgba, void *producer_stream, const char *call) {
   if (!ctx) return FLX_ERR_INVALID;
   flx_status s = flx_trace_params_refused(ctx, params, call);
   if (s) return s;
   uint32_t n = 0;
   if ((s = planes_refusal(ctx, flx_ray_image_size_check(width, height, &n), call))) return s;
-  return image_enqueue(ctx, params, nullptr, hdr, d_rays, width, height, n, d_out_rgba, producer_stream, call);
+  return image_enqueue(ctx, params, nullptr, hdr, d_rays, width, height, n, d_out_rgba, producer_stream, call, gather, volume);
 }
 
-extern "C" flx_status flx_rays_image(flx_context *ctx, const flx_trace_params *params, int hdr, const float *rays, uint32_t width, uint32_t height, float *out_rgba) {
-  static const char *const call = "flx_rays_image";
+extern "C" flx_status flx_rays_image_device(flx_context *ctx, const flx_trace_params *params, int hdr, const void *d_rays, uint32_t width, uint32_t height, void *d_out_rgba,
+                                            void *producer_stream) {
+  return image_device(ctx, params, false, nullptr, hdr, d_rays, width, height, d_out_rgba, producer_stream, "flx_rays_image_device");
+}
+
+extern "C" flx_status flx_rays_image_gather_device(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, int hdr, const void *d_rays, uint32_t width,
+                                                   uint32_t height, void *d_out_rgba, void *producer_stream) {
+  return image_device(ctx, params, true, volume, hdr, d_rays, width, height, d_out_rgba, producer_stream, "flx_rays_image_gather_device");
+}
+
+static flx_status image_host(flx_context *ctx, const flx_trace_params *params, bool gather, const flx_gather_volume *volume, int hdr, const float *rays, uint32_t width,
+                             uint32_t height, float *out_rgba, const char *call) {
   if (!ctx) return FLX_ERR_INVALID;
   flx_status s = flx_trace_params_refused(ctx, params, call);
   if (s) return s;
   uint32_t n = 0;
   if ((s = planes_refusal(ctx, flx_ray_image_size_check(width, height, &n), call))) return s;
   if (!rays || !out_rgba) return planes_refusal(ctx, FLX_RAY_PLANES_NULL, call);
-  return flx_rays_from_host(ctx, rays, n, [&]() { return flx_rays_image_device(ctx, params, hdr, ctx->d_query_rays, width, height, ctx->d_query_hits, nullptr); },
+  if (gather && (s = flx_planes_gather_volume_refused(ctx, volume, nullptr, 0, call, nullptr))) return s;      /* (before anything is staged) */
+  return flx_rays_from_host(ctx, rays, n, [&]() { return image_device(ctx, params, gather, volume, hdr, ctx->d_query_rays, width, height, ctx->d_query_hits, nullptr, call); },
                             flx_down(&ctx->d_query_hits, n, out_rgba));
+}
+
+extern "C" flx_status flx_rays_image(flx_context *ctx, const flx_trace_params *params, int hdr, const float *rays, uint32_t width, uint32_t height, float *out_rgba) {
+  return image_host(ctx, params, false, nullptr, hdr, rays, width, height, out_rgba, "flx_rays_image");
+}
+
+extern "C" flx_status flx_rays_image_gather(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, int hdr, const float *rays, uint32_t width,
+                                            uint32_t height, float *out_rgba) {
+  return image_host(ctx, params, true, volume, hdr, rays, width, height, out_rgba, "flx_rays_image_gather");
 }
 
 /* a refusal of flx_ray_temporal_args.h in words */
@@ -403,9 +467,8 @@ static flx_status temporal_refusal(flx_context *ctx, enum flx_ray_temporal_refus
 }
 static_assert(FLX_RAY_HISTORIES == FLX_RAY_TEMPORAL_HISTORIES, "the header's histories are the context's");
 
-extern "C" flx_status flx_rays_image_temporal_device(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal, const void *d_rays, uint32_t width,
-                                                     uint32_t height, void *d_out_rgba, void *producer_stream) {
-  static const char *const call = "flx_rays_image_temporal_device";
+static flx_status temporal_device(flx_context *ctx, const flx_trace_params *params, bool gather, const flx_gather_volume *volume, const flx_ray_temporal *temporal,
+                                  const void *d_rays, uint32_t width, uint32_t height, void *d_out_rgba, void *producer_stream, const char *call) {
   if (!ctx) return FLX_ERR_INVALID;
   flx_status s = flx_trace_params_refused(ctx, params, call);
   if (s) return s;
@@ -413,12 +476,21 @@ extern "C" flx_status flx_rays_image_temporal_device(flx_context *ctx, const flx
   if ((s = planes_refusal(ctx, flx_ray_image_size_check(width, height, &n), call))) return s;
   if ((s = temporal_refusal(ctx, flx_ray_temporal_check(temporal != nullptr, temporal ? temporal->history : 0, temporal ? temporal->use_filter : 0, temporal ? temporal->hdr : 0), call)))
     return s;
-  return image_enqueue(ctx, params, temporal, temporal->hdr, d_rays, width, height, n, d_out_rgba, producer_stream, call);
+  return image_enqueue(ctx, params, temporal, temporal->hdr, d_rays, width, height, n, d_out_rgba, producer_stream, call, gather, volume);
 }
 
-extern "C" flx_status flx_rays_image_temporal(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal, const float *rays, uint32_t width, uint32_t height,
-                                              float *out_rgba) {
-  static const char *const call = "flx_rays_image_temporal";
+extern "C" flx_status flx_rays_image_temporal_device(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal, const void *d_rays, uint32_t width,
+                                                     uint32_t height, void *d_out_rgba, void *producer_stream) {
+  return temporal_device(ctx, params, false, nullptr, temporal, d_rays, width, height, d_out_rgba, producer_stream, "flx_rays_image_temporal_device");
+}
+
+extern "C" flx_status flx_rays_image_temporal_gather_device(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, const flx_ray_temporal *temporal,
+                                                            const void *d_rays, uint32_t width, uint32_t height, void *d_out_rgba, void *producer_stream) {
+  return temporal_device(ctx, params, true, volume, temporal, d_rays, width, height, d_out_rgba, producer_stream, "flx_rays_image_temporal_gather_device");
+}
+
+static flx_status temporal_host(flx_context *ctx, const flx_trace_params *params, bool gather, const flx_gather_volume *volume, const flx_ray_temporal *temporal, const float *rays,
+                                uint32_t width, uint32_t height, float *out_rgba, const char *call) {
   if (!ctx) return FLX_ERR_INVALID;
   flx_status s = flx_trace_params_refused(ctx, params, call);
   if (s) return s;
@@ -427,8 +499,19 @@ extern "C" flx_status flx_rays_image_temporal(flx_context *ctx, const flx_trace_
   if ((s = temporal_refusal(ctx, flx_ray_temporal_check(temporal != nullptr, temporal ? temporal->history : 0, temporal ? temporal->use_filter : 0, temporal ? temporal->hdr : 0), call)))
     return s;
   if (!rays || !out_rgba) return planes_refusal(ctx, FLX_RAY_PLANES_NULL, call);
-  return flx_rays_from_host(ctx, rays, n, [&]() { return flx_rays_image_temporal_device(ctx, params, temporal, ctx->d_query_rays, width, height, ctx->d_query_hits, nullptr); },
+  if (gather && (s = flx_planes_gather_volume_refused(ctx, volume, nullptr, 0, call, nullptr))) return s;      /* (before anything is staged) */
+  return flx_rays_from_host(ctx, rays, n, [&]() { return temporal_device(ctx, params, gather, volume, temporal, ctx->d_query_rays, width, height, ctx->d_query_hits, nullptr, call); },
                             flx_down(&ctx->d_query_hits, n, out_rgba));
+}
+
+extern "C" flx_status flx_rays_image_temporal(flx_context *ctx, const flx_trace_params *params, const flx_ray_temporal *temporal, const float *rays, uint32_t width, uint32_t height,
+                                              float *out_rgba) {
+  return temporal_host(ctx, params, false, nullptr, temporal, rays, width, height, out_rgba, "flx_rays_image_temporal");
+}
+
+extern "C" flx_status flx_rays_image_temporal_gather(flx_context *ctx, const flx_trace_params *params, const flx_gather_volume *volume, const flx_ray_temporal *temporal,
+                                                     const float *rays, uint32_t width, uint32_t height, float *out_rgba) {
+  return temporal_host(ctx, params, true, volume, temporal, rays, width, height, out_rgba, "flx_rays_image_temporal_gather");
 }
 
 extern "C" flx_status flx_rays_history_reset(flx_context *ctx, int history) {

@@ -38,6 +38,9 @@ EXPORTS = [
     "flx_rays_trace_device", "flx_rays_trace", "flx_debug_set_trace_slab", "flx_debug_last_trace",
     "flx_rays_trace_ordered_device", "flx_rays_trace_ordered", "flx_debug_sort_keys", "flx_debug_hit_keys", "flx_debug_last_ray_order",
     "flx_rays_trace_gather_device", "flx_rays_trace_gather", "flx_debug_last_gather",
+    "flx_rays_planes_gather_device", "flx_rays_planes_gather", "flx_rays_image_gather_device", "flx_rays_image_gather", "flx_rays_image_temporal_gather_device",
+    "flx_rays_image_temporal_gather", "flx_camera_image_gather_device", "flx_camera_image_gather", "flx_camera_image_temporal_gather_device",
+    "flx_camera_image_temporal_gather", "flx_debug_last_planes_gather",
     "flx_rays_surface_device", "flx_rays_surface", "flx_frame_surface_device", "flx_frame_surface", "flx_debug_last_surface",
     "flx_rays_planes_device", "flx_rays_planes", "flx_rays_image_device", "flx_rays_image", "flx_debug_last_ray_planes",
     "flx_rays_image_temporal_device", "flx_rays_image_temporal", "flx_rays_history_reset", "flx_debug_last_ray_temporal",
@@ -463,6 +466,17 @@ def _load():
         "flx_rays_trace_gather_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), vp, vp, u32, u32, vp]),
         "flx_rays_trace_gather": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), fp, vp, u32, u32]),
         "flx_debug_last_gather": (C.c_int, [vp, C.POINTER(u32)]),
+        "flx_rays_planes_gather_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), vp, u32, vp, vp, vp]),
+        "flx_rays_planes_gather": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), fp, u32, vp, vp]),
+        "flx_rays_image_gather_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), C.c_int, vp, u32, u32, vp, vp]),
+        "flx_rays_image_gather": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), C.c_int, fp, u32, u32, fp]),
+        "flx_rays_image_temporal_gather_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), C.POINTER(RayTemporal), vp, u32, u32, vp, vp]),
+        "flx_rays_image_temporal_gather": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), C.POINTER(RayTemporal), fp, u32, u32, fp]),
+        "flx_camera_image_gather_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), C.c_int, C.POINTER(Camera), u32, u32, vp]),
+        "flx_camera_image_gather": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), C.c_int, C.POINTER(Camera), u32, u32, fp]),
+        "flx_camera_image_temporal_gather_device": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), C.POINTER(RayTemporal), C.POINTER(Camera), u32, u32, vp]),
+        "flx_camera_image_temporal_gather": (C.c_int, [vp, C.POINTER(TraceParams), C.POINTER(GatherVolume), C.POINTER(RayTemporal), C.POINTER(Camera), u32, u32, fp]),
+        "flx_debug_last_planes_gather": (C.c_int, [vp, C.POINTER(u32)]),
         "flx_debug_sort_keys": (C.c_int, [vp, C.POINTER(u32), u32, C.POINTER(u32)]),
         "flx_debug_hit_keys": (C.c_int, [vp, fp, vp, u32, C.POINTER(u32), fp]),
         "flx_debug_last_ray_order": (C.c_int, [vp, C.POINTER(u32)]),
@@ -1474,6 +1488,151 @@ class Context:
         self._check(LIB.flx_camera_image_temporal(self._h, C.byref(trace_params) if trace_params is not None else None, C.byref(temporal) if temporal is not None else None,
                                                   C.byref(camera) if camera is not None else None, width, height, _fp(out)), "flx_camera_image_temporal")
         return out
+
+    # -- ray images with a volume -----------------------------------------------------------------------
+    def gather_volume(self, grid, sh, vmap=None, maps=None, offsets=None, gain=GATHER_GAIN, reserved=0):
+        """-> the GatherVolume the *_gather calls below take: grid a VolumeGrid; sh, maps, offsets contiguous tensors ON THE CONTEXT'S DEVICE (or addresses) of
+        probes x 144, probes x bins x 16 and probes x 16 bytes, maps with vmap, offsets or not — the host calls take such a volume too: a volume is resident.  The
+        struct keeps the grid, the map and the tensors alive."""
+        call = "gather_volume"
+        probes = grid.probes if grid is not None else 0
+        s = self._device_out(sh, probes * 144, call, "sh") if sh is not None else 0
+        d = self._device_out(maps, _map_rows(vmap, probes) * 16, call, "maps") if maps is not None else 0
+        f = self._device_out(offsets, probes * 16, call, "offsets") if offsets is not None else 0
+        v = self._gather_volume(grid, s, vmap, d, f, gain, reserved, call)
+        v._keep = (grid, vmap, sh, maps, offsets)
+        return v
+
+    @staticmethod
+    def _volume_ref(volume, call):
+        if volume is not None and not isinstance(volume, GatherVolume):
+            raise TypeError("%s: volume is a GatherVolume (Context.gather_volume)" % call)
+        return C.byref(volume) if volume is not None else None      # (None goes to the library, which refuses it)
+
+    def ray_planes_gather_device(self, rays, params, volume, planes8=None, planes32=None, stream=None):
+        """flx_rays_planes_gather_device: ray_planes_device whose every sample ends in the volume's irradiance at its last point times the gain in place of the
+        params' ambient ("ray images with a volume").  volume: Context.gather_volume's.  Returns (planes8, planes32) ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET
+        COMPLETE."""
+        call = "ray_planes_gather_device"
+        r, n = _ray_rows(rays, self._device, call)
+        if params is not None and not isinstance(params, TraceParams):
+            raise TypeError("%s: params is a TraceParams" % call)
+        if planes8 is None and planes32 is None:
+            planes8 = True
+        if planes8 is True or planes32 is True:
+            import torch
+            if planes8 is True:
+                planes8 = torch.empty((5, n), dtype=torch.int32, device="cuda:%d" % self._device)
+            if planes32 is True:
+                planes32 = torch.empty((5, n, 4), dtype=torch.float32, device="cuda:%d" % self._device)
+        o8 = self._device_out(planes8, 5 * n * 4, call, "planes8") if planes8 is not None else None
+        o32 = self._device_out(planes32, 5 * n * 16, call, "planes32") if planes32 is not None else None
+        self._check(LIB.flx_rays_planes_gather_device(self._h, C.byref(params) if params is not None else None, self._volume_ref(volume, call), C.c_void_p(r), n,
+                                                      C.c_void_p(o8), C.c_void_p(o32), _stream_handle(stream)), "flx_rays_planes_gather_device")
+        return planes8, planes32
+
+    def ray_planes_gather(self, rays, params, volume, floats=False):
+        """flx_rays_planes_gather: rays [n, 8] float32 in host memory, the volume's arrays on the device -> ray_planes' result, complete"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        n = rays.shape[0]
+        p8 = np.zeros((5, n), np.uint32)
+        p32 = np.zeros((5, n, 4), np.float32) if floats else None
+        self._check(LIB.flx_rays_planes_gather(self._h, C.byref(params) if params is not None else None, self._volume_ref(volume, "ray_planes_gather"), _fp(rays), n,
+                                               p8.ctypes.data_as(C.c_void_p), p32.ctypes.data_as(C.c_void_p) if floats else None), "flx_rays_planes_gather")
+        return (p8, p32) if floats else p8
+
+    def _image_out(self, width, height, out, call):
+        if out is None:
+            import torch
+            out = torch.empty((height, width, 4), dtype=torch.float32, device="cuda:%d" % self._device)
+        return out, self._device_out(out, width * height * 16, call, "out")
+
+    def ray_image_gather_device(self, rays, width, height, params, volume, hdr=True, out=None, stream=None):
+        """flx_rays_image_gather_device: ray_image_device lit by the volume.  Returns the image ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        call = "ray_image_gather_device"
+        r, n = _ray_rows(rays, self._device, call)
+        width, height = int(width), int(height)
+        if n != width * height:
+            raise ValueError("%s: %d rays are no image of %d x %d" % (call, n, width, height))
+        out, o = self._image_out(width, height, out, call)
+        self._check(LIB.flx_rays_image_gather_device(self._h, C.byref(params) if params is not None else None, self._volume_ref(volume, call), int(bool(hdr)), C.c_void_p(r),
+                                                     width, height, C.c_void_p(o), _stream_handle(stream)), "flx_rays_image_gather_device")
+        return out
+
+    def ray_image_gather(self, rays, width, height, params, volume, hdr=True):
+        """flx_rays_image_gather: host rays, the volume's arrays on the device -> the denoised image float32 [height, width, 4], complete"""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        width, height = int(width), int(height)
+        if rays.shape[0] != width * height:
+            raise ValueError("ray_image_gather: %d rays are no image of %d x %d" % (rays.shape[0], width, height))
+        out = np.zeros((height, width, 4), np.float32)
+        self._check(LIB.flx_rays_image_gather(self._h, C.byref(params) if params is not None else None, self._volume_ref(volume, "ray_image_gather"), int(bool(hdr)), _fp(rays),
+                                              width, height, _fp(out)), "flx_rays_image_gather")
+        return out
+
+    def rays_image_temporal_gather(self, rays, width, height, trace_params, temporal, volume, device=False, out=None, stream=None):
+        """flx_rays_image_temporal_gather[_device]: rays_image_temporal lit by the volume, over the same histories (a history does not know whether a volume lit it)"""
+        call = "rays_image_temporal_gather"
+        width, height = int(width), int(height)
+        tp = C.byref(trace_params) if trace_params is not None else None
+        tt = C.byref(temporal) if temporal is not None else None
+        if device:
+            r, n = _ray_rows(rays, self._device, call)
+            if n != width * height:
+                raise ValueError("%s: %d rays are no image of %d x %d" % (call, n, width, height))
+            out, o = self._image_out(width, height, out, call)
+            self._check(LIB.flx_rays_image_temporal_gather_device(self._h, tp, self._volume_ref(volume, call), tt, C.c_void_p(r), width, height, C.c_void_p(o),
+                                                                  _stream_handle(stream)), "flx_rays_image_temporal_gather_device")
+            return out
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        if rays.shape[0] != width * height:
+            raise ValueError("%s: %d rays are no image of %d x %d" % (call, rays.shape[0], width, height))
+        img = np.zeros((height, width, 4), np.float32)
+        self._check(LIB.flx_rays_image_temporal_gather(self._h, tp, self._volume_ref(volume, call), tt, _fp(rays), width, height, _fp(img)), "flx_rays_image_temporal_gather")
+        return img
+
+    def camera_image_gather_device(self, camera, width, height, params, volume, hdr=True, out=None):
+        """flx_camera_image_gather_device: camera_image_device lit by the volume.  Returns the image ENQUEUED ON THE CONTEXT'S STREAM AND NOT YET COMPLETE."""
+        call = "camera_image_gather_device"
+        width, height = int(width), int(height)
+        out, o = self._image_out(width, height, out, call)
+        self._check(LIB.flx_camera_image_gather_device(self._h, C.byref(params) if params is not None else None, self._volume_ref(volume, call), int(bool(hdr)),
+                                                       C.byref(camera) if camera is not None else None, width, height, C.c_void_p(o)), "flx_camera_image_gather_device")
+        return out
+
+    def camera_image_gather(self, camera, width, height, params, volume, hdr=True):
+        """flx_camera_image_gather: the same -> float32 [height, width, 4] in host memory, complete"""
+        width, height = int(width), int(height)
+        out = np.zeros((height, width, 4), np.float32)
+        self._check(LIB.flx_camera_image_gather(self._h, C.byref(params) if params is not None else None, self._volume_ref(volume, "camera_image_gather"), int(bool(hdr)),
+                                                C.byref(camera) if camera is not None else None, width, height, _fp(out)), "flx_camera_image_gather")
+        return out
+
+    def camera_image_temporal_gather_device(self, camera, width, height, trace_params, temporal, volume, out=None):
+        """flx_camera_image_temporal_gather_device: camera_image_temporal_device lit by the volume.  ENQUEUED, NOT YET COMPLETE."""
+        call = "camera_image_temporal_gather_device"
+        width, height = int(width), int(height)
+        out, o = self._image_out(width, height, out, call)
+        self._check(LIB.flx_camera_image_temporal_gather_device(self._h, C.byref(trace_params) if trace_params is not None else None, self._volume_ref(volume, call),
+                                                                C.byref(temporal) if temporal is not None else None, C.byref(camera) if camera is not None else None, width,
+                                                                height, C.c_void_p(o)), "flx_camera_image_temporal_gather_device")
+        return out
+
+    def camera_image_temporal_gather(self, camera, width, height, trace_params, temporal, volume):
+        """flx_camera_image_temporal_gather: the same -> float32 [height, width, 4] in host memory, complete"""
+        width, height = int(width), int(height)
+        out = np.zeros((height, width, 4), np.float32)
+        self._check(LIB.flx_camera_image_temporal_gather(self._h, C.byref(trace_params) if trace_params is not None else None,
+                                                         self._volume_ref(volume, "camera_image_temporal_gather"), C.byref(temporal) if temporal is not None else None,
+                                                         C.byref(camera) if camera is not None else None, width, height, _fp(out)), "flx_camera_image_temporal_gather")
+        return out
+
+    def last_planes_gather(self):
+        """flx_debug_last_planes_gather -> dict (zeros when no planes or image call ran with a volume): n, slabs, slab (rays of a full one), groups (of 256 lanes, last
+        planes launch), flags (bit 0 a map, bit 1 offsets), mode (0 planes, 1 temporal canvas, 2 temporal filter), samples, lockstep"""
+        out = (C.c_uint32 * 8)()
+        self._check(LIB.flx_debug_last_planes_gather(self._h, out), "flx_debug_last_planes_gather")
+        return dict(zip(("n", "slabs", "slab", "groups", "flags", "mode", "samples", "lockstep"), list(out)))
 
     # -- light probes: SH rows of probe positions ---------------------------------------------------
     def _probe_device_args(self, positions, out, out_rows_of, row_width, stream, call):

@@ -486,9 +486,19 @@ class PathTracerHIP {
    * config.temporal: options { temporal: true, history = 0, temporalSamples = config.temporalSamples, filter = true, randomSeed }.  The same width * height rays in
    * the same order are traced again call after call; a ray whose first hit moved starts over.  The renderer keeps a frame counter per history and passes
    * counter % N as the seed (N: temporalSamples, 4 where it is <= 0, at most 16) unless randomSeed is given; the counter restarts with resetRayHistory(history) and
-   * with a change of size or N, as the history does.  Without the filter the temporal pass' colour is returned. */
+   * with a change of size or N, as the history does.  Without the filter the temporal pass' colour is returned.
+   * WITH A VOLUME: options.volume, bakeVolume's handle, and options.gain — by default Math.fround(1 / Math.PI) — are traceRays' (flx_rays_image_gather and its
+   * kin, "ray images with a volume"): every sample of every ray ends in the volume's irradiance at its last surface point times the gain where it ends in
+   * scene.ambientLight without, the lookup inline in the planes kernel; one or two bounces, the volume, the denoiser and the temporal pass are what an application
+   * puts on screen.  It works in all four forms — rays or a camera, with and without temporal; the histories are the same eight, and a history does not know
+   * whether a volume lit it: resetRayHistory is the caller's business.  A volume that is no handle and a gain that is no number are TypeErrors.  Without
+   * options.volume the call is what it was. */
   traceImage (rays, width, height, options) {
     if (this._devices) throw new Error('traceImage: one GPU only (a group of GPUs traces no rays)');
+    const volume = options ? options.volume : undefined;
+    if (volume !== undefined && (!volume || !volume._handle)) throw new TypeError('traceImage: volume is what bakeVolume returned');
+    const gain = options && options.gain !== undefined ? options.gain : Math.fround(1 / Math.PI);
+    if (volume !== undefined && typeof gain !== 'number') throw new TypeError('traceImage: gain is a number');
     const camera = isCameraDescription(rays) ? this.cameraOf(rays, width, height, 'traceImage') : null;      // the rays are made on the device: none cross the bus
     if (!camera) {
       if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('traceImage: rays is a Float32Array of 8 floats per ray, or a camera description');
@@ -510,11 +520,17 @@ class PathTracerHIP {
       if (options.randomSeed === undefined) params.randomSeed = h.counter % depth;
       const filter = options.filter === undefined ? true : !!options.filter;
       const over = { history, temporalSamples, filter, hdr };
-      const image = camera ? native().cameraImageTemporal(this._context(), camera, width, height, params, over) : native().rayImageTemporal(this._context(), rays, width, height, params, over);
+      const image = volume
+        ? (camera ? native().cameraImageTemporalGather(this._context(), camera, width, height, params, over, volume._handle, gain)
+          : native().rayImageTemporalGather(this._context(), rays, width, height, params, over, volume._handle, gain))
+        : camera ? native().cameraImageTemporal(this._context(), camera, width, height, params, over) : native().rayImageTemporal(this._context(), rays, width, height, params, over);
       h.counter++;
       return { width, height, radiance: new Float32Array(image) };
     }
-    const image = camera ? native().cameraImage(this._context(), camera, width, height, this.traceParams(options), hdr) : native().rayImage(this._context(), rays, width, height, this.traceParams(options), hdr);
+    const image = volume
+      ? (camera ? native().cameraImageGather(this._context(), camera, width, height, this.traceParams(options), hdr, volume._handle, gain)
+        : native().rayImageGather(this._context(), rays, width, height, this.traceParams(options), hdr, volume._handle, gain))
+      : camera ? native().cameraImage(this._context(), camera, width, height, this.traceParams(options), hdr) : native().rayImage(this._context(), rays, width, height, this.traceParams(options), hdr);
     return { width, height, radiance: new Float32Array(image) };
   }
 

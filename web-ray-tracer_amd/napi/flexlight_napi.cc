@@ -1028,6 +1028,124 @@ static napi_value CameraImageTemporal(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+/* ---- ray images with a volume: the four image calls above and the planes with bakeVolume's handle and a gain behind them (include/flexlight_hip_debug.h "ray images
+ * with a volume").  The library's host calls take host rays and a volume whose arrays are on the device, which is what a handle holds. */
+static bool read_gather_volume(napi_env env, napi_value volume, napi_value gain, CtxBox *box, const char *call, flx_gather_volume *v) {
+  VolumeBox *vb = get_volume(env, volume, box);
+  if (!vb) return false;
+  double g = 0;
+  if (napi_get_value_double(env, gain, &g) != napi_ok) { napi_throw_type_error(env, nullptr, (std::string(call) + ": gain is not a number").c_str()); return false; }
+  memset(v, 0, sizeof *v);
+  v->grid = &vb->grid; v->sh = vb->d_sh;
+  v->map = vb->d_maps ? &vb->map : nullptr; v->maps = vb->d_maps;
+  v->offsets = vb->d_offsets;
+  v->gain = (float)g;
+  return true;
+}
+
+/* rayPlanesGather(handle, rays Float32Array(8 n), params (traceRays'), volume, gain) -> ArrayBuffer(20 n): flx_rays_planes_gather's five RGBA8 planes, plane p from
+ * texel p n */
+static napi_value RayPlanesGather(napi_env env, napi_callback_info info) {
+  napi_value argv[5];
+  if (!get_args(env, info, 5, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  if (!box) return nullptr;
+  void *rays; size_t len;
+  if (!typed(env, argv[1], napi_float32_array, &rays, &len)) return nullptr;
+  if (len % 8 != 0 || len / 8 > 0xffffffffu) { napi_throw_range_error(env, nullptr, "rayPlanesGather: a ray needs 8 floats (origin, noise x, direction, noise y)"); return nullptr; }
+  flx_trace_params p; flx_gather_volume v;
+  if (!read_trace_params(env, argv[2], "rayPlanesGather", &p) || !read_gather_volume(env, argv[3], argv[4], box, "rayPlanesGather", &v)) return nullptr;
+  const size_t n = len / 8;
+  void *planes = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, n * 20, &planes, &buf));
+  flx_status rc = flx_rays_planes_gather(box->ctx, &p, &v, (const float *)rays, (uint32_t)n, planes, nullptr);
+  if (rc != FLX_OK) return fail(env, box->ctx, "flx_rays_planes_gather", rc);
+  return buf;
+}
+
+/* rayImageGather(handle, rays, width, height, params, hdr, volume, gain) -> ArrayBuffer(16 width height): flx_rays_image_gather — rayImage lit by the volume */
+static napi_value RayImageGather(napi_env env, napi_callback_info info) {
+  napi_value argv[8];
+  if (!get_args(env, info, 8, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  if (!box) return nullptr;
+  void *rays; size_t len; uint32_t width, height;
+  if (!typed(env, argv[1], napi_float32_array, &rays, &len) || !image_size(env, argv[2], argv[3], "rayImageGather", &width, &height)) return nullptr;
+  if (len % 8 != 0 || (uint64_t)(len / 8) != (uint64_t)width * height) { napi_throw_range_error(env, nullptr, "rayImageGather: width * height rays of 8 floats (origin, noise x, direction, noise y)"); return nullptr; }
+  flx_trace_params p; flx_gather_volume v;
+  if (!read_trace_params(env, argv[4], "rayImageGather", &p)) return nullptr;
+  bool hdr = true;
+  if (napi_get_value_bool(env, argv[5], &hdr) != napi_ok) { napi_throw_type_error(env, nullptr, "rayImageGather: hdr is a boolean"); return nullptr; }
+  if (!read_gather_volume(env, argv[6], argv[7], box, "rayImageGather", &v)) return nullptr;
+  void *image = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, (len / 8) * 16, &image, &buf));
+  flx_status rc = flx_rays_image_gather(box->ctx, &p, &v, hdr ? 1 : 0, (const float *)rays, width, height, (float *)image);
+  if (rc != FLX_OK) return fail(env, box->ctx, "flx_rays_image_gather", rc);
+  return buf;
+}
+
+/* rayImageTemporalGather(handle, rays, width, height, params, { history, temporalSamples, filter, hdr }, volume, gain) -> ArrayBuffer(16 width height):
+ * flx_rays_image_temporal_gather, over the same histories as rayImageTemporal */
+static napi_value RayImageTemporalGather(napi_env env, napi_callback_info info) {
+  napi_value argv[8];
+  if (!get_args(env, info, 8, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  if (!box) return nullptr;
+  void *rays; size_t len; uint32_t width, height;
+  if (!typed(env, argv[1], napi_float32_array, &rays, &len) || !image_size(env, argv[2], argv[3], "rayImageTemporalGather", &width, &height)) return nullptr;
+  if (len % 8 != 0 || (uint64_t)(len / 8) != (uint64_t)width * height) { napi_throw_range_error(env, nullptr, "rayImageTemporalGather: width * height rays of 8 floats (origin, noise x, direction, noise y)"); return nullptr; }
+  flx_trace_params p; flx_ray_temporal t; flx_gather_volume v;
+  if (!read_trace_params(env, argv[4], "rayImageTemporalGather", &p) || !read_ray_temporal(env, argv[5], "rayImageTemporalGather", &t) ||
+      !read_gather_volume(env, argv[6], argv[7], box, "rayImageTemporalGather", &v)) return nullptr;
+  void *image = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, (len / 8) * 16, &image, &buf));
+  flx_status rc = flx_rays_image_temporal_gather(box->ctx, &p, &v, &t, (const float *)rays, width, height, (float *)image);
+  if (rc != FLX_OK) return fail(env, box->ctx, "flx_rays_image_temporal_gather", rc);
+  return buf;
+}
+
+/* cameraImageGather(handle, camera, width, height, params, hdr, volume, gain) -> ArrayBuffer(16 width height): flx_camera_image_gather */
+static napi_value CameraImageGather(napi_env env, napi_callback_info info) {
+  napi_value argv[8];
+  if (!get_args(env, info, 8, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  if (!box) return nullptr;
+  flx_camera c; uint32_t width, height; flx_trace_params p; flx_gather_volume v;
+  if (!read_camera(env, argv[1], "cameraImageGather", &c) || !image_size(env, argv[2], argv[3], "cameraImageGather", &width, &height) ||
+      !read_trace_params(env, argv[4], "cameraImageGather", &p)) return nullptr;
+  bool hdr = true;
+  if (napi_get_value_bool(env, argv[5], &hdr) != napi_ok) { napi_throw_type_error(env, nullptr, "cameraImageGather: hdr is a boolean"); return nullptr; }
+  if (!read_gather_volume(env, argv[6], argv[7], box, "cameraImageGather", &v)) return nullptr;
+  void *image = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, image_bytes(width, height), &image, &buf));
+  flx_status rc = flx_camera_image_gather(box->ctx, &p, &v, hdr ? 1 : 0, &c, width, height, (float *)image);
+  if (rc != FLX_OK) return fail(env, box->ctx, "flx_camera_image_gather", rc);
+  return buf;
+}
+
+/* cameraImageTemporalGather(handle, camera, width, height, params, { history, temporalSamples, filter, hdr }, volume, gain) -> ArrayBuffer(16 width height):
+ * flx_camera_image_temporal_gather */
+static napi_value CameraImageTemporalGather(napi_env env, napi_callback_info info) {
+  napi_value argv[8];
+  if (!get_args(env, info, 8, argv)) return nullptr;
+  CtxBox *box = get_box(env, argv[0]);
+  if (!box) return nullptr;
+  flx_camera c; uint32_t width, height; flx_trace_params p; flx_ray_temporal t; flx_gather_volume v;
+  if (!read_camera(env, argv[1], "cameraImageTemporalGather", &c) || !image_size(env, argv[2], argv[3], "cameraImageTemporalGather", &width, &height) ||
+      !read_trace_params(env, argv[4], "cameraImageTemporalGather", &p) || !read_ray_temporal(env, argv[5], "cameraImageTemporalGather", &t) ||
+      !read_gather_volume(env, argv[6], argv[7], box, "cameraImageTemporalGather", &v)) return nullptr;
+  void *image = nullptr;
+  napi_value buf;
+  NAPI_OK(env, napi_create_arraybuffer(env, image_bytes(width, height), &image, &buf));
+  flx_status rc = flx_camera_image_temporal_gather(box->ctx, &p, &v, &t, &c, width, height, (float *)image);
+  if (rc != FLX_OK) return fail(env, box->ctx, "flx_camera_image_temporal_gather", rc);
+  return buf;
+}
+
 /* rayHistoryReset(handle, history): flx_rays_history_reset, -1 for all of the context's ray-image histories */
 static napi_value RayHistoryReset(napi_env env, napi_callback_info info) {
   napi_value argv[2];
@@ -1896,7 +2014,7 @@ static napi_value Version(napi_env env, napi_callback_info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   const struct { const char *name; napi_callback fn; } fns[] = {
-    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "traceRaysGather", TraceRaysGather }, { "traceProbes", TraceProbes }, { "probeIrradiance", ProbeIrradiance }, { "bakeVolume", BakeVolume }, { "volumeRows", VolumeRows }, { "volumeMaps", VolumeMaps }, { "updateVolume", UpdateVolume }, { "relocateVolume", RelocateVolume }, { "volumeOffsets", VolumeOffsets }, { "frameIrradiance", FrameIrradiance }, { "raysIrradiance", RaysIrradiance }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
+    { "createContext", CreateContext }, { "destroyContext", DestroyContext }, { "uploadScene", UploadScene }, { "updateSceneRows", UpdateSceneRows }, { "castRays", CastRays }, { "traceRays", TraceRays }, { "traceRaysOrdered", TraceRaysOrdered }, { "traceRaysGather", TraceRaysGather }, { "traceProbes", TraceProbes }, { "probeIrradiance", ProbeIrradiance }, { "bakeVolume", BakeVolume }, { "volumeRows", VolumeRows }, { "volumeMaps", VolumeMaps }, { "updateVolume", UpdateVolume }, { "relocateVolume", RelocateVolume }, { "volumeOffsets", VolumeOffsets }, { "frameIrradiance", FrameIrradiance }, { "raysIrradiance", RaysIrradiance }, { "rayImage", RayImage }, { "rayImageTemporal", RayImageTemporal }, { "rayHistoryReset", RayHistoryReset }, { "cameraRays", CameraRays }, { "cameraImage", CameraImage }, { "cameraImageTemporal", CameraImageTemporal }, { "rayPlanesGather", RayPlanesGather }, { "rayImageGather", RayImageGather }, { "rayImageTemporalGather", RayImageTemporalGather }, { "cameraImageGather", CameraImageGather }, { "cameraImageTemporalGather", CameraImageTemporalGather },{ "surfaceRays", SurfaceRays }, { "frameSurface", FrameSurface }, { "groupUpdateSceneRows", GroupUpdateSceneRows },
     { "uploadTransforms", UploadTransforms }, { "uploadLights", UploadLights }, { "uploadAtlas", UploadAtlas }, { "uploadTextures", UploadTextures }, { "updateTexture", UpdateTexture },
     { "tileRowCount", TileRowCount }, { "render", Render }, { "rasterRender", RasterRender }, { "renderBatch", RenderBatch }, { "temporalReset", TemporalReset }, { "deviceInfo", DeviceInfo }, { "version", Version },
     { "meshImport", MeshImport }, { "meshCounts", MeshCounts }, { "meshSetTransform", MeshSetTransform }, { "meshMove", MeshMove },
