@@ -72,14 +72,16 @@ static v3 raster_cover(v3 a, v3 b, v3 c, v3 o, v3 d, float l, float viewDepthPer
 /* The draw for one pixel as the skip-list walk meets the triangles (the order of idBuffer, scene.js:230,267): every triangle
  * the ray meets closer than the nearest depth accepted so far is a fragment; boxes are pruned with that depth (the loop of
  * pathtracer_fragment.glsl:172-227, as for the path tracer's primary rays).  Returns the number of fragments (all of them are
- * counted; at most `cap` are stored). */
-static int raster_walk(const flx_scene_view *sc, v3 origin, v3 dir, float viewDepthPerS, Fragment *frags, int cap, uint64_t *visits) {
+ * counted; at most `cap` are stored).  `trail`, if given, takes the indices of the entries fetched, in order, the terminator included (at most
+ * `tcap` of them; *visits counts them all). */
+static int raster_walk(const flx_scene_view *sc, v3 origin, v3 dir, float viewDepthPerS, Fragment *frags, int cap, uint64_t *visits, int *trail, int tcap) {
   v3 tO = origin, tD = dir;
   int cachedTI = 0, n = 0;
   float minLen = FLX_POW32;
   int size = (int)sc->n_entries_padded;
   for (int i = 0; i < size; i++) {
     const float *e = sc->geometry + (size_t)i * 12;
+    if (trail && *visits < (uint64_t)tcap) trail[*visits] = i;
     (*visits)++;
     int tI = (int)e[9] << 1;
     if (tI != cachedTI) {
@@ -241,13 +243,25 @@ int flx_raster_ref_fragments(const flx_scene_view *sc, const flx_frame_params *f
   pixel_ray(fp, inv, px, py_gl, &d, &vd);
   Fragment *fr = (Fragment *)malloc(sizeof(Fragment) * (size_t)(cap > 0 ? cap : 1));
   uint64_t visits = 0;
-  int n = raster_walk(sc, V3(fp->camera[0], fp->camera[1], fp->camera[2]), d, vd, fr, cap, &visits);
+  int n = raster_walk(sc, V3(fp->camera[0], fp->camera[1], fp->camera[2]), d, vd, fr, cap, &visits, NULL, 0);
   for (int k = 0; k < n && k < cap; k++) {
     suv[3 * k] = fr[k].suv.x; suv[3 * k + 1] = fr[k].suv.y; suv[3 * k + 2] = fr[k].suv.z;
     tI[k] = fr[k].tI; tri[k] = fr[k].tri;
   }
   free(fr);
   return n;
+}
+
+/* The entries that the walk of pixel (px, py_gl) fetches, in order, the terminator included (tests: the trips of k_raster's wave are a function of
+ * these lists, tests/raster_stacks_util.py wave_schedule); returns their number (at most cap stored). */
+int flx_raster_ref_visits(const flx_scene_view *sc, const flx_frame_params *fp, uint32_t px, uint32_t py_gl, int *out, int cap) {
+  float inv[9];
+  flx_invert3x3(fp->view_matrix, inv);
+  v3 d; float vd;
+  pixel_ray(fp, inv, px, py_gl, &d, &vd);
+  uint64_t visits = 0;
+  raster_walk(sc, V3(fp->camera[0], fp->camera[1], fp->camera[2]), d, vd, NULL, 0, &visits, out, cap);
+  return (int)visits;
 }
 
 /* One frame of the rasterizer: out_rgba flx_tile_row_count * width * 4 floats, rows packed as flx_render packs them. */
@@ -283,12 +297,12 @@ int flx_raster_ref_render(const flx_scene_view *sc, const flx_frame_params *fp, 
         v3 d; float vd;
         pixel_ray(fp, inv, px, py_gl, &d, &vd);
         uint64_t visits = 0;
-        int n = raster_walk(sc, camera, d, vd, frags, cap, &visits);
+        int n = raster_walk(sc, camera, d, vd, frags, cap, &visits, NULL, 0);
         if (n > cap) {                        /* more fragments than room: walk again with enough */
           cap = n;
           frags = (Fragment *)realloc(frags, sizeof(Fragment) * (size_t)cap);
           uint64_t again = 0;
-          raster_walk(sc, camera, d, vd, frags, cap, &again);
+          raster_walk(sc, camera, d, vd, frags, cap, &again, NULL, 0);
         }
         c.primary_visits += visits;
         float dst[4] = { 0.0f, 0.0f, 0.0f, 0.0f };                                                 /* clearColor(0,0,0,0) */

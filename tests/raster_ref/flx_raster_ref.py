@@ -42,6 +42,8 @@ class RasterRef:
         lib.flx_raster_ref_fragments.argtypes = [C.POINTER(SceneView), C.POINTER(FrameParams), C.c_uint32, C.c_uint32, fp,
                                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
         lib.flx_raster_ref_fragments.restype = C.c_int
+        lib.flx_raster_ref_visits.argtypes = [C.POINTER(SceneView), C.POINTER(FrameParams), C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.c_int]
+        lib.flx_raster_ref_visits.restype = C.c_int
         self.lib = lib
 
     def render(self, scene, params, threads=0):
@@ -78,3 +80,10 @@ class RasterRef:
         tri = (C.c_int * cap)()
         n = self.lib.flx_raster_ref_fragments(C.byref(view), C.byref(params), px, py_gl, _fp(suv), ti, tri, cap)
         return [(suv[3 * k:3 * k + 3].copy(), ti[k], tri[k]) for k in range(min(n, cap))]
+
+    def visits(self, view, params, px, py_gl, cap=4096):
+        """the entry indices that the pixel's walk fetches, in order, the terminator included"""
+        out = (C.c_int * cap)()
+        n = self.lib.flx_raster_ref_visits(C.byref(view), C.byref(params), px, py_gl, out, cap)
+        assert n <= cap, n
+        return list(out[:n])

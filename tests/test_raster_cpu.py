@@ -10,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-from flexlight_hip.scene_io import FrameParams, Scene
+from raster_stacks_util import two_layer_scene
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -91,42 +91,6 @@ def test_front_fragment_agrees_with_the_rasterizers_draw(ref, scenes, name, w, h
             assert got_tri == want_tri, (px, py, got_tri, want_tri)
             compared += 1
     assert compared > 0.97 * w * h and skipped < 0.03 * w * h, (compared, skipped)
-
-
-def two_layer_scene(near_first):
-    """Two large triangles facing the camera at depths 5 (near) and 10 (far), both translucent (tpo.x = 1: alpha 0.5), emissive 0.5, no
-    lights, no ambient; near: albedo (1, 1, 1), far: albedo (1, 0, 0).  Entry order = draw order."""
-    def tri(z, albedo):
-        geo = np.zeros(12, np.float32)
-        geo[0:9] = [-100, -100, z, 300, -100, z, -100, 300, z]
-        geo[10] = 2
-        att = np.zeros(28, np.float32)
-        att[0:9] = [0, 0, -1] * 3
-        att[15:18] = -1
-        att[18:21] = albedo
-        att[21:24] = [1, 0, 0.5]
-        att[24:27] = [1, 0, 1]
-        return geo, att
-    layers = [tri(5, [1, 1, 1]), tri(10, [1, 0, 0])]
-    if not near_first:
-        layers = layers[::-1]
-    geometry = np.zeros((256, 12), np.float32)
-    attributes = np.zeros((256, 28), np.float32)
-    for k, (g, t) in enumerate(layers):
-        geometry[k], attributes[k] = g, t
-    rotation = np.zeros(24, np.float32)
-    for r in range(3):
-        rotation[4 * r + r] = rotation[12 + 4 * r + r] = 1
-    meta = {"atlas": {"albedo": [1, 1], "pbr": [1, 1], "tpo": [1, 1]}}
-    arrays = {"geometry": geometry.reshape(-1), "attributes": attributes.reshape(-1), "ids": np.array([0, 1], np.int32),
-              "rotation": rotation, "shift": np.zeros(8, np.float32), "lights": np.zeros(0, np.float32),
-              "atlasAlbedo": np.zeros(4, np.uint8), "atlasPbr": np.zeros(4, np.uint8), "atlasTpo": np.zeros(4, np.uint8)}
-    sc = Scene(meta, arrays)
-    p = FrameParams()
-    p.width, p.height = 5, 3
-    p.view_matrix[:] = [1, 0, 0, 0, 1, 0, 0, 0, 1]              # camera at the origin looking along +z
-    p.samples, p.hdr, p.texture_width = 1, 0, 1
-    return sc, p
 
 
 @pytest.mark.parametrize("near_first", [True, False], ids=["near_then_far", "far_then_near"])

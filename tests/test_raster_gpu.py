@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import synth_scene
+from raster_stacks_util import assert_same
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "raster_ref"))
 import flx_raster_ref  # noqa: E402
@@ -23,18 +24,6 @@ def ref(oracle, tmp_path_factory):
 
 def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_same(hip, ref, sc, p, what):
-    want, want_cnt = ref.render(sc, p)
-    got, cnt = hip.raster_render(p, counters=True)
-    bad = np.argwhere((_bits(got) != _bits(want)).any(axis=-1))
-    assert bad.size == 0, "%s: %d pixels differ, first %s: got %s want %s" % (what, len(bad), bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
-    assert cnt == want_cnt, "%s: counters %s vs %s" % (what, cnt, want_cnt)
-    plain, none = hip.raster_render(p, counters=False)             # the kernel without counting code: the same image
-    assert none is None
-    assert np.array_equal(_bits(plain), _bits(want)), what
-    return got, cnt
 
 
 @pytest.mark.parametrize("hdr", [0, 1])
